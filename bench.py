@@ -16,7 +16,12 @@ batch of 32 (weak scaling); there is no collective on the data path.  ``--varian
 measures BASELINE configs[3]; ``--mode train`` measures configs[4] (forward + criteria + backward + clip + AdamW,
 gradient all-reduce over RCCL).  Rank 0 prints ONE JSON line.
 
-Extra objects on that line:
+A plain run sets up, warms up, times the K steps and prints the line.  ``--full`` adds every side measurement to an inference run:
+the parity gates against the committed golden waveforms, the roofline region, the metric all-reduce probe, the other precision, the
+batch-1 latency, the Large and training sub-records, live PMC traffic and the CPU baseline.  ``--dump-outputs DIR`` writes what the last
+timed step computed as DIR/<name>.npy (inference: audio, aux_<i>, metric_sums; training: loss, grad_norm, params).
+
+Extra objects on that line (--full):
   roofline      dominant kernel = the GCFN block's kernel (fused for Base: ~40 % of the step, 56 launches per forward).
                 ``achieved`` = ALGORITHMIC fp32 FLOPs of the launches / their hipEvent durations (measured on the launch
                 stream inside the timed region), ``frac`` = achieved / the dense bf16 MFMA peak.  The default
@@ -154,7 +159,40 @@ def parse_args():
                     help="HBM traffic of the dominant kernel from rocprofv3 PMC passes of a short sub-run (auto: in the default 1-GPU run)")
     ap.add_argument("--precision", choices=["fp32", "bf16x3", "bf16"], default=None,
                     help="projection arithmetic (default: the package default / SEPR_PRECISION)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="inference: every side measurement as well (parity gates against the golden waveforms, roofline region, metric all-reduce "
+                         "probe, other precision, batch-1 latency, Large and training sub-records, PMC traffic, CPU baseline); "
+                         "without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB)")
+    args = ap.parse_args()
+    if args.pmc == "on" and not args.full:
+        ap.error("--pmc on is a side measurement: add --full")
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs writes the last timed step: needs --steps >= 1")
+    return args
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def write_outputs(out_dir, arrays):
+    """``arrays``: name -> tensor / ndarray computed by the last timed step.  Each is written as ``out_dir/<name>.npy`` in float32
+    (float64 stays float64).  Above DUMP_BUDGET_BYTES in all, every array keeps the same fraction of its elements at fixed, seeded
+    flat positions (sorted; 1-D), so that two builds given the same arguments write comparable files."""
+    import numpy as np
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        host[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+    total = sum(a.nbytes for a in host.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        if total > DUMP_BUDGET_BYTES:
+            keep = max(1, int(a.size * DUMP_BUDGET_BYTES / total))
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=min(keep, a.size), replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def self_launch(args) -> int:
@@ -192,7 +230,7 @@ def measure_pmc_traffic(budget_s=90.0, kernel_re=None, sub_args=None):
     for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
         d = tempfile.mkdtemp(prefix=f"sepr_pmc_{ctr}_", dir="/tmp")
         cmd = [exe, "--pmc", ctr, "--kernel-trace", "--kernel-include-regex", kernel_re or PMC_KERNEL_RE, "--output-format", "csv", "-d", d, "-o", "t", "--",
-               sys.executable, os.path.abspath(__file__)] + (sub_args or ["--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-alt-precision", "--pmc", "off"])
+               sys.executable, os.path.abspath(__file__)] + (sub_args or ["--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-alt-precision", "--pmc", "off"])
         env = dict(os.environ, TMPDIR="/tmp", SEPR_PIPELINES="1")      # one pipeline: every counted launch has the full-batch size
         for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
             env.pop(k, None)
@@ -232,9 +270,9 @@ PIT_GATE_DB = 1e-3          # |PIT SI-SNR(hip) - PIT SI-SNR(reference)| per utte
 GOLDEN_4S = {"SepReformer_Base_WSJ0": "e2e_base_4s.npz", "SepReformer_Large_DM_WHAMR": "e2e_large_whamr_4s.npz"}
 
 
-def measure_infer(args, variant, steps, warmup, rank, world, dev, lib, full):
-    """One inference measurement (``full``: the headline line with every side measurement; else a bounded sub-record of
-    another BASELINE configuration inside the default run)."""
+def measure_infer(args, variant, steps, warmup, rank, world, dev, lib, headline):
+    """One inference measurement (``headline``: the headline line, with every side measurement under ``--full``; else a bounded
+    sub-record of another BASELINE configuration inside the ``--full`` default run)."""
     import torch
     from sepreformer_amd import dist as sdist
     from sepreformer_amd import lib as L
@@ -281,22 +319,32 @@ def measure_infer(args, variant, steps, warmup, rank, world, dev, lib, full):
         out = step()
     torch.cuda.synchronize(dev)
 
+    # side measurements (--full): the roofline's per-launch events, the all-reduce probe, the parity gates
+    side = args.full
     launches_per_step = 56 * 4                  # GCFN launches per forward (56) x sub-batch pipelines; sizes the event pool
-    if pl == 1:
+    if side and pl == 1:
         L.check(lib.sepr_prof_start(L.SITE_GCFN_UP, launches_per_step * max(steps, 1) + 8), "sepr_prof_start")
     sdist.barrier()
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     for _ in range(steps):
-        step()
+        out = step()
     torch.cuda.synchronize(dev)
     sdist.barrier()
     elapsed = time.perf_counter() - t0
+    if headline and args.dump_outputs and rank == 0:
+        # what the caller of the timed path receives from its last step, taken before anything else runs on the model
+        dump = {"audio": torch.stack(out[0], 0)}                                          # [S, B, T]
+        for i, a in enumerate(out[1]):
+            dump[f"aux_{i}"] = torch.stack(a, 0)                                          # [S, B, T] per auxiliary head
+        if not args.no_metric:
+            dump["metric_sums"] = metric_acc                                              # [sum PIT SI-SNR, sum SI-SNRi, utterances]
+        write_outputs(args.dump_outputs, dump)
     n_l, ms, fl = C.c_longlong(0), C.c_double(0.0), C.c_double(0.0)
     single = None
-    if pl == 1:
+    if side and pl == 1:
         L.check(lib.sepr_prof_stop(C.byref(n_l), C.byref(ms), C.byref(fl)), "sepr_prof_stop")
-    else:
+    elif side:
         model.pipelines = 1
         step()
         torch.cuda.synchronize(dev)
@@ -317,7 +365,7 @@ def measure_infer(args, variant, steps, warmup, rank, world, dev, lib, full):
     elapsed = sdist.max_over_ranks(elapsed, dev)
     # the path's collective on its own, EVERY rank takes part: wall time of one synchronised 3-scalar all-reduce, median of 10
     ar_ms = None
-    if not args.no_metric:
+    if side and not args.no_metric:
         ts, probe = [], torch.zeros(3, dtype=torch.float64, device=dev)
         for _ in range(12):
             torch.cuda.synchronize(dev)
@@ -333,7 +381,7 @@ def measure_infer(args, variant, steps, warmup, rank, world, dev, lib, full):
     # north_star gate |PIT SI-SNR(hip) - PIT SI-SNR(reference)| per utterance (reference values: tests/golden)
     parity_db = pit_delta = None
     g = None
-    if rank == 0 and variant in GOLDEN_4S and os.path.exists(os.path.join(ROOT, "tests", "golden", GOLDEN_4S[variant])):
+    if side and rank == 0 and variant in GOLDEN_4S and os.path.exists(os.path.join(ROOT, "tests", "golden", GOLDEN_4S[variant])):
         import numpy as np
         from oracle.sepreformer_oracle import agreement_db, pit_si_snr_db
         g = np.load(os.path.join(ROOT, "tests", "golden", GOLDEN_4S[variant]))
@@ -451,7 +499,10 @@ def measure_infer(args, variant, steps, warmup, rank, world, dev, lib, full):
     }
     if single is not None:
         rec["single_pipeline"] = single
-    if not args.no_metric and variant == DEFAULT_VARIANT:
+    if not side:                                # none of these was measured
+        for k in ("parity_db_vs_golden", "pit_si_snr_max_abs_delta_db", "parity_ok", "roofline", "metric_allreduce_ms"):
+            del rec[k]
+    if side and not args.no_metric and variant == DEFAULT_VARIANT:
         # configs[2] (batch 256 over 8 GPUs = this per-rank workload x 8) from measured pieces: the data path has no collective, the
         # per-step exchange is the 24-byte metric all-reduce (latency-bound: a few tens of microseconds over xGMI against a >= 24 ms step)
         step_ms = 1e3 * elapsed / max(steps, 1)
@@ -465,7 +516,7 @@ def measure_infer(args, variant, steps, warmup, rank, world, dev, lib, full):
                                  "note": "prediction, not a measurement (no multi-GPU node was available to the builder): utterance shards are independent, "
                                          "weights replicated once, the only collective is this 3-scalar all-reduce; what a real run adds is host-side launch "
                                          "jitter across 8 processes (each rank drives its own ~450-launch forward)"}
-    if not full:
+    if not headline:
         del model
         torch.cuda.empty_cache()
         return rec
@@ -486,7 +537,7 @@ def measure_infer(args, variant, steps, warmup, rank, world, dev, lib, full):
                                                                           torch.from_numpy(g["main"])), 1)}
         rec["alt_precision"]["parity_ok"] = bool(rec["alt_precision"]["parity_db_vs_golden"] >= PARITY_MIN_DB)
         model.precision = precision
-    if world == 1 and not args.no_alt_precision:
+    if side and world == 1 and not args.no_alt_precision:
         # single-utterance latency: B=1 x 4 s through the PUBLIC call, model(x)
         x1 = x[:1].contiguous()
 
@@ -589,6 +640,7 @@ def main():
         raise SystemExit(self_launch(args))
     emit = protect_stdout()
     args._emit = emit
+    args._dump = (lambda arrays: write_outputs(args.dump_outputs, arrays)) if args.dump_outputs else None
     if args.mode == "train":
         from sepreformer_amd import train_bench
         return train_bench.main(args)
@@ -619,17 +671,17 @@ def main():
     lib = L.load()
 
     variant = args.variant
-    rec = measure_infer(args, variant, args.steps, args.warmup, rank, world, dev, lib, full=True)
+    rec = measure_infer(args, variant, args.steps, args.warmup, rank, world, dev, lib, headline=True)
     if rank == 0:
         if dist_err:
             rec["collective_error"] = dist_err
-        default_run = world == 1 and variant == DEFAULT_VARIANT and not args.no_alt_precision and args.batch is None
+        default_run = args.full and world == 1 and variant == DEFAULT_VARIANT and not args.no_alt_precision and args.batch is None
         if default_run:
             # The other single-GPU configurations of BASELINE.json as bounded sub-records of the SAME driver-observed line:
             # configs[3] (Large_DM_WHAMR inference, with its own parity gate) and configs[4] (the training step).
             t_sub = time.perf_counter()
             try:
-                sub = measure_infer(args, "SepReformer_Large_DM_WHAMR", SUB_STEPS_LARGE, 2, rank, world, dev, lib, full=False)
+                sub = measure_infer(args, "SepReformer_Large_DM_WHAMR", SUB_STEPS_LARGE, 2, rank, world, dev, lib, headline=False)
                 rec["large"] = {k: sub[k] for k in ("value", "unit", "ms_per_step", "steps", "warmup", "dtype", "config", "parity_db_vs_golden",
                                                      "pit_si_snr_max_abs_delta_db", "parity_ok", "model_tflops", "model_frac_algorithmic",
                                                      "model_mfma_frac", "roofline")}
@@ -639,7 +691,7 @@ def main():
                 # HBM traffic of Large's dominant kernel (the GCFN up-projection with the conv + GLU epilogue), measured in this run
                 try:
                     pm, why = measure_pmc_traffic(90.0, LARGE_KERNEL_RE, ["--variant", "SepReformer_Large_DM_WHAMR", "--steps", "1", "--warmup", "1",
-                                                                         "--no-cpu-baseline", "--no-alt-precision", "--pmc", "off"])
+                                                                         "--full", "--no-cpu-baseline", "--no-alt-precision", "--pmc", "off"])
                 except Exception as e:          # noqa: BLE001
                     pm, why = None, f"{type(e).__name__}: {e}"[:200]
                 roof = rec["large"]["roofline"]
@@ -731,7 +783,7 @@ def main():
                         roof["traffic_source"] = f"live PMC passes failed: {why}"
                 rec["train_pmc_s"] = round(time.perf_counter() - t_pmc, 1)
             rec["sub_records_s"] = round(time.perf_counter() - t_sub, 1)
-        if world == 1 and (args.pmc == "on" or (args.pmc == "auto" and default_run)) and rec["roofline"].get("algorithmic_bytes_per_launch"):
+        if args.full and world == 1 and (args.pmc == "on" or (args.pmc == "auto" and default_run)) and rec["roofline"].get("algorithmic_bytes_per_launch"):
             # traffic re-measured in THIS run (two short PMC sub-runs at the same batch: every launch they count has the timed launches' size)
             t_pmc = time.perf_counter()
             torch.cuda.synchronize(dev)
@@ -750,7 +802,7 @@ def main():
             else:
                 rec["roofline"]["traffic_source"] = (rec["roofline"].get("traffic_source") or "") + f" (live PMC passes failed: {why})"
             rec["pmc_s"] = round(time.perf_counter() - t_pmc, 1)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             threads = int(os.environ.get("SEPR_CPU_THREADS", str(physical_cores())))
             try:
                 rec["cpu_baseline"] = cpu_baseline(VARIANTS[variant], threads)

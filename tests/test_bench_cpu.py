@@ -75,3 +75,39 @@ def test_summary_is_last_key_and_small():
     assert set(s["train"]) == {"bf16x3", "bf16", "bf16_b32"} and all(t["steps"] >= 8 for t in s["train"].values()) and s["large"]["steps"] >= 10
     assert all(t["tn_hbm"][1] is not None and t["mid"][0] is not None for t in s["train"].values())     # live PMC traffic + middle-kernel time for all three
     assert len(json.dumps(bench.make_summary(rec))) <= 1500
+
+
+def test_full_is_off_by_default_and_owns_the_side_measurements(monkeypatch):
+    """A plain run is lean: --full is off unless given; the live PMC passes are a side measurement and need it; a dump needs a timed step."""
+    b = _bench()
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"])
+    a = b.parse_args()
+    assert a.full is False and a.dump_outputs is None and a.steps == 5 and a.warmup == 2
+    for bad in (["--pmc", "on"], ["--steps", "0", "--dump-outputs", "d"]):
+        monkeypatch.setattr("sys.argv", ["bench.py", *bad])
+        with pytest.raises(SystemExit):
+            b.parse_args()
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--pmc", "on", "--dump-outputs", "d"])
+    a = b.parse_args()
+    assert a.full and a.pmc == "on" and a.dump_outputs == "d"
+
+
+def test_write_outputs_types_and_budget(tmp_path, monkeypatch):
+    """--dump-outputs files: float32 (float64 kept), whole arrays under the budget; over it, the same seeded sample on every call."""
+    import numpy as np
+    import torch
+    b = _bench()
+    arrays = {"audio": torch.arange(24, dtype=torch.float32).reshape(2, 3, 4), "sums": np.array([1.5, -2.0, 3.0]),
+              "half": torch.ones(5, dtype=torch.float16)}
+    b.write_outputs(str(tmp_path / "a"), arrays)
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in arrays}
+    assert got["audio"].dtype == np.float32 and np.array_equal(got["audio"], arrays["audio"].numpy())
+    assert got["sums"].dtype == np.float64 and np.array_equal(got["sums"], arrays["sums"])
+    assert got["half"].dtype == np.float32 and got["half"].shape == (5,)
+    monkeypatch.setattr(b, "DUMP_BUDGET_BYTES", 64)
+    big = {"x": np.arange(100, dtype=np.float32), "y": np.arange(100, dtype=np.float64)}
+    b.write_outputs(str(tmp_path / "b"), big)
+    b.write_outputs(str(tmp_path / "c"), big)
+    x, y = np.load(tmp_path / "b" / "x.npy"), np.load(tmp_path / "b" / "y.npy")
+    assert x.nbytes + y.nbytes <= 64 and x.size >= 1 and np.all(np.diff(x) > 0)
+    assert np.array_equal(x, np.load(tmp_path / "c" / "x.npy")) and np.array_equal(y, np.load(tmp_path / "c" / "y.npy"))

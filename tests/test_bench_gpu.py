@@ -22,7 +22,7 @@ def _bench(*flags, timeout=900):
 
 
 def test_bench_two_ranks_share_gpu_inference():
-    rec = _bench("--gpus", "2", "--share-gpu", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-alt-precision")
+    rec = _bench("--gpus", "2", "--share-gpu", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-alt-precision")
     assert rec["n_gpus"] == 2 and rec["rccl_ranks"] == 2 and rec["collective_backend"] == "gloo"
     assert rec["reduced_metric"]["utterances"] == 64               # 32 per rank, summed by the all-reduce
     assert rec["scaling"] == "weak" and rec["value"] > 0
@@ -46,13 +46,29 @@ def test_bench_single_gpu_runs_its_collectives_through_rccl():
     assert rec["collective_backend"] == "nccl" and rec["allreduce_bytes_per_step"] > 50_000_000
 
 
+def test_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """Without --full the line carries the headline only (no parity gate, roofline or sub-record ran); --dump-outputs writes the last
+    timed step's separated waveforms, auxiliary heads and reduced metric."""
+    import numpy as np
+    rec = _bench("--steps", "2", "--warmup", "1", "--batch", "4", "--dump-outputs", str(tmp_path))
+    assert rec["steps"] == 2 and rec["ms_per_step"] > 0 and rec["higher_is_better"] is True
+    assert abs(rec["value"] - 4 * 1e3 / rec["ms_per_step"]) <= 0.01 * rec["value"]
+    assert not {"parity_ok", "roofline", "large", "train", "cpu_baseline", "latency_b1", "alt_precision"} & set(rec)
+    audio = np.load(tmp_path / "audio.npy")
+    assert audio.dtype == np.float32 and audio.shape == (2, 4, 32000) and np.isfinite(audio).all() and np.abs(audio).max() > 0
+    aux = sorted(tmp_path.glob("aux_*.npy"))
+    assert len(aux) == 4 and all(np.load(f).shape == (2, 4, 32000) for f in aux)
+    m = np.load(tmp_path / "metric_sums.npy")
+    assert m.dtype == np.float64 and m[2] == 4.0 and m[2] == rec["reduced_metric"]["utterances"]
+
+
 def test_bench_measures_hbm_traffic_live():
     """--pmc on: the roofline's ``traffic`` comes from rocprofv3 FETCH_SIZE / WRITE_SIZE passes of THIS invocation (separate passes,
     kernel-trace only), not from a committed file; the fused GCFN kernel moves more than its algorithmic bytes and less than 3 x."""
     import shutil
     if not (shutil.which("rocprofv3") or os.path.exists("/opt/rocm/bin/rocprofv3")):
         pytest.skip("rocprofv3 not installed")
-    rec = _bench("--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-alt-precision", "--pmc", "on", timeout=600)
+    rec = _bench("--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-alt-precision", "--pmc", "on", timeout=600)
     roof = rec["roofline"]
     assert roof["traffic_source"].startswith("measured in this run"), roof["traffic_source"]
     assert 1.0 < roof["traffic_over_algorithmic"] < 3.0, roof

@@ -22,16 +22,16 @@ timeout 600 python -m pytest tests/test_criterion.py tests/test_infer.py -m gpu 
 echo "pytest [criterion + infer] rc=$?" | tee -a $OUT/summary.txt
 tail -3 "$OUT/pytest_criterion_infer.log" | grep -E "passed|failed|error" | tee -a $OUT/summary.txt
 echo "== bench" | tee -a $OUT/summary.txt
-timeout 600 python bench.py --steps $STEPS --warmup 2 > $OUT/bench.log 2> $OUT/bench.err; echo "bench rc=$?" | tee -a $OUT/summary.txt
+timeout 600 python bench.py --full --steps $STEPS --warmup 2 > $OUT/bench.log 2> $OUT/bench.err; echo "bench rc=$?" | tee -a $OUT/summary.txt
 cat $OUT/bench.log | tee -a $OUT/summary.txt
 tail -5 $OUT/bench.err
 if [ -n "${AB_ENV:-}" ]; then   # optional A/B leg: AB_ENV="SEPR_LEGACY_POINTWISE=1" etc.
   echo "== bench with $AB_ENV" | tee -a $OUT/summary.txt
-  env $AB_ENV timeout 300 python bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-alt-precision 2>> $OUT/bench.err | python -c "import sys,json; r=json.loads(sys.stdin.read()); print(r['value'], 'utt/s', r['ms_per_step'], 'ms/step parity', r['parity_db_vs_golden'])" | tee -a $OUT/summary.txt
+  env $AB_ENV timeout 300 python bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --no-alt-precision 2>> $OUT/bench.err | python -c "import sys,json; r=json.loads(sys.stdin.read()); print(r['value'], 'utt/s', r['ms_per_step'], 'ms/step parity', r['parity_db_vs_golden'])" | tee -a $OUT/summary.txt
 fi
 if [ -n "${LARGE:-1}" ]; then   # BASELINE configs[3]: Large_DM_WHAMR (F = 256), B = 32 x 4 s
   echo "== bench Large_DM_WHAMR" | tee -a $OUT/summary.txt
-  timeout 600 python bench.py --variant SepReformer_Large_DM_WHAMR --steps 3 --warmup 1 --no-cpu-baseline --no-alt-precision > $OUT/bench_large.log 2>> $OUT/bench.err; echo "bench large rc=$?" | tee -a $OUT/summary.txt
+  timeout 600 python bench.py --full --variant SepReformer_Large_DM_WHAMR --steps 3 --warmup 1 --no-cpu-baseline --no-alt-precision > $OUT/bench_large.log 2>> $OUT/bench.err; echo "bench large rc=$?" | tee -a $OUT/summary.txt
   cat $OUT/bench_large.log | tee -a $OUT/summary.txt
   (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OLDPWD/$OUT/prof_large -o bench -- python $OLDPWD/bench.py --variant SepReformer_Large_DM_WHAMR --steps 2 --warmup 1 --no-cpu-baseline --no-alt-precision --no-metric > $OLDPWD/$OUT/prof_large.log 2>&1)
   f=$(find $OUT/prof_large -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && head -16 "$f" | cut -c1-200 | tee -a $OUT/summary.txt

@@ -7,7 +7,7 @@ timeout 600 python -m pytest tests/test_gpu_parity.py -m gpu -q -x -k "test_bloc
 echo "pytest rc=$?"; tail -4 $OUT/quick_pytest.log
 for v in "$@"; do
   if [[ "$v" == *=* ]]; then e="$v"; else e="SEPR_LIB_VARIANT=$v"; fi
-  env $e timeout 300 python bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-alt-precision 2>/dev/null | python -c "
+  env $e timeout 300 python bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-alt-precision 2>/dev/null | python -c "
 import sys, json
 r = json.loads(sys.stdin.read())
 print('bench[$v]: %.1f utt/s  %.2f ms/step  parity %.1f dB  gcfn avg %.3f ms' % (r['value'], r['ms_per_step'], r['parity_db_vs_golden'], r['roofline']['avg_launch_ms']))"

@@ -12,9 +12,9 @@ if [ -n "${KSEL_PARITY:-}" ]; then
 fi
 for b in ${BENCH:-}; do
   case $b in
-    default) timeout 600 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "default bench rc=$?";;
-    infer)   timeout 300 python bench.py --no-cpu-baseline --no-alt-precision --pmc off > $OUT/bench_infer.json 2> $OUT/bench_infer.err; echo "infer bench rc=$?";;
-    large)   timeout 300 python bench.py --variant SepReformer_Large_DM_WHAMR --steps 3 --warmup 1 --no-cpu-baseline --no-alt-precision --pmc off > $OUT/bench_large.json 2> $OUT/bench_large.err; echo "large bench rc=$?";;
+    default) timeout 600 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "default bench rc=$?";;
+    infer)   timeout 300 python bench.py --full --no-cpu-baseline --no-alt-precision --pmc off > $OUT/bench_infer.json 2> $OUT/bench_infer.err; echo "infer bench rc=$?";;
+    large)   timeout 300 python bench.py --full --variant SepReformer_Large_DM_WHAMR --steps 3 --warmup 1 --no-cpu-baseline --no-alt-precision --pmc off > $OUT/bench_large.json 2> $OUT/bench_large.err; echo "large bench rc=$?";;
     train16) timeout 300 python bench.py --mode train --batch 16 --steps 3 --warmup 1 --precision bf16 > $OUT/bench_train_bf16_b16.json 2> $OUT/bench_train_bf16_b16.err; echo "train bf16 b16 rc=$?";;
     train16x3) timeout 300 python bench.py --mode train --batch 16 --steps 3 --warmup 1 --precision bf16x3 > $OUT/bench_train_bf16x3_b16.json 2> $OUT/bench_train_bf16x3_b16.err; echo "train bf16x3 b16 rc=$?";;
   esac

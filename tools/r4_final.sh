@@ -4,7 +4,7 @@ set -u
 export TMPDIR=/tmp
 OUT=$PWD/gpurun_out; mkdir -p $OUT
 t0=$(date +%s)
-timeout 900 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "default bench rc=$? wall=$(( $(date +%s) - t0 )) s"
+timeout 900 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "default bench rc=$? wall=$(( $(date +%s) - t0 )) s"
 python - <<PY
 import json
 r = json.loads(open("$OUT/bench_default.json").read().strip().split("\n")[-1])

@@ -8,5 +8,5 @@ DET_REPS=6 timeout 300 python tools/det_infer.py 2>&1 | grep -E "^rep|Error|erro
 timeout 900 python -m pytest tests/test_gpu_parity.py -m gpu -q -p no:cacheprovider -x -k "blocks or e2e_golden or pit_si_snr or full_size_batch or pipelines or ragged" 2>&1 | tail -4 | cut -c1-300
 timeout 900 python -m pytest tests/test_train_gpu.py -m gpu -q -p no:cacheprovider -x -k "ega_train or general_loader or wgrad or front_and_heads or downconv_split" 2>&1 | tail -4 | cut -c1-300
 bash tools/prof_kernel.sh "relattn_x3|gcfn_fused3_kernel<128, 2|cla_|dwconv_same" "" "SEPR_NOP=1" 2>&1 | tail -12
-timeout 300 python bench.py --no-cpu-baseline --no-alt-precision --pmc off > $OUT/bench_infer.json 2> $OUT/bench_infer.err; python -c "
+timeout 300 python bench.py --full --no-cpu-baseline --no-alt-precision --pmc off > $OUT/bench_infer.json 2> $OUT/bench_infer.err; python -c "
 import json; r=json.loads(open('$OUT/bench_infer.json').read().strip().split(chr(10))[-1]); print('infer', r['value'], r['ms_per_step'], r['parity_ok'], r['pit_si_snr_max_abs_delta_db'], r['roofline']['avg_launch_ms'], (r.get('single_pipeline') or {}).get('value'))"

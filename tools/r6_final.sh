@@ -3,7 +3,7 @@
 export TMPDIR=/tmp
 OUT=$PWD/gpurun_out; mkdir -p $OUT
 TAG=${TAG:-v7}
-( time python bench.py > $OUT/r6_bench_$TAG.json 2> $OUT/r6_bench_$TAG.err ) 2>&1 | grep real
+( time python bench.py --full > $OUT/r6_bench_$TAG.json 2> $OUT/r6_bench_$TAG.err ) 2>&1 | grep real
 python - <<PY
 import json
 r = json.loads(open("$OUT/r6_bench_$TAG.json").read().strip().splitlines()[-1])
