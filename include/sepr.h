@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define SEPR_VERSION 412 /* minor*100 + patch ("ABI 4.12").  Any struct-layout or context-size change bumps the MINOR number
+#define SEPR_VERSION 413 /* minor*100 + patch ("ABI 4.13").  Any struct-layout or context-size change bumps the MINOR number
                             (3.01 -> 3.03 grew sepr_ega_w under a patch bump: a caller built against 3.01 would have passed a short
                             struct).  A binding must compare sepr_version() with the SEPR_VERSION it was written against before its
                             first call: sepreformer_amd/lib.py refuses to load a library whose version differs. */
@@ -321,6 +321,25 @@ size_t sepr_pit_sisnr_mag_workspace(int S, int B, int T, int frame_len, int fram
 int sepr_pit_sisnr_mag_fwd(const float* est, const float* tgt, int S, int B, int T, const float* dft,
                            int frame_len, int frame_shift, double eps, float* loss, int* perm, void* ws,
                            size_t ws_bytes, sepr_stream_t stream);
+
+/* BSS-eval source criteria of mir_eval 0.7 bss_eval_sources (compute_permutation=True, distortion filters of 512 taps), the
+ * metric behind PIT_SDRi (utils/implements/criterions.py:264-289, engine.py:133) - evaluation only, no backward.
+ * est, ref [S,B,T] float32 on the device, 2 <= S <= 3; mix [B,T] or NULL (then sdr_mix must be NULL); lengths [B] is a HOST
+ * array of valid lengths, S*512 <= lengths[b] <= T (samples beyond lengths[b] are ignored).  float64 arithmetic throughout:
+ * lagged correlations, the joint Gram of the delayed references and each reference's own Gram, Cholesky factors with the
+ * right-hand sides carried as bordering rows, and the closed-form projection energies E, P_j, P_all:
+ *   SDR = 10 log10(P_j / (E - P_j)), SIR = 10 log10(P_j / (P_all - P_j)), SAR = 10 log10(P_all / (E - P_all)),
+ * a zero denominator giving +inf as mir_eval's _safe_db does.  Outputs [B,S], indexed by REFERENCE k as mir_eval returns them:
+ * sdr/sir/sar[b,k] of estimate perm[b,k], perm = the first maximiser of the mean SIR in itertools.permutations order (the
+ * reverse of sepr_pit_sisnr_fwd's estimate-indexed permutations).  sdr_mix[b,k]: the SDR of the mixture against reference k
+ * (the mixture repeated S times, as PIT_SDRi passes it: every SIR ties, so the permutation is the identity).
+ * status[b]: 0 ok, 1 a silent (all-zero) reference, estimate or mixture (mir_eval raises ValueError), 2 a non-positive
+ * Cholesky pivot; the values of a failed utterance are NaN.  Bit-identical from run to run.
+ * Workspace: sepr_bss_eval_workspace(S, B, T) bytes, about (S*512)^2 * 8 per utterance (0 for unsupported S / T). */
+size_t sepr_bss_eval_workspace(int S, int B, int T);
+int sepr_bss_eval_fwd(const float* est, const float* ref, const float* mix, const int* lengths, int S, int B, int T,
+                      double* sdr, double* sir, double* sar, int* perm, double* sdr_mix, int* status, void* ws,
+                      size_t ws_bytes, sepr_stream_t stream);
 
 /* ================================================================================================================= */
 /* Training path: train-mode forward twins that keep what the backward needs, and the       */

@@ -6,6 +6,9 @@ Mirrors ``utils/implements/criterions.py`` of the reference (SURVEY.md section 8
   (reference :180-217, called by ``engine.py:70,103``);
 * ``PIT_SISNRi(device, num_spks, scale_inv)(estims=..., mixture=..., input_sizes=..., target_attr=..., eps=...)``
   -> ``(mean summed improvement, per-speaker improvements)`` (reference :220-260, called by ``engine.py:131``).
+* ``PIT_SDRi(device, dump)(estims=..., mixture=..., input_sizes=..., target_attr=...)`` -> ``(sum of SDRi / num_utts, SDRi per
+  reference)`` (reference :264-289, called by ``engine.py:133``) on ``bss_eval_sources``, mir_eval's BSS-eval in float64 on the
+  device (``csrc/sepr_bsseval.hip`` through ``sepr_bss_eval_fwd``; the CPU restatement is ``tests/bss_eval_ref.py``).
 
 ``estims`` / ``target_attr`` are lists of ``[B,T]`` tensors (or one ``[S,B,T]`` tensor) on the HIP device.  The
 arithmetic is one pass over the waveforms in ``csrc/sepr_criterion.hip`` through ``sepr_pit_sisnr_fwd``; there is no
@@ -253,3 +256,133 @@ class PIT_SISNR_mag:
             return torch.sum(loss) / kwargs["input_sizes"].shape[0]
         out = pit_sisnr_mag(estims, targets, self._dft, self.frame_length, self.frame_shift)
         return torch.sum(out["loss"]) / kwargs["input_sizes"].shape[0]             # reference :175-176
+
+
+# ---- BSS-eval SDR (PIT_SDRi, criterions.py:264-289) ----------------------------------------------------------------------
+BSS_FLEN = 512                     # mir_eval's distortion-filter length
+BSS_WS_CAP = 1 << 30               # one call's workspace stays under 1 GiB: larger batches are split
+
+
+def _bss_stack(x: _TensorList, what: str) -> torch.Tensor:
+    t = x if isinstance(x, torch.Tensor) else torch.stack(list(x), dim=0)
+    if not t.is_cuda:
+        raise RuntimeError(f"{what} is not on the HIP device (no CPU fallback exists)")
+    return t.detach().to(torch.float32)
+
+
+def bss_eval(references: torch.Tensor, estimates: torch.Tensor, mixture: torch.Tensor = None, lengths=None):
+    """Batched BSS-eval on the device: references / estimates ``[S,B,T]``, mixture ``[B,T]`` or None, lengths ``[B]`` valid
+    samples (default T).  Returns a dict of numpy arrays ``sdr, sir, sar`` (float64) and ``perm`` (int64) ``[B,S]`` indexed by
+    reference, ``sdr_mix`` ``[B,S]`` when a mixture is given, and ``status`` ``[B]`` (0 ok, 1 silent source, 2 factorisation
+    failed).  ``csrc/sepr_bsseval.hip`` through ``sepr_bss_eval_fwd``."""
+    import numpy as np
+    ref, est = _bss_stack(references, "reference_sources"), _bss_stack(estimates, "estimated_sources")
+    if ref.dim() != 3 or ref.shape != est.shape:
+        raise ValueError(f"reference {tuple(ref.shape)} and estimated {tuple(est.shape)} sources must both be [S,B,T]")
+    S, B, T = ref.shape
+    dev = ref.device
+    if est.device != dev:
+        raise RuntimeError("estimates and references are on different devices")
+    if not 2 <= S <= 3:
+        raise ValueError(f"num_spks={S}: the device BSS-eval supports 2 or 3 sources")
+    mix = None
+    if mixture is not None:
+        mix = _bss_stack(mixture, "mixture")
+        if tuple(mix.shape) != (B, T) or mix.device != dev:
+            raise RuntimeError("mixture must be [batch, samples] on the same device as the estimates")
+    lens = [T] * B if lengths is None else [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+    if len(lens) != B:
+        raise ValueError(f"{len(lens)} lengths for a batch of {B}")
+    for b, n in enumerate(lens):
+        if not S * BSS_FLEN <= n <= T:
+            raise ValueError(f"utterance {b}: valid length {n} outside [{S * BSS_FLEN}, {T}] (BSS-eval needs at least "
+                             f"num_spks * {BSS_FLEN} samples)")
+    lib = L.load()
+    out = {k: np.empty((B, S), np.float64) for k in ("sdr", "sir", "sar")}
+    out["perm"] = np.empty((B, S), np.int64)
+    out["status"] = np.empty(B, np.int64)
+    if mix is not None:
+        out["sdr_mix"] = np.empty((B, S), np.float64)
+    per_utt = lib.sepr_bss_eval_workspace(S, 1, T)
+    step = max(1, min(B, BSS_WS_CAP // max(per_utt, 1)))
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        for b0 in range(0, B, step):
+            n = min(step, B - b0)
+            e, r = est[:, b0:b0 + n].contiguous(), ref[:, b0:b0 + n].contiguous()
+            m = None if mix is None else mix[b0:b0 + n].contiguous()
+            nbytes = lib.sepr_bss_eval_workspace(S, n, T)
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            sdr, sir, sar = (torch.empty(n, S, dtype=torch.float64, device=dev) for _ in range(3))
+            perm = torch.empty(n, S, dtype=torch.int32, device=dev)
+            status = torch.empty(n, dtype=torch.int32, device=dev)
+            sdr_mix = None if m is None else torch.empty(n, S, dtype=torch.float64, device=dev)
+            lens_c = (L._i * n)(*lens[b0:b0 + n])
+            L.check(lib.sepr_bss_eval_fwd(e.data_ptr(), r.data_ptr(), None if m is None else m.data_ptr(), lens_c, S, n, T,
+                                          sdr.data_ptr(), sir.data_ptr(), sar.data_ptr(), perm.data_ptr(),
+                                          None if sdr_mix is None else sdr_mix.data_ptr(), status.data_ptr(), ws.data_ptr(),
+                                          ws.numel(), stream.cuda_stream), "sepr_bss_eval_fwd")
+            for k, v in (("sdr", sdr), ("sir", sir), ("sar", sar), ("perm", perm), ("status", status), ("sdr_mix", sdr_mix)):
+                if v is not None:
+                    out[k][b0:b0 + n] = v.cpu().numpy()
+    return out
+
+
+def _bss_raise(status) -> None:
+    for b, s in enumerate(status.tolist()):
+        if s == 1:
+            raise ValueError(f"utterance {b}: a reference, estimated or mixture source is silent (all zeros); BSS-eval is "
+                             "undefined for it (mir_eval.separation.validate raises the same)")
+        if s == 2:
+            raise RuntimeError(f"utterance {b}: the Gram matrix of the delayed references is not positive definite "
+                               "(Cholesky pivot <= 0)")
+
+
+def bss_eval_sources(reference_sources, estimated_sources, input_sizes=None):
+    """``mir_eval.separation.bss_eval_sources(reference_sources, estimated_sources)`` (mir_eval 0.7, compute_permutation=True)
+    on the HIP device.  ``[S,T]`` tensors give ``(sdr [S], sir [S], sar [S], perm [S])`` numpy arrays as mir_eval does;
+    ``[S,B,T]`` tensors give the same with a leading batch dimension, ``input_sizes`` ``[B]`` the valid length of each
+    utterance.  Values are indexed by REFERENCE k: ``sdr[k]`` belongs to estimate ``perm[k]`` (``PIT_SISNRi`` indexes by
+    estimate instead).  A silent source raises ValueError, a failed factorisation RuntimeError."""
+    ref = reference_sources if isinstance(reference_sources, torch.Tensor) else torch.stack(list(reference_sources))
+    est = estimated_sources if isinstance(estimated_sources, torch.Tensor) else torch.stack(list(estimated_sources))
+    if ref.dim() not in (2, 3) or ref.shape != est.shape:
+        raise ValueError(f"reference {tuple(ref.shape)} and estimated {tuple(est.shape)} sources must both be [S,T] or [S,B,T]")
+    flat = ref.dim() == 2
+    if flat:
+        ref, est = ref[:, None], est[:, None]
+    out = bss_eval(ref, est, lengths=input_sizes)
+    _bss_raise(out["status"])
+    res = tuple(out[k] for k in ("sdr", "sir", "sar", "perm"))
+    return tuple(r[0] for r in res) if flat else res
+
+
+class PIT_SDRi:
+    """``PIT_SDRi(device, dump)`` of the reference (criterions.py:264-289, configs.yaml ``PIT_SDRi: {dump: 0}``):
+    ``__call__(estims=, mixture=, input_sizes=, target_attr=)`` -> ``(sum of SDRi / num_utts, SDRi per reference)`` with
+    SDRi = SDR(estimates) - SDR(mixture repeated num_spks times), BSS-eval on the device (``bss_eval`` above).  The reference
+    concatenates the mixture exactly twice (so num_spks = 3 raises there); here it is repeated num_spks times.  The mixture's
+    correlations are formed once, not once per repetition.  SDRi is indexed by reference, as mir_eval returns it."""
+
+    def __init__(self, device, dump: int = 0):
+        self.device, self.dump = torch.device(device), dump
+
+    def __repr__(self):
+        return f"<PIT_SDRi(device={self.device!r}, dump={self.dump!r})>"
+
+    def __call__(self, **kwargs):
+        import numpy as np
+        if self.device.type != "cuda":
+            raise RuntimeError("PIT_SDRi was built for a non-HIP device (no CPU fallback exists)")
+        est = _bss_stack(kwargs["estims"], "estims").to(self.device)
+        tgt = _bss_stack([t.to(self.device) for t in kwargs["target_attr"]] if not isinstance(kwargs["target_attr"], torch.Tensor)
+                         else kwargs["target_attr"].to(self.device), "target_attr")
+        mix = kwargs["mixture"].to(self.device)
+        input_sizes = kwargs["input_sizes"]
+        B = est.shape[1]
+        lengths = input_sizes.reshape(-1).tolist() if input_sizes.numel() == B else None
+        out = bss_eval(tgt, est, mixture=mix.reshape(B, -1), lengths=lengths)
+        _bss_raise(out["status"])
+        sdri = out["sdr"] - out["sdr_mix"]
+        num_utts = input_sizes.shape[0]
+        return np.sum(sdri) / num_utts, (sdri[0] if B == 1 else sdri)

@@ -5,9 +5,10 @@ Mirrors ``models/SepReformer_Base_WSJ0/engine.py``:
 * ``separate_file``  - ``Engine._inference_sample`` (:151-172): load a wav at the model's sampling rate, zero-pad
   to a multiple of the encoder stride, run the separator, crop to the input length, write
   ``<name>_in.wav`` and ``<name>_out_<i>.wav`` peak-normalised to 0.9;
-* ``test_utterances`` - the SI-SNRi part of ``Engine._test`` (:113-149): one utterance per step, device-side
-  ``PIT_SISNRi`` (eps 1e-15), one csv row per utterance, running mean divided by ``num_spks``, optional
-  ``0.5 / max|.|`` wav dumps.  (``PIT_SDRi`` is mir_eval's BSS-eval on the CPU in the reference and stays out of scope.)
+* ``evaluate_utterances`` - ``Engine._test`` (:113-149) in full: one utterance per step, device-side ``PIT_SISNRi``
+  (eps 1e-15) and ``PIT_SDRi`` (mir_eval's BSS-eval on the CPU in the reference; float64 HIP kernels here), one row per
+  utterance in each of the two csv files, running means divided by ``num_spks``, optional ``0.5 / max|.|`` wav dumps;
+* ``test_utterances`` - its SI-SNRi half alone (same loop, no SDRi).
 
 Host-side logic only; every waveform sample is computed by the HIP separator (``Model.forward``) and the HIP
 criterion kernels.  File I/O uses scipy (the reference uses librosa / soundfile, absent here): PCM16/PCM32/float
@@ -92,37 +93,63 @@ def separate_file(model, path: str, fs: int = 8000, out_prefix: Optional[str] = 
     return np.stack(raw), written
 
 
-def test_utterances(model, utterances: Iterable[Tuple[torch.Tensor, Sequence[torch.Tensor], str]],
-                    csv_path: Optional[str] = None, wav_dir: Optional[str] = None, fs: int = 8000) -> Tuple[float, int]:
-    """SI-SNRi loop of ``Engine._test``: ``utterances`` yields ``(mixture [1,T], [source_s [1,T]], key)``.
-    Returns (mean SI-SNRi per speaker in dB, number of utterances); writes one csv row per utterance."""
-    from .criterion import PIT_SISNRi
+def _test_loop(model, utterances, sisnr_csv_path, sdr_csv_path, wav_dir, fs, with_sdr):
+    """``Engine._test`` (engine.py:113-149): one utterance per step; PIT_SISNRi (eps 1e-15) and, when ``with_sdr``,
+    PIT_SDRi; one csv row per utterance and criterion; running means divided by ``num_spks``; optional wav dumps."""
+    from .criterion import PIT_SDRi, PIT_SISNRi
     dev = next(model.parameters()).device
     crit = PIT_SISNRi(dev, model.num_spks, True)
-    total, n = 0.0, 0
-    fh = open(csv_path, "w", newline="") if csv_path else None
-    writer = csv.writer(fh, quotechar="|", quoting=csv.QUOTE_MINIMAL) if fh else None
+    crit_sdr = PIT_SDRi(dev, 0) if with_sdr else None
+    total, total_sdr, n = 0.0, 0.0, 0
+    files = [open(p, "w", newline="") if p else None for p in (sisnr_csv_path, sdr_csv_path)]
+    writers = [csv.writer(fh, quotechar="|", quoting=csv.QUOTE_MINIMAL) if fh else None for fh in files]
     try:
         for mixture, sources, key in utterances:
             if mixture.shape[0] != 1:
                 raise RuntimeError("batch size is not one!!")              # engine.py:126-127
             est = separate(model, mixture)
-            m, per = crit(estims=est, mixture=mixture.to(dev), input_sizes=torch.tensor([mixture.shape[-1]]),
-                          target_attr=[s.to(dev) for s in sources], eps=1.0e-15)
+            input_sizes = torch.tensor([mixture.shape[-1]])
+            targets = [s.to(dev) for s in sources]
+            m, per = crit(estims=est, mixture=mixture.to(dev), input_sizes=input_sizes, target_attr=targets, eps=1.0e-15)
             total += float(m) / model.num_spks
+            per_sdr = None
+            if crit_sdr is not None:
+                m_sdr, per_sdr = crit_sdr(estims=est, mixture=mixture, input_sizes=input_sizes, target_attr=targets)
+                total_sdr += m_sdr.item() / model.num_spks
             n += 1
             name = key[:-4] if key.lower().endswith(".wav") else key
-            if writer:
-                writer.writerow([name] + [float(per[i]) for i in range(model.num_spks)])
+            if writers[0]:
+                writers[0].writerow([name] + [float(per[i]) for i in range(model.num_spks)])
+            if writers[1] and per_sdr is not None:
+                writers[1].writerow([name] + [per_sdr[i].item() for i in range(model.num_spks)])
             if wav_dir:
                 os.makedirs(wav_dir, exist_ok=True)
                 write_wav(os.path.join(wav_dir, f"{name}{n - 1}_mixture.wav"), peak_normalise(mixture[0].cpu().numpy(), 0.5), fs)
                 for i, e in enumerate(est):
                     write_wav(os.path.join(wav_dir, f"{name}{n - 1}_out_{i}.wav"), peak_normalise(e[0].cpu().numpy(), 0.5), fs)
     finally:
-        if fh:
-            fh.close()
-    return (total / n if n else 0.0), n
+        for fh in files:
+            if fh:
+                fh.close()
+    return (total / n if n else 0.0), (total_sdr / n if n else 0.0), n
+
+
+def test_utterances(model, utterances: Iterable[Tuple[torch.Tensor, Sequence[torch.Tensor], str]],
+                    csv_path: Optional[str] = None, wav_dir: Optional[str] = None, fs: int = 8000) -> Tuple[float, int]:
+    """SI-SNRi loop of ``Engine._test``: ``utterances`` yields ``(mixture [1,T], [source_s [1,T]], key)``.
+    Returns (mean SI-SNRi per speaker in dB, number of utterances); writes one csv row per utterance."""
+    mean, _, n = _test_loop(model, utterances, csv_path, None, wav_dir, fs, with_sdr=False)
+    return mean, n
+
+
+def evaluate_utterances(model, utterances: Iterable[Tuple[torch.Tensor, Sequence[torch.Tensor], str]],
+                        sisnr_csv_path: Optional[str] = None, sdr_csv_path: Optional[str] = None,
+                        wav_dir: Optional[str] = None, fs: int = 8000) -> Tuple[float, float, int]:
+    """``Engine._test`` in full: ``utterances`` yields ``(mixture [1,T], [source_s [1,T]], key)``.  Returns (mean SI-SNRi
+    per speaker, mean SDRi per speaker, number of utterances) in dB; writes one row per utterance to each csv file
+    (``test_SISNRi_value.csv`` / ``test_SDRi_value.csv`` in the reference) and the ``0.5 / max|.|`` wav dumps of test_save.
+    SDRi rows are indexed by reference source (mir_eval's order), SI-SNRi rows by estimate."""
+    return _test_loop(model, utterances, sisnr_csv_path, sdr_csv_path, wav_dir, fs, with_sdr=True)
 
 
 test_utterances.__test__ = False      # not a pytest test

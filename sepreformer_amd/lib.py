@@ -147,6 +147,8 @@ SIGNATURES = {
     "sepr_linear_x3_fwd": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _fp]),
     "sepr_pit_sisnr_mag_workspace": (_sz, [_i, _i, _i, _i, _i]),
     "sepr_pit_sisnr_mag_fwd": (_i, [_fp, _fp, _i, _i, _i, _fp, _i, _i, C.c_double, _fp, _fp, _fp, _sz, _fp]),
+    "sepr_bss_eval_workspace": (_sz, [_i, _i, _i]),
+    "sepr_bss_eval_fwd": (_i, [_fp, _fp, _fp, C.POINTER(_i), _i, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _sz, _fp]),
     "sepr_pit_sisnr_fwd": (_i, [_fp, _fp, _fp, _i, _i, _i, C.c_double, C.c_double, C.c_double, _fp, _fp, _fp, _fp,
                                 _fp, _sz, _fp]),
     "sepr_train_ctx_bytes": (_sz, [_i] * 8),
@@ -198,7 +200,7 @@ _lib: Optional[C.CDLL] = None
 _lock = threading.Lock()
 
 
-ABI_VERSION = 412          # include/sepr.h SEPR_VERSION this binding mirrors (tests/test_boundary_cpu.py keeps the two equal)
+ABI_VERSION = 413          # include/sepr.h SEPR_VERSION this binding mirrors (tests/test_boundary_cpu.py keeps the two equal)
 
 
 class SeprLibraryError(RuntimeError):
