@@ -341,6 +341,29 @@ int sepr_bss_eval_fwd(const float* est, const float* ref, const float* mix, cons
                       double* sdr, double* sir, double* sar, int* perm, double* sdr_mix, int* status, void* ws,
                       size_t ws_bytes, sepr_stream_t stream);
 
+/* Long-form separation (the reference has no long-form mode): boundary alignment and overlap-add of the
+ * separator's outputs on overlapping windows.  R recordings; recording r has lengths[r] = T_r >= 1 samples and
+ * Nc_r = 1 (T_r <= W) or 1 + ceil((T_r - W) / H) windows of W samples at hop H = W - O, window k covering [kH, kH + W); its
+ * windows are chunks[chunk_offset[r] .. chunk_offset[r + 1]), chunk_offset[0] = 0.  chunk_offset [R+1] and lengths [R] are
+ * HOST arrays (copied into the workspace on `stream`: under graph capture they are read when the copy node runs).
+ * chunks [total_chunks][S][W] float32 (total_chunks = chunk_offset[R]); W and O multiples of 4, 0 < O <= W / 2; chunks and y
+ * 16-byte aligned; S in {2, 3}.  Per boundary k | k+1, over a_i = source i of window k on its last O samples and b_j = source j
+ * of window k+1 on its first O samples, in float64 and a fixed order: C[i][j] = <a_i, b_j>, Ea[i] = <a_i, a_i>, Eb[j] = <b_j, b_j>;
+ *   pi_k = the lexicographically first maximiser of sum_i |C[i][pi(i)]| / sqrt(Ea[i] Eb[pi(i)] + 1e-20);
+ *   P_0 = identity, P_{k+1}(s) = pi_k(P_k(s));  g_0 = 1, g_{k+1}(s) = g_k(s) * (C[i][j] / Eb[j]) with i = P_k(s), j = pi_k(i)
+ *   when match_gain, else g = 1; the ratio is replaced by 1 (gain carried) when Ea[i] / O or Eb[j] / O is below 1e-10, the
+ *   normalised correlation |C[i][j]| / sqrt(Ea[i] Eb[j] + 1e-20) is below 0.5, or the ratio is not finite.
+ * perm [total_chunks][S] int32 = P_k(s), gain [total_chunks][S] float32 = g_k(s) (rounded from float64).
+ * y[r][s][t] = sum_k w_k(t) g_k(s) chunks[k][P_k(s)][t - kH] for t < T_r: in the overlap of boundary k - 1 | k at offset j
+ * the incoming window weighs w = (float) sin^2(pi (j + 0.5) / (2 O)) (double sine), the outgoing 1.0f - w; elsewhere 1.
+ * y is packed by the offsets: track s of recording r starts at y + S (chunk_offset[r] H + r O) + s (Nc_r H + O) and holds
+ * Nc_r H + O >= T_r samples, zero from T_r on; S (total_chunks H + R O) floats in all.  Bit-identical from run to run; no host
+ * synchronisation or allocation (capturable).  Every argument check returns SEPR_EINVAL (SEPR_EWORKSPACE for a short workspace)
+ * before any HIP call.  Workspace: sepr_stitch_workspace(R, total_chunks, S) bytes (0 for unsupported arguments). */
+size_t sepr_stitch_workspace(int R, int total_chunks, int S);
+int sepr_stitch_fwd(const float* chunks, const int* chunk_offset, const int* lengths, int R, int S, int W, int O, int match_gain,
+                    float* y, int* perm, float* gain, void* ws, size_t ws_bytes, sepr_stream_t stream);
+
 /* ================================================================================================================= */
 /* Training path: train-mode forward twins that keep what the backward needs, and the       */
 /* backward of every block.  The reference trains through torch.autograd over the same modules (engine.py:50-83:     */

@@ -8,7 +8,9 @@ Mirrors ``models/SepReformer_Base_WSJ0/engine.py``:
 * ``evaluate_utterances`` - ``Engine._test`` (:113-149) in full: one utterance per step, device-side ``PIT_SISNRi``
   (eps 1e-15) and ``PIT_SDRi`` (mir_eval's BSS-eval on the CPU in the reference; float64 HIP kernels here), one row per
   utterance in each of the two csv files, running means divided by ``num_spks``, optional ``0.5 / max|.|`` wav dumps;
-* ``test_utterances`` - its SI-SNRi half alone (same loop, no SDRi).
+* ``test_utterances`` - its SI-SNRi half alone (same loop, no SDRi);
+* ``separate_long`` / ``separate_long_file`` - beyond the reference: recordings of any length by overlapping windows of the
+  training length, batched through the separator and stitched on the device (``longform.py``).
 
 Host-side logic only; every waveform sample is computed by the HIP separator (``Model.forward``) and the HIP
 criterion kernels.  File I/O uses scipy (the reference uses librosa / soundfile, absent here): PCM16/PCM32/float
@@ -23,6 +25,8 @@ from typing import Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
+
+from .longform import separate_long  # noqa: F401  (re-exported: the long-form entry point)
 
 
 def load_wav(path: str, fs: int) -> np.ndarray:
@@ -87,6 +91,24 @@ def separate_file(model, path: str, fs: int = 8000, out_prefix: Optional[str] = 
     raw = []
     for i, e in enumerate(est):
         src = e[0].detach().cpu().numpy()
+        raw.append(src)
+        written.append(f"{prefix}_out_{i}.wav")
+        write_wav(written[-1], peak_normalise(src, 0.9), fs)
+    return np.stack(raw), written
+
+
+def separate_long_file(model, path: str, fs: int = 8000, out_prefix: Optional[str] = None, chunk_seconds: float = 4.0,
+                       overlap_seconds: float = 1.0, match_gain: bool = False, batch: int = 32) -> Tuple[np.ndarray, List[str]]:
+    """``separate_file`` through ``separate_long``: the same files, the same 0.9 peak normalisation."""
+    mix = load_wav(path, fs)
+    est = separate_long(model, torch.from_numpy(mix), chunk_seconds=chunk_seconds, overlap_seconds=overlap_seconds, fs=fs,
+                        batch=batch, match_gain=match_gain)
+    prefix = out_prefix if out_prefix is not None else path[:-4]
+    written = [prefix + "_in.wav"]
+    write_wav(written[0], peak_normalise(mix, 0.9), fs)
+    raw = []
+    for i, e in enumerate(est):
+        src = e.detach().cpu().numpy()
         raw.append(src)
         written.append(f"{prefix}_out_{i}.wav")
         write_wav(written[-1], peak_normalise(src, 0.9), fs)
@@ -164,6 +186,10 @@ def _main() -> None:
     ap.add_argument("--model", default="SepReformer_Base_WSJ0", choices=sorted(VARIANTS))
     ap.add_argument("--checkpoint", default=None, help="reference checkpoint (.pth with model_state_dict); default: synthetic weights")
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--chunk-seconds", type=float, default=None,
+                    help="long-form mode: overlapping windows of this length, stitched on the device (default: one whole-file forward)")
+    ap.add_argument("--overlap-seconds", type=float, default=1.0, help="long-form mode: overlap of consecutive windows")
+    ap.add_argument("--match-gain", action="store_true", help="long-form mode: align each speaker track's gain across windows")
     args = ap.parse_args()
     model = Model.from_config(VARIANTS[args.model], init_seed=0)
     if args.checkpoint:
@@ -172,7 +198,11 @@ def _main() -> None:
     else:
         model.load_synthetic_(0)
     model = model.eval().to(args.device)
-    _, written = separate_file(model, args.wav)
+    if args.chunk_seconds is None:
+        _, written = separate_file(model, args.wav)
+    else:
+        _, written = separate_long_file(model, args.wav, chunk_seconds=args.chunk_seconds, overlap_seconds=args.overlap_seconds,
+                                        match_gain=args.match_gain)
     print("\n".join(written))
 
 
