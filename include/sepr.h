@@ -198,7 +198,10 @@ const char* sepr_build_info(void);
 enum { SEPR_KNOB_X3_WIDE = 0 /* 0 / 1 (default) / 2: sepr_gemm_x3.hip */, SEPR_KNOB_TRAIN_GCFN_PLANES /* default 1 */,
        SEPR_KNOB_TRAIN_ATTN_ONE /* default 1 */, SEPR_KNOB_TRAIN_CLA16 /* default 1 */,
        SEPR_KNOB_FOLD_HEAD /* default 1: main OutputLayer + AudioDecoder as one launch when sepr_out_w.fold_* are set */,
-       SEPR_KNOB_TN16 /* default 1: weight-gradient contractions of two bf16 operands on the LDS-DMA + transposing-read kernel */, SEPR_KNOB_COUNT };
+       SEPR_KNOB_TN16 /* default 1: weight-gradient contractions of two bf16 operands on the LDS-DMA + transposing-read kernel */,
+       SEPR_KNOB_GB_FUSE /* default 1 (SEPR_GB_FUSE): sepr_global_block_fwd runs the EGA gate inside the GCFN kernel where that form exists;
+                            0 = always the two calls (A/B, bit-identity tests) */,
+       SEPR_KNOB_COUNT };
 int sepr_knob(int id);
 void sepr_knobs_reload(void);
 /* text of the last HIP error seen by the calling thread ("" if none) */
@@ -242,6 +245,14 @@ int sepr_cla_fwd(const float* x, float* y, int n, int T, int F, int K, const sep
  * x,y [n,T,F], T = Tp * 2^k; y must NOT alias x. */
 int sepr_ega_fwd(const float* x, float* y, int n, int T, int Tp, int F, int H, const sepr_ega_w* w,
                  void* ws, size_t ws_bytes, sepr_stream_t stream);
+
+/* One global block, modules/network.py:198-209: y_mid = EGA(x), y = GCFN(y_mid) - what sepr_ega_fwd followed by sepr_gcfn_fwd write, bit
+ * for bit.  gate_perm_p (optional; pack.py::pack_gate_fused_perm, built beside sepr_ega_w.fused_gate_p) is the gate projection with its
+ * output rows in the order of the GCFN kernel's frame fragments: with it, for F = 128, 1 < T / Tp dividing 64 and launches large enough for
+ * the 126-frame-tile GCFN kernel, the gate runs in that kernel's tile prologue (no stand-alone pass over the residual stream).  Every other
+ * case, and SEPR_GB_FUSE=0, is the two calls.  x, y_mid, y [n,T,F], pairwise distinct; workspace as for sepr_ega_fwd. */
+int sepr_global_block_fwd(const float* x, float* y_mid, float* y, int n, int T, int Tp, int F, int H, const sepr_ega_w* ega,
+                          const sepr_gcfn_w* gcfn, const void* gate_perm_p, void* ws, size_t ws_bytes, sepr_stream_t stream);
 
 /* SpkAttention.forward up to (excluding) its feed_forward GCFN, modules/network.py:233-247:
  * attention across the S speakers of each frame + residual.  x,y [B*S,T,F] (row index b*S+s);

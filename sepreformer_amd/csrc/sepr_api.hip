@@ -51,6 +51,7 @@ struct ClaFusedArgs {
 };
 size_t pit_workspace_bytes(int S, int B, int T);                                      // sepr_criterion.hip
 int launch_ega_gate(const ClaFusedArgs& a, int F, int site, hipStream_t stream);      // sepr_cla_fused.hip
+int launch_ega_outproj(const ClaFusedArgs& a, int F, int site, hipStream_t stream);   // sepr_cla_fused.hip
 int launch_ega_qkv(const ClaFusedArgs& a, int F, int site, hipStream_t stream);       // sepr_cla_fused.hip
 int launch_cla_head(const ClaFusedArgs& a, int F, int site, hipStream_t stream);      // sepr_cla_fused.hip
 int launch_cla_tail(const ClaFusedArgs& a, int F, int site, hipStream_t stream);
@@ -109,7 +110,7 @@ int g_knobs[SEPR_KNOB_COUNT];
 std::mutex g_knobs_mu;
 void knobs_read() {
   static const struct { const char* name; int dflt; } tab[SEPR_KNOB_COUNT] = {
-      {"SEPR_X3_WIDE", 1}, {"SEPR_TRAIN_GCFN_PLANES", 1}, {"SEPR_TRAIN_ATTN_ONE", 1}, {"SEPR_TRAIN_CLA16", 1}, {"SEPR_FOLD_HEAD", 1}, {"SEPR_TN16", 1}};
+      {"SEPR_X3_WIDE", 1}, {"SEPR_TRAIN_GCFN_PLANES", 1}, {"SEPR_TRAIN_ATTN_ONE", 1}, {"SEPR_TRAIN_CLA16", 1}, {"SEPR_FOLD_HEAD", 1}, {"SEPR_TN16", 1}, {"SEPR_GB_FUSE", 1}};
   for (int i = 0; i < SEPR_KNOB_COUNT; ++i) {
     const char* e = getenv(tab[i].name);
     g_knobs[i] = (e && e[0]) ? atoi(e) : tab[i].dflt;
@@ -307,8 +308,11 @@ static int relattn_x3(const sepr_ega_w* w) {
   return (w->attn.x3_qkv.wp != nullptr && !f32) ? 1 : 0;
 }
 
+// att_only (sepr_global_block_fwd, gate inside the GCFN kernel): everything up to the pooled attention rows att = ls_o * (Linear_out(o) + b_o),
+// whose workspace address is returned; no gate launch, y untouched.  The caller has checked that the folded output projection applies
+// (the rows then come from ega_outproj_kernel, bit-identical to what the gate launch computes for itself).
 static int ega_fwd_impl(const float* x, const float* x_stats, float* y, float* y_stats, int n, int T, int Tp, int F, int H, const sepr_ega_w* w,
-                        void* ws, size_t ws_bytes, sepr_stream_t stream) {
+                        void* ws, size_t ws_bytes, sepr_stream_t stream, const float** att_only = nullptr) {
   if (!x || !y || !w || x == y || n <= 0 || T <= 0 || Tp <= 0 || F <= 0 || F % 32 != 0 || T % Tp != 0) return SEPR_EINVAL;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int fac = T / Tp;
@@ -350,6 +354,14 @@ static int ega_fwd_impl(const float* x, const float* x_stats, float* y, float* y
   }
   SEPR_TRY(launch_relattn(qkv, o, n, Tp, F, H, w->pe_k, w->maxlen, relattn_x3(w), st, w->pe_k_planes));   // (network.py:106-122)
   const bool out_fused = w->fused_gate_p && w->fused_out_p && F == 128 && 64 % fac == 0;
+  if (att_only) {
+    if (!out_fused) return SEPR_EINVAL;
+    ClaFusedArgs g = {};
+    g.o = o; g.att_w = att; g.wop = w->fused_out_p; g.bo = w->attn.bo; g.lso = w->attn.ls; g.Mp = (int)Mp;
+    SEPR_TRY(launch_ega_outproj(g, F, SEPR_SITE_ATTN_PROJ, st));
+    *att_only = att;
+    return SEPR_OK;
+  }
   if (!out_fused) {  // linear_out * LayerScale (no residual inside MHA)      (network.py:124)
     GemmArgs a = gemm_args_zero();
     a.M = (int)Mp; a.N = F; a.K = F;
@@ -385,6 +397,29 @@ extern "C" int sepr_ega_fwd(const float* x, float* y, int n, int T, int Tp, int 
                             size_t ws_bytes, sepr_stream_t stream) {
   return ega_fwd_impl(x, nullptr, y, nullptr, n, T, Tp, F, H, w, ws, ws_bytes, stream);
 }
+// EGA + GCFN of one global block.  With the gate inside the GCFN kernel (large F = 128 launches, SEPR_GB_FUSE != 0) the stand-alone gate pass
+// over the residual stream is gone; every other shape is the two calls.  Either way y_mid / y hold what sepr_ega_fwd / sepr_gcfn_fwd write.
+extern "C" int sepr_global_block_fwd(const float* x, float* y_mid, float* y, int n, int T, int Tp, int F, int H, const sepr_ega_w* ega,
+                                     const sepr_gcfn_w* gcfn, const void* gate_perm_p, void* ws, size_t ws_bytes, sepr_stream_t stream) {
+  if (!x || !y_mid || !y || !ega || !gcfn || x == y_mid || y_mid == y || x == y || n <= 0 || T <= 0 || Tp <= 0 || T % Tp != 0) return SEPR_EINVAL;
+  const long long M = (long long)n * T;
+  const int fac = T / Tp;
+  const bool fused = gate_perm_p && knob(SEPR_KNOB_GB_FUSE) != 0 && F == 128 && M <= 0x7fffffffLL / 8 && fac > 1 && 64 % fac == 0 &&
+                     ega->fused_gate_p && ega->fused_out_p && gcfn->fused_w1p && gcfn->fused_w2p && gcfn_fused_takes_gate((int)M, F);
+  if (!fused) {
+    SEPR_TRY(ega_fwd_impl(x, nullptr, y_mid, nullptr, n, T, Tp, F, H, ega, ws, ws_bytes, stream));
+    return gcfn_fwd_impl(y_mid, nullptr, y, nullptr, n, T, F, gcfn, ws, ws_bytes, stream);
+  }
+  const float* att = nullptr;
+  SEPR_TRY(ega_fwd_impl(x, nullptr, y_mid, nullptr, n, T, Tp, F, H, ega, ws, ws_bytes, stream, &att));
+  GcfnFusedArgs f = {};
+  f.x = x; f.y = y; f.M = (int)M; f.T = T;
+  f.w1p = gcfn->fused_w1p; f.w2p = gcfn->fused_w2p;
+  f.b2 = gcfn->b2; f.ls = gcfn->ls; f.eps = LN_EPS; f.stagger = 0;
+  f.gate_wp = gate_perm_p; f.att = att; f.Tp = Tp; f.fac = fac; f.mid = y_mid;
+  return launch_gcfn_fused(f, F, SEPR_SITE_GCFN_UP, static_cast<hipStream_t>(stream));
+}
+
 extern "C" int sepr_ega_fwd_st(const float* x, const float* x_stats, float* y, float* y_stats, int n, int T, int Tp, int F, int H,
                                const sepr_ega_w* w, void* ws, size_t ws_bytes, sepr_stream_t stream) {
   return ega_fwd_impl(x, x_stats, y, y_stats, n, T, Tp, F, H, w, ws, ws_bytes, stream);

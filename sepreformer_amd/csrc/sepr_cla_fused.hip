@@ -467,6 +467,72 @@ __global__ __launch_bounds__(CF_NT, F > 128 ? 1 : 2) void cla_head_kernel(const 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// The attention's output projection on its own: att = ls_o * (Linear_out(o) + b_o) for all pooled rows, for the global block whose gate
+// runs inside the GCFN kernel (sepr_gcfn_fused.hip, GATE) and needs att complete before it starts.  The walk the gate launch does for its
+// tile's pooled rows (cla_head_kernel, a.o != null), 64 rows per workgroup: wave w owns output tiles 2w, 2w+1, weights global -> registers,
+// rows as B fragments straight from o; per accumulator the same operand sequence, so the rows are bit-identical to the folded form's.
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(CF_NT, 2) void ega_outproj_kernel(const ClaFusedArgs a) {
+  constexpr int F = 128, KS = F / 32, FT = F / 16, NW = CF_NW, FTW = FT / NW, ROWS = 64;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int fi = lane & 15, fg = lane >> 4;
+  const int ws = __builtin_amdgcn_readfirstlane(w);
+  const unsigned loff = (unsigned)lane * 16u;
+  const uint4* const Wob = static_cast<const uint4*>(a.wop) + (long long)(FTW * ws) * KS * 2 * 64;
+  uint4 wo[FTW][KS][2];
+#pragma unroll
+  for (int t = 0; t < FTW; ++t)
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+      for (int pl = 0; pl < 2; ++pl)
+        wo[t][ks][pl] = *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(Wob + ((t * KS + ks) * 2 + pl) * 64) + loff);
+  float4 bov[FTW], lov[FTW];
+#pragma unroll
+  for (int t = 0; t < FTW; ++t) {
+    bov[t] = ld4(a.bo + 16 * (FTW * w + t) + 4 * fg);
+    lov[t] = ld4(a.lso + 16 * (FTW * w + t) + 4 * fg);
+  }
+  const int p0 = blockIdx.x * ROWS;
+#pragma unroll 1
+  for (int nt = 0; nt * 16 < ROWS; ++nt) {
+    const int pr = p0 + 16 * nt + fi;
+    const bool ok = pr < a.Mp;
+    const float* op = a.o + (long long)(ok ? pr : 0) * F + 8 * fg;
+    bf16x8 oh[KS], ol[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      const float4 p = ld4(op + 32 * ks), q = ld4(op + 32 * ks + 4);
+      const float v[8] = {p.x, p.y, p.z, p.w, q.x, q.y, q.z, q.w};
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const __bf16 hh = (__bf16)v[e];
+        oh[ks][e] = hh;
+        ol[ks][e] = (__bf16)(v[e] - (float)hh);
+      }
+    }
+    f32x4 pa[FTW];
+#pragma unroll
+    for (int t = 0; t < FTW; ++t) pa[t] = (f32x4){bov[t].x, bov[t].y, bov[t].z, bov[t].w};
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+      for (int t = 0; t < FTW; ++t) {
+        const bf16x8 wh = *reinterpret_cast<const bf16x8*>(&wo[t][ks][0]), wlo = *reinterpret_cast<const bf16x8*>(&wo[t][ks][1]);
+        pa[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, oh[ks], pa[t], 0, 0, 0);
+        pa[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, ol[ks], pa[t], 0, 0, 0);
+        pa[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wlo, oh[ks], pa[t], 0, 0, 0);
+      }
+    if (ok) {
+#pragma unroll
+      for (int t = 0; t < FTW; ++t)
+        st4(a.att_w + (long long)pr * F + 16 * (FTW * w + t) + 4 * fg,
+            make_float4(pa[t][0] * lov[t].x, pa[t][1] * lov[t].y, pa[t][2] * lov[t].z, pa[t][3] * lov[t].w));
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // tail: y = x + ls * Linear3(GELU(Linear2'(c)))      (eval BatchNorm folded into Linear2')
 // ---------------------------------------------------------------------------------------------------------------------
 template <int F, int MT = CF_MT>
@@ -982,6 +1048,17 @@ int launch_cla_head(const ClaFusedArgs& a, int F, int site, hipStream_t stream) 
   else hipLaunchKernelGGL((cla_head_kernel<128, false>), dim3(ntiles < cap ? ntiles : cap), dim3(CF_NT), 0, stream, a);
   if (timed) prof_end(slot, (double)a.M * 2.0 * F * 2 * F, stream);
   SEPR_CHECK_LAUNCH("cla_head_kernel");
+  return SEPR_OK;
+}
+
+int launch_ega_outproj(const ClaFusedArgs& a, int F, int site, hipStream_t stream) {
+  if (a.Mp <= 0) return SEPR_OK;
+  if (F != 128 || !a.o || !a.att_w || !a.wop || !a.bo || !a.lso || a.o == a.att_w) return SEPR_EINVAL;
+  long long slot = -1;
+  const bool timed = prof_begin(site, stream, &slot);
+  hipLaunchKernelGGL(ega_outproj_kernel, dim3((a.Mp + 63) / 64), dim3(CF_NT), 0, stream, a);
+  if (timed) prof_end(slot, (double)a.Mp * 2.0 * F * F, stream);
+  SEPR_CHECK_LAUNCH("ega_outproj_kernel");
   return SEPR_OK;
 }
 

@@ -39,7 +39,17 @@ struct GcfnFusedArgs {
   float drop_scale;
   unsigned long long seed;
   const unsigned long long* salt;
+  // GATE instantiation (launch_gcfn_fused with gate_wp set: sepr_global_block_fwd): x is the EGA gate's input, the gate's output - the GCFN's
+  // input and residual - is formed in registers and its rows go to mid
+  const void* gate_wp;  // two chunks of [4 tiles][F/32][plane][64][8] bf16 + 4 KB fp32 biases, rows in the frame fragments' channel order
+                        // (pack.py::pack_gate_fused_perm); NULL = plain GCFN
+  const float* att;     // [n, Tp, F] pooled attention rows (complete before the launch)
+  int Tp, fac;          // pooled frames per sequence, T / Tp
+  float* mid;           // [M, F] gate output
 };
+
+// true when a launch of M rows takes the instantiation that can carry the gate prologue (the large F = 128 inference form)
+bool gcfn_fused_takes_gate(int M, int F);
 
 int launch_gcfn_fused(const GcfnFusedArgs& a, int F, int site, hipStream_t stream);
 int launch_glumlp_fused(const GcfnFusedArgs& a, int F, int site, hipStream_t stream);

@@ -113,9 +113,15 @@ struct bool_c { static constexpr bool value = V; };
 // ONE (training precision "bf16" only): plain bf16 operands - the normalised frames, the weights and the gated tensor are used
 // as their bf16 hi plane alone, ONE MFMA per product instead of three, no lo-plane split on the VALU, and only the hi-plane
 // blocks of every packed weight chunk are copied to LDS (half the L2 -> LDS stream).  Same packed weights, same LDS layout.
-template <int F, int MT, int NW, int MODE = 0, bool TRAIN = false, bool ONE = false, int LAT = 0>
-__global__ __launch_bounds__(64 * NW, (LAT > 0 || F > 128 || MT > 2) ? (NW > 4 ? 2 : 1) : (2 * NW) / 4) void gcfn_fused3_kernel(const GcfnFusedArgs a) {
+// GATE (F = 128, MT = 2, NW = 4, inference): the EGA gate of the same global block (network.py:132-135,151-153) runs in the tile's prologue.
+// The frames loaded are the gate's INPUT x; y = x + sigmoid(Linear(LayerNorm(x))) * att[seq, t / fac] overwrites them in registers (the gate
+// weights are packed so that a lane's accumulators are the channels it holds of x: pack.py::pack_gate_fused_perm), y's own rows go to a.mid
+// (the epilogue's residual, read back through L2) and y is what the GCFN's LayerNorm below sees.  Per frame the arithmetic is that of
+// cla_head_kernel<128, true> followed by this kernel: bit-identical to the two launches.
+template <int F, int MT, int NW, int MODE, bool TRAIN, bool ONE, int LAT, bool GATE>
+__device__ __forceinline__ void gcfn_fused3_body(const GcfnFusedArgs& a) {
   constexpr bool PLAIN = MODE >= 1;   // frames are independent: no halo, no seam exchange, no conv
+  static_assert(!GATE || (MODE == 0 && !TRAIN && !ONE && LAT == 0 && F == 128 && MT == 2 && NW == 4), "gate prologue: the large Base inference launch");
   constexpr bool FOLD = MODE == 2;    // OutputLayer with the AudioDecoder folded into its second projection (see launch_glumlp_fold)
   static_assert(!(TRAIN && PLAIN), "the train instantiation is the GCFN block");
   static_assert(!ONE || TRAIN, "plain bf16 operands do not pass the inference parity gate: a training arithmetic only");
@@ -316,10 +322,18 @@ __global__ __launch_bounds__(64 * NW, (LAT > 0 || F > 128 || MT > 2) ? (NW > 4 ?
 #endif
     // chunk 0 of the weights is requested first: it lands under the frame loads and the LayerNorm below
     __syncthreads();   // the previous tile's epilogue staging is fully consumed
+    [[maybe_unused]] const uint4* const Gg = static_cast<const uint4*>(a.gate_wp);   // GATE: two chunks of [4 tiles | 4 KB biases]
     if constexpr (LAT > 0) {
 #pragma unroll
       for (int c0 = 0; c0 < NST - 1; ++c0)
         if (c0 < NCH) lat_dma(c0);
+    } else if constexpr (GATE) {
+      // gate chunk 0 -> up-projection buffer, the first tile pair of chunk 1 -> down-projection buffer, both bias blocks -> the two constant slots
+      static_assert(W2_U4 * 2 == W1F_U4, "half a gate chunk fills the down-projection buffer");
+      dma(Gg, wl, W1F_U4 / 64);
+      dma(Gg + W1F_U4, csl, CS_U4 / 64);
+      dma(Gg + W1_U4, wl + W1F_U4, W2_U4 / 64);
+      dma(Gg + W1_U4 + W1F_U4, csl + CS_U4, CS_U4 / 64);
     } else {
       dma_w1(0);
       dma_w2(0);
@@ -332,6 +346,7 @@ __global__ __launch_bounds__(64 * NW, (LAT > 0 || F > 128 || MT > 2) ? (NW > 4 ?
 #endif
     float f0[MT], f2[MT];                                        // conv zero-padding flags (sequence start / end)
     bool edge_lane = false;
+    [[maybe_unused]] float yv[GATE ? MT : 1][GATE ? KS : 1][8];  // GATE: the fp32 frames (x, then y in place)
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
       int m = mw0 + MT * fi + mt;
@@ -398,9 +413,133 @@ __global__ __launch_bounds__(64 * NW, (LAT > 0 || F > 128 || MT > 2) ? (NW > 4 ?
         if constexpr (TRAIN && ONE) {   // side output for the backward: the bf16 rows exactly as the MFMAs read them (16 B per lane and K step)
           if (a.xhat16 && own_row) *reinterpret_cast<bf16x8*>(static_cast<__bf16*>(a.xhat16) + (long long)m * F + 32 * ks + 8 * fg) = h;
         }
+        if constexpr (GATE) {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) yv[mt][ks][e] = v[ks][e];
+        }
       }
     }
     const bool edge = __builtin_amdgcn_ballot_w64(edge_lane) != 0ull;   // wave-uniform
+    if constexpr (GATE) {
+      // ---- EGA gate on the wave's 32 frames: xh / xl hold LayerNorm(x) (frames outside the launch: zero planes, finite values, never stored) ----
+      const float* attp[MT];   // this lane's 8 channels of the frame's pooled attention row; + 32 per K step
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt) {
+        const int m = mw0 + MT * fi + mt;
+        const int mc = (m >= 0 && m < a.M) ? m : 0;
+        const int seq = mc / a.T, t = mc - seq * a.T;
+        attp[mt] = a.att + ((long long)seq * a.Tp + t / a.fac) * F + 8 * fg;
+      }
+      // one tile pair = output channels 32*kq .. +31 in the lane's own channel order (tile h, row 4*fg + r = channel 32*kq + 8*fg + 4*h + r);
+      // per accumulator the operand sequence of cla_head_kernel: bias, then (hi,hi) (hi,lo) (lo,hi) for K steps 0 .. KS-1
+      auto gate_pair = [&](const uint4* tp, const float* bias, int kq) {
+        auto ld_g = [&](int n, uint4 (&d)[2]) {   // n = h*KS + ks
+          const uint4* p = tp + (n * 2) * 64 + lane;
+          d[0] = p[0];
+          d[1] = p[64];
+        };
+        uint4 fb[RD + 1][2];
+#pragma unroll
+        for (int n = 0; n < RD; ++n) ld_g(n, fb[n]);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          float4 at[MT];
+#pragma unroll
+          for (int mt = 0; mt < MT; ++mt) at[mt] = ld4(attp[mt] + 32 * kq + 4 * h);
+          f32x4 g[MT];
+          {
+            const float4 b = ld4(bias + 16 * h + 4 * fg);
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) g[mt] = (f32x4){b.x, b.y, b.z, b.w};
+          }
+#pragma unroll
+          for (int ks = 0; ks < KS; ++ks) {
+            const int n = h * KS + ks;
+            if (n + RD < 2 * KS) ld_g(n + RD, fb[(n + RD) % (RD + 1)]);
+            SEPR_GF3_SCHED_FENCE();
+            const bf16x8 wh = *reinterpret_cast<const bf16x8*>(&fb[n % (RD + 1)][0]);
+            const bf16x8 wlo = *reinterpret_cast<const bf16x8*>(&fb[n % (RD + 1)][1]);
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) g[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, xh[mt][ks], g[mt], 0, 0, 0);
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) g[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, xl[mt][ks], g[mt], 0, 0, 0);
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) g[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wlo, xh[mt][ks], g[mt], 0, 0, 0);
+            SEPR_GF3_SCHED_FENCE();
+          }
+#pragma unroll
+          for (int mt = 0; mt < MT; ++mt) {
+            const float av[4] = {at[mt].x, at[mt].y, at[mt].z, at[mt].w};
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              yv[mt][kq][4 * h + r] = fmaf(sigmoid_f(g[mt][r]), av[r], yv[mt][kq][4 * h + r]);
+              // the update happens HERE: hipcc otherwise keeps sigmoid and att of all four tile pairs (spilled) and forms y behind the last barrier
+              asm volatile("" : "+v"(yv[mt][kq][4 * h + r]));
+            }
+          }
+        }
+      };
+      constexpr int PAIR_U4 = 2 * KS * 2 * 64;   // two tiles
+      const float* const gb0 = reinterpret_cast<const float*>(csl);
+      const float* const gb1 = reinterpret_cast<const float*>(csl + CS_U4);
+      dma_barrier();                                         // gate chunk 0 and the first half of chunk 1 have landed
+      gate_pair(wl, gb0, 0);
+      gate_pair(wl + PAIR_U4, gb0 + 32, 1);
+      dma_barrier();                                         // every wave is done with chunk 0
+      dma(Gg + W1_U4 + PAIR_U4, wl, PAIR_U4 / 64);           // second tile pair of chunk 1 -> up-projection buffer
+      gate_pair(wl + W1F_U4, gb1, 2);
+      dma_barrier();                                         // ... landed; every wave is done with the down-projection buffer
+      dma_w2(0);
+      gate_pair(wl, gb1 + 32, 3);
+      __syncthreads();                                       // every wave is done with the up-projection buffer and the bias blocks
+      dma_w1(0);                                             // lands under the stores and the LayerNorm below
+      // ---- y: own rows -> a.mid (the tile's two end frames belong to the neighbouring tiles), LayerNorm, split: the GCFN's input planes ----
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt) {
+        const int m = mw0 + MT * fi + mt, bf = w * WSTR + MT * fi + mt;
+        const bool valid = (m >= 0 && m < a.M);
+        if (valid && bf >= 1 && bf <= GF_TILE) {
+          float* yp = a.mid + (long long)m * F + 8 * fg;
+#pragma unroll
+          for (int ks = 0; ks < KS; ++ks) {
+            st4(yp + 32 * ks, make_float4(yv[mt][ks][0], yv[mt][ks][1], yv[mt][ks][2], yv[mt][ks][3]));
+            st4(yp + 32 * ks + 4, make_float4(yv[mt][ks][4], yv[mt][ks][5], yv[mt][ks][6], yv[mt][ks][7]));
+          }
+        }
+        float s = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+          for (int e = 0; e < 8; ++e) s += yv[mt][ks][e];
+        s += __shfl_xor(s, 16, 64);
+        s += __shfl_xor(s, 32, 64);
+        const float mean = s * (1.0f / F);
+        float d = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            const float c = yv[mt][ks][e] - mean;
+            d = fmaf(c, c, d);
+          }
+        d += __shfl_xor(d, 16, 64);
+        d += __shfl_xor(d, 32, 64);
+        const float rstd = valid ? 1.0f / sqrtf(d * (1.0f / F) + a.eps) : 0.f;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+          bf16x8 h, l;
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            const float xn = (yv[mt][ks][e] - mean) * rstd;
+            const __bf16 hh = (__bf16)xn;
+            h[e] = hh;
+            l[e] = (__bf16)(xn - (float)hh);
+          }
+          xh[mt][ks] = h;
+          xl[mt][ks] = l;
+        }
+      }
+    }
     f32x4 acc[FT][MT];
 #pragma unroll
     for (int ft = 0; ft < FT; ++ft)
@@ -682,7 +821,7 @@ __global__ __launch_bounds__(64 * NW, (LAT > 0 || F > 128 || MT > 2) ? (NW > 4 ?
         //  could buy; & 256 = the re-read comes from a COLD address range (the output tensor of the launch) instead of the rows the tile loaded
         //  ~20 us earlier - if that costs nothing either, the re-read is off the critical path wherever it is served from)
         xr[p] = (PLAIN || (SEPR_GF3_RESX && !TRAIN) || (SEPR_GF_ABL & 128)) ? zero4()
-                : ld4(((SEPR_GF_ABL & 256) ? a.y : a.x) + (long long)(ok ? m : 0) * F + 4 * q4);
+                : ld4(((SEPR_GF_ABL & 256) ? a.y : (GATE ? a.mid : a.x)) + (long long)(ok ? m : 0) * F + 4 * q4);
       }
       if (w / WPP == half) {
         float* base = Os + (w % WPP) * (16 * MT) * OS;
@@ -738,6 +877,15 @@ __global__ __launch_bounds__(64 * NW, (LAT > 0 || F > 128 || MT > 2) ? (NW > 4 ?
       }
     }
   }
+}
+
+template <int F, int MT, int NW, int MODE = 0, bool TRAIN = false, bool ONE = false, int LAT = 0>
+__global__ __launch_bounds__(64 * NW, (LAT > 0 || F > 128 || MT > 2) ? (NW > 4 ? 2 : 1) : (2 * NW) / 4) void gcfn_fused3_kernel(const GcfnFusedArgs a) {
+  gcfn_fused3_body<F, MT, NW, MODE, TRAIN, ONE, LAT, false>(a);
+}
+// the large Base inference launch with the EGA gate in the tile prologue (a kernel of its own name: the plain instantiations keep theirs)
+__global__ __launch_bounds__(256, 2) void gcfn_gate_fused3_kernel(const GcfnFusedArgs a) {
+  gcfn_fused3_body<128, 2, 4, 0, false, false, 0, true>(a);
 }
 
 
@@ -1236,6 +1384,25 @@ int launch_glumlp_fold(const GcfnFusedArgs& a_in, int F, int site, hipStream_t s
   return SEPR_OK;
 }
 
+// Small launches (fewer 120-frame tiles than workgroup slots, e.g. batch 1 or the bottleneck stage) take the
+// 14-frame-wave instantiation: 1.4x more, shorter tiles.  A frame's arithmetic does not depend on the tiling, so the
+// result is bit-identical; for large launches the 30-frame form is 1.7x faster per frame (weight re-use).
+static int gf_small_rows() {
+  static const int v = [] {
+    const char* e = getenv("SEPR_GF_SMALL_ROWS");
+    return e && e[0] ? atoi(e) : 17000;
+  }();
+  return v;
+}
+
+bool gcfn_fused_takes_gate(int M, int F) {
+  static const int big_ring = [] {
+    const char* e = getenv("SEPR_GF_BIG_RING");
+    return e && e[0] ? atoi(e) : 0;
+  }();
+  return F == 128 && GF3_MT == 2 && SEPR_GF3_XCH && SEPR_GF3_UPFIRST && !big_ring && M >= gf_small_rows();
+}
+
 int launch_gcfn_fused(const GcfnFusedArgs& a_in, int F, int site, hipStream_t stream) {
   if (a_in.M <= 0) return SEPR_OK;
   static const int stagger = [] {
@@ -1250,7 +1417,7 @@ int launch_gcfn_fused(const GcfnFusedArgs& a_in, int F, int site, hipStream_t st
     // Large (round 6): the row-stationary form at F = 256 needs 128 registers of frame planes + 128 of down-projection accumulators per
     // wave - it exists in the ONE-wave-per-SIMD regime (512 registers per wave: four 30-frame waves, one 106 KB workgroup per CU), which the
     // inline-asm weight copies make viable (they fly under the multiplies instead of being waited for).  Inference only.
-    if (a.train) return SEPR_EINVAL;
+    if (a.train || a.gate_wp) return SEPR_EINVAL;
     long long slot256 = -1;
     const bool timed256 = prof_begin(site, stream, &slot256);
     const int cus = lat_max_tiles();
@@ -1263,13 +1430,9 @@ int launch_gcfn_fused(const GcfnFusedArgs& a_in, int F, int site, hipStream_t st
   if (a.planes == 1 && !a.train) return SEPR_EINVAL;   // plain bf16 operands: a training arithmetic only
   long long slot = -1;
   const bool timed = prof_begin(site, stream, &slot);
-  // Small launches (fewer 120-frame tiles than workgroup slots, e.g. batch 1 or the bottleneck stage) take the
-  // 14-frame-wave instantiation: 1.4x more, shorter tiles.  A frame's arithmetic does not depend on the tiling, so the
-  // result is bit-identical; for large launches the 30-frame form is 1.7x faster per frame (weight re-use).
-  static const int small_rows = [] {
-    const char* e = getenv("SEPR_GF_SMALL_ROWS");
-    return e && e[0] ? atoi(e) : 17000;
-  }();
+  if (a.gate_wp && (a.train || !gcfn_fused_takes_gate(a.M, F) || !a.att || !a.mid || a.mid == a.y || a.mid == a.x || a.Tp <= 0 || a.fac <= 0 || a.T != a.Tp * a.fac))
+    return SEPR_EINVAL;   // the caller asks first (gcfn_fused_takes_gate): no silent plain launch of half a block
+  const int small_rows = gf_small_rows();
   if (GF3_MT == 2 && a.M < small_rows) {
     constexpr int tile_rows = 6 * 14;
     const int ntiles = (a.M + tile_rows - 1) / tile_rows;
@@ -1332,6 +1495,12 @@ int launch_gcfn_fused(const GcfnFusedArgs& a_in, int F, int site, hipStream_t st
       } else if (a.train) {
         if (F == 128) hipLaunchKernelGGL((gcfn_fused3_kernel<128, GF3_MT, GF3_NW, 0, true>), dim3(grid), dim3(64 * GF3_NW), 0, stream, a);
         else hipLaunchKernelGGL((gcfn_fused3_kernel<64, GF3_MT, GF3_NW, 0, true>), dim3(grid), dim3(64 * GF3_NW), 0, stream, a);
+      } else if (F == 128 && a.gate_wp) {
+#if SEPR_GF3_MT == 2
+        hipLaunchKernelGGL(gcfn_gate_fused3_kernel, dim3(grid), dim3(256), 0, stream, a);
+#else
+        return SEPR_EINVAL;
+#endif
       } else if (F == 128) {
         hipLaunchKernelGGL((gcfn_fused3_kernel<128, GF3_MT, GF3_NW>), dim3(grid), dim3(64 * GF3_NW), 0, stream, a);
       } else if (F == 64) {
@@ -1342,7 +1511,7 @@ int launch_gcfn_fused(const GcfnFusedArgs& a_in, int F, int site, hipStream_t st
     }
   }
   // algorithmic FLOPs of the block: both projections + the depthwise conv
-  if (timed) prof_end(slot, (double)a.M * (2.0 * F * 6 * F + 2.0 * 3 * 6 * F + 2.0 * 3 * F * F), stream);
+  if (timed) prof_end(slot, (double)a.M * (2.0 * F * 6 * F + 2.0 * 3 * 6 * F + 2.0 * 3 * F * F + (a.gate_wp ? 2.0 * F * F : 0.0)), stream);
   SEPR_CHECK_LAUNCH("gcfn_fused_kernel");
   return SEPR_OK;
 }

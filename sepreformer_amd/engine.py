@@ -163,8 +163,14 @@ class SeparatorEngine:
         return y
 
     def global_block(self, x, gw, n, T, Tp, xs=None):       # reference modules/network.py:198-209
+        if not self.chain_stats:
+            # one entry for the pair: the library runs the EGA gate inside the GCFN kernel where that form exists (SEPR_GB_FUSE=0: never)
+            h, y = torch.empty_like(x), torch.empty_like(x)
+            L.check(self.lib.sepr_global_block_fwd(x.data_ptr(), h.data_ptr(), y.data_ptr(), n, T, Tp, self.cfg.feat, self.cfg.heads,
+                                                   C.byref(gw[0]), C.byref(gw[1]), gw[2] or None, *self._wsargs, self._st), "sepr_global_block_fwd")
+            return y
         h = self.ega(x, gw[0], n, T, Tp, xs)
-        return self.gcfn(h, gw[1], n, T, self._ys if self.chain_stats else None)
+        return self.gcfn(h, gw[1], n, T, self._ys)
 
     def local_block(self, x, lw, n, T, xs=None):            # reference modules/network.py:220-224
         h = self.cla(x, lw[0], n, T, xs)

@@ -133,6 +133,16 @@ class Packed:
         self.keep.append(wp)
         return {"fused_gate_p": wp.data_ptr()}
 
+    def gate_perm(self, sd, p: str) -> int:
+        """The gate projection in the fused GCFN kernel's row order (``sepr_global_block_fwd``; bf16x3, F = 128), 0 where it does not apply."""
+        F = sd[p + ".block.linear.0.weight"].shape[0]
+        if self.precision != "bf16x3" or F != 128 or not self.fuse_gate or not self.fuse_gcfn:
+            return 0
+        wp = pack_gate_fused_perm(sd[p + ".block.linear.1.weight"], sd[p + ".block.linear.1.bias"],
+                                  sd[p + ".block.linear.0.weight"], sd[p + ".block.linear.0.bias"])
+        self.keep.append(wp)
+        return wp.data_ptr()
+
     def qkv_fused(self, sd, p: str) -> dict:
         """EGA attention in-projection ``[3F, F]`` behind its LayerNorm in the gate's chunk form (bf16x3, F = 128): pooling + LayerNorm +
         q / k / v in one launch (``launch_ega_qkv``).  ``SEPR_FUSE_QKV=0`` keeps pool_stats + the generic projection."""
@@ -355,6 +365,25 @@ def pack_gate_fused(w: torch.Tensor, b: torch.Tensor, gamma: torch.Tensor, beta:
     return torch.stack([_chunk_frags(wf, bf, [64 * c + 16 * j for j in range(4)]) for c in range(w.shape[0] // 64)], 0).contiguous()
 
 
+def gate_perm_rows(F: int) -> torch.Tensor:
+    """Row order of ``pack_gate_fused_perm``: row ``4q + r`` of 16-row tile ``pt`` is output channel ``32*(pt // 2) + 8q + 4*(pt % 2) + r`` - the
+    8 channels lane group ``q`` of a frame fragment holds at K step ``pt // 2`` (``gcfn_fused3_kernel``'s loader) split over a tile pair."""
+    pt = torch.arange(F // 16)[:, None, None]
+    q = torch.arange(4)[None, :, None]
+    r = torch.arange(4)[None, None, :]
+    return (32 * (pt // 2) + 8 * q + 4 * (pt % 2) + r).reshape(-1)
+
+
+def pack_gate_fused_perm(w: torch.Tensor, b: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor) -> torch.Tensor:
+    """``pack_gate_fused`` with the output rows in ``gate_perm_rows`` order, for the gate prologue of the fused GCFN kernel: a lane's gate
+    accumulators are then the channels it holds of the frame.  Same folded fp32 rows, same bf16 split - only their position changes."""
+    wf = (w.detach().double() * gamma.detach().double()[None, :]).float()
+    bf = (b.detach().double() + w.detach().double() @ beta.detach().double()).float()
+    rows = gate_perm_rows(w.shape[0]).to(w.device)
+    wf, bf = wf[rows], bf[rows]
+    return torch.stack([_chunk_frags(wf, bf, [64 * c + 16 * j for j in range(4)]) for c in range(w.shape[0] // 64)], 0).contiguous()
+
+
 def pack_cla_fused(w1: torch.Tensor, b1: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, w2: torch.Tensor,
                    b2: torch.Tensor, w3: torch.Tensor):
     """Weights of the fused CLA head / tail kernels (sepreformer_amd/csrc/sepr_cla_fused.hip).
@@ -518,7 +547,8 @@ class PackedModel(Packed):
             pe_planes = planes.data_ptr()
 
         def glob(p):
-            return pack_ega(self, sd, p + ".block.ega", pe, cfg.maxlen, pe_planes), pack_gcfn(self, sd, p + ".block.gcfn")
+            return (pack_ega(self, sd, p + ".block.ega", pe, cfg.maxlen, pe_planes), pack_gcfn(self, sd, p + ".block.gcfn"),
+                    self.gate_perm(sd, p + ".block.ega"))
 
         def loc(p):
             return pack_cla(self, sd, p + ".block.cla"), pack_gcfn(self, sd, p + ".block.gcfn")
