@@ -169,16 +169,7 @@ __global__ __launch_bounds__(256) void relattn_kernel(const float* __restrict__ 
 //     when V^T is read with the matching key-slot order, so PV is 3 MFMAs per 32 keys with no data movement.
 // K, V^T and the band are split into bf16 hi/lo planes once per 64-key tile while they are staged into LDS.
 // ---------------------------------------------------------------------------------------------------------------------
-#ifndef SEPR_AT_ABL
-#define SEPR_AT_ABL 0   // timing ablations of relattn_x3_kernel (WRONG results): 1 no relative-position product, 2 no exp,
-                       // 4 K / V / band staged once (first key tile only), 8 no PV product, 16 no q.k product
-#endif
-#ifndef SEPR_AT_MASKPASS
-#define SEPR_AT_MASKPASS 1   // key-bound mask as one wave-uniform pass (0: selects inside the score loop - rounds 1-4; 2: pass on every tile)
-#endif
-#ifndef SEPR_AT_NW
-#define SEPR_AT_NW 4         // 16-query waves per workgroup of the Base inference kernel (8: 128 queries per staged tile, round-5 experiment)
-#endif
+constexpr int AT_NW = 4;   // 16-query waves per workgroup: 64 queries share every staged K / V / band tile
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
@@ -198,7 +189,8 @@ __device__ __forceinline__ void split4(const float4 v, bf16x4& h, bf16x4& l) {
 // backward keeps of the probabilities - and applies inverted dropout to the probabilities that multiply V (network.py:121;
 // the softmax denominator sums the undropped ones); mask of element (row = (seq*H + h)*Tp + i, key j) = 16-bit half j & 1 of
 // sepr_drop_word(dkey, row, j >> 1) >= thr (sepr_train.h).
-template <int DK, bool TRAIN = false, bool BP = false, bool ONE = false, int NWV = 4>
+// NWV stays a template parameter (always AT_NW): it is part of the kernel's symbol name.
+template <int DK, bool TRAIN = false, bool BP = false, bool ONE = false, int NWV = AT_NW>
 __global__ __launch_bounds__(64 * NWV, DK == 16 ? 4 : 2) void relattn_x3_kernel(const float* __restrict__ QKV, float* __restrict__ O, int Tp, int F,
                                                         const float* __restrict__ pe, int maxlen, float inv_sqrt_dk,
                                                         float* __restrict__ lse = nullptr, unsigned thr = 0u, float dscale = 1.0f,
@@ -214,8 +206,8 @@ __global__ __launch_bounds__(64 * NWV, DK == 16 ? 4 : 2) void relattn_x3_kernel(
   constexpr bool bp = BP;
   DropKey dkey = {0u, 0u};
   if (TRAIN && thr) dkey = sepr_drop_key(seed, salt, 2u);
-  static_assert(NWV == 4 || NWV == 8, "waves (16-query slices) per workgroup");
-  constexpr int NT = 64 * NWV;        // NWV = 8: 128 queries share every staged K / V / band tile (SEPR_AT_NW, inference only)
+  static_assert(NWV == AT_NW, "waves (16-query slices) per workgroup");
+  constexpr int NT = 64 * NWV;
   constexpr int QB = 16 * NWV, KT = 64;
   constexpr int KSB = DK + 8;         // K / band row stride in bf16 (DK used + 8 pad; DK = 16: the pad is the zero half of K = 32)
   constexpr int OT = DK / 16;         // 16-row tiles of O^T
@@ -313,7 +305,7 @@ __global__ __launch_bounds__(64 * NWV, DK == 16 ? 4 : 2) void relattn_x3_kernel(
   for (int j0 = 0; j0 < Tp; j0 += KT) {
     __syncthreads();   // previous tile fully consumed
     // ---- registers -> LDS: K rows, V transposed and the band of the position table as bf16 hi / lo planes ----------
-    if (!(SEPR_AT_ABL & 4) || j0 == 0) {
+    {
       bf16x4 hh, ll;
 #pragma unroll
       for (int u = 0; u < NU; ++u) {
@@ -346,7 +338,7 @@ __global__ __launch_bounds__(64 * NWV, DK == 16 ? 4 : 2) void relattn_x3_kernel(
       }
     }
     __syncthreads();
-    if (j0 + KT < Tp && !(SEPR_AT_ABL & 4)) fetch(j0 + KT);   // the next tile's rows fly under this tile's arithmetic
+    if (j0 + KT < Tp) fetch(j0 + KT);   // the next tile's rows fly under this tile's arithmetic
 
     // ---- ONE online-softmax update per 64-key tile (round 4; one per 32 keys before): the scores of both 32-key pairs are formed
     //      first - two independent MFMA -> skew -> bias chains the scheduler can interleave - then one max / exchange / rescale
@@ -364,21 +356,17 @@ __global__ __launch_bounds__(64 * NWV, DK == 16 ? 4 : 2) void relattn_x3_kernel(
           const bf16x8 kh = *reinterpret_cast<const bf16x8*>(Kh + row * KSB + go);
           const bf16x8 kl = *reinterpret_cast<const bf16x8*>(Kl + row * KSB + go);
           f32x4 a = (f32x4){0.f, 0.f, 0.f, 0.f};
-          if (!(SEPR_AT_ABL & 16)) {
-            a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kh, qh, a, 0, 0, 0);
-            if constexpr (!ONE) {
-              a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kh, ql, a, 0, 0, 0);
-              a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kl, qh, a, 0, 0, 0);
-            }
-          } else {
-            a[0] = (float)kh[0] + (float)kl[1];
+          a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kh, qh, a, 0, 0, 0);
+          if constexpr (!ONE) {
+            a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kh, ql, a, 0, 0, 0);
+            a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kl, qh, a, 0, 0, 0);
           }
           sc[s] = a;
         }
         // relative-position term: P^T[b][query], band row of (query ql, key kl) is bb + b, b = ql - kl + 31
         const int bb = 16 * w - 32 * p + 32;
 #pragma unroll
-        for (int tb = 0; tb < ((SEPR_AT_ABL & 1) ? 0 : 3); ++tb) {
+        for (int tb = 0; tb < 3; ++tb) {
           const int row = bb + 16 * tb + (15 - ii);             // <= 126 except unused rows of the last tile; REVERSED inside the 16-row tile:
                                                                 // the lane's four results are then band rows in DESCENDING order (see the store)
           const int rc = row < NBAND ? row : NBAND - 1;
@@ -402,18 +390,17 @@ __global__ __launch_bounds__(64 * NWV, DK == 16 ? 4 : 2) void relattn_x3_kernel(
           const int b0 = ii + 31 - 16 * s - 4 * g;              // b of key 16 s + 4g + 0; r steps down
           float bias[4];
 #pragma unroll
-          for (int r = 0; r < 4; ++r) bias[r] = (SEPR_AT_ABL & 1) ? 0.f : psk[47 - b0 + r];  // unconditional: the reads issue back to back
+          for (int r = 0; r < 4; ++r) bias[r] = psk[47 - b0 + r];  // unconditional: the reads issue back to back
 #pragma unroll
           for (int r = 0; r < 4; ++r)
-            sv[p][s][r] = (SEPR_AT_MASKPASS || j0 + 32 * p + 16 * s + 4 * g + r < Tp) ? sc[s][r] + bias[r] : -1e30f;
+            sv[p][s][r] = sc[s][r] + bias[r];
         }
       }
-#if SEPR_AT_MASKPASS
       // only a tile that reaches past Tp pays the 16 key-bound selects: ONE wave-uniform pass (as selects inside the loop above they cost 48
       // VALU per tile and hipcc turned four of the bias reads into exec-masked blocks with their own LDS waits: 300 -> 212 VALU per full
       // tile).  Round 4 withdrew this form as "run-to-run nondeterministic, cause not established"; round 5 established it - not the pass
-      // but the packed bias add the compiler formed around it (see the mirrored store above).  2 = the pass on every tile (bisecting aid)
-      if (SEPR_AT_MASKPASS == 2 || j0 + KT > Tp) {
+      // but the packed bias add the compiler formed around it (see the mirrored store above).
+      if (j0 + KT > Tp) {
 #pragma unroll
         for (int p = 0; p < 2; ++p)
 #pragma unroll
@@ -422,7 +409,6 @@ __global__ __launch_bounds__(64 * NWV, DK == 16 ? 4 : 2) void relattn_x3_kernel(
             for (int r = 0; r < 4; ++r)
               if (j0 + 32 * p + 16 * s + 4 * g + r >= Tp) sv[p][s][r] = -1e30f;
       }
-#endif
       float mx = -1e30f;
 #pragma unroll
       for (int p = 0; p < 2; ++p)
@@ -441,7 +427,7 @@ __global__ __launch_bounds__(64 * NWV, DK == 16 ? 4 : 2) void relattn_x3_kernel(
         for (int s = 0; s < 2; ++s)
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const float pv = (SEPR_AT_ABL & 2) ? sv[p][s][r] - mnew : __expf(sv[p][s][r] - mnew);
+            const float pv = __expf(sv[p][s][r] - mnew);
             psum += pv;
             const __bf16 hh = (__bf16)pv;
             ph[p][4 * s + r] = hh;
@@ -476,10 +462,6 @@ __global__ __launch_bounds__(64 * NWV, DK == 16 ? 4 : 2) void relattn_x3_kernel(
           const bf16x4 b0v = *reinterpret_cast<const bf16x4*>(vl0), b1v = *reinterpret_cast<const bf16x4*>(vl0 + 16);
           const bf16x8 vh = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
           const bf16x8 vl = {b0v[0], b0v[1], b0v[2], b0v[3], b1v[0], b1v[1], b1v[2], b1v[3]};
-          if (SEPR_AT_ABL & 8) {
-            o[t][0] += (float)vh[0] * (float)ph[p][0] + (float)vl[1] * (float)pl[p][1];
-            continue;
-          }
           o[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vh, ph[p], o[t], 0, 0, 0);
           if constexpr (!ONE) {
             o[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vh, pl[p], o[t], 0, 0, 0);
@@ -530,13 +512,8 @@ int launch_relattn(const float* QKV, float* O, int n, int Tp, int F, int H, cons
   const float isd = 1.0f / sqrtf((float)dk);
   if (dk == 16 && x3) {
     if (pe_planes)
-#if SEPR_AT_NW == 8
-        hipLaunchKernelGGL((relattn_x3_kernel<16, false, true, false, 8>), dim3((Tp + 127) / 128, H, n), dim3(512), 0, s, QKV, O, Tp, F, pe_k, maxlen,
-                           isd, (float*)nullptr, 0u, 1.0f, 0ull, (const unsigned long long*)nullptr, static_cast<const unsigned short*>(pe_planes));
-#else
       hipLaunchKernelGGL((relattn_x3_kernel<16, false, true>), grid, dim3(256), 0, s, QKV, O, Tp, F, pe_k, maxlen, isd, (float*)nullptr, 0u, 1.0f, 0ull,
                          (const unsigned long long*)nullptr, static_cast<const unsigned short*>(pe_planes));
-#endif
     else
       hipLaunchKernelGGL((relattn_x3_kernel<16, false, false>), grid, dim3(256), 0, s, QKV, O, Tp, F, pe_k, maxlen, isd, (float*)nullptr, 0u, 1.0f,
                          0ull, (const unsigned long long*)nullptr, (const unsigned short*)nullptr);

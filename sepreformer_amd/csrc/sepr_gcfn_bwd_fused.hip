@@ -52,63 +52,10 @@ __device__ __forceinline__ void gb_wait_vm2(gb_u32x4& a, gb_u32x4& b) {
   asm volatile("s_waitcnt vmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N) : "memory");
 }
 
-#ifndef SEPR_GB_PL_WGS
-#define SEPR_GB_PL_WGS 3   // workgroups per CU the plane-staged (PL) middle kernel is compiled and launched for
-#endif
-#ifndef SEPR_GB_REGEPI
-#define SEPR_GB_REGEPI 0   // 0 (product): the row-window epilogue of gcfn_bwd_mid_kernel through LDS tiles (rounds 2-5); 1: in registers (round 6, second session:
-                           // built, bit-identical outputs, measured equal at two workgroups per CU and slower at three - hipcc spills 50-60 registers into
-                           // the 168 of the three-workgroup regime; tools/variants.mk gbepi2w / gbepi3w, profiles/r06_gcfn_bwd_regepi.txt)
-#endif
-#ifndef SEPR_GB_ONEBAR
-#define SEPR_GB_ONEBAR 0   // PL form: 0 = a counted wait + barrier in front of every slab's MFMAs (slab q multiplies while slabs q+1.. land); 1 = ONE wait for all
-                           // the tile's slabs and one barrier in front of step 0, steps >= 1 wait for their own weight fragments only (round 6, last session:
-                           // tools/variants.mk gbonebar)
-#endif
-#ifndef SEPR_GB_TOPWAIT
-#define SEPR_GB_TOPWAIT 0
-#endif
-#ifndef SEPR_GB_CONSTLDS
-#define SEPR_GB_CONSTLDS 1  // PL form, persistent launches in which a workgroup keeps ONE column block (acc_part): the block's depthwise taps / biases (8 float4 per
-                           // column quad) and up-projection biases (2 x 64) are parked in 2.5 KB of LDS once per workgroup instead of being fetched from L2 by every
-                           // tile right in front of their use (two exposed L2 latencies per tile); 53 760 B per workgroup, still three per CU
-#endif
-#ifndef SEPR_GB_REDERIVE
-#define SEPR_GB_REDERIVE 3   // product: bit 1 the plane-staged form, bit 2 the register-staged forms too (0 = rounds 4-6: 168 registers + 10 spilled / 256 + 9-13; profiles/r06_gcfn_bwd_waits.txt)
-#endif
-#ifndef SEPR_GB_SLIDE
-#define SEPR_GB_SLIDE 2     // (bit mask: 1 = pass A, 2 = pass B) LDS epilogue, interior tiles: a thread's 4 consecutive rows share their conv windows - pass A reads each h1 row of its 6-row window once
-                           // (12 ds_read_b128 instead of 24), pass B takes the neighbour rows of dc from its own registers (4 reads instead of 16); bit-identical
-#endif
-constexpr int GB_CONST_B = SEPR_GB_CONSTLDS ? (8 * 16 + 32) * 16 : 0;
-// slab row s = mt * 16 + fi of the middle kernel holds frame 4 fi + mt of the tile (REGEPI) - so that frame neighbours are a lane's own
-// accumulator tiles or one DPP row shift away - or frame s (LDS epilogue)
-__device__ __forceinline__ int gb_frame(int s) { return SEPR_GB_REGEPI ? 4 * (s & 15) + (s >> 4) : s; }
-// DPP row shifts (16-lane rows): lane i <- lane i - 1 / i + 1; the lane without a source gets 0
-__device__ __forceinline__ float gb_shr1(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x111, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float gb_shl1(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x101, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float2 ld2g(const float* p) { return *reinterpret_cast<const float2*>(p); }
-// two fp32 -> one bf16x2 word (round to nearest even, the conversion gb_store4 applies): low half = a
-__device__ __forceinline__ unsigned gb_pack2(float a, float b) {
-  typedef __bf16 gb_bf16x2 __attribute__((ext_vector_type(2)));
-  const gb_bf16x2 h = {(__bf16)a, (__bf16)b};
-  return __builtin_bit_cast(unsigned, h);
-}
-__device__ __forceinline__ float4 gb_shr4(float4 v) { return make_float4(gb_shr1(v.x), gb_shr1(v.y), gb_shr1(v.z), gb_shr1(v.w)); }
-__device__ __forceinline__ float4 gb_shl4(float4 v) { return make_float4(gb_shl1(v.x), gb_shl1(v.y), gb_shl1(v.z), gb_shl1(v.w)); }
-// inclusive scan over the 16 lanes of a DPP row (row_shr 1, 2, 4, 8; lanes shifted in from outside the row add 0): lane 15 holds the row's sum
-__device__ __forceinline__ float gb_row_total(float v) {
-#pragma clang fp contract(off)
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x111, 0xf, 0xf, false));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x112, 0xf, 0xf, false));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x114, 0xf, 0xf, false));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x118, 0xf, 0xf, false));
-  return v;
-}
+// PL form, persistent launches in which a workgroup keeps ONE column block (acc_part): the block's depthwise taps / biases (8 float4 per column quad)
+// and up-projection biases (2 x 64) are parked in 2.5 KB of LDS once per workgroup instead of being fetched from L2 by every tile right in front of
+// their use (two exposed L2 latencies per tile); 53 760 B per workgroup, still three per CU
+constexpr int GB_CONST_B = (8 * 16 + 32) * 16;
 
 namespace {
 template <bool V>
@@ -141,15 +88,14 @@ constexpr int gb_pl_outstanding(int q, int nsl, int dma) {
 constexpr int GB_BM = 64;            // rows per tile (incl. halo)
 constexpr int GB_OUT = GB_BM - 4;    // rows a tile outputs
 constexpr int GB_BKS = 64;           // K extent of one LDS slab
-#ifndef SEPR_GB_LDK_PAD
-#define SEPR_GB_LDK_PAD 16
-#endif
-constexpr int GB_LDK = GB_BKS + SEPR_GB_LDK_PAD;  // bf16 per LDS row (160 B; 144 B with pad 8)
+constexpr int GB_LDK_PAD = 16;       // 160-byte LDS rows (144-byte rows measured no different: profiles/r03_v5_pmc_train_kernels.txt)
+constexpr int GB_LDK = GB_BKS + GB_LDK_PAD;  // bf16 per LDS row
 constexpr int GB_HS = 128 + 4;       // fp32 row stride of the h1 / dc tile (64 value + 64 gate columns)
 constexpr int GB_DS = 64 + 4;        // fp32 row stride of the dgd tile
 constexpr int GB_RS = 36;            // fp32 row stride of the depthwise-partial scratch [4 waves][16 column quads][32 sums] that reuses the dgd tile
 static_assert(4 * 16 * GB_RS <= GB_BM * GB_DS, "the reduction scratch must fit the dgd tile");
 constexpr int GB_THREADS = 256;
+constexpr int GB_PL_WGS = 3;         // workgroups per CU the plane-staged (PL) middle kernel is compiled and launched for (51 KB of LDS, 168 VGPRs each)
 
 struct GcfnBwdArgs {
   const float* x;       // [M][F] block input
@@ -194,29 +140,24 @@ struct GcfnBwdArgs {
 // tile-ahead prefetch: the kernel fits three workgroups per CU (51 KB of LDS each), which cover the DMA latency a tile now pays at its
 // start (the slab buffers alias the epilogue tiles, so the next tile's slabs cannot fly under the epilogue).
 template <int PLANES, int NSL, bool PL = false>
-__global__ __launch_bounds__(GB_THREADS, PL ? SEPR_GB_PL_WGS : 2) void gcfn_bwd_mid_kernel(const GcfnBwdArgs a) {
+__global__ __launch_bounds__(GB_THREADS, PL ? GB_PL_WGS : 2) void gcfn_bwd_mid_kernel(const GcfnBwdArgs a) {
   constexpr bool ONE = PLANES == 1;
   static_assert(!PL || ONE, "plane staging exists for the plain-bf16 arithmetic");
   constexpr int NP = ONE ? 1 : 2;                              // bf16 planes per LDS buffer
   constexpr int PLANE_E = GB_BM * GB_LDK;                      // elements of one plane
   constexpr int DMA_PER_WAVE = GB_BM * 128 / 1024 / 4;                  // PL: LDS-DMA instructions per wave and slab (2)
   constexpr size_t SLAB_B = PL ? (size_t)2 * NSL * GB_BM * 128 : sizeof(unsigned short) * 2 * NP * PLANE_E;
-  // (the LDS epilogue's tiles, or the register epilogue's 6 parked 16-byte chunks per thread, alias the slab buffers)
-  constexpr size_t TILE_B = SEPR_GB_REGEPI ? (size_t)6 * GB_THREADS * 16 : sizeof(float) * GB_BM * (GB_HS + GB_DS);
+  // (the epilogue's tiles alias the slab buffers)
+  constexpr size_t TILE_B = sizeof(float) * GB_BM * (GB_HS + GB_DS);
   constexpr size_t MAIN_B = SLAB_B > TILE_B ? SLAB_B : TILE_B;
   __shared__ __attribute__((aligned(16))) unsigned char smem[MAIN_B + (PL ? GB_CONST_B : 0)];
-  [[maybe_unused]] float* const Cs = reinterpret_cast<float*>(smem + MAIN_B);   // CONSTLDS: [8 taps / biases][16 column quads][4], then [value | gate][16 quads][4] of b1
+  [[maybe_unused]] float* const Cs = reinterpret_cast<float*>(smem + MAIN_B);   // GB_CONST_B: [8 taps / biases][16 column quads][4], then [value | gate][16 quads][4] of b1
   unsigned short* const slab = reinterpret_cast<unsigned short*>(smem);
   [[maybe_unused]] float* const Hs = reinterpret_cast<float*>(smem);            // [64][GB_HS]: h1 (+ b1), later dc   (aliases the slab buffers)
   [[maybe_unused]] float* const Ds = Hs + GB_BM * GB_HS;                        // [64][GB_DS]: dgd, later the reduction scratch
 
-#if SEPR_GB_REDERIVE
-  int tid = threadIdx.x, lane = tid & 63, wn = tid >> 6;      // re-derived at the top of every tile (see SEPR_GB_REDERIVE)
+  int tid = threadIdx.x, lane = tid & 63, wn = tid >> 6;      // not const: re-derived at the top of every tile
   int fi = lane & 15, fg = lane >> 4;
-#else
-  const int tid = threadIdx.x, lane = tid & 63, wn = tid >> 6;
-  const int fi = lane & 15, fg = lane >> 4;
-#endif
   const int F = a.F, C3 = 3 * F;
   const int NB = C3 / 64;
   const int MB = (a.M + GB_OUT - 1) / GB_OUT;
@@ -258,7 +199,7 @@ __global__ __launch_bounds__(GB_THREADS, PL ? SEPR_GB_PL_WGS : 2) void gcfn_bwd_
 #pragma unroll
       for (int i = 0; i < DMA_PER_WAVE; ++i) {
         const int pos = (wn * DMA_PER_WAVE + i) * 64 + lane, row = pos >> 3, c = (pos & 7) ^ (row & 7);
-        int msn = mb_ * GB_OUT - 2 + gb_frame(row);
+        int msn = mb_ * GB_OUT - 2 + row;
         msn = msn < 0 ? 0 : (msn > a.M - 1 ? a.M - 1 : msn);
         const unsigned off = (unsigned)msn * (unsigned)(2 * F) + (unsigned)(c * 16);     // M * F * 2 < 2^32 (checked by the launcher)
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(plane + off),
@@ -268,7 +209,7 @@ __global__ __launch_bounds__(GB_THREADS, PL ? SEPR_GB_PL_WGS : 2) void gcfn_bwd_
   };
   auto load_tile = [&](int mb_) {
     if constexpr (PL) return;
-    const int msn = mb_ * GB_OUT - 2 + gb_frame(srow);
+    const int msn = mb_ * GB_OUT - 2 + srow;
     const long long row = (msn >= 0 && msn < a.M) ? msn : 0;
     const float* px = a.x + row * F + kq;
     const float* pd = a.dy + row * F + kq;
@@ -284,8 +225,8 @@ __global__ __launch_bounds__(GB_THREADS, PL ? SEPR_GB_PL_WGS : 2) void gcfn_bwd_
   int tile = blockIdx.x, mb = 0, nb = 0;
   while (tile < ntiles && !decode(tile, mb, nb)) tile += gridDim.x;
   if (tile < ntiles) load_tile(mb);
-  [[maybe_unused]] const bool cl_on = SEPR_GB_CONSTLDS && PL && a.acc_part != 0;    // (acc_part: nb is the same for every tile of this workgroup)
-  if constexpr (SEPR_GB_CONSTLDS && PL) {
+  [[maybe_unused]] const bool cl_on = PL && a.acc_part != 0;    // (acc_part: nb is the same for every tile of this workgroup)
+  if constexpr (PL) {
     if (cl_on && tile < ntiles) {
       const int C3_ = 3 * a.F, C6_ = 6 * a.F;
       if (tid < 128) {
@@ -300,21 +241,16 @@ __global__ __launch_bounds__(GB_THREADS, PL ? SEPR_GB_PL_WGS : 2) void gcfn_bwd_
       // (visible to every wave behind the first tile's barriers)
     }
   }
-#if SEPR_GB_TOPWAIT == 2
-  if constexpr (PL) __builtin_amdgcn_s_waitcnt(0x0F70);       // (experiment: the wait once, in front of the tile loop)
-#endif
   [[maybe_unused]] float wacc[2] = {0.f, 0.f};                 // acc_part: this thread's two of the workgroup's 512 partial sums
   [[maybe_unused]] const int mb_first = mb, nb_first = nb;
   [[maybe_unused]] const bool any_tile = tile < ntiles;
   while (tile < ntiles) {
-#if SEPR_GB_REDERIVE
-    if constexpr (PL || (SEPR_GB_REDERIVE & 2) != 0) {         // an opaque copy of the thread index: everything derived from it (LDS addresses, lane roles) is recomputed
-      asm volatile("" : "+v"(tid));                            // per tile instead of being hoisted out of the loop and kept (or spilled) across all of its phases
-      lane = tid & 63; wn = tid >> 6; fi = lane & 15; fg = lane >> 4;
-    }
-#endif
+    // an opaque copy of the thread index: everything derived from it (LDS addresses, lane roles) is recomputed per tile instead of being hoisted out of
+    // the loop and kept (or spilled) across all of its phases (hoisted: 168 registers + 10 spilled / 256 + 9-13; profiles/r06_gcfn_bwd_waits.txt)
+    asm volatile("" : "+v"(tid));
+    lane = tid & 63; wn = tid >> 6; fi = lane & 15; fg = lane >> 4;
     const int m0 = mb * GB_OUT;
-    const int sfr = gb_frame(srow);                            // frame (of the tile) in slab row srow
+    const int sfr = srow;                            // frame (of the tile) in slab row srow
     const int ms = m0 - 2 + sfr;                               // the row this thread stages
     const bool svalid = ms >= 0 && ms < a.M;
     const float mean = rst.x, rstd = rst.y;
@@ -383,9 +319,6 @@ __global__ __launch_bounds__(GB_THREADS, PL ? SEPR_GB_PL_WGS : 2) void gcfn_bwd_
     }
     const int tv = 4 * nb + wn, tg = C3 / 16 + 4 * nb + wn;     // this wave's value / gate tile of W1, tv also its W2^T tile
 
-#if SEPR_GB_TOPWAIT == 1
-    if constexpr (PL) __builtin_amdgcn_s_waitcnt(0x0F70);     // vmcnt(0), a wait hipcc's own bookkeeping sees (see SEPR_GB_TOPWAIT above)
-#endif
     __syncthreads();   // the previous tile's epilogue is done with the LDS tiles that alias the slab buffers
     gb_u32x4 wset[2][2][2][2];                                 // [q & 1][a | b][K step of the slab][plane]; a: value (or W2^T), b: gate
     auto load_wq = [&](int q, gb_u32x4 (&ws_)[2][2][2]) {
@@ -422,31 +355,6 @@ __global__ __launch_bounds__(GB_THREADS, PL ? SEPR_GB_PL_WGS : 2) void gcfn_bwd_
         static_assert(NQ < 2 || C1 == gb_pl_outstanding(1, NSL, DMA_PER_WAVE), "vmcnt of step 1 does not match the issue order");
         static_assert(NQ < 3 || C2 == gb_pl_outstanding(2, NSL, DMA_PER_WAVE), "vmcnt of step 2 does not match the issue order");
         static_assert(NQ < 4 || gb_pl_outstanding(3, NSL, DMA_PER_WAVE) == 0, "steps >= 3 wait vmcnt(0): nothing may be issued behind W3");
-        if constexpr (SEPR_GB_ONEBAR) {
-          // every copy and both prologue fragment sets were issued before step 0: one vmcnt(0) covers D0 .. D(NQ-1), W0, W1.  Steps q >= 2 wait for
-          // W(q) with W(q+1) - issued behind step q-1's MFMAs - still in flight.
-          if (q == 0) {
-            gb_wait_vm4<0>(wset[0][0][0][0], wset[0][0][1][0], wset[0][1][0][0], wset[0][1][1][0]);
-            if constexpr (NQ > 1) {
-              if constexpr (1 < NSL) gb_wait_vm4<0>(wset[1][0][0][0], wset[1][0][1][0], wset[1][1][0][0], wset[1][1][1][0]);
-              else gb_wait_vm2<0>(wset[1][0][0][0], wset[1][0][1][0]);
-            }
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-          } else if (q >= 2) {
-            constexpr int NXT4 = 4, NXT2 = 2;
-            const bool more = q + 1 < NQ, more_up = q + 1 < NSL;
-            if (up) {
-              if (more && more_up) gb_wait_vm4<NXT4>(wa[0][0], wa[1][0], wb[0][0], wb[1][0]);
-              else if (more) gb_wait_vm4<NXT2>(wa[0][0], wa[1][0], wb[0][0], wb[1][0]);
-              else gb_wait_vm4<0>(wa[0][0], wa[1][0], wb[0][0], wb[1][0]);
-            } else {
-              if (more && more_up) gb_wait_vm2<NXT4>(wa[0][0], wa[1][0]);
-              else if (more) gb_wait_vm2<NXT2>(wa[0][0], wa[1][0]);
-              else gb_wait_vm2<0>(wa[0][0], wa[1][0]);
-            }
-          }
-        } else {
         if (up) {
           if (q == 0) gb_wait_vm4<C0>(wa[0][0], wa[1][0], wb[0][0], wb[1][0]);
           else if (q == 1) gb_wait_vm4<C1>(wa[0][0], wa[1][0], wb[0][0], wb[1][0]);
@@ -462,7 +370,6 @@ __global__ __launch_bounds__(GB_THREADS, PL ? SEPR_GB_PL_WGS : 2) void gcfn_bwd_
         // slabs with it).  What the barrier must order is exactly what the counted wait above covers: this wave's share of slab q.
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-        }
       } else {
         load_wq(q, wset[q & 1]);
         store_slab(q);
@@ -516,188 +423,6 @@ __global__ __launch_bounds__(GB_THREADS, PL ? SEPR_GB_PL_WGS : 2) void gcfn_bwd_
         if (q + 2 < 2 * nsl) load_wq(q + 2, wset[q & 1]);      // this step's fragment registers are free again
       }
     }
-#if SEPR_GB_REGEPI
-    // ---- epilogue in registers (round 6) -------------------------------------------------------------------------------------------
-    // The accumulators already hold what the row window needs: lane (fi, fg) of wave wn has, per slab-row tile mt, the 4 hidden channels
-    // 64 nb + 16 wn + 4 fg + r of ONE frame - value, gate and dgd.  With slab row mt * 16 + fi holding frame 4 fi + mt (the copy's row map,
-    // gb_frame), the previous / next frame of a lane's tile mt is its own tile mt -+ 1; across the 4-frame seams it is the neighbouring lane's
-    // tile 3 / tile 0 - ONE DPP row shift, and the two lanes without a neighbour (fi = 0 / 15) are the two halo frames at the tile's ends whose
-    // dc is never used.  So the h1 / dgd / dc tiles, their 5 barriers, ~260 KB of LDS traffic per tile and the 64 ds_bpermute of the partial
-    // sums are gone (rounds 2-5 form: -DSEPR_GB_REGEPI=0, tools/variants.mk gbepi0); the depthwise partial sums reduce over the 16 frame lanes of
-    // a DPP row (each wave owns its own 16 channel pairs: no cross-wave step).  Element arithmetic unchanged (same fmaf order as the LDS form).
-    // Register diet (the plane-staged kernel has 168 per lane at three workgroups per CU): the 4 channels of a lane are walked as two PAIRS -
-    // taps, dc values and partial sums of one pair live at a time (a pair is also one dropout word and one packed bf16x2 output register).
-    // the next tile of this workgroup (register-staged forms: its activation slabs go in flight now, under the epilogue below)
-    // The second channel pair's inputs wait in LDS - the slab buffers are dead once every wave has left the MFMA phase; each lane parks and
-    // later re-reads ITS OWN 24 values (6 conflict-free 16-byte chunks, chunk j of thread t at (256 j + t) x 16 B): no exchange, no further barrier
-    __syncthreads();
-    {
-      float4* const pk = reinterpret_cast<float4*>(smem) + tid;
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) pk[256 * mt] = make_float4(hv[mt][2], hv[mt][3], hg[mt][2], hg[mt][3]);
-      pk[256 * 4] = make_float4(dd[0][2], dd[0][3], dd[1][2], dd[1][3]);
-      pk[256 * 5] = make_float4(dd[2][2], dd[2][3], dd[3][2], dd[3][3]);
-    }
-    int nxt = tile + gridDim.x, mb_n = 0, nb_n = 0;
-    while (nxt < ntiles && !decode(nxt, mb_n, nb_n)) nxt += gridDim.x;
-    if (nxt < ntiles) load_tile(mb_n);
-    const int cl = wn * 16 + 4 * fg, hc = 64 * nb + cl;          // hidden value channel of accumulator element 0 (gate: C3 + hc)
-    const int C6 = 2 * C3;
-    const int lo_t = (m0 >= 1) ? (m0 - 1) % a.T : 0;
-    const bool edge_tile = !(m0 >= 2 && lo_t >= 1 && lo_t + 62 <= a.T - 2 && m0 + GB_BM - 2 <= a.M);
-    constexpr bool as16 = ONE;            // (the launcher stores g / dh1 as bf16 exactly for the plain-bf16 arithmetic and checks it: out16 == ONE)
-    auto passes = [&](auto edge_c) {
-#pragma clang fp contract(off)
-      constexpr bool EDGE = decltype(edge_c)::value;
-      // outputs of the lane's 4 frames x 4 channels, held until both pairs are done (8- / 16-byte stores): bf16x2 words (as16) or floats
-      [[maybe_unused]] unsigned gP[4][2], ovP[4][2], ogP[4][2];
-      [[maybe_unused]] float gF[4][4], ovF[4][4], ogF[4][4];
-      float f0s[4], f2s[4];
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) {
-        f0s[mt] = 1.f;
-        f2s[mt] = 1.f;
-        if constexpr (EDGE) {                                  // zero padding at the sequence ends (tiles that touch one: ~1 in 130)
-          const int m = m0 - 2 + 4 * fi + mt, t = (m >= 0 ? m : 0) % a.T;
-          f0s[mt] = t > 0 ? 1.f : 0.f;
-          f2s[mt] = t < a.T - 1 ? 1.f : 0.f;
-        }
-      }
-#pragma unroll
-      for (int pr = 0; pr < 2; ++pr) {                          // channels hc + 2 pr, hc + 2 pr + 1
-        asm volatile("" ::: "memory");                         // (keeps the second pair's tap loads behind the first pair's work: registers)
-        __builtin_amdgcn_sched_barrier(0);
-        const int hp = hc + 2 * pr;
-        const float2 bv = ld2g(a.b1 + hp), bg = ld2g(a.b1 + C3 + hp);
-        const float2 wv0 = ld2g(a.dw_w + hp), wv1 = ld2g(a.dw_w + C6 + hp), wv2 = ld2g(a.dw_w + 2 * C6 + hp);
-        const float2 wg0 = ld2g(a.dw_w + C3 + hp), wg1 = ld2g(a.dw_w + C6 + C3 + hp), wg2 = ld2g(a.dw_w + 2 * C6 + C3 + hp);
-        const float2 cbv = ld2g(a.dw_b + hp), cbg = ld2g(a.dw_b + C3 + hp);
-        float Hv[4][2], Hg[4][2], Dd[4][2];
-        if (pr == 0) {
-#pragma unroll
-          for (int mt = 0; mt < 4; ++mt) {
-            Hv[mt][0] = hv[mt][0] + bv.x; Hv[mt][1] = hv[mt][1] + bv.y;
-            Hg[mt][0] = hg[mt][0] + bg.x; Hg[mt][1] = hg[mt][1] + bg.y;
-            Dd[mt][0] = dd[mt][0]; Dd[mt][1] = dd[mt][1];
-          }
-        } else {
-          const float4* const pk = reinterpret_cast<const float4*>(smem) + tid;
-#pragma unroll
-          for (int mt = 0; mt < 4; ++mt) {
-            const float4 q = pk[256 * mt];
-            Hv[mt][0] = q.x + bv.x; Hv[mt][1] = q.y + bv.y;
-            Hg[mt][0] = q.z + bg.x; Hg[mt][1] = q.w + bg.y;
-          }
-          const float4 q4 = pk[256 * 4], q5 = pk[256 * 5];
-          Dd[0][0] = q4.x; Dd[0][1] = q4.y; Dd[1][0] = q4.z; Dd[1][1] = q4.w;
-          Dd[2][0] = q5.x; Dd[2][1] = q5.y; Dd[3][0] = q5.z; Dd[3][1] = q5.w;
-        }
-        float dcv[4][2], dcg[4][2], acc[2][8];
-#pragma unroll
-        for (int e = 0; e < 2; ++e)
-#pragma unroll
-          for (int k = 0; k < 8; ++k) acc[e][k] = 0.f;
-        const float pv0[2] = {gb_shr1(Hv[3][0]), gb_shr1(Hv[3][1])}, pg0[2] = {gb_shr1(Hg[3][0]), gb_shr1(Hg[3][1])};   // frame 4 fi - 1
-        const float nv3[2] = {gb_shl1(Hv[0][0]), gb_shl1(Hv[0][1])}, ng3[2] = {gb_shl1(Hg[0][0]), gb_shl1(Hg[0][1])};   // frame 4 fi + 4
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) {
-          const int fo = 4 * fi + mt, m = m0 - 2 + fo;
-          const bool has_dc = fo >= 1 && fo <= GB_BM - 2 && m >= 0 && m < a.M;
-          const bool own = fo >= 2 && fo < 2 + GB_OUT && m < a.M;      // rows this tile outputs
-          float keep[2] = {1.f, 1.f};
-          if (drop) {                                          // network.py:55: mask of the gated tensor, element (m, hp + e)
-            const unsigned d0 = sepr_drop_word(dk0, (unsigned)m, (unsigned)(hp >> 1));
-            keep[0] = (d0 & 0xffffu) >= a.drop_thr ? a.drop_scale : 0.f;
-            keep[1] = (d0 >> 16) >= a.drop_thr ? a.drop_scale : 0.f;
-          }
-          float gd[2];
-#pragma unroll
-          for (int e = 0; e < 2; ++e) {
-            const float w0v = e ? wv0.y : wv0.x, w1v = e ? wv1.y : wv1.x, w2v = e ? wv2.y : wv2.x, cbvv = e ? cbv.y : cbv.x;
-            const float w0g = e ? wg0.y : wg0.x, w1g = e ? wg1.y : wg1.x, w2g = e ? wg2.y : wg2.x, cbgg = e ? cbg.y : cbg.x;
-            float hvm = mt > 0 ? Hv[mt > 0 ? mt - 1 : 0][e] : pv0[e], hgm = mt > 0 ? Hg[mt > 0 ? mt - 1 : 0][e] : pg0[e];
-            float hvp = mt < 3 ? Hv[mt < 3 ? mt + 1 : 3][e] : nv3[e], hgp = mt < 3 ? Hg[mt < 3 ? mt + 1 : 3][e] : ng3[e];
-            const float hvc = Hv[mt][e], hgc = Hg[mt][e];
-            if constexpr (EDGE) {
-              hvm *= f0s[mt]; hgm *= f0s[mt];
-              hvp *= f2s[mt]; hgp *= f2s[mt];
-            }
-            const float cv = fmaf(w2v, hvp, fmaf(w1v, hvc, fmaf(w0v, hvm, cbvv)));
-            const float cg = fmaf(w2g, hgp, fmaf(w1g, hgc, fmaf(w0g, hgm, cbgg)));
-            const float sg = sigmoid_f(cg);
-            gd[e] = cv * sg * keep[e];
-            const float d = Dd[mt][e] * keep[e];
-            const float dv_ = d * sg, dg_ = d * cv * sg * (1.f - sg);
-            dcv[mt][e] = has_dc ? dv_ : 0.f;
-            dcg[mt][e] = has_dc ? dg_ : 0.f;
-            if (own) {
-              acc[e][0] = fmaf(dv_, hvm, acc[e][0]); acc[e][1] = fmaf(dv_, hvc, acc[e][1]);
-              acc[e][2] = fmaf(dv_, hvp, acc[e][2]); acc[e][3] += dv_;
-              acc[e][4] = fmaf(dg_, hgm, acc[e][4]); acc[e][5] = fmaf(dg_, hgc, acc[e][5]);
-              acc[e][6] = fmaf(dg_, hgp, acc[e][6]); acc[e][7] += dg_;
-            }
-          }
-          if constexpr (as16) gP[mt][pr] = gb_pack2(gd[0], gd[1]);
-          else { gF[mt][2 * pr] = gd[0]; gF[mt][2 * pr + 1] = gd[1]; }
-          __builtin_amdgcn_sched_barrier(0);                   // (one frame at a time: hipcc otherwise interleaves all eight and spills)
-        }
-        // ---- transpose of the conv: dh[t] = w0 dc[t+1] + w1 dc[t] + w2 dc[t-1]   (frames of OTHER sequences do not contribute: f0 / f2) ----
-        const float qv0[2] = {gb_shr1(dcv[3][0]), gb_shr1(dcv[3][1])}, qg0[2] = {gb_shr1(dcg[3][0]), gb_shr1(dcg[3][1])};
-        const float rv3[2] = {gb_shl1(dcv[0][0]), gb_shl1(dcv[0][1])}, rg3[2] = {gb_shl1(dcg[0][0]), gb_shl1(dcg[0][1])};
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) {
-          const float f0 = f0s[mt], f2 = f2s[mt];
-          float ov[2], og[2];
-#pragma unroll
-          for (int e = 0; e < 2; ++e) {
-            const float w0v = e ? wv0.y : wv0.x, w1v = e ? wv1.y : wv1.x, w2v = e ? wv2.y : wv2.x;
-            const float w0g = e ? wg0.y : wg0.x, w1g = e ? wg1.y : wg1.x, w2g = e ? wg2.y : wg2.x;
-            const float pv = mt > 0 ? dcv[mt > 0 ? mt - 1 : 0][e] : qv0[e], pg = mt > 0 ? dcg[mt > 0 ? mt - 1 : 0][e] : qg0[e];
-            const float nv = mt < 3 ? dcv[mt < 3 ? mt + 1 : 3][e] : rv3[e], ng = mt < 3 ? dcg[mt < 3 ? mt + 1 : 3][e] : rg3[e];
-            ov[e] = fmaf(w0v * f2, nv, fmaf(w1v, dcv[mt][e], (w2v * f0) * pv));
-            og[e] = fmaf(w0g * f2, ng, fmaf(w1g, dcg[mt][e], (w2g * f0) * pg));
-          }
-          if constexpr (as16) { ovP[mt][pr] = gb_pack2(ov[0], ov[1]); ogP[mt][pr] = gb_pack2(og[0], og[1]); }
-          else { ovF[mt][2 * pr] = ov[0]; ovF[mt][2 * pr + 1] = ov[1]; ogF[mt][2 * pr] = og[0]; ogF[mt][2 * pr + 1] = og[1]; }
-        }
-        // depthwise gradient partials of this tile and pair: sum over the 16 lanes (frames) of each DPP row - an inclusive scan, lane 15 ends up
-        // with the row's total - and one 64-byte store per row: part[mb][pair hp + e][8]
-#pragma unroll
-        for (int e = 0; e < 2; ++e)
-#pragma unroll
-          for (int k = 0; k < 8; ++k) acc[e][k] = gb_row_total(acc[e][k]);
-        if (fi == 15) {
-          float* po = reinterpret_cast<float*>(reinterpret_cast<char*>(a.part) + ((unsigned)mb * (unsigned)C3 + (unsigned)hp) * 32u);
-#pragma unroll
-          for (int e = 0; e < 2; ++e) {
-            st4(po + 8 * e, make_float4(acc[e][0], acc[e][1], acc[e][2], acc[e][3]));
-            st4(po + 8 * e + 4, make_float4(acc[e][4], acc[e][5], acc[e][6], acc[e][7]));
-          }
-        }
-      }
-      // ---- the lane's output rows: g [M][3F], dh1 [M][6F] (value half, gate half); 32-bit byte offsets from the (scalar) tensor bases - the
-      //      launcher checks M * 6F * 4 < 2^32 - so that no 64-bit per-lane address is formed early and kept alive (or spilled) ----
-      char* const gB = static_cast<char*>(a.g);
-      char* const hB = static_cast<char*>(a.dh1);
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) {
-        const int fo = 4 * fi + mt, m = m0 - 2 + fo;
-        if (!(fo >= 2 && fo < 2 + GB_OUT && m < a.M)) continue;
-        if constexpr (as16) {
-          const unsigned og_ = ((unsigned)m * (unsigned)C3 + (unsigned)hc) * 2u, oh_ = ((unsigned)m * (unsigned)C6 + (unsigned)hc) * 2u;
-          *reinterpret_cast<uint2*>(gB + og_) = make_uint2(gP[mt][0], gP[mt][1]);
-          *reinterpret_cast<uint2*>(hB + oh_) = make_uint2(ovP[mt][0], ovP[mt][1]);
-          *reinterpret_cast<uint2*>(hB + oh_ + (unsigned)C3 * 2u) = make_uint2(ogP[mt][0], ogP[mt][1]);
-        } else {
-          const unsigned og_ = ((unsigned)m * (unsigned)C3 + (unsigned)hc) * 4u, oh_ = ((unsigned)m * (unsigned)C6 + (unsigned)hc) * 4u;
-          *reinterpret_cast<float4*>(gB + og_) = make_float4(gF[mt][0], gF[mt][1], gF[mt][2], gF[mt][3]);
-          *reinterpret_cast<float4*>(hB + oh_) = make_float4(ovF[mt][0], ovF[mt][1], ovF[mt][2], ovF[mt][3]);
-          *reinterpret_cast<float4*>(hB + oh_ + (unsigned)C3 * 4u) = make_float4(ogF[mt][0], ogF[mt][1], ogF[mt][2], ogF[mt][3]);
-        }
-      }
-    };
-    if (edge_tile) passes(gb_bool<true>{}); else passes(gb_bool<false>{});
-#else
     __syncthreads();   // every wave is done with the slab buffers: they become the h1 / dgd tiles
 
     // ---- stage h1 (+ bias) and dgd: row = frame, a lane holds 4 consecutive channels of one frame per accumulator ----
@@ -746,18 +471,11 @@ __global__ __launch_bounds__(GB_THREADS, PL ? SEPR_GB_PL_WGS : 2) void gcfn_bwd_
     auto passes = [&](auto edge_c) {
     constexpr bool EDGE = decltype(edge_c)::value;
     float4 dcv[4], dcg[4];
-    constexpr bool SLIDE = (SEPR_GB_SLIDE & 1) && !EDGE;        // pass A
-    constexpr bool SLIDE_B = (SEPR_GB_SLIDE & 2) && !EDGE;      // pass B
+    // interior tiles, pass B: a thread's 4 consecutive rows share their conv windows, so the neighbour rows of dc come from its own registers
+    // (4 LDS reads instead of 16; bit-identical)
+    constexpr bool SLIDE_B = !EDGE;
     {
 #pragma clang fp contract(off)
-      // SLIDE: rows r - 1, r of the window, carried from row to row (rows outside the tile are clamped: the rows that would use them are skipped)
-      [[maybe_unused]] float4 wvm, wgm, wvc, wgc;
-      if constexpr (SLIDE) {
-        const float* h0 = Hs + (4 * strip) * GB_HS + c4;
-        const float* hm = strip > 0 ? h0 - GB_HS : h0;
-        wvm = ld4(hm); wgm = ld4(hm + 64);
-        wvc = ld4(h0); wgc = ld4(h0 + 64);
-      }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int r = 4 * strip + i;
@@ -765,18 +483,10 @@ __global__ __launch_bounds__(GB_THREADS, PL ? SEPR_GB_PL_WGS : 2) void gcfn_bwd_
         dcv[i] = zero4();
         dcg[i] = zero4();
         float4 hvc, hgc, hvm, hgm, hvp, hgp;
-        if constexpr (SLIDE) {
-          const float* hp = Hs + (r + 1 < GB_BM ? r + 1 : GB_BM - 1) * GB_HS + c4;
-          hvp = ld4(hp); hgp = ld4(hp + 64);
-          hvm = wvm; hgm = wgm; hvc = wvc; hgc = wgc;
-          wvm = wvc; wgm = wgc; wvc = hvp; wgc = hgp;
-        }
         if (r < 1 || r > GB_BM - 2 || m < 0 || m >= a.M) continue;
         const float* hr = Hs + r * GB_HS + c4;
-        if constexpr (!SLIDE) {
-          hvc = ld4(hr); hgc = ld4(hr + 64);
-          hvm = ld4(hr - GB_HS); hgm = ld4(hr - GB_HS + 64); hvp = ld4(hr + GB_HS); hgp = ld4(hr + GB_HS + 64);
-        }
+        hvc = ld4(hr); hgc = ld4(hr + 64);
+        hvm = ld4(hr - GB_HS); hgm = ld4(hr - GB_HS + 64); hvp = ld4(hr + GB_HS); hgp = ld4(hr + GB_HS + 64);
         if constexpr (EDGE) {                                  // zero padding at the sequence ends (tiles that touch one: ~1 in 130)
           const int t = m % a.T;
           const float f0 = t > 0 ? 1.f : 0.f, f2 = t < a.T - 1 ? 1.f : 0.f;
@@ -901,18 +611,15 @@ __global__ __launch_bounds__(GB_THREADS, PL ? SEPR_GB_PL_WGS : 2) void gcfn_bwd_
         else po[o] = t;
       }
     }
-#endif
     tile = nxt;
     mb = mb_n;
     nb = nb_n;
   }
-#if !SEPR_GB_REGEPI
   if (a.acc_part && any_tile) {
     float* po = a.part + ((long long)mb_first * C3 + 64 * nb_first) * 8;
     po[tid] = wacc[0];
     po[tid + GB_THREADS] = wacc[1];
   }
-#endif
 }
 }  // namespace
 
@@ -988,16 +695,15 @@ int launch_gcfn_bwd_fused(const float* x, const float* stats, const float* dy, i
   long long slot = -1;
   const bool timed = prof_begin(SEPR_SITE_GCFN_BWD, st, &slot);
   const bool one = w->up.planes == 1;
-  if (SEPR_GB_REGEPI && ((out16 != 0) != one || M * 6LL * F * 4 >= (1LL << 32))) return SEPR_EINVAL;   // (the register epilogue: bf16 outputs <=> plain-bf16 arithmetic; 32-bit store offsets)
   a.xh16 = static_cast<const unsigned short*>(xh16);
   a.dy16 = static_cast<const unsigned short*>(dy16);
   const bool pl = one && xh16 && dy16;
   a.acc_part = 0;
   int nslots = MB;                                                     // rows of `part` the reduction walks
   if (pl) {
-    const int g3 = (ntiles < cap / 2 * SEPR_GB_PL_WGS) ? ntiles : cap / 2 * SEPR_GB_PL_WGS;   // SEPR_GB_PL_WGS workgroups per CU
+    const int g3 = (ntiles < cap / 2 * GB_PL_WGS) ? ntiles : cap / 2 * GB_PL_WGS;   // GB_PL_WGS workgroups per CU
     static const bool acc_off = [] { const char* e = getenv("SEPR_GB_ACC"); return e && e[0] == '0'; }();     // (A/B switch, read once)
-    if (!SEPR_GB_REGEPI && !acc_off && ntiles > g3 && g3 % (8 * NB) == 0) {   // every workgroup keeps its column block: tile b + k g3 -> nb = (b >> 3) % NB
+    if (!acc_off && ntiles > g3 && g3 % (8 * NB) == 0) {   // every workgroup keeps its column block: tile b + k g3 -> nb = (b >> 3) % NB
       a.acc_part = 1;
       nslots = g3 / NB;                                                // first tiles' mb = 0 .. g3 / NB - 1, all below MB (ntiles > g3)
     }

@@ -64,52 +64,9 @@ __device__ __forceinline__ float dpp_rol1(float v) {   // lane i <- lane (i+1) m
 //  * weight fragments are read from LDS two MFMA groups ahead (explicit ring + scheduling barriers), the first
 //    groups of the next phase are requested before the conv's VALU work.
 // ---------------------------------------------------------------------------------------------------------
-#ifndef SEPR_GF_ABL
-#define SEPR_GF_ABL 0   // timing ablations (wrong results): 1 no chunk loop, 2 weight chunks copied once per tile,
-                        // 4 no chunk barriers, 8 one LDS fragment read per chunk, 16 no exp/rcp in the GLU,
-                        // 32 / 64: PROXY of "fold the depthwise conv into the up-projection" (round-3 review item 6: three
-                        //   K = F MFMA passes against tap-scaled weights, the conv becomes two neighbour adds): the up-projection's
-                        //   MFMAs, its LDS fragment reads and the W1 chunk copy run THREE times, the conv keeps its neighbour
-                        //   exchange but uses adds instead of tap FMAs (32), or drops the exchange as well (64: the most
-                        //   optimistic bound - no DPP at all)
-#endif
 template <bool V>
 struct bool_c { static constexpr bool value = V; };
 
-#ifndef SEPR_GF3_RING
-#define SEPR_GF3_RING 2
-#endif
-#ifndef SEPR_GF3_REDERIVE
-#define SEPR_GF3_REDERIVE 1   // bit 1: the thread index made opaque at the top of every tile, bit 2: again in front of the epilogue - what is derived from it is then
-                              // recomputed there instead of being computed once, hoisted and kept alive (or spilled) across the chunk loop
-#endif
-#ifndef SEPR_GF3_UPFIRST
-#define SEPR_GF3_UPFIRST 1   // 1: both up-projections before both convolutions (the next chunk copy gets one more conv to land; ~1 %)
-#endif
-#ifndef SEPR_GF3_PRIO
-#define SEPR_GF3_PRIO 0
-#endif
-#ifndef SEPR_GF3_XCH
-#define SEPR_GF3_XCH 1
-#endif
-#ifndef SEPR_GF3_WGPRIO
-#define SEPR_GF3_WGPRIO 0
-#endif
-#ifndef SEPR_GF3_ASMDMA
-#define SEPR_GF3_ASMDMA 1   // 1: the weight-chunk copies are inline-asm LDS-DMA (invisible to hipcc's waitcnt pass, which otherwise puts an
-                            // s_waitcnt vmcnt(0) in front of the first LDS read behind a copy it knows about - tools/isa_trace.py shows one in
-                            // the middle of the up-projection of the 4-wave kernel); the copies are then waited for at the two chunk barriers only
-#endif
-#ifndef SEPR_GF3_FENCE256
-#define SEPR_GF3_FENCE256 1   // 0 (A/B): no scheduling fences around the MFMA groups of the F = 256 (one-wave-per-SIMD) instantiations
-#endif
-#define SEPR_GF3_SCHED_FENCE() do { if constexpr (F <= 128 || SEPR_GF3_FENCE256) __builtin_amdgcn_sched_barrier(0); } while (0)
-#ifndef SEPR_GF3_RESX
-#define SEPR_GF3_RESX 0   // EXPERIMENT (round-3 review item 6): 1 = the residual x is rebuilt from the bf16 hi + lo planes the wave
-                          // already holds ((hi + lo) / rstd + mean, 2^-17 relative) instead of being re-read from HBM in the
-                          // epilogue: removes 512 of the 1.7 KB per frame the kernel moves; costs end-to-end agreement (measured:
-                          // profiles/r03_v2_gcfn_resx_experiment.txt).  Off in the product build.
-#endif
 // ONE (training precision "bf16" only): plain bf16 operands - the normalised frames, the weights and the gated tensor are used
 // as their bf16 hi plane alone, ONE MFMA per product instead of three, no lo-plane split on the VALU, and only the hi-plane
 // blocks of every packed weight chunk are copied to LDS (half the L2 -> LDS stream).  Same packed weights, same LDS layout.
@@ -132,19 +89,18 @@ __device__ __forceinline__ void gcfn_fused3_body(const GcfnFusedArgs& a) {
     dk1 = sepr_drop_key(a.seed, a.salt, 1u);
   }
   static_assert(MT == 1 || MT == 2 || MT == 4, "frame tiles per wave");
-  constexpr int RD = SEPR_GF3_RING;      // LDS fragment read-ahead, in MFMA groups
+  constexpr int RD = 2;                  // LDS fragment read-ahead, in MFMA groups
   // (Round 6, measured no: with MT = 1 the three MFMAs of a group run back to back on ONE accumulator; issuing the value and the gate tile of a
   //  K step - and two output tiles of the down-projection - interleaved, from a 6-slot fragment ring, changed nothing: 24.8 vs 23.5 us per
   //  batch-1 launch, profiles/r06_b1_latency.txt.  Back-to-back accumulation into one tile is forwarded at the issue rate.)
   constexpr int RDX = RD, FBN = RD + 1;
-  constexpr bool UF = SEPR_GF3_UPFIRST != 0;
   constexpr int NT = 64 * NW;
   // XCH: the waves of a workgroup cover 16*MT*NW CONTIGUOUS frames and hand each other the conv's neighbour frame at
   // the wave seams through LDS (published by the barrier the chunk already has after the up-projections), so only the
   // two frames at the workgroup's ends are recomputed halo: 126 outputs per 128 frames instead of 120, and - what
   // matters more - 64000 x 2^k rows are then just under 512 x 2^k tiles, i.e. full launch rounds instead of
   // "one round + a 4 % tail" (534 tiles on 512 slots).  Without XCH every wave carries its own two halo frames.
-  constexpr bool XCH = (SEPR_GF3_XCH != 0) && MT >= 2 && UF && !PLAIN && LAT == 0;   // (ring form: ONE barrier per chunk - with a second, LDS-only
+  constexpr bool XCH = MT >= 2 && !PLAIN && LAT == 0;                                // (ring form: ONE barrier per chunk - with a second, LDS-only
                                                                                     //  barrier for the seam exchange it measured 2 % slower: r06_gcfn_ring.txt)
   constexpr int HALO = PLAIN ? 0 : 1;
   constexpr int WSTR = (XCH || PLAIN) ? 16 * MT : 16 * MT - 2;            // frames a wave advances
@@ -174,23 +130,15 @@ __device__ __forceinline__ void gcfn_fused3_body(const GcfnFusedArgs& a) {
   const uint4* w2s = wl + (LAT > 0 ? W1_U4 : W1F_U4);
   uint4* csl = wl + (LAT > 0 ? W1F_U4 : W1F_U4 + W2_U4);
 
-#if SEPR_GF3_REDERIVE
-  int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;       // re-derived from an opaque copy at the top of every tile and in front of the epilogue (SEPR_GF3_REDERIVE)
+  int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;       // not const: re-derived from an opaque copy at the top of every tile - what is derived from it is then recomputed
+                                                              // there instead of being computed once, hoisted and kept alive (or spilled) across the chunk loop
   int fi = lane & 15, fg = lane >> 4;
-#else
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int fi = lane & 15, fg = lane >> 4;
-#endif
   const int ntiles = FOLD ? a.fold_nseq * a.fold_tps : (a.M + GF_TILE - 1) / GF_TILE;
   const uint4* const W1g = static_cast<const uint4*>(a.w1p);
   const uint4* const W2g = static_cast<const uint4*>(a.w2p);
 
   // ---- weight chunks: global -> LDS by LDS-DMA, 1 KiB per wave instruction ---------------------------
-#if SEPR_GF3_REDERIVE
   [[maybe_unused]] int ws = __builtin_amdgcn_readfirstlane(w);         // the wave index as a scalar
-#else
-  [[maybe_unused]] const int ws = __builtin_amdgcn_readfirstlane(w);   // the wave index as a scalar
-#endif
   auto dma = [&](const uint4* gbase, uint4* lbase, int nblk) {   // nblk 1 KiB blocks, dealt round-robin to the waves
     unsigned loff = (unsigned)lane * 16u;
     asm volatile("" : "+v"(loff));
@@ -199,14 +147,7 @@ __device__ __forceinline__ void gcfn_fused3_body(const GcfnFusedArgs& a) {
       if (i * NW >= nblk) break;
       const int blk = i * NW + w;
       if (blk < nblk) {
-        const char* src = reinterpret_cast<const char*>(gbase + blk * 64) + loff;
-#if SEPR_GF3_ASMDMA
-        (void)src;
         glds16_asm(gbase + (i * NW + ws) * 64, loff, __builtin_amdgcn_readfirstlane(lds_addr(lbase + (i * NW + ws) * 64)));
-#else
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                         (__attribute__((address_space(3))) void*)(lbase + blk * 64), 16, 0, 0);
-#endif
       }
     }
   };
@@ -218,24 +159,13 @@ __device__ __forceinline__ void gcfn_fused3_body(const GcfnFusedArgs& a) {
       if (2 * i * NW >= nblk) break;
       const int blk = 2 * (i * NW + w);
       if (blk < nblk) {
-        const char* src = reinterpret_cast<const char*>(gbase + blk * 64) + loff;
-#if SEPR_GF3_ASMDMA
-        (void)src;
         glds16_asm(gbase + 2 * (i * NW + ws) * 64, loff, __builtin_amdgcn_readfirstlane(lds_addr(lbase + 2 * (i * NW + ws) * 64)));
-#else
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                         (__attribute__((address_space(3))) void*)(lbase + blk * 64), 16, 0, 0);
-#endif
       }
     }
   };
   auto dma_w1 = [&](int c) {
     if constexpr (ONE) dma_hi(W1g + (long long)c * W1_U4, wl, W1F_U4 / 64);
     else dma(W1g + (long long)c * W1_U4, wl, W1F_U4 / 64);
-    if (SEPR_GF_ABL & 96) {   // fold proxy: three tap-scaled weight sets = three times the up-projection copy volume
-      dma(W1g + (long long)c * W1_U4, wl, W1F_U4 / 64);
-      dma(W1g + (long long)c * W1_U4, wl, W1F_U4 / 64);
-    }
     dma(W1g + (long long)c * W1_U4 + W1F_U4, csl + (c & 1) * CS_U4, CS_U4 / 64);
   };
   auto dma_w2 = [&](int c) {
@@ -244,7 +174,7 @@ __device__ __forceinline__ void gcfn_fused3_body(const GcfnFusedArgs& a) {
   };
   auto dma_barrier = [&]() {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (!(SEPR_GF_ABL & 4)) __syncthreads();
+    __syncthreads();
   };
   // LAT: one chunk image into ring stage c % NST.  Every wave issues exactly LAT_NI copies (block index wraps, so a few blocks are
   // copied twice with the same bytes): the counted waits below are compile-time constants.
@@ -276,7 +206,7 @@ __device__ __forceinline__ void gcfn_fused3_body(const GcfnFusedArgs& a) {
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    if (c + NST - 1 < NCH && !(SEPR_GF_ABL & 2)) lat_dma(c + NST - 1);
+    if (c + NST - 1 < NCH) lat_dma(c + NST - 1);
     w1s = wl + (c % NST) * STG_U4;
     csl = wl + (c % NST) * STG_U4 + W1F_U4;
     w2s = wl + (c % NST) * STG_U4 + W1_U4;
@@ -285,13 +215,11 @@ __device__ __forceinline__ void gcfn_fused3_body(const GcfnFusedArgs& a) {
   // fragment pair (bf16 hi plane, lo plane) of one 16-channel tile at one K step
   auto ld_up = [&](int j, int g, uint4 (&d)[2]) {   // g = 2*ks + (0 value tile | 1 gate tile)
     const uint4* p = w1s + ((((g & 1) * 2 + j) * KS + (g >> 1)) * 2) * 64 + lane;
-    if ((SEPR_GF_ABL & 8) && (j | g)) return;   // ablation: one fragment read per chunk
     d[0] = p[0];
     if constexpr (!ONE) d[1] = p[64];
   };
   auto ld_dn = [&](int ft, uint4 (&d)[2]) {
     const uint4* p = w2s + (ft * 2) * 64 + lane;
-    if ((SEPR_GF_ABL & 8) && ft) return;
     d[0] = p[0];
     if constexpr (!ONE) d[1] = p[64];
   };
@@ -300,26 +228,14 @@ __device__ __forceinline__ void gcfn_fused3_body(const GcfnFusedArgs& a) {
   // and their VALU phases (depthwise conv + GLU + bf16 split) in lockstep, so the matrix pipe idles while both are in VALU
   // code and is contended while both multiply.  Every other co-resident workgroup (same parity rule as the projection
   // core, sepr_gemm.h) starts a fraction of a chunk period late.
-#if SEPR_GF3_WGPRIO
-  // EXPERIMENT (round 5): static wave priority for ONE of the two workgroups that share a CU (same parity rule as the stagger below), no per-phase
-  // flips - MI355X_MICROARCH.md "two waves per SIMD", item 4: the second-dispatched wave of a SIMD is the arbitration loser on every segment
-  {
-    const int qp = blockIdx.x >> 3;
-    if (((qp & 1) ^ ((qp >> 5) & 1)) != 0) __builtin_amdgcn_s_setprio(SEPR_GF3_WGPRIO);
-  }
-#endif
   if (a.stagger > 0) {
     const int ql = blockIdx.x >> 3;
     if (((ql & 1) ^ ((ql >> 5) & 1)) != 0)
       for (int i = 0; i < a.stagger; i += 100) __builtin_amdgcn_s_sleep(100);
   }
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-#if SEPR_GF3_REDERIVE
-    if constexpr ((SEPR_GF3_REDERIVE & 1) != 0) {
-      asm volatile("" : "+v"(tid));
-      lane = tid & 63; w = tid >> 6; fi = lane & 15; fg = lane >> 4; ws = __builtin_amdgcn_readfirstlane(w);
-    }
-#endif
+    asm volatile("" : "+v"(tid));
+    lane = tid & 63; w = tid >> 6; fi = lane & 15; fg = lane >> 4; ws = __builtin_amdgcn_readfirstlane(w);
     // chunk 0 of the weights is requested first: it lands under the frame loads and the LayerNorm below
     __syncthreads();   // the previous tile's epilogue staging is fully consumed
     [[maybe_unused]] const uint4* const Gg = static_cast<const uint4*>(a.gate_wp);   // GATE: two chunks of [4 tiles | 4 KB biases]
@@ -341,9 +257,6 @@ __device__ __forceinline__ void gcfn_fused3_body(const GcfnFusedArgs& a) {
     // ---- this wave's 32 frames (lane fi holds frames 2*fi and 2*fi+1): load, LayerNorm, split --------------
     const int mw0 = tile * GF_TILE + w * WSTR - HALO;           // wave frame 0 (GCFN: tile frame 0 is halo)
     bf16x8 xh[MT][KS], xl[MT][KS];
-#if SEPR_GF3_RESX
-    float mu_[MT], sg_[MT];
-#endif
     float f0[MT], f2[MT];                                        // conv zero-padding flags (sequence start / end)
     bool edge_lane = false;
     [[maybe_unused]] float yv[GATE ? MT : 1][GATE ? KS : 1][8];  // GATE: the fp32 frames (x, then y in place)
@@ -387,10 +300,6 @@ __device__ __forceinline__ void gcfn_fused3_body(const GcfnFusedArgs& a) {
       d += __shfl_xor(d, 16, 64);
       d += __shfl_xor(d, 32, 64);
       const float rstd = valid ? (PLAIN ? 1.0f : 1.0f / sqrtf(d * (1.0f / F) + a.eps)) : 0.f;   // invalid frames: exactly zero
-#if SEPR_GF3_RESX
-      mu_[mt] = mean;
-      sg_[mt] = PLAIN ? 1.0f : sqrtf(d * (1.0f / F) + a.eps);
-#endif
       bool own_row = false;
       if (TRAIN) {   // the frames this workgroup OUTPUTS (not its halo) report their statistics: all the backward needs
         const int lr = MT * fi + mt, bf = w * WSTR + lr;
@@ -456,7 +365,7 @@ __device__ __forceinline__ void gcfn_fused3_body(const GcfnFusedArgs& a) {
           for (int ks = 0; ks < KS; ++ks) {
             const int n = h * KS + ks;
             if (n + RD < 2 * KS) ld_g(n + RD, fb[(n + RD) % (RD + 1)]);
-            SEPR_GF3_SCHED_FENCE();
+            __builtin_amdgcn_sched_barrier(0);
             const bf16x8 wh = *reinterpret_cast<const bf16x8*>(&fb[n % (RD + 1)][0]);
             const bf16x8 wlo = *reinterpret_cast<const bf16x8*>(&fb[n % (RD + 1)][1]);
 #pragma unroll
@@ -465,7 +374,7 @@ __device__ __forceinline__ void gcfn_fused3_body(const GcfnFusedArgs& a) {
             for (int mt = 0; mt < MT; ++mt) g[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, xl[mt][ks], g[mt], 0, 0, 0);
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) g[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wlo, xh[mt][ks], g[mt], 0, 0, 0);
-            SEPR_GF3_SCHED_FENCE();
+            __builtin_amdgcn_sched_barrier(0);
           }
 #pragma unroll
           for (int mt = 0; mt < MT; ++mt) {
@@ -548,22 +457,22 @@ __device__ __forceinline__ void gcfn_fused3_body(const GcfnFusedArgs& a) {
 
     auto chunks = [&](auto edge_c) {
       constexpr bool EDGE = decltype(edge_c)::value;
-      for (int c = 0; c < ((SEPR_GF_ABL & 1) ? 0 : NCH); ++c) {
+      for (int c = 0; c < NCH; ++c) {
         if constexpr (LAT > 0) lat_enter(c);
         bf16x8 gh[MT], gw[MT];          // gated values (bf16 hi / lo) in down-projection k-slot order
         uint4 fb[FBN][2];               // fragment ring: RDX MFMA groups in flight ahead of the one being multiplied
 #pragma unroll
         for (int g = 0; g < RDX; ++g) ld_up(0, g, fb[g]);
-        f32x4 hvA[UF ? 2 : 1][MT], hgA[UF ? 2 : 1][MT];
+        f32x4 hvA[2][MT], hgA[2][MT];
 #pragma unroll
-        for (int jj = 0; jj < (UF ? 4 : 2); ++jj) {
-          // UF (up-first): both up-projections, then both convolutions - the copy of the next chunk's up-projection
-          // fragments is then issued one conv earlier and has conv + conv + down-projection to land
-          const int j = UF ? (jj & 1) : jj;
-          const bool do_up = !UF || jj < 2, do_conv = !UF || jj >= 2;
+        for (int jj = 0; jj < 4; ++jj) {
+          // up-first: both up-projections, then both convolutions - the copy of the next chunk's up-projection
+          // fragments is then issued one conv earlier and has conv + conv + down-projection to land (~1 %)
+          const int j = jj & 1;
+          const bool do_up = jj < 2, do_conv = jj >= 2;
           const float* cs = reinterpret_cast<const float*>(csl + (LAT > 0 ? 0 : (c & 1) * CS_U4)) + j * 160 + 4 * fg;
-          f32x4 (&hv)[MT] = hvA[UF ? j : 0];
-          f32x4 (&hg)[MT] = hgA[UF ? j : 0];
+          f32x4 (&hv)[MT] = hvA[j];
+          f32x4 (&hg)[MT] = hgA[j];
           if (do_up) {
           // ---- up-projection, accumulators start at the bias ------------------------------------------------
           {
@@ -574,14 +483,14 @@ __device__ __forceinline__ void gcfn_fused3_body(const GcfnFusedArgs& a) {
               hg[mt] = (f32x4){bg.x, bg.y, bg.z, bg.w};
             }
           }
-          if (SEPR_GF3_PRIO) __builtin_amdgcn_s_setprio(1);   // MFMA phases win the issue arbitration over the
-#pragma unroll                                                 // other workgroup's VALU phases
-          for (int rep3 = 0; rep3 < ((SEPR_GF_ABL & 96) ? 3 : 1); ++rep3)
+          // (the one-trip outer loop is load-bearing: without it hipcc allocates the MT = 1 training instantiations differently (153 instead of
+          //  159 VGPRs, other code) - kept so that this kernel's device code is what was measured)
+#pragma unroll
+          for (int once = 0; once < 1; ++once)
 #pragma unroll
           for (int g = 0; g < 2 * KS; ++g) {
-            if ((SEPR_GF_ABL & 96) && rep3 > 0 && g < RD) ld_up(j, g, fb[g % (RD + 1)]);   // (proxy: each pass re-reads its fragments)
             if (g + RD < 2 * KS) ld_up(j, g + RD, fb[(g + RD) % (RD + 1)]);
-            SEPR_GF3_SCHED_FENCE();
+            __builtin_amdgcn_sched_barrier(0);
             const bf16x8 wh = *reinterpret_cast<const bf16x8*>(&fb[g % (RD + 1)][0]);
             [[maybe_unused]] const bf16x8 wlo = *reinterpret_cast<const bf16x8*>(&fb[g % (RD + 1)][ONE ? 0 : 1]);
             const int ks = g >> 1;
@@ -604,9 +513,8 @@ __device__ __forceinline__ void gcfn_fused3_body(const GcfnFusedArgs& a) {
                 for (int mt = 0; mt < MT; ++mt) hg[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wlo, xh[mt][ks], hg[mt], 0, 0, 0);
               }
             }
-            SEPR_GF3_SCHED_FENCE();
+            __builtin_amdgcn_sched_barrier(0);
           }
-          if (SEPR_GF3_PRIO) __builtin_amdgcn_s_setprio(0);
           if (j == 0) {                            // the second tile pair's first fragments arrive under the conv
 #pragma unroll
             for (int g = 0; g < RDX; ++g) ld_up(1, g, fb[g]);
@@ -629,7 +537,7 @@ __device__ __forceinline__ void gcfn_fused3_body(const GcfnFusedArgs& a) {
             if constexpr (LAT == 0) {
             dma_barrier();                         // every wave has read its up-projection fragments of chunk c;
                                                    // this chunk's down-projection fragments have landed
-            if (c + 1 < NCH && !(SEPR_GF_ABL & 2)) dma_w1(c + 1);        // lands under the conv + down-projection below
+            if (c + 1 < NCH) dma_w1(c + 1);        // lands under the conv + down-projection below
             }
 #pragma unroll
             for (int g = 0; g < RDX; ++g)
@@ -697,11 +605,9 @@ __device__ __forceinline__ void gcfn_fused3_body(const GcfnFusedArgs& a) {
             for (int mt = 0; mt < MT; ++mt) {
               const float a0v = EDGE ? wv0 * f0[mt] : wv0, a2v = EDGE ? wv2 * f2[mt] : wv2;
               const float a0g = EDGE ? wg0 * f0[mt] : wg0, a2g = EDGE ? wg2 * f2[mt] : wg2;
-              float val = fmaf(a2v, nv[mt], fmaf(wv1, cv[mt], fmaf(a0v, pv[mt], cbv)));
-              float gat = fmaf(a2g, ng[mt], fmaf(wg1, cg[mt], fmaf(a0g, pg[mt], cbg)));
-              if (SEPR_GF_ABL & 32) { val = (cv[mt] + pv[mt]) + nv[mt]; gat = (cg[mt] + pg[mt]) + ng[mt]; }
-              if (SEPR_GF_ABL & 64) { val = cv[mt] + cv[mt]; gat = cg[mt] + cg[mt]; }
-              gl[mt][r] = (SEPR_GF_ABL & 16) ? val * gat : glu_prescaled(val, gat);   // 16: no transcendentals (gate taps are pre-scaled)
+              const float val = fmaf(a2v, nv[mt], fmaf(wv1, cv[mt], fmaf(a0v, pv[mt], cbv)));
+              const float gat = fmaf(a2g, ng[mt], fmaf(wg1, cg[mt], fmaf(a0g, pg[mt], cbg)));
+              gl[mt][r] = glu_prescaled(val, gat);   // (the gate taps are pre-scaled)
             }
           }
           if (TRAIN && drop) {   // network.py:55 dropout on the gated tensor: hidden channel 32c + 16j + 4fg + r of frame mw0 + MT*fi + mt
@@ -727,11 +633,10 @@ __device__ __forceinline__ void gcfn_fused3_body(const GcfnFusedArgs& a) {
             }
         }
         // ---- down-projection K step of this chunk -----------------------------------------------------------
-        if (SEPR_GF3_PRIO) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int ft = 0; ft < FT; ++ft) {
           if (ft + RD < FT) ld_dn(ft + RD, fb[(ft + RD) % (RD + 1)]);
-          SEPR_GF3_SCHED_FENCE();
+          __builtin_amdgcn_sched_barrier(0);
           const bf16x8 wh = *reinterpret_cast<const bf16x8*>(&fb[ft % (RD + 1)][0]);
           [[maybe_unused]] const bf16x8 wlo = *reinterpret_cast<const bf16x8*>(&fb[ft % (RD + 1)][ONE ? 0 : 1]);
 #pragma unroll
@@ -742,12 +647,11 @@ __device__ __forceinline__ void gcfn_fused3_body(const GcfnFusedArgs& a) {
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) acc[ft][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wlo, gh[mt], acc[ft][mt], 0, 0, 0);
           }
-          SEPR_GF3_SCHED_FENCE();
+          __builtin_amdgcn_sched_barrier(0);
         }
-        if (SEPR_GF3_PRIO) __builtin_amdgcn_s_setprio(0);
         if constexpr (LAT == 0) {
         dma_barrier();                             // down-projection fragments consumed; chunk c+1's up-projection
-        if (c + 1 < NCH && !(SEPR_GF_ABL & 2)) dma_w2(c + 1);            // fragments have landed
+        if (c + 1 < NCH) dma_w2(c + 1);            // fragments have landed
         }
       }
     };
@@ -785,12 +689,6 @@ __device__ __forceinline__ void gcfn_fused3_body(const GcfnFusedArgs& a) {
       continue;   // (the next tile starts on a barrier: the staging is consumed before the weight copies overwrite it)
     }
     // ---- epilogue: y = x + ls * (acc + b2), two waves at a time through LDS ---------------------------------
-#if SEPR_GF3_REDERIVE
-    if constexpr ((SEPR_GF3_REDERIVE & 2) != 0) {              // the epilogue's per-thread addresses are derived HERE, not in front of the chunk loop
-      asm volatile("" : "+v"(tid));
-      lane = tid & 63; w = tid >> 6; fi = lane & 15; fg = lane >> 4;
-    }
-#endif
     float* const Os = reinterpret_cast<float*>(wl);
     constexpr int WPP = 64 / (16 * MT);   // waves per 64-frame epilogue pass
     constexpr int Q = F / 4;                 // float4 per row
@@ -817,11 +715,8 @@ __device__ __forceinline__ void gcfn_fused3_body(const GcfnFusedArgs& a) {
         const bool ok = row < 64 && ww < NW && m < a.M &&
                         (PLAIN ? true : (XCH ? (bf >= 1 && bf <= GF_TILE) : (lr >= 1 && lr <= 16 * MT - 2)));
         mrow[p] = ok ? m : -1;
-        // (timing ablations, wrong results: SEPR_GF_ABL & 128 = no residual re-read at all - the upper bound of what removing the second read of x
-        //  could buy; & 256 = the re-read comes from a COLD address range (the output tensor of the launch) instead of the rows the tile loaded
-        //  ~20 us earlier - if that costs nothing either, the re-read is off the critical path wherever it is served from)
-        xr[p] = (PLAIN || (SEPR_GF3_RESX && !TRAIN) || (SEPR_GF_ABL & 128)) ? zero4()
-                : ld4(((SEPR_GF_ABL & 256) ? a.y : (GATE ? a.mid : a.x)) + (long long)(ok ? m : 0) * F + 4 * q4);
+        // (rebuilding the residual from the bf16 planes instead of this re-read costs end-to-end agreement: profiles/r03_v2_gcfn_resx_experiment.txt)
+        xr[p] = PLAIN ? zero4() : ld4((GATE ? a.mid : a.x) + (long long)(ok ? m : 0) * F + 4 * q4);
       }
       if (w / WPP == half) {
         float* base = Os + (w % WPP) * (16 * MT) * OS;
@@ -830,19 +725,6 @@ __device__ __forceinline__ void gcfn_fused3_body(const GcfnFusedArgs& a) {
 #pragma unroll
           for (int mt = 0; mt < MT; ++mt) {
             f32x4 v = acc[ft][mt];
-#if SEPR_GF3_RESX
-            if (!PLAIN && !TRAIN) {   // the FINAL y = x_rec + ls (acc + b2) is staged; the store pass below only copies
-              const int c0 = 32 * (ft >> 1) + 8 * fg + 4 * (ft & 1);
-              const float4 l4 = ld4(a.ls + c0), b4 = ld4(a.b2 + c0);
-              const float ll[4] = {l4.x, l4.y, l4.z, l4.w}, bb4[4] = {b4.x, b4.y, b4.z, b4.w};
-#pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                const int e = 4 * (ft & 1) + r;
-                const float xn = (float)xh[mt][ft >> 1][e] + (float)xl[mt][ft >> 1][e];
-                v[r] = fmaf(v[r] + bb4[r], ll[r], fmaf(xn, sg_[mt], mu_[mt]));
-              }
-            }
-#endif
             st4(base + (MT * fi + mt) * OS + 32 * (ft >> 1) + 8 * fg + 4 * (ft & 1), make_float4(v[0], v[1], v[2], v[3]));   // w2p row order
           }
       }
@@ -857,8 +739,6 @@ __device__ __forceinline__ void gcfn_fused3_body(const GcfnFusedArgs& a) {
               long long mo = mrow[p];
               if (a.out_S > 0) mo = ((long long)(mo / a.out_T) * a.out_S + a.out_s) * a.out_T + mo % a.out_T;
               st4(a.y + mo * a.ldy + a.col_off + 4 * q4, make_float4(o.x + b2.x, o.y + b2.y, o.z + b2.z, o.w + b2.w));
-            } else if (SEPR_GF3_RESX && !TRAIN) {
-              st4(a.y + (long long)mrow[p] * F + 4 * q4, o);
             } else {
               float4 v = TRAIN ? make_float4(fmaf(o.x, dsc, b2.x), fmaf(o.y, dsc, b2.y), fmaf(o.z, dsc, b2.z), fmaf(o.w, dsc, b2.w))
                                : make_float4(o.x + b2.x, o.y + b2.y, o.z + b2.z, o.w + b2.w);
@@ -906,14 +786,10 @@ __global__ __launch_bounds__(256, 2) void gcfn_gate_fused3_kernel(const GcfnFuse
 // Every accumulator sees exactly the operand sequence of gcfn_fused3_kernel (same packed weights, same products, same order): the result
 // is bit-identical, which the parity tests check against the batched launch (tests/test_gpu_parity.py).  F = 128 only.
 // ---------------------------------------------------------------------------------------------------------
-#ifndef SEPR_HS_WGS
-#define SEPR_HS_WGS 1   // workgroups per CU the 30-frame instantiation is compiled for; 2 (256 registers per wave) spills 124 dwords: the tile's
-                        // live set is 64 (frame planes) + 128 (fragment prefetch) + 48 (accumulators, gated planes) + the conv's temporaries
-#endif
 // PLAIN (MODE 1 of the kernel above: SpkSplit's and OutputLayer's GLU-MLP): no LayerNorm, conv, halo, LayerScale, residual; CPW = hidden
 // chunks per wave (a.nch = 4 CPW chunks: 2 for OutputLayer, 4 for SpkSplit, 3 for the GCFN block), input / output row maps as there.
 template <int MT, int CPW = 3, bool PLAIN = false>
-__global__ __launch_bounds__(256, MT == 2 ? SEPR_HS_WGS : 1) void gcfn_hs_kernel(const GcfnFusedArgs a) {
+__global__ __launch_bounds__(256, 1) void gcfn_hs_kernel(const GcfnFusedArgs a) {
   constexpr int F = 128, KS = F / 32, NW = 4, NCH = NW * CPW, FT = F / 16, FTW = FT / NW;
   constexpr int NG = NCH / 4;                        // groups of 4 K steps of the down-projection (one 16-fragment register block each)
   static_assert(PLAIN || CPW == 3, "the GCFN block has 3F / 32 = 12 hidden chunks");
@@ -1076,13 +952,11 @@ __global__ __launch_bounds__(256, MT == 2 ? SEPR_HS_WGS : 1) void gcfn_hs_kernel
       // the registers of this tile pair's fragments are free: request what runs in them next (the next chunk's pair, or W2)
       // (scheduling fences: hipcc otherwise sinks the loads down to their first use - and waits for each of them there)
       __builtin_amdgcn_sched_barrier(0);
-      if (!(SEPR_GF_ABL & 512)) {   // (timing ablation 512, wrong results: the weight fragments are requested once)
-        if (!last) ld_w1(c + NW, j, wf);
-        else if (j < NG) ld_w2(j, wf);
-      }
+      if (!last) ld_w1(c + NW, j, wf);
+      else if (j < NG) ld_w2(j, wf);
       __builtin_amdgcn_sched_barrier(0);
     }
-    if (last && NG > 2 && !(SEPR_GF_ABL & 512)) ld_w2(2, wc);     // (the frame planes are dead from here on)
+    if (last && NG > 2) ld_w2(2, wc);     // (the frame planes are dead from here on)
     __builtin_amdgcn_sched_barrier(0);
     bf16x8 gh[MT], gw[MT];      // gated values (bf16 hi / lo) in down-projection k-slot order
     auto conv = [&](int j, auto edge_c) {
@@ -1133,13 +1007,6 @@ __global__ __launch_bounds__(256, MT == 2 ? SEPR_HS_WGS : 1) void gcfn_hs_kernel
             gh[mt][4 * j + r] = hh;
             gw[mt][4 * j + r] = (__bf16)(g1 - (float)hh);
           }
-    } else
-    if (SEPR_GF_ABL & 1024) {   // (timing ablation 1024, wrong results: no conv / GLU / split)
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt) {
-        gh[mt] = *reinterpret_cast<const bf16x8*>(&hvA[0][mt]);
-        gw[mt] = *reinterpret_cast<const bf16x8*>(&hgA[1][mt]);
-      }
     } else
     // (the sequence-boundary form of the conv is taken by the whole wave or not at all: one small branch per chunk, the MFMA code is common)
     if (edge) {
@@ -1252,10 +1119,7 @@ __global__ __launch_bounds__(256, MT == 2 ? SEPR_HS_WGS : 1) void gcfn_hs_kernel
 //  measured not faster in round 2 and removed in round 4; it lives in git history at a01c6d4, sepr_gcfn_fused5.inc.)
 // (A one-workgroup-per-CU, software-pipelined variant of this kernel - "v4", 8 waves, doubled weight buffers, one
 //  barrier per chunk - was measured 10 % slower and removed in round 2; it lives in git history at 7cf5a73.)
-#ifndef SEPR_GF3_MT
-#define SEPR_GF3_MT 2   // v3 frame tiles per wave: 2 -> 4 waves x 30 frames (2 waves per SIMD), 1 -> 6 waves x 14 frames (3 per SIMD)
-#endif
-[[maybe_unused]] constexpr int GF3_MT = SEPR_GF3_MT, GF3_NW = (SEPR_GF3_MT == 1) ? 6 : 4;
+constexpr int GF3_MT = 2, GF3_NW = 4;   // the batched launches: 2 frame tiles per wave, 4 waves x 30 frames (2 waves per SIMD)
 
 // Latency form of the small-launch instantiations (template parameter LAT): taken when a launch has at most one tile per CU, i.e. when its
 // duration IS one workgroup's chunk walk (batch 1, Engine._inference_sample): SEPR_GF_LAT=0 switches it off.
@@ -1400,7 +1264,7 @@ bool gcfn_fused_takes_gate(int M, int F) {
     const char* e = getenv("SEPR_GF_BIG_RING");
     return e && e[0] ? atoi(e) : 0;
   }();
-  return F == 128 && GF3_MT == 2 && SEPR_GF3_XCH && SEPR_GF3_UPFIRST && !big_ring && M >= gf_small_rows();
+  return F == 128 && !big_ring && M >= gf_small_rows();
 }
 
 int launch_gcfn_fused(const GcfnFusedArgs& a_in, int F, int site, hipStream_t stream) {
@@ -1433,7 +1297,7 @@ int launch_gcfn_fused(const GcfnFusedArgs& a_in, int F, int site, hipStream_t st
   if (a.gate_wp && (a.train || !gcfn_fused_takes_gate(a.M, F) || !a.att || !a.mid || a.mid == a.y || a.mid == a.x || a.Tp <= 0 || a.fac <= 0 || a.T != a.Tp * a.fac))
     return SEPR_EINVAL;   // the caller asks first (gcfn_fused_takes_gate): no silent plain launch of half a block
   const int small_rows = gf_small_rows();
-  if (GF3_MT == 2 && a.M < small_rows) {
+  if (a.M < small_rows) {
     constexpr int tile_rows = 6 * 14;
     const int ntiles = (a.M + tile_rows - 1) / tile_rows;
     const int cap = persistent_grid();
@@ -1464,7 +1328,7 @@ int launch_gcfn_fused(const GcfnFusedArgs& a_in, int F, int site, hipStream_t st
     }
   } else {
     {
-      constexpr int tile_rows = (SEPR_GF3_XCH && GF3_MT == 2 && SEPR_GF3_UPFIRST) ? GF3_NW * 16 * GF3_MT - 2 : GF3_NW * (16 * GF3_MT - 2);
+      constexpr int tile_rows = GF3_NW * 16 * GF3_MT - 2;   // (seam exchange: only the workgroup's two end frames are halo)
       const int ntiles = (a.M + tile_rows - 1) / tile_rows;
       const int cap = persistent_grid();
       const int grid = ntiles < cap ? ntiles : cap;
@@ -1496,11 +1360,7 @@ int launch_gcfn_fused(const GcfnFusedArgs& a_in, int F, int site, hipStream_t st
         if (F == 128) hipLaunchKernelGGL((gcfn_fused3_kernel<128, GF3_MT, GF3_NW, 0, true>), dim3(grid), dim3(64 * GF3_NW), 0, stream, a);
         else hipLaunchKernelGGL((gcfn_fused3_kernel<64, GF3_MT, GF3_NW, 0, true>), dim3(grid), dim3(64 * GF3_NW), 0, stream, a);
       } else if (F == 128 && a.gate_wp) {
-#if SEPR_GF3_MT == 2
         hipLaunchKernelGGL(gcfn_gate_fused3_kernel, dim3(grid), dim3(256), 0, stream, a);
-#else
-        return SEPR_EINVAL;
-#endif
       } else if (F == 128) {
         hipLaunchKernelGGL((gcfn_fused3_kernel<128, GF3_MT, GF3_NW>), dim3(grid), dim3(64 * GF3_NW), 0, stream, a);
       } else if (F == 64) {

@@ -21,22 +21,8 @@
 
 namespace sepr {
 
-#ifndef SEPR_GEMM_PERSIST
-#define SEPR_GEMM_PERSIST 1   // 1: <= 2 workgroups per CU walking tiles, 0: one tile per workgroup (A/B builds)
-#endif
-#ifndef SEPR_GEMM_STAGGER
-#define SEPR_GEMM_STAGGER 1   // 1: de-phase the two co-resident workgroups of a CU at kernel start
-#endif
-#ifndef SEPR_ABL_NOLOAD
-#define SEPR_ABL_NOLOAD 0
-#endif
-#ifndef SEPR_ABL_NOSTORE
-#define SEPR_ABL_NOSTORE 0
-#endif
-#ifndef SEPR_GEMM_LDS_PAD
-#define SEPR_GEMM_LDS_PAD 8   // floats of padding per 32-float LDS row: 8 -> stride 40, conflict-free b128 reads
-#endif
-constexpr int GEMM_BK = 32, GEMM_LDS_STRIDE = GEMM_BK + SEPR_GEMM_LDS_PAD;
+constexpr int GEMM_LDS_PAD = 8;   // floats of padding per 32-float LDS row: stride 40, conflict-free b128 reads
+constexpr int GEMM_BK = 32, GEMM_LDS_STRIDE = GEMM_BK + GEMM_LDS_PAD;
 
 // TAG does not change the code: it gives the two GCFN projections (60 % of the model's FLOPs) their own
 // kernel symbols, so a rocprofv3 kernel trace separates them from the other users of the same
@@ -130,9 +116,6 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_kernel(const GemmArgs a)
     }
   };
   auto load_tile = [&](int kt) {
-#if SEPR_ABL_NOLOAD
-    if (kt > 0 || blockIdx.x != (unsigned)a.M) return;   // timing ablation: no global loads after setup
-#endif
     const int k = kt * GEMM_BK + 4 * c4;
     if (PRO == PRO_NORM && a.gamma) {   // gamma == NULL: affine already folded into W / bias (training path)
       g4 = ld4(a.gamma + k);
@@ -205,15 +188,6 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_kernel(const GemmArgs a)
   };
 
   auto epilogue = [&](const int m0, const int nb) {
-#if SEPR_ABL_NOSTORE
-    {   // timing ablation: keep the accumulators live, store nothing
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) asm volatile("" ::"v"(acc[i][j]));
-      return;
-    }
-#endif
     // accumulators -> LDS (the staging buffers are free after the K loop's closing barrier), then the
     // shared row-contiguous epilogue
     float* const Hs = smem;
@@ -230,7 +204,6 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_kernel(const GemmArgs a)
     epilogue_from_lds<EPI>(a, Hs, m0, nb, tid);
   };
 
-#if SEPR_GEMM_STAGGER
   // De-phase the two workgroups that share a CU.  They are dispatched together and run identical tile
   // sequences, so without this they stay in lockstep: both parked on memory at the same time, then both
   // contending for the matrix pipe (measured: 28 % SQ_WAIT_ANY yet only 60 % MFMA utilisation with two
@@ -243,7 +216,6 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_kernel(const GemmArgs a)
       for (int i = 0; i < naps; ++i) __builtin_amdgcn_s_sleep(100);
     }
   }
-#endif
   // ---- walk the tiles ---------------------------------------------------------------------------------
   int tile = blockIdx.x;
   int m0 = 0, nb = 0;

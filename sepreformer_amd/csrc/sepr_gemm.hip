@@ -54,12 +54,8 @@ int persistent_grid() {
 template <int PRO, int EPI, int TAG = 0>
 static void launch_inst(const GemmArgs& a, hipStream_t stream) {
   const int tiles = gemm_tiles(a, EPI);
-#if SEPR_GEMM_PERSIST
   const int cap = persistent_grid();
   const int grid = tiles < cap ? tiles : cap;
-#else
-  const int grid = tiles;
-#endif
   hipLaunchKernelGGL((gemm_kernel<PRO, EPI, TAG>), dim3(grid), dim3(GEMM_THREADS), 0, stream, a);
 }
 

@@ -20,9 +20,6 @@
 #include <stdio.h>
 #include <stdlib.h>
 
-#ifndef SEPR_TN_ABL
-#define SEPR_TN_ABL 0   // timing ablations (wrong results): 1 no MFMAs, 2 no conversion / LDS staging, 4 no global loads
-#endif
 namespace sepr {
 
 typedef __bf16 tn_bf16x8 __attribute__((ext_vector_type(8)));
@@ -107,11 +104,9 @@ __device__ __forceinline__ void tn_reduce_block(const TnRed& r, int blk, float* 
 // The !GEN loader is straight-line: all 16 row loads of a thread are issued back to back from clamped (always valid)
 // addresses, validity is a select afterwards, and the per-row (mean, rstd) pairs of a slab are fetched ONCE by 64 threads
 // and handed out through LDS instead of 16 x 8-byte loads per staging thread.
-#ifndef SEPR_TN_ONE_WPE
-#define SEPR_TN_ONE_WPE 2   // waves per SIMD the plain-bf16 instantiations are compiled for (3: round-5 experiment, two LDS planes + 168 VGPRs)
-#endif
+constexpr int TN_WPE = 2;   // waves per SIMD every instantiation is compiled for (plain bf16 at 3 - two LDS planes, 168 VGPRs - was not faster: profiles/r05_v4_wgrad_3waves.txt)
 template <int MD, bool GEN, bool STATS>
-__global__ __launch_bounds__(TN_THREADS, MD == 2 ? SEPR_TN_ONE_WPE : 2) void gemm_tn_kernel(const TnArgs a, const TnPlan p, float* __restrict__ part,
+__global__ __launch_bounds__(TN_THREADS, TN_WPE) void gemm_tn_kernel(const TnArgs a, const TnPlan p, float* __restrict__ part,
                                                                float* __restrict__ cpart, const int ngrid, const TnRed red) {
   // x3: [A_hi, A_lo, B_hi, B_lo][128][72] bf16 = 73 728 B;  plain bf16: [A_hi, B_hi] = 36 864 B;  f32: [A, B][64][132] fp32 = 67 584 B
   // (the plain-bf16 form stays at two workgroups per CU all the same: 208 VGPRs - profiles/r05_v4_wgrad_3waves.txt)
@@ -145,13 +140,10 @@ __global__ __launch_bounds__(TN_THREADS, MD == 2 ? SEPR_TN_ONE_WPE : 2) void gem
   // ---- staging role: threads 0..127 stage A, 128..255 stage B; each 8 rows x 4 columns per slab ----
   const bool roleA = tid < 128;
   const int t7 = tid & 127;
-#ifndef SEPR_TN_LANEMAP
-#define SEPR_TN_LANEMAP 0
-#endif
-  // lane -> (column group cg, row group mg).  LANEMAP 1 (packed-bf16 planes only): the row group is the FAST lane index, so the 8 lanes
-  // the LDS serves together store 4 row groups x 2 column groups = 8 distinct 16-byte bank windows (with cg fast, the 576-byte lane
-  // stride of the transposing store reaches only 16 of the 32 banks: PMC 65 % conflict cycles, profiles/r03_v5_pmc_train_kernels.txt)
-  const int cg = (SEPR_TN_LANEMAP && MD != 0) ? (t7 >> 2) : (t7 & 31), mg = (SEPR_TN_LANEMAP && MD != 0) ? (t7 & 3) : (t7 >> 5);
+  // lane -> (column group cg, row group mg): the column group is the fast lane index.  (The 576-byte lane stride of the transposing store of
+  // the packed-bf16 planes then reaches only 16 of the 32 banks - PMC 65 % conflict cycles, profiles/r03_v5_pmc_train_kernels.txt - but the map
+  // with the row group fast was slower, 162.8 -> 174.2 us at (128000, 768, 128): same file, "Tried".)
+  const int cg = t7 & 31, mg = t7 >> 5;
   const int col = (roleA ? n0 : k0) + 4 * cg;
   const bool col_ok = col < (roleA ? a.N : a.K);
   float4 rA[8 * TN_NB], rB[DBUF ? 8 * TN_NB : 1];
@@ -161,7 +153,6 @@ __global__ __launch_bounds__(TN_THREADS, MD == 2 ? SEPR_TN_ONE_WPE : 2) void gem
   const int row_safe = m_beg < a.M ? m_beg : 0;
   const int col_c = col_ok ? col : 0;
   auto load_slab = [&](int mb, float4 (&r)[8 * TN_NB]) {
-    if (SEPR_TN_ABL & 4) return;
     if constexpr (!GEN) {
       const float* base = roleA ? a.A : a.B;                      // wave-uniform
       const long long ld = roleA ? a.lda : a.ldb;
@@ -242,11 +233,6 @@ __global__ __launch_bounds__(TN_THREADS, MD == 2 ? SEPR_TN_ONE_WPE : 2) void gem
         if (!(m < m_end && col_ok)) r[e] = zero4();
       }
     }
-    if (SEPR_TN_ABL & 2) {
-#pragma unroll
-      for (int e = 0; e < 8 * TN_NB; ++e) asm volatile("" ::"v"(r[e].x), "v"(r[e].y), "v"(r[e].z), "v"(r[e].w));
-      return;
-    }
     if (roleA) {
 #pragma unroll
       for (int e = 0; e < 8 * TN_NB; ++e) { csum.x += r[e].x; csum.y += r[e].y; csum.z += r[e].z; csum.w += r[e].w; }
@@ -317,7 +303,6 @@ __global__ __launch_bounds__(TN_THREADS, MD == 2 ? SEPR_TN_ONE_WPE : 2) void gem
         for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
           for (int kt = 0; kt < 4; ++kt) {
-            if (SEPR_TN_ABL & 1) { acc[nt][kt][0] += (float)ah[nt][0] + (float)bh[kt][0]; continue; }
             acc[nt][kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[nt], bh[kt], acc[nt][kt], 0, 0, 0);
             if constexpr (!ONE) {
               acc[nt][kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[nt], bl[kt], acc[nt][kt], 0, 0, 0);
@@ -721,7 +706,7 @@ int launch_gemm_tn(const TnArgs& a, int x3, void* ws, size_t ws_bytes, hipStream
   }
   float* cpart = part + (size_t)p.nsplit * a.N * a.K;
   const int grid = p.tn * p.tk * p.nsplit;
-  // test switch (tools/probe/tn_fault.py, tests; read once, never set in the product): SEPR_TN_FORCE_GEN=1 routes every launch through the
+  // test switch (tests/tn_general_loader.py; read once, never set in the product): SEPR_TN_FORCE_GEN=1 routes every launch through the
   // general loader, so the public sepr_linear_wgrad_norm entry exercises it with per-row statistics at any size
   static const bool force_gen = [] { const char* e = getenv("SEPR_TN_FORCE_GEN"); return e && e[0] == '1'; }();
   const bool gen = force_gen || a.rows_out > 0 || a.B2 != nullptr || a.idx != nullptr || a.mask_a != 0 || a.stat_seq != 0;
@@ -764,7 +749,7 @@ int launch_gemm_tn(const TnArgs& a, int x3, void* ws, size_t ws_bytes, hipStream
   // (Rounds 3-4 ran the general loader at ONE workgroup per CU behind a 16 KB LDS pad: with two co-resident workgroups its bf16
   //  instantiations returned wrong, run-to-run different values in the even columns of the upper half of every B tile.  Round 5 found the
   //  cause - the packed-f32 op_sel fault described in sepr_common.h, triggered by the normalisation's v_pk_mul_f32 op_sel:[0,1] while the
-  //  other workgroup's bf16 MFMAs run - pinned the instruction form and removed the pad: tools/probe/tn_fault.py, tests/test_train_gpu.py
+  //  other workgroup's bf16 MFMAs run - pinned the instruction form and removed the pad: tests/tn_general_loader.py, tests/test_train_gpu.py
   //  test_general_loader_two_workgroups_per_cu.)
 #define SEPR_TN_LAUNCH(MD)                                                                                                   \
   do {                                                                                                                       \

@@ -26,29 +26,9 @@ namespace sepr {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
-#ifndef SEPR_ABL_NOLOAD
-#define SEPR_ABL_NOLOAD 0
-#endif
-#ifndef SEPR_X3_DEEP16
-#define SEPR_X3_DEEP16 1   // fp32 source rows on the single-plane arithmetic (training precision "bf16"): two slabs in flight (0: one; tools/variants.mk x3deep0)
-#endif
-#ifndef SEPR_X3_RAW16
-#define SEPR_X3_RAW16 1   // bf16 source rows on the single-plane arithmetic: raw staging, two slabs in flight (0: the widened one-slab form; tools/variants.mk x3raw0)
-#endif
-#ifndef SEPR_ABL_NOSTORE
-#define SEPR_ABL_NOSTORE 0
-#endif
-#ifndef SEPR_ABL_NOW
-#define SEPR_ABL_NOW 0
-#endif
-#ifndef SEPR_ABL_NOMMA
-#define SEPR_ABL_NOMMA 0
-#endif
 constexpr int X3_BKS = 64;                  // K extent of one LDS slab
-#ifndef SEPR_X3_LDK_PAD
-#define SEPR_X3_LDK_PAD 16   // 16: 160-byte rows (rounds 1-3); 8: 144-byte rows
-#endif
-constexpr int X3_LDK = X3_BKS + SEPR_X3_LDK_PAD;   // bf16 elements per LDS row
+constexpr int X3_LDK_PAD = 16;              // 160-byte LDS rows: conflict-free 16-byte fragment reads
+constexpr int X3_LDK = X3_BKS + X3_LDK_PAD; // bf16 elements per LDS row
 constexpr int X3_PLANE = GEMM_BM * X3_LDK;  // elements of one plane of one buffer
 
 template <int PRO, int EPI, int TAG = 0>
@@ -129,22 +109,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_x3_kernel(const GemmArgs
     }
   };
   auto load_slab_to = [&](int s, float4 (&ra)[8]) {
-#if SEPR_ABL_NOLOAD
-    if (s > 0 || blockIdx.x != (unsigned)a.M) return;   // timing ablation
-#endif
     const int k = s * X3_BKS + kh;
-    if constexpr (A16) {
-      const unsigned short* src16 = reinterpret_cast<const unsigned short*>(a.A) + pa + k;
-#pragma unroll
-      for (int j = 0; j < 8; j += 2) {
-        const uint4 u = *reinterpret_cast<const uint4*>(src16 + 4 * j);      // 8 bf16
-        ra[j] = make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16),
-                            __uint_as_float(u.y & 0xffff0000u));
-        ra[j + 1] = make_float4(__uint_as_float(u.z << 16), __uint_as_float(u.z & 0xffff0000u), __uint_as_float(u.w << 16),
-                                __uint_as_float(u.w & 0xffff0000u));
-      }
-      return;
-    }
     const float* src = a.A + pa + k;
     if (PRO == PRO_CAT2 && k >= a.ksplit) src = a.A2 + pa2 + (k - a.ksplit);
 #pragma unroll
@@ -153,11 +118,12 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_x3_kernel(const GemmArgs
   auto load_slab = [&](int s) { load_slab_to(s, ra); };
   // RAW (bf16 source rows on the single-plane arithmetic: the [rows, 6F] input-gradient operand of the plain-bf16 GCFN backward, K = 6F = 12
   // slabs): the slab's bf16 values ARE the LDS plane - no widening, no conversion - so a slab is 4 x 16 bytes per thread and TWO slabs are
-  // kept in flight in the registers ONE widened slab took (round 6; SEPR_X3_RAW16=0: the widened one-slab form)
-  constexpr bool RAW = A16 && ONE && PRO == PRO_PLAIN && (SEPR_X3_RAW16 != 0);
+  // kept in flight in the registers ONE widened slab took (round 6)
+  constexpr bool RAW = A16 && ONE && PRO == PRO_PLAIN;
+  static_assert(RAW || !A16, "a bf16 A operand is staged raw: plain-bf16 arithmetic, no prologue");
   // DEEP (every other single-plane instantiation, i.e. the plain-bf16 TRAINING precision only): the same two-slabs-in-flight schedule with two
-  // fp32 register sets (+32 registers), conversion at the LDS store as before (SEPR_X3_DEEP16=0: one slab; tools/variants.mk x3deep0)
-  constexpr bool DEEP = ONE && !RAW && (SEPR_X3_DEEP16 != 0);
+  // fp32 register sets (+32 registers), conversion at the LDS store as before
+  constexpr bool DEEP = ONE && !RAW;
   [[maybe_unused]] float4 rb[8];
   [[maybe_unused]] uint4 rq0[4], rq1[4];      // (two named sets: a runtime-indexed array would live in scratch)
   [[maybe_unused]] auto load_raw = [&](int s, uint4 (&r)[4]) {
@@ -194,9 +160,6 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_x3_kernel(const GemmArgs
   auto store_slab = [&](int buf) { store_slab_from(buf, ra); };
   // weight fragments of K step ks (global, fragment order: one coalesced 1 KiB load per tile and plane)
   auto load_w = [&](int ks, uint4 (&wh)[2], uint4 (&wl)[2]) {
-#if SEPR_ABL_NOW
-    if (ks > 0 || blockIdx.x != (unsigned)a.M) return;  // timing ablation
-#endif
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
       const uint4* p = Wp + wbase[nt] + (unsigned)ks * 128u + lane;
@@ -208,9 +171,6 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_x3_kernel(const GemmArgs
   f32x4 acc[2][8];
   auto mma_half = [&](const unsigned short* ph, const unsigned short* pl, int kk, int half, const uint4 (&wh)[2],
                       const uint4 (&wl)[2]) {
-#if SEPR_ABL_NOMMA
-    if (blockIdx.x != (unsigned)a.M) return;            // timing ablation
-#endif
     bf16x8 xh[4], xl[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -250,15 +210,6 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_x3_kernel(const GemmArgs
     return mb < MB;
   };
   auto epilogue = [&](const int m0, const int nb) {
-#if SEPR_ABL_NOSTORE
-    {
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) asm volatile("" ::"v"(acc[i][j]));
-      return;
-    }
-#endif
     float* const Hs = reinterpret_cast<float*>(smem);
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {

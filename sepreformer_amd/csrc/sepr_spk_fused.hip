@@ -123,24 +123,15 @@ __global__ __launch_bounds__(64 * NW, F > 128 ? 1 : (2 * NW) / 4) void spk_fused
       for (int mt = 0; mt < MT; ++mt) acc[ft][mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
     // ---- weight chunks: global -> LDS by LDS-DMA (protocol of gcfn_fused3_kernel) ------------------------------
-#ifndef SEPR_SPK_ASMDMA
-#define SEPR_SPK_ASMDMA 1   // inline-asm LDS-DMA (sepr_common.h glds16_asm): the copies are waited for at the chunk barriers only
-#endif
-    [[maybe_unused]] const int ws = __builtin_amdgcn_readfirstlane(w);
+    // inline-asm LDS-DMA (sepr_common.h glds16_asm): the copies are waited for at the chunk barriers only
+    const int ws = __builtin_amdgcn_readfirstlane(w);
     auto dma = [&](const uint4* gbase, uint4* lbase, int nblk) {
       unsigned loff = (unsigned)lane * 16u;
       asm volatile("" : "+v"(loff));
 #pragma unroll
       for (int i = 0; i < 24; ++i) {       // (24: the q/k/v fragments of a head at F = 256 are 96 KB)
         if (i >= nblk) break;
-#if SEPR_SPK_ASMDMA
         glds16_asm(gbase + (i * NW + ws) * 64, loff, __builtin_amdgcn_readfirstlane(lds_addr(lbase + (i * NW + ws) * 64)));
-#else
-        const int blk = i * NW + w;
-        const char* src = reinterpret_cast<const char*>(gbase + blk * 64) + loff;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                         (__attribute__((address_space(3))) void*)(lbase + blk * 64), 16, 0, 0);
-#endif
       }
     };
     auto dma_w1 = [&](int c) {
@@ -148,14 +139,9 @@ __global__ __launch_bounds__(64 * NW, F > 128 ? 1 : (2 * NW) / 4) void spk_fused
       dma(W1g + (long long)c * W1_U4 + W1F_U4, csl + (c & 1) * CS_U4, CS_U4 / NT);
     };
     auto dma_w2 = [&](int c) { dma(W2g + (long long)c * W2_U4, wl + W1F_U4, W2_U4 / NT); };
-#ifndef SEPR_SPK_ABL
-#define SEPR_SPK_ABL 0      // timing ablations (wrong results): 1 = weight chunks copied once per tile, 2 = no chunk
-#endif                      // barriers, 4 = no chunk loop (prologue + epilogue only), 8 = no score shuffles
     auto dma_barrier = [&]() {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#if (SEPR_SPK_ABL & 2) == 0
       __syncthreads();
-#endif
     };
     // fragment pair (bf16 hi plane, lo plane): head hh of the pair, group g = 3*ks + (0 q | 1 k | 2 v)
     auto ld_up = [&](int hh, int g, uint4 (&d)[2]) {
@@ -173,7 +159,7 @@ __global__ __launch_bounds__(64 * NW, F > 128 ? 1 : (2 * NW) / 4) void spk_fused
     dma_w1(0);
     dma_w2(0);
     dma_barrier();     // head pair 0 landed
-    for (int c = 0; c < ((SEPR_SPK_ABL & 4) ? 0 : NCH); ++c) {
+    for (int c = 0; c < NCH; ++c) {
       bf16x8 gh[MT], gw[MT];          // mixed values (bf16 hi / lo) in output-projection k-slot order, per speaker
       [[maybe_unused]] float sc0[MT][MT];          // DK32: the first tile's partial scores and v values
       [[maybe_unused]] f32x4 v0[MT];
@@ -226,9 +212,7 @@ __global__ __launch_bounds__(64 * NW, F > 128 ? 1 : (2 * NW) / 4) void spk_fused
         } else {
           dma_barrier();                         // every wave has read its q/k/v fragments of pair c; the pair's
                                                  // output-projection fragments have landed
-#if (SEPR_SPK_ABL & 1) == 0
           if (c + 1 < NCH) dma_w1(c + 1);        // lands under the mix + output projection below
-#endif
           ld_dn(0, fb[0]);
           ld_dn(1, fb[1]);
         }
@@ -242,10 +226,8 @@ __global__ __launch_bounds__(64 * NW, F > 128 ? 1 : (2 * NW) / 4) void spk_fused
             p = fmaf(pq[0][qa][1], pq[1][kc][1], p);
             p = fmaf(pq[0][qa][2], pq[1][kc][2], p);
             p = fmaf(pq[0][qa][3], pq[1][kc][3], p);
-#if (SEPR_SPK_ABL & 8) == 0
             p += __shfl_xor(p, 16, 64);          // the tile's 16 channels live in the 4 lane groups
             p += __shfl_xor(p, 32, 64);
-#endif
             sc[qa][kc] = p;
           }
         if constexpr (DK32) {
@@ -316,9 +298,7 @@ __global__ __launch_bounds__(64 * NW, F > 128 ? 1 : (2 * NW) / 4) void spk_fused
         __builtin_amdgcn_sched_barrier(0);
       }
       dma_barrier();                             // output-projection fragments consumed; pair c+1's q/k/v
-#if (SEPR_SPK_ABL & 1) == 0
       if (c + 1 < NCH) dma_w2(c + 1);            // fragments have landed
-#endif
     }
 
     // ---- epilogue: y = x + ls * (acc + bo), two waves at a time through LDS -------------------------------------

@@ -13,7 +13,7 @@ import threading
 from typing import Optional
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# SEPR_LIB_VARIANT=<tag> selects an A/B build (make -C csrc variants); unset = the product library
+# SEPR_LIB_VARIANT=<tag> loads a hand-built second library _native/libsepr_hip_<tag>.so for an A/B (tools/README.md); unset = the product library
 _VARIANT = os.environ.get("SEPR_LIB_VARIANT", "")
 LIB_PATH = os.path.join(_HERE, "_native", f"libsepr_hip_{_VARIANT}.so" if _VARIANT else "libsepr_hip.so")
 

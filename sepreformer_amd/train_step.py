@@ -75,7 +75,7 @@ class CapturedTrainStep:
             # covers collectives issued by the caller's own code with plain dist.all_reduce.
             import os
             import time
-            time.sleep(float(os.environ.get("SEPR_CAPTURE_DRAIN_S", "0.25") or 0.0))       # (0 = the round-4 behaviour, for tools/rccl_watchdog_loop.sh)
+            time.sleep(float(os.environ.get("SEPR_CAPTURE_DRAIN_S", "0.25") or 0.0))       # (0 = the round-4 behaviour: profiles/r05_fault_rccl_watchdog_*.txt)
 
         self.g_main, self.g_opt = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
         pool = torch.cuda.graph_pool_handle()

@@ -625,7 +625,7 @@ def test_isa_lint_guards_the_gfx950_packed_f32_fault():
 
 def test_hot_kernels_are_spill_free():
     """hipcc hoists the per-thread offsets of a persistent-tile kernel out of its tile loop and spills them; the kernels re-derive their
-    thread index per tile (SEPR_GB_REDERIVE / SEPR_GF3_REDERIVE / SEPR_XW_REDERIVE).  A change that brings the spills back costs 6 % of the largest training
+    thread index per tile (gcfn_bwd_mid_kernel, gcfn_fused3_kernel, gemm_x3w_kernel).  A change that brings the spills back costs 6 % of the largest training
     kernel without failing any parity test - so the shipped library is checked with tools/kres.py: the dominant kernels hold no spilled registers, and the
     library as a whole at most a handful (4 at the end of round 6, 25 before)."""
     import importlib.util

@@ -527,7 +527,7 @@ def test_gcfn_hidden_split_bitwise():
         if not hs:
             for k in ("SEPR_GF_HS", "SEPR_CF_HS", "SEPR_SPK_HS", "SEPR_CF_HEAD_HS"):
                 env.pop(k)
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "r6_hs_check.py")], env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "hs_check.py")], env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
         assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
         lines = [ln for ln in r.stdout.splitlines() if ln.startswith(("gcfn ", "cla ", "ega ", "spk ", "model "))]
         assert len(lines) >= 48, r.stdout[-2000:]

@@ -1936,7 +1936,7 @@ def test_general_loader_two_workgroups_per_cu():
     the public wgrad entry through that loader at 20 000 - 128 000 rows; every arithmetic must repeat bitwise and agree with fp64."""
     import subprocess
     env = dict(os.environ, SEPR_TN_FORCE_GEN="1")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "probe", "tn_fault.py")], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "tn_general_loader.py")], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                          text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if "wgrad_norm" in ln]

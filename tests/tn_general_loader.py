@@ -5,11 +5,11 @@ Round 3 found wrong, run-to-run different values (even columns k of the upper ha
 per-row-conditional loader normalised their B rows AND two workgroups shared a CU; the product keeps that loader at one workgroup per
 CU with a 16 KB LDS pad.  This script drives the SAME kernel through the public entry point with the pad overridden:
 
-    SEPR_TN_FORCE_GEN=1 SEPR_TN_GEN_PAD=<bytes> [SEPR_LIB_VARIANT=<tag>] python tools/probe/tn_fault.py
+    SEPR_TN_FORCE_GEN=1 SEPR_TN_GEN_PAD=<bytes> [SEPR_LIB_VARIANT=<tag>] python tests/tn_general_loader.py
 
 and prints, per shape and arithmetic: repeat equality, error vs fp64, and WHERE the repeats differ (k parity, k range inside the tile)."""
 import os, sys
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from sepreformer_amd import lib as L
 dev = torch.device("cuda:0")
