@@ -375,6 +375,24 @@ size_t sepr_stitch_workspace(int R, int total_chunks, int S);
 int sepr_stitch_fwd(const float* chunks, const int* chunk_offset, const int* lengths, int R, int S, int W, int O, int match_gain,
                     float* y, int* perm, float* gain, void* ws, size_t ws_bytes, sepr_stream_t stream);
 
+/* Sample-rate conversion of whole recordings (the reference resamples on the host inside librosa.load(path, sr=fs),
+ * engine.py:155).  Rational ratio fs_out / fs_in = L / M (coprime), K taps per output phase (K even), Hh = (K - 2) / 2:
+ *   y[n] = sum_{j < K} tap[(n M) mod L][j] * x[floor(n M / L) - Hh + j],  x zero outside [0, T),  0 <= n < N = ceil(T L / M).
+ * The products of float32 taps and float32 samples are exact in float64; they are summed in float64 in the order j = 0 .. K - 1 and the sum
+ * is rounded once to float32.  Bit-identical from run to run; a recording's result does not depend on what else is in the call.
+ * R recordings in one launch, packed as CSR: recording r is x[in_offset[r] .. in_offset[r + 1]) (T_r >= 1 samples) and receives
+ * y[out_offset[r] .. out_offset[r + 1]), out_offset[r + 1] - out_offset[r] = sepr_resample_out_len(T_r, L, M); both offset arrays start
+ * at 0 and are HOST arrays (copied into the workspace on `stream`: under graph capture they are read when the copy node runs).
+ * taps: DEVICE layout, float32 [K][L] with taps[j][q] = tap[(q M) mod L][j] - transposed and in output order, so that output n reads column
+ * n mod L (for L = 1 this is the tap row itself); sepreformer_amd/resample.py::plan builds the table for the Kaiser-windowed sinc of section 5d.
+ * R <= 65535; ratios whose tile span (255 M / L + K + 1 samples, + K for L = 1) exceeds 64 KiB of doubles are SEPR_EINVAL.  Every argument
+ * check returns SEPR_EINVAL (SEPR_EWORKSPACE for a short workspace) before any HIP call; no host synchronisation or allocation (capturable).
+ * sepr_resample_out_len: 0 for T, L or M < 1.  Workspace: sepr_resample_workspace(R) bytes (0 for unsupported R). */
+long long sepr_resample_out_len(long long T, int L, int M);
+size_t sepr_resample_workspace(int R);
+int sepr_resample_fwd(const float* x, const long long* in_offset, float* y, const long long* out_offset, int R, const float* taps, int L,
+                      int M, int K, void* ws, size_t ws_bytes, sepr_stream_t stream);
+
 /* ================================================================================================================= */
 /* Training path: train-mode forward twins that keep what the backward needs, and the       */
 /* backward of every block.  The reference trains through torch.autograd over the same modules (engine.py:50-83:     */

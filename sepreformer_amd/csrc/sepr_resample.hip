@@ -1,0 +1,109 @@
+// Sample-rate conversion of whole recordings: rational ratio L / M, band-limited, one tap row per output phase.
+//
+//   y[n] = sum_{j < K} tap[(n M) mod L][j] * x[floor(n M / L) - Hh + j],   Hh = (K - 2) / 2,   x = 0 outside [0, T)
+//
+// The taps and the samples are float32, so every product is exact in float64; the products are summed in float64 in the order
+// j = 0 .. K - 1 and the sum is rounded once to float32.  One thread per output sample, one workgroup per tile of RS_TILE
+// consecutive outputs of ONE recording (grid.y = recording): the tile's input span, (RS_TILE - 1) M / L + K + 1 samples, is staged
+// once in LDS already widened to double, zero-extended by predicate at both ends of the recording - a tile never reads another
+// recording's samples.  L = 1 (integer decimation): every output uses the same tap row, kept in LDS as doubles and read as a
+// broadcast.  L > 1: the table arrives transposed and in output order, [K][L] indexed by n mod L, so consecutive lanes read
+// consecutive taps of a table that stays in L2.  No atomics, nothing depends on the launch order: bit-identical from run to run,
+// and a recording's result does not depend on what else is in the call.
+#include "sepr_common.h"
+
+namespace sepr {
+namespace {
+constexpr int RS_TILE = 256;
+constexpr int RS_MAX_R = 65535;                  // grid.y
+constexpr size_t RS_MAX_LDS = 64 * 1024;         // dynamic LDS of one workgroup
+
+__host__ __device__ inline int rs_span(int L, int M, int K) { return (int)(((long long)(RS_TILE - 1) * M) / L) + K + 1; }
+
+template <bool ONE>
+__global__ __launch_bounds__(RS_TILE) void resample_kernel(const float* __restrict__ x, const long long* __restrict__ in_off,
+                                                           float* __restrict__ y, const long long* __restrict__ out_off,
+                                                           const float* __restrict__ taps, int L, int M, int K) {
+  extern __shared__ double rs_lds[];
+  const int r = blockIdx.y, tid = threadIdx.x;
+  const long long xo = in_off[r], T = in_off[r + 1] - xo, yo = out_off[r], N = out_off[r + 1] - yo;
+  const long long n0 = (long long)blockIdx.x * RS_TILE;
+  if (n0 >= N) return;                                              // the grid is as wide as the longest recording
+  const int Hh = (K - 2) / 2, span = rs_span(L, M, K);
+  const long long b0 = ONE ? n0 * M : (n0 * M) / L;
+  double* xs = rs_lds;
+  double* ts = rs_lds + span;
+  const long long g0 = b0 - Hh;
+  for (int i = tid; i < span; i += RS_TILE) {
+    const long long g = g0 + i;
+    xs[i] = (g >= 0 && g < T) ? (double)x[xo + g] : 0.0;
+  }
+  if (ONE)
+    for (int j = tid; j < K; j += RS_TILE) ts[j] = (double)taps[j];
+  __syncthreads();
+  const long long n = n0 + tid;
+  if (n >= N) return;
+  const long long nm = n * M;                                       // 64-bit: passes 2^31 after minutes of audio
+  const long long b = ONE ? nm : nm / L;
+  const double* xp = xs + (int)(b - b0);                            // 0 <= b - b0 <= (RS_TILE - 1) M / L + 1
+  double acc = 0.0;
+  if (ONE) {
+#pragma unroll 8
+    for (int j = 0; j < K; ++j) acc = fma(ts[j], xp[j], acc);
+  } else {
+    const float* tp = taps + (int)(n % L);
+#pragma unroll 8
+    for (int j = 0; j < K; ++j) acc = fma((double)tp[(long long)j * L], xp[j], acc);
+  }
+  y[yo + n] = (float)acc;
+}
+}  // namespace
+}  // namespace sepr
+
+extern "C" long long sepr_resample_out_len(long long T, int L, int M) {
+  if (T < 1 || L < 1 || M < 1 || T > (1LL << 62) / L) return 0;
+  return (T * L + M - 1) / M;
+}
+
+extern "C" size_t sepr_resample_workspace(int R) {
+  using namespace sepr;
+  if (R < 1 || R > RS_MAX_R) return 0;
+  return 2 * align_up((size_t)(R + 1) * sizeof(long long));
+}
+
+extern "C" int sepr_resample_fwd(const float* x, const long long* in_offset, float* y, const long long* out_offset, int R,
+                                 const float* taps, int L, int M, int K, void* ws, size_t ws_bytes, sepr_stream_t stream) {
+  using namespace sepr;
+  if (!x || !in_offset || !y || !out_offset || !taps) return SEPR_EINVAL;
+  if (R < 1 || R > RS_MAX_R || L < 1 || M < 1 || K < 2 || K % 2 != 0) return SEPR_EINVAL;
+  const size_t lds = ((size_t)rs_span(L, M, K) + (L == 1 ? (size_t)K : 0)) * sizeof(double);
+  if ((long long)(RS_TILE - 1) * M / L + K + 1 > 0x7fffffffLL || lds > RS_MAX_LDS) return SEPR_EINVAL;   // ratio beyond one tile's LDS
+  if (in_offset[0] != 0 || out_offset[0] != 0) return SEPR_EINVAL;
+  long long nmax = 0;
+  for (int r = 0; r < R; ++r) {
+    const long long T = in_offset[r + 1] - in_offset[r], N = out_offset[r + 1] - out_offset[r];
+    if (T < 1 || N < 1 || N != sepr_resample_out_len(T, L, M)) return SEPR_EINVAL;
+    if (N > (1LL << 62) / M) return SEPR_EINVAL;                    // n * M stays inside 64 bits
+    nmax = N > nmax ? N : nmax;
+  }
+  const long long tiles = (nmax + RS_TILE - 1) / RS_TILE;
+  if (tiles > 0x7fffffffLL) return SEPR_EINVAL;
+  const size_t need = sepr_resample_workspace(R);
+  if (!ws || ws_bytes < need) return SEPR_EWORKSPACE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  long long* ioff = static_cast<long long*>(ws);
+  long long* ooff = reinterpret_cast<long long*>(static_cast<char*>(ws) + need / 2);
+  hipError_t e = hipMemcpyAsync(ioff, in_offset, (size_t)(R + 1) * sizeof(long long), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(ooff, out_offset, (size_t)(R + 1) * sizeof(long long), hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) {
+    set_hip_error(e, "resample setup");
+    return SEPR_EHIP;
+  }
+  const dim3 grid((unsigned)tiles, (unsigned)R);
+  if (L == 1)
+    hipLaunchKernelGGL((resample_kernel<true>), grid, dim3(RS_TILE), lds, st, x, ioff, y, ooff, taps, L, M, K);
+  else
+    hipLaunchKernelGGL((resample_kernel<false>), grid, dim3(RS_TILE), lds, st, x, ioff, y, ooff, taps, L, M, K);
+  SEPR_CHECK_LAUNCH("resample kernel");
+  return SEPR_OK;
+}

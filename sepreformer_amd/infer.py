@@ -14,14 +14,15 @@ Mirrors ``models/SepReformer_Base_WSJ0/engine.py``:
 
 Host-side logic only; every waveform sample is computed by the HIP separator (``Model.forward``) and the HIP
 criterion kernels.  File I/O uses scipy (the reference uses librosa / soundfile, absent here): PCM16/PCM32/float
-wavs, multi-channel input averaged to mono as ``librosa.load`` does; a sampling-rate mismatch raises instead of
-resampling silently.
+wavs, multi-channel input averaged to mono as ``librosa.load`` does.  A file at another rate than the model's is converted
+on the device when asked to (``resample=True`` / ``--resample``; ``resample.py``), and the outputs can be
+written at another rate (``out_rate`` / ``--out-rate``); without the option a rate mismatch raises, as before.
 """
 from __future__ import annotations
 
 import csv
 import os
-from typing import Iterable, List, Optional, Sequence, Tuple
+from typing import Iterable, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -29,12 +30,7 @@ import torch
 from .longform import separate_long  # noqa: F401  (re-exported: the long-form entry point)
 
 
-def load_wav(path: str, fs: int) -> np.ndarray:
-    """-> float32 mono in [-1, 1) (``librosa.load(path, sr=fs)`` for a file already at ``fs``)."""
-    from scipy.io import wavfile
-    sr, data = wavfile.read(path)
-    if sr != fs:
-        raise RuntimeError(f"{path}: sampling rate {sr} != model rate {fs} (resample the file first)")
+def _decode(data: np.ndarray) -> np.ndarray:
     if data.dtype == np.int16:
         x = data.astype(np.float32) / 32768.0
     elif data.dtype == np.int32:
@@ -46,6 +42,22 @@ def load_wav(path: str, fs: int) -> np.ndarray:
     if x.ndim == 2:
         x = x.mean(axis=1)
     return np.ascontiguousarray(x)
+
+
+def load_wav(path: str, fs: int) -> np.ndarray:
+    """-> float32 mono in [-1, 1) (``librosa.load(path, sr=fs)`` for a file already at ``fs``)."""
+    from scipy.io import wavfile
+    sr, data = wavfile.read(path)
+    if sr != fs:
+        raise RuntimeError(f"{path}: sampling rate {sr} != model rate {fs} (resample the file first)")
+    return _decode(data)
+
+
+def load_audio(path: str) -> Tuple[np.ndarray, int]:
+    """-> (float32 mono in [-1, 1), the file's sampling rate): ``load_wav`` without the rate check (``librosa.load(path, sr=None)``)."""
+    from scipy.io import wavfile
+    sr, data = wavfile.read(path)
+    return _decode(data), int(sr)
 
 
 def pad_to_stride(x: torch.Tensor, stride: int) -> torch.Tensor:
@@ -81,38 +93,56 @@ def separate(model, mixture: torch.Tensor, stride: Optional[int] = None) -> List
     return [a[..., :T] for a in audio]
 
 
-def separate_file(model, path: str, fs: int = 8000, out_prefix: Optional[str] = None) -> Tuple[np.ndarray, List[str]]:
-    """``Engine._inference_sample``.  Returns the raw (un-normalised) estimates ``[S,T]`` and the files written."""
-    mix = load_wav(path, fs)
-    est = separate(model, torch.from_numpy(mix)[None])
-    prefix = out_prefix if out_prefix is not None else path[:-4]
+def _load_mixture(model, path: str, fs: int, resample: bool) -> Tuple[torch.Tensor, torch.Tensor, int]:
+    """-> (the file's samples, the mixture at ``fs``, the file's rate).  ``resample``: a file at another rate is converted
+    to ``fs`` on the model's device; otherwise a mismatch raises (``load_wav``)."""
+    if not resample:
+        mix = torch.from_numpy(load_wav(path, fs))
+        return mix, mix, fs
+    from .resample import resample as _resample
+    data, sr = load_audio(path)
+    mix = torch.from_numpy(data)
+    return mix, _resample(mix, sr, fs, device=next(model.parameters()).device), sr
+
+
+def _write_outputs(model, prefix: str, file_mix: torch.Tensor, sr: int, mix: torch.Tensor, est: Sequence[torch.Tensor], fs: int,
+                   out_rate: Union[None, int, str]) -> Tuple[np.ndarray, List[str]]:
+    """``<prefix>_in.wav`` and ``<prefix>_out_<i>.wav``, peak-normalised to 0.9, at ``out_rate`` (None: ``fs``; "input": the file's
+    rate ``sr``).  The copy of the input is the file's own samples converted from ``sr``; the estimates are converted from ``fs``,
+    all of them in one launch.  Returns the raw estimates ``[S,T]`` at ``fs`` as the separator produced them."""
+    from .resample import resample as _resample
+    rate = fs if out_rate is None else (sr if out_rate == "input" else int(out_rate))
+    dev = next(model.parameters()).device
+    copy = mix if rate == fs else _resample(file_mix, sr, rate, device=dev)
+    outs = list(est) if rate == fs else _resample([e.contiguous() for e in est], fs, rate, device=dev)
     written = [prefix + "_in.wav"]
-    write_wav(written[0], peak_normalise(mix, 0.9), fs)
-    raw = []
-    for i, e in enumerate(est):
-        src = e[0].detach().cpu().numpy()
-        raw.append(src)
+    write_wav(written[0], peak_normalise(copy.detach().cpu().numpy(), 0.9), rate)
+    for i, o in enumerate(outs):
         written.append(f"{prefix}_out_{i}.wav")
-        write_wav(written[-1], peak_normalise(src, 0.9), fs)
-    return np.stack(raw), written
+        write_wav(written[-1], peak_normalise(o.detach().cpu().numpy(), 0.9), rate)
+    return np.stack([e.detach().cpu().numpy() for e in est]), written
+
+
+def separate_file(model, path: str, fs: int = 8000, out_prefix: Optional[str] = None, resample: bool = False,
+                  out_rate: Union[None, int, str] = None) -> Tuple[np.ndarray, List[str]]:
+    """``Engine._inference_sample``.  Returns the raw (un-normalised) estimates ``[S,T]`` at ``fs`` and the files written.
+    ``resample``: a file at another rate is converted to ``fs`` on the device before separation (default: it raises).
+    ``out_rate``: the estimates and the ``_in.wav`` copy are converted to that rate before peak normalisation and writing
+    (``"input"``: the file's own rate; default: ``fs``)."""
+    file_mix, mix, sr = _load_mixture(model, path, fs, resample)
+    est = [e[0] for e in separate(model, mix[None])]
+    return _write_outputs(model, out_prefix if out_prefix is not None else path[:-4], file_mix, sr, mix, est, fs, out_rate)
 
 
 def separate_long_file(model, path: str, fs: int = 8000, out_prefix: Optional[str] = None, chunk_seconds: float = 4.0,
-                       overlap_seconds: float = 1.0, match_gain: bool = False, batch: int = 32) -> Tuple[np.ndarray, List[str]]:
-    """``separate_file`` through ``separate_long``: the same files, the same 0.9 peak normalisation."""
-    mix = load_wav(path, fs)
-    est = separate_long(model, torch.from_numpy(mix), chunk_seconds=chunk_seconds, overlap_seconds=overlap_seconds, fs=fs,
-                        batch=batch, match_gain=match_gain)
-    prefix = out_prefix if out_prefix is not None else path[:-4]
-    written = [prefix + "_in.wav"]
-    write_wav(written[0], peak_normalise(mix, 0.9), fs)
-    raw = []
-    for i, e in enumerate(est):
-        src = e.detach().cpu().numpy()
-        raw.append(src)
-        written.append(f"{prefix}_out_{i}.wav")
-        write_wav(written[-1], peak_normalise(src, 0.9), fs)
-    return np.stack(raw), written
+                       overlap_seconds: float = 1.0, match_gain: bool = False, batch: int = 32, resample: bool = False,
+                       out_rate: Union[None, int, str] = None) -> Tuple[np.ndarray, List[str]]:
+    """``separate_file`` through ``separate_long``: the same files, the same 0.9 peak normalisation, the same ``resample`` /
+    ``out_rate`` options."""
+    file_mix, mix, sr = _load_mixture(model, path, fs, resample)
+    est = separate_long(model, mix, chunk_seconds=chunk_seconds, overlap_seconds=overlap_seconds, fs=fs, batch=batch,
+                        match_gain=match_gain)
+    return _write_outputs(model, out_prefix if out_prefix is not None else path[:-4], file_mix, sr, mix, est, fs, out_rate)
 
 
 def _test_loop(model, utterances, sisnr_csv_path, sdr_csv_path, wav_dir, fs, with_sdr):
@@ -190,7 +220,12 @@ def _main() -> None:
                     help="long-form mode: overlapping windows of this length, stitched on the device (default: one whole-file forward)")
     ap.add_argument("--overlap-seconds", type=float, default=1.0, help="long-form mode: overlap of consecutive windows")
     ap.add_argument("--match-gain", action="store_true", help="long-form mode: align each speaker track's gain across windows")
+    ap.add_argument("--resample", action="store_true",
+                    help="convert a file at another sampling rate to the model's rate on the device (default: such a file is an error)")
+    ap.add_argument("--out-rate", default=None, metavar="{N,input}",
+                    help="write the outputs at N Hz, or at the input file's own rate (default: the model's rate)")
     args = ap.parse_args()
+    out_rate = args.out_rate if args.out_rate in (None, "input") else int(args.out_rate)
     model = Model.from_config(VARIANTS[args.model], init_seed=0)
     if args.checkpoint:
         ck = torch.load(args.checkpoint, map_location="cpu")
@@ -199,10 +234,10 @@ def _main() -> None:
         model.load_synthetic_(0)
     model = model.eval().to(args.device)
     if args.chunk_seconds is None:
-        _, written = separate_file(model, args.wav)
+        _, written = separate_file(model, args.wav, resample=args.resample, out_rate=out_rate)
     else:
         _, written = separate_long_file(model, args.wav, chunk_seconds=args.chunk_seconds, overlap_seconds=args.overlap_seconds,
-                                        match_gain=args.match_gain)
+                                        match_gain=args.match_gain, resample=args.resample, out_rate=out_rate)
     print("\n".join(written))
 
 

@@ -152,6 +152,9 @@ SIGNATURES = {
     "sepr_bss_eval_fwd": (_i, [_fp, _fp, _fp, C.POINTER(_i), _i, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _sz, _fp]),
     "sepr_stitch_workspace": (_sz, [_i, _i, _i]),
     "sepr_stitch_fwd": (_i, [_fp, C.POINTER(_i), C.POINTER(_i), _i, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _sz, _fp]),
+    "sepr_resample_out_len": (_ll, [_ll, _i, _i]),
+    "sepr_resample_workspace": (_sz, [_i]),
+    "sepr_resample_fwd": (_i, [_fp, C.POINTER(_ll), _fp, C.POINTER(_ll), _i, _fp, _i, _i, _i, _fp, _sz, _fp]),
     "sepr_pit_sisnr_fwd": (_i, [_fp, _fp, _fp, _i, _i, _i, C.c_double, C.c_double, C.c_double, _fp, _fp, _fp, _fp,
                                 _fp, _sz, _fp]),
     "sepr_train_ctx_bytes": (_sz, [_i] * 8),

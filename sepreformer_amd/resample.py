@@ -1,0 +1,141 @@
+"""Sample-rate conversion on the device: recordings at any rate in, the model's rate out (and back).
+
+The reference loads every file with ``librosa.load(path, sr=fs)`` (``engine.py:155``), which resamples on the host.  Here the
+conversion is one HIP launch (``csrc/sepr_resample.hip``): rational ratio ``L / M``, Kaiser-windowed sinc, one tap row per
+output phase, float64 accumulation of exact products, one rounding to float32.  The definitions are in DESIGN.md section 5d
+and include/sepr.h; tests/resample_ref.py restates them in float64.  The filter is this project's own: it does not reproduce
+soxr (librosa's default converter) sample for sample.
+
+``plan`` is host arithmetic (numpy float64) and needs no device; ``resample`` runs on the HIP device only.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Dict, List, NamedTuple, Sequence, Tuple, Union
+
+import numpy as np
+import torch
+
+from . import lib as L_
+
+ZEROS = 64          # zero crossings of the sinc per side
+ROLLOFF = 0.945     # cut-off as a fraction of the lower Nyquist frequency
+BETA = 12.0         # Kaiser window parameter
+
+
+class Plan(NamedTuple):
+    L: int              # fs_out / gcd
+    M: int              # fs_in / gcd
+    K: int              # taps per phase, 2 Hh + 2
+    Hh: int             # ceil(ZEROS / s), s = min(1, L / M)
+    taps: np.ndarray    # float32 [L][K]
+
+
+def plan(fs_in: int, fs_out: int) -> Plan:
+    """``(L, M, K, Hh, taps)`` of the converter ``fs_in -> fs_out``: ``taps[p][j] = rolloff s sinc(rolloff u) kaiser(u / Z)`` at
+    ``u = (p / L + Hh - j) s``, zero for ``|u| >= Z``; float64 arithmetic rounded once to float32."""
+    fs_in, fs_out = int(fs_in), int(fs_out)
+    if fs_in < 1 or fs_out < 1:
+        raise ValueError(f"sampling rates must be positive, got {fs_in} -> {fs_out}")
+    g = math.gcd(fs_in, fs_out)
+    L, M = fs_out // g, fs_in // g
+    s = min(1.0, L / M)
+    Hh = -((-ZEROS * max(L, M)) // L)               # ceil(Z / s) in integers: Z max(1, M / L)
+    K = 2 * Hh + 2
+    p = np.arange(L, dtype=np.float64)[:, None]
+    j = np.arange(K, dtype=np.float64)[None, :]
+    u = (p / L + Hh - j) * s
+    inside = np.abs(u) < ZEROS
+    w = np.i0(BETA * np.sqrt(np.where(inside, 1.0 - (u / ZEROS) ** 2, 0.0))) / np.i0(BETA)
+    taps = np.where(inside, ROLLOFF * s * np.sinc(ROLLOFF * u) * w, 0.0)
+    return Plan(L, M, K, Hh, taps.astype(np.float32))
+
+
+def out_len(T: int, L: int, M: int) -> int:
+    """``ceil(T L / M)``: the length ``librosa.resample`` gives."""
+    return -((-int(T) * L) // M)
+
+
+def device_table(p: Plan) -> np.ndarray:
+    """The table in the kernel's layout: float32 ``[K][L]``, column ``q`` = the tap row of phase ``(q M) mod L`` - output ``n``
+    reads column ``n mod L``, so consecutive lanes read consecutive floats."""
+    q = (np.arange(p.L, dtype=np.int64) * p.M) % p.L
+    return np.ascontiguousarray(p.taps[q].T)
+
+
+_tables: Dict[Tuple[int, int, str], Tuple[Plan, torch.Tensor]] = {}
+
+
+def _table(fs_in: int, fs_out: int, dev: torch.device) -> Tuple[Plan, torch.Tensor]:
+    key = (int(fs_in), int(fs_out), str(dev))
+    if key not in _tables:
+        p = plan(fs_in, fs_out)
+        _tables[key] = (p, torch.from_numpy(device_table(p)).to(dev))
+    return _tables[key]
+
+
+def _as_list(x) -> Tuple[List[torch.Tensor], int]:
+    """-> (1-D tensors, form): form 1 = a 1-D tensor, 2 = a [1, T] tensor, 0 = a sequence."""
+    if isinstance(x, torch.Tensor):
+        if x.dim() == 1:
+            return [x], 1
+        if x.dim() == 2 and x.shape[0] == 1:
+            return [x[0]], 2
+        raise ValueError("a tensor must be [T] or [1, T]; pass several recordings as a sequence of 1-D tensors")
+    xs = list(x)
+    for v in xs:
+        if not isinstance(v, torch.Tensor) or v.dim() != 1:
+            raise ValueError("every recording of the sequence must be a 1-D tensor")
+    return xs, 0
+
+
+@torch.no_grad()
+def resample(x: Union[torch.Tensor, Sequence[torch.Tensor]], fs_in: int, fs_out: int, device=None):
+    """Convert recordings from ``fs_in`` to ``fs_out`` on the device.
+
+    ``x``: a 1-D tensor, a ``[1, T]`` tensor, or a sequence of 1-D tensors of any lengths (each at least one sample).  Returns
+    float32 device tensors of ``ceil(T fs_out / fs_in)`` samples in the same form (a list for a sequence); all recordings of a
+    call share one launch, and a recording's result does not depend on the others.  ``fs_in == fs_out`` returns ``x`` itself.
+    Tensors already on a HIP device stay there; CPU tensors are copied to ``device`` (default ``cuda:0``) - without a HIP
+    device this raises: there is no CPU path."""
+    if int(fs_in) == int(fs_out):
+        return x
+    xs, form = _as_list(x)
+    if not xs:
+        return []
+    dev = next((v.device for v in xs if v.device.type == "cuda"), None)
+    if dev is None:
+        if not torch.cuda.is_available():
+            raise RuntimeError("resample runs on the HIP device only (there is no CPU path)")
+        dev = torch.device(device if device is not None else "cuda:0")
+    if dev.type != "cuda":
+        raise RuntimeError("resample runs on the HIP device only (there is no CPU path)")
+    for v in xs:
+        if v.shape[0] < 1:
+            raise ValueError("every recording must hold at least one sample")
+    p, table = _table(fs_in, fs_out, dev)
+    lib = L_.load()
+    xs = [v.to(device=dev, dtype=torch.float32) for v in xs]
+    R = len(xs)
+    if lib.sepr_resample_workspace(R) == 0:
+        raise ValueError(f"{R} recordings in one call: more than the kernel's grid takes")
+    lens = [int(v.shape[0]) for v in xs]
+    outs = [out_len(T, p.L, p.M) for T in lens]
+    xin = xs[0].contiguous() if R == 1 else torch.cat(xs)
+    y = torch.empty(sum(outs), dtype=torch.float32, device=dev)
+    ioff = (C.c_longlong * (R + 1))(0, *np.cumsum(lens).tolist())
+    ooff = (C.c_longlong * (R + 1))(0, *np.cumsum(outs).tolist())
+    ws = torch.empty(lib.sepr_resample_workspace(R), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        L_.check(lib.sepr_resample_fwd(xin.data_ptr(), ioff, y.data_ptr(), ooff, R, table.data_ptr(), p.L, p.M, p.K, ws.data_ptr(),
+                                       ws.numel(), stream.cuda_stream), "sepr_resample_fwd")
+        # the offsets are pageable host memory that the call's copies read when they run: they must outlive the copies
+        stream.synchronize()
+    parts = [y[int(ooff[r]):int(ooff[r + 1])] for r in range(R)]
+    if form == 1:
+        return parts[0]
+    if form == 2:
+        return parts[0][None]
+    return parts
