@@ -393,6 +393,40 @@ size_t sepr_resample_workspace(int R);
 int sepr_resample_fwd(const float* x, const long long* in_offset, float* y, const long long* out_offset, int R, const float* taps, int L,
                       int M, int K, void* ws, size_t ws_bytes, sepr_stream_t stream);
 
+/* Training batches from a device-resident corpus (the reference mixes on the host, in numpy, inside its DataLoader
+ * workers: models/SepReformer_Large_DM_{WSJ0,WHAM,WHAMR}/dataset.py::_dynamic_mixing / _direct_load / _collate).
+ * Corpus: N >= 1 utterances of at least one sample.  The first N16 are int16 (PCM16 as on disk; the sample value is s / 32768, exact in
+ * float32) and lie back to back in buf16, the other N - N16 are float32 and lie back to back in buf32.  offsets [N + 1] int64 (DEVICE) holds
+ * the cumulative element counts over all N: utterance u < N16 is buf16[offsets[u] .. offsets[u + 1]), utterance u >= N16 is
+ * buf32[offsets[u] - offsets[N16] .. offsets[u + 1] - offsets[N16]).  total16 = offsets[N16] and total32 = offsets[N] - offsets[N16] are passed
+ * by value (the table is device memory); both buffers are 16-byte aligned and ALLOCATED up to a multiple of 16 bytes (the kernels read
+ * aligned 16-byte words).  A buffer with no utterance may be NULL.
+ *
+ * sepr_corpus_energy: sum of squares per utterance.  ss16 [N16] int64 = sum s^2 of the raw int16 values - exact (a square is below 2^30), so
+ * independent of the summation order: rms = sqrt(ss / (32768^2 n)) is the same number everywhere.  ss32 [N - N16] float64 = sum of the
+ * (exact) float64 squares in a fixed order: per-workgroup partials, then one finishing pass; no atomics, bit-identical from run to run.
+ * Workspace: sepr_corpus_energy_workspace(N) bytes (0 for N < 1).
+ *
+ * sepr_dynmix_fwd: one launch builds a batch.  Example b of B has M mixture terms and S target terms, flattened as term j = b (M + S) + m
+ * (m < M: mixture terms, then the S target terms); S in {2, 3}, M in {S, S + 1}.  A term is (term_utt[j], term_start[j], term_norm[j],
+ * term_gain[j]): its value at output sample t is (x[term_start + t] * term_norm) * term_gain with x the utterance's sample value - two
+ * separately rounded float32 multiplies, never contracted.  n [B] int32 = the example's length, Tmax a multiple of 4.
+ *   mix[b][t]    = ((0 + term_0) + term_1) + ... in term order for t < n[b], 0 for n[b] <= t < Tmax          mix [B][Tmax] float32
+ *   src[s][b][t] = target term s for t < n[b], 0 beyond                                                       src[s] [B][Tmax] float32
+ * src is a HOST array of S device pointers (read before the call returns), so the rows of one [S][B][Tmax] tensor and S separate tensors
+ * are both served; mix and every src[s] 16-byte aligned.  A target term that equals mixture term s bit for bit (the WSJ0 / WHAM forms) is
+ * computed once.  All five table arrays are DEVICE memory, so the call cannot validate them: the caller guarantees
+ * term_start + n[b] <= the utterance's length; the kernel clamps the utterance index, the start and every read position, so that a bad table
+ * yields wrong samples but never a read outside the corpus buffers.  SEPR_EINVAL before any HIP call for a null pointer, B < 1 (or > 65535),
+ * S outside 2..3, M outside S..S+1, Tmax < 4 or not a multiple of 4, a misaligned pointer or an inconsistent corpus description.  No
+ * workspace, no host synchronisation or allocation (capturable: the pointers are frozen, the table contents are read at replay). */
+size_t sepr_corpus_energy_workspace(int N);
+int sepr_corpus_energy(const short* buf16, long long total16, const float* buf32, long long total32, const long long* offsets, int N16, int N,
+                       long long* ss16, double* ss32, void* ws, size_t ws_bytes, sepr_stream_t stream);
+int sepr_dynmix_fwd(const short* buf16, long long total16, const float* buf32, long long total32, const long long* offsets, int N16, int N,
+                    const int* term_utt, const int* term_start, const float* term_norm, const float* term_gain, const int* n, int B, int M,
+                    int S, int Tmax, float* mix, float* const* src, sepr_stream_t stream);
+
 /* ================================================================================================================= */
 /* Training path: train-mode forward twins that keep what the backward needs, and the       */
 /* backward of every block.  The reference trains through torch.autograd over the same modules (engine.py:50-83:     */

@@ -1,0 +1,483 @@
+"""Training batches from a device-resident corpus with dynamic mixing.
+
+The reference builds every training example of its ``*_DM_*`` variants on the host (``models/SepReformer_Large_DM_*/dataset.py``:
+``_dynamic_mixing`` picks a second utterance, RMS-normalises it to the first, draws gains and - WHAM / WHAMR - a noise file, crops
+and sums, in librosa + numpy inside ``DataLoader`` workers).  Here the whole corpus lives in HBM (``Corpus``), the random choices of
+a batch are a small table made on the host (``plan_*``, the reference's own draws from a ``random.Random`` in the reference's order)
+and ONE launch (``csrc/sepr_dynmix.hip``) gathers, scales, sums and zero-pads the batch (``DynamicMixFeed``).  The host touches no
+sample.
+
+    corpus = Corpus.from_scp({"s1": "tr_s1.scp", "s2": "tr_s2.scp"}, fs=8000, device="cuda:0")
+    feed = DynamicMixFeed(corpus, plan_wsj0, batch=16, max_len=32000, seed=0, fixed_length=True)
+    step = CapturedTrainStep(model, loss_fn, opt, x, targets)
+    for _ in range(steps):
+        feed.next_into(step.x, step.targets)
+        loss, grad_norm = step(step.x, step.targets)
+
+What is exact: a PCM16 sample is ``int16 / 32768`` (what ``librosa.load`` returns for such a file), its sum of squares an int64, the
+two multiplies and the sum of the terms the reference's float32 operations in the reference's order.  The one thing that is not the
+reference's bit for bit is the RMS: numpy takes it from a pairwise float32 sum, this module from the exact integer sum (a few ulp).
+
+Shuffling: the reference shuffles through ``DataLoader(shuffle=True)`` (torch's generator); this feed takes the epoch's key order
+from the caller (``keys=``), and by default draws a permutation from its own ``random.Random`` before every epoch.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import random
+from typing import Callable, Dict, Iterator, List, NamedTuple, Optional, Sequence, Tuple, Union
+
+import numpy as np
+import torch
+
+from . import lib as L_
+
+Term = Tuple[int, int, np.float32, np.float32]          # (utterance index, start sample, norm factor, gain)
+_ONE = np.float32(1.0)
+
+
+class Example(NamedTuple):
+    key: str
+    n: int                      # output samples (a multiple of 4)
+    mix: Tuple[Term, ...]       # M mixture terms, summed in this order
+    tgt: Tuple[Term, ...]       # S target terms
+
+
+class BatchPlan(NamedTuple):
+    keys: List[str]
+    n: np.ndarray               # int32 [B], descending
+    utt: np.ndarray             # int32 [B, M + S]: the M mixture terms, then the S target terms
+    start: np.ndarray           # int32 [B, M + S]
+    norm: np.ndarray            # float32 [B, M + S]
+    gain: np.ndarray            # float32 [B, M + S]
+    M: int
+    S: int
+
+
+def parse_scp(path: str) -> Dict[str, str]:
+    """The reference's ``key path`` lists (``utils/util_dataset.py::parse_scps``): two tokens per line, no duplicate key."""
+    out: Dict[str, str] = {}
+    with open(path) as f:
+        for line in f:
+            tok = line.strip().split()
+            if not tok:
+                continue
+            if len(tok) != 2:
+                raise RuntimeError(f"{path}: expected 'key path', got {line!r}")
+            if tok[0] in out:
+                raise ValueError(f"{path}: duplicate key {tok[0]!r}")
+            out[tok[0]] = tok[1]
+    return out
+
+
+class Corpus:
+    """Utterances resident on the device: one int16 buffer (PCM16 files as they are on disk), one float32 buffer (everything else),
+    an int64 table ``offsets [N + 1]`` of cumulative element counts on the device, names and lengths on the host.  Storage order:
+    the int16 utterances first, then the float32 ones, each group in the order given; ``index[name]`` is the utterance's number.
+
+    ``device=None`` keeps the layout on the host only (inspectable, not usable by a feed): the energies come from the device
+    (``sepr_corpus_energy``, once at load) or from the caller (``set_energies``, e.g. kept from an earlier load)."""
+
+    def __init__(self, names16, arrays16, names32, arrays32, device=None, fs: Optional[int] = None):
+        self.names: List[str] = list(names16) + list(names32)
+        if not self.names:
+            raise ValueError("an empty corpus")
+        if len(set(self.names)) != len(self.names):
+            raise ValueError("duplicate utterance names")
+        self.n16, self.fs = len(names16), fs
+        self.index: Dict[str, int] = {k: i for i, k in enumerate(self.names)}
+        self.lengths = np.array([int(a.shape[0]) for a in list(arrays16) + list(arrays32)], dtype=np.int64)
+        if int(self.lengths.min()) < 1:
+            raise ValueError("every utterance must hold at least one sample")
+        self.offsets_host = np.concatenate([[0], np.cumsum(self.lengths)]).astype(np.int64)
+        self.total16 = int(self.offsets_host[self.n16])
+        self.total32 = int(self.offsets_host[-1]) - self.total16
+        self.roles: Dict[str, List[str]] = {}            # from_scp: role -> keys in file order
+        self.ss16: Optional[np.ndarray] = None           # int64 [n16] sum of squares of the raw int16 values
+        self.ss32: Optional[np.ndarray] = None           # float64 [N - n16]
+        self._rms: Optional[np.ndarray] = None
+        self.device = None if device is None else torch.device(device)
+        self.buf16 = self.buf32 = self.offsets = None
+        self._host = (list(arrays16), list(arrays32))
+        if self.device is not None:
+            self._upload()
+
+    # ---- construction ------------------------------------------------------------------------------------------------------
+    @classmethod
+    def from_arrays(cls, arrays: Dict[str, np.ndarray], device=None, fs: Optional[int] = None) -> "Corpus":
+        """``arrays``: name -> 1-D int16 or float32 array."""
+        n16, a16, n32, a32 = [], [], [], []
+        for name, a in arrays.items():
+            a = np.asarray(a)
+            if a.ndim != 1 or a.dtype not in (np.int16, np.float32):
+                raise ValueError(f"{name}: expected a 1-D int16 or float32 array, got {a.dtype} {a.shape}")
+            (n16 if a.dtype == np.int16 else n32).append(name)
+            (a16 if a.dtype == np.int16 else a32).append(np.ascontiguousarray(a))
+        return cls(n16, a16, n32, a32, device=device, fs=fs)
+
+    @classmethod
+    def from_scp(cls, scps: Union[Dict[str, str], Sequence[str]], fs: int, device=None, resample: bool = False) -> "Corpus":
+        """Read the reference's ``key path`` lists.  ``scps``: role -> scp file (a sequence gets the roles "0", "1", ...); the
+        utterance of ``key`` in ``role`` is named ``f"{role}/{key}"`` and ``corpus.roles[role]`` lists the keys in file order (what
+        ``random.choice`` draws from).  Files are read with ``infer.load_audio``; one whose samples are all ``k / 32768`` with ``k`` an
+        int16 - every PCM16 file, for which ``librosa.load`` returns exactly that - is stored as int16, anything else as float32.  A
+        file at another rate than ``fs`` raises unless ``resample`` is set, which converts it on the device (``resample.resample``;
+        the result is float32)."""
+        from .infer import load_audio
+        if not isinstance(scps, dict):
+            scps = {str(i): p for i, p in enumerate(scps)}
+        arrays: Dict[str, np.ndarray] = {}
+        roles: Dict[str, List[str]] = {}
+        other: Dict[int, List[str]] = {}
+        for role, scp in scps.items():
+            table = parse_scp(scp)
+            roles[role] = list(table)
+            for key, path in table.items():
+                x, sr = load_audio(path)
+                name = f"{role}/{key}"
+                if sr != int(fs):
+                    if not resample:
+                        raise RuntimeError(f"{path}: sampling rate {sr} != corpus rate {fs} (pass resample=True to convert it)")
+                    other.setdefault(sr, []).append(name)
+                    arrays[name] = x
+                    continue
+                k = x * np.float32(32768.0)
+                pcm = np.clip(k, -32768.0, 32767.0).astype(np.int16)
+                arrays[name] = pcm if np.array_equal(pcm.astype(np.float32), k) else x
+        for sr, names in other.items():
+            from .resample import resample as _resample
+            ys = _resample([torch.from_numpy(arrays[nm]) for nm in names], sr, int(fs), device=device)
+            for nm, y in zip(names, ys):
+                arrays[nm] = y.cpu().numpy()
+        out = cls.from_arrays(arrays, device=device, fs=int(fs))
+        out.roles = roles
+        return out
+
+    def _upload(self) -> None:
+        dev = self.device
+        if dev.type != "cuda" or not torch.cuda.is_available():
+            raise RuntimeError("a Corpus lives on the HIP device (there is no CPU path); device=None keeps the host layout only")
+        a16, a32 = self._host
+
+        def put(arrs, total, dtype, quantum):
+            if not arrs:
+                return None
+            buf = torch.zeros((total + quantum - 1) // quantum * quantum, dtype=dtype, device=dev)      # allocated to a 16-byte multiple
+            pos, group, held = 0, [], 0
+            for a in arrs + [None]:
+                if a is not None:
+                    group.append(a)
+                    held += a.shape[0]
+                if group and (a is None or held >= (1 << 24)):
+                    buf[pos:pos + held].copy_(torch.from_numpy(np.concatenate(group)))
+                    pos, group, held = pos + held, [], 0
+            return buf
+
+        self.buf16 = put(a16, self.total16, torch.int16, 8)
+        self.buf32 = put(a32, self.total32, torch.float32, 4)
+        self.offsets = torch.from_numpy(self.offsets_host).to(dev)
+        self._host = ([], [])
+        lib = L_.load()
+        N, n16 = len(self.names), self.n16
+        ss16 = torch.zeros(max(n16, 1), dtype=torch.int64, device=dev)
+        ss32 = torch.zeros(max(N - n16, 1), dtype=torch.float64, device=dev)
+        ws = torch.empty(lib.sepr_corpus_energy_workspace(N), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            L_.check(lib.sepr_corpus_energy(*self._corpus_args(), ss16.data_ptr(), ss32.data_ptr(), ws.data_ptr(), ws.numel(),
+                                            torch.cuda.current_stream(dev).cuda_stream), "sepr_corpus_energy")
+        self.set_energies(ss16[:n16].cpu().numpy(), ss32[:N - n16].cpu().numpy())      # the N energies, copied to the host once
+
+    def _corpus_args(self):
+        return (self.buf16.data_ptr() if self.buf16 is not None else None, self.total16,
+                self.buf32.data_ptr() if self.buf32 is not None else None, self.total32, self.offsets.data_ptr(), self.n16, len(self.names))
+
+    def set_energies(self, ss16: np.ndarray, ss32: np.ndarray) -> None:
+        ss16, ss32 = np.asarray(ss16, dtype=np.int64), np.asarray(ss32, dtype=np.float64)
+        if ss16.shape != (self.n16,) or ss32.shape != (len(self.names) - self.n16,):
+            raise ValueError("one energy per utterance of each storage format")
+        self.ss16, self.ss32 = ss16, ss32
+        n = self.lengths.astype(np.float64)
+        ms = np.concatenate([ss16.astype(np.float64) / (32768.0 ** 2 * n[:self.n16]), ss32 / n[self.n16:]])
+        self._rms = np.sqrt(ms).astype(np.float32)
+
+    @property
+    def rms(self) -> np.ndarray:
+        """float32 [N]: ``float32(sqrt(ss / (32768^2 n)))`` (int16) / ``float32(sqrt(ss / n))`` (float32), in float64 until the end."""
+        if self._rms is None:
+            raise RuntimeError("the corpus has no energies: they are computed on the HIP device at load (or given with set_energies)")
+        return self._rms
+
+    def __len__(self) -> int:
+        return len(self.names)
+
+    def lookup(self, role: str, key: str) -> int:
+        return self.index[f"{role}/{key}"]
+
+
+# ---- planners: the reference's draws, in the reference's order ----------------------------------------------------------------
+def wsj0_distinct_speakers(key: str, key_random: str) -> bool:
+    """``dataset.py:97-99`` of the WSJ0 variant: neither speaker id (first three letters of the 2nd / 4th ``_`` field) matches."""
+    a, b = key.split('_'), key_random.split('_')
+    return a[1][:3] != b[3][:3] and a[3][:3] != b[1][:3]
+
+
+def _gain(rng: random.Random, lo: float, hi: float) -> np.float32:
+    """``pow(10, -random.uniform(lo, hi) / 20)``; numpy multiplies a float32 array by the float32 value of a Python float."""
+    return np.float32(pow(10, -rng.uniform(lo, hi) / 20))
+
+
+def _norm(ref_rms: np.float32, cur_rms: np.float32) -> np.float32:
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.float32(ref_rms) / np.float32(cur_rms)            # float32 divide, as ``ref_rms / curr_rms`` of two np.float32
+
+
+def plan_wsj0(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs: Sequence[str] = ("s1", "s2"),
+              accept: Callable[[str, str], bool] = wsj0_distinct_speakers, crop: bool = True) -> Example:
+    """``SepReformer_Large_DM_WSJ0/dataset.py:84-139``.  ``crop=False`` is the reference's "test" partition (no ``max_len`` crop)."""
+    keys = corpus.roles[srcs[0]]
+    while True:
+        key_random = rng.choice(keys)
+        if accept(key, key_random):
+            break
+    i1, i2 = (0, 1) if rng.random() > 0.5 else (1, 0)
+    utts = [corpus.lookup(srcs[i1], key), corpus.lookup(srcs[i2], key_random)]
+    ref = corpus.rms[utts[0]]
+    norms = [_norm(ref, corpus.rms[u]) for u in utts]
+    gains = [_gain(rng, -5, 5) for _ in utts]
+    lens = [int(corpus.lengths[u]) for u in utts]
+    min_len = min(lens)
+    starts = [rng.randint(0, ln - min_len) for ln in lens]
+    n = min_len - min_len % 4
+    if crop and n > max_len:
+        st = rng.randint(0, n - max_len)
+        starts, n = [s + st for s in starts], max_len
+    terms = tuple((u, s, nf, g) for u, s, nf, g in zip(utts, starts, norms, gains))
+    return Example(key, n, terms, terms)
+
+
+def plan_wham(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs: Sequence[str] = ("s1", "s2"), noise: str = "noise") -> Example:
+    """``SepReformer_Large_DM_WHAM/dataset.py``: no speaker rule, the noise of ``key`` normalised to the first source with a gain of
+    its own from U(-5, 5) dB, everything cropped to ``min(max_len, lengths)`` at independent random indices."""
+    key_random = rng.choice(corpus.roles[srcs[0]])
+    i1, i2 = (0, 1) if rng.random() > 0.5 else (1, 0)
+    utts = [corpus.lookup(srcs[i1], key), corpus.lookup(srcs[i2], key_random)]
+    ref = corpus.rms[utts[0]]
+    norms = [_norm(ref, corpus.rms[u]) for u in utts]
+    gains = [_gain(rng, -5, 5) for _ in utts]
+    un = corpus.lookup(noise, key)
+    norms.append(_norm(ref, corpus.rms[un]))
+    gains.append(_gain(rng, -5, 5))
+    utts.append(un)
+    lens = [int(corpus.lengths[u]) for u in utts]
+    min_len = min([max_len] + lens)
+    starts = [rng.randint(0, ln - min_len) for ln in lens]
+    n = min_len - min_len % 4
+    terms = tuple((u, s, nf, g) for u, s, nf, g in zip(utts, starts, norms, gains))
+    return Example(key, n, terms, terms[:2])
+
+
+def plan_whamr(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs: Sequence[str] = ("s1", "s2"),
+               reverb: Sequence[str] = ("s1_reverb", "s2_reverb"), noise: str = "noise") -> Example:
+    """``SepReformer_Large_DM_WHAMR/dataset.py:87-154``: the mixture is the two reverberant twins plus the noise (gains U(-3, 3) dB,
+    noise U(-6, 3) dB), the targets are the anechoic sources with their twins' norm factor, gain and crop index."""
+    key_random = rng.choice(corpus.roles[srcs[0]])
+    i1, i2 = (0, 1) if rng.random() > 0.5 else (1, 0)
+    dry = [corpus.lookup(srcs[i1], key), corpus.lookup(srcs[i2], key_random)]
+    wet = [corpus.lookup(reverb[i1], key), corpus.lookup(reverb[i2], key_random)]
+    for d, w in zip(dry, wet):
+        if corpus.lengths[d] != corpus.lengths[w]:
+            raise ValueError(f"{corpus.names[d]} and {corpus.names[w]} differ in length (the reference stacks them)")
+    ref = corpus.rms[dry[0]]
+    norms = [_norm(ref, corpus.rms[u]) for u in dry]
+    gains = [_gain(rng, -3, 3) for _ in dry]
+    un = corpus.lookup(noise, key)
+    nnorm, ngain = _norm(ref, corpus.rms[un]), _gain(rng, -6, 3)
+    lens = [int(corpus.lengths[u]) for u in dry]
+    min_len = min([max_len] + lens + [int(corpus.lengths[un])])
+    starts = [rng.randint(0, ln - min_len) for ln in lens]
+    nstart = rng.randint(0, int(corpus.lengths[un]) - min_len)
+    n = min_len - min_len % 4
+    mix = tuple((u, s, nf, g) for u, s, nf, g in zip(wet, starts, norms, gains)) + ((un, nstart, nnorm, ngain),)
+    tgt = tuple((u, s, nf, g) for u, s, nf, g in zip(dry, starts, norms, gains))
+    return Example(key, n, mix, tgt)
+
+
+def plan_direct(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs: Sequence[str] = ("s1", "s2"), mix: str = "mix",
+                crop: bool = True) -> Example:
+    """``_direct_load``: the fixed mixture file and its sources, norm and gain 1, the ``% 4`` truncation and the ``max_len`` crop.
+    The mixture is one term; the kernel takes ``M >= S`` terms, so it is followed by terms of gain 0, which add exactly nothing."""
+    um = corpus.lookup(mix, key)
+    n = int(corpus.lengths[um])
+    n -= n % 4
+    start = 0
+    if crop and n > max_len:
+        start, n = rng.randint(0, n - max_len), max_len
+    tgt = tuple((corpus.lookup(r, key), start, _ONE, _ONE) for r in srcs)
+    mixt = ((um, start, _ONE, _ONE),) + tuple((um, start, _ONE, np.float32(0.0)) for _ in srcs[1:])
+    return Example(key, n, mixt, tgt)
+
+
+def collate_plan(corpus: Corpus, examples: Sequence[Example]) -> BatchPlan:
+    """Order the examples by length, longest first (``_collate``'s stable ``sorted(..., reverse=True)``), check every term against its
+    utterance and lay the table out as the kernel reads it."""
+    egs = sorted(examples, key=lambda e: e.n, reverse=True)
+    M, S = len(egs[0].mix), len(egs[0].tgt)
+    if not (2 <= S <= 3 and S <= M <= S + 1):
+        raise ValueError(f"{M} mixture terms and {S} target terms: the kernel takes S in 2..3 and M in S..S+1")
+    B = len(egs)
+    utt, start = np.zeros((B, M + S), np.int32), np.zeros((B, M + S), np.int32)
+    norm, gain = np.zeros((B, M + S), np.float32), np.zeros((B, M + S), np.float32)
+    for b, e in enumerate(egs):
+        if len(e.mix) != M or len(e.tgt) != S:
+            raise ValueError("every example of a batch needs the same number of terms")
+        if e.n < 1:
+            raise ValueError(f"{e.key}: an example of {e.n} samples")
+        for j, (u, s, nf, g) in enumerate(e.mix + e.tgt):
+            if not (0 <= u < len(corpus)) or s < 0 or s + e.n > int(corpus.lengths[u]):
+                raise ValueError(f"{e.key}: term {j} reads [{s}, {s + e.n}) of utterance {u}")
+            utt[b, j], start[b, j], norm[b, j], gain[b, j] = u, s, nf, g
+    return BatchPlan([e.key for e in egs], np.array([e.n for e in egs], np.int32), utt, start, norm, gain, M, S)
+
+
+def _table_words(B: int, NT: int) -> int:
+    return 4 * B * NT + B
+
+
+def mix_batch(corpus: Corpus, plan: BatchPlan, Tmax: Optional[int] = None, mix: Optional[torch.Tensor] = None,
+              src: Optional[Sequence[torch.Tensor]] = None, table: Optional[torch.Tensor] = None):
+    """One ``sepr_dynmix_fwd`` launch for ``plan`` on the corpus's device (current stream) -> ``(mix [B, Tmax], [src_s [B, Tmax]])``.
+    ``table``: an int32 device tensor that already holds the plan in the kernel's layout (``DynamicMixFeed`` stages it through pinned
+    memory); without it the plan is copied from pageable memory."""
+    dev = corpus.device
+    if dev is None:
+        raise RuntimeError("the corpus is not on the HIP device (there is no CPU path)")
+    B, NT = plan.utt.shape
+    Tmax = int(Tmax if Tmax is not None else -(-int(plan.n.max()) // 4) * 4)
+    if Tmax % 4 or int(plan.n.max()) > Tmax:
+        raise ValueError(f"Tmax = {Tmax} must be a multiple of 4 and hold the longest example ({int(plan.n.max())})")
+    if table is None:
+        table = torch.from_numpy(pack_table(plan)).to(dev)
+    if mix is None:
+        mix = torch.empty(B, Tmax, dtype=torch.float32, device=dev)
+    if src is None:
+        block = torch.empty(plan.S, B, Tmax, dtype=torch.float32, device=dev)
+        src = [block[s] for s in range(plan.S)]
+    for t in [mix] + list(src):
+        if tuple(t.shape) != (B, Tmax) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"outputs must be contiguous float32 [{B}, {Tmax}] tensors on {dev}")
+    if len(src) != plan.S:
+        raise ValueError(f"{plan.S} target rows expected")
+    base, n = table.data_ptr(), B * NT
+    rows = (C.c_void_p * plan.S)(*[t.data_ptr() for t in src])
+    with torch.cuda.device(dev):
+        L_.check(L_.load().sepr_dynmix_fwd(*corpus._corpus_args(), base, base + 4 * n, base + 8 * n, base + 12 * n, base + 16 * n, B, plan.M,
+                                           plan.S, Tmax, mix.data_ptr(), rows, torch.cuda.current_stream(dev).cuda_stream), "sepr_dynmix_fwd")
+    return mix, list(src)
+
+
+def pack_table(plan: BatchPlan) -> np.ndarray:
+    """The plan as one int32 array ``[utt | start | norm bits | gain bits | n]``."""
+    return np.concatenate([plan.utt.ravel(), plan.start.ravel(), plan.norm.ravel().view(np.int32), plan.gain.ravel().view(np.int32),
+                           plan.n.astype(np.int32)])
+
+
+class DynamicMixFeed:
+    """``for input_sizes, mixture, src, key in feed`` - the reference's ``_collate`` tuple (``input_sizes`` float32 on the host,
+    ``mixture [B, T]`` and the ``S`` tensors ``src[s] [B, T]`` on the device, the keys), one epoch per iteration.
+
+    ``planner(corpus, rng, key, max_len) -> Example`` is one of ``plan_wsj0`` / ``plan_wham`` / ``plan_whamr`` / ``plan_direct`` (bind
+    other role names with ``functools.partial``).  Per batch: plan on the host, write the table into a pinned staging buffer, one
+    asynchronous copy into the static device table, one launch - all on the current stream, nothing waits for the device.
+    ``keys``: the epoch's key order, used as given every epoch; default: the keys of the corpus's first role, permuted with the
+    feed's ``random.Random(seed)`` before each epoch (the same generator then makes the examples' draws).  ``rank`` / ``world``:
+    this rank's contiguous shard of the key order (``dist.shard_range``).  A trailing partial batch is dropped.
+    ``fixed_length``: every row is ``max_len`` samples, shorter examples zero-padded - constant shapes, which a
+    ``CapturedTrainStep`` needs; ``next_into(x, targets)`` then writes the next batch straight into the step's static tensors."""
+
+    SLOTS = 4               # pinned staging buffers in flight
+
+    def __init__(self, corpus: Corpus, planner: Callable[..., Example], batch: int, max_len: int, seed: int = 0,
+                 keys: Optional[Sequence[str]] = None, fixed_length: bool = False, rank: int = 0, world: int = 1):
+        if corpus.device is None:
+            raise RuntimeError("DynamicMixFeed needs a corpus on the HIP device (there is no CPU path)")
+        if batch < 1 or max_len < 4:
+            raise ValueError("batch >= 1 and max_len >= 4")
+        if fixed_length and max_len % 4:
+            raise ValueError("fixed_length needs max_len to be a multiple of 4")
+        from .dist import shard_range
+        shard_range(1, rank, world)                     # validates rank / world
+        self.corpus, self.planner, self.batch, self.max_len = corpus, planner, int(batch), int(max_len)
+        self.fixed_length, self.rank, self.world = bool(fixed_length), rank, world
+        self.rng = random.Random(seed)
+        self.keys = None if keys is None else list(keys)
+        self._default_keys = list(next(iter(corpus.roles.values()))) if corpus.roles else None
+        if self.keys is None and self._default_keys is None:
+            raise ValueError("the corpus has no roles (it was not read from scp lists): pass keys=")
+        self._table = None
+        self._stage: List[torch.Tensor] = []
+        self._events: List[Optional[torch.cuda.Event]] = []
+        self._slot = 0
+        self._epoch: Optional[Iterator[BatchPlan]] = None
+        self.last_plan: Optional[BatchPlan] = None
+
+    # ---- host side ---------------------------------------------------------------------------------------------------------
+    def epoch_order(self) -> List[str]:
+        if self.keys is not None:
+            order = list(self.keys)
+        else:
+            order = list(self._default_keys)
+            self.rng.shuffle(order)
+        from .dist import shard_range
+        lo, hi = shard_range(len(order), self.rank, self.world)
+        return order[lo:hi]
+
+    def plans(self) -> Iterator[BatchPlan]:
+        """The batch plans of one epoch (host only)."""
+        order = self.epoch_order()
+        for i in range(0, len(order) - self.batch + 1, self.batch):
+            yield collate_plan(self.corpus, [self.planner(self.corpus, self.rng, k, self.max_len) for k in order[i:i + self.batch]])
+
+    # ---- device side -------------------------------------------------------------------------------------------------------
+    def _launch(self, plan: BatchPlan, mix=None, src=None):
+        dev = self.corpus.device
+        words = _table_words(*plan.utt.shape)
+        if self._table is None or self._table.numel() != words:
+            self._table = torch.empty(words, dtype=torch.int32, device=dev)
+            self._stage = [torch.empty(words, dtype=torch.int32).pin_memory() for _ in range(self.SLOTS)]
+            self._events = [None] * self.SLOTS
+        k = self._slot
+        self._slot = (k + 1) % self.SLOTS
+        if self._events[k] is not None:
+            self._events[k].synchronize()               # the copy that last read this staging buffer has run (SLOTS batches ago)
+        self._stage[k].numpy()[:] = pack_table(plan)
+        self._table.copy_(self._stage[k], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(dev))
+        self._events[k] = ev
+        self.last_plan = plan
+        return mix_batch(self.corpus, plan, self.max_len if self.fixed_length else None, mix, src, table=self._table)
+
+    def __iter__(self):
+        for plan in self.plans():
+            mix, src = self._launch(plan)
+            yield torch.from_numpy(plan.n.astype(np.float32)), mix, src, plan.keys
+
+    def next_plan(self) -> BatchPlan:
+        """The next batch plan, running on into the next epoch when one ends."""
+        for _ in range(2):
+            if self._epoch is None:
+                self._epoch = self.plans()
+            plan = next(self._epoch, None)
+            if plan is not None:
+                return plan
+            self._epoch = None
+        raise ValueError(f"an epoch of this shard holds fewer than {self.batch} keys")
+
+    def next_into(self, x: torch.Tensor, targets: Sequence[torch.Tensor]) -> BatchPlan:
+        """Write the next batch into ``x [B, max_len]`` and ``targets`` (``S`` tensors ``[B, max_len]``), e.g. ``step.x`` and
+        ``step.targets`` of a ``CapturedTrainStep``.  Returns the plan (``plan.n``: the lengths, ``plan.keys``)."""
+        if not self.fixed_length:
+            raise ValueError("next_into needs fixed_length=True (static tensors have one shape)")
+        plan = self.next_plan()
+        self._launch(plan, x, list(targets)[:plan.S])
+        return plan

@@ -155,6 +155,9 @@ SIGNATURES = {
     "sepr_resample_out_len": (_ll, [_ll, _i, _i]),
     "sepr_resample_workspace": (_sz, [_i]),
     "sepr_resample_fwd": (_i, [_fp, C.POINTER(_ll), _fp, C.POINTER(_ll), _i, _fp, _i, _i, _i, _fp, _sz, _fp]),
+    "sepr_corpus_energy_workspace": (_sz, [_i]),
+    "sepr_corpus_energy": (_i, [_fp, _ll, _fp, _ll, _fp, _i, _i, _fp, _fp, _fp, _sz, _fp]),
+    "sepr_dynmix_fwd": (_i, [_fp, _ll, _fp, _ll, _fp, _i, _i, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _fp, C.POINTER(_fp), _fp]),
     "sepr_pit_sisnr_fwd": (_i, [_fp, _fp, _fp, _i, _i, _i, C.c_double, C.c_double, C.c_double, _fp, _fp, _fp, _fp,
                                 _fp, _sz, _fp]),
     "sepr_train_ctx_bytes": (_sz, [_i] * 8),

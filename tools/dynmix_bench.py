@@ -1,0 +1,245 @@
+#!/usr/bin/env python3
+"""Dynamic-mixing feed beside the training step it feeds (sepreformer_amd/datafeed.py).
+
+  1. device time of one ``sepr_dynmix_fwd`` launch: hipEvents around each of 100 launches after warm-up (median, min, max), B = 16 and
+     32 x 4 s, in the WSJ0 form (2 terms) and the WHAMR form (5 terms), on a synthetic PCM16 corpus resident on the device;
+  2. in the same process: a ``CapturedTrainStep`` loop (Base, bf16, batch 16, the reference's loss, FlatAdamW) on a fixed batch against
+     the same loop fed by ``DynamicMixFeed.next_into`` - alternating, three runs each, ms per step;
+  3. the reference-form numpy mixing (decode, RMS, scale, crop, sum) from RAM-resident int16 arrays on a 16-thread pool, in utt/s
+     (reported only).
+
+Conditions of section 5e: the WHAMR-form launch at B = 16 takes at most 1 % of the fixed-batch step time of THIS run; the mean of the
+fed runs exceeds the mean of the fixed runs by at most the larger within-setting spread (max - min) of this run.
+
+Every step runs in a child process of its own under ``timeout -k 10 <s>``; the first step that fails ends the run.
+
+    python tools/dynmix_bench.py [--out profiles/dynmix_timing.json]
+"""
+import argparse
+import json
+import os
+import random
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+FS, T4S = 8000, 32000
+NKEYS = 48
+STEPS = [("device", 780), ("host", 300)]
+LOOP_STEPS, LOOP_RUNS = 20, 3
+ROLES = ("s1", "s2", "s1_reverb", "s2_reverb", "noise")
+
+
+def _stats(v):
+    v = sorted(v)
+    return {"median": v[len(v) // 2], "min": v[0], "max": v[-1], "mean": sum(v) / len(v)}
+
+
+def synth_corpus_arrays():
+    """name -> int16 array: NKEYS keys x 5 roles of 4.5 - 8 s (pseudo-random PCM16; the kernel's time does not depend on the values)."""
+    import numpy as np
+    rng = np.random.default_rng(0)
+    keys = [f"k{i:03d}a_0.{i:04d}_k{i:03d}b_-0.{i:04d}" for i in range(NKEYS)]
+    arrays = {}
+    for i, k in enumerate(keys):
+        n = int(rng.integers(36000, 64000))
+        for r in ROLES:
+            m = n if r != "noise" else int(rng.integers(36000, 64000))
+            arrays[f"{r}/{k}"] = rng.integers(-6000, 6000, size=m, dtype=np.int16)
+    return keys, arrays
+
+
+def step_device():
+    import functools
+    import numpy as np
+    import torch
+    from sepreformer_amd import datafeed as df
+    from sepreformer_amd.config import VARIANTS
+    from sepreformer_amd.criterion import PIT_SISNR_mag, PIT_SISNR_time
+    from sepreformer_amd.model import Model
+    from sepreformer_amd.optim import FlatAdamW
+    from sepreformer_amd.train_step import CapturedTrainStep
+    dev = torch.device("cuda:0")
+    keys, arrays = synth_corpus_arrays()
+    corpus = df.Corpus.from_arrays(arrays, device=dev, fs=FS)
+    corpus.roles = {r: list(keys) for r in ROLES}
+    forms = {"wsj0": functools.partial(df.plan_wsj0, accept=lambda a, b: True), "whamr": df.plan_whamr}
+    kernel = []
+    for form, planner in forms.items():
+        for B in (16, 32):
+            rng = random.Random(B)
+            plan = df.collate_plan(corpus, [planner(corpus, rng, keys[i % NKEYS], T4S) for i in range(B)])
+            table = torch.from_numpy(df.pack_table(plan)).to(dev)
+            mix = torch.empty(B, T4S, device=dev)
+            src = [torch.empty(B, T4S, device=dev) for _ in range(plan.S)]
+            ms = []
+            for i in range(20 + 100):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                df.mix_batch(corpus, plan, T4S, mix, src, table=table)
+                e1.record()
+                torch.cuda.synchronize()
+                if i >= 20:
+                    ms.append(e0.elapsed_time(e1))
+            # and back to back, without an event pair per launch
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(100):
+                df.mix_batch(corpus, plan, T4S, mix, src, table=table)
+            e1.record()
+            torch.cuda.synchronize()
+            terms = plan.M + (0 if form == "wsj0" else plan.S)
+            nbytes = int(plan.n.sum()) * 2 * terms + B * T4S * 4 * (1 + plan.S)
+            med = _stats(ms)["median"]
+            kernel.append({"form": form, "B": B, "samples": T4S, "terms_read": terms, "device_ms": _stats(ms), "launches": 100,
+                           "back_to_back_ms_per_launch": e0.elapsed_time(e1) / 100, "algorithmic_bytes": nbytes,
+                           "GBs_at_median": nbytes / (med * 1e-3) / 1e9})
+    # ---- the training step: fixed batch against fed, same process, alternating
+    B = 16
+    cfg = VARIANTS["SepReformer_Base_WSJ0"]
+    torch.manual_seed(0)
+    model = Model.from_config(cfg, init_seed=0, precision="bf16").load_synthetic_(0).to(dev).train()
+    crit_t = PIT_SISNR_time(dev, cfg.num_spks, True)
+    crit_m = PIT_SISNR_mag(dev, 512, 128, "hann", cfg.num_stages, cfg.num_spks, True, False)
+    sizes = torch.full((B,), T4S)
+    opt = FlatAdamW(model, lr=1.0e-4, weight_decay=1.0e-2)
+
+    def loss_fn(audio, aux, *tg):
+        tg = list(tg)
+        l_time = crit_t(estims=audio, input_sizes=sizes, target_attr=tg)
+        l_mag = [crit_m(estims=a, idx=i, input_sizes=sizes, target_attr=tg) for i, a in enumerate(aux)]
+        return (0.6 * l_time + 0.4 * sum(l_mag) / len(l_mag)) / cfg.num_spks
+
+    feed = df.DynamicMixFeed(corpus, df.plan_whamr, batch=B, max_len=T4S, seed=0, fixed_length=True)
+    x = torch.zeros(B, T4S, device=dev)
+    tg = [torch.zeros(B, T4S, device=dev) for _ in range(2)]
+    feed.next_into(x, tg)
+    step = CapturedTrainStep(model, loss_fn, opt, x, tg, max_norm=5.0, warmup=2)
+    fx, ftg = step.x.clone(), [t.clone() for t in step.targets]
+
+    def loop(fed):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(LOOP_STEPS):
+            if fed:
+                feed.next_into(step.x, step.targets)
+                loss, _ = step(step.x, step.targets)
+            else:
+                loss, _ = step(fx, ftg)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / LOOP_STEPS, float(loss.detach())
+
+    loop(False), loop(True)                                                   # warm both paths
+    fixed, fedr, losses = [], [], []
+    for _ in range(LOOP_RUNS):
+        ms, _ = loop(False)
+        fixed.append(ms)
+        ms, ls = loop(True)
+        fedr.append(ms)
+        losses.append(ls)
+    # host cost of planning + staging one batch on its own
+    t0 = time.perf_counter()
+    for _ in range(50):
+        feed.next_plan()
+    plan_ms = (time.perf_counter() - t0) * 1e3 / 50
+    step.release()
+    assert all(np.isfinite(v) for v in losses)
+    return {"device": torch.cuda.get_device_name(0), "kernel": kernel,
+            "loop": {"model": "SepReformer_Base_WSJ0 bf16, batch 16 x 4 s, CapturedTrainStep + FlatAdamW, the reference's loss", "steps_per_run": LOOP_STEPS,
+                     "fixed_ms_per_step": fixed, "fed_ms_per_step": fedr, "fed_form": "whamr", "fed_last_losses": losses,
+                     "host_plan_ms_per_batch": plan_ms}}
+
+
+def step_host():
+    """The reference's per-example work in numpy from RAM-resident arrays (no disk, no decoding of a file): WHAMR form."""
+    from concurrent.futures import ThreadPoolExecutor
+    import numpy as np
+    keys, arrays = synth_corpus_arrays()
+
+    def load(name):
+        return arrays[name].astype(np.float32) / np.float32(32768.0)
+
+    def example(i):
+        rng = random.Random(i)
+        key, other = keys[i % NKEYS], rng.choice(keys)
+        dry = [load(f"s1/{key}"), load(f"s2/{other}")]
+        wet = [load(f"s1_reverb/{key}"), load(f"s2_reverb/{other}")]
+        ref = np.sqrt(np.mean(np.square(dry[0])))
+        lens = [T4S]
+        for d, w in zip(dry, wet):
+            nf = ref / np.sqrt(np.mean(np.square(d)))
+            d *= nf
+            w *= nf
+            g = pow(10, -rng.uniform(-3, 3) / 20)
+            d *= np.float32(g)
+            w *= np.float32(g)
+            lens.append(len(d))
+        noise = load(f"noise/{key}")
+        noise *= ref / np.sqrt(np.mean(np.square(noise)))
+        noise = noise * pow(10, -rng.uniform(-6, 3) / 20)
+        n = min(lens + [len(noise)])
+        out = []
+        for d, w in zip(dry, wet):
+            s = rng.randint(0, len(d) - n)
+            out.append((w[s:s + n], d[s:s + n]))
+        s = rng.randint(0, len(noise) - n)
+        mix = out[0][0] + out[1][0] + noise[s:s + n]
+        return mix, [o[1] for o in out]
+
+    N = 512
+    with ThreadPoolExecutor(16) as pool:
+        list(pool.map(example, range(32)))
+        t0 = time.perf_counter()
+        list(pool.map(example, range(N)))
+        dt = time.perf_counter() - t0
+    return {"host_numpy": {"threads": 16, "examples": N, "utt_per_s": N / dt, "form": "whamr, from RAM-resident int16 arrays, no collate"}}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--step", default=None, help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    if args.step:
+        rec = {"device": step_device, "host": step_host}[args.step]()
+        print("__RESULT__" + json.dumps(rec))
+        return
+    rec, failed = {}, None
+    for name, limit in STEPS:
+        cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", name]
+        r = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("__RESULT__")]
+        if r.returncode != 0 or not lines:
+            failed = {"step": name, "returncode": r.returncode, "stderr_tail": r.stderr[-1500:]}
+            print(json.dumps(failed), file=sys.stderr)
+            break                                                          # nothing more runs on the device after a failure
+        rec.update(json.loads(lines[-1][len("__RESULT__"):]))
+        print(name, "done", flush=True)
+    if not failed:
+        lp = rec["loop"]
+        fixed, fed = lp["fixed_ms_per_step"], lp["fed_ms_per_step"]
+        mean = lambda v: sum(v) / len(v)                                    # noqa: E731
+        k = next(r for r in rec["kernel"] if r["form"] == "whamr" and r["B"] == 16)
+        spread = max(max(fixed) - min(fixed), max(fed) - min(fed))
+        rec["conditions"] = {
+            "launch_at_most_1pct_of_step": {"launch_ms_median": k["device_ms"]["median"], "fixed_step_ms_mean": mean(fixed),
+                                            "fraction": k["device_ms"]["median"] / mean(fixed), "met": k["device_ms"]["median"] <= 0.01 * mean(fixed)},
+            "fed_vs_fixed": {"fixed_mean_ms": mean(fixed), "fed_mean_ms": mean(fed), "difference_ms": mean(fed) - mean(fixed),
+                             "larger_within_setting_spread_ms": spread, "met": mean(fed) - mean(fixed) <= spread},
+            "utt_per_s": {"step_fixed": 16 / mean(fixed) * 1e3, "step_fed": 16 / mean(fed) * 1e3, "host_numpy_16_threads": rec["host_numpy"]["utt_per_s"]}}
+    if failed:
+        rec["failed"] = failed
+    line = json.dumps(rec)
+    print(line)
+    if args.out and not failed:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        open(args.out, "w").write(line + "\n")
+    sys.exit(1 if failed else 0)
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,82 @@
+#!/usr/bin/env python3
+"""Train a DM variant on real wav files at the captured step's rate: corpus on the device, dynamic mixing in one launch per batch
+(sepreformer_amd/datafeed.py), ``CapturedTrainStep`` + ``FlatAdamW``, the reference's 0.6 / 0.4 loss.  Prints the
+loss and utt/s every ``--log`` steps.  Schedulers, checkpoints and validation are not part of it.
+
+    python tools/train_from_scp.py --form wsj0 --scp s1=tr_s1.scp s2=tr_s2.scp --steps 200
+    python tools/train_from_scp.py --form whamr --scp s1=.. s2=.. s1_reverb=.. s2_reverb=.. noise=.. --model SepReformer_Large_DM_WHAMR
+"""
+import argparse
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--form", choices=["wsj0", "wham", "whamr", "direct"], required=True)
+    ap.add_argument("--scp", nargs="+", required=True, metavar="ROLE=FILE", help="roles: s1 s2 [mix] [noise] [s1_reverb s2_reverb]")
+    ap.add_argument("--model", default="SepReformer_Large_DM_WSJ0")
+    ap.add_argument("--precision", default="bf16")
+    ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--max-len", type=int, default=32000)
+    ap.add_argument("--fs", type=int, default=8000)
+    ap.add_argument("--resample", action="store_true", help="convert files at another rate on the device (default: an error)")
+    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--log", type=int, default=10)
+    ap.add_argument("--lr", type=float, default=1.0e-4)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--device", default="cuda:0")
+    args = ap.parse_args()
+
+    import torch
+    from sepreformer_amd import datafeed as df
+    from sepreformer_amd.config import VARIANTS
+    from sepreformer_amd.criterion import PIT_SISNR_mag, PIT_SISNR_time
+    from sepreformer_amd.model import Model
+    from sepreformer_amd.optim import FlatAdamW
+    from sepreformer_amd.train_step import CapturedTrainStep
+
+    dev = torch.device(args.device)
+    torch.cuda.set_device(dev)
+    torch.manual_seed(args.seed)
+    corpus = df.Corpus.from_scp(dict(a.split("=", 1) for a in args.scp), fs=args.fs, device=dev, resample=args.resample)
+    planner = {"wsj0": df.plan_wsj0, "wham": df.plan_wham, "whamr": df.plan_whamr, "direct": df.plan_direct}[args.form]
+    feed = df.DynamicMixFeed(corpus, planner, batch=args.batch, max_len=args.max_len, seed=args.seed, fixed_length=True)
+    print(f"corpus: {len(corpus)} utterances, {corpus.total16 * 2 + corpus.total32 * 4} bytes on {dev}", flush=True)
+
+    cfg = VARIANTS[args.model]
+    model = Model.from_config(cfg, init_seed=args.seed, precision=args.precision).to(dev).train()
+    crit_t = PIT_SISNR_time(dev, cfg.num_spks, True)
+    crit_m = PIT_SISNR_mag(dev, 512, 128, "hann", cfg.num_stages, cfg.num_spks, True, False)
+    sizes = torch.full((args.batch,), args.max_len)                           # fixed-length rows: the padding is part of the example
+    opt = FlatAdamW(model, lr=args.lr, weight_decay=1.0e-2)
+
+    def loss_fn(audio, aux, *tg):
+        tg = list(tg)
+        l_time = crit_t(estims=audio, input_sizes=sizes, target_attr=tg)
+        l_mag = [crit_m(estims=a, idx=i, input_sizes=sizes, target_attr=tg) for i, a in enumerate(aux)]
+        return (0.6 * l_time + 0.4 * sum(l_mag) / len(l_mag)) / cfg.num_spks
+
+    x = torch.zeros(args.batch, args.max_len, device=dev)
+    targets = [torch.zeros(args.batch, args.max_len, device=dev) for _ in range(cfg.num_spks)]
+    feed.next_into(x, targets)
+    step = CapturedTrainStep(model, loss_fn, opt, x, targets, max_norm=5.0)
+    torch.cuda.synchronize()
+    t0, done = time.perf_counter(), 0
+    for i in range(1, args.steps + 1):
+        feed.next_into(step.x, step.targets)
+        loss, gn = step(step.x, step.targets)
+        if i % args.log == 0 or i == args.steps:
+            val = float(loss.detach())                                        # synchronises: once per log interval
+            dt = time.perf_counter() - t0
+            print(f"step {i}: loss {val:.4f}  grad norm {float(gn):.3f}  {args.batch * (i - done) / dt:.1f} utt/s", flush=True)
+            t0, done = time.perf_counter(), i
+    step.release()
+
+
+if __name__ == "__main__":
+    main()
