@@ -352,6 +352,31 @@ int sepr_bss_eval_fwd(const float* est, const float* ref, const float* mix, cons
                       double* sdr, double* sir, double* sar, int* perm, double* sdr_mix, int* status, void* ws,
                       size_t ws_bytes, sepr_stream_t stream);
 
+/* STOI and ESTOI, the intelligibility measures of Taal et al. 2011 and Jensen & Taal 2016 (the definition restates
+ * pystoi 0.3.3 and is given in full in section 5f and tests/stoi_ref.py) - evaluation only, no backward.
+ * Inputs are float32 on the device and ALREADY AT 10 kHz: ref [B][S][T], est [B][S][T], mix [B][T] or NULL (then stoi_mix and estoi_mix
+ * must be NULL too, and both must be given with a mixture), lengths [B] DEVICE int32 valid samples (clamped to [0, T]; samples beyond
+ * are never read).  2 <= S <= 3, T >= 256, B S (S + 2) <= 65535.  tables: DEVICE float64 [256 + 2 * 256 * 212], built by the host once
+ * (sepreformer_amd/criterion.py::stoi_tables): w[t] = hanning(258)[1 + t], then for t < 256 and k < 212 the pair
+ * (cos, sin)(2 pi ((7 + k) t mod 512) / 512) at tables[256 + 2 (212 t + k)]; 16-byte aligned.
+ * Per (b, reference i): frames x[128 k .. 128 k + 256) w while 128 k <= len - 256; e_k = 20 log10(||frame_k|| + 2^-52); frame k is kept iff
+ * max(e) - 40 - e_k < 0; the kept frames of the reference - and the frames of every processed signal at the same indices - are
+ * overlap-added at hop 128, framed again (kept - 1 frames, windowed a second time) and transformed at 512 points; band value b =
+ * sqrt(sum |X|^2 over bins [lo_b, hi_b)), the bins of linspace(0, 10000, 513) nearest to 150 * 2^((2 b -+ 1) / 6), b < 15.  Over all
+ * segments of 30 consecutive frames: STOI = mean of the row-normalised correlations of X and min(Y ||X_row|| / (||Y_row|| + eps),
+ * X (1 + 10^(15 / 20))); ESTOI = mean of the correlations after row- then column-normalisation.  All arithmetic is float64.
+ * Outputs: stoi, estoi [B][S][S] float64, entry (i, j) = reference i against estimate j; stoi_mix, estoi_mix [B][S] = reference i
+ * against the mixture; kept [B][S] int32 = kept frames of reference i; status [B][S] int32, bit 0 = "too short" (fewer than 30 spectral
+ * frames: the values of that reference are 1e-5, as the package returns them with a warning).  Bit-identical from run to run, and an
+ * utterance's values do not depend on what else is in the call.  No atomics, no host synchronisation or allocation (capturable: the
+ * grids are sized by T, never by a count read back from the device).  Every argument check returns SEPR_EINVAL (SEPR_EWORKSPACE for a
+ * short workspace) before any HIP call.  Workspace: sepr_stoi_workspace(S, B, T) bytes (0 for unsupported arguments), about
+ * 15 (S + 2) S doubles per frame of T. */
+size_t sepr_stoi_workspace(int S, int B, int T);
+int sepr_stoi_fwd(const float* ref, const float* est, const float* mix, const int* lengths, int S, int B, int T, const double* tables,
+                  double* stoi, double* estoi, double* stoi_mix, double* estoi_mix, int* kept, int* status, void* ws, size_t ws_bytes,
+                  sepr_stream_t stream);
+
 /* Long-form separation (the reference has no long-form mode): boundary alignment and overlap-add of the
  * separator's outputs on overlapping windows.  R recordings; recording r has lengths[r] = T_r >= 1 samples and
  * Nc_r = 1 (T_r <= W) or 1 + ceil((T_r - W) / H) windows of W samples at hop H = W - O, window k covering [kH, kH + W); its

@@ -9,6 +9,8 @@ Mirrors ``utils/implements/criterions.py`` of the reference (SURVEY.md section 8
 * ``PIT_SDRi(device, dump)(estims=..., mixture=..., input_sizes=..., target_attr=...)`` -> ``(sum of SDRi / num_utts, SDRi per
   reference)`` (reference :264-289, called by ``engine.py:133``) on ``bss_eval_sources``, mir_eval's BSS-eval in float64 on the
   device (``csrc/sepr_bsseval.hip`` through ``sepr_bss_eval_fwd``; the CPU restatement is ``tests/bss_eval_ref.py``).
+* ``PIT_STOI(device, extended)`` with the same call surface -> the STOI / ESTOI improvement over the mixture (beyond the reference;
+  ``csrc/sepr_stoi.hip`` through ``sepr_stoi_fwd``; the CPU restatement is ``tests/stoi_ref.py``).
 
 ``estims`` / ``target_attr`` are lists of ``[B,T]`` tensors (or one ``[S,B,T]`` tensor) on the HIP device.  The
 arithmetic is one pass over the waveforms in ``csrc/sepr_criterion.hip`` through ``sepr_pit_sisnr_fwd``; there is no
@@ -386,3 +388,145 @@ class PIT_SDRi:
         sdri = out["sdr"] - out["sdr_mix"]
         num_utts = input_sizes.shape[0]
         return np.sum(sdri) / num_utts, (sdri[0] if B == 1 else sdri)
+
+
+# ---- STOI / ESTOI (beyond the reference, which reports SI-SNRi and SDRi only) --------------------------------
+STOI_FS = 10000                    # the rate the measure is defined at
+STOI_FRAME, STOI_BIN0, STOI_NBIN = 256, 7, 212
+STOI_WS_CAP = 1 << 30              # one call's workspace stays under 1 GiB: larger batches are split
+_stoi_tables = {}
+
+
+def stoi_tables(device) -> torch.Tensor:
+    """The constants ``sepr_stoi_fwd`` reads (include/sepr.h), float64 on ``device``: the window ``hanning(258)[1:-1]`` and the twiddle
+    pairs ``(cos, sin)(2 pi ((7 + k) t mod 512) / 512)`` for t < 256, k < 212 - the argument is reduced in integers first."""
+    import numpy as np
+    key = str(device)
+    if key not in _stoi_tables:
+        t = np.arange(STOI_FRAME, dtype=np.int64)[:, None]
+        k = STOI_BIN0 + np.arange(STOI_NBIN, dtype=np.int64)[None, :]
+        ang = 2.0 * np.pi * ((k * t) % 512).astype(np.float64) / 512.0
+        tab = np.concatenate([np.hanning(STOI_FRAME + 2)[1:-1], np.stack([np.cos(ang), np.sin(ang)], axis=2).ravel()])
+        _stoi_tables[key] = torch.from_numpy(tab).to(device)
+    return _stoi_tables[key]
+
+
+def stoi(references: torch.Tensor, estimates: torch.Tensor, mixture: torch.Tensor = None, lengths=None, fs: int = 8000):
+    """STOI and ESTOI of every (reference, estimate) pair on the device: references / estimates ``[S,B,T]``, mixture ``[B,T]`` or None,
+    lengths ``[B]`` valid samples (default T), all sampled at ``fs``.  Signals at another rate than 10 kHz go through the measure's own
+    converter first (``resample.plan_oct``, one ``sepr_resample_fwd`` launch), then ``sepr_stoi_fwd`` (``csrc/sepr_stoi.hip``).  Returns a
+    dict of device tensors: ``stoi``, ``estoi`` float64 ``[B,S,S]`` (entry (i, j): reference i against estimate j), ``stoi_mix``,
+    ``estoi_mix`` float64 ``[B,S]`` when a mixture is given, ``kept`` int32 ``[B,S]`` (frames of reference i that are not silent) and
+    ``status`` int32 ``[B,S]`` (bit 0: fewer than 30 frames left, the values of that reference are 1e-5)."""
+    from .resample import out_len, plan_oct, resample_oct
+    ref, est = _bss_stack(references, "references"), _bss_stack(estimates, "estimates")
+    if ref.dim() != 3 or ref.shape != est.shape:
+        raise ValueError(f"references {tuple(ref.shape)} and estimates {tuple(est.shape)} must both be [S,B,T]")
+    S, B, T = ref.shape
+    dev = ref.device
+    if est.device != dev:
+        raise RuntimeError("estimates and references are on different devices")
+    if not 2 <= S <= 3:
+        raise ValueError(f"num_spks={S}: the device STOI supports 2 or 3 sources")
+    mix = None
+    if mixture is not None:
+        mix = _bss_stack(mixture, "mixture")
+        if tuple(mix.shape) != (B, T) or mix.device != dev:
+            raise RuntimeError("mixture must be [batch, samples] on the same device as the estimates")
+    lens = [T] * B if lengths is None else [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+    if len(lens) != B:
+        raise ValueError(f"{len(lens)} lengths for a batch of {B}")
+    for b, n in enumerate(lens):
+        if not 1 <= n <= T:
+            raise ValueError(f"utterance {b}: valid length {n} outside [1, {T}]")
+    fs = int(fs)
+    sig = torch.cat([ref.permute(1, 0, 2), est.permute(1, 0, 2)] + ([] if mix is None else [mix[:, None]]), dim=1)   # [B][2S(+1)][T]
+    Q = sig.shape[1]
+    if fs != STOI_FS:                                   # the 10 kHz signals, ragged, then back into one zero-padded block
+        p = plan_oct(fs, STOI_FS)
+        lens10 = [out_len(n, p.L, p.M) for n in lens]
+        T10 = max(max(lens10), STOI_FRAME)
+        parts = resample_oct([sig[b, q, :lens[b]].contiguous() for b in range(B) for q in range(Q)], fs, STOI_FS)
+        if min(lens10) == T10:
+            sig = torch.stack(parts).view(B, Q, T10)
+        else:
+            sig = torch.zeros(B, Q, T10, dtype=torch.float32, device=dev)
+            for b in range(B):
+                for q in range(Q):
+                    sig[b, q, :lens10[b]] = parts[b * Q + q]
+        lens, T = lens10, T10
+    elif T < STOI_FRAME:
+        sig = torch.nn.functional.pad(sig, (0, STOI_FRAME - T))
+        T = STOI_FRAME
+    lib = L.load()
+    tab = stoi_tables(dev)
+    out = {"stoi": torch.empty(B, S, S, dtype=torch.float64, device=dev), "estoi": torch.empty(B, S, S, dtype=torch.float64, device=dev),
+           "kept": torch.empty(B, S, dtype=torch.int32, device=dev), "status": torch.empty(B, S, dtype=torch.int32, device=dev)}
+    if mix is not None:
+        out["stoi_mix"] = torch.empty(B, S, dtype=torch.float64, device=dev)
+        out["estoi_mix"] = torch.empty(B, S, dtype=torch.float64, device=dev)
+    per_utt = lib.sepr_stoi_workspace(S, 1, T)
+    if per_utt == 0:
+        raise ValueError(f"unsupported STOI problem: num_spks={S}, samples={T}")
+    step = max(1, min(B, STOI_WS_CAP // per_utt, 65535 // (S * (S + 2))))
+    lens_d = torch.tensor(lens, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        for b0 in range(0, B, step):
+            n = min(step, B - b0)
+            r, e = sig[b0:b0 + n, :S].contiguous(), sig[b0:b0 + n, S:2 * S].contiguous()
+            m = None if mix is None else sig[b0:b0 + n, 2 * S].contiguous()
+            ws = torch.empty(lib.sepr_stoi_workspace(S, n, T), dtype=torch.uint8, device=dev)
+            o = {k: v[b0:b0 + n] for k, v in out.items()}                       # leading-dimension slices are contiguous views
+            L.check(lib.sepr_stoi_fwd(r.data_ptr(), e.data_ptr(), None if m is None else m.data_ptr(), lens_d[b0:b0 + n].data_ptr(), S, n, T,
+                                      tab.data_ptr(), o["stoi"].data_ptr(), o["estoi"].data_ptr(),
+                                      None if m is None else o["stoi_mix"].data_ptr(), None if m is None else o["estoi_mix"].data_ptr(),
+                                      o["kept"].data_ptr(), o["status"].data_ptr(), ws.data_ptr(), ws.numel(), stream.cuda_stream),
+                    "sepr_stoi_fwd")
+    return out
+
+
+def stoi_pit(values, values_mix):
+    """values ``[B,S,S]`` (reference i, estimate j) and values_mix ``[B,S]`` as numpy float64 -> ``(perm [B,S], chosen [B,S], improvement
+    [B,S])`` indexed by reference: per utterance the first maximiser of the mean over ``itertools.permutations``."""
+    import itertools
+    import numpy as np
+    B, S, _ = values.shape
+    perms = list(itertools.permutations(range(S)))
+    k = np.arange(S)
+    perm = np.empty((B, S), np.int64)
+    for b in range(B):
+        perm[b] = perms[int(np.argmax([np.mean(values[b, k, list(p)]) for p in perms]))]
+    chosen = np.take_along_axis(values, perm[:, :, None], axis=2)[:, :, 0]
+    return perm, chosen, chosen - values_mix
+
+
+class PIT_STOI:
+    """``PIT_STOI(device, extended=False, fs=8000)`` with the criteria's call surface: ``__call__(estims=, mixture=, input_sizes=,
+    target_attr=)`` -> ``(sum of the improvements / num_utts, improvement per reference)`` with improvement = STOI (ESTOI when
+    ``extended``) of the chosen estimate minus that of the mixture, on the device (``stoi`` above).  The permutation is the first
+    maximiser of the mean value over ``itertools.permutations``; values are indexed by reference, as ``PIT_SDRi`` indexes them.  The
+    last call's permutation and values stay in ``perm`` / ``values``.  Evaluation only: there is no backward."""
+
+    def __init__(self, device, extended: bool = False, fs: int = 8000):
+        self.device, self.extended, self.fs = torch.device(device), bool(extended), int(fs)
+        self.perm = self.values = None
+
+    def __repr__(self):
+        return f"<PIT_STOI(device={self.device!r}, extended={self.extended!r}, fs={self.fs!r})>"
+
+    def __call__(self, **kwargs):
+        import numpy as np
+        if self.device.type != "cuda":
+            raise RuntimeError("PIT_STOI was built for a non-HIP device (no CPU fallback exists)")
+        est = _bss_stack(kwargs["estims"], "estims").to(self.device)
+        tgt = _bss_stack([t.to(self.device) for t in kwargs["target_attr"]] if not isinstance(kwargs["target_attr"], torch.Tensor)
+                         else kwargs["target_attr"].to(self.device), "target_attr")
+        mix = kwargs["mixture"].to(self.device)
+        input_sizes = kwargs["input_sizes"]
+        B = est.shape[1]
+        lengths = input_sizes.reshape(-1).tolist() if input_sizes.numel() == B else None
+        out = stoi(tgt, est, mixture=mix.reshape(B, -1), lengths=lengths, fs=self.fs)
+        key = "estoi" if self.extended else "stoi"
+        self.perm, self.values, imp = stoi_pit(out[key].cpu().numpy(), out[key + "_mix"].cpu().numpy())
+        return np.sum(imp) / input_sizes.shape[0], (imp[0] if B == 1 else imp)

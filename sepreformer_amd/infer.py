@@ -9,6 +9,8 @@ Mirrors ``models/SepReformer_Base_WSJ0/engine.py``:
   (eps 1e-15) and ``PIT_SDRi`` (mir_eval's BSS-eval on the CPU in the reference; float64 HIP kernels here), one row per
   utterance in each of the two csv files, running means divided by ``num_spks``, optional ``0.5 / max|.|`` wav dumps;
 * ``test_utterances`` - its SI-SNRi half alone (same loop, no SDRi);
+* ``evaluate_utterances_all`` - beyond the reference: the same loop with STOI and ESTOI of the estimates beside SI-SNRi and SDRi
+  (``criterion.stoi``, DESIGN.md section 5f);
 * ``separate_long`` / ``separate_long_file`` - beyond the reference: recordings of any length by overlapping windows of the
   training length, batched through the separator and stitched on the device (``longform.py``).
 
@@ -145,15 +147,18 @@ def separate_long_file(model, path: str, fs: int = 8000, out_prefix: Optional[st
     return _write_outputs(model, out_prefix if out_prefix is not None else path[:-4], file_mix, sr, mix, est, fs, out_rate)
 
 
-def _test_loop(model, utterances, sisnr_csv_path, sdr_csv_path, wav_dir, fs, with_sdr):
+def _test_loop(model, utterances, sisnr_csv_path, sdr_csv_path, wav_dir, fs, with_sdr, stoi_csv_paths=None, stoi_out=None):
     """``Engine._test`` (engine.py:113-149): one utterance per step; PIT_SISNRi (eps 1e-15) and, when ``with_sdr``,
-    PIT_SDRi; one csv row per utterance and criterion; running means divided by ``num_spks``; optional wav dumps."""
-    from .criterion import PIT_SDRi, PIT_SISNRi
+    PIT_SDRi; one csv row per utterance and criterion; running means divided by ``num_spks``; optional wav dumps.
+    ``stoi_out`` (a dict, ``evaluate_utterances_all``): STOI and ESTOI of the same estimates as well, one ``criterion.stoi`` call per
+    utterance, rows to ``stoi_csv_paths`` = (STOI file, ESTOI file), the running means into the dict."""
+    from .criterion import PIT_SDRi, PIT_SISNRi, stoi, stoi_pit
     dev = next(model.parameters()).device
     crit = PIT_SISNRi(dev, model.num_spks, True)
     crit_sdr = PIT_SDRi(dev, 0) if with_sdr else None
     total, total_sdr, n = 0.0, 0.0, 0
-    files = [open(p, "w", newline="") if p else None for p in (sisnr_csv_path, sdr_csv_path)]
+    tot_stoi = np.zeros(4)                                                  # STOI, ESTOI, and their improvements over the mixture
+    files = [open(p, "w", newline="") if p else None for p in (sisnr_csv_path, sdr_csv_path) + tuple(stoi_csv_paths or (None, None))]
     writers = [csv.writer(fh, quotechar="|", quoting=csv.QUOTE_MINIMAL) if fh else None for fh in files]
     try:
         for mixture, sources, key in utterances:
@@ -174,6 +179,15 @@ def _test_loop(model, utterances, sisnr_csv_path, sdr_csv_path, wav_dir, fs, wit
                 writers[0].writerow([name] + [float(per[i]) for i in range(model.num_spks)])
             if writers[1] and per_sdr is not None:
                 writers[1].writerow([name] + [per_sdr[i].item() for i in range(model.num_spks)])
+            if stoi_out is not None:
+                out = stoi(torch.stack([t[0] for t in targets])[:, None], torch.stack([e[0] for e in est])[:, None],
+                           mixture=mixture.to(dev), fs=fs)
+                for k, key in enumerate(("stoi", "estoi")):
+                    _, val, imp = stoi_pit(out[key].cpu().numpy(), out[key + "_mix"].cpu().numpy())
+                    tot_stoi[k] += val[0].sum() / model.num_spks
+                    tot_stoi[2 + k] += imp[0].sum() / model.num_spks
+                    if writers[2 + k]:
+                        writers[2 + k].writerow([name] + [float(v) for v in val[0]])
             if wav_dir:
                 os.makedirs(wav_dir, exist_ok=True)
                 write_wav(os.path.join(wav_dir, f"{name}{n - 1}_mixture.wav"), peak_normalise(mixture[0].cpu().numpy(), 0.5), fs)
@@ -183,6 +197,8 @@ def _test_loop(model, utterances, sisnr_csv_path, sdr_csv_path, wav_dir, fs, wit
         for fh in files:
             if fh:
                 fh.close()
+    if stoi_out is not None:
+        stoi_out.update(zip(("stoi", "estoi", "stoi_i", "estoi_i"), (tot_stoi / n if n else tot_stoi).tolist()))
     return (total / n if n else 0.0), (total_sdr / n if n else 0.0), n
 
 
@@ -202,6 +218,21 @@ def evaluate_utterances(model, utterances: Iterable[Tuple[torch.Tensor, Sequence
     (``test_SISNRi_value.csv`` / ``test_SDRi_value.csv`` in the reference) and the ``0.5 / max|.|`` wav dumps of test_save.
     SDRi rows are indexed by reference source (mir_eval's order), SI-SNRi rows by estimate."""
     return _test_loop(model, utterances, sisnr_csv_path, sdr_csv_path, wav_dir, fs, with_sdr=True)
+
+
+def evaluate_utterances_all(model, utterances: Iterable[Tuple[torch.Tensor, Sequence[torch.Tensor], str]],
+                            sisnr_csv_path: Optional[str] = None, sdr_csv_path: Optional[str] = None,
+                            stoi_csv_path: Optional[str] = None, estoi_csv_path: Optional[str] = None,
+                            wav_dir: Optional[str] = None, fs: int = 8000) -> dict:
+    """``evaluate_utterances`` plus intelligibility: the same loop, the same SI-SNRi and SDRi, and STOI / ESTOI of
+    the same estimates on the device.  Returns ``{"sisnri", "sdri", "stoi", "estoi", "stoi_i", "estoi_i", "n"}``: means per speaker over
+    the utterances; ``stoi`` / ``estoi`` are the values of the best permutation, ``stoi_i`` / ``estoi_i`` their improvement over the
+    mixture.  ``stoi_csv_path`` / ``estoi_csv_path``: one row per utterance, values indexed by reference source, in the csv dialect of
+    the other two files."""
+    extra: dict = {}
+    m_si, m_sdr, n = _test_loop(model, utterances, sisnr_csv_path, sdr_csv_path, wav_dir, fs, with_sdr=True,
+                                stoi_csv_paths=(stoi_csv_path, estoi_csv_path), stoi_out=extra)
+    return {"sisnri": m_si, "sdri": m_sdr, **extra, "n": n}
 
 
 test_utterances.__test__ = False      # not a pytest test

@@ -150,6 +150,8 @@ SIGNATURES = {
     "sepr_pit_sisnr_mag_fwd": (_i, [_fp, _fp, _i, _i, _i, _fp, _i, _i, C.c_double, _fp, _fp, _fp, _sz, _fp]),
     "sepr_bss_eval_workspace": (_sz, [_i, _i, _i]),
     "sepr_bss_eval_fwd": (_i, [_fp, _fp, _fp, C.POINTER(_i), _i, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _sz, _fp]),
+    "sepr_stoi_workspace": (_sz, [_i, _i, _i]),
+    "sepr_stoi_fwd": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _sz, _fp]),
     "sepr_stitch_workspace": (_sz, [_i, _i, _i]),
     "sepr_stitch_fwd": (_i, [_fp, C.POINTER(_i), C.POINTER(_i), _i, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _sz, _fp]),
     "sepr_resample_out_len": (_ll, [_ll, _i, _i]),

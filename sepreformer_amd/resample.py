@@ -52,6 +52,31 @@ def plan(fs_in: int, fs_out: int) -> Plan:
     return Plan(L, M, K, Hh, taps.astype(np.float32))
 
 
+def plan_oct(fs_in: int, fs_out: int = 10000) -> Plan:
+    """The converter STOI prescribes (pystoi's ``resample_oct``), in the ``[L][K]`` phase layout of ``plan``: half
+    length ``Lh = ceil((60 - 8) / (28.714 fc / 10))`` at ``fc = 1 / (2 max(L, M))``, ``h[t] = kaiser(2 Lh + 1, 0.1102 (60 - 8.7))[t]
+    2 L fc sinc(2 fc t)`` normalised to unit sum, applied as ``scipy.signal.resample_poly(x, L, M, window=h)``: a centred filter of gain
+    ``L``.  Output ``n`` at ``n M = b L + p`` is ``sum_r L h[p + L r] x[b - r]``, so ``taps[p][j] = L h[p + L (Hh - j)]`` with
+    ``Hh = floor(Lh / L)`` and ``K = 2 Hh + 2`` (zero where ``|p + L (Hh - j)| > Lh``); float64 arithmetic rounded once to float32.
+    ``sepr_resample_fwd`` runs it like any other plan."""
+    fs_in, fs_out = int(fs_in), int(fs_out)
+    if fs_in < 1 or fs_out < 1:
+        raise ValueError(f"sampling rates must be positive, got {fs_in} -> {fs_out}")
+    g = math.gcd(fs_in, fs_out)
+    L, M = fs_out // g, fs_in // g
+    fc = 1.0 / (2 * max(L, M))
+    Lh = int(math.ceil((60 - 8) / (28.714 * fc / 10)))
+    t = np.arange(-Lh, Lh + 1, dtype=np.float64)
+    h = np.kaiser(2 * Lh + 1, 0.1102 * (60 - 8.7)) * (2 * L * fc * np.sinc(2 * fc * t))
+    h = L * (h / np.sum(h))
+    Hh = Lh // L
+    K = 2 * Hh + 2
+    pos = np.arange(L, dtype=np.int64)[:, None] + L * (Hh - np.arange(K, dtype=np.int64))[None, :]      # p + L (Hh - j)
+    inside = np.abs(pos) <= Lh
+    taps = np.where(inside, h[np.clip(pos + Lh, 0, 2 * Lh)], 0.0)
+    return Plan(L, M, K, Hh, taps.astype(np.float32))
+
+
 def out_len(T: int, L: int, M: int) -> int:
     """``ceil(T L / M)``: the length ``librosa.resample`` gives."""
     return -((-int(T) * L) // M)
@@ -64,13 +89,13 @@ def device_table(p: Plan) -> np.ndarray:
     return np.ascontiguousarray(p.taps[q].T)
 
 
-_tables: Dict[Tuple[int, int, str], Tuple[Plan, torch.Tensor]] = {}
+_tables: Dict[Tuple[int, int, str, bool], Tuple[Plan, torch.Tensor]] = {}
 
 
-def _table(fs_in: int, fs_out: int, dev: torch.device) -> Tuple[Plan, torch.Tensor]:
-    key = (int(fs_in), int(fs_out), str(dev))
+def _table(fs_in: int, fs_out: int, dev: torch.device, oct: bool = False) -> Tuple[Plan, torch.Tensor]:
+    key = (int(fs_in), int(fs_out), str(dev), oct)
     if key not in _tables:
-        p = plan(fs_in, fs_out)
+        p = plan_oct(fs_in, fs_out) if oct else plan(fs_in, fs_out)
         _tables[key] = (p, torch.from_numpy(device_table(p)).to(dev))
     return _tables[key]
 
@@ -115,6 +140,30 @@ def resample(x: Union[torch.Tensor, Sequence[torch.Tensor]], fs_in: int, fs_out:
         if v.shape[0] < 1:
             raise ValueError("every recording must hold at least one sample")
     p, table = _table(fs_in, fs_out, dev)
+    parts = _convert(xs, p, table, dev)
+    if form == 1:
+        return parts[0]
+    if form == 2:
+        return parts[0][None]
+    return parts
+
+
+@torch.no_grad()
+def resample_oct(xs: Sequence[torch.Tensor], fs_in: int, fs_out: int = 10000) -> List[torch.Tensor]:
+    """1-D device tensors through the ``plan_oct`` converter (STOI's 10 kHz conversion), all in one launch -> a list of float32 device
+    tensors of ``ceil(T fs_out / fs_in)`` samples.  ``fs_in == fs_out`` returns the tensors themselves."""
+    xs = list(xs)
+    if int(fs_in) == int(fs_out) or not xs:
+        return xs
+    dev = xs[0].device
+    if dev.type != "cuda":
+        raise RuntimeError("resample runs on the HIP device only (there is no CPU path)")
+    p, table = _table(fs_in, fs_out, dev, oct=True)
+    return _convert(xs, p, table, dev)
+
+
+def _convert(xs: List[torch.Tensor], p: Plan, table: torch.Tensor, dev: torch.device) -> List[torch.Tensor]:
+    """One ``sepr_resample_fwd`` launch over the 1-D tensors ``xs`` with the plan's table."""
     lib = L_.load()
     xs = [v.to(device=dev, dtype=torch.float32) for v in xs]
     R = len(xs)
@@ -133,9 +182,4 @@ def resample(x: Union[torch.Tensor, Sequence[torch.Tensor]], fs_in: int, fs_out:
                                        ws.numel(), stream.cuda_stream), "sepr_resample_fwd")
         # the offsets are pageable host memory that the call's copies read when they run: they must outlive the copies
         stream.synchronize()
-    parts = [y[int(ooff[r]):int(ooff[r + 1])] for r in range(R)]
-    if form == 1:
-        return parts[0]
-    if form == 2:
-        return parts[0][None]
-    return parts
+    return [y[int(ooff[r]):int(ooff[r + 1])] for r in range(R)]
