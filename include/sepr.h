@@ -444,13 +444,32 @@ int sepr_resample_fwd(const float* x, const long long* in_offset, float* y, cons
  * term_start + n[b] <= the utterance's length; the kernel clamps the utterance index, the start and every read position, so that a bad table
  * yields wrong samples but never a read outside the corpus buffers.  SEPR_EINVAL before any HIP call for a null pointer, B < 1 (or > 65535),
  * S outside 2..3, M outside S..S+1, Tmax < 4 or not a multiple of 4, a misaligned pointer or an inconsistent corpus description.  No
- * workspace, no host synchronisation or allocation (capturable: the pointers are frozen, the table contents are read at replay). */
+ * workspace, no host synchronisation or allocation (capturable: the pointers are frozen, the table contents are read at replay).
+ *
+ * sepr_dynmix_speed_fwd: sepr_dynmix_fwd with speed perturbation.  term_conv [B (M + S)] int32 (DEVICE): -1 = the term is
+ * the stored utterance, as in sepr_dynmix_fwd and with its bits; k in 0 .. NC - 1 = the term is the utterance passed through converter k.  The
+ * converters are HOST arrays read before the call returns: conv_taps [NC] device pointers, each a float32 [K][L] table in the layout of
+ * sepr_resample_fwd; conv_L, conv_M, conv_K [NC]; 0 <= NC <= 16 (the four may be NULL for NC = 0).  The perturbed utterance has
+ * sepr_resample_out_len(T, L, M) samples and its sample y[n] is exactly sepr_resample_fwd's: exact float64 products summed in the order
+ * j = 0 .. K - 1, rounded once to float32, x zero outside [0, T) of THAT utterance.  A perturbed term's value at output sample t is
+ * (y[term_start + t] * term_norm) * term_gain: term_start indexes the perturbed utterance, the phase is ((term_start + t) M) mod L in 64-bit
+ * arithmetic, and the caller guarantees term_start + n[b] <= the perturbed length.  The conversion runs inside the one launch, on the cropped span
+ * only: per workgroup of 2048 outputs the input span 2047 M / L + K + 1 samples is staged in LDS, and a converter whose span exceeds 3072 samples
+ * is SEPR_EINVAL, as are NC outside 0..16, a null term_conv, a null converter array or table pointer while NC > 0, L, M or K < 1, K odd, and
+ * everything sepr_dynmix_fwd refuses - all before any HIP call.  A target term that equals mixture term s bit for bit, converter index included,
+ * is computed once.  The kernel clamps the converter index (negative = none, above NC - 1 = NC - 1), the utterance index and every read
+ * position: a bad table yields wrong samples but never a read outside the corpus.  No workspace, no host synchronisation or allocation
+ * (capturable: the pointers and the converter descriptions are frozen, the table contents are read at replay). */
 size_t sepr_corpus_energy_workspace(int N);
 int sepr_corpus_energy(const short* buf16, long long total16, const float* buf32, long long total32, const long long* offsets, int N16, int N,
                        long long* ss16, double* ss32, void* ws, size_t ws_bytes, sepr_stream_t stream);
 int sepr_dynmix_fwd(const short* buf16, long long total16, const float* buf32, long long total32, const long long* offsets, int N16, int N,
                     const int* term_utt, const int* term_start, const float* term_norm, const float* term_gain, const int* n, int B, int M,
                     int S, int Tmax, float* mix, float* const* src, sepr_stream_t stream);
+int sepr_dynmix_speed_fwd(const short* buf16, long long total16, const float* buf32, long long total32, const long long* offsets, int N16, int N,
+                          const int* term_utt, const int* term_start, const float* term_norm, const float* term_gain, const int* term_conv,
+                          const int* n, int B, int M, int S, int Tmax, float* mix, float* const* src, const float* const* conv_taps,
+                          const int* conv_L, const int* conv_M, const int* conv_K, int NC, sepr_stream_t stream);
 
 /* ================================================================================================================= */
 /* Training path: train-mode forward twins that keep what the backward needs, and the       */

@@ -11,6 +11,14 @@
 //                        arbitrary start, read as aligned 16-byte loads from the aligned-down address and realigned in registers
 //                        (v_alignbyte for the odd int16 starts), scaled by two separately rounded multiplies, summed in term
 //                        order; float4 stores of the mixture and the S target rows, zeros from n[b] on.
+//   dynmix_speed_kernel  the same batch with speed perturbation: a term whose term_conv is a converter index
+//                        is the stored utterance passed through that rational-ratio converter (the arithmetic of sepr_resample.hip:
+//                        exact float64 products summed in the order j = 0 .. K - 1, one rounding).  Per workgroup (2048 outputs of
+//                        one example) and perturbed term: the tile's input span is staged in LDS as doubles, zero outside the
+//                        utterance; the outputs are converted one per lane (consecutive lanes = consecutive outputs, so the LDS
+//                        reads and the tap columns are consecutive), written to an LDS tile of floats and read back eight per
+//                        thread into the plain kernel's scaling, summing and storing code.  Terms with term_conv < 0 take the
+//                        plain kernel's loads.
 // Nothing here depends on the launch order of workgroups: results are bit-identical from run to run.
 #include "sepr_common.h"
 
@@ -151,6 +159,148 @@ __global__ __launch_bounds__(DM_TPB) void dynmix_kernel(DmCorpus c, const int* _
   }
 }
 
+constexpr int DS_TILE = DM_TPB * DM_PER;   // output samples per workgroup
+constexpr int DS_SPAN = 3072;              // doubles of staged input: (DS_TILE - 1) M / L + K + 1 must fit (speeds of about 70 % to 140 %)
+constexpr int DS_MAX_NC = 16;
+
+struct DsConv {
+  const float* taps[DS_MAX_NC];            // [K][L], column q = the tap row of phase (q M) mod L (resample.device_table)
+  int L[DS_MAX_NC], M[DS_MAX_NC], K[DS_MAX_NC];
+  int NC;
+};
+
+__host__ __device__ inline long long ds_span(int L, int M, int K) { return ((long long)(DS_TILE - 1) * M) / L + K + 1; }
+
+// outputs t = tile0 .. tile0 + DS_TILE - 1 (below n) of the perturbed utterance of term (utt, start) through converter (tp, L, M, K), left in
+// ys[t - tile0]; thread tid then owns ys[8 tid .. 8 tid + 7].  Workgroup-uniform arguments; two barriers.  The table is not trusted:
+// whatever it holds, the staging reads stay inside the utterance's slice of the corpus buffers.
+__device__ __forceinline__ void convert_tile(const DmCorpus& c, int utt, int start, const float* __restrict__ tp, int L, int M, int K,
+                                             int tile0, int n, double* __restrict__ xs, float* __restrict__ ys) {
+  const int tid = threadIdx.x;
+  const int u = utt < 0 ? 0 : (utt >= c.N ? c.N - 1 : utt);
+  const long long o0 = c.off[u], T = c.off[u + 1] - o0;
+  const bool is16 = u < c.N16;
+  const long long total = is16 ? c.total16 : c.total32;
+  const long long e0 = o0 - (is16 ? 0 : c.off[c.N16]);
+  const long long n0 = (long long)(start < 0 ? 0 : start) + tile0;          // first output of the tile, as an index of the perturbed utterance
+  const int Hh = (K - 2) / 2;
+  const long long b0 = (n0 * M) / L, g0 = b0 - Hh;
+  const int span = (int)ds_span(L, M, K);                                    // <= DS_SPAN: the entry refuses any other converter
+  for (int i = tid; i < span; i += DM_TPB) {
+    const long long g = g0 + i;
+    double v = 0.0;
+    if (g >= 0 && g < T) {
+      const long long e = clampll(e0 + g, 0, total - 1);
+      v = is16 ? (double)((float)c.buf16[e] * 3.0517578125e-05f) : (double)c.buf32[e];
+    }
+    xs[i] = v;
+  }
+  __syncthreads();
+  const int left = n - tile0;                                                // > 0: the caller returned for tiles past n
+  const int lim = span - K;                                                  // highest window base inside the staged span
+  double acc[DM_PER];
+  const double* xp[DM_PER];
+  const float* tq[DM_PER];
+#pragma unroll
+  for (int i = 0; i < DM_PER; ++i) {
+    const long long nn = n0 + tid + i * DM_TPB;
+    const long long d = (nn * M) / L - b0;                                   // 0 .. (DS_TILE - 1) M / L + 1
+    xp[i] = xs + (int)(d < 0 ? 0 : (d > lim ? lim : d));
+    tq[i] = tp + (int)(nn % L);
+    acc[i] = 0.0;
+  }
+  if (tid < left) {                                                          // (per wave: whole waves past n skip the loop)
+#pragma unroll 2
+    for (int j = 0; j < K; ++j) {
+#pragma unroll
+      for (int i = 0; i < DM_PER; ++i) acc[i] = fma((double)tq[i][(long long)j * L], xp[i][j], acc[i]);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < DM_PER; ++i) ys[tid + i * DM_TPB] = (float)acc[i];
+  __syncthreads();
+}
+
+// term j (flattened) of the example on samples t0 .. t0 + 7: through its converter when it has one, else the plain kernel's term_value
+__device__ __forceinline__ void speed_term_value(const DmCorpus& c, const DsConv& cv, int conv, int utt, int start, float norm, float gain,
+                                                 int tile0, int t0, int n, double* xs, float* ys, float v[8]) {
+#pragma clang fp contract(off)
+  if (conv < 0 || cv.NC < 1) {
+    term_value(c, utt, start, norm, gain, t0 < n ? t0 : 0, v);
+    return;
+  }
+  const int k = conv >= cv.NC ? cv.NC - 1 : conv;
+  convert_tile(c, utt, start, cv.taps[k], cv.L[k], cv.M[k], cv.K[k], tile0, n, xs, ys);
+  const float4 lo = *reinterpret_cast<const float4*>(ys + threadIdx.x * DM_PER);
+  const float4 hi = *reinterpret_cast<const float4*>(ys + threadIdx.x * DM_PER + 4);
+  const float x[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const float a = x[i] * norm;
+    v[i] = a * gain;
+  }
+}
+
+template <int S>
+__global__ __launch_bounds__(DM_TPB) void dynmix_speed_kernel(DmCorpus c, DsConv cv, const int* __restrict__ term_utt,
+                                                              const int* __restrict__ term_start, const float* __restrict__ term_norm,
+                                                              const float* __restrict__ term_gain, const int* __restrict__ term_conv,
+                                                              const int* __restrict__ nlen, int M, int Tmax, float* __restrict__ mix, DmRows src) {
+#pragma clang fp contract(off)
+  __shared__ double xs[DS_SPAN];
+  __shared__ __attribute__((aligned(16))) float ys[DS_TILE];
+  const int b = blockIdx.y;
+  const int tile0 = blockIdx.x * DS_TILE;
+  const int t0 = tile0 + threadIdx.x * DM_PER;
+  const bool live = t0 < Tmax;                                     // no early return for a thread: the conversions hold barriers
+  const bool second = t0 + 4 < Tmax;
+  int n = nlen[b];
+  n = n < 0 ? 0 : (n > Tmax ? Tmax : n);
+  const long long row = (long long)b * Tmax + t0;
+  float acc[8], keep[S][8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) acc[i] = 0.f;
+  if (tile0 >= n) {                                                // the whole tile is the zero fill of pad_sequence (workgroup-uniform)
+    if (live) {
+      store8(mix + row, acc, t0, n, second);
+#pragma unroll
+      for (int s = 0; s < S; ++s) store8(src.p[s] + row, acc, t0, n, second);
+    }
+    return;
+  }
+  const int NT = M + S, j0 = b * NT;
+#pragma unroll
+  for (int m = 0; m < S + 1; ++m) {
+    if (m < M) {
+      float v[8];
+      const int conv = __builtin_amdgcn_readfirstlane(term_conv[j0 + m]);
+      speed_term_value(c, cv, conv, term_utt[j0 + m], term_start[j0 + m], term_norm[j0 + m], term_gain[j0 + m], tile0, t0, n, xs, ys, v);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) acc[i] = acc[i] + v[i];
+      if (m < S) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) keep[m][i] = v[i];
+      }
+    }
+  }
+  if (live) store8(mix + row, acc, t0, n, second);
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    const int jm = j0 + s, jt = j0 + M + s;
+    const int conv = __builtin_amdgcn_readfirstlane(term_conv[jt]);
+    const bool same = term_utt[jt] == term_utt[jm] && term_start[jt] == term_start[jm] &&
+                      __float_as_uint(term_norm[jt]) == __float_as_uint(term_norm[jm]) &&
+                      __float_as_uint(term_gain[jt]) == __float_as_uint(term_gain[jm]) && conv == term_conv[jm];
+    if (same) {
+      if (live) store8(src.p[s] + row, keep[s], t0, n, second);
+    } else {
+      float v[8];
+      speed_term_value(c, cv, conv, term_utt[jt], term_start[jt], term_norm[jt], term_gain[jt], tile0, t0, n, xs, ys, v);
+      if (live) store8(src.p[s] + row, v, t0, n, second);
+    }
+  }
+}
+
 // partial sum of squares of utterance u = blockIdx.x over the chunks p, p + EN_PARTS, ... (p = blockIdx.y) of EN_TPB samples
 __global__ __launch_bounds__(EN_TPB) void energy_part_kernel(DmCorpus c, long long* __restrict__ part) {
 #pragma clang fp contract(off)
@@ -243,21 +393,33 @@ extern "C" int sepr_corpus_energy(const short* buf16, long long total16, const f
   return SEPR_OK;
 }
 
+namespace sepr {
+namespace {
+// the argument checks the two mixing entries share; fills rows
+int dynmix_args_bad(const short* buf16, long long total16, const float* buf32, long long total32, const long long* offsets, int N16, int N,
+                    const int* term_utt, const int* term_start, const float* term_norm, const float* term_gain, const int* n, int B, int M, int S,
+                    int Tmax, float* mix, float* const* src, DmRows* rows) {
+  if (corpus_args_bad(buf16, total16, buf32, total32, offsets, N16, N)) return 1;
+  if (!term_utt || !term_start || !term_norm || !term_gain || !n || !mix || !src) return 1;
+  if (B < 1 || B > 65535 || S < 2 || S > 3 || M < S || M > S + 1 || Tmax < 4 || Tmax % 4 != 0) return 1;
+  uintptr_t al = reinterpret_cast<uintptr_t>(mix);
+  for (int s = 0; s < S; ++s) {
+    if (!src[s]) return 1;
+    rows->p[s] = src[s];
+    al |= reinterpret_cast<uintptr_t>(src[s]);
+  }
+  return al % 16 != 0;                                             // float4 stores
+}
+}  // namespace
+}  // namespace sepr
+
 extern "C" int sepr_dynmix_fwd(const short* buf16, long long total16, const float* buf32, long long total32, const long long* offsets,
                                int N16, int N, const int* term_utt, const int* term_start, const float* term_norm, const float* term_gain,
                                const int* n, int B, int M, int S, int Tmax, float* mix, float* const* src, sepr_stream_t stream) {
   using namespace sepr;
-  if (corpus_args_bad(buf16, total16, buf32, total32, offsets, N16, N)) return SEPR_EINVAL;
-  if (!term_utt || !term_start || !term_norm || !term_gain || !n || !mix || !src) return SEPR_EINVAL;
-  if (B < 1 || B > 65535 || S < 2 || S > 3 || M < S || M > S + 1 || Tmax < 4 || Tmax % 4 != 0) return SEPR_EINVAL;
   DmRows rows = {{nullptr, nullptr, nullptr}};
-  uintptr_t al = reinterpret_cast<uintptr_t>(mix);
-  for (int s = 0; s < S; ++s) {
-    if (!src[s]) return SEPR_EINVAL;
-    rows.p[s] = src[s];
-    al |= reinterpret_cast<uintptr_t>(src[s]);
-  }
-  if (al % 16 != 0) return SEPR_EINVAL;                            // float4 stores
+  if (dynmix_args_bad(buf16, total16, buf32, total32, offsets, N16, N, term_utt, term_start, term_norm, term_gain, n, B, M, S, Tmax, mix, src, &rows))
+    return SEPR_EINVAL;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const DmCorpus c = {buf16, buf32, offsets, total16, total32, N16, N};
   const dim3 grid((unsigned)cdiv(Tmax, DM_TPB * DM_PER), (unsigned)B);
@@ -266,5 +428,39 @@ extern "C" int sepr_dynmix_fwd(const short* buf16, long long total16, const floa
   else
     hipLaunchKernelGGL((dynmix_kernel<3>), grid, dim3(DM_TPB), 0, st, c, term_utt, term_start, term_norm, term_gain, n, M, Tmax, mix, rows);
   SEPR_CHECK_LAUNCH("dynmix kernel");
+  return SEPR_OK;
+}
+
+extern "C" int sepr_dynmix_speed_fwd(const short* buf16, long long total16, const float* buf32, long long total32, const long long* offsets,
+                                     int N16, int N, const int* term_utt, const int* term_start, const float* term_norm,
+                                     const float* term_gain, const int* term_conv, const int* n, int B, int M, int S, int Tmax, float* mix,
+                                     float* const* src, const float* const* conv_taps, const int* conv_L, const int* conv_M, const int* conv_K,
+                                     int NC, sepr_stream_t stream) {
+  using namespace sepr;
+  DmRows rows = {{nullptr, nullptr, nullptr}};
+  if (dynmix_args_bad(buf16, total16, buf32, total32, offsets, N16, N, term_utt, term_start, term_norm, term_gain, n, B, M, S, Tmax, mix, src, &rows))
+    return SEPR_EINVAL;
+  if (!term_conv || NC < 0 || NC > DS_MAX_NC) return SEPR_EINVAL;
+  if (NC > 0 && (!conv_taps || !conv_L || !conv_M || !conv_K)) return SEPR_EINVAL;
+  DsConv cv = {};
+  cv.NC = NC;
+  for (int k = 0; k < NC; ++k) {
+    if (!conv_taps[k] || conv_L[k] < 1 || conv_M[k] < 1 || conv_K[k] < 1 || conv_K[k] % 2 != 0) return SEPR_EINVAL;
+    if (ds_span(conv_L[k], conv_M[k], conv_K[k]) > DS_SPAN) return SEPR_EINVAL;   // the tile's input span exceeds the kernel's LDS plan
+    cv.taps[k] = conv_taps[k];
+    cv.L[k] = conv_L[k];
+    cv.M[k] = conv_M[k];
+    cv.K[k] = conv_K[k];
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const DmCorpus c = {buf16, buf32, offsets, total16, total32, N16, N};
+  const dim3 grid((unsigned)cdiv(Tmax, DS_TILE), (unsigned)B);
+  if (S == 2)
+    hipLaunchKernelGGL((dynmix_speed_kernel<2>), grid, dim3(DM_TPB), 0, st, c, cv, term_utt, term_start, term_norm, term_gain, term_conv, n, M,
+                       Tmax, mix, rows);
+  else
+    hipLaunchKernelGGL((dynmix_speed_kernel<3>), grid, dim3(DM_TPB), 0, st, c, cv, term_utt, term_start, term_norm, term_gain, term_conv, n, M,
+                       Tmax, mix, rows);
+  SEPR_CHECK_LAUNCH("dynmix speed kernel");
   return SEPR_OK;
 }

@@ -18,12 +18,17 @@ What is exact: a PCM16 sample is ``int16 / 32768`` (what ``librosa.load`` return
 two multiplies and the sum of the terms the reference's float32 operations in the reference's order.  The one thing that is not the
 reference's bit for bit is the RMS: numpy takes it from a pairwise float32 sum, this module from the exact integer sum (a few ulp).
 
+Speed perturbation: ``plan_wsj0`` / ``plan_wham`` / ``plan_whamr`` take ``speeds=`` (integer percentages, e.g.
+``range(95, 106)``) and draw one per source; a perturbed term is the stored utterance passed through ``resample.plan(p, 100)``, converted
+inside the mixing launch (``sepr_dynmix_speed_fwd``) on the cropped span only.
+
 Shuffling: the reference shuffles through ``DataLoader(shuffle=True)`` (torch's generator); this feed takes the epoch's key order
 from the caller (``keys=``), and by default draws a permutation from its own ``random.Random`` before every epoch.
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
 import random
 from typing import Callable, Dict, Iterator, List, NamedTuple, Optional, Sequence, Tuple, Union
 
@@ -31,8 +36,11 @@ import numpy as np
 import torch
 
 from . import lib as L_
+from . import resample as R_
 
-Term = Tuple[int, int, np.float32, np.float32]          # (utterance index, start sample, norm factor, gain)
+# (utterance index, start sample, norm factor, gain), plus the speed in percent when the planner was given speeds
+Term = Union[Tuple[int, int, np.float32, np.float32], Tuple[int, int, np.float32, np.float32, int]]
+MAX_CONVERTERS = 16                                     # converters one sepr_dynmix_speed_fwd call takes
 _ONE = np.float32(1.0)
 
 
@@ -52,6 +60,7 @@ class BatchPlan(NamedTuple):
     gain: np.ndarray            # float32 [B, M + S]
     M: int
     S: int
+    speed: Optional[np.ndarray] = None      # int32 [B, M + S] percent (100 = as recorded), None: planned without speeds
 
 
 def parse_scp(path: str) -> Dict[str, str]:
@@ -231,35 +240,81 @@ def _norm(ref_rms: np.float32, cur_rms: np.float32) -> np.float32:
         return np.float32(ref_rms) / np.float32(cur_rms)            # float32 divide, as ``ref_rms / curr_rms`` of two np.float32
 
 
+def speed_ratio(speed: int) -> Tuple[int, int]:
+    """``(L, M)`` of the converter of a speed in percent: ``L / M = 100 / speed`` in lowest terms (``resample.plan(speed, 100)``)."""
+    speed = int(speed)
+    if speed < 1:
+        raise ValueError(f"a speed is a positive integer percentage, got {speed}")
+    g = math.gcd(speed, 100)
+    return 100 // g, speed // g
+
+
+def parse_speeds(text: str) -> List[int]:
+    """``"95:105"`` (an inclusive range) or ``"95,100,105"`` (a list) -> the speeds in percent."""
+    if ":" in text:
+        lo, hi = (int(v) for v in text.split(":"))
+        out = list(range(lo, hi + 1))
+    else:
+        out = [int(v) for v in text.split(",") if v.strip()]
+    if not out or min(out) < 1:
+        raise ValueError(f"--speeds {text!r}: expected LO:HI or a comma list of positive integer percentages")
+    return out
+
+
+def perturbed_len(T: int, speed: int) -> int:
+    """Samples of an utterance of ``T`` samples at ``speed`` percent: ``ceil(T L / M)``."""
+    return int(T) if int(speed) == 100 else R_.out_len(T, *speed_ratio(speed))
+
+
+def _draw_speeds(rng: random.Random, speeds: Optional[Sequence[int]], count: int) -> Optional[List[int]]:
+    """One ``rng.choice(speeds)`` per source, in source order; no draw without speeds."""
+    if speeds is None:
+        return None
+    return [int(rng.choice(speeds)) for _ in range(count)]
+
+
+def _terms(utts, starts, norms, gains, sp) -> Tuple[Term, ...]:
+    if sp is None:
+        return tuple((u, s, nf, g) for u, s, nf, g in zip(utts, starts, norms, gains))
+    return tuple((u, s, nf, g, p) for u, s, nf, g, p in zip(utts, starts, norms, gains, sp))
+
+
 def plan_wsj0(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs: Sequence[str] = ("s1", "s2"),
-              accept: Callable[[str, str], bool] = wsj0_distinct_speakers, crop: bool = True) -> Example:
-    """``SepReformer_Large_DM_WSJ0/dataset.py:84-139``.  ``crop=False`` is the reference's "test" partition (no ``max_len`` crop)."""
+              accept: Callable[[str, str], bool] = wsj0_distinct_speakers, crop: bool = True,
+              speeds: Optional[Sequence[int]] = None) -> Example:
+    """``SepReformer_Large_DM_WSJ0/dataset.py:84-139``.  ``crop=False`` is the reference's "test" partition (no ``max_len`` crop).
+    ``speeds``: directly after the draw that orders the two sources, one ``rng.choice(speeds)`` per source; the perturbed lengths
+    replace the stored ones, the norm factors keep the stored utterances' RMS (section 5e-2)."""
     keys = corpus.roles[srcs[0]]
     while True:
         key_random = rng.choice(keys)
         if accept(key, key_random):
             break
     i1, i2 = (0, 1) if rng.random() > 0.5 else (1, 0)
+    sp = _draw_speeds(rng, speeds, 2)
     utts = [corpus.lookup(srcs[i1], key), corpus.lookup(srcs[i2], key_random)]
     ref = corpus.rms[utts[0]]
     norms = [_norm(ref, corpus.rms[u]) for u in utts]
     gains = [_gain(rng, -5, 5) for _ in utts]
-    lens = [int(corpus.lengths[u]) for u in utts]
+    lens = [perturbed_len(corpus.lengths[u], p) for u, p in zip(utts, sp or (100, 100))]
     min_len = min(lens)
     starts = [rng.randint(0, ln - min_len) for ln in lens]
     n = min_len - min_len % 4
     if crop and n > max_len:
         st = rng.randint(0, n - max_len)
         starts, n = [s + st for s in starts], max_len
-    terms = tuple((u, s, nf, g) for u, s, nf, g in zip(utts, starts, norms, gains))
+    terms = _terms(utts, starts, norms, gains, sp)
     return Example(key, n, terms, terms)
 
 
-def plan_wham(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs: Sequence[str] = ("s1", "s2"), noise: str = "noise") -> Example:
+def plan_wham(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs: Sequence[str] = ("s1", "s2"), noise: str = "noise",
+              speeds: Optional[Sequence[int]] = None) -> Example:
     """``SepReformer_Large_DM_WHAM/dataset.py``: no speaker rule, the noise of ``key`` normalised to the first source with a gain of
-    its own from U(-5, 5) dB, everything cropped to ``min(max_len, lengths)`` at independent random indices."""
+    its own from U(-5, 5) dB, everything cropped to ``min(max_len, lengths)`` at independent random indices.  ``speeds``: as in
+    ``plan_wsj0``; the noise is not perturbed."""
     key_random = rng.choice(corpus.roles[srcs[0]])
     i1, i2 = (0, 1) if rng.random() > 0.5 else (1, 0)
+    sp = _draw_speeds(rng, speeds, 2)
     utts = [corpus.lookup(srcs[i1], key), corpus.lookup(srcs[i2], key_random)]
     ref = corpus.rms[utts[0]]
     norms = [_norm(ref, corpus.rms[u]) for u in utts]
@@ -268,20 +323,24 @@ def plan_wham(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs: 
     norms.append(_norm(ref, corpus.rms[un]))
     gains.append(_gain(rng, -5, 5))
     utts.append(un)
-    lens = [int(corpus.lengths[u]) for u in utts]
+    if sp is not None:
+        sp.append(100)
+    lens = [perturbed_len(corpus.lengths[u], p) for u, p in zip(utts, sp or (100, 100, 100))]
     min_len = min([max_len] + lens)
     starts = [rng.randint(0, ln - min_len) for ln in lens]
     n = min_len - min_len % 4
-    terms = tuple((u, s, nf, g) for u, s, nf, g in zip(utts, starts, norms, gains))
+    terms = _terms(utts, starts, norms, gains, sp)
     return Example(key, n, terms, terms[:2])
 
 
 def plan_whamr(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs: Sequence[str] = ("s1", "s2"),
-               reverb: Sequence[str] = ("s1_reverb", "s2_reverb"), noise: str = "noise") -> Example:
+               reverb: Sequence[str] = ("s1_reverb", "s2_reverb"), noise: str = "noise", speeds: Optional[Sequence[int]] = None) -> Example:
     """``SepReformer_Large_DM_WHAMR/dataset.py:87-154``: the mixture is the two reverberant twins plus the noise (gains U(-3, 3) dB,
-    noise U(-6, 3) dB), the targets are the anechoic sources with their twins' norm factor, gain and crop index."""
+    noise U(-6, 3) dB), the targets are the anechoic sources with their twins' norm factor, gain and crop index.  ``speeds``: as in
+    ``plan_wsj0``; a dry source and its reverberant twin share one speed, the noise is not perturbed."""
     key_random = rng.choice(corpus.roles[srcs[0]])
     i1, i2 = (0, 1) if rng.random() > 0.5 else (1, 0)
+    sp = _draw_speeds(rng, speeds, 2)
     dry = [corpus.lookup(srcs[i1], key), corpus.lookup(srcs[i2], key_random)]
     wet = [corpus.lookup(reverb[i1], key), corpus.lookup(reverb[i2], key_random)]
     for d, w in zip(dry, wet):
@@ -292,20 +351,23 @@ def plan_whamr(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs:
     gains = [_gain(rng, -3, 3) for _ in dry]
     un = corpus.lookup(noise, key)
     nnorm, ngain = _norm(ref, corpus.rms[un]), _gain(rng, -6, 3)
-    lens = [int(corpus.lengths[u]) for u in dry]
+    lens = [perturbed_len(corpus.lengths[u], p) for u, p in zip(dry, sp or (100, 100))]
     min_len = min([max_len] + lens + [int(corpus.lengths[un])])
     starts = [rng.randint(0, ln - min_len) for ln in lens]
     nstart = rng.randint(0, int(corpus.lengths[un]) - min_len)
     n = min_len - min_len % 4
-    mix = tuple((u, s, nf, g) for u, s, nf, g in zip(wet, starts, norms, gains)) + ((un, nstart, nnorm, ngain),)
-    tgt = tuple((u, s, nf, g) for u, s, nf, g in zip(dry, starts, norms, gains))
+    mix = _terms(wet + [un], starts + [nstart], norms + [nnorm], gains + [ngain], None if sp is None else sp + [100])
+    tgt = _terms(dry, starts, norms, gains, sp)
     return Example(key, n, mix, tgt)
 
 
 def plan_direct(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs: Sequence[str] = ("s1", "s2"), mix: str = "mix",
-                crop: bool = True) -> Example:
+                crop: bool = True, speeds: Optional[Sequence[int]] = None) -> Example:
     """``_direct_load``: the fixed mixture file and its sources, norm and gain 1, the ``% 4`` truncation and the ``max_len`` crop.
-    The mixture is one term; the kernel takes ``M >= S`` terms, so it is followed by terms of gain 0, which add exactly nothing."""
+    The mixture is one term; the kernel takes ``M >= S`` terms, so it is followed by terms of gain 0, which add exactly nothing.
+    A fixed mixture cannot be perturbed: ``speeds`` raises."""
+    if speeds is not None:
+        raise ValueError("plan_direct loads a fixed mixture file: it takes no speeds")
     um = corpus.lookup(mix, key)
     n = int(corpus.lengths[um])
     n -= n % 4
@@ -327,27 +389,57 @@ def collate_plan(corpus: Corpus, examples: Sequence[Example]) -> BatchPlan:
     B = len(egs)
     utt, start = np.zeros((B, M + S), np.int32), np.zeros((B, M + S), np.int32)
     norm, gain = np.zeros((B, M + S), np.float32), np.zeros((B, M + S), np.float32)
+    speed = np.full((B, M + S), 100, np.int32)
+    any_speed = False
     for b, e in enumerate(egs):
         if len(e.mix) != M or len(e.tgt) != S:
             raise ValueError("every example of a batch needs the same number of terms")
         if e.n < 1:
             raise ValueError(f"{e.key}: an example of {e.n} samples")
-        for j, (u, s, nf, g) in enumerate(e.mix + e.tgt):
-            if not (0 <= u < len(corpus)) or s < 0 or s + e.n > int(corpus.lengths[u]):
-                raise ValueError(f"{e.key}: term {j} reads [{s}, {s + e.n}) of utterance {u}")
-            utt[b, j], start[b, j], norm[b, j], gain[b, j] = u, s, nf, g
-    return BatchPlan([e.key for e in egs], np.array([e.n for e in egs], np.int32), utt, start, norm, gain, M, S)
+        for j, term in enumerate(e.mix + e.tgt):
+            u, s, nf, g = term[:4]
+            p = int(term[4]) if len(term) > 4 else 100
+            any_speed |= len(term) > 4
+            if not (0 <= u < len(corpus)) or p < 1 or s < 0 or s + e.n > perturbed_len(corpus.lengths[u], p):
+                raise ValueError(f"{e.key}: term {j} reads [{s}, {s + e.n}) of utterance {u}" + (f" at {p} % speed" if p != 100 else ""))
+            utt[b, j], start[b, j], norm[b, j], gain[b, j], speed[b, j] = u, s, nf, g, p
+    return BatchPlan([e.key for e in egs], np.array([e.n for e in egs], np.int32), utt, start, norm, gain, M, S, speed if any_speed else None)
 
 
-def _table_words(B: int, NT: int) -> int:
-    return 4 * B * NT + B
+def _table_words(B: int, NT: int, speeds: bool = False) -> int:
+    return (5 if speeds else 4) * B * NT + B
+
+
+def plan_speeds(plan: BatchPlan) -> List[int]:
+    """The distinct speeds other than 100 of a plan, ascending: the default converter set of ``pack_table`` and ``mix_batch``."""
+    return [] if plan.speed is None else sorted({int(p) for p in plan.speed.ravel()} - {100})
+
+
+_converters: Dict[Tuple[str, Tuple[int, ...]], tuple] = {}
+
+
+def _converter_args(dev: torch.device, speeds: Sequence[int]):
+    """The converter arguments of ``sepr_dynmix_speed_fwd`` for ``speeds`` (converter k = ``resample.plan(speeds[k], 100)``): the tables
+    are built once per (device, speed) and stay on the device (``resample._table``), the host arrays once per (device, set)."""
+    key = (str(dev), tuple(int(p) for p in speeds))
+    if key not in _converters:
+        if len(key[1]) > MAX_CONVERTERS:
+            raise ValueError(f"{len(key[1])} distinct speeds: one launch takes {MAX_CONVERTERS} converters")
+        made = [R_._table(p, 100, dev) for p in key[1]]
+        NC = len(made)
+        _converters[key] = ((C.c_void_p * max(NC, 1))(*[t.data_ptr() for _, t in made]), (C.c_int * max(NC, 1))(*[p.L for p, _ in made]),
+                            (C.c_int * max(NC, 1))(*[p.M for p, _ in made]), (C.c_int * max(NC, 1))(*[p.K for p, _ in made]), NC)
+    return _converters[key]
 
 
 def mix_batch(corpus: Corpus, plan: BatchPlan, Tmax: Optional[int] = None, mix: Optional[torch.Tensor] = None,
-              src: Optional[Sequence[torch.Tensor]] = None, table: Optional[torch.Tensor] = None):
-    """One ``sepr_dynmix_fwd`` launch for ``plan`` on the corpus's device (current stream) -> ``(mix [B, Tmax], [src_s [B, Tmax]])``.
-    ``table``: an int32 device tensor that already holds the plan in the kernel's layout (``DynamicMixFeed`` stages it through pinned
-    memory); without it the plan is copied from pageable memory."""
+              src: Optional[Sequence[torch.Tensor]] = None, table: Optional[torch.Tensor] = None,
+              speeds: Optional[Sequence[int]] = None):
+    """One ``sepr_dynmix_fwd`` launch for ``plan`` on the corpus's device (current stream) -> ``(mix [B, Tmax], [src_s [B, Tmax]])``;
+    a plan that carries speeds goes through ``sepr_dynmix_speed_fwd``.  ``table``: an int32 device tensor that already holds the plan in
+    the kernel's layout (``DynamicMixFeed`` stages it through pinned memory); without it the plan is copied from pageable memory.
+    ``speeds``: the converter set the table's index block refers to (``pack_table``); default: the plan's own speeds.  A captured launch
+    keeps the set it was captured with, so a table rewritten between replays must be packed against that set."""
     dev = corpus.device
     if dev is None:
         raise RuntimeError("the corpus is not on the HIP device (there is no CPU path)")
@@ -355,8 +447,12 @@ def mix_batch(corpus: Corpus, plan: BatchPlan, Tmax: Optional[int] = None, mix: 
     Tmax = int(Tmax if Tmax is not None else -(-int(plan.n.max()) // 4) * 4)
     if Tmax % 4 or int(plan.n.max()) > Tmax:
         raise ValueError(f"Tmax = {Tmax} must be a multiple of 4 and hold the longest example ({int(plan.n.max())})")
+    if plan.speed is not None and speeds is None:
+        speeds = plan_speeds(plan)
     if table is None:
-        table = torch.from_numpy(pack_table(plan)).to(dev)
+        table = torch.from_numpy(pack_table(plan, speeds)).to(dev)
+    if table.numel() < _table_words(B, NT, plan.speed is not None):
+        raise ValueError("the device table is shorter than the plan's layout")
     if mix is None:
         mix = torch.empty(B, Tmax, dtype=torch.float32, device=dev)
     if src is None:
@@ -370,15 +466,30 @@ def mix_batch(corpus: Corpus, plan: BatchPlan, Tmax: Optional[int] = None, mix: 
     base, n = table.data_ptr(), B * NT
     rows = (C.c_void_p * plan.S)(*[t.data_ptr() for t in src])
     with torch.cuda.device(dev):
-        L_.check(L_.load().sepr_dynmix_fwd(*corpus._corpus_args(), base, base + 4 * n, base + 8 * n, base + 12 * n, base + 16 * n, B, plan.M,
-                                           plan.S, Tmax, mix.data_ptr(), rows, torch.cuda.current_stream(dev).cuda_stream), "sepr_dynmix_fwd")
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if plan.speed is None:
+            L_.check(L_.load().sepr_dynmix_fwd(*corpus._corpus_args(), base, base + 4 * n, base + 8 * n, base + 12 * n, base + 16 * n, B, plan.M,
+                                               plan.S, Tmax, mix.data_ptr(), rows, stream), "sepr_dynmix_fwd")
+        else:
+            L_.check(L_.load().sepr_dynmix_speed_fwd(*corpus._corpus_args(), base, base + 4 * n, base + 8 * n, base + 12 * n, base + 16 * n + 4 * B,
+                                                     base + 16 * n, B, plan.M, plan.S, Tmax, mix.data_ptr(), rows, *_converter_args(dev, speeds),
+                                                     stream), "sepr_dynmix_speed_fwd")
     return mix, list(src)
 
 
-def pack_table(plan: BatchPlan) -> np.ndarray:
-    """The plan as one int32 array ``[utt | start | norm bits | gain bits | n]``."""
-    return np.concatenate([plan.utt.ravel(), plan.start.ravel(), plan.norm.ravel().view(np.int32), plan.gain.ravel().view(np.int32),
-                           plan.n.astype(np.int32)])
+def pack_table(plan: BatchPlan, speeds: Optional[Sequence[int]] = None) -> np.ndarray:
+    """The plan as one int32 array ``[utt | start | norm bits | gain bits | n]``; a plan that carries speeds appends the converter-index
+    block ``[conv]``: -1 for a term at 100 %, else the position of the term's speed in ``speeds`` (default ``plan_speeds(plan)``)."""
+    parts = [plan.utt.ravel(), plan.start.ravel(), plan.norm.ravel().view(np.int32), plan.gain.ravel().view(np.int32), plan.n.astype(np.int32)]
+    if plan.speed is not None:
+        order = [int(p) for p in (plan_speeds(plan) if speeds is None else speeds)]
+        index = {p: k for k, p in enumerate(order)}
+        index[100] = -1
+        missing = sorted({int(p) for p in plan.speed.ravel()} - set(index))
+        if missing:
+            raise ValueError(f"speeds {missing} of the plan are not in the converter set {order}")
+        parts.append(np.array([index[int(p)] for p in plan.speed.ravel()], np.int32))
+    return np.concatenate(parts)
 
 
 class DynamicMixFeed:
@@ -386,7 +497,7 @@ class DynamicMixFeed:
     ``mixture [B, T]`` and the ``S`` tensors ``src[s] [B, T]`` on the device, the keys), one epoch per iteration.
 
     ``planner(corpus, rng, key, max_len) -> Example`` is one of ``plan_wsj0`` / ``plan_wham`` / ``plan_whamr`` / ``plan_direct`` (bind
-    other role names with ``functools.partial``).  Per batch: plan on the host, write the table into a pinned staging buffer, one
+    other role names, or ``speeds=range(95, 106)`` for speed perturbation, with ``functools.partial``).  Per batch: plan on the host, write the table into a pinned staging buffer, one
     asynchronous copy into the static device table, one launch - all on the current stream, nothing waits for the device.
     ``keys``: the epoch's key order, used as given every epoch; default: the keys of the corpus's first role, permuted with the
     feed's ``random.Random(seed)`` before each epoch (the same generator then makes the examples' draws).  ``rank`` / ``world``:
@@ -414,6 +525,7 @@ class DynamicMixFeed:
         if self.keys is None and self._default_keys is None:
             raise ValueError("the corpus has no roles (it was not read from scp lists): pass keys=")
         self._table = None
+        self._speeds: List[int] = []                    # the converter set: every speed a plan has used, in order of first use
         self._stage: List[torch.Tensor] = []
         self._events: List[Optional[torch.cuda.Event]] = []
         self._slot = 0
@@ -440,7 +552,8 @@ class DynamicMixFeed:
     # ---- device side -------------------------------------------------------------------------------------------------------
     def _launch(self, plan: BatchPlan, mix=None, src=None):
         dev = self.corpus.device
-        words = _table_words(*plan.utt.shape)
+        words = _table_words(*plan.utt.shape, plan.speed is not None)
+        self._speeds += [p for p in plan_speeds(plan) if p not in self._speeds]
         if self._table is None or self._table.numel() != words:
             self._table = torch.empty(words, dtype=torch.int32, device=dev)
             self._stage = [torch.empty(words, dtype=torch.int32).pin_memory() for _ in range(self.SLOTS)]
@@ -449,13 +562,13 @@ class DynamicMixFeed:
         self._slot = (k + 1) % self.SLOTS
         if self._events[k] is not None:
             self._events[k].synchronize()               # the copy that last read this staging buffer has run (SLOTS batches ago)
-        self._stage[k].numpy()[:] = pack_table(plan)
+        self._stage[k].numpy()[:] = pack_table(plan, self._speeds)
         self._table.copy_(self._stage[k], non_blocking=True)
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(dev))
         self._events[k] = ev
         self.last_plan = plan
-        return mix_batch(self.corpus, plan, self.max_len if self.fixed_length else None, mix, src, table=self._table)
+        return mix_batch(self.corpus, plan, self.max_len if self.fixed_length else None, mix, src, table=self._table, speeds=self._speeds)
 
     def __iter__(self):
         for plan in self.plans():

@@ -11,9 +11,14 @@
 Conditions of section 5e: the WHAMR-form launch at B = 16 takes at most 1 % of the fixed-batch step time of THIS run; the mean of the
 fed runs exceeds the mean of the fixed runs by at most the larger within-setting spread (max - min) of this run.
 
+``--speeds 95:105`` measures speed perturbation instead (section 5e-2), in one child process with the settings alternating: the plain
+launch against the launch with every source term perturbed (WSJ0 form, S = 2, B = 16 and 32 x 4 s), and the bf16 training step fed
+without and with speeds; the step without speeds of that same run is the yardstick.
+
 Every step runs in a child process of its own under ``timeout -k 10 <s>``; the first step that fails ends the run.
 
     python tools/dynmix_bench.py [--out profiles/dynmix_timing.json]
+    python tools/dynmix_bench.py --speeds 95:105 [--out profiles/dynmix_speed.json]
 """
 import argparse
 import json
@@ -154,6 +159,100 @@ def step_device():
                      "host_plan_ms_per_batch": plan_ms}}
 
 
+def step_speed(speeds):
+    """Plain launch against perturbed launch, and the training step fed without and with speeds; everything alternating."""
+    import functools
+    import numpy as np
+    import torch
+    from sepreformer_amd import datafeed as df
+    from sepreformer_amd.config import VARIANTS
+    from sepreformer_amd.criterion import PIT_SISNR_mag, PIT_SISNR_time
+    from sepreformer_amd.model import Model
+    from sepreformer_amd.optim import FlatAdamW
+    from sepreformer_amd.train_step import CapturedTrainStep
+    dev = torch.device("cuda:0")
+    keys, arrays = synth_corpus_arrays()
+    corpus = df.Corpus.from_arrays(arrays, device=dev, fs=FS)
+    corpus.roles = {r: list(keys) for r in ROLES}
+    speeds = df.parse_speeds(speeds)
+    every = [p for p in speeds if p != 100]                                   # "every source term perturbed": 100 % left out of the draw
+    plain = functools.partial(df.plan_wsj0, accept=lambda a, b: True)
+    kernel = []
+    for B in (16, 32):
+        sets = {}
+        for name, planner in (("plain", plain), ("perturbed", functools.partial(plain, speeds=every))):
+            rng = random.Random(B)
+            plan = df.collate_plan(corpus, [planner(corpus, rng, keys[i % NKEYS], T4S) for i in range(B)])
+            table = torch.from_numpy(df.pack_table(plan, every)).to(dev)
+            sets[name] = (plan, table, torch.empty(B, T4S, device=dev), [torch.empty(B, T4S, device=dev) for _ in range(plan.S)], [])
+        for i in range(20 + 100):
+            for plan, table, mix, src, ms in sets.values():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                df.mix_batch(corpus, plan, T4S, mix, src, table=table, speeds=every)
+                e1.record()
+                torch.cuda.synchronize()
+                if i >= 20:
+                    ms.append(e0.elapsed_time(e1))
+        plan = sets["perturbed"][0]
+        taps = sum(int(n) * int(df.R_.plan(int(p), 100).K) for n, row in zip(plan.n, plan.speed[:, :plan.M]) for p in row)
+        kernel.append({"form": "wsj0", "B": B, "samples": T4S, "S": plan.S, "plain_device_ms": _stats(sets["plain"][4]),
+                       "perturbed_device_ms": _stats(sets["perturbed"][4]), "launches": 100, "perturbed_terms": int((plan.speed[:, :plan.M] != 100).sum()),
+                       "f64_fma": taps, "Gfma_per_s_at_median": taps / (_stats(sets["perturbed"][4])["median"] * 1e-3) / 1e9})
+    B = 16
+    cfg = VARIANTS["SepReformer_Base_WSJ0"]
+    torch.manual_seed(0)
+    model = Model.from_config(cfg, init_seed=0, precision="bf16").load_synthetic_(0).to(dev).train()
+    crit_t = PIT_SISNR_time(dev, cfg.num_spks, True)
+    crit_m = PIT_SISNR_mag(dev, 512, 128, "hann", cfg.num_stages, cfg.num_spks, True, False)
+    sizes = torch.full((B,), T4S)
+    opt = FlatAdamW(model, lr=1.0e-4, weight_decay=1.0e-2)
+
+    def loss_fn(audio, aux, *tg):
+        tg = list(tg)
+        l_time = crit_t(estims=audio, input_sizes=sizes, target_attr=tg)
+        l_mag = [crit_m(estims=a, idx=i, input_sizes=sizes, target_attr=tg) for i, a in enumerate(aux)]
+        return (0.6 * l_time + 0.4 * sum(l_mag) / len(l_mag)) / cfg.num_spks
+
+    feeds = {"plain": df.DynamicMixFeed(corpus, plain, batch=B, max_len=T4S, seed=0, fixed_length=True),
+             "speeds": df.DynamicMixFeed(corpus, functools.partial(plain, speeds=speeds), batch=B, max_len=T4S, seed=0, fixed_length=True)}
+    x = torch.zeros(B, T4S, device=dev)
+    tg = [torch.zeros(B, T4S, device=dev) for _ in range(2)]
+    feeds["plain"].next_into(x, tg)
+    step = CapturedTrainStep(model, loss_fn, opt, x, tg, max_norm=5.0, warmup=2)
+
+    def loop(feed):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(LOOP_STEPS):
+            feed.next_into(step.x, step.targets)
+            loss, _ = step(step.x, step.targets)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / LOOP_STEPS, float(loss.detach())
+
+    for f in feeds.values():
+        loop(f)                                                               # warm both paths
+    runs = {name: [] for name in feeds}
+    losses = []
+    for _ in range(LOOP_RUNS):
+        for name, f in feeds.items():
+            ms, ls = loop(f)
+            runs[name].append(ms)
+            losses.append(ls)
+    plan_ms = {}
+    for name, f in feeds.items():
+        t0 = time.perf_counter()
+        for _ in range(50):
+            f.next_plan()
+        plan_ms[name] = (time.perf_counter() - t0) * 1e3 / 50
+    step.release()
+    assert all(np.isfinite(v) for v in losses)
+    return {"device": torch.cuda.get_device_name(0), "speeds": speeds, "kernel": kernel,
+            "loop": {"model": "SepReformer_Base_WSJ0 bf16, batch 16 x 4 s, CapturedTrainStep + FlatAdamW, the reference's loss, fed in the WSJ0 form",
+                     "steps_per_run": LOOP_STEPS, "plain_ms_per_step": runs["plain"], "speeds_ms_per_step": runs["speeds"],
+                     "host_plan_ms_per_batch": plan_ms}}
+
+
 def step_host():
     """The reference's per-example work in numpy from RAM-resident arrays (no disk, no decoding of a file): WHAMR form."""
     from concurrent.futures import ThreadPoolExecutor
@@ -203,14 +302,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--step", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--speeds", default=None, metavar="LO:HI", help="measure speed perturbation (an inclusive range or a comma list of percentages)")
     args = ap.parse_args()
     if args.step:
-        rec = {"device": step_device, "host": step_host}[args.step]()
+        rec = {"device": step_device, "host": step_host, "speed": lambda: step_speed(args.speeds)}[args.step]()
         print("__RESULT__" + json.dumps(rec))
         return
     rec, failed = {}, None
-    for name, limit in STEPS:
-        cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", name]
+    for name, limit in ([("speed", 600)] if args.speeds else STEPS):
+        cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", name] + (["--speeds", args.speeds] if args.speeds else [])
         r = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
         lines = [ln for ln in r.stdout.splitlines() if ln.startswith("__RESULT__")]
         if r.returncode != 0 or not lines:
@@ -219,7 +319,16 @@ def main():
             break                                                          # nothing more runs on the device after a failure
         rec.update(json.loads(lines[-1][len("__RESULT__"):]))
         print(name, "done", flush=True)
-    if not failed:
+    if not failed and args.speeds:
+        lp = rec["loop"]
+        a, b = lp["plain_ms_per_step"], lp["speeds_ms_per_step"]
+        mean = lambda v: sum(v) / len(v)                                    # noqa: E731
+        k = next(r for r in rec["kernel"] if r["B"] == 16)
+        rec["summary"] = {"plain_launch_ms_median": k["plain_device_ms"]["median"], "perturbed_launch_ms_median": k["perturbed_device_ms"]["median"],
+                          "plain_step_ms_mean": mean(a), "speeds_step_ms_mean": mean(b), "difference_ms": mean(b) - mean(a),
+                          "plain_step_spread_ms": max(a) - min(a), "speeds_step_spread_ms": max(b) - min(b),
+                          "perturbed_launch_share_of_plain_step": k["perturbed_device_ms"]["median"] / mean(a)}
+    elif not failed:
         lp = rec["loop"]
         fixed, fed = lp["fixed_ms_per_step"], lp["fed_ms_per_step"]
         mean = lambda v: sum(v) / len(v)                                    # noqa: E731

@@ -5,6 +5,7 @@ loss and utt/s every ``--log`` steps.  Schedulers, checkpoints and validation ar
 
     python tools/train_from_scp.py --form wsj0 --scp s1=tr_s1.scp s2=tr_s2.scp --steps 200
     python tools/train_from_scp.py --form whamr --scp s1=.. s2=.. s1_reverb=.. s2_reverb=.. noise=.. --model SepReformer_Large_DM_WHAMR
+    python tools/train_from_scp.py --form wsj0 --scp s1=tr_s1.scp s2=tr_s2.scp --speeds 95:105      # speed perturbation (section 5e-2)
 """
 import argparse
 import os
@@ -25,13 +26,18 @@ def main():
     ap.add_argument("--max-len", type=int, default=32000)
     ap.add_argument("--fs", type=int, default=8000)
     ap.add_argument("--resample", action="store_true", help="convert files at another rate on the device (default: an error)")
+    ap.add_argument("--speeds", default=None, metavar="LO:HI", help="speed perturbation: one speed in percent per source and example, drawn from "
+                    "the inclusive range LO:HI or from a comma list (default: off)")
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--log", type=int, default=10)
     ap.add_argument("--lr", type=float, default=1.0e-4)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args()
+    if args.speeds and args.form == "direct":
+        ap.error("--speeds needs dynamic mixing (--form wsj0, wham or whamr)")
 
+    import functools
     import torch
     from sepreformer_amd import datafeed as df
     from sepreformer_amd.config import VARIANTS
@@ -45,6 +51,8 @@ def main():
     torch.manual_seed(args.seed)
     corpus = df.Corpus.from_scp(dict(a.split("=", 1) for a in args.scp), fs=args.fs, device=dev, resample=args.resample)
     planner = {"wsj0": df.plan_wsj0, "wham": df.plan_wham, "whamr": df.plan_whamr, "direct": df.plan_direct}[args.form]
+    if args.speeds:
+        planner = functools.partial(planner, speeds=df.parse_speeds(args.speeds))
     feed = df.DynamicMixFeed(corpus, planner, batch=args.batch, max_len=args.max_len, seed=args.seed, fixed_length=True)
     print(f"corpus: {len(corpus)} utterances, {corpus.total16 * 2 + corpus.total32 * 4} bytes on {dev}", flush=True)
 
