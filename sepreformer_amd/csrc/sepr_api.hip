@@ -299,14 +299,8 @@ extern "C" int sepr_cla_fwd_st(const float* x, const float* x_stats, float* y, f
   return cla_fwd_impl(x, x_stats, y, y_stats, n, T, F, K, w, ws, ws_bytes, stream);
 }
 
-// the bf16x3 attention kernel serves the bf16x3 arithmetic mode (packed q/k/v present); SEPR_ATTN_F32=1 keeps the f32 one
-static int relattn_x3(const sepr_ega_w* w) {
-  static const bool f32 = [] {
-    const char* e = getenv("SEPR_ATTN_F32");
-    return e && e[0] == '1';
-  }();
-  return (w->attn.x3_qkv.wp != nullptr && !f32) ? 1 : 0;
-}
+// the bf16x3 attention kernel serves the bf16x3 arithmetic mode (packed q/k/v present)
+static int relattn_x3(const sepr_ega_w* w) { return w->attn.x3_qkv.wp != nullptr ? 1 : 0; }
 
 // att_only (sepr_global_block_fwd, gate inside the GCFN kernel): everything up to the pooled attention rows att = ls_o * (Linear_out(o) + b_o),
 // whose workspace address is returned; no gate launch, y untouched.  The caller has checked that the folded output projection applies

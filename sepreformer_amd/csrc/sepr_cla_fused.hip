@@ -831,21 +831,20 @@ __global__ __launch_bounds__(256, 1) void cla_tail_hs_kernel(const ClaFusedArgs 
 
 
 // ---------------------------------------------------------------------------------------------------------------------
-// cla_head_hs_kernel (round 6): the output-split form of the three head-type launches for at most one tile per CU (batch 1).  The four waves
+// cla_head_hs_kernel (round 6): the output-split form of the head-type launches for at most one tile per CU (batch 1).  The four waves
 // hold the SAME 16*MT frames (LayerNorm computed by each) and split the OUTPUT tiles; a weight fragment has one reader and goes global ->
 // registers; no LDS, no barrier, direct stores.  Per accumulator the operand sequence of cla_head_kernel: bit-identical.
 //   HS_GLU   CLA head:  wave w = chunk w (v0 v1 g0 g1 -> 32 gated channels)
 //   HS_GATE  EGA gate with the folded output projection (a.o set): wave w = output tiles 2w, 2w+1 of BOTH projections - the attention's
 //            LayerScale(linear_out(o)) of a frame's pooled row is computed in the lane that needs it (one N tile per frame tile, rows chosen
 //            per lane) and never leaves the registers
-//   HS_QKV   pooling + LayerNorm + q / k / v: wave w = output tiles 6w .. 6w+5 of the [rows, 3F] tensor
 // ---------------------------------------------------------------------------------------------------------------------
-constexpr int HS_GLU = 0, HS_GATE = 1, HS_QKV = 2;
+constexpr int HS_GLU = 0, HS_GATE = 1;
 template <int MODE, int MT>
 __global__ __launch_bounds__(256, 1) void cla_head_hs_kernel(const ClaFusedArgs a) {
   constexpr int F = 128, KS = F / 32;
   constexpr int W1F_U4 = 4 * KS * 2 * 64, CS_U4 = 256, W1_U4 = W1F_U4 + CS_U4;
-  constexpr int NTW = MODE == HS_GLU ? 4 : (MODE == HS_GATE ? 2 : 6);     // plain 16-row tiles of the projection per wave
+  constexpr int NTW = MODE == HS_GLU ? 4 : 2;     // plain 16-row tiles of the projection per wave
   constexpr int TILE = 16 * MT;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int fi = lane & 15, fg = lane >> 4;
@@ -904,8 +903,7 @@ __global__ __launch_bounds__(256, 1) void cla_head_hs_kernel(const ClaFusedArgs 
   __builtin_amdgcn_sched_barrier(0);
   // ---- frames (every wave holds all of them; lane fi holds frames MT*fi .. MT*fi + MT-1) ----
   bf16x8 xh[MT][KS], xl[MT][KS];
-  if constexpr (MODE == HS_QKV) load_frames_pooled<F, MT>(a.x, tile0, a.M, a.pool, a.eps, fi, fg, xh, xl);
-  else load_frames<F, true, MT>(a.x, tile0, a.M, a.eps, fi, fg, xh, xl);
+  load_frames<F, true, MT>(a.x, tile0, a.M, a.eps, fi, fg, xh, xl);
   f32x4 acc[NTW][MT];
 #pragma unroll
   for (int i = 0; i < NTW; ++i) {
@@ -933,18 +931,6 @@ __global__ __launch_bounds__(256, 1) void cla_head_hs_kernel(const ClaFusedArgs 
           const f32x4 hv = acc[j][mt], hg = acc[2 + j][mt];
           st4(a.y + (long long)m * F + 32 * w + 16 * j + 4 * fg,
               make_float4(hv[0] * sigmoid_f(hg[0]), hv[1] * sigmoid_f(hg[1]), hv[2] * sigmoid_f(hg[2]), hv[3] * sigmoid_f(hg[3])));
-        }
-      }
-    }
-  } else if constexpr (MODE == HS_QKV) {
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-      const int m = tile0 + MT * fi + mt;
-      if (m < a.M) {
-#pragma unroll
-        for (int i = 0; i < NTW; ++i) {
-          const f32x4 v = acc[i][mt];
-          st4(a.y + (long long)m * a.ldy + 16 * (NTW * w + i) + 4 * fg, make_float4(v[0], v[1], v[2], v[3]));
         }
       }
     }
@@ -1003,10 +989,7 @@ __global__ __launch_bounds__(256, 1) void cla_head_hs_kernel(const ClaFusedArgs 
 // frame tiles per wave (2 / 4: 32- / 64-frame workgroup tiles) of the output-split head forms for a launch of M rows, 0 = not taken
 // (SEPR_CF_HEAD_HS=0 switches them off)
 static int head_hs_tiles(int M, int cus) {
-  static const bool on = [] {
-    const char* e = getenv("SEPR_CF_HEAD_HS");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = env_int("SEPR_CF_HEAD_HS", 1) != 0;
   if (!on) return 0;
   if ((M + 31) / 32 <= cus) return 2;
   if ((M + 63) / 64 <= cus) return 4;
@@ -1014,14 +997,8 @@ static int head_hs_tiles(int M, int cus) {
 }
 
 // small launches (round 6): when even the 64-frame tiles of the MT = 1 instantiations leave workgroup slots free (cap = two per CU), a launch's
-// duration is one workgroup's dependent chain - halve it.  SEPR_CF_SMALL=<max 64-frame tiles> overrides the bound (0: never; A/B).
-static bool small_launch(int M, int cap) {
-  static const int bound = [] {
-    const char* e = getenv("SEPR_CF_SMALL");
-    return e ? atoi(e) : -1;
-  }();
-  return (M + 63) / 64 <= (bound < 0 ? cap : bound);
-}
+// duration is one workgroup's dependent chain - halve it.
+static bool small_launch(int M, int cap) { return (M + 63) / 64 <= cap; }
 
 int launch_cla_head(const ClaFusedArgs& a, int F, int site, hipStream_t stream) {
   if (a.M <= 0) return SEPR_OK;
@@ -1082,16 +1059,6 @@ int launch_ega_qkv(const ClaFusedArgs& a, int F, int site, hipStream_t stream) {
   const bool timed = prof_begin(site, stream, &slot);
   const int ntiles = (a.M + 127) / 128;
   const int cap = persistent_grid();
-  // (the output-split form of this launch - cla_head_hs_kernel<HS_QKV, .>, SEPR_CF_QKV_HS=1 - measured 19.1 us against 13.4 us for the three
-  //  workgroups per tile below: 32 workgroups at 1000 pooled rows, each wave repeating the pooled loads; profiles/r06_gcfn_hidden_split.txt (8))
-  static const bool qkv_hs = [] {
-    const char* e = getenv("SEPR_CF_QKV_HS");
-    return e && e[0] == '1';
-  }();
-  const int hs = qkv_hs ? head_hs_tiles(a.M, cap / 2) : 0;
-  if (hs == 2) hipLaunchKernelGGL((cla_head_hs_kernel<HS_QKV, 2>), dim3((a.M + 31) / 32), dim3(256), 0, stream, a);
-  else if (hs == 4) hipLaunchKernelGGL((cla_head_hs_kernel<HS_QKV, 4>), dim3((a.M + 63) / 64), dim3(256), 0, stream, a);
-  else
   if (small_launch(3 * a.M, cap)) hipLaunchKernelGGL((cla_head_kernel<128, true, 1, true>), dim3((a.M + 63) / 64, 3), dim3(CF_NT), 0, stream, a);
   else if (small_launch(a.M, cap)) hipLaunchKernelGGL((cla_head_kernel<128, true, 1, true>), dim3((a.M + 63) / 64), dim3(CF_NT), 0, stream, a);
   else hipLaunchKernelGGL((cla_head_kernel<128, true, CF_MT, true>), dim3(ntiles < cap ? ntiles : cap), dim3(CF_NT), 0, stream, a);
@@ -1108,10 +1075,7 @@ int launch_cla_tail(const ClaFusedArgs& a, int F, int site, hipStream_t stream) 
   const int ntiles = (a.M + 127) / 128;
   const int cap = persistent_grid();
   // at most one tile per CU: the hidden-split form, 32- or 64-frame tiles (SEPR_CF_HS=0 switches it off, 2 / 4 force a tile size)
-  static const int hs_force = [] {
-    const char* e = getenv("SEPR_CF_HS");
-    return e && e[0] ? atoi(e) : -1;
-  }();
+  static const int hs_force = env_int("SEPR_CF_HS", -1);
   const int cus = cap / 2;
   const int hs_mt = hs_force == 0 ? 0 : (hs_force == 4 ? ((a.M + 63) / 64 <= cus ? 4 : 0) : ((a.M + 31) / 32 <= cus ? 2 : (hs_force < 0 && (a.M + 63) / 64 <= cus ? 4 : 0)));
   if (F == 256) hipLaunchKernelGGL((cla_tail_kernel<256>), dim3(ntiles < cap / 2 ? ntiles : cap / 2), dim3(CF_NT), 0, stream, a);

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "../../include/sepr.h"
 
@@ -222,6 +223,13 @@ struct Arena {
   }
   bool ok() const { return base != nullptr && off <= size; }
 };
+
+// One process-wide environment switch as an int: unset or empty -> dflt, anything else through atoi.  Call sites keep the value in a
+// `static const`, so a variable is read once per process (the latched, reloadable table is knob() in sepr_api.hip).
+inline int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e && e[0] ? atoi(e) : dflt;
+}
 
 inline int cdiv(long long a, long long b) { return static_cast<int>((a + b - 1) / b); }
 

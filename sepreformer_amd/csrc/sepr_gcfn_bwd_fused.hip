@@ -702,8 +702,7 @@ int launch_gcfn_bwd_fused(const float* x, const float* stats, const float* dy, i
   int nslots = MB;                                                     // rows of `part` the reduction walks
   if (pl) {
     const int g3 = (ntiles < cap / 2 * GB_PL_WGS) ? ntiles : cap / 2 * GB_PL_WGS;   // GB_PL_WGS workgroups per CU
-    static const bool acc_off = [] { const char* e = getenv("SEPR_GB_ACC"); return e && e[0] == '0'; }();     // (A/B switch, read once)
-    if (!acc_off && ntiles > g3 && g3 % (8 * NB) == 0) {   // every workgroup keeps its column block: tile b + k g3 -> nb = (b >> 3) % NB
+    if (ntiles > g3 && g3 % (8 * NB) == 0) {   // every workgroup keeps its column block: tile b + k g3 -> nb = (b >> 3) % NB
       a.acc_part = 1;
       nslots = g3 / NB;                                                // first tiles' mb = 0 .. g3 / NB - 1, all below MB (ntiles > g3)
     }

@@ -1122,21 +1122,7 @@ __global__ __launch_bounds__(256, 1) void gcfn_hs_kernel(const GcfnFusedArgs a) 
 constexpr int GF3_MT = 2, GF3_NW = 4;   // the batched launches: 2 frame tiles per wave, 4 waves x 30 frames (2 waves per SIMD)
 
 // Latency form of the small-launch instantiations (template parameter LAT): taken when a launch has at most one tile per CU, i.e. when its
-// duration IS one workgroup's chunk walk (batch 1, Engine._inference_sample): SEPR_GF_LAT=0 switches it off.
-static int lat_ring() {
-  static const int v = [] {
-    const char* e = getenv("SEPR_GF_LAT");
-    return (e && e[0] ? atoi(e) : 3) != 0 ? 3 : 0;
-  }();
-  return v;
-}
-static int lat_nw() {   // A/B: SEPR_GF_LAT_NW=6 keeps the 6-wave tiles for every latency-form launch
-  static const int v = [] {
-    const char* e = getenv("SEPR_GF_LAT_NW");
-    return e && e[0] ? atoi(e) : 4;
-  }();
-  return v;
-}
+// duration IS one workgroup's chunk walk (batch 1, Engine._inference_sample).
 static int lat_max_tiles() {
   static const int v = [] {
     int dev = 0, cus = 256;
@@ -1150,10 +1136,7 @@ static int lat_max_tiles() {
 // tile with which the launch fits one workgroup per CU (per-launch times by size: profiles/r06_gcfn_hidden_split.txt).  SEPR_GF_HS=0 switches the
 // form off, 2 / 3 / 4 force one tile size (A/B).
 static int hs_tiles(int M) {
-  static const int force = [] {
-    const char* e = getenv("SEPR_GF_HS");
-    return e && e[0] ? atoi(e) : -1;
-  }();
+  static const int force = env_int("SEPR_GF_HS", -1);
   const int cus = lat_max_tiles();
   if (force == 0) return 0;
   if (force >= 2 && force <= 4) return (M + 16 * force - 3) / (16 * force - 2) <= cus ? force : 0;
@@ -1162,12 +1145,8 @@ static int hs_tiles(int M) {
   return 0;
 }
 
-static int hs_tiles_plain(int M) {   // same for the PLAIN instantiations (no halo: 32- / 48-frame tiles); SEPR_GF_HS_PLAIN=0 switches them off
-  static const int on = [] {
-    const char* e = getenv("SEPR_GF_HS_PLAIN");
-    const char* g = getenv("SEPR_GF_HS");
-    return !((e && e[0] == '0') || (g && g[0] == '0'));
-  }();
+static int hs_tiles_plain(int M) {   // same for the PLAIN instantiations (no halo: 32- / 48-frame tiles)
+  static const bool on = env_int("SEPR_GF_HS", -1) != 0;
   if (!on) return 0;
   const int cus = lat_max_tiles();
   for (int mt = 2; mt <= 3; ++mt)
@@ -1202,9 +1181,9 @@ int launch_glumlp_fused(const GcfnFusedArgs& a, int F, int site, hipStream_t str
   if (a.M < 12000) {
     const int ntiles = (a.M + 95) / 96;
     // one tile per CU at most: the latency form (3-stage weight ring, one workgroup per CU), 4 waves (one per SIMD) when that still fits
-    const int lat = ntiles <= lat_max_tiles() ? lat_ring() : 0;
+    const bool lat = ntiles <= lat_max_tiles();
     const int nt4 = (a.M + 63) / 64;
-    if (lat && nt4 <= lat_max_tiles() && lat_nw() != 6)
+    if (lat && nt4 <= lat_max_tiles())
       hipLaunchKernelGGL((gcfn_fused3_kernel<128, 1, 4, 1, false, false, 3>), dim3(nt4), dim3(256), 0, stream, a);
     else if (lat) hipLaunchKernelGGL((gcfn_fused3_kernel<128, 1, 6, 1, false, false, 3>), dim3(ntiles), dim3(384), 0, stream, a);
     else hipLaunchKernelGGL((gcfn_fused3_kernel<128, 1, 6, 1>), dim3(ntiles < cap ? ntiles : cap), dim3(384), 0, stream, a);
@@ -1252,29 +1231,16 @@ int launch_glumlp_fold(const GcfnFusedArgs& a_in, int F, int site, hipStream_t s
 // 14-frame-wave instantiation: 1.4x more, shorter tiles.  A frame's arithmetic does not depend on the tiling, so the
 // result is bit-identical; for large launches the 30-frame form is 1.7x faster per frame (weight re-use).
 static int gf_small_rows() {
-  static const int v = [] {
-    const char* e = getenv("SEPR_GF_SMALL_ROWS");
-    return e && e[0] ? atoi(e) : 17000;
-  }();
+  static const int v = env_int("SEPR_GF_SMALL_ROWS", 17000);
   return v;
 }
 
-bool gcfn_fused_takes_gate(int M, int F) {
-  static const int big_ring = [] {
-    const char* e = getenv("SEPR_GF_BIG_RING");
-    return e && e[0] ? atoi(e) : 0;
-  }();
-  return F == 128 && !big_ring && M >= gf_small_rows();
-}
+bool gcfn_fused_takes_gate(int M, int F) { return F == 128 && M >= gf_small_rows(); }
 
 int launch_gcfn_fused(const GcfnFusedArgs& a_in, int F, int site, hipStream_t stream) {
   if (a_in.M <= 0) return SEPR_OK;
-  static const int stagger = [] {
-    const char* e = getenv("SEPR_GF_STAGGER");
-    return e && e[0] ? atoi(e) : 0;
-  }();
   GcfnFusedArgs a = a_in;
-  a.stagger = stagger;
+  a.stagger = 0;
   if (!a.x || !a.y || !a.w1p || !a.w2p || !a.b2 || !a.ls || a.T <= 0 || (F != 64 && F != 128 && F != 256)) return SEPR_EINVAL;
   if (a.x == a.y) return SEPR_EINVAL;   // halo frames of a tile are outputs of its neighbours
   if (F == 256) {
@@ -1315,9 +1281,9 @@ int launch_gcfn_fused(const GcfnFusedArgs& a_in, int F, int site, hipStream_t st
       else if (mt == 3) hipLaunchKernelGGL((gcfn_hs_kernel<3>), dim3(nt), dim3(256), 0, stream, a);
       else hipLaunchKernelGGL((gcfn_hs_kernel<4>), dim3(nt), dim3(256), 0, stream, a);
     } else if (F == 128) {
-      const int lat = ntiles <= lat_max_tiles() ? lat_ring() : 0;
+      const bool lat = ntiles <= lat_max_tiles();
       const int nt4 = (a.M + 4 * 14 - 1) / (4 * 14);
-      if (lat && nt4 <= lat_max_tiles() && lat_nw() != 6)
+      if (lat && nt4 <= lat_max_tiles())
         hipLaunchKernelGGL((gcfn_fused3_kernel<128, 1, 4, 0, false, false, 3>), dim3(nt4), dim3(256), 0, stream, a);
       else if (lat) hipLaunchKernelGGL((gcfn_fused3_kernel<128, 1, 6, 0, false, false, 3>), dim3(grid), dim3(384), 0, stream, a);
       else hipLaunchKernelGGL((gcfn_fused3_kernel<128, 1, 6>), dim3(grid), dim3(384), 0, stream, a);
@@ -1332,27 +1298,6 @@ int launch_gcfn_fused(const GcfnFusedArgs& a_in, int F, int site, hipStream_t st
       const int ntiles = (a.M + tile_rows - 1) / tile_rows;
       const int cap = persistent_grid();
       const int grid = ntiles < cap ? ntiles : cap;
-      static const int big_ring = [] {   // EXPERIMENT (round 6): the ring form for LARGE launches - one 8-wave workgroup per CU, 30-frame waves
-        const char* e = getenv("SEPR_GF_BIG_RING");
-        return e && e[0] ? atoi(e) : 0;
-      }();
-      if (big_ring >= 2 && !a.train && F == 128) {
-        // EXPERIMENT (round 6): the one-wave-per-SIMD regime at F = 128 - four 64-frame waves (MT = 4, 512 registers), one workgroup per CU;
-        // 2 = two-barrier form with the seam exchange (254-frame tiles), 3 = ring form without it (248-frame tiles)
-        const int cus = lat_max_tiles();
-        if (big_ring == 2) {
-          const int nt = (a.M + 253) / 254;
-          hipLaunchKernelGGL((gcfn_fused3_kernel<128, 4, 4>), dim3(nt < cus ? nt : cus), dim3(256), 0, stream, a);
-        } else {
-          const int nt = (a.M + 247) / 248;
-          hipLaunchKernelGGL((gcfn_fused3_kernel<128, 4, 4, 0, false, false, 3>), dim3(nt < cus ? nt : cus), dim3(256), 0, stream, a);
-        }
-      } else
-      if (big_ring && !a.train && F == 128) {
-        const int nt8 = (a.M + 8 * 30 - 1) / (8 * 30);
-        const int cus = lat_max_tiles();
-        hipLaunchKernelGGL((gcfn_fused3_kernel<128, 2, 8, 0, false, false, 3>), dim3(nt8 < cus ? nt8 : cus), dim3(512), 0, stream, a);
-      } else
       if (a.train && a.planes == 1) {
         if (F == 128) hipLaunchKernelGGL((gcfn_fused3_kernel<128, GF3_MT, GF3_NW, 0, true, true>), dim3(grid), dim3(64 * GF3_NW), 0, stream, a);
         else hipLaunchKernelGGL((gcfn_fused3_kernel<64, GF3_MT, GF3_NW, 0, true, true>), dim3(grid), dim3(64 * GF3_NW), 0, stream, a);

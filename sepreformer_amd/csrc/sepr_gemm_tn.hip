@@ -43,9 +43,8 @@ inline TnPlan tn_plan(int M, int N, int K) {
   const int tiles = p.tn * p.tk;
   // Row slices: enough workgroups to fill the chip (2 co-resident per CU = 512), but every slice pays a partial tile of
   // up to 64 KB written and re-read by the reduction, so a slice is at least 256 rows (its inputs: 256 x (N + K) x 4 B).
-  // SEPR_TN_WGS / SEPR_TN_MINROWS: experiment knobs of tools/wgrad_bench.py (read once; the defaults are the product plan)
-  static const int target_wgs = [] { const char* e = getenv("SEPR_TN_WGS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 512; }();
-  static const int min_rows = [] { const char* e = getenv("SEPR_TN_MINROWS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 256; }();
+  constexpr int target_wgs = 512;   // (384 / 256 workgroups: 3-30 % slower at the big shapes - docs/HISTORY.md "Contraction plan sweep")
+  constexpr int min_rows = 256;     // (flat between 128 and 256 rows, slower from 512 up - docs/HISTORY.md "minimum rows per slice")
   int ns = target_wgs / tiles;
   if (ns < 1) ns = 1;
   const int max_by_rows = (M + min_rows - 1) / min_rows;
@@ -682,18 +681,15 @@ void tn_parts_set(void* parts, size_t bytes) {
   g_parts.stream = nullptr;
 }
 
-int launch_gemm_tn(const TnArgs& a, int x3, void* ws, size_t ws_bytes, hipStream_t s_main) {
+int launch_gemm_tn(const TnArgs& a, int x3, void* ws, size_t ws_bytes, hipStream_t s) {
   if (a.M <= 0) return SEPR_OK;
   if (!a.A || !a.B || !a.G || a.N <= 0 || a.K <= 0 || (a.N % 4) || (a.K % 4) || (a.lda % 4) || (a.ldb % 4)) return SEPR_EINVAL;
   if (a.B2 && ((a.ksplit % 4) || (a.ldb2 % 4))) return SEPR_EINVAL;
   const TnPlan p = tn_plan(a.M, a.N, a.K);
   const size_t need = tn_workspace_bytes(a.M, a.N, a.K);
   if (!ws || ws_bytes < need) return SEPR_EWORKSPACE;
-  // contraction + its split-M reduction run on the registered weight-gradient side stream when there is one (sepr_train.h wgrad_stream):
-  // nothing in a backward walk consumes their output before the window's join
-  hipStream_t s = wgrad_stream(s_main);
   // this contraction's reduction can wait for the next contraction (see above): outputs in the window's arena, partial tiles in a buffer half
-  bool defer_red = g_parts.base != nullptr && s == s_main && need <= g_parts.half && fin_defers(a.G) && (!a.colsum || fin_defers(a.colsum)) &&
+  bool defer_red = g_parts.base != nullptr && need <= g_parts.half && fin_defers(a.G) && (!a.colsum || fin_defers(a.colsum)) &&
                    (!g_parts.used || g_parts.stream == s);
   // a pending job rides on this launch when it was issued on this stream; otherwise it runs on its own now
   if (g_pend.valid && g_pend.stream != s) SEPR_TRY(tn_flush_pending());
@@ -708,16 +704,12 @@ int launch_gemm_tn(const TnArgs& a, int x3, void* ws, size_t ws_bytes, hipStream
   const int grid = p.tn * p.tk * p.nsplit;
   // test switch (tests/tn_general_loader.py; read once, never set in the product): SEPR_TN_FORCE_GEN=1 routes every launch through the
   // general loader, so the public sepr_linear_wgrad_norm entry exercises it with per-row statistics at any size
-  static const bool force_gen = [] { const char* e = getenv("SEPR_TN_FORCE_GEN"); return e && e[0] == '1'; }();
+  static const bool force_gen = env_int("SEPR_TN_FORCE_GEN", 0) == 1;
   const bool gen = force_gen || a.rows_out > 0 || a.B2 != nullptr || a.idx != nullptr || a.mask_a != 0 || a.stat_seq != 0;
   if (gen && (a.a16 || a.b16)) return SEPR_EINVAL;      // (checked before the profiling slot opens)
   // the filter gradients of the waveform ends (K = 16 taps, exact arithmetic, windowed-frame row map): one pass over A on the VALU
-  static const bool smallk_off = [] {
-    const char* e = getenv("SEPR_TN_SMALLK");
-    return e && e[0] == '0';
-  }();
   const bool smallk = x3 == 0 && a.K == 16 && a.N <= 256 && a.rows_out > 0 && !a.B2 && !a.idx && !a.stats && !a.mask_a && a.b_shift == 0 && !a.colsum &&
-                      !a.a16 && !a.b16 && p.tn * p.tk <= 2 && !smallk_off;
+                      !a.a16 && !a.b16 && p.tn * p.tk <= 2;
   if (smallk) SEPR_TRY(tn_flush_pending());             // (its kernel carries no riding blocks)
   long long slot = -1;
   const bool timed = prof_begin(SEPR_SITE_WGRAD, s, &slot);

@@ -1,22 +1,8 @@
 // Instantiations + host launcher of the bf16x3 projection core.
 #include "sepr_gemm_x3w.h"
 #include "sepr_pointwise.h"
-#include <stdlib.h>
 
 namespace sepr {
-
-// workgroups per launch: SEPR_X3_GRID = "tiles" -> one tile per workgroup (no persistent walk), an integer k ->
-// k workgroups per CU; default 2 per CU (what fits: 80 KB of LDS each)
-static int x3_grid_cap() {
-  static const int v = [] {
-    const char* e = getenv("SEPR_X3_GRID");
-    if (!e || !e[0]) return persistent_grid();
-    if (e[0] == 't') return 0;
-    const int k = atoi(e);
-    return k > 0 ? persistent_grid() / 2 * k : persistent_grid();
-  }();
-  return v;
-}
 
 // SEPR_X3_WIDE: 0 = the 128 x 128 core only, 1 (default) = the 128 x 256 core (sepr_gemm_x3w.h) for launches with an even number of
 // 128-column tiles and at least two wide tiles per CU, 2 = for every launch with an even number of column tiles (A/B)
@@ -26,14 +12,14 @@ static int x3_wide_mode() { return knob(SEPR_KNOB_X3_WIDE); }
 
 template <int PRO, int EPI, int TAG = 0>
 static void launch_x3_inst(const GemmArgs& a, hipStream_t stream) {
-  const int cap = x3_grid_cap();
+  const int cap = persistent_grid();
   if constexpr (EPI != EPI_LNBWD) {
     const bool glu = (EPI == EPI_GLU) || (EPI == EPI_GLUSAVE) || (EPI == EPI_DWGLU);
     const int NB = glu ? (a.N / 2 + 63) / 64 : (a.N + GEMM_BN - 1) / GEMM_BN;
     const int wmode = x3_wide_mode();
     const int wtiles = gemm_tiles_wide(a, EPI);
-    if (wmode > 0 && NB >= 2 && (NB % 2) == 0 && (wmode == 2 || wtiles >= persistent_grid())) {
-      const int grid = (cap <= 0 || wtiles < cap) ? wtiles : cap;
+    if (wmode > 0 && NB >= 2 && (NB % 2) == 0 && (wmode == 2 || wtiles >= cap)) {
+      const int grid = wtiles < cap ? wtiles : cap;
       hipLaunchKernelGGL((gemm_x3w_kernel<PRO, EPI, TAG>), dim3(grid), dim3(GEMM_THREADS), 0, stream, a);
       // output-row statistics: in the kernel's tile tail when a wide tile holds whole rows, else by the row-statistics kernel
       if (a.stats_out && !(NB == 2 && EPI == EPI_RES)) (void)launch_rowstats(a.Y, a.stats_out, a.M, a.N, a.stats_eps, stream);
@@ -41,7 +27,7 @@ static void launch_x3_inst(const GemmArgs& a, hipStream_t stream) {
     }
   }
   const int tiles = gemm_tiles(a, EPI);
-  const int grid = (cap <= 0 || tiles < cap) ? tiles : cap;
+  const int grid = tiles < cap ? tiles : cap;
   hipLaunchKernelGGL((gemm_x3_kernel<PRO, EPI, TAG>), dim3(grid), dim3(GEMM_THREADS), 0, stream, a);
   if (a.stats_out) (void)launch_rowstats(a.Y, a.stats_out, a.M, a.N, a.stats_eps, stream);
 }

@@ -14,10 +14,7 @@ constexpr int TPB = 256;
 // SEPR_LEGACY_POINTWISE=1 routes the 65-tap depthwise conv and the speaker mix through their first-generation
 // kernels (A/B measurements and bisecting a parity failure; read once)
 static bool legacy_pointwise() {
-  static const bool v = [] {
-    const char* e = getenv("SEPR_LEGACY_POINTWISE");
-    return e && e[0] == '1';
-  }();
+  static const bool v = env_int("SEPR_LEGACY_POINTWISE", 0) == 1;
   return v;
 }
 

@@ -599,10 +599,7 @@ int launch_spk_fused(const SpkFusedArgs& a, int F, int site, hipStream_t stream)
   const int cap = persistent_grid();
   const int grid = ntiles < cap ? ntiles : cap;
   // at most one tile per CU: the hidden-split form, 16- or 32-frame tiles (SEPR_SPK_HS=0 switches it off)
-  static const bool hs_on = [] {
-    const char* e = getenv("SEPR_SPK_HS");
-    return !(e && e[0] == '0');
-  }();
+  static const bool hs_on = env_int("SEPR_SPK_HS", 1) != 0;
   const int cus = cap / 2;
   if (F == 128 && hs_on && (a.NF + 15) / 16 <= cus) hipLaunchKernelGGL((spk_hs_kernel<1>), dim3((a.NF + 15) / 16), dim3(256), 0, stream, a);
   else if (F == 128 && hs_on && (a.NF + 31) / 32 <= cus) hipLaunchKernelGGL((spk_hs_kernel<2>), dim3((a.NF + 31) / 32), dim3(256), 0, stream, a);

@@ -419,7 +419,6 @@ int cla_bwd(const float* x, const float* dy, float* dx, int n, int T, int F, int
   SEPR_TRY(wgrad(dd, 2 * F, k.c, F, nullptr, g->w2, g->b2, M, 2 * F, F, 1, x3, tnw, tnb, st));                   // linear2 (direct)
   SEPR_TRY(plain(dd, 2 * F, dc, F, M, F, 2 * F, w->l2_t, nullptr, st));
   SEPR_TRY(launch_dwconv_wgrad(k.u, dc, n, T, F, K, g->dw_w, g->dw_b, wgw, wgb, st));
-  wgrad_join(st);   // dd (dz) is re-used for da below while linear2's contraction - on the weight-gradient side stream, if one is registered - may still read it
   if (F % 128 == 0 && K == 65) {   // correlation with reversed taps, GLU backward in its epilogue (round 4): dd := da [M][2F]
     SEPR_TRY(launch_dwconv_same_glu_bwd(dc, k.a, dd, n, T, F, K, w->dw_wf, w->zeros, st));
   } else {
@@ -459,14 +458,10 @@ int mha_qkv_bwd(const float* dqkv, const float* xin, const float* stats, float* 
 // =====================================================================================================================
 // The attention of the packed-bf16 precisions runs flash-style on the bf16 MFMA (sepr_attention.hip TRAIN instantiation,
 // sepr_train_attn_x3.hip): its context keeps one log-sum-exp per query row where the exact-f32 VALU kernels keep the [Tp, Tp]
-// probabilities (k.P below is then [n*H, Tp]).  SEPR_TRAIN_ATTN_VALU=1 forces the VALU kernels (A/B, tests).
+// probabilities (k.P below is then [n*H, Tp]).
 bool ega_mfma(const sepr_ega_tw* w, int F, int H) {
-  static const bool force_valu = [] {
-    const char* e = getenv("SEPR_TRAIN_ATTN_VALU");
-    return e && e[0] == '1';
-  }();
   const int dk = H > 0 ? F / H : 0;
-  return w && w->attn.qkv.wp && !force_valu && (dk == 16 || dk == 32);
+  return w && w->attn.qkv.wp && (dk == 16 || dk == 32);
 }
 struct EgaCtx { float *stats, *stats_p, *xd, *qkv, *P, *o, *att, *zg; };
 EgaCtx ega_ctx(Carve& cx, int n, int T, int Tp, int F, int H, bool mfma = false) {

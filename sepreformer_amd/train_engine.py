@@ -46,38 +46,9 @@ class TrainEngine:
         # (profiles/r06_wgrad_dma.txt) - off by default, SEPR_TRAIN_RIDE=1 enables
         self._ride = os.environ.get("SEPR_TRAIN_RIDE", "0") == "1"
         self._parts: Optional[torch.Tensor] = None          # double buffer of partial tiles (riding reductions)
-        # Weight-gradient side stream (round 6, include/sepr.h sepr_train_wgrad_stream; SEPR_TRAIN_WGRAD_STREAM=1, OFF by default): inside backward()
-        # the contractions run on a second stream beside the input-gradient chain; two workspaces alternate between consecutive block calls (a
-        # call's workspace is still read by its side-stream contractions after it returns).  Bit-identical gradients, all 149 training tests
-        # green with it on - and MEASURED NOT FASTER: 211.9 / 213.3 vs 214.4 / 213.8 utt/s captured, 195 vs 211 eager (profiles/r06_train_wgrad_stream.txt):
-        # every contraction and every kernel of the input-gradient chain fills the machine on its own, two streams only interleave them.
-        self._wg_on = os.environ.get("SEPR_TRAIN_WGRAD_STREAM", "0") == "1"
-        self._wg_side: Optional[torch.cuda.Stream] = None
-        self._wg_active = False
-        self._ws_alt: list = [None, None]
-        self._ws_slot = 0
-        self._wg_keep: list = []                 # tensors a side-stream kernel may still read (the last few d(activation) tensors)
-        self._attn_valu = os.environ.get("SEPR_TRAIN_ATTN_VALU", "0") == "1"     # (the library latches it at its first EGA call as well)
 
     # ---- plumbing -------------------------------------------------------------------------------------------------------
     def _workspace(self, nbytes: int):
-        if self._wg_active:
-            # one call = one block's backward: close the bracket of the workspace the previous call used, take the OTHER one and wait for
-            # the side-stream work of the call that last used it (two calls ago)
-            lib = self.lib
-            st = torch.cuda.current_stream(self.device).cuda_stream
-            L.check(lib.sepr_train_wgrad_mark(self._ws_slot), "sepr_train_wgrad_mark")
-            self._ws_slot ^= 1
-            L.check(lib.sepr_train_wgrad_wait(self._ws_slot, st), "sepr_train_wgrad_wait")
-            buf = self._ws_alt[self._ws_slot]
-            if buf is None or buf.numel() < nbytes:
-                if torch.cuda.is_current_stream_capturing():
-                    raise RuntimeError("TrainEngine: a backward workspace would have to grow during a hipGraph capture (run one eager step of this shape first)")
-                torch.cuda.synchronize(self.device)          # (warm-up only) the side stream may still read the buffers being replaced
-                self._ws_alt = [None, None]                   # BOTH grow to the largest request seen: which call lands on which buffer is a matter of parity
-                self._ws_alt = [torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=self.device) for _ in range(2)]
-                buf = self._ws_alt[self._ws_slot]
-            return buf.data_ptr(), buf.numel()
         if self._ws is None or self._ws.numel() < nbytes:
             self._ws = None
             self._ws = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=self.device)
@@ -120,7 +91,7 @@ class TrainEngine:
         """Sizing op of an EGA block: the packed-bf16 precisions run the attention flash-style on the bf16 MFMA (context = one
         log-sum-exp per query row instead of the [Tp, Tp] probabilities); mirrors ``ega_mfma`` of csrc/sepr_train_api.hip."""
         dk = self.cfg.feat // self.cfg.heads
-        mfma = bool(tw.attn.qkv.wp) and dk in (16, 32) and not self._attn_valu
+        mfma = bool(tw.attn.qkv.wp) and dk in (16, 32)
         return L.TOP_EGA_X3 if mfma else L.TOP_EGA
 
     # ---- single blocks (also what the unit tests drive) --------------------------------------------------------------------
@@ -350,21 +321,7 @@ class TrainEngine:
         # there) and at the end.  The arena holds the reduced contractions in between: about one model's worth of parameters.
         if not self._defer:
             return self._backward_walk(tape, dims, d_wav, d_aux, tp, p_drop, on_decoder_done)
-        st_main = torch.cuda.current_stream(self.device).cuda_stream
-        if self._wg_on:
-            if self._wg_side is None:
-                self._wg_side = torch.cuda.Stream(device=self.device)
-            L.check(self.lib.sepr_train_wgrad_stream(self._wg_side.cuda_stream), "sepr_train_wgrad_stream")
-            self._wg_active = True
-            self._ws_slot = 0
-        try:
-            self._backward_deferred(tape, dims, d_wav, d_aux, tp, p_drop, on_decoder_done)
-        finally:
-            if self._wg_active:
-                self._wg_active = False
-                self.lib.sepr_train_wgrad_join(st_main)
-                self.lib.sepr_train_wgrad_stream(None)
-                self._wg_keep.clear()
+        self._backward_deferred(tape, dims, d_wav, d_aux, tp, p_drop, on_decoder_done)
 
     def _backward_deferred(self, tape, dims, d_wav, d_aux, tp, p_drop, on_decoder_done):
         if self._fin_arena is None:
@@ -372,7 +329,7 @@ class TrainEngine:
             self._fin_arena = torch.empty(int(1.25 * 4 * n_par) + (8 << 20), dtype=torch.uint8, device=self.device)
         st_ = torch.cuda.current_stream(self.device).cuda_stream
         L.check(self.lib.sepr_train_defer_begin(self._fin_arena.data_ptr(), self._fin_arena.numel()), "sepr_train_defer_begin")
-        if self._ride and not self._wg_on:
+        if self._ride:
             # riding reductions (include/sepr.h sepr_train_defer_parts): the partial tiles of a contraction wait in one half of this double
             # buffer for the next contraction's launch, which runs their reduction in appended blocks (~290 launches fewer per step)
             if self._parts is None:
@@ -398,11 +355,6 @@ class TrainEngine:
         enc_saved = tape[0][2]                       # the auxiliary heads mask with the encoder output ("front" record)
         for rec in reversed(tape):
             kind = rec[0]
-            if self._wg_active and dcur is not None:
-                # a side-stream contraction may read the gradient tensor a block was given after the walk has dropped it: hold the last few
-                self._wg_keep.append(dcur)
-                if len(self._wg_keep) > 6:
-                    del self._wg_keep[0]
             if kind == "block":
                 dcur = self.block_bwd(rec[1], dcur)
             elif kind == "head_main":

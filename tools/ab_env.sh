@@ -1,6 +1,6 @@
 #!/bin/bash
 # whole-model A/B over environment settings (one bench run each; "-" = defaults):
-#   bash tools/ab_env.sh - "SEPR_X3_GRID=tiles" "SEPR_X3_GRID=4 SEPR_GF_GRID=tiles"
+#   bash tools/ab_env.sh - "SEPR_X3_WIDE=0" "SEPR_X3_WIDE=2 SEPR_GF_SMALL_ROWS=0"
 export TMPDIR=/tmp
 mkdir -p gpurun_out; : > gpurun_out/ab_env.txt
 for v in "$@"; do
