@@ -296,6 +296,19 @@ int sepr_outlayer_decoder_fwd(const float* x, int nS, int S, int Tsrc, int L, co
                               const float* enc, int F, int N, int K, int stride, const sepr_out_w* w,
                               float* wav, void* ws, size_t ws_bytes, sepr_stream_t stream);
 
+/* The auxiliary heads (model.py:47-52) as NH basis calls + ONE decoder launch that reads each encoder frame once for all heads and
+ * speakers, instead of NH sepr_outlayer_decoder_fwd(idx, enc) calls that each read enc once per speaker.  The waveforms are bit-identical.
+ * sepr_outlayer_basis_fwd: the two OutputLayer projections of a head on its nS*Tsrc SOURCE rows (Tsrc <= L; the launches
+ * sepr_outlayer_decoder_fwd issues for an upsampled head): x [nS,Tsrc,F] -> o2 [nS*Tsrc,N], caller-owned.  Workspace as for
+ * SEPR_OP_OUTLAYER.
+ * sepr_aux_decoder_fwd: for h < NH, 1 <= NH <= 4: wav[h] [S,B,Tout] = decoder(ReLU(o2[h][b*S+s, idx[h][l]]) * enc[b,l]) with wdec[h] [K,N] (sepr_out_w.wdec), idx[h] [L] the
+ * nearest-upsample table with values < Tsrc[h] <= L.  o2, idx, wdec, wav, Tsrc are HOST arrays of NH entries (device pointers / ints), copied into
+ * the launch.  S in {2,3}, K = 16, 4 <= stride <= 16, N % 64 == 0; SEPR_EINVAL for anything else or a NULL entry (use the per-head call then). */
+int sepr_outlayer_basis_fwd(const float* x, int nS, int Tsrc, int L, int F, int N, const sepr_out_w* w, float* o2, void* ws,
+                            size_t ws_bytes, sepr_stream_t stream);
+int sepr_aux_decoder_fwd(int NH, const float* const* o2, const int* const* idx, const float* const* wdec, float* const* wav,
+                         const int* Tsrc, const float* enc, int B, int S, int L, int N, int K, int stride, sepr_stream_t stream);
+
 /* GroupNorm(1 group) statistics of x [n, count] -> stats [n,2] = (mean, rstd).  modules/module.py:28,117 */
 int sepr_groupnorm_stats(const float* x, int n, long long count, float eps, float* stats, void* ws,
                          size_t ws_bytes, sepr_stream_t stream);

@@ -538,32 +538,13 @@ extern "C" int sepr_fuse_fwd(const float* lo, const float* skip, float* y, int n
   return project(PRO_CAT2, EPI_STORE, a, w->x3, SEPR_SITE_FUSE, static_cast<hipStream_t>(stream));
 }
 
-extern "C" int sepr_outlayer_decoder_fwd(const float* x, int nS, int S, int Tsrc, int L, const int* idx, const float* enc,
-                                         int F, int N, int K, int stride, const sepr_out_w* w, float* wav, void* ws,
-                                         size_t ws_bytes, sepr_stream_t stream) {
-  if (!x || !w || !wav || nS <= 0 || S <= 0 || nS % S != 0 || Tsrc <= 0 || L <= 0 || F % 32 != 0 || N % 4 != 0) return SEPR_EINVAL;
-  if (!idx && L > Tsrc) return SEPR_EINVAL;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const long long M = (long long)nS * L;
-  if (M > 0x7fffffffLL / 8) return SEPR_EINVAL;
-  if (w->fold_w2p && w->fold_b && w->fused_w1p && (F == 128 || F == 256) && !idx && !enc && K == 16 && stride == 4 && knob(SEPR_KNOB_FOLD_HEAD)) {
-    // main head (masking = False, model.py:28): end_conv1x1.2 and the ConvTranspose1d are one linear map - one launch, no [rows, N]
-    // basis tensor, no workspace (launch_glumlp_fold)
-    GcfnFusedArgs f = {};
-    f.x = x; f.y = wav; f.T = L; f.in_src = Tsrc;
-    f.w1p = w->fused_w1p; f.w2p = w->fold_w2p; f.b2 = w->fold_b;
-    f.nch = 2 * F / 32; f.out_S = S; f.fold_nseq = nS; f.fold_N = N;
-    return launch_glumlp_fold(f, F, SEPR_SITE_OUT, st);
-  }
-  Arena ar(ws, ws_bytes);
-  float* o1 = ar.f32(2LL * F * M);
-  float* o2 = ar.f32((long long)N * M);
-  if (!ar.ok()) return SEPR_EWORKSPACE;
-  // Both projections are per-frame maps, so for an upsampled head (idx != NULL) they run on the Tsrc source frames of
-  // every sequence, not on the L repeated ones; the decoder kernel applies idx, the ReLU mask and the encoder product
-  // while it reads the rows.  Without idx the row map is the crop of module.py:250.
-  const bool unique = idx != nullptr && Tsrc <= L;   // (a down-sampling map keeps the gather in the first projection)
-  const long long Mp = unique ? (long long)nS * Tsrc : M;
+// OutputLayer's two projections (module.py:250-256) of x [nS, Tsrc, F] into the basis rows o2 [Mp, N]; o1 [Mp, 2F] is scratch of the
+// two-launch form.  Both projections are per-frame maps, so for an upsampled head (unique) they run on the Tsrc source frames of
+// every sequence, not on the L repeated ones (Mp = nS * Tsrc); the decoder kernel applies idx, the ReLU mask and the encoder product
+// while it reads the rows.  Otherwise Mp = nS * L rows, gathered through idx or, without idx, cropped as in module.py:250.
+static int outlayer_basis(const float* x, int nS, int Tsrc, int L, const int* idx, bool unique, int F, int N, const sepr_out_w* w,
+                          float* o1, float* o2, hipStream_t st) {
+  const long long Mp = (long long)nS * (unique ? Tsrc : L);
   if (w->fused_w1p && w->fused_w2p && (F == 128 || F == 256) && N % F == 0 && (unique || !idx)) {
     // one kernel per F basis columns: Linear F->4F + GLU + Linear 2F->N; the crop of module.py:250 is the kernel's row map
     const int nch = 2 * F / 32;
@@ -593,10 +574,59 @@ extern "C" int sepr_outlayer_decoder_fwd(const float* x, int nS, int S, int Tsrc
     SEPR_TRY(project(PRO_PLAIN, EPI_STORE, a, w->x3_2, SEPR_SITE_OUT, st));
   }
   }
+  return SEPR_OK;
+}
+
+extern "C" int sepr_outlayer_decoder_fwd(const float* x, int nS, int S, int Tsrc, int L, const int* idx, const float* enc,
+                                         int F, int N, int K, int stride, const sepr_out_w* w, float* wav, void* ws,
+                                         size_t ws_bytes, sepr_stream_t stream) {
+  if (!x || !w || !wav || nS <= 0 || S <= 0 || nS % S != 0 || Tsrc <= 0 || L <= 0 || F % 32 != 0 || N % 4 != 0) return SEPR_EINVAL;
+  if (!idx && L > Tsrc) return SEPR_EINVAL;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const long long M = (long long)nS * L;
+  if (M > 0x7fffffffLL / 8) return SEPR_EINVAL;
+  if (w->fold_w2p && w->fold_b && w->fused_w1p && (F == 128 || F == 256) && !idx && !enc && K == 16 && stride == 4 && knob(SEPR_KNOB_FOLD_HEAD)) {
+    // main head (masking = False, model.py:28): end_conv1x1.2 and the ConvTranspose1d are one linear map - one launch, no [rows, N]
+    // basis tensor, no workspace (launch_glumlp_fold)
+    GcfnFusedArgs f = {};
+    f.x = x; f.y = wav; f.T = L; f.in_src = Tsrc;
+    f.w1p = w->fused_w1p; f.w2p = w->fold_w2p; f.b2 = w->fold_b;
+    f.nch = 2 * F / 32; f.out_S = S; f.fold_nseq = nS; f.fold_N = N;
+    return launch_glumlp_fold(f, F, SEPR_SITE_OUT, st);
+  }
+  Arena ar(ws, ws_bytes);
+  float* o1 = ar.f32(2LL * F * M);
+  float* o2 = ar.f32((long long)N * M);
+  if (!ar.ok()) return SEPR_EWORKSPACE;
+  const bool unique = idx != nullptr && Tsrc <= L;   // (a down-sampling map keeps the gather in the first projection)
+  SEPR_TRY(outlayer_basis(x, nS, Tsrc, L, idx, unique, F, N, w, o1, o2, st));
   // ReLU(.) * encoder_output for the auxiliary heads (module.py:257-260, network.py:41) + ConvTranspose1d (:278-283)
   const int Tout = (L - 1) * stride + K;
   SEPR_TRY(launch_decoder(o2, nS, S, L, N, K, stride, w->wdec, wav, Tout, unique ? idx : nullptr, Tsrc, enc, st));
   return SEPR_OK;
+}
+
+extern "C" int sepr_outlayer_basis_fwd(const float* x, int nS, int Tsrc, int L, int F, int N, const sepr_out_w* w, float* o2, void* ws,
+                                       size_t ws_bytes, sepr_stream_t stream) {
+  if (!x || !w || !o2 || nS <= 0 || Tsrc <= 0 || L < Tsrc || F % 32 != 0 || N % 4 != 0) return SEPR_EINVAL;
+  const long long Mp = (long long)nS * Tsrc;
+  if (Mp > 0x7fffffffLL / 8) return SEPR_EINVAL;
+  Arena ar(ws, ws_bytes);
+  float* o1 = ar.f32(2LL * F * Mp);
+  if (!ar.ok()) return SEPR_EWORKSPACE;
+  return outlayer_basis(x, nS, Tsrc, L, nullptr, true, F, N, w, o1, o2, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int sepr_aux_decoder_fwd(int NH, const float* const* o2, const int* const* idx, const float* const* wdec, float* const* wav,
+                                    const int* Tsrc, const float* enc, int B, int S, int L, int N, int K, int stride,
+                                    sepr_stream_t stream) {
+  if (NH < 1 || NH > AUX_DEC_MAX_HEADS || !o2 || !idx || !wdec || !wav || !Tsrc || !enc) return SEPR_EINVAL;
+  AuxDecoderArgs a = {};
+  for (int h = 0; h < NH; ++h) {
+    if (!o2[h] || !idx[h] || !wdec[h] || !wav[h] || Tsrc[h] <= 0 || Tsrc[h] > L) return SEPR_EINVAL;
+    a.o2[h] = o2[h]; a.idx[h] = idx[h]; a.wdec[h] = wdec[h]; a.wav[h] = wav[h]; a.Tsrc[h] = Tsrc[h];
+  }
+  return launch_aux_decoder(a, NH, B, S, L, N, K, stride, enc, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int sepr_groupnorm_stats(const float* x, int n, long long count, float eps, float* stats, void* ws, size_t ws_bytes,

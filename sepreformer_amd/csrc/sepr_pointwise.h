@@ -44,6 +44,19 @@ int launch_encoder(const float* wav, int B, int T, int L, const float* w, int N,
 int launch_decoder(const float* O2, int nS, int S, int L, int N, int K, int stride, const float* wdec, float* wav,
                    int Tout, const int* idx, int Tsrc, const float* enc, hipStream_t s);
 
+// the masked decoders of up to AUX_DEC_MAX_HEADS auxiliary heads in one launch, each encoder frame read once: head h gathers
+// O2_h [B*S, Tsrc_h, N] through idx_h [L], multiplies ReLU(.) by enc [B, L, N] and decodes with wdec_h [K, N] into wav_h [S, B, Tout];
+// bit-identical to launch_decoder per head (S in {2, 3}, K = 16, N % 64 == 0)
+constexpr int AUX_DEC_MAX_HEADS = 4;
+struct AuxDecoderArgs {
+  const float* o2[AUX_DEC_MAX_HEADS];
+  const int* idx[AUX_DEC_MAX_HEADS];
+  const float* wdec[AUX_DEC_MAX_HEADS];
+  float* wav[AUX_DEC_MAX_HEADS];
+  int Tsrc[AUX_DEC_MAX_HEADS];
+};
+int launch_aux_decoder(const AuxDecoderArgs& a, int NH, int B, int S, int L, int N, int K, int stride, const float* enc, hipStream_t s);
+
 // EGA attention with relative-position bias.  QKV [n,Tp,3F] -> O [n,Tp,F]
 // pe_planes (optional, x3 only): pe_k pre-split into bf16 planes [2: hi, lo][2*maxlen][F/H] (sepr_ega_w.pe_k_planes)
 int launch_relattn(const float* QKV, float* O, int n, int Tp, int F, int H, const float* pe_k, int maxlen, int x3,

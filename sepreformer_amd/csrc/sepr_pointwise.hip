@@ -935,4 +935,127 @@ int launch_decoder(const float* O2, int nS, int S, int L, int N, int K, int stri
   return SEPR_OK;
 }
 
+// The auxiliary heads of one forward in ONE launch.  Every head multiplies its mask by the SAME encoder frames, so decoder_kernel's
+// [B, L, N] encoder read - once per head and speaker - is the bulk of the four launches' traffic.  Here a workgroup owns decoder_kernel's
+// 64-row tile of one UTTERANCE: a K trip loads the tile's encoder fragments once and uses them for every head h < NH and speaker
+// s < S; a head's tap fragments are loaded once per trip and shared by its speakers; only the O2_h source rows (a few per wave,
+// L1/L2) are gathered per pair.  Every (head, speaker) pair has its own accumulator pair and sees decoder_kernel's operand sequence
+// (channels ascending, the four products of a step alternating d0 / d1, d0 + d1 at the end), and the overlap-add is decoder_kernel's,
+// so the waveforms are bit-identical to NH decoder_kernel launches.  (Pointers that arrive inside a by-value struct are generic to hipcc,
+// which would make every fragment load a flat_load: ldg4 states the global address space.)  Registers: 8 * NH * S accumulators (64 at 4 x 2) + one trip's fragments;
+// for S = 2 the bound of 3 waves per SIMD keeps hipcc from hoisting every load of a trip (200 VGPRs + 64 AGPRs unbounded, 148 registers with it, no spill; S = 3 spills
+// under that bound and is built for 2).
+__device__ __forceinline__ float4 ldg4(const float* p) {
+  const f32x4 v = *(const f32x4 __attribute__((address_space(1)))*)p;
+  return make_float4(v[0], v[1], v[2], v[3]);
+}
+
+template <int S>
+__global__ __launch_bounds__(TPB, S == 2 ? 3 : 2) void aux_decoder_kernel(AuxDecoderArgs a, int NH, int B, int L, int N, int stride, int Tout,
+                                                         const float* __restrict__ enc) {
+  constexpr int K = 16;
+  __shared__ __attribute__((aligned(16))) float Ds[AUX_DEC_MAX_HEADS * S * DEC_ROWS * K];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int fi = lane & 15, fg = lane >> 4;
+  const int hb = (K - 1) / stride;
+  const int b = blockIdx.y, l0 = blockIdx.x * DEC_FT;
+  const int l = l0 - hb + 16 * w + fi;
+  const bool valid = (l >= 0 && l < L);
+  const int lc = valid ? l : 0;
+  const float* erow = enc + ((long long)b * L + lc) * N + 4 * fg;
+  const float* xrow[AUX_DEC_MAX_HEADS];          // speaker 0's source row of this lane's frame; speaker s is Tsrc * N further
+  const float* wrow[AUX_DEC_MAX_HEADS];          // tap fi
+  f32x4 d0[AUX_DEC_MAX_HEADS][S], d1[AUX_DEC_MAX_HEADS][S];
+#pragma unroll
+  for (int h = 0; h < AUX_DEC_MAX_HEADS; ++h) {
+    xrow[h] = wrow[h] = nullptr;
+    if (h < NH) {
+      xrow[h] = a.o2[h] + ((long long)b * S * a.Tsrc[h] + a.idx[h][lc]) * N + 4 * fg;
+      wrow[h] = a.wdec[h] + (long long)fi * N + 4 * fg;
+    }
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+      d0[h][s] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      d1[h][s] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+  }
+  const int steps = N / 16;
+#pragma unroll 1
+  for (int cb = 0; cb < steps; cb += 4) {
+    float4 e[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) e[u] = ld4(erow + 16 * (cb + u));
+#pragma unroll
+    for (int h = 0; h < AUX_DEC_MAX_HEADS; ++h) {
+      if (h < NH) {
+        float4 wv[4], x[S][4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          wv[u] = ldg4(wrow[h] + 16 * (cb + u));
+#pragma unroll
+          for (int s = 0; s < S; ++s) x[s][u] = ldg4(xrow[h] + (long long)s * a.Tsrc[h] * N + 16 * (cb + u));
+        }
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            float4 m = make_float4(fmaxf(x[s][u].x, 0.f) * e[u].x, fmaxf(x[s][u].y, 0.f) * e[u].y, fmaxf(x[s][u].z, 0.f) * e[u].z,
+                                   fmaxf(x[s][u].w, 0.f) * e[u].w);
+            if (!valid) m = zero4();
+            d0[h][s] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[u].x, m.x, d0[h][s], 0, 0, 0);
+            d1[h][s] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[u].y, m.y, d1[h][s], 0, 0, 0);
+            d0[h][s] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[u].z, m.z, d0[h][s], 0, 0, 0);
+            d1[h][s] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[u].w, m.w, d1[h][s], 0, 0, 0);
+          }
+        }
+      }
+    }
+  }
+  // lane holds D_{h,s}[frame = 16w + fi][tap = 4fg + r]
+#pragma unroll
+  for (int h = 0; h < AUX_DEC_MAX_HEADS; ++h) {
+    if (h < NH) {
+#pragma unroll
+      for (int s = 0; s < S; ++s) {
+        const f32x4 d = d0[h][s] + d1[h][s];
+        st4(Ds + ((h * S + s) * DEC_ROWS + 16 * w + fi) * K + 4 * fg, make_float4(d[0], d[1], d[2], d[3]));
+      }
+    }
+  }
+  __syncthreads();
+  for (int p = 0; p < NH * S; ++p) {
+    const int h = p / S, s = p - h * S;
+    const float* Dp = Ds + p * DEC_ROWS * K;
+    float* dst = a.wav[h] + ((long long)s * B + b) * Tout;
+    for (int tl = tid; tl < DEC_FT * stride; tl += TPB) {
+      const long long tau = (long long)l0 * stride + tl;
+      if (tau >= Tout) continue;
+      const int lr = tl / stride, ph = tl - lr * stride;
+      float y = 0.f;
+      for (int j = 0; j <= hb; ++j) {
+        const int k = ph + j * stride;
+        if (k < K) y += Dp[(lr - j + hb) * K + k];
+      }
+      dst[tau] = y;
+    }
+  }
+}
+
+int launch_aux_decoder(const AuxDecoderArgs& a, int NH, int B, int S, int L, int N, int K, int stride, const float* enc, hipStream_t s) {
+  if (NH < 1 || NH > AUX_DEC_MAX_HEADS || B <= 0 || L <= 0 || !enc) return SEPR_EINVAL;
+  if (K != 16 || stride < 4 || stride > 16 || N <= 0 || N > 4096 || N % 64 != 0 || (S != 2 && S != 3)) return SEPR_EINVAL;
+  if ((K - 1) / stride > DEC_HB || B > 65535) return SEPR_EINVAL;
+  for (int h = 0; h < NH; ++h)
+    if (!a.o2[h] || !a.idx[h] || !a.wdec[h] || !a.wav[h] || a.Tsrc[h] <= 0) return SEPR_EINVAL;
+  const int hb = (K - 1) / stride;
+  const int tiles = (L + hb + DEC_FT - 1) / DEC_FT;
+  const int Tout = (L - 1) * stride + K;
+  if (S == 2)
+    hipLaunchKernelGGL((aux_decoder_kernel<2>), dim3(tiles, B), dim3(TPB), 0, s, a, NH, B, L, N, stride, Tout, enc);
+  else
+    hipLaunchKernelGGL((aux_decoder_kernel<3>), dim3(tiles, B), dim3(TPB), 0, s, a, NH, B, L, N, stride, Tout, enc);
+  SEPR_CHECK_LAUNCH("aux_decoder_kernel");
+  return SEPR_OK;
+}
+
 }  // namespace sepr

@@ -45,11 +45,20 @@ class SeparatorEngine:
         self.lib = L.load()
         self._ws: Optional[torch.Tensor] = None
         self._idx_cache: Dict[Tuple[int, int], torch.Tensor] = {}
+        self._aux_args: Dict[tuple, tuple] = {}
         self._graphs: Dict[tuple, tuple] = {}
         # the speaker splits of the skip connections and the auxiliary heads depend on nothing downstream of their
         # input, so they are enqueued on a side stream and fill the CUs that the small launches of the deeper
         # stages leave idle (SEPR_OVERLAP=0: everything on one stream)
         self.overlap = os.environ.get("SEPR_OVERLAP", "1") != "0"
+        # SEPR_AUX_MERGE: the auxiliary heads enqueue only their basis projections where the head used to be enqueued, and ONE launch after
+        # the last of them decodes all heads, reading the encoder output once instead of once per head and speaker (sepr_aux_decoder_fwd;
+        # bit-identical).  Unset = auto: where the merged grid fills the device (_aux_merge_pays); 1 = wherever the kernel takes the shape;
+        # 0 = one sepr_outlayer_decoder_fwd per head.
+        env = os.environ.get("SEPR_AUX_MERGE", "auto")
+        self.aux_merge = env != "0"
+        self._aux_merge_auto = env not in ("0", "1")
+        self._cus = torch.cuda.get_device_properties(device).multi_processor_count
         self._side: Optional[torch.cuda.Stream] = None
         self._ws2: Optional[torch.Tensor] = None
         self._held: list = []
@@ -227,6 +236,43 @@ class SeparatorEngine:
             C.byref(w), wav.data_ptr(), *(wsargs or self._wsargs), st or self._st), "sepr_outlayer_decoder_fwd")
         return wav
 
+    def head_basis(self, x, w, nS, Tsrc, L_, wsargs=None, st=None):
+        """The two OutputLayer projections of an auxiliary head on its source frames -> o2 ``[nS * Tsrc, N]``."""
+        c = self.cfg
+        o2 = self._new(nS * Tsrc, c.enc_channels)
+        L.check(self.lib.sepr_outlayer_basis_fwd(x.data_ptr(), nS, Tsrc, L_, c.feat, c.enc_channels, C.byref(w), o2.data_ptr(),
+                                                 *(wsargs or self._wsargs), st or self._st), "sepr_outlayer_basis_fwd")
+        return o2
+
+    def aux_decode(self, o2s, Tsrcs, L_, enc, B, st=None):
+        """One launch: every auxiliary head's mask, encoder product and decoder -> list of wav ``[S, B, Tout]``."""
+        c, NH = self.cfg, len(o2s)
+        Tout = (L_ - 1) * c.enc_stride + c.enc_kernel
+        wav = self._new(NH, c.num_spks, B, Tout)                       # one allocation; the heads are its slices
+        ptrs = lambda vals: (C.c_void_p * NH)(*vals)                  # noqa: E731
+        key = (L_, tuple(Tsrcs))
+        fixed = self._aux_args.get(key)                               # the per-shape argument arrays: built once (host time of a batch-1 forward)
+        if fixed is None:
+            fixed = self._aux_args[key] = (ptrs(self._idx(T_, L_).data_ptr() for T_ in Tsrcs), ptrs(self.pk.out_aux[i].wdec for i in range(NH)),
+                                           (C.c_int * NH)(*Tsrcs))
+        step = wav.stride(0) * wav.element_size()
+        L.check(self.lib.sepr_aux_decoder_fwd(
+            NH, ptrs(t.data_ptr() for t in o2s), fixed[0], fixed[1], ptrs(wav.data_ptr() + h * step for h in range(NH)), fixed[2],
+            enc.data_ptr(), B, c.num_spks, L_, c.enc_channels, c.enc_kernel, c.enc_stride, st or self._st), "sepr_aux_decoder_fwd")
+        return list(wav.unbind(0))
+
+    def _aux_merge_ok(self, L_, Lp):
+        """The shapes sepr_aux_decoder_fwd takes (anything else: one sepr_outlayer_decoder_fwd per head)."""
+        c = self.cfg
+        return (self.aux_merge and c.num_stages <= 4 and c.num_spks in (2, 3) and c.enc_kernel == 16 and 4 <= c.enc_stride <= 16
+                and c.enc_channels % 64 == 0 and Lp // 2 <= L_)
+
+    def _aux_merge_pays(self, B, L_):
+        """Auto mode: a merged workgroup walks all NH * S pairs of its tile one after the other, where the per-head launches spread them
+        over NH * S times as many workgroups.  With fewer tiles than CUs that is a longer chain on an emptier device (batch 1 x 4 s: 132
+        workgroups on 256 CUs, measured 0.02 ms slower eager, equal graphed), so small forwards keep the per-head launches."""
+        return B * ((L_ + 3 + 60) // 61) >= self._cus
+
     # ---- two half-batch pipelines ---------------------------------------------------------------------
     @torch.no_grad()
     def forward_split(self, x: torch.Tensor, with_aux: bool = True, parts: int = 2):
@@ -374,8 +420,16 @@ class SeparatorEngine:
         # temporal expanding part                                     (module.py:207-215)
         nS = B * S
         aux: List[torch.Tensor] = []
+        merge = with_aux and self._aux_merge_ok(L_, Lp) and (not self._aux_merge_auto or self._aux_merge_pays(B, L_))
+        o2s: List[torch.Tensor] = []
+        o2T: List[int] = []
         for i in range(R):
-            if with_aux:                                              # auxiliary head of this stage's input (model.py:47-52)
+            if merge:                                                 # this head's basis rows now, all decoders in one launch after the last
+                o2s.append(self._aside(lambda ws, sh, x_=cur, i_=i, T_=Tc: self.head_basis(x_, pk.out_aux[i_], nS, T_, L_, ws, sh), cur))
+                o2T.append(Tc)
+                if i == R - 1:
+                    aux = self._aside(lambda ws, sh: self.aux_decode(o2s, o2T, L_, enc, B, sh), enc, *o2s)
+            elif with_aux:                                            # auxiliary head of this stage's input (model.py:47-52)
                 aux.append(self._aside(lambda ws, sh, x_=cur, i_=i, T_=Tc: self.head(x_, pk.out_aux[i_], nS, T_, L_, self._idx(T_, L_), enc, B, ws, sh), cur, enc))
             skip, Ts = skips[R - 1 - i]
             if Ts != 2 * Tc:
