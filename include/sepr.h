@@ -472,7 +472,25 @@ int sepr_resample_fwd(const float* x, const long long* in_offset, float* y, cons
  * everything sepr_dynmix_fwd refuses - all before any HIP call.  A target term that equals mixture term s bit for bit, converter index included,
  * is computed once.  The kernel clamps the converter index (negative = none, above NC - 1 = NC - 1), the utterance index and every read
  * position: a bad table yields wrong samples but never a read outside the corpus.  No workspace, no host synchronisation or allocation
- * (capturable: the pointers and the converter descriptions are frozen, the table contents are read at replay). */
+ * (capturable: the pointers and the converter descriptions are frozen, the table contents are read at replay).
+ *
+ * sepr_dynmix_reverb_fwd: sepr_dynmix_fwd with reverberation by convolution.  The RIR bank is R >= 1 float32 impulse
+ * responses h_r of len_r samples, 1 <= len_r <= 16384, back to back in rir [rir_total] (DEVICE, 4-byte aligned) with rir_off [R + 1] int64 (DEVICE)
+ * their cumulative sample counts.  term_rir [B (M + S)] int32 (DEVICE): -1 = the term is the stored utterance, with sepr_dynmix_fwd's loads and
+ * bits; r in 0 .. R - 1 = the term is the utterance convolved with the first term_taps [B (M + S)] (int32, DEVICE, 1 <= taps <= len_r) samples of
+ * h_r:
+ *   y[t] = float32(sum_{j = 0 .. taps - 1} double(h_r[j]) * double(x[term_start + t - j])),   x = 0 outside [0, T) of THAT utterance,
+ * the products exact in float64, added in the order j = 0 .. taps - 1 as fma(h, x, acc) from acc = 0.0, one rounding to float32; the term's
+ * value is (y[t] * term_norm) * term_gain, the two separately rounded float32 multiplies.  So a term is "convolve the whole utterance, truncate
+ * to its stored length, crop" bit for bit - the tail of the samples before the crop is in the crop, the reverberant utterance keeps the stored
+ * length (the caller guarantees term_start + n[b] <= T as for a plain term) - and h = [1.0] gives the plain term's bits.  The convolution runs
+ * inside the one launch: per workgroup of 2048 outputs the taps are walked in ascending chunks of 1024, each staging 3071 input samples in LDS,
+ * the float64 sums staying in registers, so no RIR length changes the LDS plan.  A target term that equals mixture term s in all six fields is
+ * computed once.  The kernel clamps the RIR index (negative = none, above R - 1 = R - 1), taps to 1 .. min(len_r, 16384), every RIR read into
+ * [0, rir_total), and the utterance index, the start and every corpus read as sepr_dynmix_fwd does: a bad table yields wrong samples but never a
+ * read outside the buffers.  SEPR_EINVAL before any HIP call for everything sepr_dynmix_fwd refuses, a null term_rir, term_taps, rir or
+ * rir_off, R < 1, rir_total < 1 or a misaligned rir.  No workspace, no host synchronisation or allocation (capturable: the pointers are
+ * frozen, the table contents - RIR indices and tap counts included - are read at replay). */
 size_t sepr_corpus_energy_workspace(int N);
 int sepr_corpus_energy(const short* buf16, long long total16, const float* buf32, long long total32, const long long* offsets, int N16, int N,
                        long long* ss16, double* ss32, void* ws, size_t ws_bytes, sepr_stream_t stream);
@@ -483,6 +501,10 @@ int sepr_dynmix_speed_fwd(const short* buf16, long long total16, const float* bu
                           const int* term_utt, const int* term_start, const float* term_norm, const float* term_gain, const int* term_conv,
                           const int* n, int B, int M, int S, int Tmax, float* mix, float* const* src, const float* const* conv_taps,
                           const int* conv_L, const int* conv_M, const int* conv_K, int NC, sepr_stream_t stream);
+int sepr_dynmix_reverb_fwd(const short* buf16, long long total16, const float* buf32, long long total32, const long long* offsets, int N16, int N,
+                           const int* term_utt, const int* term_start, const float* term_norm, const float* term_gain, const int* term_rir,
+                           const int* term_taps, const int* n, int B, int M, int S, int Tmax, float* mix, float* const* src, const float* rir,
+                           long long rir_total, const long long* rir_off, int R, sepr_stream_t stream);
 
 /* ================================================================================================================= */
 /* Training path: train-mode forward twins that keep what the backward needs, and the       */

@@ -19,6 +19,13 @@
 //                        reads and the tap columns are consecutive), written to an LDS tile of floats and read back eight per
 //                        thread into the plain kernel's scaling, summing and storing code.  Terms with term_conv < 0 take the
 //                        plain kernel's loads.
+//   dynmix_reverb_kernel the same batch with reverberation: a term whose term_rir is an index into the RIR bank
+//                        is the stored utterance convolved with the first term_taps samples of that impulse response, exact float64
+//                        products summed in the order j = 0 .. taps - 1, one rounding.  The speed kernel's geometry (2048 outputs of
+//                        one example per workgroup, one output per lane, transposed through the float tile), but a long FIR filter:
+//                        the taps are walked in ascending chunks of 1024, each chunk staging its 3071 input samples as doubles and
+//                        its taps as doubles (in the float tile, which is idle until the end), the float64 accumulators staying in
+//                        registers across the chunks - so the LDS plan does not depend on the length of the impulse response.
 // Nothing here depends on the launch order of workgroups: results are bit-identical from run to run.
 #include "sepr_common.h"
 
@@ -301,6 +308,159 @@ __global__ __launch_bounds__(DM_TPB) void dynmix_speed_kernel(DmCorpus c, DsConv
   }
 }
 
+constexpr int DR_CHUNK = 1024;             // taps per chunk: the chunk's span DS_TILE + DR_CHUNK - 1 = 3071 doubles fits xs [DS_SPAN]
+constexpr int DR_MAX_TAPS = 16384;
+static_assert(DS_TILE + DR_CHUNK - 1 <= DS_SPAN, "a chunk's input span must fit the staged doubles");
+static_assert(DR_CHUNK * sizeof(double) == DS_TILE * sizeof(float), "the chunk's taps as doubles share the float tile");
+
+struct DrBank {
+  const float* h;                          // the R impulse responses back to back
+  const long long* off;                    // [R + 1] cumulative sample counts
+  long long total;
+  int R;
+};
+
+// outputs t = tile0 .. tile0 + DS_TILE - 1 of term (utt, start) convolved with the first `taps` samples of impulse response r, as
+//   y[t] = float32(sum_{j < taps} double(h[j]) * double(x[start + t - j])),   x = 0 outside [0, T) of that utterance,
+// left in v[0 .. 7] for t = t0 .. t0 + 7 of thread tid (t0 = tile0 + 8 tid).  Workgroup-uniform arguments; every thread of the workgroup
+// passes every barrier.  Thread tid owns the outputs tid + 256 i: consecutive lanes read consecutive doubles of xs, and the tap is one
+// broadcast read.  hs and ys are the same 8 KB: the taps of a chunk as doubles while the chunks run, the tile of floats at the end.
+// The tables are not trusted: r, taps, the utterance and every read position are clamped, so no read leaves the bank or the corpus.
+__device__ __forceinline__ void reverb_tile(const DmCorpus& c, const DrBank& bk, int r, int taps, int utt, int start, int tile0, int n,
+                                            double* __restrict__ xs, double* __restrict__ hs, float x8[8]) {
+  const int tid = threadIdx.x;
+  const int u = utt < 0 ? 0 : (utt >= c.N ? c.N - 1 : utt);
+  const long long o0 = c.off[u], T = c.off[u + 1] - o0;
+  const bool is16 = u < c.N16;
+  const long long total = is16 ? c.total16 : c.total32;
+  const long long e0 = o0 - (is16 ? 0 : c.off[c.N16]);
+  const long long st = clampll(start, 0, T > 0 ? T : 0);
+  const int rr = r >= bk.R ? bk.R - 1 : r;                                   // r >= 0 here
+  const long long h0 = clampll(bk.off[rr], 0, bk.total - 1);
+  const long long hl = clampll(bk.off[rr + 1] - h0, 1, bk.total - h0 < DR_MAX_TAPS ? bk.total - h0 : DR_MAX_TAPS);
+  const int K = taps < 1 ? 1 : (taps > (int)hl ? (int)hl : taps);            // h0 + K <= total: every tap read is inside the bank
+  const float* __restrict__ hp = bk.h + h0;
+  const int left = n - tile0;                                                // > 0: the caller returned for tiles past n
+  double acc[DM_PER];
+#pragma unroll
+  for (int i = 0; i < DM_PER; ++i) acc[i] = 0.0;
+  const double* xp = xs + tid + (DR_CHUNK - 1);
+  for (int k0 = 0; k0 < K; k0 += DR_CHUNK) {
+    const long long g0 = st + tile0 - k0 - (DR_CHUNK - 1);                  // the utterance index of xs[0]
+    // a chunk whose whole span lies before the utterance's first sample adds fma(h, 0, acc) = acc (acc is never -0): it and every
+    // later chunk - their spans lie further back still - are skipped without changing a bit
+    if (g0 + (DS_TILE + DR_CHUNK - 2) < 0) break;
+    const int kc = K - k0 < DR_CHUNK ? K - k0 : DR_CHUNK;
+    __syncthreads();                                                         // the last readers of xs / hs (or of the float tile) are done
+    for (int i = tid; i < DS_TILE + DR_CHUNK - 1; i += DM_TPB) {
+      const long long g = g0 + i;
+      double v = 0.0;
+      if (g >= 0 && g < T) {
+        const long long e = clampll(e0 + g, 0, total - 1);
+        v = is16 ? (double)((float)c.buf16[e] * 3.0517578125e-05f) : (double)c.buf32[e];
+      }
+      xs[i] = v;
+    }
+    for (int i = tid; i < kc; i += DM_TPB) hs[i] = (double)hp[k0 + i];
+    __syncthreads();
+    if (tid < left) {                                                        // (per wave: whole waves past n skip the loop)
+#pragma unroll 4
+      for (int j = 0; j < kc; ++j) {
+        const double hj = hs[j];
+#pragma unroll
+        for (int i = 0; i < DM_PER; ++i) acc[i] = fma(hj, xp[i * DM_TPB - j], acc[i]);
+      }
+    }
+  }
+  __syncthreads();                                                           // hs has been read: it becomes the float tile
+  float* ys = reinterpret_cast<float*>(hs);
+#pragma unroll
+  for (int i = 0; i < DM_PER; ++i) ys[tid + i * DM_TPB] = (float)acc[i];
+  __syncthreads();
+  const float4 lo = *reinterpret_cast<const float4*>(ys + tid * DM_PER);
+  const float4 hi = *reinterpret_cast<const float4*>(ys + tid * DM_PER + 4);
+  x8[0] = lo.x, x8[1] = lo.y, x8[2] = lo.z, x8[3] = lo.w, x8[4] = hi.x, x8[5] = hi.y, x8[6] = hi.z, x8[7] = hi.w;
+}
+
+// term j (flattened) of the example on samples t0 .. t0 + 7: reverberated when it names an impulse response, else the plain kernel's term_value
+__device__ __forceinline__ void reverb_term_value(const DmCorpus& c, const DrBank& bk, int r, int taps, int utt, int start, float norm, float gain,
+                                                  int tile0, int t0, int n, double* xs, double* hs, float v[8]) {
+#pragma clang fp contract(off)
+  if (r < 0) {
+    term_value(c, utt, start, norm, gain, t0 < n ? t0 : 0, v);
+    return;
+  }
+  float x[8];
+  reverb_tile(c, bk, r, taps, utt, start, tile0, n, xs, hs, x);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const float a = x[i] * norm;
+    v[i] = a * gain;
+  }
+}
+
+template <int S>
+__global__ __launch_bounds__(DM_TPB) void dynmix_reverb_kernel(DmCorpus c, DrBank bk, const int* __restrict__ term_utt,
+                                                               const int* __restrict__ term_start, const float* __restrict__ term_norm,
+                                                               const float* __restrict__ term_gain, const int* __restrict__ term_rir,
+                                                               const int* __restrict__ term_taps, const int* __restrict__ nlen, int M, int Tmax,
+                                                               float* __restrict__ mix, DmRows src) {
+#pragma clang fp contract(off)
+  __shared__ double xs[DS_SPAN];
+  __shared__ __attribute__((aligned(16))) double hs[DR_CHUNK];     // a chunk's taps; at the end of a term the tile of DS_TILE floats
+  const int b = blockIdx.y;
+  const int tile0 = blockIdx.x * DS_TILE;
+  const int t0 = tile0 + threadIdx.x * DM_PER;
+  const bool live = t0 < Tmax;                                     // no early return for a thread: the convolutions hold barriers
+  const bool second = t0 + 4 < Tmax;
+  int n = __builtin_amdgcn_readfirstlane(nlen[b]);
+  n = n < 0 ? 0 : (n > Tmax ? Tmax : n);
+  const long long row = (long long)b * Tmax + t0;
+  float acc[8], keep[S][8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) acc[i] = 0.f;
+  if (tile0 >= n) {                                                // the whole tile is the zero fill of pad_sequence (workgroup-uniform)
+    if (live) {
+      store8(mix + row, acc, t0, n, second);
+#pragma unroll
+      for (int s = 0; s < S; ++s) store8(src.p[s] + row, acc, t0, n, second);
+    }
+    return;
+  }
+  const int NT = M + S, j0 = b * NT;
+#pragma unroll
+  for (int m = 0; m < S + 1; ++m) {
+    if (m < M) {
+      float v[8];
+      const int r = __builtin_amdgcn_readfirstlane(term_rir[j0 + m]), taps = __builtin_amdgcn_readfirstlane(term_taps[j0 + m]);
+      const int utt = __builtin_amdgcn_readfirstlane(term_utt[j0 + m]), start = __builtin_amdgcn_readfirstlane(term_start[j0 + m]);
+      reverb_term_value(c, bk, r, taps, utt, start, term_norm[j0 + m], term_gain[j0 + m], tile0, t0, n, xs, hs, v);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) acc[i] = acc[i] + v[i];
+      if (m < S) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) keep[m][i] = v[i];
+      }
+    }
+  }
+  if (live) store8(mix + row, acc, t0, n, second);
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    const int jm = j0 + s, jt = j0 + M + s;
+    const int r = __builtin_amdgcn_readfirstlane(term_rir[jt]), taps = __builtin_amdgcn_readfirstlane(term_taps[jt]);
+    const int utt = __builtin_amdgcn_readfirstlane(term_utt[jt]), start = __builtin_amdgcn_readfirstlane(term_start[jt]);
+    const bool same = utt == term_utt[jm] && start == term_start[jm] && __float_as_uint(term_norm[jt]) == __float_as_uint(term_norm[jm]) &&
+                      __float_as_uint(term_gain[jt]) == __float_as_uint(term_gain[jm]) && r == term_rir[jm] && taps == term_taps[jm];
+    if (__builtin_amdgcn_readfirstlane(same)) {                    // all six fields: the target IS the mixture term - computed once
+      if (live) store8(src.p[s] + row, keep[s], t0, n, second);
+    } else {
+      float v[8];
+      reverb_term_value(c, bk, r, taps, utt, start, term_norm[jt], term_gain[jt], tile0, t0, n, xs, hs, v);
+      if (live) store8(src.p[s] + row, v, t0, n, second);
+    }
+  }
+}
+
 // partial sum of squares of utterance u = blockIdx.x over the chunks p, p + EN_PARTS, ... (p = blockIdx.y) of EN_TPB samples
 __global__ __launch_bounds__(EN_TPB) void energy_part_kernel(DmCorpus c, long long* __restrict__ part) {
 #pragma clang fp contract(off)
@@ -462,5 +622,30 @@ extern "C" int sepr_dynmix_speed_fwd(const short* buf16, long long total16, cons
     hipLaunchKernelGGL((dynmix_speed_kernel<3>), grid, dim3(DM_TPB), 0, st, c, cv, term_utt, term_start, term_norm, term_gain, term_conv, n, M,
                        Tmax, mix, rows);
   SEPR_CHECK_LAUNCH("dynmix speed kernel");
+  return SEPR_OK;
+}
+
+extern "C" int sepr_dynmix_reverb_fwd(const short* buf16, long long total16, const float* buf32, long long total32, const long long* offsets,
+                                      int N16, int N, const int* term_utt, const int* term_start, const float* term_norm,
+                                      const float* term_gain, const int* term_rir, const int* term_taps, const int* n, int B, int M, int S,
+                                      int Tmax, float* mix, float* const* src, const float* rir, long long rir_total, const long long* rir_off,
+                                      int R, sepr_stream_t stream) {
+  using namespace sepr;
+  DmRows rows = {{nullptr, nullptr, nullptr}};
+  if (dynmix_args_bad(buf16, total16, buf32, total32, offsets, N16, N, term_utt, term_start, term_norm, term_gain, n, B, M, S, Tmax, mix, src, &rows))
+    return SEPR_EINVAL;
+  if (!term_rir || !term_taps || !rir || !rir_off || R < 1 || rir_total < 1) return SEPR_EINVAL;
+  if (reinterpret_cast<uintptr_t>(rir) % 4 != 0) return SEPR_EINVAL;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const DmCorpus c = {buf16, buf32, offsets, total16, total32, N16, N};
+  const DrBank bk = {rir, rir_off, rir_total, R};
+  const dim3 grid((unsigned)cdiv(Tmax, DS_TILE), (unsigned)B);
+  if (S == 2)
+    hipLaunchKernelGGL((dynmix_reverb_kernel<2>), grid, dim3(DM_TPB), 0, st, c, bk, term_utt, term_start, term_norm, term_gain, term_rir, term_taps,
+                       n, M, Tmax, mix, rows);
+  else
+    hipLaunchKernelGGL((dynmix_reverb_kernel<3>), grid, dim3(DM_TPB), 0, st, c, bk, term_utt, term_start, term_norm, term_gain, term_rir, term_taps,
+                       n, M, Tmax, mix, rows);
+  SEPR_CHECK_LAUNCH("dynmix reverb kernel");
   return SEPR_OK;
 }

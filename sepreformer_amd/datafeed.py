@@ -22,6 +22,10 @@ Speed perturbation: ``plan_wsj0`` / ``plan_wham`` / ``p
 ``range(95, 106)``) and draw one per source; a perturbed term is the stored utterance passed through ``resample.plan(p, 100)``, converted
 inside the mixing launch (``sepr_dynmix_speed_fwd``) on the cropped span only.
 
+Reverberation: the same three planners take ``rirs=`` (a ``reverb.RirBank``) and draw one impulse response per
+source; a reverberant term is the stored utterance convolved with the first ``taps`` samples of that response inside the mixing launch
+(``sepr_dynmix_reverb_fwd``) - the whole response in the mixture, by default its direct path in the target.
+
 Shuffling: the reference shuffles through ``DataLoader(shuffle=True)`` (torch's generator); this feed takes the epoch's key order
 from the caller (``keys=``), and by default draws a permutation from its own ``random.Random`` before every epoch.
 """
@@ -37,9 +41,12 @@ import torch
 
 from . import lib as L_
 from . import resample as R_
+from .reverb import RirBank
 
-# (utterance index, start sample, norm factor, gain), plus the speed in percent when the planner was given speeds
-Term = Union[Tuple[int, int, np.float32, np.float32], Tuple[int, int, np.float32, np.float32, int]]
+# (utterance index, start sample, norm factor, gain), plus the speed in percent when the planner was given speeds, or plus
+# (100, RIR index or -1, taps) when it was given an RIR bank
+Term = Union[Tuple[int, int, np.float32, np.float32], Tuple[int, int, np.float32, np.float32, int],
+             Tuple[int, int, np.float32, np.float32, int, int, int]]
 MAX_CONVERTERS = 16                                     # converters one sepr_dynmix_speed_fwd call takes
 _ONE = np.float32(1.0)
 
@@ -61,6 +68,8 @@ class BatchPlan(NamedTuple):
     M: int
     S: int
     speed: Optional[np.ndarray] = None      # int32 [B, M + S] percent (100 = as recorded), None: planned without speeds
+    rir: Optional[np.ndarray] = None        # int32 [B, M + S] index into the RIR bank (-1 = none), None: planned without RIRs
+    taps: Optional[np.ndarray] = None       # int32 [B, M + S] leading samples of that RIR the term is convolved with
 
 
 def parse_scp(path: str) -> Dict[str, str]:
@@ -273,7 +282,48 @@ def _draw_speeds(rng: random.Random, speeds: Optional[Sequence[int]], count: int
     return [int(rng.choice(speeds)) for _ in range(count)]
 
 
-def _terms(utts, starts, norms, gains, sp) -> Tuple[Term, ...]:
+def _draw_rirs(rng: random.Random, rirs: Optional[RirBank], speeds, count: int) -> Optional[List[int]]:
+    """One ``rng.randrange(len(rirs))`` per source, in source order; no draw without a bank."""
+    if rirs is None:
+        return None
+    if speeds is not None:
+        raise ValueError("speeds and rirs in one plan are not built: pass one of them")
+    return [rng.randrange(len(rirs)) for _ in range(count)]
+
+
+def _mix_rv(rirs: RirBank, rv: Sequence[int]) -> List[Tuple[int, int]]:
+    """The mixture's (rir, taps) of the sources: the whole impulse response."""
+    return [(r, int(rirs.lengths[r])) for r in rv]
+
+
+def _target_rv(rirs: RirBank, rv: Sequence[int], target: Union[str, int]) -> List[Tuple[int, int]]:
+    """The targets' (rir, taps): ``"direct"`` = the direct path of the same response (``rirs.direct_taps()``), ``"dry"`` = no response,
+    ``"full"`` = the mixture's term, an integer = that many taps, clipped to the response's length."""
+    if target == "direct":
+        return [(r, int(rirs._direct[r])) for r in rv]
+    if target == "dry":
+        return [(-1, 1) for _ in rv]
+    if target == "full":
+        return _mix_rv(rirs, rv)
+    if isinstance(target, (int, np.integer)) and not isinstance(target, bool) and int(target) >= 1:
+        return [(r, min(int(target), int(rirs.lengths[r]))) for r in rv]
+    raise ValueError(f"target = {target!r}: 'direct', 'dry', 'full' or a tap count >= 1")
+
+
+def _same_device(a: Optional[torch.device], b: Optional[torch.device]) -> bool:
+    """``cuda`` and ``cuda:<current>`` name one device."""
+    if a is None or b is None or a.type != b.type:
+        return False
+    idx = lambda d: d.index if d.index is not None else (torch.cuda.current_device() if d.type == "cuda" else 0)      # noqa: E731
+    return idx(a) == idx(b)
+
+
+_NO_RIR = (-1, 1)                                      # a term that is not reverberated inside a plan with RIRs (the noise)
+
+
+def _terms(utts, starts, norms, gains, sp, rv=None) -> Tuple[Term, ...]:
+    if rv is not None:
+        return tuple((u, s, nf, g, 100, r, k) for u, s, nf, g, (r, k) in zip(utts, starts, norms, gains, rv))
     if sp is None:
         return tuple((u, s, nf, g) for u, s, nf, g in zip(utts, starts, norms, gains))
     return tuple((u, s, nf, g, p) for u, s, nf, g, p in zip(utts, starts, norms, gains, sp))
@@ -281,10 +331,12 @@ def _terms(utts, starts, norms, gains, sp) -> Tuple[Term, ...]:
 
 def plan_wsj0(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs: Sequence[str] = ("s1", "s2"),
               accept: Callable[[str, str], bool] = wsj0_distinct_speakers, crop: bool = True,
-              speeds: Optional[Sequence[int]] = None) -> Example:
+              speeds: Optional[Sequence[int]] = None, rirs: Optional[RirBank] = None, target: Union[str, int] = "direct") -> Example:
     """``SepReformer_Large_DM_WSJ0/dataset.py:84-139``.  ``crop=False`` is the reference's "test" partition (no ``max_len`` crop).
     ``speeds``: directly after the draw that orders the two sources, one ``rng.choice(speeds)`` per source; the perturbed lengths
-    replace the stored ones, the norm factors keep the stored utterances' RMS (section 5e-2)."""
+    replace the stored ones, the norm factors keep the stored utterances' RMS (section 5e-2).  ``rirs``: at that same position, one
+    ``rng.randrange(len(rirs))`` per source; the mixture terms take the whole impulse response, the target terms what ``target`` says
+    (``_target_rv``); lengths and norm factors stay the stored utterances' (section 5e-3)."""
     keys = corpus.roles[srcs[0]]
     while True:
         key_random = rng.choice(keys)
@@ -292,6 +344,7 @@ def plan_wsj0(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs: 
             break
     i1, i2 = (0, 1) if rng.random() > 0.5 else (1, 0)
     sp = _draw_speeds(rng, speeds, 2)
+    rv = _draw_rirs(rng, rirs, speeds, 2)
     utts = [corpus.lookup(srcs[i1], key), corpus.lookup(srcs[i2], key_random)]
     ref = corpus.rms[utts[0]]
     norms = [_norm(ref, corpus.rms[u]) for u in utts]
@@ -303,18 +356,22 @@ def plan_wsj0(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs: 
     if crop and n > max_len:
         st = rng.randint(0, n - max_len)
         starts, n = [s + st for s in starts], max_len
+    if rv is not None:
+        return Example(key, n, _terms(utts, starts, norms, gains, None, _mix_rv(rirs, rv)),
+                       _terms(utts, starts, norms, gains, None, _target_rv(rirs, rv, target)))
     terms = _terms(utts, starts, norms, gains, sp)
     return Example(key, n, terms, terms)
 
 
 def plan_wham(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs: Sequence[str] = ("s1", "s2"), noise: str = "noise",
-              speeds: Optional[Sequence[int]] = None) -> Example:
+              speeds: Optional[Sequence[int]] = None, rirs: Optional[RirBank] = None, target: Union[str, int] = "direct") -> Example:
     """``SepReformer_Large_DM_WHAM/dataset.py``: no speaker rule, the noise of ``key`` normalised to the first source with a gain of
     its own from U(-5, 5) dB, everything cropped to ``min(max_len, lengths)`` at independent random indices.  ``speeds``: as in
-    ``plan_wsj0``; the noise is not perturbed."""
+    ``plan_wsj0``; the noise is not perturbed.  ``rirs`` / ``target``: as in ``plan_wsj0``; the noise is not reverberated."""
     key_random = rng.choice(corpus.roles[srcs[0]])
     i1, i2 = (0, 1) if rng.random() > 0.5 else (1, 0)
     sp = _draw_speeds(rng, speeds, 2)
+    rv = _draw_rirs(rng, rirs, speeds, 2)
     utts = [corpus.lookup(srcs[i1], key), corpus.lookup(srcs[i2], key_random)]
     ref = corpus.rms[utts[0]]
     norms = [_norm(ref, corpus.rms[u]) for u in utts]
@@ -329,20 +386,27 @@ def plan_wham(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs: 
     min_len = min([max_len] + lens)
     starts = [rng.randint(0, ln - min_len) for ln in lens]
     n = min_len - min_len % 4
+    if rv is not None:
+        return Example(key, n, _terms(utts, starts, norms, gains, None, _mix_rv(rirs, rv) + [_NO_RIR]),
+                       _terms(utts[:2], starts, norms, gains, None, _target_rv(rirs, rv, target)))
     terms = _terms(utts, starts, norms, gains, sp)
     return Example(key, n, terms, terms[:2])
 
 
 def plan_whamr(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs: Sequence[str] = ("s1", "s2"),
-               reverb: Sequence[str] = ("s1_reverb", "s2_reverb"), noise: str = "noise", speeds: Optional[Sequence[int]] = None) -> Example:
+               reverb: Sequence[str] = ("s1_reverb", "s2_reverb"), noise: str = "noise", speeds: Optional[Sequence[int]] = None,
+               rirs: Optional[RirBank] = None, target: Union[str, int] = "direct") -> Example:
     """``SepReformer_Large_DM_WHAMR/dataset.py:87-154``: the mixture is the two reverberant twins plus the noise (gains U(-3, 3) dB,
     noise U(-6, 3) dB), the targets are the anechoic sources with their twins' norm factor, gain and crop index.  ``speeds``: as in
-    ``plan_wsj0``; a dry source and its reverberant twin share one speed, the noise is not perturbed."""
+    ``plan_wsj0``; a dry source and its reverberant twin share one speed, the noise is not perturbed.  ``rirs`` / ``target``: as in
+    ``plan_wsj0``; the mixture is then the DRY sources reverberated in the launch plus the noise, and the ``reverb`` roles are never
+    looked up - a corpus without pre-rendered twins serves."""
     key_random = rng.choice(corpus.roles[srcs[0]])
     i1, i2 = (0, 1) if rng.random() > 0.5 else (1, 0)
     sp = _draw_speeds(rng, speeds, 2)
+    rv = _draw_rirs(rng, rirs, speeds, 2)
     dry = [corpus.lookup(srcs[i1], key), corpus.lookup(srcs[i2], key_random)]
-    wet = [corpus.lookup(reverb[i1], key), corpus.lookup(reverb[i2], key_random)]
+    wet = dry if rv is not None else [corpus.lookup(reverb[i1], key), corpus.lookup(reverb[i2], key_random)]
     for d, w in zip(dry, wet):
         if corpus.lengths[d] != corpus.lengths[w]:
             raise ValueError(f"{corpus.names[d]} and {corpus.names[w]} differ in length (the reference stacks them)")
@@ -356,18 +420,23 @@ def plan_whamr(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs:
     starts = [rng.randint(0, ln - min_len) for ln in lens]
     nstart = rng.randint(0, int(corpus.lengths[un]) - min_len)
     n = min_len - min_len % 4
+    if rv is not None:
+        return Example(key, n, _terms(dry + [un], starts + [nstart], norms + [nnorm], gains + [ngain], None, _mix_rv(rirs, rv) + [_NO_RIR]),
+                       _terms(dry, starts, norms, gains, None, _target_rv(rirs, rv, target)))
     mix = _terms(wet + [un], starts + [nstart], norms + [nnorm], gains + [ngain], None if sp is None else sp + [100])
     tgt = _terms(dry, starts, norms, gains, sp)
     return Example(key, n, mix, tgt)
 
 
 def plan_direct(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs: Sequence[str] = ("s1", "s2"), mix: str = "mix",
-                crop: bool = True, speeds: Optional[Sequence[int]] = None) -> Example:
+                crop: bool = True, speeds: Optional[Sequence[int]] = None, rirs: Optional[RirBank] = None) -> Example:
     """``_direct_load``: the fixed mixture file and its sources, norm and gain 1, the ``% 4`` truncation and the ``max_len`` crop.
     The mixture is one term; the kernel takes ``M >= S`` terms, so it is followed by terms of gain 0, which add exactly nothing.
-    A fixed mixture cannot be perturbed: ``speeds`` raises."""
+    A fixed mixture cannot be perturbed or reverberated: ``speeds`` and ``rirs`` raise."""
     if speeds is not None:
         raise ValueError("plan_direct loads a fixed mixture file: it takes no speeds")
+    if rirs is not None:
+        raise ValueError("plan_direct loads a fixed mixture file: it takes no rirs")
     um = corpus.lookup(mix, key)
     n = int(corpus.lengths[um])
     n -= n % 4
@@ -379,9 +448,9 @@ def plan_direct(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs
     return Example(key, n, mixt, tgt)
 
 
-def collate_plan(corpus: Corpus, examples: Sequence[Example]) -> BatchPlan:
+def collate_plan(corpus: Corpus, examples: Sequence[Example], rirs: Optional[RirBank] = None) -> BatchPlan:
     """Order the examples by length, longest first (``_collate``'s stable ``sorted(..., reverse=True)``), check every term against its
-    utterance and lay the table out as the kernel reads it."""
+    utterance - and, for a reverberant term, against the bank ``rirs`` - and lay the table out as the kernel reads it."""
     egs = sorted(examples, key=lambda e: e.n, reverse=True)
     M, S = len(egs[0].mix), len(egs[0].tgt)
     if not (2 <= S <= 3 and S <= M <= S + 1):
@@ -390,7 +459,8 @@ def collate_plan(corpus: Corpus, examples: Sequence[Example]) -> BatchPlan:
     utt, start = np.zeros((B, M + S), np.int32), np.zeros((B, M + S), np.int32)
     norm, gain = np.zeros((B, M + S), np.float32), np.zeros((B, M + S), np.float32)
     speed = np.full((B, M + S), 100, np.int32)
-    any_speed = False
+    rir, taps = np.full((B, M + S), -1, np.int32), np.ones((B, M + S), np.int32)
+    any_speed = any_rir = False
     for b, e in enumerate(egs):
         if len(e.mix) != M or len(e.tgt) != S:
             raise ValueError("every example of a batch needs the same number of terms")
@@ -399,15 +469,27 @@ def collate_plan(corpus: Corpus, examples: Sequence[Example]) -> BatchPlan:
         for j, term in enumerate(e.mix + e.tgt):
             u, s, nf, g = term[:4]
             p = int(term[4]) if len(term) > 4 else 100
-            any_speed |= len(term) > 4
+            any_speed |= len(term) == 5 or p != 100
+            if len(term) > 5:
+                any_rir = True
+                r, k = int(term[5]), int(term[6])
+                if rirs is None:
+                    raise ValueError(f"{e.key}: term {j} carries an RIR, collate_plan was given no bank (rirs=)")
+                if not (-1 <= r < len(rirs)) or (r >= 0 and not (1 <= k <= int(rirs.lengths[r]))):
+                    raise ValueError(f"{e.key}: term {j} takes {k} taps of RIR {r}; the bank holds {len(rirs)}"
+                                     + (f", this one {int(rirs.lengths[r])} samples" if 0 <= r < len(rirs) else ""))
+                rir[b, j], taps[b, j] = r, k
             if not (0 <= u < len(corpus)) or p < 1 or s < 0 or s + e.n > perturbed_len(corpus.lengths[u], p):
                 raise ValueError(f"{e.key}: term {j} reads [{s}, {s + e.n}) of utterance {u}" + (f" at {p} % speed" if p != 100 else ""))
             utt[b, j], start[b, j], norm[b, j], gain[b, j], speed[b, j] = u, s, nf, g, p
-    return BatchPlan([e.key for e in egs], np.array([e.n for e in egs], np.int32), utt, start, norm, gain, M, S, speed if any_speed else None)
+    if any_speed and any_rir:
+        raise ValueError("a plan with speeds and RIRs is not built: pass one of them")
+    return BatchPlan([e.key for e in egs], np.array([e.n for e in egs], np.int32), utt, start, norm, gain, M, S, speed if any_speed else None,
+                     rir if any_rir else None, taps if any_rir else None)
 
 
-def _table_words(B: int, NT: int, speeds: bool = False) -> int:
-    return (5 if speeds else 4) * B * NT + B
+def _table_words(B: int, NT: int, speeds: bool = False, rirs: bool = False) -> int:
+    return (4 + (1 if speeds else 0) + (2 if rirs else 0)) * B * NT + B
 
 
 def plan_speeds(plan: BatchPlan) -> List[int]:
@@ -434,9 +516,10 @@ def _converter_args(dev: torch.device, speeds: Sequence[int]):
 
 def mix_batch(corpus: Corpus, plan: BatchPlan, Tmax: Optional[int] = None, mix: Optional[torch.Tensor] = None,
               src: Optional[Sequence[torch.Tensor]] = None, table: Optional[torch.Tensor] = None,
-              speeds: Optional[Sequence[int]] = None):
+              speeds: Optional[Sequence[int]] = None, rirs: Optional[RirBank] = None):
     """One ``sepr_dynmix_fwd`` launch for ``plan`` on the corpus's device (current stream) -> ``(mix [B, Tmax], [src_s [B, Tmax]])``;
-    a plan that carries speeds goes through ``sepr_dynmix_speed_fwd``.  ``table``: an int32 device tensor that already holds the plan in
+    a plan that carries speeds goes through ``sepr_dynmix_speed_fwd``, one that carries RIRs through ``sepr_dynmix_reverb_fwd`` with the
+    bank ``rirs``, which must be on the corpus's device.  ``table``: an int32 device tensor that already holds the plan in
     the kernel's layout (``DynamicMixFeed`` stages it through pinned memory); without it the plan is copied from pageable memory.
     ``speeds``: the converter set the table's index block refers to (``pack_table``); default: the plan's own speeds.  A captured launch
     keeps the set it was captured with, so a table rewritten between replays must be packed against that set."""
@@ -449,9 +532,16 @@ def mix_batch(corpus: Corpus, plan: BatchPlan, Tmax: Optional[int] = None, mix: 
         raise ValueError(f"Tmax = {Tmax} must be a multiple of 4 and hold the longest example ({int(plan.n.max())})")
     if plan.speed is not None and speeds is None:
         speeds = plan_speeds(plan)
+    if plan.rir is not None:
+        if plan.speed is not None:
+            raise ValueError("a plan with speeds and RIRs is not built")
+        if rirs is None:
+            raise ValueError("the plan carries RIRs: pass the bank (rirs=)")
+        if not _same_device(rirs.device, dev):
+            raise ValueError(f"the RIR bank is on {rirs.device}, the corpus on {dev}")
     if table is None:
         table = torch.from_numpy(pack_table(plan, speeds)).to(dev)
-    if table.numel() < _table_words(B, NT, plan.speed is not None):
+    if table.numel() < _table_words(B, NT, plan.speed is not None, plan.rir is not None):
         raise ValueError("the device table is shorter than the plan's layout")
     if mix is None:
         mix = torch.empty(B, Tmax, dtype=torch.float32, device=dev)
@@ -467,7 +557,11 @@ def mix_batch(corpus: Corpus, plan: BatchPlan, Tmax: Optional[int] = None, mix: 
     rows = (C.c_void_p * plan.S)(*[t.data_ptr() for t in src])
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
-        if plan.speed is None:
+        if plan.rir is not None:
+            L_.check(L_.load().sepr_dynmix_reverb_fwd(*corpus._corpus_args(), base, base + 4 * n, base + 8 * n, base + 12 * n, base + 16 * n + 4 * B,
+                                                      base + 20 * n + 4 * B, base + 16 * n, B, plan.M, plan.S, Tmax, mix.data_ptr(), rows,
+                                                      *rirs._bank_args(), stream), "sepr_dynmix_reverb_fwd")
+        elif plan.speed is None:
             L_.check(L_.load().sepr_dynmix_fwd(*corpus._corpus_args(), base, base + 4 * n, base + 8 * n, base + 12 * n, base + 16 * n, B, plan.M,
                                                plan.S, Tmax, mix.data_ptr(), rows, stream), "sepr_dynmix_fwd")
         else:
@@ -479,7 +573,8 @@ def mix_batch(corpus: Corpus, plan: BatchPlan, Tmax: Optional[int] = None, mix: 
 
 def pack_table(plan: BatchPlan, speeds: Optional[Sequence[int]] = None) -> np.ndarray:
     """The plan as one int32 array ``[utt | start | norm bits | gain bits | n]``; a plan that carries speeds appends the converter-index
-    block ``[conv]``: -1 for a term at 100 %, else the position of the term's speed in ``speeds`` (default ``plan_speeds(plan)``)."""
+    block ``[conv]``: -1 for a term at 100 %, else the position of the term's speed in ``speeds`` (default ``plan_speeds(plan)``); a plan
+    that carries RIRs appends ``[rir | taps]`` after ``n``."""
     parts = [plan.utt.ravel(), plan.start.ravel(), plan.norm.ravel().view(np.int32), plan.gain.ravel().view(np.int32), plan.n.astype(np.int32)]
     if plan.speed is not None:
         order = [int(p) for p in (plan_speeds(plan) if speeds is None else speeds)]
@@ -489,6 +584,8 @@ def pack_table(plan: BatchPlan, speeds: Optional[Sequence[int]] = None) -> np.nd
         if missing:
             raise ValueError(f"speeds {missing} of the plan are not in the converter set {order}")
         parts.append(np.array([index[int(p)] for p in plan.speed.ravel()], np.int32))
+    if plan.rir is not None:
+        parts += [plan.rir.ravel().astype(np.int32), plan.taps.ravel().astype(np.int32)]
     return np.concatenate(parts)
 
 
@@ -497,7 +594,8 @@ class DynamicMixFeed:
     ``mixture [B, T]`` and the ``S`` tensors ``src[s] [B, T]`` on the device, the keys), one epoch per iteration.
 
     ``planner(corpus, rng, key, max_len) -> Example`` is one of ``plan_wsj0`` / ``plan_wham`` / ``plan_whamr`` / ``plan_direct`` (bind
-    other role names, or ``speeds=range(95, 106)`` for speed perturbation, with ``functools.partial``).  Per batch: plan on the host, write the table into a pinned staging buffer, one
+    other role names, or ``speeds=range(95, 106)`` for speed perturbation, with ``functools.partial``; for reverberation bind ``rirs=bank`` and
+    pass the same bank as the feed's ``rirs=``).  Per batch: plan on the host, write the table into a pinned staging buffer, one
     asynchronous copy into the static device table, one launch - all on the current stream, nothing waits for the device.
     ``keys``: the epoch's key order, used as given every epoch; default: the keys of the corpus's first role, permuted with the
     feed's ``random.Random(seed)`` before each epoch (the same generator then makes the examples' draws).  ``rank`` / ``world``:
@@ -508,9 +606,12 @@ class DynamicMixFeed:
     SLOTS = 4               # pinned staging buffers in flight
 
     def __init__(self, corpus: Corpus, planner: Callable[..., Example], batch: int, max_len: int, seed: int = 0,
-                 keys: Optional[Sequence[str]] = None, fixed_length: bool = False, rank: int = 0, world: int = 1):
+                 keys: Optional[Sequence[str]] = None, fixed_length: bool = False, rank: int = 0, world: int = 1,
+                 rirs: Optional[RirBank] = None):
         if corpus.device is None:
             raise RuntimeError("DynamicMixFeed needs a corpus on the HIP device (there is no CPU path)")
+        if rirs is not None and not _same_device(rirs.device, corpus.device):
+            raise ValueError(f"the RIR bank is on {rirs.device}, the corpus on {corpus.device}")
         if batch < 1 or max_len < 4:
             raise ValueError("batch >= 1 and max_len >= 4")
         if fixed_length and max_len % 4:
@@ -518,7 +619,7 @@ class DynamicMixFeed:
         from .dist import shard_range
         shard_range(1, rank, world)                     # validates rank / world
         self.corpus, self.planner, self.batch, self.max_len = corpus, planner, int(batch), int(max_len)
-        self.fixed_length, self.rank, self.world = bool(fixed_length), rank, world
+        self.fixed_length, self.rank, self.world, self.rirs = bool(fixed_length), rank, world, rirs
         self.rng = random.Random(seed)
         self.keys = None if keys is None else list(keys)
         self._default_keys = list(next(iter(corpus.roles.values()))) if corpus.roles else None
@@ -547,12 +648,12 @@ class DynamicMixFeed:
         """The batch plans of one epoch (host only)."""
         order = self.epoch_order()
         for i in range(0, len(order) - self.batch + 1, self.batch):
-            yield collate_plan(self.corpus, [self.planner(self.corpus, self.rng, k, self.max_len) for k in order[i:i + self.batch]])
+            yield collate_plan(self.corpus, [self.planner(self.corpus, self.rng, k, self.max_len) for k in order[i:i + self.batch]], self.rirs)
 
     # ---- device side -------------------------------------------------------------------------------------------------------
     def _launch(self, plan: BatchPlan, mix=None, src=None):
         dev = self.corpus.device
-        words = _table_words(*plan.utt.shape, plan.speed is not None)
+        words = _table_words(*plan.utt.shape, plan.speed is not None, plan.rir is not None)
         self._speeds += [p for p in plan_speeds(plan) if p not in self._speeds]
         if self._table is None or self._table.numel() != words:
             self._table = torch.empty(words, dtype=torch.int32, device=dev)
@@ -568,7 +669,8 @@ class DynamicMixFeed:
         ev.record(torch.cuda.current_stream(dev))
         self._events[k] = ev
         self.last_plan = plan
-        return mix_batch(self.corpus, plan, self.max_len if self.fixed_length else None, mix, src, table=self._table, speeds=self._speeds)
+        return mix_batch(self.corpus, plan, self.max_len if self.fixed_length else None, mix, src, table=self._table, speeds=self._speeds,
+                         rirs=self.rirs)
 
     def __iter__(self):
         for plan in self.plans():

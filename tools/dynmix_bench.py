@@ -15,10 +15,16 @@ fed runs exceeds the mean of the fixed runs by at most the larger within-setting
 launch against the launch with every source term perturbed (WSJ0 form, S = 2, B = 16 and 32 x 4 s), and the bf16 training step fed
 without and with speeds; the step without speeds of that same run is the yardstick.
 
+``--rirs 64:0.6`` measures reverberation by convolution instead (section 5e-3), in one child process with the settings alternating: the
+plain WHAMR-form launch (5 terms) against the reverberant form (3 mixture terms, the two sources under a whole impulse response, and 2
+direct-path targets) at RT60 = 0.3, 0.6 and 1.0 s, B = 16 and 32 x 4 s; and the bf16 training step fed plainly and fed with
+reverberation from COUNT synthetic responses of RT60 seconds; the plainly fed step of that same run is the yardstick.
+
 Every step runs in a child process of its own under ``timeout -k 10 <s>``; the first step that fails ends the run.
 
     python tools/dynmix_bench.py [--out profiles/dynmix_timing.json]
     python tools/dynmix_bench.py --speeds 95:105 [--out profiles/dynmix_speed.json]
+    python tools/dynmix_bench.py --rirs 64:0.6 [--out profiles/dynmix_reverb.json]
 """
 import argparse
 import json
@@ -253,6 +259,107 @@ def step_speed(speeds):
                      "host_plan_ms_per_batch": plan_ms}}
 
 
+def step_reverb(spec):
+    """Plain WHAMR-form launch against the reverberant launch at three RT60s, and the training step fed plainly and with reverberation;
+    everything alternating."""
+    import functools
+    import numpy as np
+    import torch
+    from sepreformer_amd import datafeed as df
+    from sepreformer_amd.config import VARIANTS
+    from sepreformer_amd.criterion import PIT_SISNR_mag, PIT_SISNR_time
+    from sepreformer_amd.model import Model
+    from sepreformer_amd.optim import FlatAdamW
+    from sepreformer_amd.reverb import RirBank, parse_synthetic, synthetic_rirs
+    from sepreformer_amd.train_step import CapturedTrainStep
+    count, rt_lo, rt_hi = parse_synthetic(spec)
+    dev = torch.device("cuda:0")
+    keys, arrays = synth_corpus_arrays()
+    corpus = df.Corpus.from_arrays(arrays, device=dev, fs=FS)
+    corpus.roles = {r: list(keys) for r in ROLES}
+    banks = {rt: RirBank.from_arrays(synthetic_rirs(count, FS, rt60=rt, seed=0), FS, device=dev) for rt in (0.3, 0.6, 1.0)}
+    kernel = []
+    for B in (16, 32):
+        sets = {}
+        for name, bank in [("plain", None)] + [(f"rt60_{rt}", b) for rt, b in banks.items()]:
+            planner = df.plan_whamr if bank is None else functools.partial(df.plan_whamr, rirs=bank)
+            rng = random.Random(B)
+            plan = df.collate_plan(corpus, [planner(corpus, rng, keys[i % NKEYS], T4S) for i in range(B)], rirs=bank)
+            table = torch.from_numpy(df.pack_table(plan)).to(dev)
+            sets[name] = (plan, bank, table, torch.empty(B, T4S, device=dev), [torch.empty(B, T4S, device=dev) for _ in range(plan.S)], [])
+        for i in range(20 + 100):
+            for plan, bank, table, mix, src, ms in sets.values():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                df.mix_batch(corpus, plan, T4S, mix, src, table=table, rirs=bank)
+                e1.record()
+                torch.cuda.synchronize()
+                if i >= 20:
+                    ms.append(e0.elapsed_time(e1))
+        rec = {"form": "whamr", "B": B, "samples": T4S, "S": 2, "launches": 100, "plain_device_ms": _stats(sets["plain"][5])}
+        for rt in banks:
+            plan, ms = sets[f"rt60_{rt}"][0], sets[f"rt60_{rt}"][5]
+            fma = int(sum(int(n) * int(k) for n, rr, kk in zip(plan.n, plan.rir, plan.taps) for r, k in zip(rr, kk) if r >= 0))
+            rec[f"rt60_{rt}"] = {"device_ms": _stats(ms), "f64_fma": fma, "Gfma_per_s_at_median": fma / (_stats(ms)["median"] * 1e-3) / 1e9,
+                                 "mixture_taps_mean": float(plan.taps[:, :2].mean()), "target_taps_mean": float(plan.taps[:, 3:].mean())}
+        kernel.append(rec)
+    B = 16
+    cfg = VARIANTS["SepReformer_Base_WSJ0"]
+    torch.manual_seed(0)
+    model = Model.from_config(cfg, init_seed=0, precision="bf16").load_synthetic_(0).to(dev).train()
+    crit_t = PIT_SISNR_time(dev, cfg.num_spks, True)
+    crit_m = PIT_SISNR_mag(dev, 512, 128, "hann", cfg.num_stages, cfg.num_spks, True, False)
+    sizes = torch.full((B,), T4S)
+    opt = FlatAdamW(model, lr=1.0e-4, weight_decay=1.0e-2)
+
+    def loss_fn(audio, aux, *tg):
+        tg = list(tg)
+        l_time = crit_t(estims=audio, input_sizes=sizes, target_attr=tg)
+        l_mag = [crit_m(estims=a, idx=i, input_sizes=sizes, target_attr=tg) for i, a in enumerate(aux)]
+        return (0.6 * l_time + 0.4 * sum(l_mag) / len(l_mag)) / cfg.num_spks
+
+    bank = RirBank.from_arrays(synthetic_rirs(count, FS, rt60=(rt_lo, rt_hi), seed=1), FS, device=dev)
+    feeds = {"plain": df.DynamicMixFeed(corpus, df.plan_whamr, batch=B, max_len=T4S, seed=0, fixed_length=True),
+             "reverb": df.DynamicMixFeed(corpus, functools.partial(df.plan_whamr, rirs=bank), batch=B, max_len=T4S, seed=0, fixed_length=True,
+                                         rirs=bank)}
+    x = torch.zeros(B, T4S, device=dev)
+    tg = [torch.zeros(B, T4S, device=dev) for _ in range(2)]
+    feeds["plain"].next_into(x, tg)
+    step = CapturedTrainStep(model, loss_fn, opt, x, tg, max_norm=5.0, warmup=2)
+
+    def loop(feed):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(LOOP_STEPS):
+            feed.next_into(step.x, step.targets)
+            loss, _ = step(step.x, step.targets)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / LOOP_STEPS, float(loss.detach())
+
+    for f in feeds.values():
+        loop(f)                                                               # warm both paths
+    runs = {name: [] for name in feeds}
+    losses = []
+    for _ in range(LOOP_RUNS):
+        for name, f in feeds.items():
+            ms, ls = loop(f)
+            runs[name].append(ms)
+            losses.append(ls)
+    plan_ms = {}
+    for name, f in feeds.items():
+        t0 = time.perf_counter()
+        for _ in range(50):
+            f.next_plan()
+        plan_ms[name] = (time.perf_counter() - t0) * 1e3 / 50
+    step.release()
+    assert all(np.isfinite(v) for v in losses)
+    return {"device": torch.cuda.get_device_name(0), "rirs": {"count": count, "rt60": [rt_lo, rt_hi], "samples": [int(bank.lengths.min()), int(bank.lengths.max())]},
+            "kernel": kernel,
+            "loop": {"model": "SepReformer_Base_WSJ0 bf16, batch 16 x 4 s, CapturedTrainStep + FlatAdamW, the reference's loss, fed in the WHAMR form",
+                     "steps_per_run": LOOP_STEPS, "plain_ms_per_step": runs["plain"], "reverb_ms_per_step": runs["reverb"],
+                     "host_plan_ms_per_batch": plan_ms}}
+
+
 def step_host():
     """The reference's per-example work in numpy from RAM-resident arrays (no disk, no decoding of a file): WHAMR form."""
     from concurrent.futures import ThreadPoolExecutor
@@ -303,14 +410,18 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--step", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--speeds", default=None, metavar="LO:HI", help="measure speed perturbation (an inclusive range or a comma list of percentages)")
+    ap.add_argument("--rirs", default=None, metavar="COUNT:RT60", help="measure reverberation by convolution (COUNT synthetic impulse responses of RT60 s)")
     args = ap.parse_args()
+    if args.speeds and args.rirs:
+        ap.error("--speeds and --rirs are measured in runs of their own")
     if args.step:
-        rec = {"device": step_device, "host": step_host, "speed": lambda: step_speed(args.speeds)}[args.step]()
+        rec = {"device": step_device, "host": step_host, "speed": lambda: step_speed(args.speeds), "reverb": lambda: step_reverb(args.rirs)}[args.step]()
         print("__RESULT__" + json.dumps(rec))
         return
     rec, failed = {}, None
-    for name, limit in ([("speed", 600)] if args.speeds else STEPS):
-        cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", name] + (["--speeds", args.speeds] if args.speeds else [])
+    for name, limit in ([("speed", 600)] if args.speeds else [("reverb", 600)] if args.rirs else STEPS):
+        cmd = (["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", name] + (["--speeds", args.speeds] if args.speeds else [])
+               + (["--rirs", args.rirs] if args.rirs else []))
         r = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
         lines = [ln for ln in r.stdout.splitlines() if ln.startswith("__RESULT__")]
         if r.returncode != 0 or not lines:
@@ -328,6 +439,17 @@ def main():
                           "plain_step_ms_mean": mean(a), "speeds_step_ms_mean": mean(b), "difference_ms": mean(b) - mean(a),
                           "plain_step_spread_ms": max(a) - min(a), "speeds_step_spread_ms": max(b) - min(b),
                           "perturbed_launch_share_of_plain_step": k["perturbed_device_ms"]["median"] / mean(a)}
+    elif not failed and args.rirs:
+        lp = rec["loop"]
+        a, b = lp["plain_ms_per_step"], lp["reverb_ms_per_step"]
+        mean = lambda v: sum(v) / len(v)                                    # noqa: E731
+        k = next(r for r in rec["kernel"] if r["B"] == 16)
+        spread = max(max(a) - min(a), max(b) - min(b))
+        rec["summary"] = {"plain_launch_ms_median": k["plain_device_ms"]["median"],
+                          "reverb_launch_ms_median": {rt: k[rt]["device_ms"]["median"] for rt in k if rt.startswith("rt60_")},
+                          "plain_step_ms_mean": mean(a), "reverb_step_ms_mean": mean(b), "difference_ms": mean(b) - mean(a),
+                          "plain_step_spread_ms": max(a) - min(a), "reverb_step_spread_ms": max(b) - min(b),
+                          "reverb_exceeds_plain_by_more_than_the_larger_spread": mean(b) - mean(a) > spread}
     elif not failed:
         lp = rec["loop"]
         fixed, fed = lp["fixed_ms_per_step"], lp["fed_ms_per_step"]

@@ -6,6 +6,8 @@ loss and utt/s every ``--log`` steps.  Schedulers, checkpoints and validation ar
     python tools/train_from_scp.py --form wsj0 --scp s1=tr_s1.scp s2=tr_s2.scp --steps 200
     python tools/train_from_scp.py --form whamr --scp s1=.. s2=.. s1_reverb=.. s2_reverb=.. noise=.. --model SepReformer_Large_DM_WHAMR
     python tools/train_from_scp.py --form wsj0 --scp s1=tr_s1.scp s2=tr_s2.scp --speeds 95:105      # speed perturbation (section 5e-2)
+    python tools/train_from_scp.py --form whamr --scp s1=.. s2=.. noise=.. --rir-scp rirs.scp        # reverberation in the launch (section 5e-3)
+    python tools/train_from_scp.py --form whamr --scp s1=.. s2=.. noise=.. --synthetic-rirs 64:0.2:0.8
 """
 import argparse
 import os
@@ -28,6 +30,13 @@ def main():
     ap.add_argument("--resample", action="store_true", help="convert files at another rate on the device (default: an error)")
     ap.add_argument("--speeds", default=None, metavar="LO:HI", help="speed perturbation: one speed in percent per source and example, drawn from "
                     "the inclusive range LO:HI or from a comma list (default: off)")
+    rir = ap.add_mutually_exclusive_group()
+    rir.add_argument("--rir-scp", default=None, metavar="FILE", help="reverberation: a 'key path' list of impulse-response wav files; one is drawn per "
+                     "source and example and convolved inside the mixing launch (with --form whamr the *_reverb roles are then not needed)")
+    rir.add_argument("--synthetic-rirs", default=None, metavar="COUNT:RT60LO:RT60HI", help="reverberation from COUNT synthetic impulse responses "
+                     "with RT60 drawn from [RT60LO, RT60HI] seconds (sepreformer_amd.reverb.synthetic_rirs)")
+    ap.add_argument("--reverb-target", choices=["direct", "dry", "full"], default="direct", help="the targets under reverberation: the direct "
+                    "path of the same impulse response (default), the dry source, or the whole response")
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--log", type=int, default=10)
     ap.add_argument("--lr", type=float, default=1.0e-4)
@@ -36,6 +45,17 @@ def main():
     args = ap.parse_args()
     if args.speeds and args.form == "direct":
         ap.error("--speeds needs dynamic mixing (--form wsj0, wham or whamr)")
+    reverb = args.rir_scp or args.synthetic_rirs
+    if reverb and args.form == "direct":
+        ap.error("--rir-scp / --synthetic-rirs need dynamic mixing (--form wsj0, wham or whamr)")
+    if reverb and args.speeds:
+        ap.error("--speeds together with --rir-scp / --synthetic-rirs is not built: pass one of them")
+    if args.synthetic_rirs:
+        from sepreformer_amd.reverb import parse_synthetic
+        try:
+            synth = parse_synthetic(args.synthetic_rirs)
+        except ValueError as e:
+            ap.error(f"--synthetic-rirs: {e}")
 
     import functools
     import torch
@@ -53,7 +73,16 @@ def main():
     planner = {"wsj0": df.plan_wsj0, "wham": df.plan_wham, "whamr": df.plan_whamr, "direct": df.plan_direct}[args.form]
     if args.speeds:
         planner = functools.partial(planner, speeds=df.parse_speeds(args.speeds))
-    feed = df.DynamicMixFeed(corpus, planner, batch=args.batch, max_len=args.max_len, seed=args.seed, fixed_length=True)
+    bank = None
+    if reverb:
+        from sepreformer_amd.reverb import RirBank, synthetic_rirs
+        if args.rir_scp:
+            bank = RirBank.from_scp(args.rir_scp, fs=args.fs, device=dev, resample=args.resample)
+        else:
+            bank = RirBank.from_arrays(synthetic_rirs(synth[0], args.fs, rt60=synth[1:], seed=args.seed), args.fs, device=dev)
+        planner = functools.partial(planner, rirs=bank, target=args.reverb_target)
+        print(f"RIR bank: {len(bank)} impulse responses, {int(bank.lengths.min())} .. {int(bank.lengths.max())} samples", flush=True)
+    feed = df.DynamicMixFeed(corpus, planner, batch=args.batch, max_len=args.max_len, seed=args.seed, fixed_length=True, rirs=bank)
     print(f"corpus: {len(corpus)} utterances, {corpus.total16 * 2 + corpus.total32 * 4} bytes on {dev}", flush=True)
 
     cfg = VARIANTS[args.model]
