@@ -288,7 +288,21 @@ __device__ __forceinline__ void gcfn_fused3_body(const GcfnFusedArgs& a) {
       }
       s += __shfl_xor(s, 16, 64);
       s += __shfl_xor(s, 32, 64);
-      const float mean = PLAIN ? 0.f : s * (1.0f / F);
+      float mean = PLAIN ? 0.f : s * (1.0f / F);
+      if constexpr (TRAIN && !PLAIN) {
+        // One refinement step: mean += mean(x - mean).  The running sum above rounds at every add, so the mean of a row of F equal values c
+        // is a few ulps off c and xhat = (c - mean) rstd is 1e-4 |c| instead of 0 once the variance vanishes (rstd = 1 / sqrt(eps) = 316).
+        // The backward multiplies these statistics into the net1.1 weight gradient and recomputes h1 from them (docs/HISTORY.md, backward
+        // branch parity).  The residuals x - mean are exact for such a row and their sum is too, so the refined mean is c itself.
+        float r = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+          for (int e = 0; e < 8; ++e) r += v[ks][e] - mean;
+        r += __shfl_xor(r, 16, 64);
+        r += __shfl_xor(r, 32, 64);
+        mean += r * (1.0f / F);
+      }
       float d = 0.f;
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks)

@@ -4,7 +4,12 @@
 // they are working on (6 + 9 MFMAs per 16 x 32 block, against 2 x 4 bytes of HBM traffic per score for stored P and dS).
 //
 //   scores[i][j] = (q_i . k_j + q_i . pe[r(i,j)]) / sqrt(dk),  P = exp(scores - lse_i),  Pd = dropout(P)
-//   D_i = dO_i . o_i;  dP = dropout'(dO_i . v_j);  dS = P (dP - D_i) / sqrt(dk)
+//   dP = dropout'(dO_i . v_j);  D_i = sum_j P dP / sum_j P;  dS = P (dP - D_i) / sqrt(dk)
+// D_i is the row sum of the very P and dP the backward recomputes (a first sweep over the keys in the query-major kernel), not the textbook
+// dO_i . o_i with the forward's stored output: the two agree only to the 2^-18 of a split product relative to |dO| |v|, and that much of
+// sum_j dS[i][j] != 0 is what is left of dq, dk and the table gradient when the rows of k and v are nearly equal (an input far below the
+// LayerNorm eps, one loud channel): linear_k.weight read 56 - 67 dB against the float64 oracle there, 80 - 92 dB with the sum taken here
+// (docs/HISTORY.md, backward branch parity).
 //   dq_i = sum_j dS[i][j] (k_j + pe[r]);  dk_j = sum_i dS[i][j] q_i;  dv_j = sum_i Pd[i][j] dO_i;  dpe[r] += sum dS[i][j] q_i
 //
 // An MFMA contracts over the index that lives INSIDE a lane, never over the 16 lanes of a fragment row, so the two
@@ -32,6 +37,8 @@ constexpr int AX_QB = 64, AX_KT = 64, AX_NBAND = AX_QB + AX_KT - 1;
 constexpr int AX_PSK = 52;      // bias skew scratch row stride (floats; 48 used)
 constexpr int AX_PSD = 68;      // dS un-skew scratch row stride (floats; 64 used)
 constexpr int AX_BTS = 152;     // transposed band row stride (bf16): band rows 0..126 + zero pad up to column 143
+template <bool V>
+struct ax_bool { static constexpr bool value = V; };
 
 __device__ __forceinline__ void ax_split4(const float4 v, ax_bf16x4& h, ax_bf16x4& l) {
   const float x[4] = {v.x, v.y, v.z, v.w};
@@ -65,11 +72,11 @@ __device__ __forceinline__ f32x4 ax_mma(const ax_bf16x8 ah, const ax_bf16x8 al, 
 
 struct AxArgs {
   const float* QKV;    // [n, Tp, 3F]
-  const float* O;      // [n, Tp, F]   forward output (D_i)
+  const float* O;      // [n, Tp, F]   forward output (not read: D_i comes from the recomputed P and dP, see the head of the file)
   const float* dO;     // [n, Tp, F]
   const float* lse;    // [n*H, Tp]
   float* dQKV;         // [n, Tp, 3F]
-  float* Dbuf;         // [n*H, Tp]    D_i = dO_i . o_i (written by the query-major kernel, read by the key-major one)
+  float* Dbuf;         // [n*H, Tp]    D_i (written by the query-major kernel, read by the key-major one)
   float* dS;           // [n*H, Tp, Tp] (query-major kernel -> table-gradient kernel)
   const float* pe;     // [2*maxlen, dk]
   int Tp, F, H, maxlen;
@@ -140,31 +147,25 @@ __global__ __launch_bounds__(256) void relattn_bwd_q_x3_kernel(const AxArgs a) {
     if constexpr (!ONE) Btl[e] = (__bf16)0.f;
   }
 
-  // B fragments of this lane's query: q (scaled) and dO; D_i; lse_i
+  // B fragments of this lane's query: q (scaled) and dO; lse_i
   ax_bf16x8 qh, ql, gh, gl;
-  float Di = 0.f;
   {
     const long long row = (long long)seq * Tp + (active ? i : Tp - 1);
     const float* qp = base + (long long)(active ? i : Tp - 1) * ld + 8 * gk;
     const float* gp = a.dO + row * F + h * DK + 8 * gk;
-    const float* op = a.O + row * F + h * DK + 8 * gk;
-    const float4 q0 = ld4(qp), q1 = ld4(qp + 4), g0 = ld4(gp), g1 = ld4(gp + 4), o0 = ld4(op), o1 = ld4(op + 4);
+    const float4 q0 = ld4(qp), q1 = ld4(qp + 4), g0 = ld4(gp), g1 = ld4(gp + 4);
     float xq[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
     float xg[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
-    const float xo[8] = {o0.x, o0.y, o0.z, o0.w, o1.x, o1.y, o1.z, o1.w};
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      if (lowk) Di = fmaf(xg[e], xo[e], Di);
       xq[e] = lowk ? xq[e] * a.isd : 0.f;
       xg[e] = lowk ? xg[e] : 0.f;
     }
     ax_split8(xq, qh, ql);
     ax_split8(xg, gh, gl);
   }
-  Di += __shfl_xor(Di, 16, 64);
-  Di += __shfl_xor(Di, 32, 64);
   const float lse_i = a.lse[nh * Tp + (active ? i : Tp - 1)];
-  if (active && g == 0) a.Dbuf[nh * Tp + i] = Di;
+  float Di = 0.f, Asum = 0.f, Zsum = 0.f;      // D_i, and this lane's share of sum_j P dP and sum_j P (first sweep)
 
   f32x4 dq[OT];
 #pragma unroll
@@ -196,6 +197,10 @@ __global__ __launch_bounds__(256) void relattn_bwd_q_x3_kernel(const AxArgs a) {
       rb[u] = ld4(a.pe + (long long)(rel + a.maxlen) * DK + 4 * (idx % (DK / 4)));
     }
   };
+  // The sweep over the key tiles runs twice: PRE = true recomputes P and dP only and sums D_i's numerator and denominator; PRE = false
+  // is the backward proper.  Both stage the same tiles (the transposed planes, which only dq reads, in the second sweep only).
+  auto sweep = [&](auto pre_c) {
+  constexpr bool PRE = decltype(pre_c)::value;
   fetch(0);
   for (int j0 = 0; j0 < Tp; j0 += KT) {
     __syncthreads();
@@ -208,10 +213,12 @@ __global__ __launch_bounds__(256) void relattn_bwd_q_x3_kernel(const AxArgs a) {
         ax_split4(rk[u], hh, ll);
         *reinterpret_cast<ax_bf16x4*>(Kh + sjj * KSB + 4 * sc4) = hh;
         if constexpr (!ONE) *reinterpret_cast<ax_bf16x4*>(Kl + sjj * KSB + 4 * sc4) = ll;
+        if constexpr (!PRE) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          Kth[(4 * sc4 + e) * VSB + sjj] = hh[e];
-          if constexpr (!ONE) Ktl[(4 * sc4 + e) * VSB + sjj] = ll[e];
+          for (int e = 0; e < 4; ++e) {
+            Kth[(4 * sc4 + e) * VSB + sjj] = hh[e];
+            if constexpr (!ONE) Ktl[(4 * sc4 + e) * VSB + sjj] = ll[e];
+          }
         }
         ax_split4(rv[u], hh, ll);
         *reinterpret_cast<ax_bf16x4*>(Vh + sjj * KSB + 4 * sc4) = hh;
@@ -225,10 +232,12 @@ __global__ __launch_bounds__(256) void relattn_bwd_q_x3_kernel(const AxArgs a) {
           ax_split4(rb[u], hh, ll);
           *reinterpret_cast<ax_bf16x4*>(Bh + rr * KSB + 4 * sc4) = hh;
           if constexpr (!ONE) *reinterpret_cast<ax_bf16x4*>(Bl + rr * KSB + 4 * sc4) = ll;
+          if constexpr (!PRE) {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            Bth[(4 * sc4 + e) * AX_BTS + rr] = hh[e];
-            if constexpr (!ONE) Btl[(4 * sc4 + e) * AX_BTS + rr] = ll[e];
+            for (int e = 0; e < 4; ++e) {
+              Bth[(4 * sc4 + e) * AX_BTS + rr] = hh[e];
+              if constexpr (!ONE) Btl[(4 * sc4 + e) * AX_BTS + rr] = ll[e];
+            }
           }
         }
       }
@@ -282,8 +291,13 @@ __global__ __launch_bounds__(256) void relattn_bwd_q_x3_kernel(const AxArgs a) {
         for (int r = 0; r < 4; ++r) {
           const bool kin = jbase + r < Tp;
           const float pv = kin ? __expf(sc[s][r] + bias[r] - lse_i) : 0.f;
+          if constexpr (PRE) {
+            Asum = fmaf(pv, dp[s][r] * keep[r], Asum);
+            Zsum += pv;
+          }
           ds[4 * s + r] = pv * (dp[s][r] * keep[r] - Di) * a.isd;
         }
+        if constexpr (PRE) continue;
         // the dS rows go to HBM once, for the table gradient (16 bytes per lane, 64 contiguous bytes per query)
         if (a.ds16) {       // kernel-uniform
           __bf16* d16 = reinterpret_cast<__bf16*>(a.dS) + (nh * Tp + (active ? i : 0)) * Tp;
@@ -302,6 +316,7 @@ __global__ __launch_bounds__(256) void relattn_bwd_q_x3_kernel(const AxArgs a) {
             if (jbase + r < Tp) dsrow[jbase + r] = ds[4 * s + r];
         }
       }
+      if constexpr (PRE) continue;
       ax_bf16x8 dsh, dsl;
       ax_split8(ds, dsh, dsl);
       // ---- dQ^T[d][query] += K^T[d][key slots] . dS^T[key slots][query] ------------------------------------------------------
@@ -340,6 +355,15 @@ __global__ __launch_bounds__(256) void relattn_bwd_q_x3_kernel(const AxArgs a) {
       }
     }
   }
+  };
+  sweep(ax_bool<true>{});
+  Asum += __shfl_xor(Asum, 16, 64);
+  Asum += __shfl_xor(Asum, 32, 64);
+  Zsum += __shfl_xor(Zsum, 16, 64);
+  Zsum += __shfl_xor(Zsum, 32, 64);
+  Di = Zsum > 0.f ? Asum / Zsum : 0.f;      // (sum_j P is 1 to rounding; dividing makes sum_j P (dP - D_i) vanish for the P in hand)
+  if (active && g == 0) a.Dbuf[nh * Tp + i] = Di;
+  sweep(ax_bool<false>{});
   if (active) {
 #pragma unroll
     for (int t = 0; t < OT; ++t)

@@ -1,6 +1,7 @@
 """Branch parity: what the block tests measure once the residual is taken out, against a float64 reference, on hard inputs.
 Shared by tests/test_branch_parity_cpu.py (the proof that the bar has teeth, reference side only) and
-tests/test_branch_parity_gpu.py (the device against the same cases).  Test infrastructure only.
+tests/test_branch_parity_gpu.py (the device against the same cases); the second half of the file holds the same instrument for the training
+backward (tests/test_branch_parity_bwd_cpu.py, tests/test_branch_parity_bwd_gpu.py).  Test infrastructure only.
 
 Why.  GCFN, CLA, EGA and SpkAttention return ``x + branch(x)``; the kernels pass ``x`` through and compute the branch, which with the
 synthetic weights is 5 - 15 % of ``x``.  ``agreement_db(y, want)`` therefore sees a defect of the computed part 17 - 27 dB smaller than it
@@ -234,67 +235,80 @@ def _cl(t):
 def reference(case: Case, variant: str, sd, inp) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """(output, residual input or None) of ``case`` from the oracle in the dtype of ``sd``, in the device's channel-last layout
     (heads / e2e: ``[S, B, samples]``; e2e also stacks the auxiliary outputs behind the main ones)."""
+    dt = sd["separator.pos_emb.pe_k.weight"].dtype
+    with torch.no_grad():
+        return _forward(case, variant, sd, {k: v.to(dt) for k, v in inp.items()})
+
+
+@contextlib.contextmanager
+def _bn_training(sd, p):
+    """Train-mode BatchNorm ``p`` of the oracle: batch statistics, and the in-place update of the running ones goes to a copy."""
+    sdc = dict(sd)
+    for name in ("running_mean", "running_var", "num_batches_tracked"):
+        if p + name in sdc:
+            sdc[p + name] = sdc[p + name].clone()
+    orc.BN_TRAINING = True
+    try:
+        yield sdc
+    finally:
+        orc.BN_TRAINING = False
+
+
+def _forward(case: Case, variant: str, sd, t):
+    """The oracle call of ``case`` on the tensors ``t`` (already in the dtype of ``sd``); grad mode is the caller's."""
     cfg = VARIANTS[variant]
     F, H, S = cfg.feat, cfg.heads, cfg.num_spks
-    dt = sd["separator.pos_emb.pe_k.weight"].dtype
-    t = {k: v.to(dt) for k, v in inp.items()}
     k, s = case.kind, case.shape
-    with torch.no_grad():
-        if k in ("gcfn", "gcfn_train"):
-            return orc.gcfn(sd, E0 + ".g_block_1.block.gcfn", t["x"]), t["x"]
-        if k == "cla":
-            return orc.cla(sd, E0 + ".l_block_1.block.cla", t["x"]), t["x"]
-        if k == "cla_train":                                             # train-mode BatchNorm: batch statistics (and an in-place update
-            p = E0 + ".l_block_1.block.cla.BN."                          # of the running ones: on a copy)
-            sdc = dict(sd)
-            for name in ("running_mean", "running_var", "num_batches_tracked"):
-                if p + name in sdc:
-                    sdc[p + name] = sdc[p + name].clone()
-            orc.BN_TRAINING = True
-            try:
-                return orc.cla(sdc, E0 + ".l_block_1.block.cla", t["x"]), t["x"]
-            finally:
-                orc.BN_TRAINING = False
-        if k in ("ega", "ega_train"):
-            pos = _pos_k(sd, s["Tp"], cfg.maxlen, variant)
-            return orc.ega(sd, E0 + ".g_block_1.block.ega", _cl(t["x"]), pos, H), t["x"]
-        if k in ("spkattn", "spkattn_train"):                            # network.py:241-247 in channel-last terms
-            B, T = s["B"], s["T"]
-            xr = t["x"].view(B, S, T, F).permute(0, 2, 1, 3).reshape(B * T, S, F)
-            yr = xr + orc.mha(sd, D0 + ".spk_attn_1.self_attn", xr, None, H)
-            return yr.view(B, T, S, F).permute(0, 2, 1, 3).reshape(B * S, T, F), t["x"]
-        if k == "down":
-            return orc.down_conv(sd, E0 + ".downconv", t["x"]), None
-        if k == "split":
-            p = "separator.spk_split_blocks.0" if cfg.per_level_split else "separator.spk_split_block"
-            return _cl(orc.spk_split(sd, p, _cl(t["x"]), S)), None
-        if k == "fuse":
-            up = orc.TF.interpolate(_cl(t["lo"]), size=s["T"], mode="nearest")
-            y = orc.TF.conv1d(torch.cat([up, _cl(t["sk"])], 1), sd["separator.simple_fusion.0.weight"], sd["separator.simple_fusion.0.bias"])
-            return _cl(y), None
-        if k == "encoder":
-            return _cl(orc.audio_encoder(sd, t["wav"], cfg.enc_stride)), None
-        if k == "projector":
-            e = orc.audio_encoder(sd, t["wav"], cfg.enc_stride)
-            return _cl(orc.pad_signal(orc.feature_projector(sd, e), cfg.num_stages)), None
-        if k in ("head_main", "head_aux"):
-            e = orc.audio_encoder(sd, t["wav"], cfg.enc_stride)
-            B = s["B"]
-            if k == "head_main":
-                o = orc.output_layer(sd, "out_layer", _cl(t["z"]), e, S, False)
-                w = sd["audio_decoder.weight"]
-            else:
-                up = orc.TF.interpolate(_cl(t["z"]), size=e.shape[-1], mode="nearest")
-                o = orc.output_layer(sd, "out_layer_bn.1", up, e, S, True)
-                w = sd["decoder_bn.1.weight"]
-            return torch.stack([orc.audio_decoder(w, o[i], cfg.enc_stride).reshape(B, -1) for i in range(S)], 0), None
-        if k == "e2e":
-            audio, aux = orc.model_forward(sd, cfg, t["wav"])
-            B = s["B"]
-            n = min(a.reshape(B, -1).shape[-1] for a in list(audio) + [a for st in aux for a in st])
-            rows = [torch.stack([a.reshape(B, -1)[:, :n] for a in audio], 0)]
-            rows += [torch.stack([a.reshape(B, -1)[:, :n] for a in st], 0) for st in aux]
-            return torch.stack(rows, 0), None                            # [1 + R, S, B, n]
+    if k in ("gcfn", "gcfn_train"):
+        return orc.gcfn(sd, E0 + ".g_block_1.block.gcfn", t["x"]), t["x"]
+    if k == "cla":
+        return orc.cla(sd, E0 + ".l_block_1.block.cla", t["x"]), t["x"]
+    if k == "cla_train":
+        with _bn_training(sd, E0 + ".l_block_1.block.cla.BN.") as sdc:
+            return orc.cla(sdc, E0 + ".l_block_1.block.cla", t["x"]), t["x"]
+    if k in ("ega", "ega_train"):
+        pos = _pos_k(sd, s["Tp"], cfg.maxlen, variant)
+        return orc.ega(sd, E0 + ".g_block_1.block.ega", _cl(t["x"]), pos, H), t["x"]
+    if k in ("spkattn", "spkattn_train"):                            # network.py:241-247 in channel-last terms
+        B, T = s["B"], s["T"]
+        xr = t["x"].view(B, S, T, F).permute(0, 2, 1, 3).reshape(B * T, S, F)
+        yr = xr + orc.mha(sd, D0 + ".spk_attn_1.self_attn", xr, None, H)
+        return yr.view(B, T, S, F).permute(0, 2, 1, 3).reshape(B * S, T, F), t["x"]
+    if k == "down":
+        return orc.down_conv(sd, E0 + ".downconv", t["x"]), None
+    if k == "down_train":
+        with _bn_training(sd, E0 + ".downconv.BN.") as sdc:
+            return orc.down_conv(sdc, E0 + ".downconv", t["x"]), None
+    if k == "split":
+        p = "separator.spk_split_blocks.0" if cfg.per_level_split else "separator.spk_split_block"
+        return _cl(orc.spk_split(sd, p, _cl(t["x"]), S)), None
+    if k == "fuse":
+        up = orc.TF.interpolate(_cl(t["lo"]), size=s["T"], mode="nearest")
+        y = orc.TF.conv1d(torch.cat([up, _cl(t["sk"])], 1), sd["separator.simple_fusion.0.weight"], sd["separator.simple_fusion.0.bias"])
+        return _cl(y), None
+    if k == "encoder":
+        return _cl(orc.audio_encoder(sd, t["wav"], cfg.enc_stride)), None
+    if k == "projector":
+        e = orc.audio_encoder(sd, t["wav"], cfg.enc_stride)
+        return _cl(orc.pad_signal(orc.feature_projector(sd, e), cfg.num_stages)), None
+    if k in ("head_main", "head_aux"):
+        e = orc.audio_encoder(sd, t["wav"], cfg.enc_stride)
+        B = s["B"]
+        if k == "head_main":
+            o = orc.output_layer(sd, "out_layer", _cl(t["z"]), e, S, False)
+            w = sd["audio_decoder.weight"]
+        else:
+            up = orc.TF.interpolate(_cl(t["z"]), size=e.shape[-1], mode="nearest")
+            o = orc.output_layer(sd, "out_layer_bn.1", up, e, S, True)
+            w = sd["decoder_bn.1.weight"]
+        return torch.stack([orc.audio_decoder(w, o[i], cfg.enc_stride).reshape(B, -1) for i in range(S)], 0), None
+    if k == "e2e":
+        audio, aux = orc.model_forward(sd, cfg, t["wav"])
+        B = s["B"]
+        n = min(a.reshape(B, -1).shape[-1] for a in list(audio) + [a for st in aux for a in st])
+        rows = [torch.stack([a.reshape(B, -1)[:, :n] for a in audio], 0)]
+        rows += [torch.stack([a.reshape(B, -1)[:, :n] for a in st], 0) for st in aux]
+        return torch.stack(rows, 0), None                            # [1 + R, S, B, n]
     raise KeyError(k)
 
 
@@ -311,7 +325,7 @@ class _Proxy:
 
 @contextlib.contextmanager
 def patched(**names):
-    """Replace module globals of the oracle (``TF``, ``torch``, ``mha``, ``_ln``, ``_lin``, ``rel_pos_k``) for the duration."""
+    """Replace module globals of the oracle (``TF``, ``torch``, ``mha``, ``_ln``, ``_lin``, ``_bn_eval``, ``rel_pos_k``) for the duration."""
     old = {k: getattr(orc, k) for k in names}
     try:
         for k, v in names.items():
@@ -332,10 +346,32 @@ def _split(a):
     return hi.double(), lo.double()
 
 
-def _mm_x3(a, b):
+def _mm_x3_raw(a, b):
     ah, al = _split(a)
     bh, bl = _split(b)
     return torch.matmul(ah, bh) + torch.matmul(ah, bl) + torch.matmul(al, bh)
+
+
+class _MMx3(torch.autograd.Function):
+    """The split product with the device's backward.  ``_split`` goes through ``.bfloat16()``, whose autograd backward rounds the GRADIENT
+    to bf16, so differentiating ``_mm_x3_raw`` would corrupt the reference.  The device's dgrad and wgrad are split products themselves:
+    ``dA = mm_x3(dC, B^T)``, ``dB = mm_x3(A^T, dC)`` (fp32-rounded operands, float64 sums), summed over the dimensions ``matmul`` broadcast."""
+
+    @staticmethod
+    def forward(ctx, a, b):
+        ctx.save_for_backward(a, b)
+        return _mm_x3_raw(a, b)
+
+    @staticmethod
+    def backward(ctx, dc):
+        a, b = ctx.saved_tensors
+        da = _mm_x3_raw(dc, b.transpose(-1, -2)).sum_to_size(a.shape) if ctx.needs_input_grad[0] else None
+        db = _mm_x3_raw(a.transpose(-1, -2), dc).sum_to_size(b.shape) if ctx.needs_input_grad[1] else None
+        return da, db
+
+
+def _mm_x3(a, b):
+    return _MMx3.apply(a, b)
 
 
 def _lin_x3(sd, p, x):
@@ -461,4 +497,362 @@ def mutants() -> Dict[str, dict]:
         "layernorm_eps_1e-6": {"ctx": lambda: patched(_ln=_ln_eps), "kinds": {"gcfn", "cla", "ega", "spkattn", "gcfn_train", "cla_train", "ega_train", "spkattn_train"}},
         "groupnorm_eps_1e-9": {"ctx": lambda: patched(TF=_Proxy(TF, group_norm=_gn_eps)), "kinds": {"projector", "split", "e2e"}},
         "pos_term_unscaled": {"ctx": lambda: patched(mha=_mha_variant(pos_unscaled=True)), "kinds": EGA_KINDS},
+    }
+
+
+# ======================================================================================================================
+# the backward: the same instrument on the branch GRADIENT (tests/test_branch_parity_bwd_cpu.py, tests/test_branch_parity_bwd_gpu.py)
+#
+# ``dx = dy + J^T dy``: the backward kernels pass ``dy`` through and compute only the second term, 3 - 30 % of ``dy`` with the synthetic
+# weights, so ``agreement_db`` on whole ``dx`` hides a defect of the computed part by 10 - 30 dB exactly as it does on ``y``.  The measure is
+# ``branch_db(dx, dy, dx64, dy64)``; a parameter gradient is measured with ``agreement_db`` against its float64 gradient; the reference is
+# float64 ``torch.autograd`` over the oracle; ``floor_db`` is float32 autograd against it on the very case, one figure per tensor, and
+# ``floor_x3_db`` the float64 backward through the split products (``_MMx3``), rounded to float32.  ``bar()`` is unchanged.
+#
+# A tensor whose float64 gradient is (next to) nothing - max-abs <= ZERO_REL x the largest parameter-gradient max-abs of the block in that
+# case - has no agreement to measure: the STRUCTURAL_ZERO biases of tests/test_train_gpu.py (float32 against float64 autograd reads
+# -175 dB there) and the tensors a family makes exactly zero (``zeros``: the weight of a LayerNorm whose input rows are all zero).  It is
+# judged on magnitude, ``max|g| <= MAG_TOL x scale``, the rule agree_grad of tests/test_train_gpu.py uses.  With ``dy = zeros`` every
+# gradient and ``dx`` must be exactly 0.
+# ======================================================================================================================
+ZERO_REL = 1e-9
+MAG_TOL = 1e-3
+STRUCTURAL_ZERO = ("linear_k.bias", "dw_conv_1d.bias", "cla.linear2.bias", "down_conv.bias")    # tests/test_train_gpu.py's list (the CPU test compares)
+BWD_X_FAMILIES = ["randn", "plus100"]                                # the x families every hard dy family runs against
+BWD_DY_FAMILIES = ["row_range", "silent_rows", "loud", "zeros"]
+BWD_PAIRS: List[Tuple[str, str]] = [(xf, "randn") for xf in ROW_FAMILIES] + [(xf, df) for df in BWD_DY_FAMILIES for xf in BWD_X_FAMILIES]
+BWD_PAIRS_LARGE: List[Tuple[str, str]] = [(xf, "randn") for xf in WORST_FLOORS]
+PE_K = "separator.pos_emb.pe_k.weight"
+BWD_KIND = {"gcfn_train": "gcfn", "cla_train": "cla", "ega_train": "ega", "spkattn_train": "spkattn", "down_train": "down", "split": "split", "fuse": "fuse"}
+
+# the shapes tests/test_train_gpu.py already names (milliseconds each on the device) ...
+BWD_CASES: List[Case] = (
+    [Case("gcfn_train", BWD_PAIRS, n=n, T=T) for n, T in ((2, 37), (3, 300), (1, 1))]
+    + [Case("cla_train", BWD_PAIRS, n=n, T=T) for n, T in ((2, 24), (2, 150), (3, 700))]         # below the 65-tap window, one tile, several
+    + [Case("ega_train", BWD_PAIRS, n=2, fac=f, Tp=Tp) for f, Tp in ((1, 25), (4, 30), (2, 130), (16, 9))]   # Tp 130 > tiny's maxlen 40
+    + [Case("spkattn_train", BWD_PAIRS, B=3, T=33)]
+    + [Case("down_train", BWD_PAIRS, n=2, T=T) for T in (40, 41, 6)]
+    + [Case("split", BWD_PAIRS, B=3, T=129), Case("fuse", BWD_PAIRS, B=2, T=24)]
+)
+# ... and one several-tile shape per residual block on randn and the three lowest floors
+BWD_LARGE_CASES: List[Case] = [Case("gcfn_train", BWD_PAIRS_LARGE, n=3, T=2731), Case("cla_train", BWD_PAIRS_LARGE, n=2, T=2100),
+                               Case("ega_train", BWD_PAIRS_LARGE, n=2, fac=8, Tp=300)]
+
+
+def param_prefixes(case: Case, cfg) -> Tuple[str, ...]:
+    """The state-dict prefixes of the parameters ``case`` has gradients for (the prefix check_param_grads of tests/test_train_gpu.py is given)."""
+    k = BWD_KIND[case.kind]
+    if k == "split":
+        return ("separator.spk_split_blocks.0." if cfg.per_level_split else "separator.spk_split_block.",)
+    return {"gcfn": (E0 + ".g_block_1.block.gcfn.",), "cla": (E0 + ".l_block_1.block.cla.",), "ega": (E0 + ".g_block_1.block.ega.", PE_K),
+            "spkattn": (D0 + ".spk_attn_1.self_attn.",), "down": (E0 + ".downconv.",), "fuse": ("separator.simple_fusion.0.",)}[k]
+
+
+def dy_shape(case: Case, cfg):
+    k, s = BWD_KIND[case.kind], case.shape
+    F, S = cfg.feat, cfg.num_spks
+    if k in ("gcfn", "cla"):
+        return (s["n"], s["T"], F)
+    if k == "ega":
+        return (s["n"], s["Tp"] * s["fac"], F)
+    if k == "down":
+        K = cfg.down_kernel
+        return (s["n"], (s["T"] + 2 * ((K - 1) // 2) - K) // 2 + 1, F)
+    if k == "split":
+        return (s["B"] * S, s["T"], F)
+    return (s["B"] * S, s["T"], F)                                    # spkattn, fuse
+
+
+def make_dy(case: Case, cfg, family: str) -> torch.Tensor:
+    """The output gradient of ``case`` (channel-last, float32) from ``input_families`` under a seed of its own."""
+    seed = 500 + sum(ord(ch) for ch in case.tag) % 991
+    return input_families(dy_shape(case, cfg), seed)[family]
+
+
+_DX_NAME = {"x": "dx", "lo": "dlo", "sk": "dskip"}
+
+
+def reference_bwd(case: Case, variant: str, sd_dtype, inp, dy):
+    """``torch.autograd`` over the oracle call ``reference()`` makes for the kind: ({"dx": ...} in the device's channel-last layout
+    (fuse: "dlo" and "dskip"), the residual term of ``dx`` (``dy``, or None for a block without a residual), {state-dict key: gradient})."""
+    from oracle import train_oracle as tor
+    cfg = VARIANTS[variant]
+    pre = param_prefixes(case, cfg)
+    sdl = tor.leaf_state({k: v for k, v in state(variant).items() if k.startswith(pre)}, sd_dtype)   # the block's own entries: all its call reads
+    t = {k: v.to(sd_dtype).clone().requires_grad_(True) for k, v in inp.items()}
+    dyt = dy.to(sd_dtype)
+    with torch.enable_grad():
+        y, res = _forward(case, variant, sdl, t)
+        y.backward(dyt)
+    grads = {k: v.grad for k, v in sdl.items() if v.requires_grad and v.grad is not None}
+    return {_DX_NAME[k]: v.grad for k, v in t.items()}, (None if res is None else dyt), grads
+
+
+def reference_bwd_x3(case, variant, inp, dy):
+    """The float64 backward through the bf16 hi+lo products (forward and backward), every result rounded to float32 (device storage)."""
+    with x3_context():
+        dx, res, grads = reference_bwd(case, variant, torch.float64, inp, dy)
+    rnd = lambda v: v.float().double()                                # noqa: E731
+    return {k: rnd(v) for k, v in dx.items()}, res, {k: rnd(v) for k, v in grads.items()}
+
+
+def measure_bwd(r: dict, name: str, got) -> float:
+    """The figure of tensor ``name`` of floors_bwd()'s ``r``: the branch for ``dx`` of a residual block, plain agreement otherwise."""
+    if name in r["dx64"]:
+        dy = r["dy"] if r["residual"] else None                      # float32, as the device received it
+        return branch_db(got, dy, r["dx64"][name], None if dy is None else dy.double())
+    return orc.agreement_db(got.double(), r["g64"][name])
+
+
+_floor_bwd_cache: Dict[tuple, dict] = {}
+
+
+def floors_bwd(case: Case, variant: str, xfam: str, dyfam: str, want_x3: bool = True) -> dict:
+    """Everything the reference side says about one (case, x family, dy family): inputs, float64 ``dx64`` / ``g64``, per tensor its
+    ``rule`` ("db" | "magnitude" | "zero"), ``floor_db`` and ``floor_x3_db`` (None where the rule is not "db"), and ``scale``.
+    Cached; the cache holds one variant at a time (float64 gradients of the Large width are megabytes per case)."""
+    key = (case.tag, variant, xfam, dyfam)
+    got = _floor_bwd_cache.get(key)
+    if got is None:
+        for old in [q for q in _floor_bwd_cache if q[1] != variant]:
+            del _floor_bwd_cache[old]
+        cfg = VARIANTS[variant]
+        inp, dy = make_inputs(case, cfg, xfam), make_dy(case, cfg, dyfam)
+        dx64, res, g64 = reference_bwd(case, variant, torch.float64, inp, dy)
+        got = {"inp": inp, "dy": dy, "residual": res is not None, "dx64": dx64, "g64": g64,
+               "finite": all(bool(torch.isfinite(v).all()) for v in list(dx64.values()) + list(g64.values())),
+               "scale": max(float(v.abs().max()) for v in g64.values()), "rule": {}, "floor_db": {}, "floor_x3_db": None}
+        if float(dy.abs().max()) == 0.0:
+            got["rule"] = {n: "zero" for n in list(dx64) + list(g64)}
+            got["floor_db"] = {n: None for n in got["rule"]}
+        else:
+            dx32, _, g32 = reference_bwd(case, variant, torch.float32, inp, dy)
+            got["g32_max"] = {n: float(v.abs().max()) for n, v in g32.items()}
+            for n, v in list(dx32.items()) + list(g32.items()):
+                small = n in g64 and (n.endswith(STRUCTURAL_ZERO) or float(g64[n].abs().max()) <= ZERO_REL * got["scale"])
+                got["rule"][n] = "magnitude" if small else "db"
+                got["floor_db"][n] = None if small else measure_bwd(got, n, v)
+        _floor_bwd_cache[key] = got
+    if want_x3 and got["floor_x3_db"] is None:
+        if all(rule != "db" for rule in got["rule"].values()):
+            got["floor_x3_db"] = {n: None for n in got["rule"]}
+        else:
+            dx3, _, g3 = reference_bwd_x3(case, variant, got["inp"], got["dy"])
+            got["floor_x3_db"] = {n: (measure_bwd(got, n, v) if got["rule"][n] == "db" else None) for n, v in list(dx3.items()) + list(g3.items())}
+    return got
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# backward mutants: the oracle's exact forward with ONE planted defect in the gradient.  Each is a torch.autograd.Function whose backward
+# asks plain autograd for the gradient of the very op (so with the defect off it is bit-identical to the oracle's own backward, checked
+# by the CPU test) and then spoils it the way a kernel would.
+# ----------------------------------------------------------------------------------------------------------------------
+def _grad_of(fn, inputs, dy):
+    """Plain autograd of ``fn`` at ``inputs`` (detached) for the output gradient ``dy``."""
+    with torch.enable_grad():
+        leaves = [a.detach().requires_grad_(True) for a in inputs]
+        return torch.autograd.grad(fn(*leaves), leaves, dy)
+
+
+class _LNBwd(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, b, drop_term, eps_bwd):
+        ctx.save_for_backward(x, w, b)
+        ctx.defect = (drop_term, eps_bwd)
+        return TF.layer_norm(x, (w.shape[0],), w, b, 1e-5)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, b = ctx.saved_tensors
+        drop_term, eps = ctx.defect
+        dx, dw, db = _grad_of(lambda x_, w_, b_: TF.layer_norm(x_, (w.shape[0],), w_, b_, eps), (x, w, b), dy)
+        if drop_term:                                                 # dx = rstd (g - mean(g) - xhat mean(g xhat)), g = dy w: the last term is lost
+            xc = x - x.mean(-1, keepdim=True)
+            rstd = torch.rsqrt(xc.pow(2).mean(-1, keepdim=True) + 1e-5)
+            xhat = xc * rstd
+            dx = dx + rstd * xhat * (dy * w * xhat).mean(-1, keepdim=True)
+        return dx, dw, db, None, None
+
+
+def _ln_bwd(drop_term=False, eps_bwd=1e-5):
+    return lambda sd, p, x: _LNBwd.apply(x, sd[p + ".weight"], sd[p + ".bias"], drop_term, eps_bwd)
+
+
+class _SoftmaxBwd(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, s, dim, no_rowsum):
+        ctx.save_for_backward(s)
+        ctx.dim, ctx.no_rowsum = dim, no_rowsum
+        return torch.softmax(s, dim=dim)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (s,) = ctx.saved_tensors
+        (ds,) = _grad_of(lambda s_: torch.softmax(s_, dim=ctx.dim), (s,), dy)
+        if ctx.no_rowsum:                                             # ds = p (dy - sum(dy p)): the row sum is not subtracted
+            p = torch.softmax(s, dim=ctx.dim)
+            ds = ds + p * (dy * p).sum(ctx.dim, keepdim=True)
+        return ds, None, None
+
+
+def _softmax_bwd(no_rowsum=False):
+    return lambda s, dim=-1: _SoftmaxBwd.apply(s, dim, no_rowsum)
+
+
+class _BNBwd(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, b, rm, rv, training, const_stats):
+        ctx.save_for_backward(x, w, b, rm.clone(), rv.clone())
+        ctx.training, ctx.const_stats = training, const_stats
+        return TF.batch_norm(x, rm, rv, w, b, training, 0.1, 1e-5)   # (train mode: updates rm / rv in place, as the oracle's call does)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, b, rm, rv = ctx.saved_tensors
+        dx, dw, db = _grad_of(lambda x_, w_, b_: TF.batch_norm(x_, rm.clone(), rv.clone(), w_, b_, ctx.training, 0.1, 1e-5), (x, w, b), dy)
+        if ctx.const_stats and ctx.training:                          # batch mean and variance taken as constants: dx = dy w rstd
+            dims = [d for d in range(x.dim()) if d != 1]
+            rstd = torch.rsqrt(x.var(dims, unbiased=False, keepdim=True) + 1e-5)
+            dx = dy * w.view(1, -1, *([1] * (x.dim() - 2))) * rstd
+        return dx, dw, db, None, None, None, None
+
+
+def _bn_bwd(const_stats=False):
+    return lambda sd, p, x: _BNBwd.apply(x, sd[p + ".weight"], sd[p + ".bias"], sd[p + ".running_mean"], sd[p + ".running_var"],
+                                         orc.BN_TRAINING, const_stats)
+
+
+class _DW3Bwd(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, b, halo_lost):
+        ctx.save_for_backward(x, w, b)
+        ctx.halo_lost = halo_lost
+        return TF.conv1d(x, w, b, padding=1, groups=x.shape[1])
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, b = ctx.saved_tensors
+        dx, dw, db = _grad_of(lambda x_, w_, b_: TF.conv1d(x_, w_, b_, padding=1, groups=x.shape[1]), (x, w, b), dy)
+        if ctx.halo_lost and x.shape[-1] > 128:                       # y[128] = w0 x[127] + ...: frame 127 of sequence 0 loses dy[128] w0
+            dx = dx.clone()
+            dx[0, :, 127] -= w[:, 0, 0] * dy[0, :, 128]
+        return dx, dw, db, None
+
+
+def _dw3_bwd(halo_lost=False):
+    def conv1d(x, w, b=None, stride=1, padding=0, dilation=1, groups=1):
+        if groups == x.shape[1] and groups > 1 and w.shape[-1] == 3 and b is not None and stride == 1 and padding == 1:   # GCFN's 3-tap depthwise
+            return _DW3Bwd.apply(x, w, b, halo_lost)
+        return TF.conv1d(x, w, b, stride=stride, padding=padding, dilation=dilation, groups=groups)
+    return conv1d
+
+
+class _UpBwd(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, size, last_lost):
+        ctx.save_for_backward(x)
+        ctx.size, ctx.last_lost = size, last_lost
+        return TF.interpolate(x, size=size, mode="nearest")
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        (dx,) = _grad_of(lambda x_: TF.interpolate(x_, size=ctx.size, mode="nearest"), (x,), dy)
+        fac = ctx.size // x.shape[-1]
+        if ctx.last_lost and fac > 1 and fac * x.shape[-1] == ctx.size:   # dx[i] = sum of dy over i's fac frames: the last one is left out
+            dx = dx - dy[..., fac - 1::fac]
+        return dx, None, None
+
+
+def _up_bwd(last_lost=False):
+    return lambda x, size=None, mode="nearest": _UpBwd.apply(x, size, last_lost)
+
+
+class _PoolBwd(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, out_len, wrong_count):
+        ctx.save_for_backward(x)
+        ctx.out_len, ctx.wrong_count = out_len, wrong_count
+        return TF.adaptive_avg_pool1d(x, out_len)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        (dx,) = _grad_of(lambda x_: TF.adaptive_avg_pool1d(x_, ctx.out_len), (x,), dy)
+        if ctx.wrong_count:                                           # the last window hands dy / (fac + 1) to its frames
+            fac = x.shape[-1] // ctx.out_len
+            dx = dx.clone()
+            dx[..., x.shape[-1] - fac:] *= fac / (fac + 1.0)
+        return dx, None, None
+
+
+def _pool_bwd(wrong_count=False):
+    return lambda x, out_len: _PoolBwd.apply(x, out_len, wrong_count)
+
+
+class _PosKBwd(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, w, t, maxlen, drop_clamped):
+        pos = torch.arange(0, t).long()
+        raw = pos[:, None] - pos[None, :]
+        ctx.save_for_backward(w)
+        ctx.idx = raw.clamp(-maxlen, maxlen - 1) + maxlen
+        ctx.inside = ((raw >= -maxlen) & (raw <= maxlen - 1)) if drop_clamped else None
+        return TF.embedding(ctx.idx, w)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (w,) = ctx.saved_tensors
+        if ctx.inside is not None:                                    # pairs beyond the clamp are dropped instead of adding into the edge rows
+            dy = dy * ctx.inside[..., None].to(dy.dtype)
+        (dw,) = _grad_of(lambda w_: TF.embedding(ctx.idx, w_), (w,), dy)
+        return dw, None, None, None
+
+
+def _pos_k_bwd(drop_clamped=False):
+    return lambda sd, t, maxlen: _PosKBwd.apply(sd[PE_K], t, maxlen, drop_clamped)
+
+
+class _LinBwd(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, b, last_row_lost):
+        ctx.save_for_backward(x, w, b)
+        ctx.last_row_lost = last_row_lost
+        return TF.linear(x, w, b)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, b = ctx.saved_tensors
+        dx, dw, db = _grad_of(TF.linear, (x, w, b), dy)
+        if ctx.last_row_lost:                                         # the weight gradient leaves out the last row of the flattened batch
+            dw = dw - torch.outer(dy.reshape(-1, dy.shape[-1])[-1], x.reshape(-1, x.shape[-1])[-1])
+        return dx, dw, db, None
+
+
+def _lin_bwd(last_row_lost=False):
+    return lambda sd, p, x: _LinBwd.apply(x, sd[p + ".weight"], sd[p + ".bias"], last_row_lost)
+
+
+_ATTN = {"ega_train", "spkattn_train"}
+_LN_KINDS = {"gcfn_train", "cla_train", "ega_train", "spkattn_train"}
+
+
+def bwd_mutants() -> Dict[str, dict]:
+    """name -> {"ctx": () -> context that plants the defect, "off": the same Function with the defect off, "kinds": the kinds it can touch}."""
+    tf = lambda **kw: patched(TF=_Proxy(TF, **kw))                     # noqa: E731
+    return {
+        "ln_bwd_xhat_term_lost": {"ctx": lambda: patched(_ln=_ln_bwd(drop_term=True)), "off": lambda: patched(_ln=_ln_bwd()), "kinds": _LN_KINDS},
+        "ln_bwd_eps_1e-6": {"ctx": lambda: patched(_ln=_ln_bwd(eps_bwd=1e-6)), "off": lambda: patched(_ln=_ln_bwd()), "kinds": _LN_KINDS},
+        "softmax_bwd_no_rowsum": {"ctx": lambda: patched(torch=_Proxy(torch, softmax=_softmax_bwd(True))),
+                                  "off": lambda: patched(torch=_Proxy(torch, softmax=_softmax_bwd())), "kinds": _ATTN},
+        "bn_bwd_stats_constant": {"ctx": lambda: patched(_bn_eval=_bn_bwd(True)), "off": lambda: patched(_bn_eval=_bn_bwd()),
+                                  "kinds": {"cla_train", "down_train"}},
+        "dwconv_bwd_halo_lost": {"ctx": lambda: tf(conv1d=_dw3_bwd(True)), "off": lambda: tf(conv1d=_dw3_bwd()), "kinds": {"gcfn_train"}},
+        "upsample_bwd_last_lost": {"ctx": lambda: tf(interpolate=_up_bwd(True)), "off": lambda: tf(interpolate=_up_bwd()),
+                                   "kinds": {"ega_train", "fuse"}},
+        "avgpool_bwd_wrong_count": {"ctx": lambda: tf(adaptive_avg_pool1d=_pool_bwd(True)), "off": lambda: tf(adaptive_avg_pool1d=_pool_bwd()),
+                                    "kinds": {"ega_train"}},
+        "pe_k_grad_clamped_dropped": {"ctx": lambda: patched(rel_pos_k=_pos_k_bwd(True)), "off": lambda: patched(rel_pos_k=_pos_k_bwd()),
+                                      "kinds": {"ega_train"}},
+        "wgrad_last_row_lost": {"ctx": lambda: patched(_lin=_lin_bwd(True)), "off": lambda: patched(_lin=_lin_bwd()), "kinds": _LN_KINDS},
     }
