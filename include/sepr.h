@@ -506,6 +506,37 @@ int sepr_dynmix_reverb_fwd(const short* buf16, long long total16, const float* b
                            const int* term_taps, const int* n, int B, int M, int S, int Tmax, float* mix, float* const* src, const float* rir,
                            long long rir_total, const long long* rir_off, int R, sepr_stream_t stream);
 
+/* ---- room impulse responses by the image-source method (a new entry, no struct change: ABI 4.13) -------
+ * sepr_rir_ism_fwd simulates R impulse responses of N samples, one per shoebox room, in one call.  The definition is independent of the
+ * order of summation and bit-reproducible in numpy (tests/rirsim_ref.py):
+ *   constants   HW = 40 (a pulse has TW = 2 HW + 1 = 81 taps), Q = 32 fractional steps, FB = 48 fixed-point fraction bits,
+ *               FOURPI = float64(4 pi).
+ *   lut         [Q + 1][TW] float64 (DEVICE), built by the host: lut[k][j] = sinc(x) 0.5 (1 + cos(pi x / (HW + 1))), x = (j - HW) - k / Q,
+ *               zero for |x| > HW + 1.  The entry reads the table it is given; it does not compute one.
+ *   rooms       [R][10] float64 (DEVICE): Lx Ly Lz sx sy sz mx my mz beta - the room, an omnidirectional source s and microphone m, one
+ *               reflection coefficient beta in [0, 1) for all six walls.  fsc = fs / c (samples per metre), computed by the caller.
+ *   images      per axis, for an integer k and a parity p in {0, 1}: offset = fl(fl(k (2 L)) + c_p) with c_0 = fl(s - m), c_1 = -fl(s + m)
+ *               (the image 2 k L + (1 - 2 p) s seen from m, written so that exchanging s and m negates or keeps every offset exactly), and
+ *               n = |2 k - p| reflections.
+ *   per image   float64, every operation rounded separately (no contraction): d = sqrt((dx dx + dy dy) + dz dz), tau = d fsc,
+ *               i0 = floor(tau), a = bpow[nx + ny + nz] / (FOURPI d) with bpow[0] = 1, bpow[n] = bpow[n - 1] beta (a sequential product).
+ *               The image belongs to the response iff i0 - HW <= N - 1.
+ *   taps        for j = 0 .. TW - 1 and t = i0 - HW + j in [0, N): f = tau - i0, k = floor(f Q), w = f Q - k,
+ *               v = lut[k][j] + w (lut[k + 1][j] - lut[k][j]); the tap adds the INTEGER rint((a v) 2^48) (half to even) to acc[r][t].
+ *   output      acc [R][N] int64 (DEVICE, the caller's workspace, zeroed by the entry and left holding the sums); h = acc / 2^48 (exact);
+ *               rir [R][N] float32 (DEVICE) = float32(h / max|h_r|) with normalise = 1 (an all-zero response stays zero), float32(h) with
+ *               normalise = 0; peak_idx [R] int32 (DEVICE) = the first index of the maximum of |h_r|.
+ * Integer addition commutes, so the kernel's decomposition (tiles of 256 samples, 8 column splits per tile, 64-bit LDS and global atomic adds)
+ * does not show in the result: two calls give equal bits.  SEPR_EINVAL before any HIP call: a null pointer, R outside 1 .. 65535, N outside
+ * 1 .. 16384, normalise other than 0 or 1, fsc not positive and finite, sqrt(3) (N + HW + 1) / fsc / 1.5 + 3 >= 1024 (the table of powers of
+ * beta, bounded for the smallest room dimension the contract allows, 1.5 m), rooms, lut or acc not 8-byte aligned, rir or peak_idx not 4-byte
+ * aligned.  What the entry cannot see - the rooms are device memory - is the caller's to check (reverb.validate_rooms: every dimension
+ * >= 1.5 m, source and microphone >= 0.1 m from every wall and from each other, 0 <= beta < 1); the kernel clamps the room sizes to
+ * [1.5, 1e6], the positions into the room, beta to [0, 1] and every derived index, so a bad table gives wrong samples and bounded work but
+ * never an access outside acc, rir, lut or its LDS arrays.  No host synchronisation or allocation (capturable). */
+int sepr_rir_ism_fwd(const double* rooms, int R, int N, double fsc, const double* lut, long long* acc, float* rir, int* peak_idx, int normalise,
+                     sepr_stream_t stream);
+
 /* ================================================================================================================= */
 /* Training path: train-mode forward twins that keep what the backward needs, and the       */
 /* backward of every block.  The reference trains through torch.autograd over the same modules (engine.py:50-83:     */

@@ -601,13 +601,16 @@ class DynamicMixFeed:
     feed's ``random.Random(seed)`` before each epoch (the same generator then makes the examples' draws).  ``rank`` / ``world``:
     this rank's contiguous shard of the key order (``dist.shard_range``).  A trailing partial batch is dropped.
     ``fixed_length``: every row is ``max_len`` samples, shorter examples zero-padded - constant shapes, which a
-    ``CapturedTrainStep`` needs; ``next_into(x, targets)`` then writes the next batch straight into the step's static tensors."""
+    ``CapturedTrainStep`` needs; ``next_into(x, targets)`` then writes the next batch straight into the step's static tensors.
+    ``rooms`` (a ``reverb.RoomSampler``, with ``rirs=RirBank.simulate(...)``): every ``rooms_every``-th epoch, the first included, begins by
+    re-simulating the bank in place from ``rooms.draw(len(rirs), seed=(seed, epoch))``, so an utterance does not meet
+    the same room in every epoch; ``rooms=None`` changes nothing."""
 
     SLOTS = 4               # pinned staging buffers in flight
 
     def __init__(self, corpus: Corpus, planner: Callable[..., Example], batch: int, max_len: int, seed: int = 0,
                  keys: Optional[Sequence[str]] = None, fixed_length: bool = False, rank: int = 0, world: int = 1,
-                 rirs: Optional[RirBank] = None):
+                 rirs: Optional[RirBank] = None, rooms=None, rooms_every: int = 1):
         if corpus.device is None:
             raise RuntimeError("DynamicMixFeed needs a corpus on the HIP device (there is no CPU path)")
         if rirs is not None and not _same_device(rirs.device, corpus.device):
@@ -620,6 +623,14 @@ class DynamicMixFeed:
         shard_range(1, rank, world)                     # validates rank / world
         self.corpus, self.planner, self.batch, self.max_len = corpus, planner, int(batch), int(max_len)
         self.fixed_length, self.rank, self.world, self.rirs = bool(fixed_length), rank, world, rirs
+        if rooms is not None:
+            if rirs is None or getattr(rirs, "_sim", None) is None:
+                raise ValueError("rooms= redraws a simulated bank: pass rirs=RirBank.simulate(...)")
+            if int(rooms_every) < 1:
+                raise ValueError("rooms_every >= 1")
+            if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or int(seed) < 0:
+                raise ValueError("rooms= needs a non-negative integer seed (the rooms of an epoch are drawn from (seed, epoch))")
+        self.rooms, self.rooms_every, self.seed, self.epoch = rooms, int(rooms_every), seed, 0
         self.rng = random.Random(seed)
         self.keys = None if keys is None else list(keys)
         self._default_keys = list(next(iter(corpus.roles.values()))) if corpus.roles else None
@@ -644,8 +655,17 @@ class DynamicMixFeed:
         lo, hi = shard_range(len(order), self.rank, self.world)
         return order[lo:hi]
 
+    def _begin_epoch(self) -> None:
+        """With ``rooms=``: before the first plan of every ``rooms_every``-th epoch the bank is re-simulated in place from
+        ``rooms.draw(len(bank), seed=(seed, epoch))`` - numpy's generator, so the planners' ``random.Random`` makes the draws it would make
+        without ``rooms``.  The epoch's plans then read the new ``_direct``; the launches of the epoch before are already queued."""
+        epoch, self.epoch = self.epoch, self.epoch + 1
+        if self.rooms is not None and epoch % self.rooms_every == 0:
+            self.rirs.resimulate(self.rooms.draw(len(self.rirs), seed=(int(self.seed), epoch)))
+
     def plans(self) -> Iterator[BatchPlan]:
-        """The batch plans of one epoch (host only)."""
+        """The batch plans of one epoch (host only - except with ``rooms=``, where the epoch begins by simulating its rooms on the device)."""
+        self._begin_epoch()
         order = self.epoch_order()
         for i in range(0, len(order) - self.batch + 1, self.batch):
             yield collate_plan(self.corpus, [self.planner(self.corpus, self.rng, k, self.max_len) for k in order[i:i + self.batch]], self.rirs)

@@ -20,11 +20,17 @@ plain WHAMR-form launch (5 terms) against the reverberant form (3 mixture terms,
 direct-path targets) at RT60 = 0.3, 0.6 and 1.0 s, B = 16 and 32 x 4 s; and the bf16 training step fed plainly and fed with
 reverberation from COUNT synthetic responses of RT60 seconds; the plainly fed step of that same run is the yardstick.
 
+``--room-rirs 64:0.2:0.6`` measures simulating a bank of shoebox rooms on the device instead (section 5e-4), in one child process: the
+hipEvent time of one ``sepr_rir_ism_fwd`` call for COUNT rooms, the numpy restatement's CPU time for one room, the realised decay of a few
+responses beside the nominal RT60, and the bf16 training step fed from a fixed simulated bank against the same feed re-simulating its
+rooms every epoch (three steps here), alternating.  Condition: one simulation takes less than one training step of the same run.
+
 Every step runs in a child process of its own under ``timeout -k 10 <s>``; the first step that fails ends the run.
 
     python tools/dynmix_bench.py [--out profiles/dynmix_timing.json]
     python tools/dynmix_bench.py --speeds 95:105 [--out profiles/dynmix_speed.json]
     python tools/dynmix_bench.py --rirs 64:0.6 [--out profiles/dynmix_reverb.json]
+    python tools/dynmix_bench.py --room-rirs 64:0.2:0.6 [--out profiles/rir_ism.json]
 """
 import argparse
 import json
@@ -360,6 +366,120 @@ def step_reverb(spec):
                      "host_plan_ms_per_batch": plan_ms}}
 
 
+def step_rooms(spec):
+    """Simulating a bank of shoebox rooms on the device (section 5e-4): hipEvent time of one ``sepr_rir_ism_fwd`` call for COUNT rooms,
+    the numpy restatement's CPU time for ONE of them (and that the two agree exactly), the realised decay of a few responses beside the
+    nominal rt60, and the bf16 training step fed from a fixed simulated bank against the same feed with ``rooms_every=1``, alternating."""
+    import functools
+    import numpy as np
+    import torch
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import rirsim_ref
+    from sepreformer_amd import datafeed as df
+    from sepreformer_amd import lib as L_
+    from sepreformer_amd.config import VARIANTS
+    from sepreformer_amd.criterion import PIT_SISNR_mag, PIT_SISNR_time
+    from sepreformer_amd.model import Model
+    from sepreformer_amd.optim import FlatAdamW
+    from sepreformer_amd.reverb import RirBank, RoomSampler, parse_rooms, schroeder_rt60
+    from sepreformer_amd.train_step import CapturedTrainStep
+    count, rt_lo, rt_hi = parse_rooms(spec)
+    dev = torch.device("cuda:0")
+    sampler = RoomSampler(rt60=(rt_lo, rt_hi))
+    rooms = sampler.draw(count, seed=0)
+    bank = RirBank.simulate(rooms, FS, device=dev)
+    N, sim = int(bank.lengths[0]), bank._sim
+    lib = L_.load()
+    ms = []
+    for i in range(5 + 20):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        L_.check(lib.sepr_rir_ism_fwd(sim["rooms"].data_ptr(), count, N, sim["fsc"], sim["lut"].data_ptr(), sim["acc"].data_ptr(), bank.buf.data_ptr(),
+                                      sim["out"].data_ptr() + 4 * count * N, sim["normalise"], torch.cuda.current_stream().cuda_stream), "sepr_rir_ism_fwd")
+        e1.record()
+        torch.cuda.synchronize()
+        if i >= 5:
+            ms.append(e0.elapsed_time(e1))
+    wall = []
+    for i in range(5):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        bank.resimulate(sampler.draw(count, seed=(0, i)))
+        wall.append((time.perf_counter() - t0) * 1e3)
+    bank.resimulate(rooms)
+    t0 = time.perf_counter()
+    acc0, images0 = rirsim_ref.ism_acc(np.asarray(rooms[0]), sim["fsc"], N)
+    cpu_s = time.perf_counter() - t0
+    exact = bool(np.array_equal(sim["acc"][0].cpu().numpy(), acc0))
+    # realised decay: a few rooms simulated long enough for the -25 dB point, whatever their rt60
+    few = min(count, 6)
+    long_n = min(16384, int(np.ceil(2.5 * FS * rt_hi)))
+    longer = RirBank.simulate(rooms[:few], FS, length=long_n, device=dev, normalise=None)
+    decay = [{"room_m": [round(float(v), 3) for v in rooms[r, :3]], "beta": float(rooms[r, 9]), "nominal_rt60_s": float(rooms.rt60[r]),
+              "schroeder_T20_s": schroeder_rt60(longer.rir(r), FS), "peak_idx": int(longer.peak_idx[r])} for r in range(few)]
+    del longer
+
+    keys, arrays = synth_corpus_arrays()
+    corpus = df.Corpus.from_arrays(arrays, device=dev, fs=FS)
+    corpus.roles = {r: list(keys) for r in ROLES}
+    B = 16
+    cfg = VARIANTS["SepReformer_Base_WSJ0"]
+    torch.manual_seed(0)
+    model = Model.from_config(cfg, init_seed=0, precision="bf16").load_synthetic_(0).to(dev).train()
+    crit_t = PIT_SISNR_time(dev, cfg.num_spks, True)
+    crit_m = PIT_SISNR_mag(dev, 512, 128, "hann", cfg.num_stages, cfg.num_spks, True, False)
+    sizes = torch.full((B,), T4S)
+    opt = FlatAdamW(model, lr=1.0e-4, weight_decay=1.0e-2)
+
+    def loss_fn(audio, aux, *tg):
+        tg = list(tg)
+        l_time = crit_t(estims=audio, input_sizes=sizes, target_attr=tg)
+        l_mag = [crit_m(estims=a, idx=i, input_sizes=sizes, target_attr=tg) for i, a in enumerate(aux)]
+        return (0.6 * l_time + 0.4 * sum(l_mag) / len(l_mag)) / cfg.num_spks
+
+    redrawn = RirBank.simulate(rooms, FS, device=dev)
+    feeds = {"fixed": df.DynamicMixFeed(corpus, functools.partial(df.plan_whamr, rirs=bank), batch=B, max_len=T4S, seed=0, fixed_length=True, rirs=bank),
+             "rooms": df.DynamicMixFeed(corpus, functools.partial(df.plan_whamr, rirs=redrawn), batch=B, max_len=T4S, seed=0, fixed_length=True,
+                                        rirs=redrawn, rooms=sampler, rooms_every=1)}
+    x = torch.zeros(B, T4S, device=dev)
+    tg = [torch.zeros(B, T4S, device=dev) for _ in range(2)]
+    feeds["fixed"].next_into(x, tg)
+    step = CapturedTrainStep(model, loss_fn, opt, x, tg, max_norm=5.0, warmup=2)
+
+    def loop(feed):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(LOOP_STEPS):
+            feed.next_into(step.x, step.targets)
+            loss, _ = step(step.x, step.targets)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / LOOP_STEPS, float(loss.detach())
+
+    for f in feeds.values():
+        loop(f)                                                               # warm both paths
+    runs = {name: [] for name in feeds}
+    losses = []
+    for _ in range(LOOP_RUNS):
+        for name, f in feeds.items():
+            e_before = f.epoch
+            ms_step, ls = loop(f)
+            runs[name].append(ms_step)
+            losses.append(ls)
+            if name == "rooms":
+                epochs_per_run = f.epoch - e_before
+    step.release()
+    assert all(np.isfinite(v) for v in losses)
+    return {"device": torch.cuda.get_device_name(0),
+            "rooms": {"count": count, "rt60_nominal": [rt_lo, rt_hi], "samples": N, "fs": FS, "sampler": "RoomSampler defaults",
+                      "images_room0": images0},
+            "simulate": {"device_ms": _stats(ms), "launches": 20, "resimulate_wall_ms": _stats(wall),
+                         "restatement_cpu_s_one_room": cpu_s, "restatement_equals_device_sums": exact},
+            "decay": decay,
+            "loop": {"model": "SepReformer_Base_WSJ0 bf16, batch 16 x 4 s, CapturedTrainStep + FlatAdamW, the reference's loss, fed in the WHAMR form "
+                              "from a simulated bank", "steps_per_run": LOOP_STEPS, "steps_per_epoch": NKEYS // B,
+                     "resimulations_per_run_rooms": epochs_per_run, "fixed_ms_per_step": runs["fixed"], "rooms_ms_per_step": runs["rooms"]}}
+
+
 def step_host():
     """The reference's per-example work in numpy from RAM-resident arrays (no disk, no decoding of a file): WHAMR form."""
     from concurrent.futures import ThreadPoolExecutor
@@ -411,17 +531,19 @@ def main():
     ap.add_argument("--step", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--speeds", default=None, metavar="LO:HI", help="measure speed perturbation (an inclusive range or a comma list of percentages)")
     ap.add_argument("--rirs", default=None, metavar="COUNT:RT60", help="measure reverberation by convolution (COUNT synthetic impulse responses of RT60 s)")
+    ap.add_argument("--room-rirs", default=None, metavar="COUNT[:RT60LO:RT60HI]", help="measure simulating COUNT shoebox rooms on the device (image-source method)")
     args = ap.parse_args()
-    if args.speeds and args.rirs:
-        ap.error("--speeds and --rirs are measured in runs of their own")
+    if sum(bool(v) for v in (args.speeds, args.rirs, args.room_rirs)) > 1:
+        ap.error("--speeds, --rirs and --room-rirs are measured in runs of their own")
     if args.step:
-        rec = {"device": step_device, "host": step_host, "speed": lambda: step_speed(args.speeds), "reverb": lambda: step_reverb(args.rirs)}[args.step]()
+        rec = {"device": step_device, "host": step_host, "speed": lambda: step_speed(args.speeds), "reverb": lambda: step_reverb(args.rirs),
+               "rooms": lambda: step_rooms(args.room_rirs)}[args.step]()
         print("__RESULT__" + json.dumps(rec))
         return
     rec, failed = {}, None
-    for name, limit in ([("speed", 600)] if args.speeds else [("reverb", 600)] if args.rirs else STEPS):
+    for name, limit in ([("speed", 600)] if args.speeds else [("reverb", 600)] if args.rirs else [("rooms", 600)] if args.room_rirs else STEPS):
         cmd = (["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", name] + (["--speeds", args.speeds] if args.speeds else [])
-               + (["--rirs", args.rirs] if args.rirs else []))
+               + (["--rirs", args.rirs] if args.rirs else []) + (["--room-rirs", args.room_rirs] if args.room_rirs else []))
         r = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
         lines = [ln for ln in r.stdout.splitlines() if ln.startswith("__RESULT__")]
         if r.returncode != 0 or not lines:
@@ -450,6 +572,14 @@ def main():
                           "plain_step_ms_mean": mean(a), "reverb_step_ms_mean": mean(b), "difference_ms": mean(b) - mean(a),
                           "plain_step_spread_ms": max(a) - min(a), "reverb_step_spread_ms": max(b) - min(b),
                           "reverb_exceeds_plain_by_more_than_the_larger_spread": mean(b) - mean(a) > spread}
+    elif not failed and args.room_rirs:
+        lp = rec["loop"]
+        a, b = lp["fixed_ms_per_step"], lp["rooms_ms_per_step"]
+        mean = lambda v: sum(v) / len(v)                                    # noqa: E731
+        sim_ms = rec["simulate"]["device_ms"]["median"]
+        rec["summary"] = {"simulate_ms_median": sim_ms, "fixed_step_ms_mean": mean(a), "rooms_step_ms_mean": mean(b), "difference_ms": mean(b) - mean(a),
+                          "fixed_step_spread_ms": max(a) - min(a), "rooms_step_spread_ms": max(b) - min(b),
+                          "condition_one_simulation_under_one_step": {"simulate_ms": sim_ms, "step_ms": mean(a), "met": sim_ms < mean(a)}}
     elif not failed:
         lp = rec["loop"]
         fixed, fed = lp["fixed_ms_per_step"], lp["fed_ms_per_step"]

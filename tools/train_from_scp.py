@@ -8,6 +8,7 @@ loss and utt/s every ``--log`` steps.  Schedulers, checkpoints and validation ar
     python tools/train_from_scp.py --form wsj0 --scp s1=tr_s1.scp s2=tr_s2.scp --speeds 95:105      # speed perturbation (section 5e-2)
     python tools/train_from_scp.py --form whamr --scp s1=.. s2=.. noise=.. --rir-scp rirs.scp        # reverberation in the launch (section 5e-3)
     python tools/train_from_scp.py --form whamr --scp s1=.. s2=.. noise=.. --synthetic-rirs 64:0.2:0.8
+    python tools/train_from_scp.py --form whamr --scp s1=.. s2=.. noise=.. --room-rirs 64:0.2:0.6     # simulated rooms, redrawn per epoch (section 5e-4)
 """
 import argparse
 import os
@@ -35,6 +36,10 @@ def main():
                      "source and example and convolved inside the mixing launch (with --form whamr the *_reverb roles are then not needed)")
     rir.add_argument("--synthetic-rirs", default=None, metavar="COUNT:RT60LO:RT60HI", help="reverberation from COUNT synthetic impulse responses "
                      "with RT60 drawn from [RT60LO, RT60HI] seconds (sepreformer_amd.reverb.synthetic_rirs)")
+    rir.add_argument("--room-rirs", default=None, metavar="COUNT[:RT60LO:RT60HI]", help="reverberation from COUNT shoebox rooms simulated on the device by the "
+                     "image-source method (sepreformer_amd.reverb.RoomSampler; nominal RT60 drawn from [RT60LO, RT60HI] seconds, default 0.2:0.6), "
+                     "re-simulated every --rooms-every epochs")
+    ap.add_argument("--rooms-every", type=int, default=1, help="with --room-rirs: redraw the rooms at the start of every N-th epoch (default 1)")
     ap.add_argument("--reverb-target", choices=["direct", "dry", "full"], default="direct", help="the targets under reverberation: the direct "
                     "path of the same impulse response (default), the dry source, or the whole response")
     ap.add_argument("--steps", type=int, default=100)
@@ -45,11 +50,19 @@ def main():
     args = ap.parse_args()
     if args.speeds and args.form == "direct":
         ap.error("--speeds needs dynamic mixing (--form wsj0, wham or whamr)")
-    reverb = args.rir_scp or args.synthetic_rirs
+    reverb = args.rir_scp or args.synthetic_rirs or args.room_rirs
     if reverb and args.form == "direct":
-        ap.error("--rir-scp / --synthetic-rirs need dynamic mixing (--form wsj0, wham or whamr)")
+        ap.error("--rir-scp / --synthetic-rirs / --room-rirs need dynamic mixing (--form wsj0, wham or whamr)")
     if reverb and args.speeds:
-        ap.error("--speeds together with --rir-scp / --synthetic-rirs is not built: pass one of them")
+        ap.error("--speeds together with --rir-scp / --synthetic-rirs / --room-rirs is not built: pass one of them")
+    if args.room_rirs:
+        from sepreformer_amd.reverb import parse_rooms
+        try:
+            room_spec = parse_rooms(args.room_rirs)
+        except ValueError as e:
+            ap.error(f"--room-rirs: {e}")
+        if args.rooms_every < 1:
+            ap.error("--rooms-every >= 1")
     if args.synthetic_rirs:
         from sepreformer_amd.reverb import parse_synthetic
         try:
@@ -73,16 +86,20 @@ def main():
     planner = {"wsj0": df.plan_wsj0, "wham": df.plan_wham, "whamr": df.plan_whamr, "direct": df.plan_direct}[args.form]
     if args.speeds:
         planner = functools.partial(planner, speeds=df.parse_speeds(args.speeds))
-    bank = None
+    bank = sampler = None
     if reverb:
-        from sepreformer_amd.reverb import RirBank, synthetic_rirs
+        from sepreformer_amd.reverb import RirBank, RoomSampler, synthetic_rirs
         if args.rir_scp:
             bank = RirBank.from_scp(args.rir_scp, fs=args.fs, device=dev, resample=args.resample)
+        elif args.room_rirs:
+            sampler = RoomSampler(rt60=room_spec[1:])
+            bank = RirBank.simulate(sampler.draw(room_spec[0], seed=(args.seed, 0)), args.fs, device=dev)      # the feed redraws it per epoch
         else:
             bank = RirBank.from_arrays(synthetic_rirs(synth[0], args.fs, rt60=synth[1:], seed=args.seed), args.fs, device=dev)
         planner = functools.partial(planner, rirs=bank, target=args.reverb_target)
         print(f"RIR bank: {len(bank)} impulse responses, {int(bank.lengths.min())} .. {int(bank.lengths.max())} samples", flush=True)
-    feed = df.DynamicMixFeed(corpus, planner, batch=args.batch, max_len=args.max_len, seed=args.seed, fixed_length=True, rirs=bank)
+    feed = df.DynamicMixFeed(corpus, planner, batch=args.batch, max_len=args.max_len, seed=args.seed, fixed_length=True, rirs=bank,
+                              rooms=sampler, rooms_every=args.rooms_every)
     print(f"corpus: {len(corpus)} utterances, {corpus.total16 * 2 + corpus.total32 * 4} bytes on {dev}", flush=True)
 
     cfg = VARIANTS[args.model]
