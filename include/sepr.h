@@ -201,6 +201,8 @@ enum { SEPR_KNOB_X3_WIDE = 0 /* 0 / 1 (default) / 2: sepr_gemm_x3.hip */, SEPR_K
        SEPR_KNOB_TN16 /* default 1: weight-gradient contractions of two bf16 operands on the LDS-DMA + transposing-read kernel */,
        SEPR_KNOB_GB_FUSE /* default 1 (SEPR_GB_FUSE): sepr_global_block_fwd runs the EGA gate inside the GCFN kernel where that form exists;
                             0 = always the two calls (A/B, bit-identity tests) */,
+       SEPR_KNOB_ATTN_PACK /* default 1 (SEPR_ATTN_PACK): the dk = 16 bf16x3 inference attention runs relattn_x3p_kernel (hi and lo plane of a K /
+                              band row in one K = 32 MFMA fragment, read once); 0 = relattn_x3_kernel (A/B) */,
        SEPR_KNOB_COUNT };
 int sepr_knob(int id);
 void sepr_knobs_reload(void);
