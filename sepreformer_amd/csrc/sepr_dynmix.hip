@@ -7,25 +7,24 @@
 //   energy_part_kernel / energy_finish_kernel   sum of squares per utterance, once at load: int64 for int16 utterances (exact, so
 //                        independent of the order), float64 in a fixed order for float32 utterances; per-workgroup partials and a
 //                        finishing pass, no atomics;
-//   dynmix_kernel        one thread per eight output samples of one example: every term is eight consecutive samples from an
-//                        arbitrary start, read as aligned 16-byte loads from the aligned-down address and realigned in registers
-//                        (v_alignbyte for the odd int16 starts), scaled by two separately rounded multiplies, summed in term
-//                        order; float4 stores of the mixture and the S target rows, zeros from n[b] on.
-//   dynmix_speed_kernel  the same batch with speed perturbation: a term whose term_conv is a converter index
-//                        is the stored utterance passed through that rational-ratio converter (the arithmetic of sepr_resample.hip:
-//                        exact float64 products summed in the order j = 0 .. K - 1, one rounding).  Per workgroup (2048 outputs of
-//                        one example) and perturbed term: the tile's input span is staged in LDS as doubles, zero outside the
-//                        utterance; the outputs are converted one per lane (consecutive lanes = consecutive outputs, so the LDS
-//                        reads and the tap columns are consecutive), written to an LDS tile of floats and read back eight per
-//                        thread into the plain kernel's scaling, summing and storing code.  Terms with term_conv < 0 take the
-//                        plain kernel's loads.
-//   dynmix_reverb_kernel the same batch with reverberation: a term whose term_rir is an index into the RIR bank
-//                        is the stored utterance convolved with the first term_taps samples of that impulse response, exact float64
-//                        products summed in the order j = 0 .. taps - 1, one rounding.  The speed kernel's geometry (2048 outputs of
-//                        one example per workgroup, one output per lane, transposed through the float tile), but a long FIR filter:
-//                        the taps are walked in ascending chunks of 1024, each chunk staging its 3071 input samples as doubles and
-//                        its taps as doubles (in the float tile, which is idle until the end), the float64 accumulators staying in
-//                        registers across the chunks - so the LDS plan does not depend on the length of the impulse response.
+//   dynmix_kernel<S, F>  the mixing skeleton of the plain and the reverberant launch: zero fill from n[b] on, the M terms scaled by two
+//                        separately rounded multiplies and summed in term order, float4 stores of the mixture and the S target rows, a
+//                        target that IS its mixture term (every field of the form equal) stored from the kept values.
+//     F = PlainForm      (sepr_dynmix_fwd) one thread per eight output samples of one example: every term is eight consecutive samples
+//                        from an arbitrary start, read as aligned 16-byte loads from the aligned-down address and realigned in
+//                        registers (v_alignbyte for the odd int16 starts).  No LDS, no barrier, a thread past Tmax or n returns early.
+//     F = ReverbForm     (sepr_dynmix_reverb_fwd) a term whose rir is an index into the RIR bank is the stored
+//                        utterance convolved with the first taps samples of that impulse response, exact float64 products summed in the
+//                        order j = 0 .. taps - 1, one rounding.  2048 outputs of one example per workgroup, one output per lane,
+//                        transposed through a float tile; the taps are walked in ascending chunks of 1024, each staging its 3071 input
+//                        samples and its taps as doubles in LDS, the float64 accumulators staying in registers - so the 32 768-byte LDS
+//                        plan does not depend on the response's length.  It holds barriers: no thread returns early, and n, a term's
+//                        integer fields and the same-term flag are wave-uniform (readfirstlane) before any branch around a barrier.
+//   dynmix_speed_kernel  (sepr_dynmix_speed_fwd, section 5e-2) the same batch with speed perturbation, a kernel of its own (docs/HISTORY.md:
+//                        as an instance of the skeleton it ran 0.8 to 1.1 us longer per launch at B = 16): a term whose term_conv is a converter
+//                        index is the stored utterance through that rational-ratio converter (the arithmetic of sepr_resample.hip).  The
+//                        same tile geometry: input span staged in LDS as doubles, outputs converted one per lane, transposed through an
+//                        LDS tile of floats.  It shares term_value, scale8, store8 and the launcher.
 // Nothing here depends on the launch order of workgroups: results are bit-identical from run to run.
 #include "sepr_common.h"
 
@@ -86,10 +85,19 @@ struct DmCorpus {
   int N16, N;
 };
 
-// (sample * norm) * gain of term j of the example on samples t0 .. t0 + 7.  The table is not trusted: the utterance index, the start
+// (sample * norm) * gain of every form: two roundings, as numpy's `samps *= norm_factor` followed by `gain * samps`
+__device__ __forceinline__ void scale8(const float x[8], float norm, float gain, float v[8]) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const float a = x[i] * norm;
+    v[i] = a * gain;
+  }
+}
+
+// (sample * norm) * gain of the stored term (utt, start) on samples t0 .. t0 + 7.  The table is not trusted: the utterance index, the start
 // and the element position are clamped, so whatever it holds no read leaves the corpus buffers.
 __device__ __forceinline__ void term_value(const DmCorpus& c, int utt, int start, float norm, float gain, int t0, float v[8]) {
-#pragma clang fp contract(off)
   const int u = utt < 0 ? 0 : (utt >= c.N ? c.N - 1 : utt);
   const long long o0 = c.off[u], len = c.off[u + 1] - o0;
   const long long st = clampll(start, 0, len > 0 ? len : 0);
@@ -99,11 +107,7 @@ __device__ __forceinline__ void term_value(const DmCorpus& c, int utt, int start
   } else {
     load8_f32(c.buf32, clampll(o0 - c.off[c.N16] + st + t0, 0, c.total32 - 1), (c.total32 + 3) & ~3LL, x);
   }
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const float a = x[i] * norm;       // two roundings, as numpy's `samps *= norm_factor` followed by `gain * samps`
-    v[i] = a * gain;
-  }
+  scale8(x, norm, gain, v);
 }
 
 __device__ __forceinline__ void store8(float* __restrict__ row, const float v[8], int t0, int n, bool second) {
@@ -114,61 +118,60 @@ __device__ __forceinline__ void store8(float* __restrict__ row, const float v[8]
   if (second) st4(row + 4, make_float4(m[4], m[5], m[6], m[7]));
 }
 
-template <int S>
-__global__ __launch_bounds__(DM_TPB) void dynmix_kernel(DmCorpus c, const int* __restrict__ term_utt, const int* __restrict__ term_start,
-                                                        const float* __restrict__ term_norm, const float* __restrict__ term_gain,
-                                                        const int* __restrict__ nlen, int M, int Tmax, float* __restrict__ mix, DmRows src) {
-#pragma clang fp contract(off)
-  const int b = blockIdx.y;
-  const int t0 = (blockIdx.x * DM_TPB + threadIdx.x) * DM_PER;
-  if (t0 >= Tmax) return;
-  const bool second = t0 + 4 < Tmax;                               // Tmax is a multiple of 4, not of 8
-  int n = nlen[b];
-  n = n < 0 ? 0 : (n > Tmax ? Tmax : n);
-  const long long row = (long long)b * Tmax + t0;
-  float acc[8], keep[S][8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) acc[i] = 0.f;
-  if (t0 >= n) {                                                   // the zero fill of pad_sequence
-    store8(mix + row, acc, t0, n, second);
-#pragma unroll
-    for (int s = 0; s < S; ++s) store8(src.p[s] + row, acc, t0, n, second);
-    return;
-  }
-  const int NT = M + S, j0 = b * NT;
-#pragma unroll
-  for (int m = 0; m < S + 1; ++m) {
-    if (m < M) {
-      float v[8];
-      term_value(c, term_utt[j0 + m], term_start[j0 + m], term_norm[j0 + m], term_gain[j0 + m], t0, v);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) acc[i] = acc[i] + v[i];         // ((0 + t0) + t1) + ...: Python's sum(), then `+ noise`
-      if (m < S) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) keep[m][i] = v[i];
-      }
-    }
-  }
-  store8(mix + row, acc, t0, n, second);
-#pragma unroll
-  for (int s = 0; s < S; ++s) {
-    const int jm = j0 + s, jt = j0 + M + s;
-    const bool same = term_utt[jt] == term_utt[jm] && term_start[jt] == term_start[jm] &&
-                      __float_as_uint(term_norm[jt]) == __float_as_uint(term_norm[jm]) &&
-                      __float_as_uint(term_gain[jt]) == __float_as_uint(term_gain[jm]);
-    if (same) {                                                    // WSJ0 / WHAM: the target IS the mixture term - computed once
-      store8(src.p[s] + row, keep[s], t0, n, second);
-    } else {
-      float v[8];
-      term_value(c, term_utt[jt], term_start[jt], term_norm[jt], term_gain[jt], t0, v);
-      store8(src.p[s] + row, v, t0, n, second);
-    }
-  }
-}
-
+// ---- the tiled forms: a workgroup makes DS_TILE outputs of one example, one output per lane, through 32 768 bytes of LDS ----------
 constexpr int DS_TILE = DM_TPB * DM_PER;   // output samples per workgroup
 constexpr int DS_SPAN = 3072;              // doubles of staged input: (DS_TILE - 1) M / L + K + 1 must fit (speeds of about 70 % to 140 %)
 constexpr int DS_MAX_NC = 16;
+constexpr int DR_CHUNK = 1024;             // taps per chunk: the chunk's span DS_TILE + DR_CHUNK - 1 = 3071 doubles fits xs [DS_SPAN]
+constexpr int DR_MAX_TAPS = 16384;
+static_assert(DS_TILE + DR_CHUNK - 1 <= DS_SPAN, "a chunk's input span must fit the staged doubles");
+static_assert(DR_CHUNK * sizeof(double) == DS_TILE * sizeof(float), "the chunk's taps as doubles share the float tile");
+
+struct DsLds {
+  double xs[DS_SPAN];                                  // the staged input span
+  __attribute__((aligned(16))) double hs[DR_CHUNK];    // a chunk's taps; at the end of a term the tile of DS_TILE floats
+};
+
+// one utterance's slice of the corpus buffers.  The table is not trusted: the index is clamped and every staged element position is
+// clamped into its buffer, so whatever span is asked for no read leaves the corpus.
+struct DmUtt {
+  long long T, e0, total;                  // samples of the utterance, its first element in its buffer, the buffer's element count
+  bool is16;
+
+  __device__ __forceinline__ DmUtt(const DmCorpus& c, int utt) {
+    const int u = utt < 0 ? 0 : (utt >= c.N ? c.N - 1 : utt);
+    const long long o0 = c.off[u];
+    T = c.off[u + 1] - o0;
+    is16 = u < c.N16;
+    total = is16 ? c.total16 : c.total32;
+    e0 = o0 - (is16 ? 0 : c.off[c.N16]);
+  }
+
+  // xs[i] = double(sample g0 + i) for i < count, zero outside [0, T); all threads of the workgroup, no barrier
+  __device__ __forceinline__ void stage(const DmCorpus& c, long long g0, int count, double* __restrict__ xs) const {
+    for (int i = threadIdx.x; i < count; i += DM_TPB) {
+      const long long g = g0 + i;
+      double v = 0.0;
+      if (g >= 0 && g < T) {
+        const long long e = clampll(e0 + g, 0, total - 1);
+        v = is16 ? (double)((float)c.buf16[e] * 3.0517578125e-05f) : (double)c.buf32[e];
+      }
+      xs[i] = v;
+    }
+  }
+};
+
+// the tile's outputs from one per lane (thread tid holds t = tile0 + tid + DM_TPB i) to x[0 .. 7] = t0 .. t0 + 7 (t0 = tile0 + 8 tid),
+// transposed through the float tile; the caller has made sure that nobody still reads ys.  One barrier.
+__device__ __forceinline__ void tile_out8(const double acc[DM_PER], float* __restrict__ ys, float x[8]) {
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int i = 0; i < DM_PER; ++i) ys[tid + i * DM_TPB] = (float)acc[i];
+  __syncthreads();
+  const float4 lo = *reinterpret_cast<const float4*>(ys + tid * DM_PER);
+  const float4 hi = *reinterpret_cast<const float4*>(ys + tid * DM_PER + 4);
+  x[0] = lo.x, x[1] = lo.y, x[2] = lo.z, x[3] = lo.w, x[4] = hi.x, x[5] = hi.y, x[6] = hi.z, x[7] = hi.w;
+}
 
 struct DsConv {
   const float* taps[DS_MAX_NC];            // [K][L], column q = the tap row of phase (q M) mod L (resample.device_table)
@@ -177,6 +180,58 @@ struct DsConv {
 };
 
 __host__ __device__ inline long long ds_span(int L, int M, int K) { return ((long long)(DS_TILE - 1) * M) / L + K + 1; }
+
+struct DrBank {
+  const float* h;                          // the R impulse responses back to back
+  const long long* off;                    // [R + 1] cumulative sample counts
+  long long total;
+  int R;
+};
+
+// outputs t = tile0 .. tile0 + DS_TILE - 1 of term (utt, start) convolved with the first `taps` samples of impulse response r, as
+//   y[t] = float32(sum_{j < taps} double(h[j]) * double(x[start + t - j])),   x = 0 outside [0, T) of that utterance,
+// left in x8[0 .. 7] for t = t0 .. t0 + 7 of thread tid (t0 = tile0 + 8 tid).  Workgroup-uniform arguments; every thread of the workgroup
+// passes every barrier.  Thread tid owns the outputs tid + 256 i: consecutive lanes read consecutive doubles of xs, and the tap is one
+// broadcast read.  hs is the taps of a chunk as doubles while the chunks run, the tile of floats at the end.
+// The tables are not trusted: r, taps, the utterance and every read position are clamped, so no read leaves the bank or the corpus.
+__device__ __forceinline__ void reverb_tile(const DmCorpus& c, const DrBank& bk, int r, int taps, int utt, int start, int tile0, int n,
+                                            DsLds& lds, float x8[8]) {
+  const int tid = threadIdx.x;
+  const DmUtt ut(c, utt);
+  const long long st = clampll(start, 0, ut.T > 0 ? ut.T : 0);
+  const int rr = r >= bk.R ? bk.R - 1 : r;                                   // r >= 0 here
+  const long long h0 = clampll(bk.off[rr], 0, bk.total - 1);
+  const long long hl = clampll(bk.off[rr + 1] - h0, 1, bk.total - h0 < DR_MAX_TAPS ? bk.total - h0 : DR_MAX_TAPS);
+  const int K = taps < 1 ? 1 : (taps > (int)hl ? (int)hl : taps);            // h0 + K <= total: every tap read is inside the bank
+  const float* __restrict__ hp = bk.h + h0;
+  const int left = n - tile0;                                                // > 0: the caller returned for tiles past n
+  double acc[DM_PER];
+#pragma unroll
+  for (int i = 0; i < DM_PER; ++i) acc[i] = 0.0;
+  double* __restrict__ hs = lds.hs;
+  const double* xp = lds.xs + tid + (DR_CHUNK - 1);
+  for (int k0 = 0; k0 < K; k0 += DR_CHUNK) {
+    const long long g0 = st + tile0 - k0 - (DR_CHUNK - 1);                  // the utterance index of xs[0]
+    // a chunk whose whole span lies before the utterance's first sample adds fma(h, 0, acc) = acc (acc is never -0): it and every
+    // later chunk - their spans lie further back still - are skipped without changing a bit
+    if (g0 + (DS_TILE + DR_CHUNK - 2) < 0) break;
+    const int kc = K - k0 < DR_CHUNK ? K - k0 : DR_CHUNK;
+    __syncthreads();                                                         // the last readers of xs / hs (or of the float tile) are done
+    ut.stage(c, g0, DS_TILE + DR_CHUNK - 1, lds.xs);
+    for (int i = tid; i < kc; i += DM_TPB) hs[i] = (double)hp[k0 + i];
+    __syncthreads();
+    if (tid < left) {                                                        // (per wave: whole waves past n skip the loop)
+#pragma unroll 4
+      for (int j = 0; j < kc; ++j) {
+        const double hj = hs[j];
+#pragma unroll
+        for (int i = 0; i < DM_PER; ++i) acc[i] = fma(hj, xp[i * DM_TPB - j], acc[i]);
+      }
+    }
+  }
+  __syncthreads();                                                           // hs has been read: it becomes the float tile
+  tile_out8(acc, reinterpret_cast<float*>(hs), x8);
+}
 
 // outputs t = tile0 .. tile0 + DS_TILE - 1 (below n) of the perturbed utterance of term (utt, start) through converter (tp, L, M, K), left in
 // ys[t - tile0]; thread tid then owns ys[8 tid .. 8 tid + 7].  Workgroup-uniform arguments; two barriers.  The table is not trusted:
@@ -228,7 +283,7 @@ __device__ __forceinline__ void convert_tile(const DmCorpus& c, int utt, int sta
   __syncthreads();
 }
 
-// term j (flattened) of the example on samples t0 .. t0 + 7: through its converter when it has one, else the plain kernel's term_value
+// a term of the speed kernel on samples t0 .. t0 + 7: through its converter when it has one, else term_value
 __device__ __forceinline__ void speed_term_value(const DmCorpus& c, const DsConv& cv, int conv, int utt, int start, float norm, float gain,
                                                  int tile0, int t0, int n, double* xs, float* ys, float v[8]) {
 #pragma clang fp contract(off)
@@ -241,13 +296,11 @@ __device__ __forceinline__ void speed_term_value(const DmCorpus& c, const DsConv
   const float4 lo = *reinterpret_cast<const float4*>(ys + threadIdx.x * DM_PER);
   const float4 hi = *reinterpret_cast<const float4*>(ys + threadIdx.x * DM_PER + 4);
   const float x[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const float a = x[i] * norm;
-    v[i] = a * gain;
-  }
+  scale8(x, norm, gain, v);
 }
 
+// The speed launch keeps the body and the code it had before the skeleton (per-lane reads of n and the term fields included: every lane
+// reads the same address, which is what keeps its barriers safe).
 template <int S>
 __global__ __launch_bounds__(DM_TPB) void dynmix_speed_kernel(DmCorpus c, DsConv cv, const int* __restrict__ term_utt,
                                                               const int* __restrict__ term_start, const float* __restrict__ term_norm,
@@ -308,118 +361,81 @@ __global__ __launch_bounds__(DM_TPB) void dynmix_speed_kernel(DmCorpus c, DsConv
   }
 }
 
-constexpr int DR_CHUNK = 1024;             // taps per chunk: the chunk's span DS_TILE + DR_CHUNK - 1 = 3071 doubles fits xs [DS_SPAN]
-constexpr int DR_MAX_TAPS = 16384;
-static_assert(DS_TILE + DR_CHUNK - 1 <= DS_SPAN, "a chunk's input span must fit the staged doubles");
-static_assert(DR_CHUNK * sizeof(double) == DS_TILE * sizeof(float), "the chunk's taps as doubles share the float tile");
-
-struct DrBank {
-  const float* h;                          // the R impulse responses back to back
-  const long long* off;                    // [R + 1] cumulative sample counts
-  long long total;
-  int R;
+// ---- the forms of a term: what the mixing skeleton below does not share ---------------------------------------------------------
+// A form is the kernel's first argument - the corpus and the banks its terms read, side by side as the kernels before it took them - and says
+//   kTiled          whether value8 holds barriers: then no thread returns early, n, the term's integer fields and the `same` flag are
+//                   wave-uniform (readfirstlane) before any branch around a barrier, and the zero fill is decided per workgroup;
+//   Cols, cols()    the columns of term j beyond (utt, start, norm, gain), read from the table's extra columns `col...` (kernel
+//                   parameters of their own, where the kernels before had them, so they stay __restrict__ and the reads scalar loads);
+//   same(a, b)      whether those columns name the same term;
+//   value8(...)     (raw * norm) * gain of the term on samples t0 .. t0 + 7 of this thread: scale8 of its eight raw samples - the
+//                   stored ones (term_value) or the chunked FIR filter's tile.
+struct PlainForm {
+  static constexpr bool kTiled = false;
+  DmCorpus c;
+  struct Cols {};
+  __device__ __forceinline__ static Cols cols(int) { return {}; }
+  __device__ __forceinline__ static bool same(Cols, Cols) { return true; }
+  __device__ __forceinline__ void value8(int utt, int start, float norm, float gain, Cols, int, int t0, int, float v[8]) const {
+    term_value(c, utt, start, norm, gain, t0, v);
+  }
 };
 
-// outputs t = tile0 .. tile0 + DS_TILE - 1 of term (utt, start) convolved with the first `taps` samples of impulse response r, as
-//   y[t] = float32(sum_{j < taps} double(h[j]) * double(x[start + t - j])),   x = 0 outside [0, T) of that utterance,
-// left in v[0 .. 7] for t = t0 .. t0 + 7 of thread tid (t0 = tile0 + 8 tid).  Workgroup-uniform arguments; every thread of the workgroup
-// passes every barrier.  Thread tid owns the outputs tid + 256 i: consecutive lanes read consecutive doubles of xs, and the tap is one
-// broadcast read.  hs and ys are the same 8 KB: the taps of a chunk as doubles while the chunks run, the tile of floats at the end.
-// The tables are not trusted: r, taps, the utterance and every read position are clamped, so no read leaves the bank or the corpus.
-__device__ __forceinline__ void reverb_tile(const DmCorpus& c, const DrBank& bk, int r, int taps, int utt, int start, int tile0, int n,
-                                            double* __restrict__ xs, double* __restrict__ hs, float x8[8]) {
-  const int tid = threadIdx.x;
-  const int u = utt < 0 ? 0 : (utt >= c.N ? c.N - 1 : utt);
-  const long long o0 = c.off[u], T = c.off[u + 1] - o0;
-  const bool is16 = u < c.N16;
-  const long long total = is16 ? c.total16 : c.total32;
-  const long long e0 = o0 - (is16 ? 0 : c.off[c.N16]);
-  const long long st = clampll(start, 0, T > 0 ? T : 0);
-  const int rr = r >= bk.R ? bk.R - 1 : r;                                   // r >= 0 here
-  const long long h0 = clampll(bk.off[rr], 0, bk.total - 1);
-  const long long hl = clampll(bk.off[rr + 1] - h0, 1, bk.total - h0 < DR_MAX_TAPS ? bk.total - h0 : DR_MAX_TAPS);
-  const int K = taps < 1 ? 1 : (taps > (int)hl ? (int)hl : taps);            // h0 + K <= total: every tap read is inside the bank
-  const float* __restrict__ hp = bk.h + h0;
-  const int left = n - tile0;                                                // > 0: the caller returned for tiles past n
-  double acc[DM_PER];
-#pragma unroll
-  for (int i = 0; i < DM_PER; ++i) acc[i] = 0.0;
-  const double* xp = xs + tid + (DR_CHUNK - 1);
-  for (int k0 = 0; k0 < K; k0 += DR_CHUNK) {
-    const long long g0 = st + tile0 - k0 - (DR_CHUNK - 1);                  // the utterance index of xs[0]
-    // a chunk whose whole span lies before the utterance's first sample adds fma(h, 0, acc) = acc (acc is never -0): it and every
-    // later chunk - their spans lie further back still - are skipped without changing a bit
-    if (g0 + (DS_TILE + DR_CHUNK - 2) < 0) break;
-    const int kc = K - k0 < DR_CHUNK ? K - k0 : DR_CHUNK;
-    __syncthreads();                                                         // the last readers of xs / hs (or of the float tile) are done
-    for (int i = tid; i < DS_TILE + DR_CHUNK - 1; i += DM_TPB) {
-      const long long g = g0 + i;
-      double v = 0.0;
-      if (g >= 0 && g < T) {
-        const long long e = clampll(e0 + g, 0, total - 1);
-        v = is16 ? (double)((float)c.buf16[e] * 3.0517578125e-05f) : (double)c.buf32[e];
-      }
-      xs[i] = v;
-    }
-    for (int i = tid; i < kc; i += DM_TPB) hs[i] = (double)hp[k0 + i];
-    __syncthreads();
-    if (tid < left) {                                                        // (per wave: whole waves past n skip the loop)
-#pragma unroll 4
-      for (int j = 0; j < kc; ++j) {
-        const double hj = hs[j];
-#pragma unroll
-        for (int i = 0; i < DM_PER; ++i) acc[i] = fma(hj, xp[i * DM_TPB - j], acc[i]);
-      }
-    }
+// the speed entry's corpus and converters for dynmix_launch; its kernel is dynmix_speed_kernel, not an instance of the skeleton
+struct SpeedForm {
+  DmCorpus c;
+  DsConv cv;
+};
+
+// a term whose rir is an index into the bank is the stored utterance under the first taps samples of that response; rir < 0: as stored
+struct ReverbForm {
+  static constexpr bool kTiled = true;
+  DmCorpus c;
+  DrBank bk;
+  struct Cols {
+    int rir, taps;
+  };
+  __device__ __forceinline__ static Cols cols(const int* __restrict__ term_rir, const int* __restrict__ term_taps, int j) {
+    return {__builtin_amdgcn_readfirstlane(term_rir[j]), __builtin_amdgcn_readfirstlane(term_taps[j])};
   }
-  __syncthreads();                                                           // hs has been read: it becomes the float tile
-  float* ys = reinterpret_cast<float*>(hs);
-#pragma unroll
-  for (int i = 0; i < DM_PER; ++i) ys[tid + i * DM_TPB] = (float)acc[i];
-  __syncthreads();
-  const float4 lo = *reinterpret_cast<const float4*>(ys + tid * DM_PER);
-  const float4 hi = *reinterpret_cast<const float4*>(ys + tid * DM_PER + 4);
-  x8[0] = lo.x, x8[1] = lo.y, x8[2] = lo.z, x8[3] = lo.w, x8[4] = hi.x, x8[5] = hi.y, x8[6] = hi.z, x8[7] = hi.w;
+  __device__ __forceinline__ static bool same(Cols a, Cols b) { return a.rir == b.rir && a.taps == b.taps; }
+  __device__ __forceinline__ void value8(int utt, int start, float norm, float gain, Cols t, int tile0, int t0, int n, float v[8]) const {
+    if (t.rir < 0) {
+      term_value(c, utt, start, norm, gain, t0 < n ? t0 : 0, v);
+      return;
+    }
+    __shared__ DsLds lds;
+    float x[8];
+    reverb_tile(c, bk, t.rir, t.taps, utt, start, tile0, n, lds, x);
+    scale8(x, norm, gain, v);
+  }
+};
+
+template <class F>
+__device__ __forceinline__ int uniform(int v) {
+  return F::kTiled ? __builtin_amdgcn_readfirstlane(v) : v;
 }
 
-// term j (flattened) of the example on samples t0 .. t0 + 7: reverberated when it names an impulse response, else the plain kernel's term_value
-__device__ __forceinline__ void reverb_term_value(const DmCorpus& c, const DrBank& bk, int r, int taps, int utt, int start, float norm, float gain,
-                                                  int tile0, int t0, int n, double* xs, double* hs, float v[8]) {
+// The mixing skeleton of every form: one workgroup per DS_TILE samples of one example, one thread per eight.
+template <int S, class F, class... Col>
+__global__ __launch_bounds__(DM_TPB) void dynmix_kernel(F form, const int* __restrict__ term_utt, const int* __restrict__ term_start,
+                                                        const float* __restrict__ term_norm, const float* __restrict__ term_gain,
+                                                        const Col* __restrict__... col, const int* __restrict__ nlen, int M, int Tmax,
+                                                        float* __restrict__ mix, DmRows src) {
 #pragma clang fp contract(off)
-  if (r < 0) {
-    term_value(c, utt, start, norm, gain, t0 < n ? t0 : 0, v);
-    return;
-  }
-  float x[8];
-  reverb_tile(c, bk, r, taps, utt, start, tile0, n, xs, hs, x);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const float a = x[i] * norm;
-    v[i] = a * gain;
-  }
-}
-
-template <int S>
-__global__ __launch_bounds__(DM_TPB) void dynmix_reverb_kernel(DmCorpus c, DrBank bk, const int* __restrict__ term_utt,
-                                                               const int* __restrict__ term_start, const float* __restrict__ term_norm,
-                                                               const float* __restrict__ term_gain, const int* __restrict__ term_rir,
-                                                               const int* __restrict__ term_taps, const int* __restrict__ nlen, int M, int Tmax,
-                                                               float* __restrict__ mix, DmRows src) {
-#pragma clang fp contract(off)
-  __shared__ double xs[DS_SPAN];
-  __shared__ __attribute__((aligned(16))) double hs[DR_CHUNK];     // a chunk's taps; at the end of a term the tile of DS_TILE floats
   const int b = blockIdx.y;
   const int tile0 = blockIdx.x * DS_TILE;
-  const int t0 = tile0 + threadIdx.x * DM_PER;
-  const bool live = t0 < Tmax;                                     // no early return for a thread: the convolutions hold barriers
-  const bool second = t0 + 4 < Tmax;
-  int n = __builtin_amdgcn_readfirstlane(nlen[b]);
+  const int t0 = (blockIdx.x * DM_TPB + threadIdx.x) * DM_PER;
+  if (!F::kTiled && t0 >= Tmax) return;
+  const bool live = !F::kTiled || t0 < Tmax;                       // a tiled form keeps its threads for the barriers and masks their stores
+  const bool second = t0 + 4 < Tmax;                               // Tmax is a multiple of 4, not of 8
+  int n = uniform<F>(nlen[b]);
   n = n < 0 ? 0 : (n > Tmax ? Tmax : n);
   const long long row = (long long)b * Tmax + t0;
   float acc[8], keep[S][8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) acc[i] = 0.f;
-  if (tile0 >= n) {                                                // the whole tile is the zero fill of pad_sequence (workgroup-uniform)
+  if ((F::kTiled ? tile0 : t0) >= n) {                             // the zero fill of pad_sequence; tiled: the whole tile, workgroup-uniform
     if (live) {
       store8(mix + row, acc, t0, n, second);
 #pragma unroll
@@ -432,11 +448,10 @@ __global__ __launch_bounds__(DM_TPB) void dynmix_reverb_kernel(DmCorpus c, DrBan
   for (int m = 0; m < S + 1; ++m) {
     if (m < M) {
       float v[8];
-      const int r = __builtin_amdgcn_readfirstlane(term_rir[j0 + m]), taps = __builtin_amdgcn_readfirstlane(term_taps[j0 + m]);
-      const int utt = __builtin_amdgcn_readfirstlane(term_utt[j0 + m]), start = __builtin_amdgcn_readfirstlane(term_start[j0 + m]);
-      reverb_term_value(c, bk, r, taps, utt, start, term_norm[j0 + m], term_gain[j0 + m], tile0, t0, n, xs, hs, v);
+      form.value8(uniform<F>(term_utt[j0 + m]), uniform<F>(term_start[j0 + m]), term_norm[j0 + m], term_gain[j0 + m],
+                  F::cols(col..., j0 + m), tile0, t0, n, v);
 #pragma unroll
-      for (int i = 0; i < 8; ++i) acc[i] = acc[i] + v[i];
+      for (int i = 0; i < 8; ++i) acc[i] = acc[i] + v[i];         // ((0 + t0) + t1) + ...: Python's sum(), then `+ noise`
       if (m < S) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) keep[m][i] = v[i];
@@ -447,15 +462,15 @@ __global__ __launch_bounds__(DM_TPB) void dynmix_reverb_kernel(DmCorpus c, DrBan
 #pragma unroll
   for (int s = 0; s < S; ++s) {
     const int jm = j0 + s, jt = j0 + M + s;
-    const int r = __builtin_amdgcn_readfirstlane(term_rir[jt]), taps = __builtin_amdgcn_readfirstlane(term_taps[jt]);
-    const int utt = __builtin_amdgcn_readfirstlane(term_utt[jt]), start = __builtin_amdgcn_readfirstlane(term_start[jt]);
-    const bool same = utt == term_utt[jm] && start == term_start[jm] && __float_as_uint(term_norm[jt]) == __float_as_uint(term_norm[jm]) &&
-                      __float_as_uint(term_gain[jt]) == __float_as_uint(term_gain[jm]) && r == term_rir[jm] && taps == term_taps[jm];
-    if (__builtin_amdgcn_readfirstlane(same)) {                    // all six fields: the target IS the mixture term - computed once
+    const bool same = term_utt[jt] == term_utt[jm] && term_start[jt] == term_start[jm] &&
+                      __float_as_uint(term_norm[jt]) == __float_as_uint(term_norm[jm]) &&
+                      __float_as_uint(term_gain[jt]) == __float_as_uint(term_gain[jm]) && F::same(F::cols(col..., jt), F::cols(col..., jm));
+    if (uniform<F>(same)) {                                        // every field of the form: the target IS the mixture term - computed once
       if (live) store8(src.p[s] + row, keep[s], t0, n, second);
     } else {
       float v[8];
-      reverb_term_value(c, bk, r, taps, utt, start, term_norm[jt], term_gain[jt], tile0, t0, n, xs, hs, v);
+      form.value8(uniform<F>(term_utt[jt]), uniform<F>(term_start[jt]), term_norm[jt], term_gain[jt], F::cols(col..., jt), tile0, t0, n,
+                  v);
       if (live) store8(src.p[s] + row, v, t0, n, second);
     }
   }
@@ -555,20 +570,37 @@ extern "C" int sepr_corpus_energy(const short* buf16, long long total16, const f
 
 namespace sepr {
 namespace {
-// the argument checks the two mixing entries share; fills rows
-int dynmix_args_bad(const short* buf16, long long total16, const float* buf32, long long total32, const long long* offsets, int N16, int N,
-                    const int* term_utt, const int* term_start, const float* term_norm, const float* term_gain, const int* n, int B, int M, int S,
-                    int Tmax, float* mix, float* const* src, DmRows* rows) {
-  if (corpus_args_bad(buf16, total16, buf32, total32, offsets, N16, N)) return 1;
-  if (!term_utt || !term_start || !term_norm || !term_gain || !n || !mix || !src) return 1;
-  if (B < 1 || B > 65535 || S < 2 || S > 3 || M < S || M > S + 1 || Tmax < 4 || Tmax % 4 != 0) return 1;
+// what the three mixing entries share: the checks of the common arguments, the corpus and the target rows as kernel arguments, the grid,
+// the dispatch on S and the launch check.  An entry checks its own arguments BEFORE it calls this and passes them in `form` and `col`;
+// every refusal is SEPR_EINVAL, so which check comes first does not show.
+template <class F, class... Col>
+int dynmix_launch(const short* buf16, long long total16, const float* buf32, long long total32, const long long* offsets, int N16, int N,
+                  const int* term_utt, const int* term_start, const float* term_norm, const float* term_gain, const int* n, int B, int M, int S,
+                  int Tmax, float* mix, float* const* src, sepr_stream_t stream, F form, const char* what, const Col*... col) {
+  if (corpus_args_bad(buf16, total16, buf32, total32, offsets, N16, N)) return SEPR_EINVAL;
+  if (!term_utt || !term_start || !term_norm || !term_gain || !n || !mix || !src) return SEPR_EINVAL;
+  if (B < 1 || B > 65535 || S < 2 || S > 3 || M < S || M > S + 1 || Tmax < 4 || Tmax % 4 != 0) return SEPR_EINVAL;
+  DmRows rows = {{nullptr, nullptr, nullptr}};
   uintptr_t al = reinterpret_cast<uintptr_t>(mix);
   for (int s = 0; s < S; ++s) {
-    if (!src[s]) return 1;
-    rows->p[s] = src[s];
+    if (!src[s]) return SEPR_EINVAL;
+    rows.p[s] = src[s];
     al |= reinterpret_cast<uintptr_t>(src[s]);
   }
-  return al % 16 != 0;                                             // float4 stores
+  if (al % 16 != 0) return SEPR_EINVAL;                            // float4 stores
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  form.c = {buf16, buf32, offsets, total16, total32, N16, N};
+  const dim3 grid((unsigned)cdiv(Tmax, DS_TILE), (unsigned)B);
+  // `head`: the kernel's leading arguments, its corpus and banks; `col`: term_conv (speed), term_rir and term_taps (reverb), none (plain)
+  auto go = [&](auto kernel, const auto&... head) {
+    hipLaunchKernelGGL(kernel, grid, dim3(DM_TPB), 0, st, head..., term_utt, term_start, term_norm, term_gain, col..., n, M, Tmax, mix, rows);
+  };
+  if constexpr (__is_same(F, SpeedForm))             // a kernel of its own (see dynmix_speed_kernel) with the argument list it always had
+    S == 2 ? go(dynmix_speed_kernel<2>, form.c, form.cv) : go(dynmix_speed_kernel<3>, form.c, form.cv);
+  else
+    S == 2 ? go(dynmix_kernel<2, F, Col...>, form) : go(dynmix_kernel<3, F, Col...>, form);
+  SEPR_CHECK_LAUNCH(what);
+  return SEPR_OK;
 }
 }  // namespace
 }  // namespace sepr
@@ -577,18 +609,8 @@ extern "C" int sepr_dynmix_fwd(const short* buf16, long long total16, const floa
                                int N16, int N, const int* term_utt, const int* term_start, const float* term_norm, const float* term_gain,
                                const int* n, int B, int M, int S, int Tmax, float* mix, float* const* src, sepr_stream_t stream) {
   using namespace sepr;
-  DmRows rows = {{nullptr, nullptr, nullptr}};
-  if (dynmix_args_bad(buf16, total16, buf32, total32, offsets, N16, N, term_utt, term_start, term_norm, term_gain, n, B, M, S, Tmax, mix, src, &rows))
-    return SEPR_EINVAL;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const DmCorpus c = {buf16, buf32, offsets, total16, total32, N16, N};
-  const dim3 grid((unsigned)cdiv(Tmax, DM_TPB * DM_PER), (unsigned)B);
-  if (S == 2)
-    hipLaunchKernelGGL((dynmix_kernel<2>), grid, dim3(DM_TPB), 0, st, c, term_utt, term_start, term_norm, term_gain, n, M, Tmax, mix, rows);
-  else
-    hipLaunchKernelGGL((dynmix_kernel<3>), grid, dim3(DM_TPB), 0, st, c, term_utt, term_start, term_norm, term_gain, n, M, Tmax, mix, rows);
-  SEPR_CHECK_LAUNCH("dynmix kernel");
-  return SEPR_OK;
+  return dynmix_launch(buf16, total16, buf32, total32, offsets, N16, N, term_utt, term_start, term_norm, term_gain, n, B, M, S, Tmax, mix, src,
+                       stream, PlainForm{}, "dynmix kernel");
 }
 
 extern "C" int sepr_dynmix_speed_fwd(const short* buf16, long long total16, const float* buf32, long long total32, const long long* offsets,
@@ -597,32 +619,20 @@ extern "C" int sepr_dynmix_speed_fwd(const short* buf16, long long total16, cons
                                      float* const* src, const float* const* conv_taps, const int* conv_L, const int* conv_M, const int* conv_K,
                                      int NC, sepr_stream_t stream) {
   using namespace sepr;
-  DmRows rows = {{nullptr, nullptr, nullptr}};
-  if (dynmix_args_bad(buf16, total16, buf32, total32, offsets, N16, N, term_utt, term_start, term_norm, term_gain, n, B, M, S, Tmax, mix, src, &rows))
-    return SEPR_EINVAL;
   if (!term_conv || NC < 0 || NC > DS_MAX_NC) return SEPR_EINVAL;
   if (NC > 0 && (!conv_taps || !conv_L || !conv_M || !conv_K)) return SEPR_EINVAL;
-  DsConv cv = {};
-  cv.NC = NC;
+  SpeedForm form = {};
+  form.cv.NC = NC;
   for (int k = 0; k < NC; ++k) {
     if (!conv_taps[k] || conv_L[k] < 1 || conv_M[k] < 1 || conv_K[k] < 1 || conv_K[k] % 2 != 0) return SEPR_EINVAL;
     if (ds_span(conv_L[k], conv_M[k], conv_K[k]) > DS_SPAN) return SEPR_EINVAL;   // the tile's input span exceeds the kernel's LDS plan
-    cv.taps[k] = conv_taps[k];
-    cv.L[k] = conv_L[k];
-    cv.M[k] = conv_M[k];
-    cv.K[k] = conv_K[k];
+    form.cv.taps[k] = conv_taps[k];
+    form.cv.L[k] = conv_L[k];
+    form.cv.M[k] = conv_M[k];
+    form.cv.K[k] = conv_K[k];
   }
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const DmCorpus c = {buf16, buf32, offsets, total16, total32, N16, N};
-  const dim3 grid((unsigned)cdiv(Tmax, DS_TILE), (unsigned)B);
-  if (S == 2)
-    hipLaunchKernelGGL((dynmix_speed_kernel<2>), grid, dim3(DM_TPB), 0, st, c, cv, term_utt, term_start, term_norm, term_gain, term_conv, n, M,
-                       Tmax, mix, rows);
-  else
-    hipLaunchKernelGGL((dynmix_speed_kernel<3>), grid, dim3(DM_TPB), 0, st, c, cv, term_utt, term_start, term_norm, term_gain, term_conv, n, M,
-                       Tmax, mix, rows);
-  SEPR_CHECK_LAUNCH("dynmix speed kernel");
-  return SEPR_OK;
+  return dynmix_launch(buf16, total16, buf32, total32, offsets, N16, N, term_utt, term_start, term_norm, term_gain, n, B, M, S, Tmax, mix, src,
+                       stream, form, "dynmix speed kernel", term_conv);
 }
 
 extern "C" int sepr_dynmix_reverb_fwd(const short* buf16, long long total16, const float* buf32, long long total32, const long long* offsets,
@@ -631,21 +641,10 @@ extern "C" int sepr_dynmix_reverb_fwd(const short* buf16, long long total16, con
                                       int Tmax, float* mix, float* const* src, const float* rir, long long rir_total, const long long* rir_off,
                                       int R, sepr_stream_t stream) {
   using namespace sepr;
-  DmRows rows = {{nullptr, nullptr, nullptr}};
-  if (dynmix_args_bad(buf16, total16, buf32, total32, offsets, N16, N, term_utt, term_start, term_norm, term_gain, n, B, M, S, Tmax, mix, src, &rows))
-    return SEPR_EINVAL;
   if (!term_rir || !term_taps || !rir || !rir_off || R < 1 || rir_total < 1) return SEPR_EINVAL;
   if (reinterpret_cast<uintptr_t>(rir) % 4 != 0) return SEPR_EINVAL;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const DmCorpus c = {buf16, buf32, offsets, total16, total32, N16, N};
-  const DrBank bk = {rir, rir_off, rir_total, R};
-  const dim3 grid((unsigned)cdiv(Tmax, DS_TILE), (unsigned)B);
-  if (S == 2)
-    hipLaunchKernelGGL((dynmix_reverb_kernel<2>), grid, dim3(DM_TPB), 0, st, c, bk, term_utt, term_start, term_norm, term_gain, term_rir, term_taps,
-                       n, M, Tmax, mix, rows);
-  else
-    hipLaunchKernelGGL((dynmix_reverb_kernel<3>), grid, dim3(DM_TPB), 0, st, c, bk, term_utt, term_start, term_norm, term_gain, term_rir, term_taps,
-                       n, M, Tmax, mix, rows);
-  SEPR_CHECK_LAUNCH("dynmix reverb kernel");
-  return SEPR_OK;
+  ReverbForm form = {};
+  form.bk = {rir, rir_off, rir_total, R};
+  return dynmix_launch(buf16, total16, buf32, total32, offsets, N16, N, term_utt, term_start, term_norm, term_gain, n, B, M, S, Tmax, mix, src,
+                       stream, form, "dynmix reverb kernel", term_rir, term_taps);
 }

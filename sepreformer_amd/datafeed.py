@@ -488,8 +488,16 @@ def collate_plan(corpus: Corpus, examples: Sequence[Example], rirs: Optional[Rir
                      rir if any_rir else None, taps if any_rir else None)
 
 
+def table_layout(B: int, NT: int, speeds: bool = False, rirs: bool = False) -> Dict[str, Tuple[int, int]]:
+    """The device table of a plan, the one place that says where its blocks lie: name -> (first int32 word, words), in memory order
+    ``utt | start | norm | gain | n``, then ``conv`` for a plan with speeds, then ``rir | taps`` for one with RIRs."""
+    names = ("utt", "start", "norm", "gain", "n") + (("conv",) if speeds else ()) + (("rir", "taps") if rirs else ())
+    words = [B if name == "n" else B * NT for name in names]
+    return {name: (sum(words[:k]), words[k]) for k, name in enumerate(names)}
+
+
 def _table_words(B: int, NT: int, speeds: bool = False, rirs: bool = False) -> int:
-    return (4 + (1 if speeds else 0) + (2 if rirs else 0)) * B * NT + B
+    return sum(words for _, words in table_layout(B, NT, speeds, rirs).values())
 
 
 def plan_speeds(plan: BatchPlan) -> List[int]:
@@ -530,8 +538,6 @@ def mix_batch(corpus: Corpus, plan: BatchPlan, Tmax: Optional[int] = None, mix: 
     Tmax = int(Tmax if Tmax is not None else -(-int(plan.n.max()) // 4) * 4)
     if Tmax % 4 or int(plan.n.max()) > Tmax:
         raise ValueError(f"Tmax = {Tmax} must be a multiple of 4 and hold the longest example ({int(plan.n.max())})")
-    if plan.speed is not None and speeds is None:
-        speeds = plan_speeds(plan)
     if plan.rir is not None:
         if plan.speed is not None:
             raise ValueError("a plan with speeds and RIRs is not built")
@@ -553,40 +559,33 @@ def mix_batch(corpus: Corpus, plan: BatchPlan, Tmax: Optional[int] = None, mix: 
             raise ValueError(f"outputs must be contiguous float32 [{B}, {Tmax}] tensors on {dev}")
     if len(src) != plan.S:
         raise ValueError(f"{plan.S} target rows expected")
-    base, n = table.data_ptr(), B * NT
+    at = {name: table.data_ptr() + 4 * first for name, (first, _) in table_layout(B, NT, plan.speed is not None, plan.rir is not None).items()}
     rows = (C.c_void_p * plan.S)(*[t.data_ptr() for t in src])
+    entry, cols, own = "sepr_dynmix_fwd", (), ()        # the entry, the table columns of its form, the form's own arguments
+    if plan.rir is not None:
+        entry, cols, own = "sepr_dynmix_reverb_fwd", (at["rir"], at["taps"]), rirs._bank_args()
+    elif plan.speed is not None:
+        entry, cols, own = "sepr_dynmix_speed_fwd", (at["conv"],), _converter_args(dev, plan_speeds(plan) if speeds is None else speeds)
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        if plan.rir is not None:
-            L_.check(L_.load().sepr_dynmix_reverb_fwd(*corpus._corpus_args(), base, base + 4 * n, base + 8 * n, base + 12 * n, base + 16 * n + 4 * B,
-                                                      base + 20 * n + 4 * B, base + 16 * n, B, plan.M, plan.S, Tmax, mix.data_ptr(), rows,
-                                                      *rirs._bank_args(), stream), "sepr_dynmix_reverb_fwd")
-        elif plan.speed is None:
-            L_.check(L_.load().sepr_dynmix_fwd(*corpus._corpus_args(), base, base + 4 * n, base + 8 * n, base + 12 * n, base + 16 * n, B, plan.M,
-                                               plan.S, Tmax, mix.data_ptr(), rows, stream), "sepr_dynmix_fwd")
-        else:
-            L_.check(L_.load().sepr_dynmix_speed_fwd(*corpus._corpus_args(), base, base + 4 * n, base + 8 * n, base + 12 * n, base + 16 * n + 4 * B,
-                                                     base + 16 * n, B, plan.M, plan.S, Tmax, mix.data_ptr(), rows, *_converter_args(dev, speeds),
-                                                     stream), "sepr_dynmix_speed_fwd")
+        L_.check(getattr(L_.load(), entry)(*corpus._corpus_args(), at["utt"], at["start"], at["norm"], at["gain"], *cols, at["n"], B, plan.M, plan.S,
+                                           Tmax, mix.data_ptr(), rows, *own, torch.cuda.current_stream(dev).cuda_stream), entry)
     return mix, list(src)
 
 
 def pack_table(plan: BatchPlan, speeds: Optional[Sequence[int]] = None) -> np.ndarray:
-    """The plan as one int32 array ``[utt | start | norm bits | gain bits | n]``; a plan that carries speeds appends the converter-index
-    block ``[conv]``: -1 for a term at 100 %, else the position of the term's speed in ``speeds`` (default ``plan_speeds(plan)``); a plan
-    that carries RIRs appends ``[rir | taps]`` after ``n``."""
-    parts = [plan.utt.ravel(), plan.start.ravel(), plan.norm.ravel().view(np.int32), plan.gain.ravel().view(np.int32), plan.n.astype(np.int32)]
+    """The plan as one int32 array in the order of ``table_layout`` (``norm`` and ``gain`` as their bits).  The ``conv`` block of a plan that
+    carries speeds: -1 for a term at 100 %, else the position of the term's speed in ``speeds`` (default ``plan_speeds(plan)``)."""
+    blocks = {"utt": plan.utt, "start": plan.start, "norm": plan.norm.view(np.int32), "gain": plan.gain.view(np.int32), "n": plan.n,
+              "rir": plan.rir, "taps": plan.taps}
     if plan.speed is not None:
         order = [int(p) for p in (plan_speeds(plan) if speeds is None else speeds)]
-        index = {p: k for k, p in enumerate(order)}
-        index[100] = -1
+        index = {**{p: k for k, p in enumerate(order)}, 100: -1}
         missing = sorted({int(p) for p in plan.speed.ravel()} - set(index))
         if missing:
             raise ValueError(f"speeds {missing} of the plan are not in the converter set {order}")
-        parts.append(np.array([index[int(p)] for p in plan.speed.ravel()], np.int32))
-    if plan.rir is not None:
-        parts += [plan.rir.ravel().astype(np.int32), plan.taps.ravel().astype(np.int32)]
-    return np.concatenate(parts)
+        blocks["conv"] = np.array([index[int(p)] for p in plan.speed.ravel()], np.int32)
+    layout = table_layout(*plan.utt.shape, plan.speed is not None, plan.rir is not None)
+    return np.concatenate([blocks[name].ravel().astype(np.int32, copy=False) for name in layout])
 
 
 class DynamicMixFeed:

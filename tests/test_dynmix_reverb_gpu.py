@@ -11,6 +11,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import dynmix_one_field as one                                               # noqa: E402
 import dynmix_ref as dr                                                      # noqa: E402
 import dynmix_reverb_ref as ref                                              # noqa: E402
 
@@ -255,3 +256,22 @@ def test_through_the_feed(golden):
         df.mix_batch(corpus, f1.last_plan, T)
     with pytest.raises(ValueError, match="bank is on"):
         df.mix_batch(corpus, f1.last_plan, T, rirs=rv.RirBank.from_arrays(hs, 8000))
+
+
+def test_a_target_that_differs_in_one_field_is_recomputed():
+    """B = 6: utt, start, norm bits, gain bits, rir, taps.  The example that changes the response alone pairs two responses of equal
+    length, the one that changes the tap count alone cuts a response that has non-zero samples beyond the shorter count."""
+    rng = np.random.default_rng(23)
+    arrays = {"a16": rng.integers(-20000, 20000, size=2600, dtype=np.int16), "b16": rng.integers(-20000, 20000, size=2600, dtype=np.int16),
+              "a32": rng.normal(0, 0.1, size=2700).astype(np.float32), "b32": rng.normal(0, 0.1, size=2700).astype(np.float32)}
+    corpus = df.Corpus.from_arrays(arrays, device=DEV)
+    utts, i = [arrays[nm] for nm in corpus.names], corpus.index
+    hs = [rng.normal(0, 0.2, size=300).astype(np.float32) for _ in range(2)]
+    assert all(np.all(h[77:] != 0) for h in hs)
+    bank = rv.RirBank.from_arrays(hs, 8000, device=DEV, normalise=None)
+    same, changed = one.plans(df, {"utt": (i["a16"], i["a32"]), "start": (3, 40), "norm": (0.75, 1.5), "gain": (1.25, 0.5), "rir": (0, 1),
+                                   "taps": (300, 300)},
+                              {"utt": (i["b16"], i["b32"]), "start": (4, 47), "norm": (0.8, 1.4), "gain": (1.3, 0.6), "rir": (1, 0),
+                               "taps": (120, 77)})
+    assert len(changed.n) == 6
+    one.check(lambda p: df.mix_batch(corpus, p, one.TMAX, rirs=bank), lambda p: ref_batch(utts, hs, p, one.TMAX), same, changed)

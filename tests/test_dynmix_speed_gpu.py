@@ -14,6 +14,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import dynmix_one_field as one                                               # noqa: E402
 import dynmix_ref as dr                                                      # noqa: E402
 import dynmix_speed_ref as ref                                               # noqa: E402
 
@@ -277,3 +278,18 @@ def test_captured_train_step_fed_with_speeds(golden):
     step.release()
     print("losses", losses)
     assert perturbed > 0 and all(np.isfinite(v) for v in losses) and len(set(losses)) > 1
+
+
+def test_a_target_that_differs_in_one_field_is_recomputed():
+    """B = 5: utt, start, norm bits, gain bits, conv.  Every term goes through a converter, and the example that changes the speed alone
+    pairs a converter with another converter; the two utterances of a pair differ in content and both hold start + n at every speed."""
+    rng = np.random.default_rng(23)
+    arrays = {"a16": rng.integers(-20000, 20000, size=2600, dtype=np.int16), "b16": rng.integers(-20000, 20000, size=2600, dtype=np.int16),
+              "a32": rng.normal(0, 0.1, size=2700).astype(np.float32), "b32": rng.normal(0, 0.1, size=2700).astype(np.float32)}
+    corpus = df.Corpus.from_arrays(arrays, device=DEV)
+    utts, i = [arrays[nm] for nm in corpus.names], corpus.index
+    assert ref.perturbed_len(2600, 105) >= 47 + one.TMAX
+    same, changed = one.plans(df, {"utt": (i["a16"], i["a32"]), "start": (3, 40), "norm": (0.75, 1.5), "gain": (1.25, 0.5), "speed": (95, 104)},
+                              {"utt": (i["b16"], i["b32"]), "start": (4, 47), "norm": (0.8, 1.4), "gain": (1.3, 0.6), "speed": (105, 96)})
+    assert len(changed.n) == 5 and 100 not in changed.speed
+    one.check(lambda p: df.mix_batch(corpus, p, one.TMAX), lambda p: ref_batch(utts, p, one.TMAX), same, changed)
