@@ -492,7 +492,28 @@ int sepr_resample_fwd(const float* x, const long long* in_offset, float* y, cons
  * [0, rir_total), and the utterance index, the start and every corpus read as sepr_dynmix_fwd does: a bad table yields wrong samples but never a
  * read outside the buffers.  SEPR_EINVAL before any HIP call for everything sepr_dynmix_fwd refuses, a null term_rir, term_taps, rir or
  * rir_off, R < 1, rir_total < 1 or a misaligned rir.  No workspace, no host synchronisation or allocation (capturable: the pointers are
- * frozen, the table contents - RIR indices and tap counts included - are read at replay). */
+ * frozen, the table contents - RIR indices and tap counts included - are read at replay).
+ *
+ * sepr_dynmix_speed_reverb_fwd: both inside one launch, the talker first and the room second.  The arguments are the common
+ * ones, the three columns term_conv, term_rir, term_taps [B (M + S)] int32 (DEVICE), the converter arrays of sepr_dynmix_speed_fwd (0 <= NC <= 16)
+ * and the bank arguments of sepr_dynmix_reverb_fwd.  A term is (utt, start, norm, gain, conv, rir, taps).  With conv >= 0 and rir >= 0, x the stored
+ * utterance of T samples and (L, M, K) the converter:
+ *   y    the perturbed utterance of P = sepr_resample_out_len(T, L, M) samples; y[n] is exactly sepr_dynmix_speed_fwd's / sepr_resample_fwd's float32
+ *        sample (exact float64 products, j = 0 .. K - 1 in order, one rounding, x zero outside [0, T) of THAT utterance);
+ *   z[t] = float32(sum_{j = 0 .. taps - 1} double(h_rir[j]) * double(y[term_start + t - j])),   y ZERO outside [0, P) - not the converter evaluated
+ *        at negative positions, where it would ring - the products exact in float64, added as fma(h, y, acc) in the order j = 0 .. taps - 1 from
+ *        acc = 0.0, one rounding;
+ * the term's value is (z[t] * term_norm) * term_gain, the two separately rounded float32 multiplies.  term_start indexes the perturbed utterance; the
+ * caller guarantees term_start + n[b] <= P.  So the term is "convert the whole utterance, convolve, truncate to P, crop" bit for bit; conv = -1 gives
+ * sepr_dynmix_reverb_fwd's bits, rir = -1 sepr_dynmix_speed_fwd's, both -1 sepr_dynmix_fwd's, and h = [1.0] sepr_dynmix_speed_fwd's (a perturbed
+ * sample that is -0.0 comes out +0.0).  Per workgroup of 2048 outputs and chunk of kc <= 1024 taps, the 2048 + kc - 1 perturbed samples the chunk
+ * reaches (fewer at the utterance's beginning and in the last tile of an example) are converted into LDS as doubles, in passes whose input span fits
+ * 3072 samples, and the FIR sums stay in registers across chunks; 57344 bytes of LDS whatever the response's length.  A target term that equals
+ * mixture term s in all seven fields is computed once.  The kernel clamps conv, rir, taps, the utterance index, the start and every read position as
+ * the two entries do: a bad table yields wrong samples but never a read outside the corpus, the bank or a tap table.  SEPR_EINVAL before any HIP
+ * call for everything sepr_dynmix_speed_fwd or sepr_dynmix_reverb_fwd refuses (a converter whose 2048-output span exceeds 3072 samples included).
+ * No workspace, no host synchronisation or allocation (capturable: the pointers and the converter descriptions are frozen, the table contents are
+ * read at replay).  A new entry, no struct change: ABI 4.13. */
 size_t sepr_corpus_energy_workspace(int N);
 int sepr_corpus_energy(const short* buf16, long long total16, const float* buf32, long long total32, const long long* offsets, int N16, int N,
                        long long* ss16, double* ss32, void* ws, size_t ws_bytes, sepr_stream_t stream);
@@ -507,6 +528,12 @@ int sepr_dynmix_reverb_fwd(const short* buf16, long long total16, const float* b
                            const int* term_utt, const int* term_start, const float* term_norm, const float* term_gain, const int* term_rir,
                            const int* term_taps, const int* n, int B, int M, int S, int Tmax, float* mix, float* const* src, const float* rir,
                            long long rir_total, const long long* rir_off, int R, sepr_stream_t stream);
+int sepr_dynmix_speed_reverb_fwd(const short* buf16, long long total16, const float* buf32, long long total32, const long long* offsets, int N16,
+                                 int N, const int* term_utt, const int* term_start, const float* term_norm, const float* term_gain,
+                                 const int* term_conv, const int* term_rir, const int* term_taps, const int* n, int B, int M, int S, int Tmax,
+                                 float* mix, float* const* src, const float* const* conv_taps, const int* conv_L, const int* conv_M,
+                                 const int* conv_K, int NC, const float* rir, long long rir_total, const long long* rir_off, int R,
+                                 sepr_stream_t stream);
 
 /* ---- room impulse responses by the image-source method (a new entry, no struct change: ABI 4.13) -------
  * sepr_rir_ism_fwd simulates R impulse responses of N samples, one per shoebox room, in one call.  The definition is independent of the

@@ -20,6 +20,11 @@
 //                        samples and its taps as doubles in LDS, the float64 accumulators staying in registers - so the 32 768-byte LDS
 //                        plan does not depend on the response's length.  It holds barriers: no thread returns early, and n, a term's
 //                        integer fields and the same-term flag are wave-uniform (readfirstlane) before any branch around a barrier.
+//     F = SpeedReverbForm (sepr_dynmix_speed_reverb_fwd, section 5e-5) a term may carry a converter AND a response: the utterance perturbed
+//                        first, reverberated second.  The geometry of ReverbForm; per tap chunk the span of the perturbed utterance that the
+//                        chunk reaches is converted into LDS as doubles (convert_tile's arithmetic, in passes whose input span fits the
+//                        staged doubles), then the FIR loop runs over it.  57 344 bytes of LDS; a term with one of the two takes that
+//                        form's code and gives its bits.
 //   dynmix_speed_kernel  (sepr_dynmix_speed_fwd, section 5e-2) the same batch with speed perturbation, a kernel of its own (docs/HISTORY.md:
 //                        as an instance of the skeleton it ran 0.8 to 1.1 us longer per launch at B = 16): a term whose term_conv is a converter
 //                        index is the stored utterance through that rational-ratio converter (the arithmetic of sepr_resample.hip).  The
@@ -411,6 +416,167 @@ struct ReverbForm {
   }
 };
 
+// ---- speed perturbation, then the room ------------------------------------------------------------------------
+// 57 344 bytes of LDS: the 32 768 of the two tiled forms before it - which the terms with only a converter (convert_tile) or only a response
+// (reverb_tile) use exactly as those forms do - and the perturbed span of a tap chunk as doubles.
+struct SrLds {
+  DsLds a;                                             // xs: the staged INPUT span of a conversion pass; hs: a chunk's taps, then the float tile
+  double ys[DS_SPAN];                                  // the chunk's span of the PERTURBED utterance, float32 values widened
+};
+static_assert(sizeof(SrLds) <= 57344, "static LDS of the combined form");
+
+// perturbed samples of the positions i = i0 + tid + 256 k (k < NI) below i1 into yd[i]: position i is sample q0 + i >= 0 of the perturbed utterance,
+//   y[q] = float32(sum_{j < K} double(tap[(q M) mod L][j]) * x[floor(q M / L) - Hh + j]),
+// convert_tile's arithmetic and order; xs[0] is input sample b0 - Hh and `span` doubles are staged.  No barrier.  Every window base is clamped into
+// [0, span - K] (span <= DS_SPAN, K <= span: the entry refuses any other converter) and every phase lies in [0, L): no read leaves xs or the tap table.
+template <int NI>
+__device__ __forceinline__ void convert_group(const double* __restrict__ xs, int span, long long b0, const float* __restrict__ tp, int L, int M,
+                                              int K, long long q0, int i0, int i1, double* __restrict__ yd) {
+  const int tid = threadIdx.x;
+  if (i0 + tid >= i1) return;                                                // (per wave: whole waves without a position skip the loop)
+  const int lim = span - K;
+  double acc[NI];
+  const double* xp[NI];
+  const float* tq[NI];
+#pragma unroll
+  for (int i = 0; i < NI; ++i) {
+    const int pos = i0 + tid + i * DM_TPB;
+    const long long nn = q0 + (pos < i1 ? pos : i0);                        // a lane past i1 converts the group's first position and drops it
+    const long long d = (nn * M) / L - b0;
+    xp[i] = xs + (int)(d < 0 ? 0 : (d > lim ? lim : d));
+    tq[i] = tp + (int)(nn % L);
+    acc[i] = 0.0;
+  }
+#pragma unroll 2
+  for (int j = 0; j < K; ++j) {
+#pragma unroll
+    for (int i = 0; i < NI; ++i) acc[i] = fma((double)tq[i][(long long)j * L], xp[i][j], acc[i]);
+  }
+#pragma unroll
+  for (int i = 0; i < NI; ++i) {
+    const int pos = i0 + tid + i * DM_TPB;
+    if (pos < i1) yd[pos] = (double)(float)acc[i];                          // the one rounding of the perturbed sample
+  }
+}
+
+// outputs t = tile0 .. tile0 + DS_TILE - 1 of term (utt, start) perturbed by converter `conv` and then convolved with the first `taps` samples of
+// impulse response r:
+//   z[t] = float32(sum_{j < taps} double(h[j]) * double(y[start + t - j])),   y = the perturbed utterance, ZERO outside [0, P),
+// left in x8 as reverb_tile leaves its outputs.  Workgroup-uniform arguments; every thread of the workgroup passes every barrier.  Per tap chunk
+// the span of y that the chunk's kc taps reach - positions DR_CHUNK - kc .. DR_CHUNK + min(n - tile0, DS_TILE) - 2 of ys, not all 3071 - is
+// converted in passes of at most W positions, W the most whose input span fits xs (W >= DS_TILE by the entry's check, so at most two passes),
+// then reverb_tile's FIR loop runs over ys; the float64 accumulators stay in registers across chunks and passes.
+// The tables are not trusted.  conv is clamped to [0, NC - 1], r and taps as in reverb_tile (every tap read inside the bank), the utterance by
+// DmUtt (every staged element clamped into its buffer), start into [0, P]; ys is written and read at indices in [DR_CHUNK - kc, DS_TILE +
+// DR_CHUNK - 1) only, xs below `span` <= DS_SPAN only.
+__device__ __forceinline__ void speed_reverb_tile(const DmCorpus& c, const DsConv& cv, const DrBank& bk, int conv, int r, int taps, int utt,
+                                                  int start, int tile0, int n, SrLds& lds, float x8[8]) {
+  const int tid = threadIdx.x;
+  const DmUtt ut(c, utt);
+  const int ck = conv >= cv.NC ? cv.NC - 1 : conv;                           // conv >= 0 and NC >= 1 here
+  const float* __restrict__ tp = cv.taps[ck];
+  const int L = cv.L[ck], M = cv.M[ck], Kc = cv.K[ck], Hh = (Kc - 2) / 2;
+  const long long P = ut.T > 0 ? (ut.T * L + M - 1) / M : 0;                 // sepr_resample_out_len
+  const long long st = clampll(start, 0, P);
+  const int rr = r >= bk.R ? bk.R - 1 : r;                                   // r >= 0 here
+  const long long h0 = clampll(bk.off[rr], 0, bk.total - 1);
+  const long long hl = clampll(bk.off[rr + 1] - h0, 1, bk.total - h0 < DR_MAX_TAPS ? bk.total - h0 : DR_MAX_TAPS);
+  const int K = taps < 1 ? 1 : (taps > (int)hl ? (int)hl : taps);            // h0 + K <= total: every tap read is inside the bank
+  const float* __restrict__ hp = bk.h + h0;
+  const int left = n - tile0;                                                // > 0: the caller returned for tiles past n
+  const int top = (DR_CHUNK - 1) + (left < DS_TILE ? left : DS_TILE);        // positions from here on reach no output below n
+  const long long Wl = ((long long)(DS_SPAN - Kc - 1) * L) / M + 1;          // ((W - 1) M) / L + K + 1 <= DS_SPAN
+  const int W = Wl > DS_SPAN ? DS_SPAN : (Wl < 1 ? 1 : (int)Wl);
+  double acc[DM_PER];
+#pragma unroll
+  for (int i = 0; i < DM_PER; ++i) acc[i] = 0.0;
+  double* __restrict__ hs = lds.a.hs;
+  double* __restrict__ ys = lds.ys;
+  const double* yp = lds.ys + tid + (DR_CHUNK - 1);
+  for (int k0 = 0; k0 < K; k0 += DR_CHUNK) {
+    const long long g0 = st + tile0 - k0 - (DR_CHUNK - 1);                  // the index of ys[0] in the perturbed utterance
+    // as in reverb_tile: a chunk whose whole span lies before perturbed sample 0 adds fma(h, 0, acc) = acc, and so do all after it
+    if (g0 + (DS_TILE + DR_CHUNK - 2) < 0) break;
+    const int kc = K - k0 < DR_CHUNK ? K - k0 : DR_CHUNK;
+    const int lo = DR_CHUNK - kc;                                            // the FIR loop reads ys[lo ..] only
+    const int ca = g0 + lo < 0 ? (int)(-g0) : lo;                            // positions [ca, cb) are converted, the rest of [lo, 3071) is zero:
+    const long long pe = P - g0;                                             // before sample 0, from sample P on, or of no use below n
+    const int cb = pe < top ? (pe < 0 ? 0 : (int)pe) : top;
+    __syncthreads();                                                         // the last readers of ys / hs (or of the float tile) are done
+    for (int i = lo + tid; i < DS_TILE + DR_CHUNK - 1; i += DM_TPB) {
+      if (i < ca || i >= cb) ys[i] = 0.0;
+    }
+    for (int i = tid; i < kc; i += DM_TPB) hs[i] = (double)hp[k0 + i];
+    for (int a = ca; a < cb; a += W) {
+      const int e = cb - a > W ? a + W : cb;
+      const long long b0 = ((g0 + a) * M) / L;                               // g0 + a >= 0
+      const long long sp = ((g0 + e - 1) * M) / L - b0 + Kc;                 // <= ((W - 1) M) / L + 1 + K <= DS_SPAN
+      const int span = sp > DS_SPAN ? DS_SPAN : (int)sp;
+      if (a != ca) __syncthreads();                                          // the pass before has read xs
+      ut.stage(c, b0 - Hh, span, lds.a.xs);
+      __syncthreads();
+      for (int i0 = a; i0 < e; i0 += DS_TILE) {
+        if (e - i0 > DS_TILE / 2) {
+          convert_group<DM_PER>(lds.a.xs, span, b0, tp, L, M, Kc, g0, i0, e - i0 > DS_TILE ? i0 + DS_TILE : e, ys);
+        } else {
+          convert_group<DM_PER / 2>(lds.a.xs, span, b0, tp, L, M, Kc, g0, i0, e, ys);
+        }
+      }
+    }
+    __syncthreads();
+    if (tid < left) {                                                        // (per wave: whole waves past n skip the loop)
+#pragma unroll 4
+      for (int j = 0; j < kc; ++j) {
+        const double hj = hs[j];
+#pragma unroll
+        for (int i = 0; i < DM_PER; ++i) acc[i] = fma(hj, yp[i * DM_TPB - j], acc[i]);
+      }
+    }
+  }
+  __syncthreads();                                                           // hs has been read: it becomes the float tile
+  tile_out8(acc, reinterpret_cast<float*>(hs), x8);
+}
+
+// a term may carry a converter (conv >= 0), a response (rir >= 0), both or neither.  One of the two alone takes the code of the form that has
+// only that one (convert_tile, reverb_tile) in the first 32 768 bytes of the LDS, neither takes term_value: each with that form's bits.
+struct SpeedReverbForm {
+  static constexpr bool kTiled = true;
+  DmCorpus c;
+  DsConv cv;
+  DrBank bk;
+  struct Cols {
+    int conv, rir, taps;
+  };
+  __device__ __forceinline__ static Cols cols(const int* __restrict__ term_conv, const int* __restrict__ term_rir,
+                                              const int* __restrict__ term_taps, int j) {
+    return {__builtin_amdgcn_readfirstlane(term_conv[j]), __builtin_amdgcn_readfirstlane(term_rir[j]),
+            __builtin_amdgcn_readfirstlane(term_taps[j])};
+  }
+  __device__ __forceinline__ static bool same(Cols a, Cols b) { return a.conv == b.conv && a.rir == b.rir && a.taps == b.taps; }
+  __device__ __forceinline__ void value8(int utt, int start, float norm, float gain, Cols t, int tile0, int t0, int n, float v[8]) const {
+    const bool perturbed = t.conv >= 0 && cv.NC >= 1;
+    if (!perturbed && t.rir < 0) {
+      term_value(c, utt, start, norm, gain, t0 < n ? t0 : 0, v);
+      return;
+    }
+    __shared__ SrLds lds;
+    float x[8];
+    if (!perturbed) {
+      reverb_tile(c, bk, t.rir, t.taps, utt, start, tile0, n, lds.a, x);
+    } else if (t.rir < 0) {
+      const int k = t.conv >= cv.NC ? cv.NC - 1 : t.conv;
+      float* ys = reinterpret_cast<float*>(lds.a.hs);
+      convert_tile(c, utt, start, cv.taps[k], cv.L[k], cv.M[k], cv.K[k], tile0, n, lds.a.xs, ys);
+      const float4 lo = *reinterpret_cast<const float4*>(ys + threadIdx.x * DM_PER);
+      const float4 hi = *reinterpret_cast<const float4*>(ys + threadIdx.x * DM_PER + 4);
+      x[0] = lo.x, x[1] = lo.y, x[2] = lo.z, x[3] = lo.w, x[4] = hi.x, x[5] = hi.y, x[6] = hi.z, x[7] = hi.w;
+    } else {
+      speed_reverb_tile(c, cv, bk, t.conv, t.rir, t.taps, utt, start, tile0, n, lds, x);
+    }
+    scale8(x, norm, gain, v);
+  }
+};
+
 template <class F>
 __device__ __forceinline__ int uniform(int v) {
   return F::kTiled ? __builtin_amdgcn_readfirstlane(v) : v;
@@ -570,7 +736,7 @@ extern "C" int sepr_corpus_energy(const short* buf16, long long total16, const f
 
 namespace sepr {
 namespace {
-// what the three mixing entries share: the checks of the common arguments, the corpus and the target rows as kernel arguments, the grid,
+// what the four mixing entries share: the checks of the common arguments, the corpus and the target rows as kernel arguments, the grid,
 // the dispatch on S and the launch check.  An entry checks its own arguments BEFORE it calls this and passes them in `form` and `col`;
 // every refusal is SEPR_EINVAL, so which check comes first does not show.
 template <class F, class... Col>
@@ -591,7 +757,7 @@ int dynmix_launch(const short* buf16, long long total16, const float* buf32, lon
   hipStream_t st = static_cast<hipStream_t>(stream);
   form.c = {buf16, buf32, offsets, total16, total32, N16, N};
   const dim3 grid((unsigned)cdiv(Tmax, DS_TILE), (unsigned)B);
-  // `head`: the kernel's leading arguments, its corpus and banks; `col`: term_conv (speed), term_rir and term_taps (reverb), none (plain)
+  // `head`: the kernel's leading arguments, its corpus and banks; `col`: term_conv (speed), term_rir and term_taps (reverb), all three (speed-reverb), none (plain)
   auto go = [&](auto kernel, const auto&... head) {
     hipLaunchKernelGGL(kernel, grid, dim3(DM_TPB), 0, st, head..., term_utt, term_start, term_norm, term_gain, col..., n, M, Tmax, mix, rows);
   };
@@ -601,6 +767,30 @@ int dynmix_launch(const short* buf16, long long total16, const float* buf32, lon
     S == 2 ? go(dynmix_kernel<2, F, Col...>, form) : go(dynmix_kernel<3, F, Col...>, form);
   SEPR_CHECK_LAUNCH(what);
   return SEPR_OK;
+}
+
+// the converter arguments of the speed entries, checked and copied into cv; 0 = fine
+int converters_bad(const float* const* conv_taps, const int* conv_L, const int* conv_M, const int* conv_K, int NC, DsConv& cv) {
+  if (NC < 0 || NC > DS_MAX_NC) return 1;
+  if (NC > 0 && (!conv_taps || !conv_L || !conv_M || !conv_K)) return 1;
+  cv.NC = NC;
+  for (int k = 0; k < NC; ++k) {
+    if (!conv_taps[k] || conv_L[k] < 1 || conv_M[k] < 1 || conv_K[k] < 1 || conv_K[k] % 2 != 0) return 1;
+    if (ds_span(conv_L[k], conv_M[k], conv_K[k]) > DS_SPAN) return 1;        // the tile's input span exceeds the kernel's LDS plan
+    cv.taps[k] = conv_taps[k];
+    cv.L[k] = conv_L[k];
+    cv.M[k] = conv_M[k];
+    cv.K[k] = conv_K[k];
+  }
+  return 0;
+}
+
+// the bank arguments of the reverberant entries, checked and copied into bk; 0 = fine
+int bank_bad(const float* rir, long long rir_total, const long long* rir_off, int R, DrBank& bk) {
+  if (!rir || !rir_off || R < 1 || rir_total < 1) return 1;
+  if (reinterpret_cast<uintptr_t>(rir) % 4 != 0) return 1;
+  bk = {rir, rir_off, rir_total, R};
+  return 0;
 }
 }  // namespace
 }  // namespace sepr
@@ -619,18 +809,8 @@ extern "C" int sepr_dynmix_speed_fwd(const short* buf16, long long total16, cons
                                      float* const* src, const float* const* conv_taps, const int* conv_L, const int* conv_M, const int* conv_K,
                                      int NC, sepr_stream_t stream) {
   using namespace sepr;
-  if (!term_conv || NC < 0 || NC > DS_MAX_NC) return SEPR_EINVAL;
-  if (NC > 0 && (!conv_taps || !conv_L || !conv_M || !conv_K)) return SEPR_EINVAL;
   SpeedForm form = {};
-  form.cv.NC = NC;
-  for (int k = 0; k < NC; ++k) {
-    if (!conv_taps[k] || conv_L[k] < 1 || conv_M[k] < 1 || conv_K[k] < 1 || conv_K[k] % 2 != 0) return SEPR_EINVAL;
-    if (ds_span(conv_L[k], conv_M[k], conv_K[k]) > DS_SPAN) return SEPR_EINVAL;   // the tile's input span exceeds the kernel's LDS plan
-    form.cv.taps[k] = conv_taps[k];
-    form.cv.L[k] = conv_L[k];
-    form.cv.M[k] = conv_M[k];
-    form.cv.K[k] = conv_K[k];
-  }
+  if (!term_conv || converters_bad(conv_taps, conv_L, conv_M, conv_K, NC, form.cv)) return SEPR_EINVAL;
   return dynmix_launch(buf16, total16, buf32, total32, offsets, N16, N, term_utt, term_start, term_norm, term_gain, n, B, M, S, Tmax, mix, src,
                        stream, form, "dynmix speed kernel", term_conv);
 }
@@ -641,10 +821,22 @@ extern "C" int sepr_dynmix_reverb_fwd(const short* buf16, long long total16, con
                                       int Tmax, float* mix, float* const* src, const float* rir, long long rir_total, const long long* rir_off,
                                       int R, sepr_stream_t stream) {
   using namespace sepr;
-  if (!term_rir || !term_taps || !rir || !rir_off || R < 1 || rir_total < 1) return SEPR_EINVAL;
-  if (reinterpret_cast<uintptr_t>(rir) % 4 != 0) return SEPR_EINVAL;
   ReverbForm form = {};
-  form.bk = {rir, rir_off, rir_total, R};
+  if (!term_rir || !term_taps || bank_bad(rir, rir_total, rir_off, R, form.bk)) return SEPR_EINVAL;
   return dynmix_launch(buf16, total16, buf32, total32, offsets, N16, N, term_utt, term_start, term_norm, term_gain, n, B, M, S, Tmax, mix, src,
                        stream, form, "dynmix reverb kernel", term_rir, term_taps);
+}
+
+extern "C" int sepr_dynmix_speed_reverb_fwd(const short* buf16, long long total16, const float* buf32, long long total32, const long long* offsets,
+                                            int N16, int N, const int* term_utt, const int* term_start, const float* term_norm,
+                                            const float* term_gain, const int* term_conv, const int* term_rir, const int* term_taps, const int* n,
+                                            int B, int M, int S, int Tmax, float* mix, float* const* src, const float* const* conv_taps,
+                                            const int* conv_L, const int* conv_M, const int* conv_K, int NC, const float* rir, long long rir_total,
+                                            const long long* rir_off, int R, sepr_stream_t stream) {
+  using namespace sepr;
+  SpeedReverbForm form = {};
+  if (!term_conv || converters_bad(conv_taps, conv_L, conv_M, conv_K, NC, form.cv)) return SEPR_EINVAL;
+  if (!term_rir || !term_taps || bank_bad(rir, rir_total, rir_off, R, form.bk)) return SEPR_EINVAL;
+  return dynmix_launch(buf16, total16, buf32, total32, offsets, N16, N, term_utt, term_start, term_norm, term_gain, n, B, M, S, Tmax, mix, src,
+                       stream, form, "dynmix speed-reverb kernel", term_conv, term_rir, term_taps);
 }

@@ -26,6 +26,10 @@ Reverberation: the same three planners take ``rirs=`` (
 source; a reverberant term is the stored utterance convolved with the first ``taps`` samples of that response inside the mixing launch
 (``sepr_dynmix_reverb_fwd``) - the whole response in the mixture, by default its direct path in the target.
 
+Both: with ``speed_reverb=True`` the three planners take ``speeds=`` and ``rirs=`` together; a term that carries both is
+the PERTURBED utterance under the response - the talker speaks faster or slower, then the room answers - made inside the one launch
+(``sepr_dynmix_speed_reverb_fwd``).
+
 Shuffling: the reference shuffles through ``DataLoader(shuffle=True)`` (torch's generator); this feed takes the epoch's key order
 from the caller (``keys=``), and by default draws a permutation from its own ``random.Random`` before every epoch.
 """
@@ -44,7 +48,7 @@ from . import resample as R_
 from .reverb import RirBank
 
 # (utterance index, start sample, norm factor, gain), plus the speed in percent when the planner was given speeds, or plus
-# (100, RIR index or -1, taps) when it was given an RIR bank
+# (speed, RIR index or -1, taps) when it was given an RIR bank - the speed 100 unless it was given both (speed_reverb=True)
 Term = Union[Tuple[int, int, np.float32, np.float32], Tuple[int, int, np.float32, np.float32, int],
              Tuple[int, int, np.float32, np.float32, int, int, int]]
 MAX_CONVERTERS = 16                                     # converters one sepr_dynmix_speed_fwd call takes
@@ -282,12 +286,12 @@ def _draw_speeds(rng: random.Random, speeds: Optional[Sequence[int]], count: int
     return [int(rng.choice(speeds)) for _ in range(count)]
 
 
-def _draw_rirs(rng: random.Random, rirs: Optional[RirBank], speeds, count: int) -> Optional[List[int]]:
-    """One ``rng.randrange(len(rirs))`` per source, in source order; no draw without a bank."""
+def _draw_rirs(rng: random.Random, rirs: Optional[RirBank], speeds, count: int, speed_reverb: bool = False) -> Optional[List[int]]:
+    """One ``rng.randrange(len(rirs))`` per source, in source order; no draw without a bank.  With speeds it takes ``speed_reverb``."""
     if rirs is None:
         return None
-    if speeds is not None:
-        raise ValueError("speeds and rirs in one plan are not built: pass one of them")
+    if speeds is not None and not speed_reverb:
+        raise ValueError("speeds and rirs in one plan: pass one of them, or speed_reverb=True to perturb each source and then reverberate it")
     return [rng.randrange(len(rirs)) for _ in range(count)]
 
 
@@ -323,7 +327,7 @@ _NO_RIR = (-1, 1)                                      # a term that is not reve
 
 def _terms(utts, starts, norms, gains, sp, rv=None) -> Tuple[Term, ...]:
     if rv is not None:
-        return tuple((u, s, nf, g, 100, r, k) for u, s, nf, g, (r, k) in zip(utts, starts, norms, gains, rv))
+        return tuple((u, s, nf, g, p, r, k) for u, s, nf, g, p, (r, k) in zip(utts, starts, norms, gains, sp or [100] * len(rv), rv))
     if sp is None:
         return tuple((u, s, nf, g) for u, s, nf, g in zip(utts, starts, norms, gains))
     return tuple((u, s, nf, g, p) for u, s, nf, g, p in zip(utts, starts, norms, gains, sp))
@@ -331,12 +335,15 @@ def _terms(utts, starts, norms, gains, sp, rv=None) -> Tuple[Term, ...]:
 
 def plan_wsj0(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs: Sequence[str] = ("s1", "s2"),
               accept: Callable[[str, str], bool] = wsj0_distinct_speakers, crop: bool = True,
-              speeds: Optional[Sequence[int]] = None, rirs: Optional[RirBank] = None, target: Union[str, int] = "direct") -> Example:
+              speeds: Optional[Sequence[int]] = None, rirs: Optional[RirBank] = None, target: Union[str, int] = "direct",
+              speed_reverb: bool = False) -> Example:
     """``SepReformer_Large_DM_WSJ0/dataset.py:84-139``.  ``crop=False`` is the reference's "test" partition (no ``max_len`` crop).
     ``speeds``: directly after the draw that orders the two sources, one ``rng.choice(speeds)`` per source; the perturbed lengths
     replace the stored ones, the norm factors keep the stored utterances' RMS (section 5e-2).  ``rirs``: at that same position, one
     ``rng.randrange(len(rirs))`` per source; the mixture terms take the whole impulse response, the target terms what ``target`` says
-    (``_target_rv``); lengths and norm factors stay the stored utterances' (section 5e-3)."""
+    (``_target_rv``); lengths and norm factors stay the stored utterances' (section 5e-3).  Both take ``speed_reverb=True``: the speeds are
+    drawn first, then the responses; every later draw uses the perturbed lengths; a source term is the perturbed utterance under the
+    whole response and its target the same speed under what ``target`` says (section 5e-5)."""
     keys = corpus.roles[srcs[0]]
     while True:
         key_random = rng.choice(keys)
@@ -344,7 +351,7 @@ def plan_wsj0(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs: 
             break
     i1, i2 = (0, 1) if rng.random() > 0.5 else (1, 0)
     sp = _draw_speeds(rng, speeds, 2)
-    rv = _draw_rirs(rng, rirs, speeds, 2)
+    rv = _draw_rirs(rng, rirs, speeds, 2, speed_reverb)
     utts = [corpus.lookup(srcs[i1], key), corpus.lookup(srcs[i2], key_random)]
     ref = corpus.rms[utts[0]]
     norms = [_norm(ref, corpus.rms[u]) for u in utts]
@@ -357,21 +364,23 @@ def plan_wsj0(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs: 
         st = rng.randint(0, n - max_len)
         starts, n = [s + st for s in starts], max_len
     if rv is not None:
-        return Example(key, n, _terms(utts, starts, norms, gains, None, _mix_rv(rirs, rv)),
-                       _terms(utts, starts, norms, gains, None, _target_rv(rirs, rv, target)))
+        return Example(key, n, _terms(utts, starts, norms, gains, sp, _mix_rv(rirs, rv)),
+                       _terms(utts, starts, norms, gains, sp, _target_rv(rirs, rv, target)))
     terms = _terms(utts, starts, norms, gains, sp)
     return Example(key, n, terms, terms)
 
 
 def plan_wham(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs: Sequence[str] = ("s1", "s2"), noise: str = "noise",
-              speeds: Optional[Sequence[int]] = None, rirs: Optional[RirBank] = None, target: Union[str, int] = "direct") -> Example:
+              speeds: Optional[Sequence[int]] = None, rirs: Optional[RirBank] = None, target: Union[str, int] = "direct",
+              speed_reverb: bool = False) -> Example:
     """``SepReformer_Large_DM_WHAM/dataset.py``: no speaker rule, the noise of ``key`` normalised to the first source with a gain of
     its own from U(-5, 5) dB, everything cropped to ``min(max_len, lengths)`` at independent random indices.  ``speeds``: as in
-    ``plan_wsj0``; the noise is not perturbed.  ``rirs`` / ``target``: as in ``plan_wsj0``; the noise is not reverberated."""
+    ``plan_wsj0``; the noise is not perturbed.  ``rirs`` / ``target`` / ``speed_reverb``: as in ``plan_wsj0``; the noise is not
+    reverberated."""
     key_random = rng.choice(corpus.roles[srcs[0]])
     i1, i2 = (0, 1) if rng.random() > 0.5 else (1, 0)
     sp = _draw_speeds(rng, speeds, 2)
-    rv = _draw_rirs(rng, rirs, speeds, 2)
+    rv = _draw_rirs(rng, rirs, speeds, 2, speed_reverb)
     utts = [corpus.lookup(srcs[i1], key), corpus.lookup(srcs[i2], key_random)]
     ref = corpus.rms[utts[0]]
     norms = [_norm(ref, corpus.rms[u]) for u in utts]
@@ -387,24 +396,25 @@ def plan_wham(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs: 
     starts = [rng.randint(0, ln - min_len) for ln in lens]
     n = min_len - min_len % 4
     if rv is not None:
-        return Example(key, n, _terms(utts, starts, norms, gains, None, _mix_rv(rirs, rv) + [_NO_RIR]),
-                       _terms(utts[:2], starts, norms, gains, None, _target_rv(rirs, rv, target)))
+        return Example(key, n, _terms(utts, starts, norms, gains, sp, _mix_rv(rirs, rv) + [_NO_RIR]),
+                       _terms(utts[:2], starts, norms, gains, sp, _target_rv(rirs, rv, target)))
     terms = _terms(utts, starts, norms, gains, sp)
     return Example(key, n, terms, terms[:2])
 
 
 def plan_whamr(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs: Sequence[str] = ("s1", "s2"),
                reverb: Sequence[str] = ("s1_reverb", "s2_reverb"), noise: str = "noise", speeds: Optional[Sequence[int]] = None,
-               rirs: Optional[RirBank] = None, target: Union[str, int] = "direct") -> Example:
+               rirs: Optional[RirBank] = None, target: Union[str, int] = "direct", speed_reverb: bool = False) -> Example:
     """``SepReformer_Large_DM_WHAMR/dataset.py:87-154``: the mixture is the two reverberant twins plus the noise (gains U(-3, 3) dB,
     noise U(-6, 3) dB), the targets are the anechoic sources with their twins' norm factor, gain and crop index.  ``speeds``: as in
     ``plan_wsj0``; a dry source and its reverberant twin share one speed, the noise is not perturbed.  ``rirs`` / ``target``: as in
     ``plan_wsj0``; the mixture is then the DRY sources reverberated in the launch plus the noise, and the ``reverb`` roles are never
-    looked up - a corpus without pre-rendered twins serves."""
+    looked up - a corpus without pre-rendered twins serves.  ``speed_reverb=True`` with both: the dry sources perturbed and then
+    reverberated in the launch (playing a pre-rendered twin faster, the other order, is ``speeds=`` alone)."""
     key_random = rng.choice(corpus.roles[srcs[0]])
     i1, i2 = (0, 1) if rng.random() > 0.5 else (1, 0)
     sp = _draw_speeds(rng, speeds, 2)
-    rv = _draw_rirs(rng, rirs, speeds, 2)
+    rv = _draw_rirs(rng, rirs, speeds, 2, speed_reverb)
     dry = [corpus.lookup(srcs[i1], key), corpus.lookup(srcs[i2], key_random)]
     wet = dry if rv is not None else [corpus.lookup(reverb[i1], key), corpus.lookup(reverb[i2], key_random)]
     for d, w in zip(dry, wet):
@@ -421,8 +431,9 @@ def plan_whamr(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs:
     nstart = rng.randint(0, int(corpus.lengths[un]) - min_len)
     n = min_len - min_len % 4
     if rv is not None:
-        return Example(key, n, _terms(dry + [un], starts + [nstart], norms + [nnorm], gains + [ngain], None, _mix_rv(rirs, rv) + [_NO_RIR]),
-                       _terms(dry, starts, norms, gains, None, _target_rv(rirs, rv, target)))
+        return Example(key, n, _terms(dry + [un], starts + [nstart], norms + [nnorm], gains + [ngain], None if sp is None else sp + [100],
+                                      _mix_rv(rirs, rv) + [_NO_RIR]),
+                       _terms(dry, starts, norms, gains, sp, _target_rv(rirs, rv, target)))
     mix = _terms(wet + [un], starts + [nstart], norms + [nnorm], gains + [ngain], None if sp is None else sp + [100])
     tgt = _terms(dry, starts, norms, gains, sp)
     return Example(key, n, mix, tgt)
@@ -448,9 +459,11 @@ def plan_direct(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs
     return Example(key, n, mixt, tgt)
 
 
-def collate_plan(corpus: Corpus, examples: Sequence[Example], rirs: Optional[RirBank] = None) -> BatchPlan:
+def collate_plan(corpus: Corpus, examples: Sequence[Example], rirs: Optional[RirBank] = None, speed_reverb: bool = False) -> BatchPlan:
     """Order the examples by length, longest first (``_collate``'s stable ``sorted(..., reverse=True)``), check every term against its
-    utterance - and, for a reverberant term, against the bank ``rirs`` - and lay the table out as the kernel reads it."""
+    utterance - at its speed - and, for a reverberant term, against the bank ``rirs``, and lay the table out as the kernel reads it.
+    ``speed_reverb``: terms may carry a speed and a response; a plan with responses then has ``speed``, ``rir`` and ``taps`` all set, whatever
+    speeds were drawn (so the batches of one feed share one table layout and one entry)."""
     egs = sorted(examples, key=lambda e: e.n, reverse=True)
     M, S = len(egs[0].mix), len(egs[0].tgt)
     if not (2 <= S <= 3 and S <= M <= S + 1):
@@ -482,8 +495,9 @@ def collate_plan(corpus: Corpus, examples: Sequence[Example], rirs: Optional[Rir
             if not (0 <= u < len(corpus)) or p < 1 or s < 0 or s + e.n > perturbed_len(corpus.lengths[u], p):
                 raise ValueError(f"{e.key}: term {j} reads [{s}, {s + e.n}) of utterance {u}" + (f" at {p} % speed" if p != 100 else ""))
             utt[b, j], start[b, j], norm[b, j], gain[b, j], speed[b, j] = u, s, nf, g, p
-    if any_speed and any_rir:
-        raise ValueError("a plan with speeds and RIRs is not built: pass one of them")
+    if any_speed and any_rir and not speed_reverb:
+        raise ValueError("a plan with speeds and RIRs takes speed_reverb=True (each source perturbed, then reverberated)")
+    any_speed |= any_rir and speed_reverb
     return BatchPlan([e.key for e in egs], np.array([e.n for e in egs], np.int32), utt, start, norm, gain, M, S, speed if any_speed else None,
                      rir if any_rir else None, taps if any_rir else None)
 
@@ -527,7 +541,7 @@ def mix_batch(corpus: Corpus, plan: BatchPlan, Tmax: Optional[int] = None, mix: 
               speeds: Optional[Sequence[int]] = None, rirs: Optional[RirBank] = None):
     """One ``sepr_dynmix_fwd`` launch for ``plan`` on the corpus's device (current stream) -> ``(mix [B, Tmax], [src_s [B, Tmax]])``;
     a plan that carries speeds goes through ``sepr_dynmix_speed_fwd``, one that carries RIRs through ``sepr_dynmix_reverb_fwd`` with the
-    bank ``rirs``, which must be on the corpus's device.  ``table``: an int32 device tensor that already holds the plan in
+    bank ``rirs``, which must be on the corpus's device, one that carries both through ``sepr_dynmix_speed_reverb_fwd``.  ``table``: an int32 device tensor that already holds the plan in
     the kernel's layout (``DynamicMixFeed`` stages it through pinned memory); without it the plan is copied from pageable memory.
     ``speeds``: the converter set the table's index block refers to (``pack_table``); default: the plan's own speeds.  A captured launch
     keeps the set it was captured with, so a table rewritten between replays must be packed against that set."""
@@ -539,8 +553,6 @@ def mix_batch(corpus: Corpus, plan: BatchPlan, Tmax: Optional[int] = None, mix: 
     if Tmax % 4 or int(plan.n.max()) > Tmax:
         raise ValueError(f"Tmax = {Tmax} must be a multiple of 4 and hold the longest example ({int(plan.n.max())})")
     if plan.rir is not None:
-        if plan.speed is not None:
-            raise ValueError("a plan with speeds and RIRs is not built")
         if rirs is None:
             raise ValueError("the plan carries RIRs: pass the bank (rirs=)")
         if not _same_device(rirs.device, dev):
@@ -562,7 +574,10 @@ def mix_batch(corpus: Corpus, plan: BatchPlan, Tmax: Optional[int] = None, mix: 
     at = {name: table.data_ptr() + 4 * first for name, (first, _) in table_layout(B, NT, plan.speed is not None, plan.rir is not None).items()}
     rows = (C.c_void_p * plan.S)(*[t.data_ptr() for t in src])
     entry, cols, own = "sepr_dynmix_fwd", (), ()        # the entry, the table columns of its form, the form's own arguments
-    if plan.rir is not None:
+    if plan.rir is not None and plan.speed is not None:
+        entry, cols = "sepr_dynmix_speed_reverb_fwd", (at["conv"], at["rir"], at["taps"])
+        own = (*_converter_args(dev, plan_speeds(plan) if speeds is None else speeds), *rirs._bank_args())
+    elif plan.rir is not None:
         entry, cols, own = "sepr_dynmix_reverb_fwd", (at["rir"], at["taps"]), rirs._bank_args()
     elif plan.speed is not None:
         entry, cols, own = "sepr_dynmix_speed_fwd", (at["conv"],), _converter_args(dev, plan_speeds(plan) if speeds is None else speeds)
@@ -594,7 +609,8 @@ class DynamicMixFeed:
 
     ``planner(corpus, rng, key, max_len) -> Example`` is one of ``plan_wsj0`` / ``plan_wham`` / ``plan_whamr`` / ``plan_direct`` (bind
     other role names, or ``speeds=range(95, 106)`` for speed perturbation, with ``functools.partial``; for reverberation bind ``rirs=bank`` and
-    pass the same bank as the feed's ``rirs=``).  Per batch: plan on the host, write the table into a pinned staging buffer, one
+    pass the same bank as the feed's ``rirs=``; for both bind ``speed_reverb=True`` as well - the feed reads the flag from the
+    ``functools.partial`` and passes it to ``collate_plan``; a planner wrapped otherwise says it with the feed's ``speed_reverb=``).  Per batch: plan on the host, write the table into a pinned staging buffer, one
     asynchronous copy into the static device table, one launch - all on the current stream, nothing waits for the device.
     ``keys``: the epoch's key order, used as given every epoch; default: the keys of the corpus's first role, permuted with the
     feed's ``random.Random(seed)`` before each epoch (the same generator then makes the examples' draws).  ``rank`` / ``world``:
@@ -609,7 +625,7 @@ class DynamicMixFeed:
 
     def __init__(self, corpus: Corpus, planner: Callable[..., Example], batch: int, max_len: int, seed: int = 0,
                  keys: Optional[Sequence[str]] = None, fixed_length: bool = False, rank: int = 0, world: int = 1,
-                 rirs: Optional[RirBank] = None, rooms=None, rooms_every: int = 1):
+                 rirs: Optional[RirBank] = None, rooms=None, rooms_every: int = 1, speed_reverb: Optional[bool] = None):
         if corpus.device is None:
             raise RuntimeError("DynamicMixFeed needs a corpus on the HIP device (there is no CPU path)")
         if rirs is not None and not _same_device(rirs.device, corpus.device):
@@ -630,6 +646,9 @@ class DynamicMixFeed:
             if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or int(seed) < 0:
                 raise ValueError("rooms= needs a non-negative integer seed (the rooms of an epoch are drawn from (seed, epoch))")
         self.rooms, self.rooms_every, self.seed, self.epoch = rooms, int(rooms_every), seed, 0
+        if speed_reverb is None:                        # the flag the user bound on the planner
+            speed_reverb = (getattr(planner, "keywords", None) or {}).get("speed_reverb", False)
+        self.speed_reverb = bool(speed_reverb)
         self.rng = random.Random(seed)
         self.keys = None if keys is None else list(keys)
         self._default_keys = list(next(iter(corpus.roles.values()))) if corpus.roles else None
@@ -667,7 +686,8 @@ class DynamicMixFeed:
         self._begin_epoch()
         order = self.epoch_order()
         for i in range(0, len(order) - self.batch + 1, self.batch):
-            yield collate_plan(self.corpus, [self.planner(self.corpus, self.rng, k, self.max_len) for k in order[i:i + self.batch]], self.rirs)
+            yield collate_plan(self.corpus, [self.planner(self.corpus, self.rng, k, self.max_len) for k in order[i:i + self.batch]], self.rirs,
+                               self.speed_reverb)
 
     # ---- device side -------------------------------------------------------------------------------------------------------
     def _launch(self, plan: BatchPlan, mix=None, src=None):

@@ -25,12 +25,18 @@ hipEvent time of one ``sepr_rir_ism_fwd`` call for COUNT rooms, the numpy restat
 responses beside the nominal RT60, and the bf16 training step fed from a fixed simulated bank against the same feed re-simulating its
 rooms every epoch (three steps here), alternating.  Condition: one simulation takes less than one training step of the same run.
 
+``--speeds 95:105 --rirs 64:0.6`` together measure both in one source (section 5e-5), in one child process with the settings alternating:
+the combined launch (each source perturbed, then under a whole response of RT60 seconds; direct-path targets at the same speed) beside the
+reverb-only and the speed-only launch of the same plan shapes (WHAMR form, B = 16 and 32 x 4 s), and the bf16 training step fed with
+reverberation alone and with both; the reverb-fed step of that same run is the yardstick.
+
 Every step runs in a child process of its own under ``timeout -k 10 <s>``; the first step that fails ends the run.
 
     python tools/dynmix_bench.py [--out profiles/dynmix_timing.json]
     python tools/dynmix_bench.py --speeds 95:105 [--out profiles/dynmix_speed.json]
     python tools/dynmix_bench.py --rirs 64:0.6 [--out profiles/dynmix_reverb.json]
     python tools/dynmix_bench.py --room-rirs 64:0.2:0.6 [--out profiles/rir_ism.json]
+    python tools/dynmix_bench.py --speeds 95:105 --rirs 64:0.6 [--out profiles/dynmix_speed_reverb.json]
 """
 import argparse
 import json
@@ -366,6 +372,147 @@ def step_reverb(spec):
                      "host_plan_ms_per_batch": plan_ms}}
 
 
+def _fed_loops(corpus, feeds):
+    """The bf16 training step (Base, batch 16 x 4 s, CapturedTrainStep + FlatAdamW, the reference's loss) fed by each of ``feeds`` in turn:
+    LOOP_RUNS runs of LOOP_STEPS steps per feed, alternating, after one warming run each.  -> ({name: [ms per step]}, {name: host ms per plan})."""
+    import numpy as np
+    import torch
+    from sepreformer_amd.config import VARIANTS
+    from sepreformer_amd.criterion import PIT_SISNR_mag, PIT_SISNR_time
+    from sepreformer_amd.model import Model
+    from sepreformer_amd.optim import FlatAdamW
+    from sepreformer_amd.train_step import CapturedTrainStep
+    dev, B = corpus.device, 16
+    cfg = VARIANTS["SepReformer_Base_WSJ0"]
+    torch.manual_seed(0)
+    model = Model.from_config(cfg, init_seed=0, precision="bf16").load_synthetic_(0).to(dev).train()
+    crit_t = PIT_SISNR_time(dev, cfg.num_spks, True)
+    crit_m = PIT_SISNR_mag(dev, 512, 128, "hann", cfg.num_stages, cfg.num_spks, True, False)
+    sizes = torch.full((B,), T4S)
+    opt = FlatAdamW(model, lr=1.0e-4, weight_decay=1.0e-2)
+
+    def loss_fn(audio, aux, *tg):
+        tg = list(tg)
+        l_time = crit_t(estims=audio, input_sizes=sizes, target_attr=tg)
+        l_mag = [crit_m(estims=a, idx=i, input_sizes=sizes, target_attr=tg) for i, a in enumerate(aux)]
+        return (0.6 * l_time + 0.4 * sum(l_mag) / len(l_mag)) / cfg.num_spks
+
+    x = torch.zeros(B, T4S, device=dev)
+    tg = [torch.zeros(B, T4S, device=dev) for _ in range(2)]
+    next(iter(feeds.values())).next_into(x, tg)
+    step = CapturedTrainStep(model, loss_fn, opt, x, tg, max_norm=5.0, warmup=2)
+
+    def loop(feed):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(LOOP_STEPS):
+            feed.next_into(step.x, step.targets)
+            loss, _ = step(step.x, step.targets)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / LOOP_STEPS, float(loss.detach())
+
+    for f in feeds.values():
+        loop(f)                                                               # warm every path
+    runs = {name: [] for name in feeds}
+    losses = []
+    for _ in range(LOOP_RUNS):
+        for name, f in feeds.items():
+            ms, ls = loop(f)
+            runs[name].append(ms)
+            losses.append(ls)
+    plan_ms = {}
+    for name, f in feeds.items():
+        t0 = time.perf_counter()
+        for _ in range(50):
+            f.next_plan()
+        plan_ms[name] = (time.perf_counter() - t0) * 1e3 / 50
+    step.release()
+    assert all(np.isfinite(v) for v in losses)
+    return runs, plan_ms
+
+
+def step_speed_reverb(speeds, spec):
+    """The combined launch beside the reverb-only and the speed-only launch of the same plan shapes, and the training step fed with
+    reverberation alone and with both; everything alternating."""
+    import functools
+    import numpy as np
+    import torch
+    from sepreformer_amd import datafeed as df
+    from sepreformer_amd.reverb import RirBank, parse_synthetic, synthetic_rirs
+    count, rt_lo, rt_hi = parse_synthetic(spec)
+    dev = torch.device("cuda:0")
+    keys, arrays = synth_corpus_arrays()
+    corpus = df.Corpus.from_arrays(arrays, device=dev, fs=FS)
+    corpus.roles = {r: list(keys) for r in ROLES}
+    speeds = df.parse_speeds(speeds)
+    every = [p for p in speeds if p != 100]                                   # "every source perturbed": 100 % left out of the draw
+    bank = RirBank.from_arrays(synthetic_rirs(count, FS, rt60=rt_hi, seed=0), FS, device=dev)
+    planners = {"reverb": functools.partial(df.plan_whamr, rirs=bank), "speed": functools.partial(df.plan_whamr, speeds=every),
+                "both": functools.partial(df.plan_whamr, speeds=every, rirs=bank, speed_reverb=True)}
+    DS_TILE, DR_CHUNK = 2048, 1024
+    kernel = []
+    for B in (16, 32):
+        sets = {}
+        for name, planner in planners.items():
+            rng = random.Random(B)
+            use = None if name == "speed" else bank
+            plan = df.collate_plan(corpus, [planner(corpus, rng, keys[i % NKEYS], T4S) for i in range(B)], rirs=use, speed_reverb=name == "both")
+            table = torch.from_numpy(df.pack_table(plan, every)).to(dev)
+            sets[name] = (plan, use, table, torch.empty(B, T4S, device=dev), [torch.empty(B, T4S, device=dev) for _ in range(plan.S)], [])
+        # the reverb-only and the speed-only plan again, through the COMBINED entry (all speeds 100 / all responses -1): the same bits from the
+        # new kernel's code for those terms, which says what the conversions cost beside the FIR loop inside one kernel
+        for name, extra in (("reverb", dict(speed=np.full_like(sets["reverb"][0].utt, 100))),
+                            ("speed", dict(rir=np.full_like(sets["speed"][0].utt, -1), taps=np.ones_like(sets["speed"][0].utt)))):
+            plan = sets[name][0]._replace(**extra)
+            table = torch.from_numpy(df.pack_table(plan, every)).to(dev)
+            sets[name + "_through_combined_entry"] = (plan, bank, table, torch.empty(B, T4S, device=dev),
+                                                      [torch.empty(B, T4S, device=dev) for _ in range(plan.S)], [])
+        for i in range(20 + 100):
+            for plan, use, table, mix, src, ms in sets.values():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                df.mix_batch(corpus, plan, T4S, mix, src, table=table, rirs=use, speeds=every)
+                e1.record()
+                torch.cuda.synchronize()
+                if i >= 20:
+                    ms.append(e0.elapsed_time(e1))
+        rec = {"form": "whamr", "B": B, "samples": T4S, "S": 2, "launches": 100}
+        for name, (plan, use, _, _, _, ms) in sets.items():
+            fir = conv = 0
+            for n, row_p, row_r, row_k in zip(plan.n, plan.speed if plan.speed is not None else [[100] * 5] * B,
+                                              plan.rir if plan.rir is not None else [[-1] * 5] * B, plan.taps if plan.taps is not None else [[1] * 5] * B):
+                for p, r, k in zip(row_p, row_r, row_k):
+                    K = int(df.R_.plan(int(p), 100).K) if p != 100 else 0
+                    if r >= 0:
+                        fir += int(n) * int(k)
+                    if p != 100 and r < 0:
+                        conv += int(n) * K
+                    if p != 100 and r >= 0:                                     # per tile and chunk: the 2048 + kc - 1 perturbed samples it reaches
+                        for t0 in range(0, int(n), DS_TILE):
+                            for k0 in range(0, int(k), DR_CHUNK):
+                                conv += (min(DS_TILE, int(n) - t0) + min(DR_CHUNK, int(k) - k0) - 1) * K
+            med = _stats(ms)["median"]
+            rec[name] = {"device_ms": _stats(ms), "fir_f64_fma": fir, "conversion_f64_fma_upper": conv,
+                         "Gfma_per_s_at_median": (fir + conv) / (med * 1e-3) / 1e9,
+                         "mixture_taps_mean": float(plan.taps[:, :2].mean()) if plan.taps is not None else None}
+        for name in ("reverb", "speed"):                                      # the two entries agree bit for bit where they must
+            a, b = sets[name], sets[name + "_through_combined_entry"]
+            rec[name + "_through_combined_entry"]["equals_" + name + "_entry"] = bool(torch.equal(a[3], b[3]) and
+                                                                                      all(torch.equal(x, y) for x, y in zip(a[4], b[4])))
+        kernel.append(rec)
+    loop_bank = RirBank.from_arrays(synthetic_rirs(count, FS, rt60=(rt_lo, rt_hi), seed=1), FS, device=dev)
+    feeds = {"reverb": df.DynamicMixFeed(corpus, functools.partial(df.plan_whamr, rirs=loop_bank), batch=16, max_len=T4S, seed=0, fixed_length=True,
+                                         rirs=loop_bank),
+             "both": df.DynamicMixFeed(corpus, functools.partial(df.plan_whamr, speeds=speeds, rirs=loop_bank, speed_reverb=True), batch=16,
+                                       max_len=T4S, seed=0, fixed_length=True, rirs=loop_bank)}
+    runs, plan_ms = _fed_loops(corpus, feeds)
+    return {"device": torch.cuda.get_device_name(0), "speeds": speeds,
+            "rirs": {"count": count, "rt60": [rt_lo, rt_hi], "samples": [int(loop_bank.lengths.min()), int(loop_bank.lengths.max())]}, "kernel": kernel,
+            "loop": {"model": "SepReformer_Base_WSJ0 bf16, batch 16 x 4 s, CapturedTrainStep + FlatAdamW, the reference's loss, fed in the WHAMR form",
+                     "steps_per_run": LOOP_STEPS, "reverb_ms_per_step": runs["reverb"], "both_ms_per_step": runs["both"],
+                     "host_plan_ms_per_batch": plan_ms}}
+
+
 def step_rooms(spec):
     """Simulating a bank of shoebox rooms on the device (section 5e-4): hipEvent time of one ``sepr_rir_ism_fwd`` call for COUNT rooms,
     the numpy restatement's CPU time for ONE of them (and that the two agree exactly), the realised decay of a few responses beside the
@@ -533,15 +680,16 @@ def main():
     ap.add_argument("--rirs", default=None, metavar="COUNT:RT60", help="measure reverberation by convolution (COUNT synthetic impulse responses of RT60 s)")
     ap.add_argument("--room-rirs", default=None, metavar="COUNT[:RT60LO:RT60HI]", help="measure simulating COUNT shoebox rooms on the device (image-source method)")
     args = ap.parse_args()
-    if sum(bool(v) for v in (args.speeds, args.rirs, args.room_rirs)) > 1:
-        ap.error("--speeds, --rirs and --room-rirs are measured in runs of their own")
+    both = bool(args.speeds and args.rirs)                                   # the two together: section 5e-5
+    if sum(bool(v) for v in (args.speeds, args.rirs, args.room_rirs)) > (2 if both and not args.room_rirs else 1):
+        ap.error("--speeds, --rirs and --room-rirs are measured in runs of their own (--speeds with --rirs measures both in one source)")
     if args.step:
         rec = {"device": step_device, "host": step_host, "speed": lambda: step_speed(args.speeds), "reverb": lambda: step_reverb(args.rirs),
-               "rooms": lambda: step_rooms(args.room_rirs)}[args.step]()
+               "rooms": lambda: step_rooms(args.room_rirs), "both": lambda: step_speed_reverb(args.speeds, args.rirs)}[args.step]()
         print("__RESULT__" + json.dumps(rec))
         return
     rec, failed = {}, None
-    for name, limit in ([("speed", 600)] if args.speeds else [("reverb", 600)] if args.rirs else [("rooms", 600)] if args.room_rirs else STEPS):
+    for name, limit in ([("both", 600)] if both else [("speed", 600)] if args.speeds else [("reverb", 600)] if args.rirs else [("rooms", 600)] if args.room_rirs else STEPS):
         cmd = (["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", name] + (["--speeds", args.speeds] if args.speeds else [])
                + (["--rirs", args.rirs] if args.rirs else []) + (["--room-rirs", args.room_rirs] if args.room_rirs else []))
         r = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
@@ -552,7 +700,21 @@ def main():
             break                                                          # nothing more runs on the device after a failure
         rec.update(json.loads(lines[-1][len("__RESULT__"):]))
         print(name, "done", flush=True)
-    if not failed and args.speeds:
+    if not failed and both:
+        lp = rec["loop"]
+        a, b = lp["reverb_ms_per_step"], lp["both_ms_per_step"]
+        mean = lambda v: sum(v) / len(v)                                    # noqa: E731
+        k = next(r for r in rec["kernel"] if r["B"] == 16)
+        spread = max(max(a) - min(a), max(b) - min(b))
+        med = {name: k[name]["device_ms"]["median"] for name in k if isinstance(k[name], dict)}
+        rec["summary"] = {"launch_ms_median": med, "both_minus_reverb_launch_ms": med["both"] - med["reverb"],
+                          "both_minus_reverb_through_combined_entry_ms": med["both"] - med["reverb_through_combined_entry"],
+                          "conversion_fma_upper_over_fir_fma": k["both"]["conversion_f64_fma_upper"] / k["both"]["fir_f64_fma"],
+                          "launch_excess_over_reverb": med["both"] / med["reverb"] - 1.0,
+                          "reverb_step_ms_mean": mean(a), "both_step_ms_mean": mean(b), "difference_ms": mean(b) - mean(a),
+                          "reverb_step_spread_ms": max(a) - min(a), "both_step_spread_ms": max(b) - min(b),
+                          "both_exceeds_reverb_by_more_than_the_larger_spread": mean(b) - mean(a) > spread}
+    elif not failed and args.speeds:
         lp = rec["loop"]
         a, b = lp["plain_ms_per_step"], lp["speeds_ms_per_step"]
         mean = lambda v: sum(v) / len(v)                                    # noqa: E731

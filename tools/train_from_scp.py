@@ -9,6 +9,7 @@ loss and utt/s every ``--log`` steps.  Schedulers, checkpoints and validation ar
     python tools/train_from_scp.py --form whamr --scp s1=.. s2=.. noise=.. --rir-scp rirs.scp        # reverberation in the launch (section 5e-3)
     python tools/train_from_scp.py --form whamr --scp s1=.. s2=.. noise=.. --synthetic-rirs 64:0.2:0.8
     python tools/train_from_scp.py --form whamr --scp s1=.. s2=.. noise=.. --room-rirs 64:0.2:0.6     # simulated rooms, redrawn per epoch (section 5e-4)
+    python tools/train_from_scp.py --form whamr --scp s1=.. s2=.. noise=.. --room-rirs 64:0.2:0.6 --speeds 95:105      # each source perturbed, then reverberated (section 5e-5)
 """
 import argparse
 import os
@@ -30,7 +31,8 @@ def main():
     ap.add_argument("--fs", type=int, default=8000)
     ap.add_argument("--resample", action="store_true", help="convert files at another rate on the device (default: an error)")
     ap.add_argument("--speeds", default=None, metavar="LO:HI", help="speed perturbation: one speed in percent per source and example, drawn from "
-                    "the inclusive range LO:HI or from a comma list (default: off)")
+                    "the inclusive range LO:HI or from a comma list (default: off); together with one of the RIR options each source is perturbed first and "
+                    "reverberated second, inside the one launch")
     rir = ap.add_mutually_exclusive_group()
     rir.add_argument("--rir-scp", default=None, metavar="FILE", help="reverberation: a 'key path' list of impulse-response wav files; one is drawn per "
                      "source and example and convolved inside the mixing launch (with --form whamr the *_reverb roles are then not needed)")
@@ -53,8 +55,6 @@ def main():
     reverb = args.rir_scp or args.synthetic_rirs or args.room_rirs
     if reverb and args.form == "direct":
         ap.error("--rir-scp / --synthetic-rirs / --room-rirs need dynamic mixing (--form wsj0, wham or whamr)")
-    if reverb and args.speeds:
-        ap.error("--speeds together with --rir-scp / --synthetic-rirs / --room-rirs is not built: pass one of them")
     if args.room_rirs:
         from sepreformer_amd.reverb import parse_rooms
         try:
@@ -96,7 +96,7 @@ def main():
             bank = RirBank.simulate(sampler.draw(room_spec[0], seed=(args.seed, 0)), args.fs, device=dev)      # the feed redraws it per epoch
         else:
             bank = RirBank.from_arrays(synthetic_rirs(synth[0], args.fs, rt60=synth[1:], seed=args.seed), args.fs, device=dev)
-        planner = functools.partial(planner, rirs=bank, target=args.reverb_target)
+        planner = functools.partial(planner, rirs=bank, target=args.reverb_target, speed_reverb=bool(args.speeds))
         print(f"RIR bank: {len(bank)} impulse responses, {int(bank.lengths.min())} .. {int(bank.lengths.max())} samples", flush=True)
     feed = df.DynamicMixFeed(corpus, planner, batch=args.batch, max_len=args.max_len, seed=args.seed, fixed_length=True, rirs=bank,
                               rooms=sampler, rooms_every=args.rooms_every)
