@@ -270,21 +270,6 @@ int sepr_downconv_fwd(const float* x, float* y, int n, int T, int F, int K, cons
 int sepr_spksplit_fwd(const float* x, float* y, int B, int S, int T, int F, float gn_eps,
                       const sepr_split_w* w, void* ws, size_t ws_bytes, sepr_stream_t stream);
 
-/* Statistics-threaded forms of the four residual blocks (ABI 4.10).  Every block of the residual stream starts with a LayerNorm over the F
- * channels of each frame (network.py:50,81,133,162) and ends by writing that stream; x_stats / y_stats [rows][2] = (mean, rstd) of the rows
- * of x / y in the library's LayerNorm arithmetic (eps 1e-5).  x_stats (or NULL): as returned through y_stats by the call that produced x -
- * the block's own statistics pass over x is skipped.  y_stats (or NULL): receives the statistics of y; they come out of the last
- * projection's tile tail where a workgroup tile holds whole rows (F = 256: the generic bf16x3 path of the Large variants), else from one
- * extra pass over y.  Results are identical to the plain entry points.  Everything else as in the function without the suffix. */
-int sepr_gcfn_fwd_st(const float* x, const float* x_stats, float* y, float* y_stats, int n, int T, int F, const sepr_gcfn_w* w, void* ws,
-                     size_t ws_bytes, sepr_stream_t stream);
-int sepr_cla_fwd_st(const float* x, const float* x_stats, float* y, float* y_stats, int n, int T, int F, int K, const sepr_cla_w* w,
-                    void* ws, size_t ws_bytes, sepr_stream_t stream);
-int sepr_ega_fwd_st(const float* x, const float* x_stats, float* y, float* y_stats, int n, int T, int Tp, int F, int H,
-                    const sepr_ega_w* w, void* ws, size_t ws_bytes, sepr_stream_t stream);
-int sepr_spkattn_fwd_st(const float* x, const float* x_stats, float* y, float* y_stats, int nS, int S, int T, int F, int H,
-                        const sepr_mha_w* w, void* ws, size_t ws_bytes, sepr_stream_t stream);
-
 /* Decoder-side fusion, modules/module.py:212-214: nearest x2 upsample of lo [n,T/2,F], concat with
  * skip [n,T,F] along channels, Conv1d(2F->F,k=1) -> y [n,T,F]. */
 int sepr_fuse_fwd(const float* lo, const float* skip, float* y, int n, int T, int F, const sepr_fuse_w* w,
@@ -794,13 +779,6 @@ int sepr_train_pack_gcfn_fused(const void* const* w1, const void* const* b1, con
  * is per host thread (thread-local state); without one the entry points behave exactly as before. */
 int sepr_train_defer_begin(void* arena, size_t arena_bytes);
 int sepr_train_defer_flush(int close, sepr_stream_t stream);
-/* Riding reductions (ABI 4.12).  Every weight-gradient contraction is followed by the fixed-order reduction of its row-slice partial tiles:
- * ~300 launches of 5-7 us per step, launch latency again.  With a double buffer registered on an open window (parts: 256-byte aligned device
- * scratch, 2 x 40 MB covers every contraction of the shipped configurations; NULL unregisters), a contraction whose outputs live in the
- * window's arena writes its partial tiles into one half of it and its reduction runs in blocks appended to the NEXT contraction's launch on
- * the same stream (or on its own at the flush) - same arithmetic, bit-identical gradients, ~290 launches fewer.  A contraction that does not
- * fit a half keeps the immediate form.  The registration ends with the window (flush(close = 1)) or the next sepr_train_defer_begin. */
-int sepr_train_defer_parts(void* parts, size_t parts_bytes);
 
 /* PIT_SISNR_time backward (criterions.py:191-217): d(sum_b loss[b] * gl[b]) / d est.  est, tgt, dest [S,B,T]; perm from the forward. */
 int sepr_pit_sisnr_bwd(const float* est, const float* tgt, const int* perm, const float* gl, int S, int B, int T, double eps,

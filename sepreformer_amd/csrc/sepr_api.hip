@@ -66,18 +66,6 @@ static int project(int pro, int epi, GemmArgs& a, const sepr_x3_w& x3, int site,
   return launch_gemm(pro, epi, a, site, st);
 }
 
-// the same, with the LayerNorm statistics of the output rows delivered to y_stats (optional): the bf16x3 core takes them from its tile tail
-// or launches rowstats itself (GemmArgs.stats_out); the exact-f32 core is followed by a rowstats launch here
-static int project_stats(int pro, int epi, GemmArgs& a, const sepr_x3_w& x3, int site, hipStream_t st, float* y_stats) {
-  if (y_stats && x3.wp) {
-    a.stats_out = y_stats;
-    a.stats_eps = LN_EPS;
-    return project(pro, epi, a, x3, site, st);
-  }
-  SEPR_TRY(project(pro, epi, a, x3, site, st));
-  return y_stats ? launch_rowstats(a.Y, y_stats, a.M, a.N, LN_EPS, st) : SEPR_OK;
-}
-
 // ---- workspace plans (floats unless noted) --------------------------------------------------------
 static size_t ws_gcfn(long long M, int F) {
   return align_up(2 * M * 4) + align_up(3LL * F * M * 4) + 1024;
@@ -187,12 +175,8 @@ extern "C" int sepr_projector_fwd(const float* enc, int B, int L, int Lp, int N,
   return launch_gemm(PRO_NORM, EPI_STORE, a, SEPR_SITE_PROJECTOR, static_cast<hipStream_t>(stream));
 }
 
-// The *_st entry points (ABI 4.10) thread the LayerNorm row statistics along the residual stream: x_stats (optional) = (mean, rstd) of x's rows
-// as the previous block's *_st call returned them - the block's own statistics pass is skipped; y_stats (optional) = where the statistics of
-// y's rows go (taken from the last projection's tile tail when that tile holds whole rows, else by one rowstats launch).  The values are
-// those of rowstats_kernel either way (sepr_common.h rowstats_one), so a chained walk and an unchained one give identical results.
-static int gcfn_fwd_impl(const float* x, const float* x_stats, float* y, float* y_stats, int n, int T, int F, const sepr_gcfn_w* w, void* ws,
-                         size_t ws_bytes, sepr_stream_t stream) {
+extern "C" int sepr_gcfn_fwd(const float* x, float* y, int n, int T, int F, const sepr_gcfn_w* w, void* ws, size_t ws_bytes,
+                             sepr_stream_t stream) {
   if (!x || !y || !w || n <= 0 || T <= 0 || F <= 0 || F % 32 != 0) return SEPR_EINVAL;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const long long M = (long long)n * T;
@@ -203,15 +187,13 @@ static int gcfn_fwd_impl(const float* x, const float* x_stats, float* y, float* 
     f.x = x; f.y = y; f.M = (int)M; f.T = T;
     f.w1p = w->fused_w1p; f.w2p = w->fused_w2p;
     f.b2 = w->b2; f.ls = w->ls; f.eps = LN_EPS; f.stagger = 0;
-    SEPR_TRY(launch_gcfn_fused(f, F, SEPR_SITE_GCFN_UP, st));
-    return y_stats ? launch_rowstats(y, y_stats, M, F, LN_EPS, st) : SEPR_OK;
+    return launch_gcfn_fused(f, F, SEPR_SITE_GCFN_UP, st);
   }
   Arena ar(ws, ws_bytes);
-  float* stats_ws = ar.f32(2 * M);
+  float* stats = ar.f32(2 * M);
   float* g = ar.f32(3LL * F * M);
   if (!ar.ok()) return SEPR_EWORKSPACE;
-  const float* stats = x_stats ? x_stats : stats_ws;
-  if (!x_stats) SEPR_TRY(launch_rowstats(x, stats_ws, M, F, LN_EPS, st));
+  SEPR_TRY(launch_rowstats(x, stats, M, F, LN_EPS, st));
   {  // net1: LayerNorm -> Linear F->6F, then depthwise k=3 + GLU on the tile while it is still in LDS:
      // the [rows, 6F] hidden tensor (3 KB per row) never goes to HBM      (network.py:61-65)
     GemmArgs a = gemm_args_zero();
@@ -226,48 +208,35 @@ static int gcfn_fwd_impl(const float* x, const float* x_stats, float* y, float* 
     a.M = (int)M; a.N = F; a.K = 3 * F;
     a.A = g; a.lda = 3 * F; a.W = w->w2; a.bias = w->b2;
     a.Y = y; a.ldc = F; a.R = x; a.ls = w->ls;
-    SEPR_TRY(project_stats(PRO_PLAIN, EPI_RES, a, w->x3_down, SEPR_SITE_GCFN_DOWN, st, y_stats));
+    SEPR_TRY(project(PRO_PLAIN, EPI_RES, a, w->x3_down, SEPR_SITE_GCFN_DOWN, st));
   }
   return SEPR_OK;
 }
-extern "C" int sepr_gcfn_fwd(const float* x, float* y, int n, int T, int F, const sepr_gcfn_w* w, void* ws, size_t ws_bytes,
-                             sepr_stream_t stream) {
-  return gcfn_fwd_impl(x, nullptr, y, nullptr, n, T, F, w, ws, ws_bytes, stream);
-}
-extern "C" int sepr_gcfn_fwd_st(const float* x, const float* x_stats, float* y, float* y_stats, int n, int T, int F, const sepr_gcfn_w* w,
-                                void* ws, size_t ws_bytes, sepr_stream_t stream) {
-  return gcfn_fwd_impl(x, x_stats, y, y_stats, n, T, F, w, ws, ws_bytes, stream);
-}
-
-static int cla_fwd_impl(const float* x, const float* x_stats, float* y, float* y_stats, int n, int T, int F, int K, const sepr_cla_w* w, void* ws,
-                        size_t ws_bytes, sepr_stream_t stream) {
+extern "C" int sepr_cla_fwd(const float* x, float* y, int n, int T, int F, int K, const sepr_cla_w* w, void* ws,
+                            size_t ws_bytes, sepr_stream_t stream) {
   if (!x || !y || !w || n <= 0 || T <= 0 || F <= 0 || F % 64 != 0) return SEPR_EINVAL;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const long long M = (long long)n * T;
   if (M > 0x7fffffffLL / 8) return SEPR_EINVAL;
   Arena ar(ws, ws_bytes);
-  float* stats_ws = ar.f32(2 * M);
+  float* stats = ar.f32(2 * M);
   float* u = ar.f32((long long)F * M);
   float* c = ar.f32((long long)F * M);
   float* d = ar.f32(2LL * F * M);
   if (!ar.ok()) return SEPR_EWORKSPACE;
   if (w->fused_w1p && w->fused_w2p && w->fused_w3p && (F == 128 || F == 256) && x != y) {
     // three launches: LayerNorm+linear1+GLU | depthwise conv | linear2+BN+GELU+linear3+LayerScale+residual
-    ClaFusedArgs h;
-    h.x = x; h.res = nullptr; h.y = u; h.M = (int)M;
-    h.w1p = w->fused_w1p; h.w2p = nullptr; h.b3 = nullptr; h.ls = nullptr; h.eps = LN_EPS;
-    h.att = nullptr; h.T = 0; h.Tp = 0; h.fac = 0; h.ldy = 0; h.pool = 0; h.o = nullptr; h.att_w = nullptr; h.wop = nullptr; h.bo = nullptr; h.lso = nullptr; h.Mp = 0;
+    ClaFusedArgs h = {};
+    h.x = x; h.y = u; h.M = (int)M;
+    h.w1p = w->fused_w1p; h.eps = LN_EPS;
     SEPR_TRY(launch_cla_head(h, F, SEPR_SITE_CLA, st));
     SEPR_TRY(launch_dwconv_same(u, c, n, T, F, K, w->dw_w, w->dw_b, st));
-    ClaFusedArgs t;
+    ClaFusedArgs t = {};
     t.x = c; t.res = x; t.y = y; t.M = (int)M;
-    t.w1p = w->fused_w2p; t.w2p = w->fused_w3p; t.b3 = w->b3; t.ls = w->ls; t.eps = 0.f;
-    t.att = nullptr; t.T = 0; t.Tp = 0; t.fac = 0; t.ldy = 0; t.pool = 0; t.o = nullptr; t.att_w = nullptr; t.wop = nullptr; t.bo = nullptr; t.lso = nullptr; t.Mp = 0;
-    SEPR_TRY(launch_cla_tail(t, F, SEPR_SITE_CLA, st));
-    return y_stats ? launch_rowstats(y, y_stats, M, F, LN_EPS, st) : SEPR_OK;
+    t.w1p = w->fused_w2p; t.w2p = w->fused_w3p; t.b3 = w->b3; t.ls = w->ls;
+    return launch_cla_tail(t, F, SEPR_SITE_CLA, st);
   }
-  const float* stats = x_stats ? x_stats : stats_ws;
-  if (!x_stats) SEPR_TRY(launch_rowstats(x, stats_ws, M, F, LN_EPS, st));
+  SEPR_TRY(launch_rowstats(x, stats, M, F, LN_EPS, st));
   {  // LayerNorm -> linear1 F->2F -> GLU                                  (network.py:175-177)
     GemmArgs a = gemm_args_zero();
     a.M = (int)M; a.N = 2 * F; a.K = F;
@@ -287,58 +256,46 @@ static int cla_fwd_impl(const float* x, const float* x_stats, float* y, float* y
     a.M = (int)M; a.N = F; a.K = 2 * F;
     a.A = d; a.lda = 2 * F; a.W = w->w3; a.bias = w->b3;
     a.Y = y; a.ldc = F; a.R = x; a.ls = w->ls;
-    SEPR_TRY(project_stats(PRO_PLAIN, EPI_RES, a, w->x3_3, SEPR_SITE_CLA, st, y_stats));
+    SEPR_TRY(project(PRO_PLAIN, EPI_RES, a, w->x3_3, SEPR_SITE_CLA, st));
   }
   return SEPR_OK;
 }
-extern "C" int sepr_cla_fwd(const float* x, float* y, int n, int T, int F, int K, const sepr_cla_w* w, void* ws,
-                            size_t ws_bytes, sepr_stream_t stream) {
-  return cla_fwd_impl(x, nullptr, y, nullptr, n, T, F, K, w, ws, ws_bytes, stream);
-}
-extern "C" int sepr_cla_fwd_st(const float* x, const float* x_stats, float* y, float* y_stats, int n, int T, int F, int K, const sepr_cla_w* w,
-                               void* ws, size_t ws_bytes, sepr_stream_t stream) {
-  return cla_fwd_impl(x, x_stats, y, y_stats, n, T, F, K, w, ws, ws_bytes, stream);
-}
-
 // the bf16x3 attention kernel serves the bf16x3 arithmetic mode (packed q/k/v present)
 static int relattn_x3(const sepr_ega_w* w) { return w->attn.x3_qkv.wp != nullptr ? 1 : 0; }
 
 // att_only (sepr_global_block_fwd, gate inside the GCFN kernel): everything up to the pooled attention rows att = ls_o * (Linear_out(o) + b_o),
 // whose workspace address is returned; no gate launch, y untouched.  The caller has checked that the folded output projection applies
 // (the rows then come from ega_outproj_kernel, bit-identical to what the gate launch computes for itself).
-static int ega_fwd_impl(const float* x, const float* x_stats, float* y, float* y_stats, int n, int T, int Tp, int F, int H, const sepr_ega_w* w,
-                        void* ws, size_t ws_bytes, sepr_stream_t stream, const float** att_only = nullptr) {
+static int ega_fwd_impl(const float* x, float* y, int n, int T, int Tp, int F, int H, const sepr_ega_w* w, void* ws, size_t ws_bytes,
+                        sepr_stream_t stream, const float** att_only = nullptr) {
   if (!x || !y || !w || x == y || n <= 0 || T <= 0 || Tp <= 0 || F <= 0 || F % 32 != 0 || T % Tp != 0) return SEPR_EINVAL;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int fac = T / Tp;
   const long long M = (long long)n * T, Mp = (long long)n * Tp;
   if (M > 0x7fffffffLL / 8) return SEPR_EINVAL;
   Arena ar(ws, ws_bytes);
-  float* stats_ws = ar.f32(2 * M);
-  float* stats_pws = ar.f32(2 * Mp);
+  float* stats = ar.f32(2 * M);
+  float* stats_p = ar.f32(2 * Mp);
   float* xd = ar.f32((long long)F * Mp);
   float* qkv = ar.f32(3LL * F * Mp);
   float* o = ar.f32((long long)F * Mp);
   float* att = ar.f32((long long)F * Mp);
   if (!ar.ok()) return SEPR_EWORKSPACE;
   const float* xpool = x;
-  const float* stats_p = stats_pws;
-  const bool qkv_fused = w->fused_qkv_p && F == 128 && !x_stats;
+  const bool qkv_fused = w->fused_qkv_p && F == 128;
   if (qkv_fused) {
     // ONE launch: adaptive_avg_pool1d, LayerNorm, q / k / v (network.py:146, :99-102) - no pooled copy of x, no statistics pass
-    ClaFusedArgs q;
-    q.x = x; q.res = nullptr; q.y = qkv; q.M = (int)Mp;
-    q.w1p = w->fused_qkv_p; q.w2p = nullptr; q.b3 = nullptr; q.ls = nullptr; q.eps = LN_EPS;
-    q.att = nullptr; q.T = 0; q.Tp = 0; q.fac = 0; q.ldy = 3 * F; q.pool = fac; q.o = nullptr; q.att_w = nullptr; q.wop = nullptr; q.bo = nullptr; q.lso = nullptr; q.Mp = 0;
+    ClaFusedArgs q = {};
+    q.x = x; q.y = qkv; q.M = (int)Mp;
+    q.w1p = w->fused_qkv_p; q.eps = LN_EPS;
+    q.ldy = 3 * F; q.pool = fac;
     SEPR_TRY(launch_ega_qkv(q, F, SEPR_SITE_ATTN_PROJ, st));
   } else
   if (fac > 1) {  // adaptive_avg_pool1d + the LayerNorm statistics of the pooled rows  (network.py:146, :99)
-    SEPR_TRY(launch_pool_stats(x, xd, stats_pws, n, Tp, fac, F, LN_EPS, st));
+    SEPR_TRY(launch_pool_stats(x, xd, stats_p, n, Tp, fac, F, LN_EPS, st));
     xpool = xd;
-  } else if (x_stats) {
-    stats_p = x_stats;          // no pooling: the attention's LayerNorm sees x's own rows
   } else {
-    SEPR_TRY(launch_rowstats(xpool, stats_pws, Mp, F, LN_EPS, st));
+    SEPR_TRY(launch_rowstats(xpool, stats_p, Mp, F, LN_EPS, st));
   }
   if (!qkv_fused) {  // MHA: LayerNorm -> q,k,v                              (network.py:99-102)
     GemmArgs a = gemm_args_zero();
@@ -365,32 +322,29 @@ static int ega_fwd_impl(const float* x, const float* x_stats, float* y, float* y
     SEPR_TRY(project(PRO_PLAIN, EPI_RES, a, w->attn.x3_out, SEPR_SITE_ATTN_PROJ, st));
   }
   if (w->fused_gate_p && (F == 128 || F == 256)) {
-    ClaFusedArgs g;
+    ClaFusedArgs g = {};
     g.x = x; g.res = x; g.y = y; g.M = (int)M;
-    g.w1p = w->fused_gate_p; g.w2p = nullptr; g.b3 = nullptr; g.ls = nullptr; g.eps = LN_EPS;
-    g.att = att; g.T = T; g.Tp = Tp; g.fac = fac; g.ldy = 0; g.pool = 0;
-    g.o = nullptr; g.att_w = nullptr; g.wop = nullptr; g.bo = nullptr; g.lso = nullptr; g.Mp = 0;
+    g.w1p = w->fused_gate_p; g.eps = LN_EPS;
+    g.att = att; g.T = T; g.Tp = Tp; g.fac = fac;
     if (out_fused) {   // linear_out + LayerScale of the attention inside the gate launch (the tile's own pooled rows)
       g.o = o; g.att_w = att; g.wop = w->fused_out_p; g.bo = w->attn.bo; g.lso = w->attn.ls; g.Mp = (int)Mp;
     }
-    SEPR_TRY(launch_ega_gate(g, F, SEPR_SITE_EGA_GATE, st));
-    return y_stats ? launch_rowstats(y, y_stats, M, F, LN_EPS, st) : SEPR_OK;
+    return launch_ega_gate(g, F, SEPR_SITE_EGA_GATE, st);
   }
-  const float* stats = x_stats ? x_stats : stats_ws;
-  if (!x_stats) SEPR_TRY(launch_rowstats(x, stats_ws, M, F, LN_EPS, st));
+  SEPR_TRY(launch_rowstats(x, stats, M, F, LN_EPS, st));
   {  // x + sigmoid(Linear(LayerNorm(x))) * upsample(att)                   (network.py:132-135,151-153)
     GemmArgs a = gemm_args_zero();
     a.M = (int)M; a.N = F; a.K = F;
     a.A = x; a.lda = F; a.stats = stats; a.gamma = w->gate_ln_g; a.beta = w->gate_ln_b;
     a.W = w->gate_w; a.bias = w->gate_b;
     a.Y = y; a.ldc = F; a.R = x; a.aux = att; a.T = T; a.Tp = Tp; a.fac = fac;
-    SEPR_TRY(project_stats(PRO_NORM, EPI_GATE, a, w->x3_gate, SEPR_SITE_EGA_GATE, st, y_stats));
+    SEPR_TRY(project(PRO_NORM, EPI_GATE, a, w->x3_gate, SEPR_SITE_EGA_GATE, st));
   }
   return SEPR_OK;
 }
 extern "C" int sepr_ega_fwd(const float* x, float* y, int n, int T, int Tp, int F, int H, const sepr_ega_w* w, void* ws,
                             size_t ws_bytes, sepr_stream_t stream) {
-  return ega_fwd_impl(x, nullptr, y, nullptr, n, T, Tp, F, H, w, ws, ws_bytes, stream);
+  return ega_fwd_impl(x, y, n, T, Tp, F, H, w, ws, ws_bytes, stream);
 }
 // EGA + GCFN of one global block.  With the gate inside the GCFN kernel (large F = 128 launches, SEPR_GB_FUSE != 0) the stand-alone gate pass
 // over the residual stream is gone; every other shape is the two calls.  Either way y_mid / y hold what sepr_ega_fwd / sepr_gcfn_fwd write.
@@ -402,11 +356,11 @@ extern "C" int sepr_global_block_fwd(const float* x, float* y_mid, float* y, int
   const bool fused = gate_perm_p && knob(SEPR_KNOB_GB_FUSE) != 0 && F == 128 && M <= 0x7fffffffLL / 8 && fac > 1 && 64 % fac == 0 &&
                      ega->fused_gate_p && ega->fused_out_p && gcfn->fused_w1p && gcfn->fused_w2p && gcfn_fused_takes_gate((int)M, F);
   if (!fused) {
-    SEPR_TRY(ega_fwd_impl(x, nullptr, y_mid, nullptr, n, T, Tp, F, H, ega, ws, ws_bytes, stream));
-    return gcfn_fwd_impl(y_mid, nullptr, y, nullptr, n, T, F, gcfn, ws, ws_bytes, stream);
+    SEPR_TRY(ega_fwd_impl(x, y_mid, n, T, Tp, F, H, ega, ws, ws_bytes, stream));
+    return sepr_gcfn_fwd(y_mid, y, n, T, F, gcfn, ws, ws_bytes, stream);
   }
   const float* att = nullptr;
-  SEPR_TRY(ega_fwd_impl(x, nullptr, y_mid, nullptr, n, T, Tp, F, H, ega, ws, ws_bytes, stream, &att));
+  SEPR_TRY(ega_fwd_impl(x, y_mid, n, T, Tp, F, H, ega, ws, ws_bytes, stream, &att));
   GcfnFusedArgs f = {};
   f.x = x; f.y = y; f.M = (int)M; f.T = T;
   f.w1p = gcfn->fused_w1p; f.w2p = gcfn->fused_w2p;
@@ -415,13 +369,8 @@ extern "C" int sepr_global_block_fwd(const float* x, float* y_mid, float* y, int
   return launch_gcfn_fused(f, F, SEPR_SITE_GCFN_UP, static_cast<hipStream_t>(stream));
 }
 
-extern "C" int sepr_ega_fwd_st(const float* x, const float* x_stats, float* y, float* y_stats, int n, int T, int Tp, int F, int H,
-                               const sepr_ega_w* w, void* ws, size_t ws_bytes, sepr_stream_t stream) {
-  return ega_fwd_impl(x, x_stats, y, y_stats, n, T, Tp, F, H, w, ws, ws_bytes, stream);
-}
-
-static int spkattn_fwd_impl(const float* x, const float* x_stats, float* y, float* y_stats, int nS, int S, int T, int F, int H, const sepr_mha_w* w,
-                            void* ws, size_t ws_bytes, sepr_stream_t stream) {
+extern "C" int sepr_spkattn_fwd(const float* x, float* y, int nS, int S, int T, int F, int H, const sepr_mha_w* w, void* ws,
+                                size_t ws_bytes, sepr_stream_t stream) {
   if (!x || !y || !w || nS <= 0 || S <= 0 || nS % S != 0 || T <= 0 || F <= 0 || F % 32 != 0) return SEPR_EINVAL;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const long long M = (long long)nS * T;
@@ -432,17 +381,14 @@ static int spkattn_fwd_impl(const float* x, const float* x_stats, float* y, floa
     f.x = x; f.y = y; f.NF = (int)(M / 2); f.T = T;
     f.w1p = w->fused_qkv_p; f.w2p = w->fused_out_p;
     f.bo = w->bo; f.ls = w->ls; f.eps = LN_EPS; f.inv_sqrt_dk = 1.0f / sqrtf((float)(F / H));
-    SEPR_TRY(launch_spk_fused(f, F, SEPR_SITE_ATTN_PROJ, st));
-    return y_stats ? launch_rowstats(y, y_stats, M, F, LN_EPS, st) : SEPR_OK;
+    return launch_spk_fused(f, F, SEPR_SITE_ATTN_PROJ, st);
   }
   Arena ar(ws, ws_bytes);
-  float* stats_ws = ar.f32(2 * M);
+  float* stats = ar.f32(2 * M);
   float* qkv = ar.f32(3LL * F * M);
   float* o = ar.f32((long long)F * M);
   if (!ar.ok()) return SEPR_EWORKSPACE;
-  if (x == y && x_stats && y_stats == x_stats) return SEPR_EINVAL;   // (in-place call: the input statistics are still read while the output's are written)
-  const float* stats = x_stats ? x_stats : stats_ws;
-  if (!x_stats) SEPR_TRY(launch_rowstats(x, stats_ws, M, F, LN_EPS, st));
+  SEPR_TRY(launch_rowstats(x, stats, M, F, LN_EPS, st));
   {
     GemmArgs a = gemm_args_zero();
     a.M = (int)M; a.N = 3 * F; a.K = F;
@@ -456,19 +402,10 @@ static int spkattn_fwd_impl(const float* x, const float* x_stats, float* y, floa
     a.M = (int)M; a.N = F; a.K = F;
     a.A = o; a.lda = F; a.W = w->wo; a.bias = w->bo;
     a.Y = y; a.ldc = F; a.R = x; a.ls = w->ls;
-    SEPR_TRY(project_stats(PRO_PLAIN, EPI_RES, a, w->x3_out, SEPR_SITE_ATTN_PROJ, st, y_stats));
+    SEPR_TRY(project(PRO_PLAIN, EPI_RES, a, w->x3_out, SEPR_SITE_ATTN_PROJ, st));
   }
   return SEPR_OK;
 }
-extern "C" int sepr_spkattn_fwd(const float* x, float* y, int nS, int S, int T, int F, int H, const sepr_mha_w* w, void* ws,
-                                size_t ws_bytes, sepr_stream_t stream) {
-  return spkattn_fwd_impl(x, nullptr, y, nullptr, nS, S, T, F, H, w, ws, ws_bytes, stream);
-}
-extern "C" int sepr_spkattn_fwd_st(const float* x, const float* x_stats, float* y, float* y_stats, int nS, int S, int T, int F, int H,
-                                   const sepr_mha_w* w, void* ws, size_t ws_bytes, sepr_stream_t stream) {
-  return spkattn_fwd_impl(x, x_stats, y, y_stats, nS, S, T, F, H, w, ws, ws_bytes, stream);
-}
-
 extern "C" int sepr_downconv_fwd(const float* x, float* y, int n, int T, int F, int K, const sepr_down_w* w,
                                  sepr_stream_t stream) {
   if (!x || !y || !w || n <= 0 || T <= 0) return SEPR_EINVAL;

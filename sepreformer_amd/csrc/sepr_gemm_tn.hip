@@ -57,9 +57,8 @@ inline TnPlan tn_plan(int M, int N, int K) {
   return p;
 }
 
-// The split-M reduction of ONE contraction, as a job: tn_reduce_kernel runs it on its own; a contraction kernel runs the job of the PREVIOUS
-// contraction in blocks appended to its grid (blockIdx.x >= ngrid; launch_gemm_tn "riding reduction").  Block = 64 output elements x 4 lanes
-// over the slices (fixed order inside a lane, lanes combined in a fixed order): the same arithmetic wherever it runs.
+// The split-M reduction of one contraction (tn_reduce_kernel, launched right behind it).  Block = 64 output elements x 4 lanes over the
+// slices: fixed order inside a lane, lanes combined in a fixed order.
 struct TnRed {
   const float* part;
   const float* cpart;
@@ -68,7 +67,7 @@ struct TnRed {
   int ldg, accumulate;
   float* colsum;
   int colsum_acc;
-  int nblocks;          // 0: no job
+  int nblocks;
 };
 __device__ __forceinline__ void tn_reduce_block(const TnRed& r, int blk, float* sh /* [4][64] */) {
   const long long total = (long long)r.N * r.K;
@@ -106,23 +105,13 @@ __device__ __forceinline__ void tn_reduce_block(const TnRed& r, int blk, float* 
 constexpr int TN_WPE = 2;   // waves per SIMD every instantiation is compiled for (plain bf16 at 3 - two LDS planes, 168 VGPRs - was not faster: profiles/r05_v4_wgrad_3waves.txt)
 template <int MD, bool GEN, bool STATS>
 __global__ __launch_bounds__(TN_THREADS, TN_WPE) void gemm_tn_kernel(const TnArgs a, const TnPlan p, float* __restrict__ part,
-                                                               float* __restrict__ cpart, const int ngrid, const TnRed red) {
+                                                               float* __restrict__ cpart, const int ngrid) {
   // x3: [A_hi, A_lo, B_hi, B_lo][128][72] bf16 = 73 728 B;  plain bf16: [A_hi, B_hi] = 36 864 B;  f32: [A, B][64][132] fp32 = 67 584 B
   // (the plain-bf16 form stays at two workgroups per CU all the same: 208 VGPRs - profiles/r05_v4_wgrad_3waves.txt)
   constexpr bool X3 = MD != 0, ONE = MD == 2;
   __shared__ __attribute__((aligned(16))) unsigned char smem[X3 ? (ONE ? 2 : 4) * TN_T * TN_LDM * 2 : 2 * TN_SLAB * TN_LDF * 4];   // ONE: hi planes only
   __shared__ float csum_s[4][TN_T];
-  // DBUF: TWO slabs of operand rows in flight in registers (the loads of slab s+2 issued before the MFMAs of slab s, consumed two
-  // barriers later).  Built in round 4 for the plain-bf16 instantiation and NOT enabled: next to the 64 accumulator and 32 fragment
-  // registers a second 64-register row set spills 67 dwords per lane into the slab loop (scratch traffic shares vmcnt with the
-  // operand stream), and the launch is HBM-stream-bound at two workgroups per CU anyway (64 KB per slab per workgroup against
-  // ~500 cycles of MFMAs).  The code path is kept behind the constant for the day the accumulator tile shrinks.
-  constexpr bool DBUF = false;
-  __shared__ float2 st_s[DBUF ? 2 : 1][TN_SLAB];          // (mean, rstd) of the slab's rows (!GEN && STATS)
-  if ((int)blockIdx.x >= ngrid) {          // riding reduction: the previous contraction's partial tiles (launch_gemm_tn)
-    tn_reduce_block(red, (int)blockIdx.x - ngrid, reinterpret_cast<float*>(smem));
-    return;
-  }
+  __shared__ float2 st_s[TN_SLAB];          // (mean, rstd) of the slab's rows (!GEN && STATS)
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid >> 1, wn = wid & 1;
   const int fi = lane & 15, fg = lane >> 4;
@@ -145,7 +134,7 @@ __global__ __launch_bounds__(TN_THREADS, TN_WPE) void gemm_tn_kernel(const TnArg
   const int cg = t7 & 31, mg = t7 >> 5;
   const int col = (roleA ? n0 : k0) + 4 * cg;
   const bool col_ok = col < (roleA ? a.N : a.K);
-  float4 rA[8 * TN_NB], rB[DBUF ? 8 * TN_NB : 1];
+  float4 rA[8 * TN_NB];
   float4 csum = zero4();
   float2 my_st = make_float2(0.f, 1.f);      // wave 2 only: statistics of row (slab base + lane) for the next slab
 
@@ -220,10 +209,10 @@ __global__ __launch_bounds__(TN_THREADS, TN_WPE) void gemm_tn_kernel(const TnArg
   };
   // the statistics a slab's B rows are normalised with travel wave 2 -> LDS -> every staging thread of B (published by the
   // barrier at the top of the loop; the previous slab's readers are past the barrier in the middle of the loop)
-  auto publish_stats = [&](int buf) {
-    if (!GEN && STATS && wid == 2) st_s[buf][lane] = my_st;
+  auto publish_stats = [&]() {
+    if (!GEN && STATS && wid == 2) st_s[lane] = my_st;
   };
-  auto store_slab = [&](float4 (&r)[8 * TN_NB], int sbuf, int mb) {
+  auto store_slab = [&](float4 (&r)[8 * TN_NB], int mb) {
 #pragma clang fp contract(off)
     if constexpr (!GEN) {
 #pragma unroll
@@ -239,7 +228,7 @@ __global__ __launch_bounds__(TN_THREADS, TN_WPE) void gemm_tn_kernel(const TnArg
 #pragma unroll
       for (int e = 0; e < 8 * TN_NB; ++e) {
         // (columns past K hold (0 - mean) * rstd garbage: they only ever reach accumulator columns that are never stored)
-        const float2 st = st_s[sbuf][32 * (e >> 3) + 8 * mg + (e & 7)];
+        const float2 st = st_s[32 * (e >> 3) + 8 * mg + (e & 7)];
         // pinned like the general loader (round 6): the natural source - st an 8-byte pair, rstd its high dword - is what hipcc's SLP
         // vectoriser turns into v_pk_mul_f32 op_sel:[0,1], the gfx950-faulty form (sepr_common.h norm4_pinned; tools/isa_lint.py)
         r[e] = norm4_pinned(r[e], st.x, st.y);
@@ -329,38 +318,15 @@ __global__ __launch_bounds__(TN_THREADS, TN_WPE) void gemm_tn_kernel(const TnArg
     }
   };
 
-  if constexpr (DBUF) {
-    // slab s lives in rA for even s, rB for odd s; its statistics in st_s[s & 1]
-    if (m_beg < m_end) load_slab(m_beg, rA);
-    publish_stats(0);
-    if (m_beg + TN_SLAB < m_end) load_slab(m_beg + TN_SLAB, rB);
-    publish_stats(1);
-    for (int mb = m_beg; mb < m_end; mb += 2 * TN_SLAB) {
-      __syncthreads();            // every wave is done reading the previous slab
-      store_slab(rA, 0, mb);
-      __syncthreads();
-      if (mb + 2 * TN_SLAB < m_end) load_slab(mb + 2 * TN_SLAB, rA);
-      mma_slab();
-      publish_stats(0);           // statistics of slab mb + 2 slabs (readers of st_s[0] are past the barrier above)
-      if (mb + TN_SLAB >= m_end) break;
-      __syncthreads();
-      store_slab(rB, 1, mb + TN_SLAB);
-      __syncthreads();
-      if (mb + 3 * TN_SLAB < m_end) load_slab(mb + 3 * TN_SLAB, rB);
-      mma_slab();
-      publish_stats(1);
-    }
-  } else {
-    if (m_beg < m_end) load_slab(m_beg, rA);
-    publish_stats(0);
-    for (int mb = m_beg; mb < m_end; mb += TN_SLAB) {
-      __syncthreads();            // every wave is done reading the previous slab
-      store_slab(rA, 0, mb);
-      __syncthreads();
-      if (mb + TN_SLAB < m_end) load_slab(mb + TN_SLAB, rA);
-      mma_slab();
-      publish_stats(0);           // statistics of the slab just requested (no reader of st_s between the two barriers above and the next)
-    }
+  if (m_beg < m_end) load_slab(m_beg, rA);
+  publish_stats();
+  for (int mb = m_beg; mb < m_end; mb += TN_SLAB) {
+    __syncthreads();            // every wave is done reading the previous slab
+    store_slab(rA, mb);
+    __syncthreads();
+    if (mb + TN_SLAB < m_end) load_slab(mb + TN_SLAB, rA);
+    mma_slab();
+    publish_stats();           // statistics of the slab just requested (no reader of st_s between the two barriers above and the next)
   }
 
   // ---- partial tile -> workspace: part[split][n][k] ----
@@ -391,26 +357,22 @@ __global__ __launch_bounds__(TN_THREADS, TN_WPE) void gemm_tn_kernel(const TnArg
 
 // ---------------------------------------------------------------------------------------------------------------------
 // gemm_tnd_kernel (round 6): the plain-bf16 contraction with its operands staged by LDS-DMA - for plain [M][ld] operands (no row map, no
-// normalisation prologue) with N and K multiples of 128: the largest contractions of a training step (the plain-bf16 precision stores dh1,
-// g, x^ and dropout(dy) of every GCFN block and the CLA intermediates as bf16: A16 / B16; every other projection hands over fp32 rows).
+// normalisation prologue) that are both bf16, with N and K multiples of 128: the largest contractions of a training step (the plain-bf16
+// precision stores dh1, g, x^ and dropout(dy) of every GCFN block and the CLA intermediates as bf16; every other projection hands over
+// fp32 rows and stays on gemm_tn_kernel - the fp32 form of this kernel was measured not faster, docs/HISTORY.md).
 // gemm_tn_kernel stages its slabs through registers (8-byte loads, widen, transpose on the VALU, 16-byte LDS stores) with ONE slab in
 // flight per workgroup, and its load phase and MFMA phase do not overlap (profiles/r03_v3_gemm_tn_ablation.txt): 3.0 TB/s on the
 // 256 000-row launches.  Here:
-//   * slabs of 32 rows x (128 + 128) columns go global -> LDS by LDS-DMA (16 B per lane; 128 B of a bf16 row / 256 B of an fp32 row per
-//     instruction: whole cache lines), into a ring of TND_NS stages - three slabs in flight per workgroup while one multiplies (two bf16
-//     operands: 16 KB stages, two workgroups per CU; fp32 operands: 24 / 32 KB stages, one workgroup per CU); the copies are inline asm with
-//     counted vmcnt waits and one raw barrier per slab (sepr_common.h glds16_asm);
-//   * the MFMA contraction index is the ROW index, so a lane needs 8 rows of one column.  bf16 image: ds_read_b64_tr_b16, gfx950's
-//     transposing LDS read, delivers 4 rows x 1 column per lane from a row-major image (two reads per fragment, no VALU at all); the slot
-//     of fragment element e of lane group fg is row 16 (e >> 2) + 4 fg + (e & 3).  fp32 image: ds_read2st64_b32 (two rows, 256 B apart,
-//     per instruction: four per fragment) and the same round-to-nearest conversion gemm_tn_kernel<2> applies while staging; element e
-//     of lane group fg is row 8 fg + e.  (Any bijection works as long as both operands of a launch use the same one - the contraction sums
-//     over it - so a mixed launch reads its bf16 image with the fp32 image's map, through plain 2-byte reads.)
-//   * LDS images, lane-linear per copy instruction (the copy's per-lane SOURCE address carries the permutation):
-//       bf16: [8 rows][64 columns] = 64 slots of 16 B; slot of (row r, chunk c) = 8 r + (c ^ (((r >> 1) & 3) << 1)): the 32 lanes the LDS
-//             serves together (rows 0-7 x 32 B of one 16-column tile) hit 16 distinct 16-byte bank windows;
-//       fp32: [4 rows][64 columns] = 64 slots; slot of (row r, chunk c) = 16 r + (c ^ 4 (row group bit 1)): lane groups fg = 0 / 1 (row
-//             groups 2 fg + h) read bank halves 16 floats apart;
+//   * slabs of 32 rows x (128 + 128) columns go global -> LDS by LDS-DMA (16 B per lane; 128 B of a bf16 row per instruction: whole cache
+//     lines), into a ring of TND_NS stages of 16 KB - three slabs in flight per workgroup while one multiplies, two workgroups per CU; the
+//     copies are inline asm with counted vmcnt waits and one raw barrier per slab (sepr_common.h glds16_asm);
+//   * the MFMA contraction index is the ROW index, so a lane needs 8 rows of one column: ds_read_b64_tr_b16, gfx950's transposing LDS
+//     read, delivers 4 rows x 1 column per lane from a row-major image (two reads per fragment, no VALU at all); the slot of fragment
+//     element e of lane group fg is row 16 (e >> 2) + 4 fg + (e & 3).  (Any bijection works as long as both operands use the same one -
+//     the contraction sums over it.)
+//   * LDS image, lane-linear per copy instruction (the copy's per-lane SOURCE address carries the permutation): [8 rows][64 columns] =
+//     64 slots of 16 B; slot of (row r, chunk c) = 8 r + (c ^ (((r >> 1) & 3) << 1)): the 32 lanes the LDS serves together (rows 0-7 x
+//     32 B of one 16-column tile) hit 16 distinct 16-byte bank windows;
 //   * column sums of A (bias gradients): 4 extra MFMAs per slab against an all-ones B fragment in the k0 == 0 tiles.
 // Partial tiles and their fixed-order reduction (tn_reduce_kernel) are those of gemm_tn_kernel: same plan, same workspace.
 // ---------------------------------------------------------------------------------------------------------------------
@@ -418,17 +380,11 @@ constexpr int TND_NS = 4;                  // ring stages (one multiplying, TND_
 constexpr int TND_ROWS = 32;               // rows per slab = one MFMA K step
 typedef short tn_s16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 tnd_bf16x8 __attribute__((ext_vector_type(8)));
-template <bool A32, bool B32>
-__global__ __launch_bounds__(TN_THREADS, (A32 || B32) ? 1 : 2) void gemm_tnd_kernel(const TnArgs a, const TnPlan p, float* __restrict__ part,
-                                                                                float* __restrict__ cpart, const int ngrid, const TnRed red) {
-  constexpr bool MIXED = A32 != B32;
-  constexpr int IMG_A = TND_ROWS * TN_T * (A32 ? 4 : 2), IMG_B = TND_ROWS * TN_T * (B32 ? 4 : 2), STAGE_B = IMG_A + IMG_B;
-  constexpr int NIA = A32 ? 4 : 2, NIB = B32 ? 4 : 2, NI = NIA + NIB;      // copies per wave and slab
+__global__ __launch_bounds__(TN_THREADS, 2) void gemm_tnd_kernel(const TnArgs a, const TnPlan p, float* __restrict__ part,
+                                                                 float* __restrict__ cpart, const int ngrid) {
+  constexpr int IMG = TND_ROWS * TN_T * 2, STAGE_B = 2 * IMG;      // one operand's slab image; a ring stage holds A's and B's
+  constexpr int NI = 4;                                             // copies per wave and slab
   __shared__ __attribute__((aligned(1024))) unsigned char ring[TND_NS * STAGE_B];
-  if ((int)blockIdx.x >= ngrid) {          // riding reduction: the previous contraction's partial tiles (launch_gemm_tn)
-    tn_reduce_block(red, (int)blockIdx.x - ngrid, reinterpret_cast<float*>(ring));
-    return;
-  }
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wid >> 1, wn = wid & 1;
   const int fi = lane & 15, fg = lane >> 4;
@@ -441,12 +397,11 @@ __global__ __launch_bounds__(TN_THREADS, (A32 || B32) ? 1 : 2) void gemm_tnd_ker
   const int nslab = m_end > m_beg ? (m_end - m_beg + TND_ROWS - 1) / TND_ROWS : 0;
   const bool csum_tile = cpart != nullptr && k0 == 0;
 
-  // ---- copy role: wave w copies column group w & 1 (64 columns) of both operands: bf16 - row groups (8 rows) 2 (w >> 1) + {0, 1};
-  //      fp32 - row groups (4 rows) 4 (w >> 1) + {0 .. 3}.  Lane l writes slot l of its copy's 1 KB block ----
+  // ---- copy role: wave w copies column group w & 1 (64 columns) of both operands, row groups (8 rows) 2 (w >> 1) + {0, 1}.
+  //      Lane l writes slot l of its copy's 1 KB block ----
   const int g64 = wid & 1, wq = wid >> 1;
-  const int r8 = lane >> 3, c8 = (lane & 7) ^ (((r8 >> 1) & 3) << 1);       // bf16 block: row, source chunk (8 columns)
-  const int r4 = lane >> 4, p4 = lane & 15;                                  // fp32 block: row, slot position (source chunk = p4 ^ 4 (rg bit 1))
-  const unsigned ldaB = (unsigned)a.lda * (A32 ? 4u : 2u), ldbB = (unsigned)a.ldb * (B32 ? 4u : 2u);
+  const int r8 = lane >> 3, c8 = (lane & 7) ^ (((r8 >> 1) & 3) << 1);       // row, source chunk (8 columns)
+  const unsigned ldaB = (unsigned)a.lda * 2u, ldbB = (unsigned)a.ldb * 2u;
   const unsigned ring_lds = lds_addr(ring);
   auto copy16 = [&](const float* src, unsigned ldB, int col0, unsigned img, int mb) {
 #pragma unroll
@@ -457,21 +412,11 @@ __global__ __launch_bounds__(TN_THREADS, (A32 || B32) ? 1 : 2) void gemm_tnd_ker
       glds16_asm(src, (unsigned)m * ldB + (unsigned)(col0 + 64 * g64 + 8 * c8) * 2u, __builtin_amdgcn_readfirstlane(img + (unsigned)((g64 * 4 + rg) * 1024)));
     }
   };
-  auto copy32 = [&](const float* src, unsigned ldB, int col0, unsigned img, int mb) {
-#pragma unroll
-    for (int h = 0; h < 4; ++h) {
-      const int rg = 4 * wq + h;
-      int m = mb + 4 * rg + r4;
-      m = m < a.M ? m : a.M - 1;
-      const int c4 = p4 ^ (((rg >> 1) & 1) << 2);
-      glds16_asm(src, (unsigned)m * ldB + (unsigned)(col0 + 64 * g64 + 4 * c4) * 4u, __builtin_amdgcn_readfirstlane(img + (unsigned)((g64 * 8 + rg) * 1024)));
-    }
-  };
   auto issue = [&](int s) {
     const int mb = m_beg + s * TND_ROWS;
     const unsigned stage = ring_lds + (unsigned)((s % TND_NS) * STAGE_B);
-    if constexpr (A32) copy32(a.A, ldaB, n0, stage, mb); else copy16(a.A, ldaB, n0, stage, mb);
-    if constexpr (B32) copy32(a.B, ldbB, k0, stage + IMG_A, mb); else copy16(a.B, ldbB, k0, stage + IMG_A, mb);
+    copy16(a.A, ldaB, n0, stage, mb);
+    copy16(a.B, ldbB, k0, stage + IMG, mb);
   };
 
   f32x4 acc[4][4], accs[4];
@@ -482,7 +427,7 @@ __global__ __launch_bounds__(TN_THREADS, (A32 || B32) ? 1 : 2) void gemm_tnd_ker
     for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
   }
   // ---- fragment reads ----
-  // bf16 image, transposing read h of tile t: lane (fg, i = fi) supplies row 16 h + 4 fg + (i >> 2), columns 16 t + 4 (i & 3) .. + 3 of its
+  // transposing read h of tile t: lane (fg, i = fi) supplies row 16 h + 4 fg + (i >> 2), columns 16 t + 4 (i & 3) .. + 3 of its
   // wave's column group g: block (g, row group 2 h + (fg >> 1)), row 4 (fg & 1) + (i >> 2) of the block, chunk 2 t + ((i & 3) >> 1)
   const int rr = 4 * (fg & 1) + (fi >> 2), sw = ((rr >> 1) & 3) << 1;
   auto frag16 = [&](const unsigned char* img, int g, int t) -> tnd_bf16x8 {
@@ -491,25 +436,6 @@ __global__ __launch_bounds__(TN_THREADS, (A32 || B32) ? 1 : 2) void gemm_tnd_ker
     const tn_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) tn_s16x4*)(q));
     const tn_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) tn_s16x4*)(q + 2048));
     return __builtin_bit_cast(tnd_bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-  };
-  // fp32 image: element e = row 8 fg + e, column 16 t + fi of column group g: block (g, row group 2 fg + (e >> 2)), row e & 3, chunk 4 t + (fi >> 2)
-  auto frag32 = [&](const unsigned char* img, int g, int t) -> tnd_bf16x8 {
-    const float* q = reinterpret_cast<const float*>(img + (unsigned)(g * 8 + 2 * fg) * 1024u + (unsigned)(((4 * t + (fi >> 2)) ^ ((fg & 1) << 2)) * 16 + (fi & 3) * 4));
-    tnd_bf16x8 v;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = (__bf16)q[(e >> 2) * 256 + (e & 3) * 64];      // (row stride 256 B, row-group stride 1 KB)
-    return v;
-  };
-  // bf16 image through the fp32 image's row map (mixed launches): 2-byte reads, rows 8 fg + e
-  auto frag16m = [&](const unsigned char* img, int g, int t) -> tnd_bf16x8 {
-    tnd_bf16x8 v;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const int r = 8 * fg + e, rb = r & 7;          // block (g, r >> 3), row rb, chunk c = 2 t + (fi >> 3), element fi & 7
-      const unsigned slot = (unsigned)(8 * rb + ((2 * t + (fi >> 3)) ^ (((rb >> 1) & 3) << 1)));
-      v[e] = *reinterpret_cast<const __bf16*>(img + (unsigned)(g * 4 + (r >> 3)) * 1024u + slot * 16u + (unsigned)(fi & 7) * 2u);
-    }
-    return v;
   };
   const tnd_bf16x8 ones = {(__bf16)1.f, (__bf16)1.f, (__bf16)1.f, (__bf16)1.f, (__bf16)1.f, (__bf16)1.f, (__bf16)1.f, (__bf16)1.f};
 
@@ -523,8 +449,8 @@ __global__ __launch_bounds__(TN_THREADS, (A32 || B32) ? 1 : 2) void gemm_tnd_ker
     issue(s + TND_NS - 1);                    // into the stage slab s - 1 occupied (always issued: the counted wait above stays a constant)
     unsigned char* const stg = ring + (s % TND_NS) * STAGE_B;
     if (m_beg + (s + 1) * TND_ROWS > a.M) {   // the tensor ends inside this slab (last slice only): rows of A past it multiply as zeros
-      for (int q = tid; q < IMG_A / 16; q += TN_THREADS) {
-        const int blk = q >> 6, r = A32 ? 4 * (blk & 7) + ((q & 63) >> 4) : 8 * (blk & 3) + ((q & 63) >> 3);
+      for (int q = tid; q < IMG / 16; q += TN_THREADS) {
+        const int blk = q >> 6, r = 8 * (blk & 3) + ((q & 63) >> 3);
         if (m_beg + s * TND_ROWS + r >= a.M) *reinterpret_cast<uint4*>(stg + q * 16) = make_uint4(0u, 0u, 0u, 0u);
       }
       __syncthreads();
@@ -532,12 +458,8 @@ __global__ __launch_bounds__(TN_THREADS, (A32 || B32) ? 1 : 2) void gemm_tnd_ker
     tnd_bf16x8 af[4], bf[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-      if constexpr (A32) af[t] = frag32(stg, wm, t);
-      else if constexpr (MIXED) af[t] = frag16m(stg, wm, t);
-      else af[t] = frag16(stg, wm, t);
-      if constexpr (B32) bf[t] = frag32(stg + IMG_A, wn, t);
-      else if constexpr (MIXED) bf[t] = frag16m(stg + IMG_A, wn, t);
-      else bf[t] = frag16(stg + IMG_A, wn, t);
+      af[t] = frag16(stg, wm, t);
+      bf[t] = frag16(stg + IMG, wn, t);
     }
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt)
@@ -641,46 +563,6 @@ size_t tn_workspace_bytes(int M, int N, int K) {
   return align_up((size_t)p.nsplit * ((size_t)N * K + N) * sizeof(float));
 }
 
-// ---- riding reduction (round 6) -------------------------------------------------------------------------------------------------------
-// A training step runs ~300 contractions, each followed by its split-M reduction: a 5-7 us launch of which ~5 us are launch latency and the
-// drain of the contraction's tail.  While a deferred-finisher window is open (sepr_train.h) nothing reads a contraction's G / colsum before
-// the window's flush when they live in the window's arena, so the reduction need not run right behind its contraction: its job is kept
-// PENDING and runs in blocks appended to the grid of the NEXT contraction on the same stream (stream order: the partial tiles are complete;
-// the extra blocks are over long before the contraction's own) - or on its own at the flush.  The partial tiles of such a job live in one half
-// of a caller-provided double buffer (sepr_train_defer_parts) instead of the block's workspace, which the next block call carves differently:
-// contraction i writes half i % 2 while the riding blocks read half (i - 1) % 2.  Same reduction arithmetic, same results.
-namespace {
-struct TnPending {
-  bool valid = false;
-  TnRed job;
-  hipStream_t stream = nullptr;
-};
-struct TnParts {
-  char* base = nullptr;
-  size_t half = 0;
-  int toggle = 0;
-  bool used = false;
-  hipStream_t stream = nullptr;     // the stream of the window's riding launches (another stream: that launch keeps the immediate form)
-};
-thread_local TnPending g_pend;
-thread_local TnParts g_parts;
-const TnRed kNoRed = {nullptr, nullptr, 0, 0, 0, nullptr, 0, 0, nullptr, 0, 0};
-}  // namespace
-int tn_flush_pending() {
-  if (!g_pend.valid) return SEPR_OK;
-  g_pend.valid = false;
-  hipLaunchKernelGGL(tn_reduce_kernel, dim3(g_pend.job.nblocks), dim3(256), 0, g_pend.stream, g_pend.job);
-  SEPR_CHECK_LAUNCH("tn_reduce_kernel");
-  return SEPR_OK;
-}
-void tn_parts_set(void* parts, size_t bytes) {
-  g_parts.base = static_cast<char*>(parts);
-  g_parts.half = parts ? (bytes / 2) / 256 * 256 : 0;
-  g_parts.toggle = 0;
-  g_parts.used = false;
-  g_parts.stream = nullptr;
-}
-
 int launch_gemm_tn(const TnArgs& a, int x3, void* ws, size_t ws_bytes, hipStream_t s) {
   if (a.M <= 0) return SEPR_OK;
   if (!a.A || !a.B || !a.G || a.N <= 0 || a.K <= 0 || (a.N % 4) || (a.K % 4) || (a.lda % 4) || (a.ldb % 4)) return SEPR_EINVAL;
@@ -688,18 +570,7 @@ int launch_gemm_tn(const TnArgs& a, int x3, void* ws, size_t ws_bytes, hipStream
   const TnPlan p = tn_plan(a.M, a.N, a.K);
   const size_t need = tn_workspace_bytes(a.M, a.N, a.K);
   if (!ws || ws_bytes < need) return SEPR_EWORKSPACE;
-  // this contraction's reduction can wait for the next contraction (see above): outputs in the window's arena, partial tiles in a buffer half
-  bool defer_red = g_parts.base != nullptr && need <= g_parts.half && fin_defers(a.G) && (!a.colsum || fin_defers(a.colsum)) &&
-                   (!g_parts.used || g_parts.stream == s);
-  // a pending job rides on this launch when it was issued on this stream; otherwise it runs on its own now
-  if (g_pend.valid && g_pend.stream != s) SEPR_TRY(tn_flush_pending());
   float* part = static_cast<float*>(ws);
-  if (defer_red) {
-    part = reinterpret_cast<float*>(g_parts.base + (size_t)g_parts.toggle * g_parts.half);
-    g_parts.toggle ^= 1;
-    g_parts.used = true;
-    g_parts.stream = s;
-  }
   float* cpart = part + (size_t)p.nsplit * a.N * a.K;
   const int grid = p.tn * p.tk * p.nsplit;
   // test switch (tests/tn_general_loader.py; read once, never set in the product): SEPR_TN_FORCE_GEN=1 routes every launch through the
@@ -710,10 +581,9 @@ int launch_gemm_tn(const TnArgs& a, int x3, void* ws, size_t ws_bytes, hipStream
   // the filter gradients of the waveform ends (K = 16 taps, exact arithmetic, windowed-frame row map): one pass over A on the VALU
   const bool smallk = x3 == 0 && a.K == 16 && a.N <= 256 && a.rows_out > 0 && !a.B2 && !a.idx && !a.stats && !a.mask_a && a.b_shift == 0 && !a.colsum &&
                       !a.a16 && !a.b16 && p.tn * p.tk <= 2;
-  if (smallk) SEPR_TRY(tn_flush_pending());             // (its kernel carries no riding blocks)
   long long slot = -1;
   const bool timed = prof_begin(SEPR_SITE_WGRAD, s, &slot);
-  TnRed mine;                                           // this contraction's reduction
+  TnRed mine;                                           // this contraction's reduction: launched right behind it, same stream
   mine.part = part; mine.cpart = cpart; mine.nsplit = p.nsplit; mine.N = a.N; mine.K = a.K;
   mine.G = a.G; mine.ldg = a.ldg; mine.accumulate = a.accumulate;
   mine.colsum = a.colsum; mine.colsum_acc = a.colsum_accumulate;
@@ -726,18 +596,11 @@ int launch_gemm_tn(const TnArgs& a, int x3, void* ws, size_t ws_bytes, hipStream
     }
     mine.colsum = nullptr;
     mine.nblocks = (int)(((long long)a.N * a.K + 63) / 64);
-    if (defer_red) {
-      g_pend.valid = true; g_pend.job = mine; g_pend.stream = s;
-    } else {
-      hipLaunchKernelGGL(tn_reduce_kernel, dim3(mine.nblocks), dim3(256), 0, s, mine);
-    }
+    hipLaunchKernelGGL(tn_reduce_kernel, dim3(mine.nblocks), dim3(256), 0, s, mine);
     SEPR_CHECK_LAUNCH("tn_smallk_kernel");
     return SEPR_OK;
   }
   float* cp = a.colsum ? cpart : nullptr;
-  const TnRed red = g_pend.valid ? g_pend.job : kNoRed;
-  const int gridr = grid + red.nblocks;                 // the pending job's blocks ride behind this contraction's
-  g_pend.valid = false;
   // (Rounds 3-4 ran the general loader at ONE workgroup per CU behind a 16 KB LDS pad: with two co-resident workgroups its bf16
   //  instantiations returned wrong, run-to-run different values in the even columns of the upper half of every B tile.  Round 5 found the
   //  cause - the packed-f32 op_sel fault described in sepr_common.h, triggered by the normalisation's v_pk_mul_f32 op_sel:[0,1] while the
@@ -745,25 +608,20 @@ int launch_gemm_tn(const TnArgs& a, int x3, void* ws, size_t ws_bytes, hipStream
   //  test_general_loader_two_workgroups_per_cu.)
 #define SEPR_TN_LAUNCH(MD)                                                                                                   \
   do {                                                                                                                       \
-    if (gen) hipLaunchKernelGGL((gemm_tn_kernel<MD, true, false>), dim3(gridr), dim3(TN_THREADS), 0, s, a, p, part, cp, grid, red);      \
-    else if (a.stats) hipLaunchKernelGGL((gemm_tn_kernel<MD, false, true>), dim3(gridr), dim3(TN_THREADS), 0, s, a, p, part, cp, grid, red); \
-    else hipLaunchKernelGGL((gemm_tn_kernel<MD, false, false>), dim3(gridr), dim3(TN_THREADS), 0, s, a, p, part, cp, grid, red);         \
+    if (gen) hipLaunchKernelGGL((gemm_tn_kernel<MD, true, false>), dim3(grid), dim3(TN_THREADS), 0, s, a, p, part, cp, grid);      \
+    else if (a.stats) hipLaunchKernelGGL((gemm_tn_kernel<MD, false, true>), dim3(grid), dim3(TN_THREADS), 0, s, a, p, part, cp, grid); \
+    else hipLaunchKernelGGL((gemm_tn_kernel<MD, false, false>), dim3(grid), dim3(TN_THREADS), 0, s, a, p, part, cp, grid);         \
   } while (0)
   // (A packed-row kernel for two bf16 operands - v_perm transpose, v_dot2 column sums, two slabs in flight, 5x fewer staging VALU
   //  instructions, bit-identical G - was built and measured in round 4: 182.55 vs 182.55 utt/s, no gain; git history 'gemm_tn16'.
   //  The contraction is not bound by its staging arithmetic.)
-  // plain operands, whole 128 x 128 tiles, plain-bf16 arithmetic: the LDS-DMA kernel (gemm_tnd_kernel; SEPR_TN16=0 keeps the register-staged form,
-  // SEPR_TN16=1 (default) takes launches with two bf16 operands only, 2 fp32 / mixed operands too - measured not faster, profiles/r06_wgrad_dma.txt)
+  // two plain bf16 operands, whole 128 x 128 tiles, plain-bf16 arithmetic: the LDS-DMA kernel (gemm_tnd_kernel; SEPR_TN16=0 keeps the
+  // register-staged form, SEPR_TN16=1 is the default)
   const int tnd_knob = knob(SEPR_KNOB_TN16);
-  const bool tnd = x3 == 2 && !gen && !a.stats && a.N % TN_T == 0 && a.K % TN_T == 0 && a.lda % (a.a16 ? 8 : 4) == 0 && a.ldb % (a.b16 ? 8 : 4) == 0 &&
-                   (long long)a.M * a.lda * (a.a16 ? 2 : 4) < (1LL << 32) && (long long)a.M * a.ldb * (a.b16 ? 2 : 4) < (1LL << 32) &&
-                   ((uintptr_t)a.A & 15) == 0 && ((uintptr_t)a.B & 15) == 0 && (tnd_knob >= 2 || (tnd_knob == 1 && a.a16 && a.b16));
-  if (tnd) {
-    if (a.a16 && a.b16) hipLaunchKernelGGL((gemm_tnd_kernel<false, false>), dim3(gridr), dim3(TN_THREADS), 0, s, a, p, part, cp, grid, red);
-    else if (a.a16) hipLaunchKernelGGL((gemm_tnd_kernel<false, true>), dim3(gridr), dim3(TN_THREADS), 0, s, a, p, part, cp, grid, red);
-    else if (a.b16) hipLaunchKernelGGL((gemm_tnd_kernel<true, false>), dim3(gridr), dim3(TN_THREADS), 0, s, a, p, part, cp, grid, red);
-    else hipLaunchKernelGGL((gemm_tnd_kernel<true, true>), dim3(gridr), dim3(TN_THREADS), 0, s, a, p, part, cp, grid, red);
-  }
+  const bool tnd = tnd_knob != 0 && a.a16 && a.b16 && x3 == 2 && !gen && !a.stats && a.N % TN_T == 0 && a.K % TN_T == 0 && a.lda % 8 == 0 &&
+                   a.ldb % 8 == 0 && (long long)a.M * a.lda * 2 < (1LL << 32) && (long long)a.M * a.ldb * 2 < (1LL << 32) &&
+                   ((uintptr_t)a.A & 15) == 0 && ((uintptr_t)a.B & 15) == 0;
+  if (tnd) hipLaunchKernelGGL(gemm_tnd_kernel, dim3(grid), dim3(TN_THREADS), 0, s, a, p, part, cp, grid);
   else if (x3 == 2) SEPR_TN_LAUNCH(2);
   else if (x3) SEPR_TN_LAUNCH(1);
   else SEPR_TN_LAUNCH(0);
@@ -773,11 +631,7 @@ int launch_gemm_tn(const TnArgs& a, int x3, void* ws, size_t ws_bytes, hipStream
     // both operands once (bf16 sources: 2 bytes per element) + the statistics: what a contraction over M rows has to read
     prof_bytes((double)a.M * ((double)a.N * (a.a16 ? 2.0 : 4.0) + (double)a.K * (a.b16 ? 2.0 : 4.0) + (a.stats ? 8.0 : 0.0)));
   }
-  if (defer_red) {
-    g_pend.valid = true; g_pend.job = mine; g_pend.stream = s;
-  } else {
-    hipLaunchKernelGGL(tn_reduce_kernel, dim3(mine.nblocks), dim3(256), 0, s, mine);
-  }
+  hipLaunchKernelGGL(tn_reduce_kernel, dim3(mine.nblocks), dim3(256), 0, s, mine);
   SEPR_CHECK_LAUNCH("gemm_tn_kernel");
   return SEPR_OK;
 }

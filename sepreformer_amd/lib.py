@@ -135,10 +135,6 @@ SIGNATURES = {
     "sepr_ega_fwd": (_i, [_fp, _fp, _i, _i, _i, _i, _i, C.POINTER(EgaW), _fp, _sz, _fp]),
     "sepr_spkattn_fwd": (_i, [_fp, _fp, _i, _i, _i, _i, _i, C.POINTER(MhaW), _fp, _sz, _fp]),
     "sepr_global_block_fwd": (_i, [_fp, _fp, _fp, _i, _i, _i, _i, _i, C.POINTER(EgaW), C.POINTER(GcfnW), _fp, _fp, _sz, _fp]),
-    "sepr_gcfn_fwd_st": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, C.POINTER(GcfnW), _fp, _sz, _fp]),
-    "sepr_cla_fwd_st": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, C.POINTER(ClaW), _fp, _sz, _fp]),
-    "sepr_ega_fwd_st": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, C.POINTER(EgaW), _fp, _sz, _fp]),
-    "sepr_spkattn_fwd_st": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, C.POINTER(MhaW), _fp, _sz, _fp]),
     "sepr_downconv_fwd": (_i, [_fp, _fp, _i, _i, _i, _i, C.POINTER(DownW), _fp]),
     "sepr_spksplit_fwd": (_i, [_fp, _fp, _i, _i, _i, _i, _f, C.POINTER(SplitW), _fp, _sz, _fp]),
     "sepr_fuse_fwd": (_i, [_fp, _fp, _fp, _i, _i, _i, C.POINTER(FuseW), _fp]),
@@ -200,7 +196,6 @@ SIGNATURES = {
     "sepr_train_fold_bias": (_i, [_fp, _fp, _fp, _i, _i, _i, _i, _fp, _fp]),
     "sepr_train_defer_begin": (_i, [_fp, _sz]),
     "sepr_train_defer_flush": (_i, [_i, _fp]),
-    "sepr_train_defer_parts": (_i, [_fp, _sz]),
     "sepr_train_pack_gcfn_fused": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _fp, _fp, _fp]),
     "sepr_pit_sisnr_bwd": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _d, _d, _fp, _fp, _sz, _fp]),
     "sepr_pit_sisnr_mag_bwd_workspace": (_sz, [_i, _i, _i, _i, _i]),

@@ -643,7 +643,7 @@ def test_hot_kernels_are_spill_free():
 
     for sub in ("gcfn_bwd_mid_kernel<1, 2, true>", "gcfn_bwd_mid_kernel<3, 2, false>", "gcfn_fused3_kernel<128, 2, 4, 0, false, false, 0>",
                 "gcfn_fused3_kernel<128, 2, 4, 0, true, true, 0>", "gcfn_fused3_kernel<128, 2, 4, 0, true, false, 0>", "gcfn_fused3_kernel<256, 2, 4, 0, false, false, 0>",
-                "gemm_tnd_kernel<false, false>", "gemm_x3_kernel<0, 8, 48>", "cla_tail_kernel<128, 2>"):
+                "gemm_tnd_kernel(", "gemm_x3_kernel<0, 8, 48>", "cla_tail_kernel<128, 2>"):
         r = one(sub)
         assert int(r["spill"]) == 0 and int(r["scratch"]) == 0, (sub, r)
     assert int(one("gcfn_bwd_mid_kernel<1, 2, true>")["vgpr"]) <= 168      # three workgroups per CU

@@ -291,25 +291,6 @@ def test_ega_base_width_crosses_maxlen(precision):
         agree(f"{tag}.ega.fac{fac}.Tp{Tp}.clamped", y, want)
 
 
-def test_large_statistics_chain_is_bit_identical():
-    """Round 6 (include/sepr.h ``*_st``): on the generic projection path (F = 256) every block hands the LayerNorm statistics of its output
-    rows - taken from the wide core's tile tail where a tile holds whole rows, else from a rowstats launch - to the next block.  The walk
-    with the chain must equal the walk with one statistics pass per block bit for bit, at a size whose top level runs the wide core
-    (>= 65 536 rows) and whose deeper levels run the narrow one."""
-    m, _ = gpu_model("SepReformer_Large_DM_WHAMR", "bf16x3")
-    eng = m.engine()
-    assert not eng.chain_stats                           # (off by default: measured not faster, profiles/r06_large_statschain_*.csv)
-    x = synth_mixture(9, 32000, seed=77).cuda()          # 9 x 8000 = 72 000 rows at the top level
-    try:
-        b = eng.forward(x)
-        eng.chain_stats = True
-        a = eng.forward(x)
-    finally:
-        eng.chain_stats = False
-    assert torch.isfinite(a[0]).all() and torch.equal(a[0], b[0])
-    assert all(torch.equal(p_, q_) for p_, q_ in zip(a[1], b[1]))
-
-
 def test_groupnorm_stats_entry():
     lib = L.load()
     x = rnd(5, 40000, seed=3) * 2 + 0.7
