@@ -66,26 +66,41 @@ static int project(int pro, int epi, GemmArgs& a, const sepr_x3_w& x3, int site,
   return launch_gemm(pro, epi, a, site, st);
 }
 
-// ---- workspace plans (floats unless noted) --------------------------------------------------------
-static size_t ws_gcfn(long long M, int F) {
-  return align_up(2 * M * 4) + align_up(3LL * F * M * 4) + 1024;
-}
-static size_t ws_cla(long long M, int F) {
-  return align_up(2 * M * 4) + 2 * align_up((long long)F * M * 4) + align_up(2LL * F * M * 4) + 1024;
-}
-static size_t ws_ega(long long M, long long Mp, int F) {
-  return align_up(2 * M * 4) + align_up(2 * Mp * 4) + 3 * align_up((long long)F * Mp * 4) + align_up(3LL * F * Mp * 4) + 2048;
-}
-static size_t ws_spk(long long M, int F) {
-  return align_up(2 * M * 4) + align_up(3LL * F * M * 4) + align_up((long long)F * M * 4) + 1024;
-}
-static size_t ws_split(long long M, int n_out, int T, int F, int S) {
-  return align_up(2LL * F * S * M * 4) + align_up((size_t)n_out * gn_chunks((long long)T * F) * 2 * 8) + align_up((size_t)n_out * 2 * 4) + 1024;
-}
-static size_t ws_out(long long M, int F, int N) {
-  return align_up(2LL * F * M * 4) + align_up((long long)N * M * 4) + 1024;
-}
-static size_t ws_enc(int B, int L) { return align_up((size_t)B * encoder_tiles(L) * 2 * 8) + 512; }
+// ---- workspace layouts: what each entry carves from its workspace, stated once.  The entry runs the layout on the caller's buffer,
+// sepr_workspace_bytes on a sizing Arena (no launch, no pointer read). ------------------------------------------------------------
+struct EncWs {      // sepr_encoder_fwd; L = encoder frames
+  double* part;
+  EncWs(Arena& a, int B, int L) { part = a.f64((size_t)B * encoder_tiles(L) * 2); }
+};
+struct GcfnWs {     // sepr_gcfn_fwd, two-projection form
+  float *stats, *g;
+  GcfnWs(Arena& a, long long M, int F) { stats = a.f32(2 * M); g = a.f32(3LL * F * M); }
+};
+struct ClaWs {      // sepr_cla_fwd (the fused form leaves stats and d unused)
+  float *stats, *u, *c, *d;
+  ClaWs(Arena& a, long long M, int F) { stats = a.f32(2 * M); u = a.f32((long long)F * M); c = a.f32((long long)F * M); d = a.f32(2LL * F * M); }
+};
+struct EgaWs {      // sepr_ega_fwd / sepr_global_block_fwd; Mp = pooled rows
+  float *stats, *stats_p, *xd, *qkv, *o, *att;
+  EgaWs(Arena& a, long long M, long long Mp, int F) {
+    stats = a.f32(2 * M); stats_p = a.f32(2 * Mp); xd = a.f32(F * Mp); qkv = a.f32(3 * F * Mp); o = a.f32(F * Mp); att = a.f32(F * Mp);
+  }
+};
+struct SpkWs {      // sepr_spkattn_fwd, unfused form
+  float *stats, *qkv, *o;
+  SpkWs(Arena& a, long long M, int F) { stats = a.f32(2 * M); qkv = a.f32(3LL * F * M); o = a.f32((long long)F * M); }
+};
+struct SplitWs {    // sepr_spksplit_fwd (the fused form leaves z unused)
+  float *z, *stats;
+  double* part;
+  SplitWs(Arena& a, int B, int S, int T, int F) {
+    z = a.f32(2LL * F * S * B * T); part = a.f64((size_t)(B * S) * gn_chunks((long long)T * F) * 2); stats = a.f32((size_t)(B * S) * 2);
+  }
+};
+struct OutWs {      // sepr_outlayer_decoder_fwd with a basis tensor; M = sequences x output frames L
+  float *o1, *o2;
+  OutWs(Arena& a, long long M, int F, int N) { o1 = a.f32(2LL * F * M); o2 = a.f32((long long)N * M); }
+};
 
 }  // namespace sepr
 
@@ -136,13 +151,13 @@ extern "C" size_t sepr_workspace_bytes(int op, int n, int T, int Tp, int F, int 
   if (n <= 0 || T <= 0 || F <= 0) return 0;
   const long long M = (long long)n * T;
   switch (op) {
-    case SEPR_OP_ENCODER: return ws_enc(n, T);  // T = encoder frames L
-    case SEPR_OP_GCFN: return ws_gcfn(M, F);
-    case SEPR_OP_CLA: return ws_cla(M, F);
-    case SEPR_OP_EGA: return Tp > 0 ? ws_ega(M, (long long)n * Tp, F) : 0;
-    case SEPR_OP_SPKATTN: return ws_spk(M, F);
-    case SEPR_OP_SPKSPLIT: return S > 0 ? ws_split(M, n * S, T, F, S) : 0;
-    case SEPR_OP_OUTLAYER: return N > 0 ? ws_out(M, F, N) : 0;  // T = output frames L
+    case SEPR_OP_ENCODER: return layout_bytes<EncWs>(n, T) + 512;  // T = encoder frames L
+    case SEPR_OP_GCFN: return layout_bytes<GcfnWs>(M, F) + 1024;
+    case SEPR_OP_CLA: return layout_bytes<ClaWs>(M, F) + 1024;
+    case SEPR_OP_EGA: return Tp > 0 ? layout_bytes<EgaWs>(M, (long long)n * Tp, F) + 2048 : 0;
+    case SEPR_OP_SPKATTN: return layout_bytes<SpkWs>(M, F) + 1024;
+    case SEPR_OP_SPKSPLIT: return S > 0 ? layout_bytes<SplitWs>(n, S, T, F) + 1024 : 0;
+    case SEPR_OP_OUTLAYER: return N > 0 ? layout_bytes<OutWs>(M, F, N) + 1024 : 0;  // T = output frames L
     default: return 0;
   }
 }
@@ -154,11 +169,10 @@ extern "C" int sepr_encoder_fwd(const float* wav, int B, int T, const float* w_e
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int L = (T - K) / stride + 1;
   Arena ar(ws, ws_bytes);
-  const int ntile = encoder_tiles(L);
-  double* part = ar.f64((size_t)B * ntile * 2);
-  if (!part) return SEPR_EWORKSPACE;
-  SEPR_TRY(launch_encoder(wav, B, T, L, w_enc, N, K, stride, enc, part, st));
-  SEPR_TRY(launch_gn_finalize(part, B, ntile, (long long)L * N, gn_eps, gn_stats, st));
+  const EncWs k(ar, B, L);
+  if (!ar.ok()) return SEPR_EWORKSPACE;
+  SEPR_TRY(launch_encoder(wav, B, T, L, w_enc, N, K, stride, enc, k.part, st));
+  SEPR_TRY(launch_gn_finalize(k.part, B, encoder_tiles(L), (long long)L * N, gn_eps, gn_stats, st));
   return SEPR_OK;
 }
 
@@ -190,23 +204,22 @@ extern "C" int sepr_gcfn_fwd(const float* x, float* y, int n, int T, int F, cons
     return launch_gcfn_fused(f, F, SEPR_SITE_GCFN_UP, st);
   }
   Arena ar(ws, ws_bytes);
-  float* stats = ar.f32(2 * M);
-  float* g = ar.f32(3LL * F * M);
+  const GcfnWs k(ar, M, F);
   if (!ar.ok()) return SEPR_EWORKSPACE;
-  SEPR_TRY(launch_rowstats(x, stats, M, F, LN_EPS, st));
+  SEPR_TRY(launch_rowstats(x, k.stats, M, F, LN_EPS, st));
   {  // net1: LayerNorm -> Linear F->6F, then depthwise k=3 + GLU on the tile while it is still in LDS:
      // the [rows, 6F] hidden tensor (3 KB per row) never goes to HBM      (network.py:61-65)
     GemmArgs a = gemm_args_zero();
     a.M = (int)M; a.N = 6 * F; a.K = F;
-    a.A = x; a.lda = F; a.stats = stats; a.gamma = w->ln_g; a.beta = w->ln_b;
-    a.W = w->w1; a.bias = w->b1; a.Y = g; a.ldc = 3 * F;
+    a.A = x; a.lda = F; a.stats = k.stats; a.gamma = w->ln_g; a.beta = w->ln_b;
+    a.W = w->w1; a.bias = w->b1; a.Y = k.g; a.ldc = 3 * F;
     a.dw_w = w->dw_w; a.dw_b = w->dw_b; a.T = T;
     SEPR_TRY(project(PRO_NORM, EPI_DWGLU, a, w->x3_up, SEPR_SITE_GCFN_UP, st));
   }
   {  // net2 Linear 3F->F, LayerScale, residual                            (network.py:65-66)
     GemmArgs a = gemm_args_zero();
     a.M = (int)M; a.N = F; a.K = 3 * F;
-    a.A = g; a.lda = 3 * F; a.W = w->w2; a.bias = w->b2;
+    a.A = k.g; a.lda = 3 * F; a.W = w->w2; a.bias = w->b2;
     a.Y = y; a.ldc = F; a.R = x; a.ls = w->ls;
     SEPR_TRY(project(PRO_PLAIN, EPI_RES, a, w->x3_down, SEPR_SITE_GCFN_DOWN, st));
   }
@@ -219,42 +232,39 @@ extern "C" int sepr_cla_fwd(const float* x, float* y, int n, int T, int F, int K
   const long long M = (long long)n * T;
   if (M > 0x7fffffffLL / 8) return SEPR_EINVAL;
   Arena ar(ws, ws_bytes);
-  float* stats = ar.f32(2 * M);
-  float* u = ar.f32((long long)F * M);
-  float* c = ar.f32((long long)F * M);
-  float* d = ar.f32(2LL * F * M);
+  const ClaWs k(ar, M, F);
   if (!ar.ok()) return SEPR_EWORKSPACE;
   if (w->fused_w1p && w->fused_w2p && w->fused_w3p && (F == 128 || F == 256) && x != y) {
     // three launches: LayerNorm+linear1+GLU | depthwise conv | linear2+BN+GELU+linear3+LayerScale+residual
     ClaFusedArgs h = {};
-    h.x = x; h.y = u; h.M = (int)M;
+    h.x = x; h.y = k.u; h.M = (int)M;
     h.w1p = w->fused_w1p; h.eps = LN_EPS;
     SEPR_TRY(launch_cla_head(h, F, SEPR_SITE_CLA, st));
-    SEPR_TRY(launch_dwconv_same(u, c, n, T, F, K, w->dw_w, w->dw_b, st));
+    SEPR_TRY(launch_dwconv_same(k.u, k.c, n, T, F, K, w->dw_w, w->dw_b, st));
     ClaFusedArgs t = {};
-    t.x = c; t.res = x; t.y = y; t.M = (int)M;
+    t.x = k.c; t.res = x; t.y = y; t.M = (int)M;
     t.w1p = w->fused_w2p; t.w2p = w->fused_w3p; t.b3 = w->b3; t.ls = w->ls;
     return launch_cla_tail(t, F, SEPR_SITE_CLA, st);
   }
-  SEPR_TRY(launch_rowstats(x, stats, M, F, LN_EPS, st));
+  SEPR_TRY(launch_rowstats(x, k.stats, M, F, LN_EPS, st));
   {  // LayerNorm -> linear1 F->2F -> GLU                                  (network.py:175-177)
     GemmArgs a = gemm_args_zero();
     a.M = (int)M; a.N = 2 * F; a.K = F;
-    a.A = x; a.lda = F; a.stats = stats; a.gamma = w->ln_g; a.beta = w->ln_b;
-    a.W = w->w1; a.bias = w->b1; a.Y = u; a.ldc = F;
+    a.A = x; a.lda = F; a.stats = k.stats; a.gamma = w->ln_g; a.beta = w->ln_b;
+    a.W = w->w1; a.bias = w->b1; a.Y = k.u; a.ldc = F;
     SEPR_TRY(project(PRO_NORM, EPI_GLU, a, w->x3_1, SEPR_SITE_CLA, st));
   }
-  SEPR_TRY(launch_dwconv_same(u, c, n, T, F, K, w->dw_w, w->dw_b, st));   // (network.py:178-180)
+  SEPR_TRY(launch_dwconv_same(k.u, k.c, n, T, F, K, w->dw_w, w->dw_b, st));   // (network.py:178-180)
   {  // linear2 F->2F, eval BatchNorm (folded), GELU                       (network.py:181-185)
     GemmArgs a = gemm_args_zero();
     a.M = (int)M; a.N = 2 * F; a.K = F;
-    a.A = c; a.lda = F; a.W = w->w2; a.bias = w->b2; a.Y = d; a.ldc = 2 * F;
+    a.A = k.c; a.lda = F; a.W = w->w2; a.bias = w->b2; a.Y = k.d; a.ldc = 2 * F;
     SEPR_TRY(project(PRO_PLAIN, EPI_GELU, a, w->x3_2, SEPR_SITE_CLA, st));
   }
   {  // linear3 2F->F, LayerScale, residual                                (network.py:185-187)
     GemmArgs a = gemm_args_zero();
     a.M = (int)M; a.N = F; a.K = 2 * F;
-    a.A = d; a.lda = 2 * F; a.W = w->w3; a.bias = w->b3;
+    a.A = k.d; a.lda = 2 * F; a.W = w->w3; a.bias = w->b3;
     a.Y = y; a.ldc = F; a.R = x; a.ls = w->ls;
     SEPR_TRY(project(PRO_PLAIN, EPI_RES, a, w->x3_3, SEPR_SITE_CLA, st));
   }
@@ -274,70 +284,65 @@ static int ega_fwd_impl(const float* x, float* y, int n, int T, int Tp, int F, i
   const long long M = (long long)n * T, Mp = (long long)n * Tp;
   if (M > 0x7fffffffLL / 8) return SEPR_EINVAL;
   Arena ar(ws, ws_bytes);
-  float* stats = ar.f32(2 * M);
-  float* stats_p = ar.f32(2 * Mp);
-  float* xd = ar.f32((long long)F * Mp);
-  float* qkv = ar.f32(3LL * F * Mp);
-  float* o = ar.f32((long long)F * Mp);
-  float* att = ar.f32((long long)F * Mp);
+  const EgaWs k(ar, M, Mp, F);
   if (!ar.ok()) return SEPR_EWORKSPACE;
   const float* xpool = x;
   const bool qkv_fused = w->fused_qkv_p && F == 128;
   if (qkv_fused) {
     // ONE launch: adaptive_avg_pool1d, LayerNorm, q / k / v (network.py:146, :99-102) - no pooled copy of x, no statistics pass
     ClaFusedArgs q = {};
-    q.x = x; q.y = qkv; q.M = (int)Mp;
+    q.x = x; q.y = k.qkv; q.M = (int)Mp;
     q.w1p = w->fused_qkv_p; q.eps = LN_EPS;
     q.ldy = 3 * F; q.pool = fac;
     SEPR_TRY(launch_ega_qkv(q, F, SEPR_SITE_ATTN_PROJ, st));
   } else
   if (fac > 1) {  // adaptive_avg_pool1d + the LayerNorm statistics of the pooled rows  (network.py:146, :99)
-    SEPR_TRY(launch_pool_stats(x, xd, stats_p, n, Tp, fac, F, LN_EPS, st));
-    xpool = xd;
+    SEPR_TRY(launch_pool_stats(x, k.xd, k.stats_p, n, Tp, fac, F, LN_EPS, st));
+    xpool = k.xd;
   } else {
-    SEPR_TRY(launch_rowstats(xpool, stats_p, Mp, F, LN_EPS, st));
+    SEPR_TRY(launch_rowstats(xpool, k.stats_p, Mp, F, LN_EPS, st));
   }
   if (!qkv_fused) {  // MHA: LayerNorm -> q,k,v                              (network.py:99-102)
     GemmArgs a = gemm_args_zero();
     a.M = (int)Mp; a.N = 3 * F; a.K = F;
-    a.A = xpool; a.lda = F; a.stats = stats_p; a.gamma = w->attn.ln_g; a.beta = w->attn.ln_b;
-    a.W = w->attn.wqkv; a.bias = w->attn.bqkv; a.Y = qkv; a.ldc = 3 * F;
+    a.A = xpool; a.lda = F; a.stats = k.stats_p; a.gamma = w->attn.ln_g; a.beta = w->attn.ln_b;
+    a.W = w->attn.wqkv; a.bias = w->attn.bqkv; a.Y = k.qkv; a.ldc = 3 * F;
     SEPR_TRY(project(PRO_NORM, EPI_STORE, a, w->attn.x3_qkv, SEPR_SITE_ATTN_PROJ, st));
   }
-  SEPR_TRY(launch_relattn(qkv, o, n, Tp, F, H, w->pe_k, w->maxlen, relattn_x3(w), st, w->pe_k_planes));   // (network.py:106-122)
+  SEPR_TRY(launch_relattn(k.qkv, k.o, n, Tp, F, H, w->pe_k, w->maxlen, relattn_x3(w), st, w->pe_k_planes));   // (network.py:106-122)
   const bool out_fused = w->fused_gate_p && w->fused_out_p && F == 128 && 64 % fac == 0;
   if (att_only) {
     if (!out_fused) return SEPR_EINVAL;
     ClaFusedArgs g = {};
-    g.o = o; g.att_w = att; g.wop = w->fused_out_p; g.bo = w->attn.bo; g.lso = w->attn.ls; g.Mp = (int)Mp;
+    g.o = k.o; g.att_w = k.att; g.wop = w->fused_out_p; g.bo = w->attn.bo; g.lso = w->attn.ls; g.Mp = (int)Mp;
     SEPR_TRY(launch_ega_outproj(g, F, SEPR_SITE_ATTN_PROJ, st));
-    *att_only = att;
+    *att_only = k.att;
     return SEPR_OK;
   }
   if (!out_fused) {  // linear_out * LayerScale (no residual inside MHA)      (network.py:124)
     GemmArgs a = gemm_args_zero();
     a.M = (int)Mp; a.N = F; a.K = F;
-    a.A = o; a.lda = F; a.W = w->attn.wo; a.bias = w->attn.bo;
-    a.Y = att; a.ldc = F; a.R = nullptr; a.ls = w->attn.ls;
+    a.A = k.o; a.lda = F; a.W = w->attn.wo; a.bias = w->attn.bo;
+    a.Y = k.att; a.ldc = F; a.R = nullptr; a.ls = w->attn.ls;
     SEPR_TRY(project(PRO_PLAIN, EPI_RES, a, w->attn.x3_out, SEPR_SITE_ATTN_PROJ, st));
   }
   if (w->fused_gate_p && (F == 128 || F == 256)) {
     ClaFusedArgs g = {};
     g.x = x; g.res = x; g.y = y; g.M = (int)M;
     g.w1p = w->fused_gate_p; g.eps = LN_EPS;
-    g.att = att; g.T = T; g.Tp = Tp; g.fac = fac;
+    g.att = k.att; g.T = T; g.Tp = Tp; g.fac = fac;
     if (out_fused) {   // linear_out + LayerScale of the attention inside the gate launch (the tile's own pooled rows)
-      g.o = o; g.att_w = att; g.wop = w->fused_out_p; g.bo = w->attn.bo; g.lso = w->attn.ls; g.Mp = (int)Mp;
+      g.o = k.o; g.att_w = k.att; g.wop = w->fused_out_p; g.bo = w->attn.bo; g.lso = w->attn.ls; g.Mp = (int)Mp;
     }
     return launch_ega_gate(g, F, SEPR_SITE_EGA_GATE, st);
   }
-  SEPR_TRY(launch_rowstats(x, stats, M, F, LN_EPS, st));
+  SEPR_TRY(launch_rowstats(x, k.stats, M, F, LN_EPS, st));
   {  // x + sigmoid(Linear(LayerNorm(x))) * upsample(att)                   (network.py:132-135,151-153)
     GemmArgs a = gemm_args_zero();
     a.M = (int)M; a.N = F; a.K = F;
-    a.A = x; a.lda = F; a.stats = stats; a.gamma = w->gate_ln_g; a.beta = w->gate_ln_b;
+    a.A = x; a.lda = F; a.stats = k.stats; a.gamma = w->gate_ln_g; a.beta = w->gate_ln_b;
     a.W = w->gate_w; a.bias = w->gate_b;
-    a.Y = y; a.ldc = F; a.R = x; a.aux = att; a.T = T; a.Tp = Tp; a.fac = fac;
+    a.Y = y; a.ldc = F; a.R = x; a.aux = k.att; a.T = T; a.Tp = Tp; a.fac = fac;
     SEPR_TRY(project(PRO_NORM, EPI_GATE, a, w->x3_gate, SEPR_SITE_EGA_GATE, st));
   }
   return SEPR_OK;
@@ -384,23 +389,21 @@ extern "C" int sepr_spkattn_fwd(const float* x, float* y, int nS, int S, int T, 
     return launch_spk_fused(f, F, SEPR_SITE_ATTN_PROJ, st);
   }
   Arena ar(ws, ws_bytes);
-  float* stats = ar.f32(2 * M);
-  float* qkv = ar.f32(3LL * F * M);
-  float* o = ar.f32((long long)F * M);
+  const SpkWs k(ar, M, F);
   if (!ar.ok()) return SEPR_EWORKSPACE;
-  SEPR_TRY(launch_rowstats(x, stats, M, F, LN_EPS, st));
+  SEPR_TRY(launch_rowstats(x, k.stats, M, F, LN_EPS, st));
   {
     GemmArgs a = gemm_args_zero();
     a.M = (int)M; a.N = 3 * F; a.K = F;
-    a.A = x; a.lda = F; a.stats = stats; a.gamma = w->ln_g; a.beta = w->ln_b;
-    a.W = w->wqkv; a.bias = w->bqkv; a.Y = qkv; a.ldc = 3 * F;
+    a.A = x; a.lda = F; a.stats = k.stats; a.gamma = w->ln_g; a.beta = w->ln_b;
+    a.W = w->wqkv; a.bias = w->bqkv; a.Y = k.qkv; a.ldc = 3 * F;
     SEPR_TRY(project(PRO_NORM, EPI_STORE, a, w->x3_qkv, SEPR_SITE_ATTN_PROJ, st));
   }
-  SEPR_TRY(launch_spkmix(qkv, o, nS / S, S, T, F, H, st));
+  SEPR_TRY(launch_spkmix(k.qkv, k.o, nS / S, S, T, F, H, st));
   {  // x + LayerScale(linear_out(.))                                       (network.py:124,244)
     GemmArgs a = gemm_args_zero();
     a.M = (int)M; a.N = F; a.K = F;
-    a.A = o; a.lda = F; a.W = w->wo; a.bias = w->bo;
+    a.A = k.o; a.lda = F; a.W = w->wo; a.bias = w->bo;
     a.Y = y; a.ldc = F; a.R = x; a.ls = w->ls;
     SEPR_TRY(project(PRO_PLAIN, EPI_RES, a, w->x3_out, SEPR_SITE_ATTN_PROJ, st));
   }
@@ -424,9 +427,7 @@ extern "C" int sepr_spksplit_fwd(const float* x, float* y, int B, int S, int T, 
   const long long count = (long long)T * F;
   const int nchunk = gn_chunks(count);
   Arena ar(ws, ws_bytes);
-  float* z = ar.f32(2LL * F * S * M);
-  double* part = ar.f64((size_t)n_out * nchunk * 2);
-  float* stats = ar.f32((size_t)n_out * 2);
+  const SplitWs k(ar, B, S, T, F);
   if (!ar.ok()) return SEPR_EWORKSPACE;
   if (w->fused_w1p && w->fused_w2p && (F == 128 || F == 256) && x != y) {
     // one kernel per speaker: Conv1d F->4FS + GLU + the speaker's F rows of Conv1d 2FS->FS, written straight to sequence
@@ -445,21 +446,21 @@ extern "C" int sepr_spksplit_fwd(const float* x, float* y, int B, int S, int T, 
   {  // Conv1d F->4FS (k=1) + GLU over the channel axis                     (module.py:114-115)
     GemmArgs a = gemm_args_zero();
     a.M = (int)M; a.N = 4 * F * S; a.K = F;
-    a.A = x; a.lda = F; a.W = w->w1; a.bias = w->b1; a.Y = z; a.ldc = 2 * F * S;
+    a.A = x; a.lda = F; a.W = w->w1; a.bias = w->b1; a.Y = k.z; a.ldc = 2 * F * S;
     SEPR_TRY(project(PRO_PLAIN, EPI_GLU, a, w->x3_1, SEPR_SITE_SPLIT, st));
   }
   {  // Conv1d 2FS->FS (k=1), then view(B*S, F, T): channel s*F+f -> sequence b*S+s  (module.py:116,123)
     GemmArgs a = gemm_args_zero();
     a.M = (int)M; a.N = F * S; a.K = 2 * F * S;
-    a.A = z; a.lda = 2 * F * S; a.W = w->w2; a.bias = w->b2; a.Y = y; a.ldc = F;
+    a.A = k.z; a.lda = 2 * F * S; a.W = w->w2; a.bias = w->b2; a.Y = y; a.ldc = F;
     a.T = T; a.S = S; a.Fs = F;
     SEPR_TRY(project(PRO_PLAIN, EPI_SPLIT, a, w->x3_2, SEPR_SITE_SPLIT, st));
   }
   }
   // GroupNorm(1, F) over (F, T) of every (b, s)                            (module.py:124)
-  SEPR_TRY(launch_gn_partial(y, part, n_out, count, nchunk, st));
-  SEPR_TRY(launch_gn_finalize(part, n_out, nchunk, count, gn_eps, stats, st));
-  SEPR_TRY(launch_gn_apply(y, stats, w->gn_g, w->gn_b, n_out, T, F, st));
+  SEPR_TRY(launch_gn_partial(y, k.part, n_out, count, nchunk, st));
+  SEPR_TRY(launch_gn_finalize(k.part, n_out, nchunk, count, gn_eps, k.stats, st));
+  SEPR_TRY(launch_gn_apply(y, k.stats, w->gn_g, w->gn_b, n_out, T, F, st));
   return SEPR_OK;
 }
 
@@ -533,14 +534,13 @@ extern "C" int sepr_outlayer_decoder_fwd(const float* x, int nS, int S, int Tsrc
     return launch_glumlp_fold(f, F, SEPR_SITE_OUT, st);
   }
   Arena ar(ws, ws_bytes);
-  float* o1 = ar.f32(2LL * F * M);
-  float* o2 = ar.f32((long long)N * M);
+  const OutWs k(ar, M, F, N);
   if (!ar.ok()) return SEPR_EWORKSPACE;
   const bool unique = idx != nullptr && Tsrc <= L;   // (a down-sampling map keeps the gather in the first projection)
-  SEPR_TRY(outlayer_basis(x, nS, Tsrc, L, idx, unique, F, N, w, o1, o2, st));
+  SEPR_TRY(outlayer_basis(x, nS, Tsrc, L, idx, unique, F, N, w, k.o1, k.o2, st));
   // ReLU(.) * encoder_output for the auxiliary heads (module.py:257-260, network.py:41) + ConvTranspose1d (:278-283)
   const int Tout = (L - 1) * stride + K;
-  SEPR_TRY(launch_decoder(o2, nS, S, L, N, K, stride, w->wdec, wav, Tout, unique ? idx : nullptr, Tsrc, enc, st));
+  SEPR_TRY(launch_decoder(k.o2, nS, S, L, N, K, stride, w->wdec, wav, Tout, unique ? idx : nullptr, Tsrc, enc, st));
   return SEPR_OK;
 }
 

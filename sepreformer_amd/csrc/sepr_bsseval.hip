@@ -314,13 +314,21 @@ __global__ __launch_bounds__(256) void bss_crit_kernel(const float* __restrict__
     if (sdr_mix) sdr_mix[b * S + k] = st ? nan : vsdr[S][k];     // identical rows: every SIR ties, popt = identity
   }
 }
+struct BssWs {   // two blocks, each split with no alignment inside: correlations [B][ncorr] | Gram systems [B][mats]; lengths [B] | a flag per (b, s)
+  double *corr, *mats;
+  int *lens, *flags;
+  BssWs(Arena& a, int S, int B) {
+    corr = a.f64((size_t)B * (size_t)(bss_ncorr(S) + bss_mats(S))); mats = corr + (long long)B * bss_ncorr(S);
+    lens = a.of<int>((size_t)B * (S + 1)); flags = lens + B;
+  }
+};
 }  // namespace
 }  // namespace sepr
 
 extern "C" size_t sepr_bss_eval_workspace(int S, int B, int T) {
   using namespace sepr;
   if (S < 2 || S > 3 || B <= 0 || T < S * BSS_F) return 0;
-  return align_up((size_t)B * (size_t)(bss_ncorr(S) + bss_mats(S)) * sizeof(double)) + align_up((size_t)B * (S + 1) * sizeof(int));
+  return layout_bytes<BssWs>(S, B);
 }
 
 extern "C" int sepr_bss_eval_fwd(const float* est, const float* ref, const float* mix, const int* lengths, int S, int B, int T,
@@ -332,15 +340,12 @@ extern "C" int sepr_bss_eval_fwd(const float* est, const float* ref, const float
   if (!mix && sdr_mix) return SEPR_EINVAL;
   for (int b = 0; b < B; ++b)
     if (lengths[b] < S * BSS_F || lengths[b] > T) return SEPR_EINVAL;
-  const size_t need = sepr_bss_eval_workspace(S, B, T);
-  if (!ws || ws_bytes < need) return SEPR_EWORKSPACE;
+  Arena ar(ws, ws_bytes);
+  const BssWs wk(ar, S, B);
+  if (!ar.ok_need()) return SEPR_EWORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  double* corr = static_cast<double*>(ws);
-  double* mats = corr + (long long)B * bss_ncorr(S);
-  int* lens = reinterpret_cast<int*>(static_cast<char*>(ws) + align_up((size_t)B * (size_t)(bss_ncorr(S) + bss_mats(S)) * sizeof(double)));
-  int* flags = lens + B;
-  hipError_t e = hipMemcpyAsync(lens, lengths, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemsetAsync(flags, 0, (size_t)B * S * sizeof(int), st);
+  hipError_t e = hipMemcpyAsync(wk.lens, lengths, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemsetAsync(wk.flags, 0, (size_t)B * S * sizeof(int), st);
   if (e != hipSuccess) {
     set_hip_error(e, "bss_eval setup");
     return SEPR_EHIP;
@@ -350,14 +355,14 @@ extern "C" int sepr_bss_eval_fwd(const float* est, const float* ref, const float
 #define SEPR_BSS_CASE(SS)                                                                                                      \
   case SS: {                                                                                                                   \
     const int nblk = bss_np(SS) * (2 * BSS_F / BSS_LAGS) + (SS + 1) * SS * (BSS_F / BSS_LAGS);                                 \
-    hipLaunchKernelGGL((bss_corr_kernel<SS>), dim3(nblk, B), dim3(BSS_LAGS), 0, st, est, ref, mix, lens, B, T, corr);         \
-    hipLaunchKernelGGL((bss_gram_kernel<SS>), dim3(256, B * SS), dim3(256), 0, st, corr, mats, have_mix);                     \
+    hipLaunchKernelGGL((bss_corr_kernel<SS>), dim3(nblk, B), dim3(BSS_LAGS), 0, st, est, ref, mix, wk.lens, B, T, wk.corr);         \
+    hipLaunchKernelGGL((bss_gram_kernel<SS>), dim3(256, B * SS), dim3(256), 0, st, wk.corr, wk.mats, have_mix);                     \
     for (int k = 0; k < nd; ++k) {                                                                                             \
-      hipLaunchKernelGGL((bss_panel_kernel<SS>), dim3(nd + 1 - k, B * SS), dim3(256), 0, st, mats, k, flags);                 \
+      hipLaunchKernelGGL((bss_panel_kernel<SS>), dim3(nd + 1 - k, B * SS), dim3(256), 0, st, wk.mats, k, wk.flags);                 \
       const int m = nd - k - 1;                                                                                                \
-      if (m > 0) hipLaunchKernelGGL((bss_update_kernel<SS>), dim3(m * (m + 1) / 2 + m, B * SS), dim3(256), 0, st, mats, k);    \
+      if (m > 0) hipLaunchKernelGGL((bss_update_kernel<SS>), dim3(m * (m + 1) / 2 + m, B * SS), dim3(256), 0, st, wk.mats, k);    \
     }                                                                                                                          \
-    hipLaunchKernelGGL((bss_crit_kernel<SS>), dim3(B), dim3(256), 0, st, est, mix, lens, B, T, corr, mats, flags, sdr, sir,   \
+    hipLaunchKernelGGL((bss_crit_kernel<SS>), dim3(B), dim3(256), 0, st, est, mix, wk.lens, B, T, wk.corr, wk.mats, wk.flags, sdr, sir,   \
                        sar, perm, sdr_mix, status);                                                                            \
   } break;
   switch (S) {

@@ -208,21 +208,34 @@ int knob(int id);
 
 inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 
-// sequential carve-out of the caller's workspace
+// Sequential carve-out of the caller's workspace, every take 256-byte aligned.  A workspace's layout - which buffers, in which order,
+// how large - is stated ONCE, by code that takes an Arena&: run on the caller's buffer and followed by ok() it hands out the pointers,
+// run on Arena::sizing() it only counts and need() is the size.
 struct Arena {
   char* base;
   size_t size, off;
-  Arena(void* p, size_t n) : base(static_cast<char*>(p)), size(n), off(0) {}
+  bool dry;
+  Arena(void* p, size_t n, bool d = false) : base(static_cast<char*>(p)), size(n), off(0), dry(d) {}
+  static Arena sizing() { return Arena(nullptr, 0, true); }
   float* f32(size_t count) { return static_cast<float*>(take(count * sizeof(float))); }
   double* f64(size_t count) { return static_cast<double*>(take(count * sizeof(double))); }
+  template <class T>
+  T* of(size_t count) { return static_cast<T*>(take(count * sizeof(T))); }
   void* take(size_t bytes) {
-    size_t o = align_up(off);
+    const size_t o = align_up(off);
     off = o + bytes;
+    if (dry) return reinterpret_cast<void*>(0x1000);   // never dereferenced
     if (base == nullptr || off > size) return nullptr;
     return base + o;
   }
-  bool ok() const { return base != nullptr && off <= size; }
+  bool ok() const { return dry || (base != nullptr && off <= size); }
+  size_t need() const { return align_up(off); }
+  // ok() with the last take rounded up as well: the whole of need(), which is what a size entry reports
+  bool ok_need() const { return dry || (base != nullptr && need() <= size); }
 };
+// bytes of the layout struct L(Arena&, shape...)
+template <class L, class... Shape>
+size_t layout_bytes(Shape... shape) { Arena a = Arena::sizing(); (void)L(a, shape...); return a.need(); }
 
 // One process-wide environment switch as an int: unset or empty -> dflt, anything else through atoi.  Call sites keep the value in a
 // `static const`, so a variable is read once per process (the latched, reloadable table is knob() in sepr_api.hip).

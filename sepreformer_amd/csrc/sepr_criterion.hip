@@ -145,10 +145,17 @@ __global__ __launch_bounds__(64) void pit_finalize_kernel(const double* __restri
 }
 }  // namespace
 
+struct PitWs {   // the chunks' fp64 partial moments; the backward adds four coefficients per (b, s)
+  double* part;
+  float* coef;
+  PitWs(Arena& a, int S, int B, int T, bool bwd) {
+    part = a.f64((size_t)B * ((T + PIT_CHUNK - 1) / PIT_CHUNK) * pit_nq(S));
+    coef = bwd ? a.f32((size_t)B * S * 4) : nullptr;
+  }
+};
 size_t pit_workspace_bytes(int S, int B, int T) {
   if (S < 1 || S > PIT_SMAX || B <= 0 || T <= 0) return 0;
-  const int nchunk = (T + PIT_CHUNK - 1) / PIT_CHUNK;
-  return align_up((size_t)B * nchunk * pit_nq(S) * sizeof(double));
+  return layout_bytes<PitWs>(S, B, T, false);
 }
 
 }  // namespace sepr
@@ -159,10 +166,10 @@ extern "C" int sepr_pit_sisnr_fwd(const float* est, const float* tgt, const floa
   using namespace sepr;
   if (!est || !tgt || !loss || S < 1 || S > PIT_SMAX || B <= 0 || T <= 0 || B > 65535) return SEPR_EINVAL;
   if ((sisnri || sisnri_perm) && !mix) return SEPR_EINVAL;
-  const size_t need = pit_workspace_bytes(S, B, T);
-  if (!ws || ws_bytes < need) return SEPR_EWORKSPACE;
+  Arena ar(ws, ws_bytes);
+  double* part = PitWs(ar, S, B, T, false).part;
+  if (!ar.ok_need()) return SEPR_EWORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  double* part = static_cast<double*>(ws);
   const int nchunk = (T + PIT_CHUNK - 1) / PIT_CHUNK;
   const dim3 grid(nchunk, B);
   const int have_mix = mix ? 1 : 0;
@@ -299,33 +306,35 @@ __global__ __launch_bounds__(64) void mag_finalize_kernel(const double* __restri
   }
 }
 
+// geometry and workspace of the magnitude loss, carved from `a` (sized by the same code on Arena::sizing())
 struct MagPlan {
   int nchunk, NF, Tpad, nfr, ldc;
-  size_t o_part, o_means, o_scales, o_xz, o_c, o_sums, total;
+  double* part;
+  float *means, *scales, *xz, *C;
+  double* sums;
 };
-MagPlan mag_plan(int S, int B, int T, int N, int hop) {
+MagPlan mag_plan(Arena& a, int S, int B, int T, int N, int hop) {
   MagPlan p;
   p.nchunk = (T + PIT_CHUNK - 1) / PIT_CHUNK;
   p.NF = (T + hop - 1) / hop;
   p.Tpad = p.NF * hop;
   p.nfr = p.Tpad >= N ? (p.Tpad - N) / hop + 1 : 0;
   p.ldc = ((N + 2) + 3) / 4 * 4;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes); return o; };
-  p.o_part = take((size_t)B * p.nchunk * pit_nq(S) * sizeof(double));
-  p.o_means = take((size_t)2 * S * B * sizeof(float));
-  p.o_scales = take((size_t)B * S * S * sizeof(float));
-  p.o_xz = take((size_t)2 * S * B * p.Tpad * sizeof(float));
-  p.o_c = take((size_t)2 * S * B * p.nfr * p.ldc * sizeof(float));
-  p.o_sums = take((size_t)B * S * S * 2 * sizeof(double));
-  p.total = off;
+  p.part = PitWs(a, S, B, T, false).part;
+  p.means = a.f32((size_t)2 * S * B);
+  p.scales = a.f32((size_t)B * S * S);
+  p.xz = a.f32((size_t)2 * S * B * p.Tpad);
+  p.C = a.f32((size_t)2 * S * B * p.nfr * p.ldc);
+  p.sums = a.f64((size_t)B * S * S * 2);
   return p;
 }
 }  // namespace
 
 size_t pit_mag_workspace_bytes(int S, int B, int T, int N, int hop) {
   if (S < 1 || S > PIT_SMAX || B <= 0 || T <= 0 || N <= 0 || hop <= 0 || N % 32 != 0 || hop % 4 != 0) return 0;
-  return mag_plan(S, B, T, N, hop).total;
+  Arena a = Arena::sizing();
+  mag_plan(a, S, B, T, N, hop);
+  return a.need();
 }
 }  // namespace sepr
 
@@ -339,18 +348,14 @@ extern "C" int sepr_pit_sisnr_mag_fwd(const float* est, const float* tgt, int S,
   using namespace sepr;
   if (!est || !tgt || !dft || !loss || S < 1 || S > PIT_SMAX || B <= 0 || T <= 0 || B > 65535) return SEPR_EINVAL;
   if (frame_len <= 0 || frame_len % 32 != 0 || frame_shift <= 0 || frame_shift % 4 != 0) return SEPR_EINVAL;
-  const MagPlan p = mag_plan(S, B, T, frame_len, frame_shift);
+  Arena ar(ws, ws_bytes);
+  const MagPlan p = mag_plan(ar, S, B, T, frame_len, frame_shift);
   if (p.nfr <= 0) return SEPR_EINVAL;                                 // shorter than one frame
-  if (!ws || ws_bytes < p.total) return SEPR_EWORKSPACE;
+  if (!ar.ok_need()) return SEPR_EWORKSPACE;
   if ((long long)2 * S * B * p.nfr > 0x7fffffffLL / 8 || (long long)2 * S * B * p.Tpad >= (1LL << 32)) return SEPR_EINVAL;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  char* base = static_cast<char*>(ws);
-  double* part = reinterpret_cast<double*>(base + p.o_part);
-  float* means = reinterpret_cast<float*>(base + p.o_means);
-  float* scales = reinterpret_cast<float*>(base + p.o_scales);
-  float* xz = reinterpret_cast<float*>(base + p.o_xz);
-  float* C = reinterpret_cast<float*>(base + p.o_c);
-  double* sums = reinterpret_cast<double*>(base + p.o_sums);
+  double *part = p.part, *sums = p.sums;
+  float *means = p.means, *scales = p.scales, *xz = p.xz, *C = p.C;
   const int nbin = frame_len / 2 + 1;
 #define SEPR_MAG_CASE(SS)                                                                                                    \
   case SS:                                                                                                                   \
@@ -463,12 +468,13 @@ extern "C" int sepr_pit_sisnr_bwd(const float* est, const float* tgt, const int*
                                   double clamp_min, float* dest, void* ws, size_t ws_bytes, sepr_stream_t stream) {
   using namespace sepr;
   if (!est || !tgt || !perm || !gl || !dest || S < 1 || S > PIT_SMAX || B <= 0 || T <= 0 || B > 65535) return SEPR_EINVAL;
-  const size_t need = pit_workspace_bytes(S, B, T) + align_up((size_t)B * S * 4 * sizeof(float));
-  if (!ws || ws_bytes < need) return SEPR_EWORKSPACE;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  double* part = static_cast<double*>(ws);
-  float* coef = reinterpret_cast<float*>(static_cast<char*>(ws) + pit_workspace_bytes(S, B, T));
   const int nchunk = (T + PIT_CHUNK - 1) / PIT_CHUNK;
+  Arena ar(ws, ws_bytes);
+  const PitWs k(ar, S, B, T, true);
+  if (!ar.ok_need()) return SEPR_EWORKSPACE;
+  double* part = k.part;
+  float* coef = k.coef;
+  hipStream_t st = static_cast<hipStream_t>(stream);
 #define SEPR_PITB(SS)                                                                                                             \
   case SS:                                                                                                                        \
     hipLaunchKernelGGL((pit_partial_kernel<SS>), dim3(nchunk, B), dim3(PIT_TPB), 0, st, est, tgt, (const float*)nullptr, B, T,   \
@@ -501,20 +507,19 @@ namespace {
 struct MagBwdPlan {
   MagPlan f;
   int ldd;      // leading dimension of dC: frame_len + 2 rounded up to a multiple of 32 (K of the adjoint projection)
-  size_t o_dc, o_pc, o_fr, o_da, o_coef, total;
+  float* dC;
+  double* dLdc;
+  float *fr, *da;
 };
-MagBwdPlan mag_bwd_plan(int S, int B, int T, int N, int hop) {
+MagBwdPlan mag_bwd_plan(Arena& a, int S, int B, int T, int N, int hop) {
   MagBwdPlan p;
-  p.f = mag_plan(S, B, T, N, hop);
+  p.f = mag_plan(a, S, B, T, N, hop);
   p.ldd = ((N + 2) + 31) / 32 * 32;
-  size_t off = p.f.total;
-  auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes); return o; };
-  p.o_dc = take((size_t)S * B * p.f.nfr * p.ldd * sizeof(float));      // d(re, im) of the estimates' STFT
-  p.o_pc = take((size_t)S * B * 2 * sizeof(double));                      // dL/dc partial (one per (s,b)), spare
-  p.o_fr = take((size_t)S * B * p.f.nfr * N * sizeof(float));             // adjoint frames before overlap-add
-  p.o_da = take((size_t)S * B * p.f.Tpad * sizeof(float));                // d a~ (padded length)
-  p.o_coef = take((size_t)S * B * 4 * sizeof(float));
-  p.total = off;
+  p.dC = a.f32((size_t)S * B * p.f.nfr * p.ldd);      // d(re, im) of the estimates' STFT
+  p.dLdc = a.f64((size_t)S * B * 2);                  // dL/dc partial (one per (s,b)), spare
+  p.fr = a.f32((size_t)S * B * p.f.nfr * N);          // adjoint frames before overlap-add
+  p.da = a.f32((size_t)S * B * p.f.Tpad);             // d a~ (padded length)
+  a.f32((size_t)S * B * 4);                           // (unused: kept so that the size does not move)
   return p;
 }
 
@@ -624,7 +629,9 @@ __global__ __launch_bounds__(256) void demean_kernel(const float* __restrict__ d
 extern "C" size_t sepr_pit_sisnr_mag_bwd_workspace(int S, int B, int T, int frame_len, int frame_shift) {
   using namespace sepr;
   if (S < 1 || S > PIT_SMAX || B <= 0 || T <= 0 || frame_len <= 0 || frame_shift <= 0 || frame_len % 32 || frame_shift % 4) return 0;
-  return mag_bwd_plan(S, B, T, frame_len, frame_shift).total;
+  Arena a = Arena::sizing();
+  mag_bwd_plan(a, S, B, T, frame_len, frame_shift);
+  return a.need();
 }
 
 extern "C" int sepr_pit_sisnr_mag_bwd(const float* est, const float* tgt, const int* perm, const float* gl, int S, int B, int T,
@@ -633,22 +640,14 @@ extern "C" int sepr_pit_sisnr_mag_bwd(const float* est, const float* tgt, const 
   using namespace sepr;
   if (!est || !tgt || !perm || !gl || !dft || !dft_t || !dest || S < 1 || S > PIT_SMAX || B <= 0 || T <= 0 || B > 65535) return SEPR_EINVAL;
   if (frame_len <= 0 || frame_len % 32 != 0 || frame_shift <= 0 || frame_shift % 4 != 0) return SEPR_EINVAL;
-  const MagBwdPlan bp = mag_bwd_plan(S, B, T, frame_len, frame_shift);
+  Arena ar(ws, ws_bytes);
+  const MagBwdPlan bp = mag_bwd_plan(ar, S, B, T, frame_len, frame_shift);
   const MagPlan& p = bp.f;
   if (p.nfr <= 0) return SEPR_EINVAL;
-  if (!ws || ws_bytes < bp.total) return SEPR_EWORKSPACE;
+  if (!ar.ok_need()) return SEPR_EWORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  char* base = static_cast<char*>(ws);
-  double* part = reinterpret_cast<double*>(base + p.o_part);
-  float* means = reinterpret_cast<float*>(base + p.o_means);
-  float* scales = reinterpret_cast<float*>(base + p.o_scales);
-  float* xz = reinterpret_cast<float*>(base + p.o_xz);
-  float* C = reinterpret_cast<float*>(base + p.o_c);
-  double* sums = reinterpret_cast<double*>(base + p.o_sums);
-  float* dC = reinterpret_cast<float*>(base + bp.o_dc);
-  double* dLdc = reinterpret_cast<double*>(base + bp.o_pc);
-  float* fr = reinterpret_cast<float*>(base + bp.o_fr);
-  float* da = reinterpret_cast<float*>(base + bp.o_da);
+  double *part = p.part, *sums = p.sums, *dLdc = bp.dLdc;
+  float *means = p.means, *scales = p.scales, *xz = p.xz, *C = p.C, *dC = bp.dC, *fr = bp.fr, *da = bp.da;
   const int nbin = frame_len / 2 + 1;
   // ---- recompute the forward quantities (moments, scales, zero-mean padded waveforms, STFT of all 2S waveforms, pair sums)
 #define SEPR_MAGB1(SS)                                                                                                              \

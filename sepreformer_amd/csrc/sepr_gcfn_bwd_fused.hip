@@ -623,10 +623,14 @@ __global__ __launch_bounds__(GB_THREADS, PL ? GB_PL_WGS : 2) void gcfn_bwd_mid_k
 }
 }  // namespace
 
-size_t gcfn_bwd_fused_ws(long long M, int F) {   // partials + the pre-reduction scratch of launch_gcfn_mid_reduce
-  const long long MB = (M + GB_OUT - 1) / GB_OUT;
-  return align_up((size_t)MB * 3 * F * 8 * sizeof(float)) + gcfn_mid_reduce_ws(3 * F);
-}
+struct GcfnBwdWs {   // the tiles' depthwise partials [MB][3F][8] + the pre-reduction scratch of launch_gcfn_mid_reduce
+  float *part, *scratch;
+  GcfnBwdWs(Arena& a, long long M, int F) {
+    part = a.f32((size_t)((M + GB_OUT - 1) / GB_OUT) * 3 * F * 8);
+    scratch = static_cast<float*>(a.take(gcfn_mid_reduce_ws(3 * F)));
+  }
+};
+size_t gcfn_bwd_fused_ws(long long M, int F) { return layout_bytes<GcfnBwdWs>(M, F); }
 
 namespace {
 // dy [M][F] fp32 -> out [M][F] bf16 = bf16(dropout1(dy)) (network.py:57's mask, 16-bit generator site 1, keep scale folded in; p = 0: a
@@ -678,12 +682,14 @@ int launch_gcfn_bwd_fused(const float* x, const float* stats, const float* dy, i
     return SEPR_EINVAL;
   if (M > 0x7fffffffLL / 8) return SEPR_EINVAL;
   if (xh16 && dy16 && M * F * 2 >= (1LL << 32)) return SEPR_EINVAL;   // 32-bit byte offsets of the plane-staged form
-  if (!ws || ws_bytes < gcfn_bwd_fused_ws(M, F)) return SEPR_EWORKSPACE;
+  Arena ar(ws, ws_bytes);
+  const GcfnBwdWs k(ar, M, F);
+  if (!ar.ok_need()) return SEPR_EWORKSPACE;
   GcfnBwdArgs a;
   a.x = x; a.stats = stats; a.dy = dy; a.M = (int)M; a.T = T; a.F = F;
   a.w1p = w->up.wp; a.b1 = w->up.b; a.w2tp = w->down_t.wp; a.dw_w = w->dw_w; a.dw_b = w->dw_b;
   a.g = g; a.dh1 = dh1; a.out16 = out16; a.dyq = p > 0.f ? dyq : nullptr;
-  a.part = static_cast<float*>(ws);
+  a.part = k.part;
   a.drop_thr = p > 0.f ? sepr_drop_thr16(p) : 0u;
   a.drop_scale = p > 0.f ? sepr_drop_scale16(p) : 1.0f;
   a.seed = seed; a.salt = salt;
@@ -723,8 +729,7 @@ int launch_gcfn_bwd_fused(const float* x, const float* stats, const float* dy, i
     prof_bytes((double)M * (8.0 * F + 8.0 + (out16 ? 2.0 : 4.0) * 9.0 * F + (p > 0.f ? 4.0 * F : 0.0)));   // x, dy, stats in; g, dh1 (, dyq) out
   }
   SEPR_CHECK_LAUNCH("gcfn_bwd_mid_kernel");
-  float* scratch = reinterpret_cast<float*>(static_cast<char*>(ws) + align_up((size_t)MB * 3 * F * 8 * sizeof(float)));
-  return launch_gcfn_mid_reduce(a.part, nslots, 3 * F, dw_g, db_g, scratch, st);
+  return launch_gcfn_mid_reduce(a.part, nslots, 3 * F, dw_g, db_g, k.scratch, st);
 }
 
 }  // namespace sepr

@@ -557,10 +557,13 @@ __global__ __launch_bounds__(256) void tn_reduce_kernel(const TnRed r) {
 }
 }  // namespace
 
+struct TnWs {   // ONE block: the splits' partial G [nsplit][N][K], their partial column sums [nsplit][N] right behind (no alignment between)
+  float *part, *cpart;
+  TnWs(Arena& a, const TnPlan& p, int N, int K) { part = a.f32((size_t)p.nsplit * ((size_t)N * K + N)); cpart = part + (size_t)p.nsplit * N * K; }
+};
 size_t tn_workspace_bytes(int M, int N, int K) {
   if (M <= 0 || N <= 0 || K <= 0) return 0;
-  const TnPlan p = tn_plan(M, N, K);
-  return align_up((size_t)p.nsplit * ((size_t)N * K + N) * sizeof(float));
+  return layout_bytes<TnWs>(tn_plan(M, N, K), N, K);
 }
 
 int launch_gemm_tn(const TnArgs& a, int x3, void* ws, size_t ws_bytes, hipStream_t s) {
@@ -568,10 +571,10 @@ int launch_gemm_tn(const TnArgs& a, int x3, void* ws, size_t ws_bytes, hipStream
   if (!a.A || !a.B || !a.G || a.N <= 0 || a.K <= 0 || (a.N % 4) || (a.K % 4) || (a.lda % 4) || (a.ldb % 4)) return SEPR_EINVAL;
   if (a.B2 && ((a.ksplit % 4) || (a.ldb2 % 4))) return SEPR_EINVAL;
   const TnPlan p = tn_plan(a.M, a.N, a.K);
-  const size_t need = tn_workspace_bytes(a.M, a.N, a.K);
-  if (!ws || ws_bytes < need) return SEPR_EWORKSPACE;
-  float* part = static_cast<float*>(ws);
-  float* cpart = part + (size_t)p.nsplit * a.N * a.K;
+  Arena ar(ws, ws_bytes);
+  const TnWs k(ar, p, a.N, a.K);
+  if (!ar.ok_need()) return SEPR_EWORKSPACE;
+  float *part = k.part, *cpart = k.cpart;
   const int grid = p.tn * p.tk * p.nsplit;
   // test switch (tests/tn_general_loader.py; read once, never set in the product): SEPR_TN_FORCE_GEN=1 routes every launch through the
   // general loader, so the public sepr_linear_wgrad_norm entry exercises it with per-row statistics at any size

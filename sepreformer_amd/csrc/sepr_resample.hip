@@ -57,6 +57,10 @@ __global__ __launch_bounds__(RS_TILE) void resample_kernel(const float* __restri
   }
   y[yo + n] = (float)acc;
 }
+struct ResampleWs {   // device copies of in_offset and out_offset [R + 1]
+  long long *ioff, *ooff;
+  ResampleWs(Arena& a, int R) { ioff = a.of<long long>((size_t)(R + 1)); ooff = a.of<long long>((size_t)(R + 1)); }
+};
 }  // namespace
 }  // namespace sepr
 
@@ -68,7 +72,7 @@ extern "C" long long sepr_resample_out_len(long long T, int L, int M) {
 extern "C" size_t sepr_resample_workspace(int R) {
   using namespace sepr;
   if (R < 1 || R > RS_MAX_R) return 0;
-  return 2 * align_up((size_t)(R + 1) * sizeof(long long));
+  return layout_bytes<ResampleWs>(R);
 }
 
 extern "C" int sepr_resample_fwd(const float* x, const long long* in_offset, float* y, const long long* out_offset, int R,
@@ -88,22 +92,21 @@ extern "C" int sepr_resample_fwd(const float* x, const long long* in_offset, flo
   }
   const long long tiles = (nmax + RS_TILE - 1) / RS_TILE;
   if (tiles > 0x7fffffffLL) return SEPR_EINVAL;
-  const size_t need = sepr_resample_workspace(R);
-  if (!ws || ws_bytes < need) return SEPR_EWORKSPACE;
+  Arena ar(ws, ws_bytes);
+  const ResampleWs k(ar, R);
+  if (!ar.ok_need()) return SEPR_EWORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  long long* ioff = static_cast<long long*>(ws);
-  long long* ooff = reinterpret_cast<long long*>(static_cast<char*>(ws) + need / 2);
-  hipError_t e = hipMemcpyAsync(ioff, in_offset, (size_t)(R + 1) * sizeof(long long), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(ooff, out_offset, (size_t)(R + 1) * sizeof(long long), hipMemcpyHostToDevice, st);
+  hipError_t e = hipMemcpyAsync(k.ioff, in_offset, (size_t)(R + 1) * sizeof(long long), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(k.ooff, out_offset, (size_t)(R + 1) * sizeof(long long), hipMemcpyHostToDevice, st);
   if (e != hipSuccess) {
     set_hip_error(e, "resample setup");
     return SEPR_EHIP;
   }
   const dim3 grid((unsigned)tiles, (unsigned)R);
   if (L == 1)
-    hipLaunchKernelGGL((resample_kernel<true>), grid, dim3(RS_TILE), lds, st, x, ioff, y, ooff, taps, L, M, K);
+    hipLaunchKernelGGL((resample_kernel<true>), grid, dim3(RS_TILE), lds, st, x, k.ioff, y, k.ooff, taps, L, M, K);
   else
-    hipLaunchKernelGGL((resample_kernel<false>), grid, dim3(RS_TILE), lds, st, x, ioff, y, ooff, taps, L, M, K);
+    hipLaunchKernelGGL((resample_kernel<false>), grid, dim3(RS_TILE), lds, st, x, k.ioff, y, k.ooff, taps, L, M, K);
   SEPR_CHECK_LAUNCH("resample kernel");
   return SEPR_OK;
 }

@@ -226,14 +226,20 @@ __global__ __launch_bounds__(STITCH_TPB) void stitch_ola_kernel(const float* __r
   }
   st4(y + e, out);
 }
+struct StitchWs {
+  double* stats;      // [total chunks][stitch_ns(S)] overlap statistics
+  int *coff, *lens;   // device copies of chunk_offset [R + 1] and lengths [R]
+  StitchWs(Arena& a, int R, int total, int S) {
+    stats = a.f64((size_t)total * stitch_ns(S)); coff = a.of<int>((size_t)(R + 1)); lens = a.of<int>((size_t)R);
+  }
+};
 }  // namespace
 }  // namespace sepr
 
 extern "C" size_t sepr_stitch_workspace(int R, int total_chunks, int S) {
   using namespace sepr;
   if (S < 2 || S > 3 || R <= 0 || total_chunks < R) return 0;
-  return align_up((size_t)total_chunks * stitch_ns(S) * sizeof(double)) + align_up((size_t)(R + 1) * sizeof(int)) +
-         align_up((size_t)R * sizeof(int));
+  return layout_bytes<StitchWs>(R, total_chunks, S);
 }
 
 extern "C" int sepr_stitch_fwd(const float* chunks, const int* chunk_offset, const int* lengths, int R, int S, int W, int O,
@@ -253,15 +259,12 @@ extern "C" int sepr_stitch_fwd(const float* chunks, const int* chunk_offset, con
   }
   const int total = chunk_offset[R];
   if ((long long)S * ((long long)total * H + (long long)R * O) / 4 > (long long)STITCH_TPB * 0x7fffffffLL) return SEPR_EINVAL;
-  const size_t need = sepr_stitch_workspace(R, total, S);
-  if (!ws || ws_bytes < need) return SEPR_EWORKSPACE;
+  Arena ar(ws, ws_bytes);
+  const StitchWs k(ar, R, total, S);
+  if (!ar.ok_need()) return SEPR_EWORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  char* p = static_cast<char*>(ws);
-  double* stats = reinterpret_cast<double*>(p);
-  int* coff = reinterpret_cast<int*>(p + align_up((size_t)total * stitch_ns(S) * sizeof(double)));
-  int* lens = reinterpret_cast<int*>(reinterpret_cast<char*>(coff) + align_up((size_t)(R + 1) * sizeof(int)));
-  hipError_t e = hipMemcpyAsync(coff, chunk_offset, (size_t)(R + 1) * sizeof(int), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(lens, lengths, (size_t)R * sizeof(int), hipMemcpyHostToDevice, st);
+  hipError_t e = hipMemcpyAsync(k.coff, chunk_offset, (size_t)(R + 1) * sizeof(int), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(k.lens, lengths, (size_t)R * sizeof(int), hipMemcpyHostToDevice, st);
   if (e != hipSuccess) {
     set_hip_error(e, "stitch setup");
     return SEPR_EHIP;
@@ -271,10 +274,10 @@ extern "C" int sepr_stitch_fwd(const float* chunks, const int* chunk_offset, con
 #define SEPR_STITCH_CASE(SS)                                                                                                   \
   case SS:                                                                                                                     \
     if (total > R)                                                                                                             \
-      hipLaunchKernelGGL((stitch_stats_kernel<SS>), dim3(total), dim3(STITCH_TPB), 0, st, chunks, coff, R, W, O, stats);     \
-    hipLaunchKernelGGL((stitch_plan_kernel<SS>), dim3(R), dim3(64), 0, st, stats, coff, O, mg, perm, gain);                  \
+      hipLaunchKernelGGL((stitch_stats_kernel<SS>), dim3(total), dim3(STITCH_TPB), 0, st, chunks, k.coff, R, W, O, k.stats);     \
+    hipLaunchKernelGGL((stitch_plan_kernel<SS>), dim3(R), dim3(64), 0, st, k.stats, k.coff, O, mg, perm, gain);                  \
     hipLaunchKernelGGL((stitch_ola_kernel<SS>), dim3((unsigned)((nquads + STITCH_TPB - 1) / STITCH_TPB)), dim3(STITCH_TPB), 0, \
-                       st, chunks, coff, lens, R, W, O, perm, gain, y, nquads);                                               \
+                       st, chunks, k.coff, k.lens, R, W, O, perm, gain, y, nquads);                                               \
     break;
   switch (S) {
     SEPR_STITCH_CASE(2)

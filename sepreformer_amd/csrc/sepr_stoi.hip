@@ -281,18 +281,24 @@ inline int st_tiles(int T) { return st_frames(T) > ST_NSEG ? (st_frames(T) - ST_
 inline bool st_shape_ok(int S, int B, int T) {
   return S >= 2 && S <= 3 && B >= 1 && T >= ST_FRAME && T <= (1 << 30) && (long long)B * S * (S + 2) <= 65535;
 }
-inline size_t st_bytes_energy(int S, int B, int T) { return align_up((size_t)B * S * st_frames(T) * sizeof(double)); }
-inline size_t st_bytes_idx(int S, int B, int T) { return align_up((size_t)B * S * st_frames(T) * sizeof(int)); }
-inline size_t st_bytes_nk(int S, int B) { return align_up((size_t)B * S * sizeof(int)); }
-inline size_t st_bytes_bands(int S, int B, int T) { return align_up((size_t)B * S * (S + 2) * ST_BANDS * st_frames(T) * sizeof(double)); }
-inline size_t st_bytes_part(int S, int B, int T) { return align_up((size_t)B * S * (S + 1) * (st_tiles(T) + 1) * 2 * sizeof(double)); }
+struct StoiWs {
+  double* energy;   // [B S][frames] frame energies of the references
+  int *idx, *nk;    // [B S][frames] kept-frame indices, [B S] their counts
+  double *bands;    // [B S (S + 2)][bands][frames] one-third-octave envelopes
+  double* part;     // [B S (S + 1)][tiles + 1][2] segment partials
+  StoiWs(Arena& a, int S, int B, int T) {
+    const size_t bs = (size_t)B * S, fr = st_frames(T);
+    energy = a.f64(bs * fr); idx = a.of<int>(bs * fr); nk = a.of<int>(bs);
+    bands = a.f64(bs * (S + 2) * ST_BANDS * fr); part = a.f64(bs * (S + 1) * (st_tiles(T) + 1) * 2);
+  }
+};
 }  // namespace
 }  // namespace sepr
 
 extern "C" size_t sepr_stoi_workspace(int S, int B, int T) {
   using namespace sepr;
   if (!st_shape_ok(S, B, T)) return 0;
-  return st_bytes_energy(S, B, T) + st_bytes_idx(S, B, T) + st_bytes_nk(S, B) + st_bytes_bands(S, B, T) + st_bytes_part(S, B, T);
+  return layout_bytes<StoiWs>(S, B, T);
 }
 
 extern "C" int sepr_stoi_fwd(const float* ref, const float* est, const float* mix, const int* lengths, int S, int B, int T,
@@ -302,29 +308,20 @@ extern "C" int sepr_stoi_fwd(const float* ref, const float* est, const float* mi
   if (!ref || !est || !lengths || !tables || !stoi || !estoi || !kept || !status) return SEPR_EINVAL;
   if (!st_shape_ok(S, B, T)) return SEPR_EINVAL;
   if ((mix == nullptr) != (stoi_mix == nullptr) || (mix == nullptr) != (estoi_mix == nullptr)) return SEPR_EINVAL;
-  const size_t need = sepr_stoi_workspace(S, B, T);
-  if (!ws || ws_bytes < need) return SEPR_EWORKSPACE;
+  Arena ar(ws, ws_bytes);
+  const StoiWs k(ar, S, B, T);
+  if (!ar.ok_need()) return SEPR_EWORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  char* p = static_cast<char*>(ws);
-  double* energy = reinterpret_cast<double*>(p);
-  p += st_bytes_energy(S, B, T);
-  int* idx = reinterpret_cast<int*>(p);
-  p += st_bytes_idx(S, B, T);
-  int* nk = reinterpret_cast<int*>(p);
-  p += st_bytes_nk(S, B);
-  double* bands = reinterpret_cast<double*>(p);
-  p += st_bytes_bands(S, B, T);
-  double* part = reinterpret_cast<double*>(p);
   const int Fmax = st_frames(T), ntiles = st_tiles(T), npairs = B * S * (S + 1);
   const double* win = tables;
   const double2* tw = reinterpret_cast<const double2*>(tables + ST_FRAME);
-  hipLaunchKernelGGL(stoi_mask_kernel, dim3(B * S), dim3(256), 0, st, ref, lengths, S, T, Fmax, win, energy, idx, nk, kept, status);
+  hipLaunchKernelGGL(stoi_mask_kernel, dim3(B * S), dim3(256), 0, st, ref, lengths, S, T, Fmax, win, k.energy, k.idx, k.nk, kept, status);
   if (Fmax > 1)
     hipLaunchKernelGGL(stoi_band_kernel, dim3(cdiv(Fmax - 1, ST_FT), B * S * (S + 2)), dim3(256), 0, st, ref, est, mix, S, T, Fmax, win, tw,
-                       idx, nk, bands);
+                       k.idx, k.nk, k.bands);
   if (ntiles > 0)
-    hipLaunchKernelGGL(stoi_seg_kernel, dim3(ntiles, npairs), dim3(256), 0, st, S, Fmax, ntiles, mix ? 1 : 0, nk, bands, part);
-  hipLaunchKernelGGL(stoi_final_kernel, dim3(cdiv(npairs, 64)), dim3(64), 0, st, S, npairs, ntiles, mix ? 1 : 0, nk, part, stoi, estoi, stoi_mix,
+    hipLaunchKernelGGL(stoi_seg_kernel, dim3(ntiles, npairs), dim3(256), 0, st, S, Fmax, ntiles, mix ? 1 : 0, k.nk, k.bands, k.part);
+  hipLaunchKernelGGL(stoi_final_kernel, dim3(cdiv(npairs, 64)), dim3(64), 0, st, S, npairs, ntiles, mix ? 1 : 0, k.nk, k.part, stoi, estoi, stoi_mix,
                      estoi_mix);
   SEPR_CHECK_LAUNCH("stoi kernels");
   return SEPR_OK;

@@ -5,9 +5,10 @@
 // the row-wise pieces of sepr_train_pw.hip / sepr_train_attn.hip.
 //
 // Layout of a block's context and scratch is defined ONCE, by the block's own implementation running in "dry" mode
-// (Carve::dry): sepr_train_ctx_bytes / sepr_train_ws_bytes replay the same carving without launching anything.
+// (Arena::sizing, sepr_common.h): sepr_train_ctx_bytes / sepr_train_ws_bytes replay the same carving without launching anything.
 #include <stdlib.h>
 #include <string.h>
+#include <algorithm>
 
 #include "sepr_gcfn_fused.h"
 #include "sepr_pointwise.h"
@@ -22,29 +23,12 @@ const float LN_EPS_T = 1e-5f, BN_EPS_T = 1e-5f, BN_MOM = 0.1f;
 // (configs.yaml: kernel_size 16, stride 4).  Any other geometry is a clear SEPR_EINVAL instead of an undersized workspace.
 constexpr int TRAIN_ENC_K = 16, TRAIN_ENC_STRIDE = 4;
 
-struct Carve {
-  char* base;
-  size_t size, off;
-  bool dry;
-  Carve(void* p, size_t n, bool d) : base(static_cast<char*>(p)), size(n), off(0), dry(d) {}
-  void* take(size_t bytes) {
-    const size_t o = align_up(off);
-    off = o + bytes;
-    if (dry) return reinterpret_cast<void*>(0x1000);   // never dereferenced
-    if (!base || off > size) return nullptr;
-    return base + o;
-  }
-  float* f32(size_t count) { return static_cast<float*>(take(count * sizeof(float))); }
-  bool ok() const { return dry || (base != nullptr && off <= size); }
-  size_t need() const { return align_up(off); }
-};
-
 // Scratch of ONE finished projection - the reduced contraction G [N][K] and its column sums s [N] (sepr_train.h finishers).  With a
 // deferred-finisher window open on this thread the pair lives in the window's arena until the flush (every projection its OWN slot: the
 // finisher runs later, so the buffers of a block cannot be shared between its projections as the workspace copies are); otherwise, and
 // in sizing runs, it is carved from the workspace like everything else (the carve itself is identical in both cases).
 struct FinBuf { float* G; float* s; };
-FinBuf fin_buf(Carve& ws, long long nk, int n) {
+FinBuf fin_buf(Arena& ws, long long nk, int n) {
   FinBuf b;
   b.G = ws.f32((size_t)nk);
   b.s = ws.f32((size_t)n);
@@ -118,7 +102,7 @@ sepr_u64 site_off(int site) { return (sepr_u64)site << 44; }
 // GCFN  (network.py:46-66)
 // =====================================================================================================================
 struct GcfnCtx { float *stats, *h1, *g; };
-GcfnCtx gcfn_ctx(Carve& c, long long M, int F) {
+GcfnCtx gcfn_ctx(Arena& c, long long M, int F) {
   GcfnCtx k;
   k.stats = c.f32(2 * M);
   k.h1 = c.f32(6LL * F * M);
@@ -144,7 +128,7 @@ bool gcfn_pl16(const sepr_gcfn_tw* w, int pl_dry) {
 int attn_one(const sepr_lin& qkv) {
   return (knob(SEPR_KNOB_TRAIN_ATTN_ONE) != 0 && qkv.planes == 1) ? 1 : 0;
 }
-int gcfn_fused_fwd(const float* x, float* y, int n, int T, int F, const sepr_gcfn_tw* w, Carve& cx, float p, sepr_u64 seed,
+int gcfn_fused_fwd(const float* x, float* y, int n, int T, int F, const sepr_gcfn_tw* w, Arena& cx, float p, sepr_u64 seed,
                    hipStream_t st, int pl_dry = -1) {
   const long long M = (long long)n * T;
   float* stats = cx.f32(2 * M);
@@ -166,7 +150,7 @@ int gcfn_fused_fwd(const float* x, float* y, int n, int T, int F, const sepr_gcf
   return launch_gcfn_fused(f, F, SEPR_SITE_GCFN_UP, st);
 }
 int gcfn_fused_bwd(const float* x, const float* dy, float* dx, int n, int T, int F, const sepr_gcfn_tw* w, const sepr_gcfn_grad* g,
-                   Carve& cx, Carve& ws, float p, sepr_u64 seed, hipStream_t st, int pl_dry = -1) {
+                   Arena& cx, Arena& ws, float p, sepr_u64 seed, hipStream_t st, int pl_dry = -1) {
   const long long M = (long long)n * T;
   float* stats = cx.f32(2 * M);
   const bool pl = gcfn_pl16(w, pl_dry);
@@ -184,8 +168,7 @@ int gcfn_fused_bwd(const float* x, const float* dy, float* dx, int n, int T, int
   float* dWh = fb1.G;
   float* s1 = fb1.s;
   float* dxh = ws.f32((long long)F * M);
-  const size_t tnb = tn_workspace_bytes((int)M, 6 * F, F) > tn_workspace_bytes((int)M, F, 3 * F) ? tn_workspace_bytes((int)M, 6 * F, F)
-                                                                                                   : tn_workspace_bytes((int)M, F, 3 * F);
+  const size_t tnb = std::max(tn_workspace_bytes((int)M, 6 * F, F), tn_workspace_bytes((int)M, F, 3 * F));
   void* tnw = ws.take(tnb);
   const size_t midb = gcfn_bwd_fused_ws(M, F);
   void* midw = ws.take(midb);
@@ -219,7 +202,7 @@ int gcfn_fused_bwd(const float* x, const float* dy, float* dx, int n, int T, int
   SEPR_TRY(launch_finish_norm_linear(dWh, s1, w->w1, w->ln_g, w->ln_b, g->w1, g->b1, g->ln_g, g->ln_b, 6 * F, F, st));
   return dgrad_ln(static_cast<const float*>(dh1), 6 * F, 6 * F, w->up_t, o16 ? 1 : 0, x, stats, dy, nullptr, 0, 0, 0, dx, dxh, M, F, st);
 }
-int gcfn_fwd(const float* x, float* y, int n, int T, int F, const sepr_gcfn_tw* w, Carve& cx, Carve& ws, float p, sepr_u64 seed,
+int gcfn_fwd(const float* x, float* y, int n, int T, int F, const sepr_gcfn_tw* w, Arena& cx, Arena& ws, float p, sepr_u64 seed,
              hipStream_t st) {
   const long long M = (long long)n * T;
   GcfnCtx k = gcfn_ctx(cx, M, F);
@@ -242,8 +225,8 @@ int gcfn_fwd(const float* x, float* y, int n, int T, int F, const sepr_gcfn_tw* 
   }
   return SEPR_OK;
 }
-int gcfn_bwd(const float* x, const float* dy, float* dx, int n, int T, int F, const sepr_gcfn_tw* w, const sepr_gcfn_grad* g, Carve& cx,
-             Carve& ws, float p, sepr_u64 seed, hipStream_t st) {
+int gcfn_bwd(const float* x, const float* dy, float* dx, int n, int T, int F, const sepr_gcfn_tw* w, const sepr_gcfn_grad* g, Arena& cx,
+             Arena& ws, float p, sepr_u64 seed, hipStream_t st) {
   const long long M = (long long)n * T;
   GcfnCtx k = gcfn_ctx(cx, M, F);
   float* dyp = p > 0.f ? ws.f32((long long)F * M) : nullptr;
@@ -256,8 +239,7 @@ int gcfn_bwd(const float* x, const float* dy, float* dx, int n, int T, int F, co
   float* dWh = fb1.G;
   float* s1 = fb1.s;
   float* dxh = ws.f32((long long)F * M);
-  const size_t tnb = tn_workspace_bytes((int)M, 6 * F, F) > tn_workspace_bytes((int)M, F, 3 * F) ? tn_workspace_bytes((int)M, 6 * F, F)
-                                                                                                   : tn_workspace_bytes((int)M, F, 3 * F);
+  const size_t tnb = std::max(tn_workspace_bytes((int)M, 6 * F, F), tn_workspace_bytes((int)M, F, 3 * F));
   void* tnw = ws.take(tnb);
   const size_t midb = gcfn_mid_bwd_ws(n, T, 3 * F);
   void* midw = ws.take(midb);
@@ -293,7 +275,7 @@ bool cla_h16(const sepr_cla_tw* w, int F, int K) {
 }
 constexpr unsigned CLA_DROP_SITE = 3u;   // 16-bit generator site of the CLA output dropout (0, 1: fused GCFN; 2: attention probabilities)
 struct ClaCtx { float *stats, *a, *u, *c, *z, *bn, *d; };
-ClaCtx cla_ctx(Carve& cx, long long M, int F) {
+ClaCtx cla_ctx(Arena& cx, long long M, int F) {
   ClaCtx k;
   k.stats = cx.f32(2 * M);
   k.a = cx.f32(2LL * F * M);    // linear1 output (pre-GLU)
@@ -304,7 +286,7 @@ ClaCtx cla_ctx(Carve& cx, long long M, int F) {
   k.d = cx.f32(2LL * F * M);    // gelu(bn(z)) (post-dropout input of linear3 when p > 0 ... dropout sits after linear3)
   return k;
 }
-int cla_fwd(const float* x, float* y, int n, int T, int F, int K, const sepr_cla_tw* w, Carve& cx, Carve& ws, float p, sepr_u64 seed,
+int cla_fwd(const float* x, float* y, int n, int T, int F, int K, const sepr_cla_tw* w, Arena& cx, Arena& ws, float p, sepr_u64 seed,
             hipStream_t st) {
   const long long M = (long long)n * T;
   ClaCtx k = cla_ctx(cx, M, F);
@@ -348,7 +330,7 @@ int cla_fwd(const float* x, float* y, int n, int T, int F, int K, const sepr_cla
   return SEPR_OK;
 }
 int cla_bwd(const float* x, const float* dy, float* dx, int n, int T, int F, int K, const sepr_cla_tw* w, const sepr_cla_grad* g,
-            Carve& cx, Carve& ws, float p, sepr_u64 seed, hipStream_t st) {
+            Arena& cx, Arena& ws, float p, sepr_u64 seed, hipStream_t st) {
   const long long M = (long long)n * T;
   ClaCtx k = cla_ctx(cx, M, F);
   float* dyp = p > 0.f ? ws.f32((long long)F * M) : nullptr;
@@ -464,7 +446,7 @@ bool ega_mfma(const sepr_ega_tw* w, int F, int H) {
   return w && w->attn.qkv.wp && (dk == 16 || dk == 32);
 }
 struct EgaCtx { float *stats, *stats_p, *xd, *qkv, *P, *o, *att, *zg; };
-EgaCtx ega_ctx(Carve& cx, int n, int T, int Tp, int F, int H, bool mfma = false) {
+EgaCtx ega_ctx(Arena& cx, int n, int T, int Tp, int F, int H, bool mfma = false) {
   const long long M = (long long)n * T, Mp = (long long)n * Tp;
   EgaCtx k;
   k.stats = cx.f32(2 * M);
@@ -477,7 +459,7 @@ EgaCtx ega_ctx(Carve& cx, int n, int T, int Tp, int F, int H, bool mfma = false)
   k.zg = cx.f32((long long)F * M);
   return k;
 }
-int ega_fwd(const float* x, float* y, int n, int T, int Tp, int F, int H, const sepr_ega_tw* w, Carve& cx, Carve& ws, float p,
+int ega_fwd(const float* x, float* y, int n, int T, int Tp, int F, int H, const sepr_ega_tw* w, Arena& cx, Arena& ws, float p,
             sepr_u64 seed, hipStream_t st, int mfma_dry = -1) {
   const long long M = (long long)n * T, Mp = (long long)n * Tp;
   const int fac = T / Tp;
@@ -510,7 +492,7 @@ int ega_fwd(const float* x, float* y, int n, int T, int Tp, int F, int H, const 
   return SEPR_OK;
 }
 int ega_bwd(const float* x, const float* dy, float* dx, int n, int T, int Tp, int F, int H, const sepr_ega_tw* w, const sepr_ega_grad* g,
-            Carve& cx, Carve& ws, float p, sepr_u64 seed, hipStream_t st, int mfma_dry = -1) {
+            Arena& cx, Arena& ws, float p, sepr_u64 seed, hipStream_t st, int mfma_dry = -1) {
   const long long M = (long long)n * T, Mp = (long long)n * Tp;
   const int fac = T / Tp;
   const bool mfma = mfma_dry >= 0 ? mfma_dry != 0 : ega_mfma(w, F, H);
@@ -523,8 +505,7 @@ int ega_bwd(const float* x, const float* dy, float* dx, int n, int T, int Tp, in
   float* dxd = ws.f32((long long)F * Mp);
   const FinBuf fbo = fin_buf(ws, (long long)F * F, F), fbq = fin_buf(ws, 3LL * F * F, 3 * F), fbg = fin_buf(ws, (long long)F * F, F);   // out, q/k/v, gate
   float* dxh = ws.f32((long long)F * M);
-  size_t tnb = tn_workspace_bytes((int)M, F, F);
-  if (tn_workspace_bytes((int)Mp, 3 * F, F) > tnb) tnb = tn_workspace_bytes((int)Mp, 3 * F, F);
+  const size_t tnb = std::max(tn_workspace_bytes((int)M, F, F), tn_workspace_bytes((int)Mp, 3 * F, F));
   void* tnw = ws.take(tnb);
   const size_t atb = mfma ? relattn_x3_bwd_ws(n, Tp, F, H) : relattn_train_ws(n, Tp, F, H);
   void* atw = ws.take(atb);
@@ -553,14 +534,14 @@ int ega_bwd(const float* x, const float* dy, float* dx, int n, int T, int Tp, in
 // SpkAttention up to its feed-forward  (network.py:233-247)
 // =====================================================================================================================
 struct SpkCtx { float *stats, *qkv, *o; };
-SpkCtx spk_ctx(Carve& cx, long long M, int F) {
+SpkCtx spk_ctx(Arena& cx, long long M, int F) {
   SpkCtx k;
   k.stats = cx.f32(2 * M);
   k.qkv = cx.f32(3LL * F * M);
   k.o = cx.f32((long long)F * M);
   return k;
 }
-int spk_fwd(const float* x, float* y, int nS, int S, int T, int F, int H, const sepr_mha_tw* w, Carve& cx, Carve& ws, float p,
+int spk_fwd(const float* x, float* y, int nS, int S, int T, int F, int H, const sepr_mha_tw* w, Arena& cx, Arena& ws, float p,
             sepr_u64 seed, hipStream_t st) {
   const long long M = (long long)nS * T;
   SpkCtx k = spk_ctx(cx, M, F);
@@ -581,7 +562,7 @@ int spk_fwd(const float* x, float* y, int nS, int S, int T, int F, int H, const 
   return lin(PRO_PLAIN, EPI_RES, a, w->out, SEPR_SITE_NONE, st);
 }
 int spk_bwd(const float* x, const float* dy, float* dx, int nS, int S, int T, int F, int H, const sepr_mha_tw* w, const sepr_mha_grad* g,
-            Carve& cx, Carve& ws, float p, sepr_u64 seed, hipStream_t st) {
+            Arena& cx, Arena& ws, float p, sepr_u64 seed, hipStream_t st) {
   const long long M = (long long)nS * T;
   SpkCtx k = spk_ctx(cx, M, F);
   float* dO = ws.f32((long long)F * M);
@@ -609,13 +590,13 @@ int spk_bwd(const float* x, const float* dy, float* dx, int nS, int S, int T, in
 // =====================================================================================================================
 struct DownCtx { float *c, *bn; };
 int down_To(int T, int K) { return (T + 2 * ((K - 1) / 2) - K) / 2 + 1; }
-DownCtx down_ctx(Carve& cx, int n, int To, int F) {
+DownCtx down_ctx(Arena& cx, int n, int To, int F) {
   DownCtx k;
   k.c = cx.f32((long long)n * To * F);
   k.bn = cx.f32(2 * F);
   return k;
 }
-int down_fwd(const float* x, float* y, int n, int T, int F, int K, const sepr_down_tw* w, Carve& cx, Carve& ws, hipStream_t st) {
+int down_fwd(const float* x, float* y, int n, int T, int F, int K, const sepr_down_tw* w, Arena& cx, Arena& ws, hipStream_t st) {
   const int To = down_To(T, K);
   DownCtx k = down_ctx(cx, n, To, F);
   const size_t csb = colstats_ws((long long)n * To, F);
@@ -627,7 +608,7 @@ int down_fwd(const float* x, float* y, int n, int T, int F, int K, const sepr_do
   return launch_bn_gelu_fwd(k.c, k.bn, w->bn_g, w->bn_b, y, (long long)n * To, F, st);                          // :75-76
 }
 int down_bwd(const float* x, const float* dy, float* dx, int n, int T, int F, int K, const sepr_down_tw* w, const sepr_down_grad* g,
-             Carve& cx, Carve& ws, hipStream_t st) {
+             Arena& cx, Arena& ws, hipStream_t st) {
   const int To = down_To(T, K);
   DownCtx k = down_ctx(cx, n, To, F);
   float* dc = ws.f32((long long)n * To * F);
@@ -645,7 +626,7 @@ int down_bwd(const float* x, const float* dy, float* dx, int n, int T, int F, in
 // SpkSplitStage (module.py:110-125)
 // =====================================================================================================================
 struct SplitCtx { float *a, *z, *v, *stats; };
-SplitCtx split_ctx(Carve& cx, int B, int S, int T, int F) {
+SplitCtx split_ctx(Arena& cx, int B, int S, int T, int F) {
   const long long M = (long long)B * T;
   SplitCtx k;
   k.a = cx.f32(4LL * F * S * M);     // linear.0 output (pre-GLU)
@@ -654,7 +635,7 @@ SplitCtx split_ctx(Carve& cx, int B, int S, int T, int F) {
   k.stats = cx.f32(2LL * B * S);
   return k;
 }
-int split_fwd(const float* x, float* y, int B, int S, int T, int F, float eps, const sepr_split_tw* w, Carve& cx, Carve& ws,
+int split_fwd(const float* x, float* y, int B, int S, int T, int F, float eps, const sepr_split_tw* w, Arena& cx, Arena& ws,
               hipStream_t st) {
   const long long M = (long long)B * T;
   SplitCtx k = split_ctx(cx, B, S, T, F);
@@ -677,7 +658,7 @@ int split_fwd(const float* x, float* y, int B, int S, int T, int F, float eps, c
   return launch_gn_apply_oop(k.v, k.stats, w->gn_g, w->gn_b, y, n_out, T, F, st);                // :124
 }
 int split_bwd(const float* x, const float* dy, float* dx, int dx_acc, int B, int S, int T, int F, const sepr_split_tw* w,
-              const sepr_split_grad* g, Carve& cx, Carve& ws, hipStream_t st) {
+              const sepr_split_grad* g, Arena& cx, Arena& ws, hipStream_t st) {
   const long long M = (long long)B * T;
   SplitCtx k = split_ctx(cx, B, S, T, F);
   float* dv = ws.f32((long long)F * S * M);      // [M][S*F] (channel-split inverted)
@@ -685,8 +666,7 @@ int split_bwd(const float* x, const float* dy, float* dx, int dx_acc, int B, int
   float* da = ws.f32(4LL * F * S * M);
   const size_t gnb = gn_bwd_ws(B * S, T, F);
   void* gnw = ws.take(gnb);
-  size_t tnb = tn_workspace_bytes((int)M, F * S, 2 * F * S);
-  if (tn_workspace_bytes((int)M, 4 * F * S, F) > tnb) tnb = tn_workspace_bytes((int)M, 4 * F * S, F);
+  const size_t tnb = std::max(tn_workspace_bytes((int)M, F * S, 2 * F * S), tn_workspace_bytes((int)M, 4 * F * S, F));
   void* tnw = ws.take(tnb);
   if (ws.dry) return SEPR_OK;
   if (!cx.ok() || !ws.ok()) return SEPR_EWORKSPACE;
@@ -713,7 +693,7 @@ extern "C" int sepr_gcfn_train_fwd(const float* x, float* y, int n, int T, int F
                                    void* ws, size_t ws_bytes, float p_drop, sepr_u64 seed, sepr_stream_t stream) {
   if (!x || !y || !w || n <= 0 || T <= 0 || F <= 0 || F % 32 || !rows_ok((long long)n * T) || x == y) return SEPR_EINVAL;
   DropSaltScope salt_scope(w->seed_salt);
-  Carve cx(ctx, ctx_bytes, false), wk(ws, ws_bytes, false);
+  Arena cx(ctx, ctx_bytes), wk(ws, ws_bytes);
   if (gcfn_is_fused(w, F)) return gcfn_fused_fwd(x, y, n, T, F, w, cx, p_drop, seed, SEPR_ST);
   return gcfn_fwd(x, y, n, T, F, w, cx, wk, p_drop, seed, SEPR_ST);
 }
@@ -722,7 +702,7 @@ extern "C" int sepr_gcfn_bwd(const float* x, const float* dy, float* dx, int n, 
                              sepr_u64 seed, sepr_stream_t stream) {
   if (!x || !dy || !dx || !w || !g || n <= 0 || T <= 0 || F <= 0 || F % 32 || !rows_ok((long long)n * T)) return SEPR_EINVAL;
   DropSaltScope salt_scope(w->seed_salt);
-  Carve cx(const_cast<void*>(ctx), ctx_bytes, false), wk(ws, ws_bytes, false);
+  Arena cx(const_cast<void*>(ctx), ctx_bytes), wk(ws, ws_bytes);
   if (gcfn_is_fused(w, F)) return gcfn_fused_bwd(x, dy, dx, n, T, F, w, g, cx, wk, p_drop, seed, SEPR_ST);
   return gcfn_bwd(x, dy, dx, n, T, F, w, g, cx, wk, p_drop, seed, SEPR_ST);
 }
@@ -730,7 +710,7 @@ extern "C" int sepr_cla_train_fwd(const float* x, float* y, int n, int T, int F,
                                   void* ws, size_t ws_bytes, float p_drop, sepr_u64 seed, sepr_stream_t stream) {
   if (!x || !y || !w || n <= 0 || T <= 0 || F <= 0 || F % 64 || !rows_ok((long long)n * T) || x == y) return SEPR_EINVAL;
   DropSaltScope salt_scope(w->seed_salt);
-  Carve cx(ctx, ctx_bytes, false), wk(ws, ws_bytes, false);
+  Arena cx(ctx, ctx_bytes), wk(ws, ws_bytes);
   return cla_fwd(x, y, n, T, F, K, w, cx, wk, p_drop, seed, SEPR_ST);
 }
 extern "C" int sepr_cla_bwd(const float* x, const float* dy, float* dx, int n, int T, int F, int K, const sepr_cla_tw* w,
@@ -738,7 +718,7 @@ extern "C" int sepr_cla_bwd(const float* x, const float* dy, float* dx, int n, i
                             sepr_u64 seed, sepr_stream_t stream) {
   if (!x || !dy || !dx || !w || !g || n <= 0 || T <= 0 || F <= 0 || F % 64 || !rows_ok((long long)n * T)) return SEPR_EINVAL;
   DropSaltScope salt_scope(w->seed_salt);
-  Carve cx(const_cast<void*>(ctx), ctx_bytes, false), wk(ws, ws_bytes, false);
+  Arena cx(const_cast<void*>(ctx), ctx_bytes), wk(ws, ws_bytes);
   return cla_bwd(x, dy, dx, n, T, F, K, w, g, cx, wk, p_drop, seed, SEPR_ST);
 }
 extern "C" int sepr_ega_train_fwd(const float* x, float* y, int n, int T, int Tp, int F, int H, const sepr_ega_tw* w, void* ctx,
@@ -747,7 +727,7 @@ extern "C" int sepr_ega_train_fwd(const float* x, float* y, int n, int T, int Tp
       !rows_ok((long long)n * T))
     return SEPR_EINVAL;
   DropSaltScope salt_scope(w->attn.seed_salt);
-  Carve cx(ctx, ctx_bytes, false), wk(ws, ws_bytes, false);
+  Arena cx(ctx, ctx_bytes), wk(ws, ws_bytes);
   return ega_fwd(x, y, n, T, Tp, F, H, w, cx, wk, p_drop, seed, SEPR_ST);
 }
 extern "C" int sepr_ega_bwd(const float* x, const float* dy, float* dx, int n, int T, int Tp, int F, int H, const sepr_ega_tw* w,
@@ -757,7 +737,7 @@ extern "C" int sepr_ega_bwd(const float* x, const float* dy, float* dx, int n, i
       !rows_ok((long long)n * T))
     return SEPR_EINVAL;
   DropSaltScope salt_scope(w->attn.seed_salt);
-  Carve cx(const_cast<void*>(ctx), ctx_bytes, false), wk(ws, ws_bytes, false);
+  Arena cx(const_cast<void*>(ctx), ctx_bytes), wk(ws, ws_bytes);
   return ega_bwd(x, dy, dx, n, T, Tp, F, H, w, g, cx, wk, p_drop, seed, SEPR_ST);
 }
 extern "C" int sepr_spkattn_train_fwd(const float* x, float* y, int nS, int S, int T, int F, int H, const sepr_mha_tw* w, void* ctx,
@@ -765,7 +745,7 @@ extern "C" int sepr_spkattn_train_fwd(const float* x, float* y, int nS, int S, i
   if (!x || !y || !w || nS <= 0 || S <= 0 || nS % S || T <= 0 || F <= 0 || F % 32 || H <= 0 || F % H || !rows_ok((long long)nS * T))
     return SEPR_EINVAL;
   DropSaltScope salt_scope(w->seed_salt);
-  Carve cx(ctx, ctx_bytes, false), wk(ws, ws_bytes, false);
+  Arena cx(ctx, ctx_bytes), wk(ws, ws_bytes);
   return spk_fwd(x, y, nS, S, T, F, H, w, cx, wk, p_drop, seed, SEPR_ST);
 }
 extern "C" int sepr_spkattn_bwd(const float* x, const float* dy, float* dx, int nS, int S, int T, int F, int H, const sepr_mha_tw* w,
@@ -775,33 +755,33 @@ extern "C" int sepr_spkattn_bwd(const float* x, const float* dy, float* dx, int 
       !rows_ok((long long)nS * T))
     return SEPR_EINVAL;
   DropSaltScope salt_scope(w->seed_salt);
-  Carve cx(const_cast<void*>(ctx), ctx_bytes, false), wk(ws, ws_bytes, false);
+  Arena cx(const_cast<void*>(ctx), ctx_bytes), wk(ws, ws_bytes);
   return spk_bwd(x, dy, dx, nS, S, T, F, H, w, g, cx, wk, p_drop, seed, SEPR_ST);
 }
 extern "C" int sepr_downconv_train_fwd(const float* x, float* y, int n, int T, int F, int K, const sepr_down_tw* w, void* ctx,
                                        size_t ctx_bytes, void* ws, size_t ws_bytes, sepr_stream_t stream) {
   if (!x || !y || !w || n <= 0 || T <= 0 || F <= 0 || F % 4 || K <= 0 || !(K & 1)) return SEPR_EINVAL;
-  Carve cx(ctx, ctx_bytes, false), wk(ws, ws_bytes, false);
+  Arena cx(ctx, ctx_bytes), wk(ws, ws_bytes);
   return down_fwd(x, y, n, T, F, K, w, cx, wk, SEPR_ST);
 }
 extern "C" int sepr_downconv_bwd(const float* x, const float* dy, float* dx, int n, int T, int F, int K, const sepr_down_tw* w,
                                  const sepr_down_grad* g, const void* ctx, size_t ctx_bytes, void* ws, size_t ws_bytes,
                                  sepr_stream_t stream) {
   if (!x || !dy || !dx || !w || !g || n <= 0 || T <= 0 || F <= 0 || F % 4 || K <= 0 || !(K & 1)) return SEPR_EINVAL;
-  Carve cx(const_cast<void*>(ctx), ctx_bytes, false), wk(ws, ws_bytes, false);
+  Arena cx(const_cast<void*>(ctx), ctx_bytes), wk(ws, ws_bytes);
   return down_bwd(x, dy, dx, n, T, F, K, w, g, cx, wk, SEPR_ST);
 }
 extern "C" int sepr_spksplit_train_fwd(const float* x, float* y, int B, int S, int T, int F, float gn_eps, const sepr_split_tw* w,
                                        void* ctx, size_t ctx_bytes, void* ws, size_t ws_bytes, sepr_stream_t stream) {
   if (!x || !y || !w || B <= 0 || S <= 0 || T <= 0 || F <= 0 || F % 32 || !rows_ok((long long)B * T * S)) return SEPR_EINVAL;
-  Carve cx(ctx, ctx_bytes, false), wk(ws, ws_bytes, false);
+  Arena cx(ctx, ctx_bytes), wk(ws, ws_bytes);
   return split_fwd(x, y, B, S, T, F, gn_eps, w, cx, wk, SEPR_ST);
 }
 extern "C" int sepr_spksplit_bwd(const float* x, const float* dy, float* dx, int dx_accumulate, int B, int S, int T, int F,
                                  const sepr_split_tw* w, const sepr_split_grad* g, const void* ctx, size_t ctx_bytes, void* ws,
                                  size_t ws_bytes, sepr_stream_t stream) {
   if (!x || !dy || !dx || !w || !g || B <= 0 || S <= 0 || T <= 0 || F <= 0 || F % 32 || !rows_ok((long long)B * T * S)) return SEPR_EINVAL;
-  Carve cx(const_cast<void*>(ctx), ctx_bytes, false), wk(ws, ws_bytes, false);
+  Arena cx(const_cast<void*>(ctx), ctx_bytes), wk(ws, ws_bytes);
   return split_bwd(x, dy, dx, dx_accumulate, B, S, T, F, w, g, cx, wk, SEPR_ST);
 }
 
@@ -837,7 +817,7 @@ namespace sepr {
 namespace {
 
 int fuse_bwd(const float* lo, const float* skip, const float* dy, float* dlo, float* dskip, int n, int T, int F, const sepr_fuse_tw* w,
-             const sepr_fuse_grad* g, Carve& ws, hipStream_t st) {
+             const sepr_fuse_grad* g, Arena& ws, hipStream_t st) {
   const long long M = (long long)n * T;
   float* dcat = ws.f32(2LL * F * M);
   const size_t tnb = tn_workspace_bytes((int)M, F, 2 * F);
@@ -856,7 +836,7 @@ int fuse_bwd(const float* lo, const float* skip, const float* dy, float* dlo, fl
 }
 
 struct OutCtx { float *a1, *o1, *o2; };
-OutCtx out_ctx(Carve& cx, long long Mp, int F, int N) {
+OutCtx out_ctx(Arena& cx, long long Mp, int F, int N) {
   OutCtx k;
   k.a1 = cx.f32(4LL * F * Mp);
   k.o1 = cx.f32(2LL * F * Mp);
@@ -864,7 +844,7 @@ OutCtx out_ctx(Carve& cx, long long Mp, int F, int N) {
   return k;
 }
 int out_fwd(const float* x, int nS, int S, int Tsrc, int L, const int* idx, const float* enc, int F, int N, int K, int stride,
-            const sepr_out_tw* w, float* wav, Carve& cx, hipStream_t st) {
+            const sepr_out_tw* w, float* wav, Arena& cx, hipStream_t st) {
   const long long Mp = idx ? (long long)nS * Tsrc : (long long)nS * L;
   OutCtx k = out_ctx(cx, Mp, F, N);
   if (cx.dry) return SEPR_OK;
@@ -883,7 +863,7 @@ int out_fwd(const float* x, int nS, int S, int Tsrc, int L, const int* idx, cons
 }
 int out_bwd(const float* x, const float* dwav, float* dx, int dx_acc, float* denc, int nS, int S, int Tsrc, int L, const int* idx,
             const int* idx_start, const float* enc, int F, int N, int K, int stride, const sepr_out_tw* w, const sepr_out_grad* g,
-            Carve& cx, Carve& ws, hipStream_t st) {
+            Arena& cx, Arena& ws, hipStream_t st) {
   const bool aux = idx != nullptr;
   const long long Mp = aux ? (long long)nS * Tsrc : (long long)nS * L, ML = (long long)nS * L;
   const int Tout = (L - 1) * stride + K;
@@ -894,9 +874,7 @@ int out_bwd(const float* x, const float* dwav, float* dx, int dx_acc, float* den
   float* do2 = aux ? ws.f32((long long)N * Mp) : dm;
   float* do1 = ws.f32(2LL * F * Mp);
   float* da1 = ws.f32(4LL * F * Mp);
-  size_t tnb = tn_workspace_bytes((int)ML, N, K);
-  if (tn_workspace_bytes((int)Mp, N, 2 * F) > tnb) tnb = tn_workspace_bytes((int)Mp, N, 2 * F);
-  if (tn_workspace_bytes((int)Mp, 4 * F, F) > tnb) tnb = tn_workspace_bytes((int)Mp, 4 * F, F);
+  const size_t tnb = std::max({tn_workspace_bytes((int)ML, N, K), tn_workspace_bytes((int)Mp, N, 2 * F), tn_workspace_bytes((int)Mp, 4 * F, F)});
   void* tnw = ws.take(tnb);
   if (ws.dry) return SEPR_OK;
   if (!cx.ok() || !ws.ok()) return SEPR_EWORKSPACE;
@@ -943,7 +921,7 @@ int out_bwd(const float* x, const float* dwav, float* dx, int dx_acc, float* den
 }
 
 int front_fwd(const float* wav, int B, int T, int N, int K, int stride, int F, int Lp, float eps, const sepr_front_tw* w, float* enc,
-              float* out, Carve& cx, Carve& ws, hipStream_t st) {
+              float* out, Arena& cx, Arena& ws, hipStream_t st) {
   const int L = (T - K) / stride + 1;
   float* stats = cx.f32(2 * B);
   const int ntile = encoder_tiles(L);
@@ -960,7 +938,7 @@ int front_fwd(const float* wav, int B, int T, int N, int K, int stride, int F, i
   return launch_gemm(PRO_NORM, EPI_STORE, a, SEPR_SITE_PROJECTOR, st);
 }
 int front_bwd(const float* wav, const float* enc, const float* dout, float* denc_aux, int B, int T, int N, int K, int stride, int F,
-              int Lp, const sepr_front_tw* w, const sepr_front_grad* g, Carve& cx, Carve& ws, hipStream_t st) {
+              int Lp, const sepr_front_tw* w, const sepr_front_grad* g, Arena& cx, Arena& ws, hipStream_t st) {
   const int L = (T - K) / stride + 1;
   const long long ML = (long long)B * L;
   float* stats = cx.f32(2 * B);
@@ -969,8 +947,7 @@ int front_bwd(const float* wav, const float* enc, const float* dout, float* denc
   float* deh = ws.f32((long long)N * ML);
   float* de = ws.f32((long long)N * ML);
   float* dump = ws.f32(2 * N);
-  size_t tnb = tn_workspace_bytes(B * Lp, F, N);
-  if (tn_workspace_bytes((int)ML, N, K) > tnb) tnb = tn_workspace_bytes((int)ML, N, K);
+  const size_t tnb = std::max(tn_workspace_bytes(B * Lp, F, N), tn_workspace_bytes((int)ML, N, K));
   void* tnw = ws.take(tnb);
   const size_t gnb = gn_bwd_ws(B, L, N);
   void* gnw = ws.take(gnb);
@@ -1012,7 +989,7 @@ int front_bwd(const float* wav, const float* enc, const float* dout, float* denc
 extern "C" int sepr_fuse_bwd(const float* lo, const float* skip, const float* dy, float* dlo, float* dskip, int n, int T, int F,
                              const sepr_fuse_tw* w, const sepr_fuse_grad* g, void* ws, size_t ws_bytes, sepr_stream_t stream) {
   if (!lo || !skip || !dy || !dlo || !dskip || !w || !g || n <= 0 || T <= 0 || (T & 1) || F <= 0 || F % 32) return SEPR_EINVAL;
-  Carve wk(ws, ws_bytes, false);
+  Arena wk(ws, ws_bytes);
   return fuse_bwd(lo, skip, dy, dlo, dskip, n, T, F, w, g, wk, SEPR_ST);
 }
 extern "C" int sepr_outlayer_decoder_train_fwd(const float* x, int nS, int S, int Tsrc, int L, const int* idx, const float* enc, int F,
@@ -1023,7 +1000,7 @@ extern "C" int sepr_outlayer_decoder_train_fwd(const float* x, int nS, int S, in
   if (K != TRAIN_ENC_K || stride != TRAIN_ENC_STRIDE) return SEPR_EINVAL;   // sepr_train_ctx_bytes / ws_bytes size for this geometry
   if (!idx && L > Tsrc) return SEPR_EINVAL;
   if (idx && (Tsrc > L || !enc)) return SEPR_EINVAL;
-  Carve cx(ctx, ctx_bytes, false);
+  Arena cx(ctx, ctx_bytes);
   return out_fwd(x, nS, S, Tsrc, L, idx, enc, F, N, K, stride, w, wav, cx, SEPR_ST);
 }
 extern "C" int sepr_outlayer_decoder_bwd(const float* x, const float* dwav, float* dx, int dx_accumulate, float* denc, int nS, int S,
@@ -1034,7 +1011,7 @@ extern "C" int sepr_outlayer_decoder_bwd(const float* x, const float* dwav, floa
   if (K != TRAIN_ENC_K || stride != TRAIN_ENC_STRIDE) return SEPR_EINVAL;
   if (!idx && L > Tsrc) return SEPR_EINVAL;
   if (idx && Tsrc > L) return SEPR_EINVAL;
-  Carve cx(const_cast<void*>(ctx), ctx_bytes, false), wk(ws, ws_bytes, false);
+  Arena cx(const_cast<void*>(ctx), ctx_bytes), wk(ws, ws_bytes);
   return out_bwd(x, dwav, dx, dx_accumulate, denc, nS, S, Tsrc, L, idx, idx_start, enc, F, N, K, stride, w, g, cx, wk, SEPR_ST);
 }
 extern "C" int sepr_front_train_fwd(const float* wav, int B, int T, int N, int K, int stride, int F, int Lp, float gn_eps,
@@ -1042,7 +1019,7 @@ extern "C" int sepr_front_train_fwd(const float* wav, int B, int T, int N, int K
                                     size_t ws_bytes, sepr_stream_t stream) {
   if (!wav || !w || !enc || !out || B <= 0 || T < K || stride <= 0 || Lp < (T - K) / stride + 1) return SEPR_EINVAL;
   if (K != TRAIN_ENC_K || stride != TRAIN_ENC_STRIDE) return SEPR_EINVAL;
-  Carve cx(ctx, ctx_bytes, false), wk(ws, ws_bytes, false);
+  Arena cx(ctx, ctx_bytes), wk(ws, ws_bytes);
   return front_fwd(wav, B, T, N, K, stride, F, Lp, gn_eps, w, enc, out, cx, wk, SEPR_ST);
 }
 extern "C" int sepr_front_bwd(const float* wav, const float* enc, const float* dout, float* denc_aux, int B, int T, int N, int K,
@@ -1050,13 +1027,13 @@ extern "C" int sepr_front_bwd(const float* wav, const float* enc, const float* d
                               size_t ctx_bytes, void* ws, size_t ws_bytes, sepr_stream_t stream) {
   if (!wav || !enc || !dout || !w || !g || B <= 0 || T < K || stride <= 0) return SEPR_EINVAL;
   if (K != TRAIN_ENC_K || stride != TRAIN_ENC_STRIDE) return SEPR_EINVAL;
-  Carve cx(const_cast<void*>(ctx), ctx_bytes, false), wk(ws, ws_bytes, false);
+  Arena cx(const_cast<void*>(ctx), ctx_bytes), wk(ws, ws_bytes);
   return front_bwd(wav, enc, dout, denc_aux, B, T, N, K, stride, F, Lp, w, g, cx, wk, SEPR_ST);
 }
 
 // ---- sizing: replay each block's carving in dry mode --------------------------------------------------------------
 static void train_sizes(int op, int n, int T, int Tp, int F, int N, int S, int H, int K, size_t* ctx_b, size_t* ws_b) {
-  Carve cf(nullptr, 0, true), wf(nullptr, 0, true), cb(nullptr, 0, true), wb(nullptr, 0, true);
+  Arena cf = Arena::sizing(), wf = Arena::sizing(), cb = Arena::sizing(), wb = Arena::sizing();
   const float p1 = 0.5f;      // size for the dropout-enabled layout (superset)
   switch (op) {
     case SEPR_TOP_GCFN:
@@ -1103,7 +1080,7 @@ static void train_sizes(int op, int n, int T, int Tp, int F, int N, int S, int H
       for (int aux = 0; aux < 2; ++aux) {
         if (aux && Tp > T) continue;
         if (!aux && T > Tp) continue;
-        Carve c1(nullptr, 0, true), c2(nullptr, 0, true), w2(nullptr, 0, true);
+        Arena c1 = Arena::sizing(), c2 = Arena::sizing(), w2 = Arena::sizing();
         out_fwd(nullptr, n, S, Tp, T, aux ? &dummy_idx : nullptr, nullptr, F, N, TRAIN_ENC_K, TRAIN_ENC_STRIDE, nullptr, nullptr, c1, nullptr);
         out_bwd(nullptr, nullptr, nullptr, 0, nullptr, n, S, Tp, T, aux ? &dummy_idx : nullptr, nullptr, nullptr, F, N, TRAIN_ENC_K, TRAIN_ENC_STRIDE, nullptr,
                 nullptr, c2, w2, nullptr);

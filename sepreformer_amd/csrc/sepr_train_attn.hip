@@ -335,12 +335,17 @@ size_t bwd_shm(int Tp, int DK) {
 }
 }  // namespace
 
+struct RelattnBwdWs {   // dS [NH][Tp][Tp], then the relative-position band partials [ngroups][ntiles][Tp + AT_QT - 1][DK]
+  float *dS, *band;
+  RelattnBwdWs(Arena& a, int n, int Tp, int F, int H) {
+    const long long NH = (long long)n * H;
+    const int ntiles = (Tp + AT_QT - 1) / AT_QT, ngroups = (int)((NH + AT_GROUP - 1) / AT_GROUP);
+    dS = a.f32((size_t)NH * Tp * Tp); band = a.f32((size_t)ngroups * ntiles * (Tp + AT_QT - 1) * (F / H));
+  }
+};
 size_t relattn_train_ws(int n, int Tp, int F, int H) {
   if (n <= 0 || Tp <= 0 || H <= 0) return 0;
-  const int DK = F / H;
-  const long long NH = (long long)n * H;
-  const int ntiles = (Tp + AT_QT - 1) / AT_QT, ngroups = (int)((NH + AT_GROUP - 1) / AT_GROUP);
-  return align_up((size_t)NH * Tp * Tp * sizeof(float)) + align_up((size_t)ngroups * ntiles * (Tp + AT_QT - 1) * DK * sizeof(float));
+  return layout_bytes<RelattnBwdWs>(n, Tp, F, H);
 }
 
 int launch_relattn_train_fwd(const float* QKV, float* O, float* P, int n, int Tp, int F, int H, const float* pe_k, int maxlen, float p,
@@ -380,28 +385,28 @@ int launch_relattn_bwd(const float* QKV, const float* P, const float* O, const f
   const int nslot = Tp + AT_QT - 1;
   const int nown = (nslot * (DK / 4) + AT_THREADS - 1) / AT_THREADS;
   if (nown > 32) return SEPR_EINVAL;
-  if (!ws || ws_bytes < relattn_train_ws(n, Tp, F, H)) return SEPR_EWORKSPACE;
-  float* dS = static_cast<float*>(ws);
-  float* band = reinterpret_cast<float*>(static_cast<char*>(ws) + align_up((size_t)NH * Tp * Tp * sizeof(float)));
+  Arena ar(ws, ws_bytes);
+  const RelattnBwdWs k(ar, n, Tp, F, H);
+  if (!ar.ok_need()) return SEPR_EWORKSPACE;
   const float isd = 1.0f / sqrtf((float)DK);
 #define SEPR_ROWS(DD, NO)                                                                                                         \
   hipLaunchKernelGGL((relattn_bwd_rows_kernel<DD, NO>), dim3(ngroups, ntiles), dim3(AT_THREADS), bwd_shm(Tp, DD), s, QKV, P, O, dO, \
-                     dQKV, dS, band, NH, Tp, F, H, pe_k, maxlen, isd, thr, dscale, seed, offset, drop_salt())
+                     dQKV, k.dS, k.band, NH, Tp, F, H, pe_k, maxlen, isd, thr, dscale, seed, offset, drop_salt())
   if (DK == 16) {
     if (nown <= 8) SEPR_ROWS(16, 8);
     else if (nown <= 16) SEPR_ROWS(16, 16);
     else SEPR_ROWS(16, 32);
-    hipLaunchKernelGGL((relattn_bwd_cols_kernel<16>), dim3(NH, ntiles), dim3(AT_THREADS), 0, s, QKV, P, dS, dO, dQKV, Tp, F, H, thr,
+    hipLaunchKernelGGL((relattn_bwd_cols_kernel<16>), dim3(NH, ntiles), dim3(AT_THREADS), 0, s, QKV, P, k.dS, dO, dQKV, Tp, F, H, thr,
                        dscale, seed, offset, drop_salt());
   } else {
     if (nown <= 8) SEPR_ROWS(32, 8);
     else if (nown <= 16) SEPR_ROWS(32, 16);
     else SEPR_ROWS(32, 32);
-    hipLaunchKernelGGL((relattn_bwd_cols_kernel<32>), dim3(NH, ntiles), dim3(AT_THREADS), 0, s, QKV, P, dS, dO, dQKV, Tp, F, H, thr,
+    hipLaunchKernelGGL((relattn_bwd_cols_kernel<32>), dim3(NH, ntiles), dim3(AT_THREADS), 0, s, QKV, P, k.dS, dO, dQKV, Tp, F, H, thr,
                        dscale, seed, offset, drop_salt());
   }
 #undef SEPR_ROWS
-  hipLaunchKernelGGL(relattn_band_reduce_kernel, dim3((2 * maxlen * DK + 63) / 64), dim3(AT_THREADS), 0, s, band,
+  hipLaunchKernelGGL(relattn_band_reduce_kernel, dim3((2 * maxlen * DK + 63) / 64), dim3(AT_THREADS), 0, s, k.band,
                      ngroups, ntiles, Tp, DK, maxlen, dpe_g);
   SEPR_CHECK_LAUNCH("relattn_bwd kernels");
   return SEPR_OK;

@@ -722,13 +722,16 @@ __global__ __launch_bounds__(256) void relattn_band_reduce2_kernel(const float* 
 }
 }  // namespace
 
+struct RelattnX3BwdWs {   // dS [NH][Tp][Tp], the rows' D = sum dO . O [NH][Tp], the band partials [ngroups][2 Tp - 1][DK]
+  float *dS, *Dbuf, *band;
+  RelattnX3BwdWs(Arena& a, int n, int Tp, int F, int H) {
+    const long long NH = (long long)n * H, ngroups = (NH + AXB_GROUP - 1) / AXB_GROUP;
+    dS = a.f32((size_t)NH * Tp * Tp); Dbuf = a.f32((size_t)NH * Tp); band = a.f32((size_t)ngroups * (2 * Tp - 1) * (F / H));
+  }
+};
 size_t relattn_x3_bwd_ws(int n, int Tp, int F, int H) {
   if (n <= 0 || Tp <= 0 || H <= 0) return 0;
-  const int DK = F / H;
-  const long long NH = (long long)n * H;
-  const long long ngroups = (NH + AXB_GROUP - 1) / AXB_GROUP;
-  return align_up((size_t)NH * Tp * Tp * sizeof(float)) + align_up((size_t)NH * Tp * sizeof(float)) +
-         align_up((size_t)ngroups * (2 * Tp - 1) * DK * sizeof(float));
+  return layout_bytes<RelattnX3BwdWs>(n, Tp, F, H);
 }
 
 int launch_relattn_x3_bwd(const float* QKV, const float* lse, const float* O, const float* dO, float* dQKV, float* dpe_g, int n, int Tp,
@@ -739,16 +742,15 @@ int launch_relattn_x3_bwd(const float* QKV, const float* lse, const float* O, co
     return SEPR_EINVAL;
   const int DK = F / H;
   if (DK != 16 && DK != 32) return SEPR_EINVAL;
-  if (!ws || ws_bytes < relattn_x3_bwd_ws(n, Tp, F, H)) return SEPR_EWORKSPACE;
+  Arena ar(ws, ws_bytes);
+  const RelattnX3BwdWs k(ar, n, Tp, F, H);
+  if (!ar.ok_need()) return SEPR_EWORKSPACE;
   const long long NH = (long long)n * H;
   if (NH * Tp >= (1LL << 31)) return SEPR_EINVAL;              // dropout row ids are 32-bit
   const int ngroups = (int)((NH + AXB_GROUP - 1) / AXB_GROUP);
-  char* wp = static_cast<char*>(ws);
   AxArgs a;
   a.QKV = QKV; a.O = O; a.dO = dO; a.lse = lse; a.dQKV = dQKV;
-  a.dS = reinterpret_cast<float*>(wp);
-  a.Dbuf = reinterpret_cast<float*>(wp + align_up((size_t)NH * Tp * Tp * sizeof(float)));
-  float* band = reinterpret_cast<float*>(wp + align_up((size_t)NH * Tp * Tp * sizeof(float)) + align_up((size_t)NH * Tp * sizeof(float)));
+  a.dS = k.dS; a.Dbuf = k.Dbuf;
   a.pe = pe_k; a.Tp = Tp; a.F = F; a.H = H; a.maxlen = maxlen;
   a.isd = 1.0f / sqrtf((float)DK);
   a.thr = p > 0.f ? sepr_drop_thr16(p) : 0u;
@@ -766,8 +768,8 @@ int launch_relattn_x3_bwd(const float* QKV, const float* lse, const float* O, co
       hipLaunchKernelGGL((relattn_bwd_q_x3_kernel<16, false>), grid, dim3(256), 0, s, a);
       hipLaunchKernelGGL((relattn_bwd_kv_x3_kernel<16, false>), grid, dim3(256), 0, s, a);
     }
-    if (a.ds16) hipLaunchKernelGGL((relattn_band_kernel<16, true>), bgrid, dim3(256), 0, s, QKV, a.dS, band, (int)NH, Tp, F, H);
-    else hipLaunchKernelGGL((relattn_band_kernel<16, false>), bgrid, dim3(256), 0, s, QKV, a.dS, band, (int)NH, Tp, F, H);
+    if (a.ds16) hipLaunchKernelGGL((relattn_band_kernel<16, true>), bgrid, dim3(256), 0, s, QKV, a.dS, k.band, (int)NH, Tp, F, H);
+    else hipLaunchKernelGGL((relattn_band_kernel<16, false>), bgrid, dim3(256), 0, s, QKV, a.dS, k.band, (int)NH, Tp, F, H);
   } else {
     if (a.one) {
       hipLaunchKernelGGL((relattn_bwd_q_x3_kernel<32, true>), grid, dim3(256), 0, s, a);
@@ -776,10 +778,10 @@ int launch_relattn_x3_bwd(const float* QKV, const float* lse, const float* O, co
       hipLaunchKernelGGL((relattn_bwd_q_x3_kernel<32, false>), grid, dim3(256), 0, s, a);
       hipLaunchKernelGGL((relattn_bwd_kv_x3_kernel<32, false>), grid, dim3(256), 0, s, a);
     }
-    if (a.ds16) hipLaunchKernelGGL((relattn_band_kernel<32, true>), bgrid, dim3(256), 0, s, QKV, a.dS, band, (int)NH, Tp, F, H);
-    else hipLaunchKernelGGL((relattn_band_kernel<32, false>), bgrid, dim3(256), 0, s, QKV, a.dS, band, (int)NH, Tp, F, H);
+    if (a.ds16) hipLaunchKernelGGL((relattn_band_kernel<32, true>), bgrid, dim3(256), 0, s, QKV, a.dS, k.band, (int)NH, Tp, F, H);
+    else hipLaunchKernelGGL((relattn_band_kernel<32, false>), bgrid, dim3(256), 0, s, QKV, a.dS, k.band, (int)NH, Tp, F, H);
   }
-  hipLaunchKernelGGL(relattn_band_reduce2_kernel, dim3((2 * maxlen * DK + 255) / 256), dim3(256), 0, s, band, ngroups, Tp, DK, maxlen, dpe_g);
+  hipLaunchKernelGGL(relattn_band_reduce2_kernel, dim3((2 * maxlen * DK + 255) / 256), dim3(256), 0, s, k.band, ngroups, Tp, DK, maxlen, dpe_g);
   SEPR_CHECK_LAUNCH("relattn_x3 backward kernels");
   return SEPR_OK;
 }

@@ -270,10 +270,13 @@ __global__ __launch_bounds__(TPB) void gcfn_mid_reduce_kernel(const float* __res
 }
 }  // namespace
 
-size_t gcfn_mid_bwd_ws(int n, int T, int C) {
-  const int nchunk = (T + GM_TC - 1) / GM_TC;
-  return align_up((size_t)n * nchunk * C * 8 * sizeof(float)) + align_up((size_t)PR_GROUPS * C * 8 * sizeof(float));
-}
+// workspace of the three depthwise weight-gradient launchers: the blocks' partial rows [rows][width], then the scratch of prereduce()
+struct PartWs {
+  float *part, *scratch;
+  PartWs(Arena& a, size_t rows, size_t width) { part = a.f32(rows * width); scratch = a.f32((size_t)PR_GROUPS * width); }
+};
+struct GcfnMidWs : PartWs { GcfnMidWs(Arena& a, int n, int T, int C) : PartWs(a, (size_t)n * ((T + GM_TC - 1) / GM_TC), (size_t)C * 8) {} };
+size_t gcfn_mid_bwd_ws(int n, int T, int C) { return layout_bytes<GcfnMidWs>(n, T, C); }
 // reduction of [nblk][C][8] depthwise partials (the fused backward's tiles, sepr_gcfn_bwd_fused.hip) into the parameter gradients
 size_t gcfn_mid_reduce_ws(int C) { return align_up((size_t)PR_GROUPS * C * 8 * sizeof(float)); }
 int launch_gcfn_mid_reduce(const float* part, int nblk, int C, float* dw_g, float* db_g, float* scratch, hipStream_t s) {
@@ -290,14 +293,14 @@ int launch_gcfn_mid_bwd(const float* h1, const float* dg, float* dh1, int n, int
                         hipStream_t s) {
   if (n <= 0 || T <= 0) return SEPR_OK;
   if (!h1 || !dg || !dh1 || !dw_w || !dw_b || !dw_g || !db_g || C <= 0) return SEPR_EINVAL;
-  if (!ws || ws_bytes < gcfn_mid_bwd_ws(n, T, C)) return SEPR_EWORKSPACE;
+  Arena ar(ws, ws_bytes);
+  const GcfnMidWs k(ar, n, T, C);
+  if (!ar.ok_need()) return SEPR_EWORKSPACE;
   const int nchunk = (T + GM_TC - 1) / GM_TC;
-  float* part = static_cast<float*>(ws);
   hipLaunchKernelGGL(gcfn_mid_bwd_kernel, dim3(n * nchunk, (C + TPB - 1) / TPB), dim3(TPB), 0, s, h1, dg, dh1, T, C, nchunk, dw_w,
-                     dw_b, part, p > 0.f ? sepr_drop_threshold(p) : 0u, p > 0.f ? 1.0f / (1.0f - p) : 1.0f, seed, offset, drop_salt());
-  float* scratch = reinterpret_cast<float*>(static_cast<char*>(ws) + align_up((size_t)n * nchunk * C * 8 * sizeof(float)));
+                     dw_b, k.part, p > 0.f ? sepr_drop_threshold(p) : 0u, p > 0.f ? 1.0f / (1.0f - p) : 1.0f, seed, offset, drop_salt());
   const float* rows = nullptr;
-  const int nrows = prereduce(part, n * nchunk, C * 8, scratch, &rows, s);
+  const int nrows = prereduce(k.part, n * nchunk, C * 8, k.scratch, &rows, s);
   hipLaunchKernelGGL(gcfn_mid_reduce_kernel, dim3((C * 8 + TPB - 1) / TPB), dim3(TPB), 0, s, rows, nrows, C, dw_g, db_g);
   SEPR_CHECK_LAUNCH("gcfn_mid_bwd_kernel");
   return SEPR_OK;
@@ -426,18 +429,19 @@ __global__ __launch_bounds__(TPB) void dwconv_wgrad_reduce_kernel(const float* _
 }
 }  // namespace
 
-size_t dwconv_wgrad_ws(int n, int T, int C, int K) {
-  const int nchunk = (T + WG_TC - 1) / WG_TC;
-  return align_up((size_t)n * nchunk * (K + 1) * C * sizeof(float)) + align_up((size_t)PR_GROUPS * (K + 1) * C * sizeof(float));
-}
+struct DwconvWgradWs : PartWs {
+  DwconvWgradWs(Arena& a, int n, int T, int C, int K) : PartWs(a, (size_t)n * ((T + WG_TC - 1) / WG_TC), (size_t)(K + 1) * C) {}
+};
+size_t dwconv_wgrad_ws(int n, int T, int C, int K) { return layout_bytes<DwconvWgradWs>(n, T, C, K); }
 int launch_dwconv_wgrad(const float* x, const float* dy, int n, int T, int C, int K, float* dw_g, float* db_g, void* ws,
                         size_t ws_bytes, hipStream_t s) {
   if (n <= 0 || T <= 0) return SEPR_OK;
   if (!x || !dy || !dw_g || !db_g || C <= 0 || (C % 4) || K <= 0 || (K & 1) == 0 || K > WG_KMAX) return SEPR_EINVAL;
-  if (!ws || ws_bytes < dwconv_wgrad_ws(n, T, C, K)) return SEPR_EWORKSPACE;
+  Arena ar(ws, ws_bytes);
+  const DwconvWgradWs k(ar, n, T, C, K);
+  if (!ar.ok_need()) return SEPR_EWORKSPACE;
   const int nchunk = (T + WG_TC - 1) / WG_TC;
   const size_t shm = (size_t)((WG_TC + K - 1 + 16) + WG_TC) * WG_CB * sizeof(float);
-  float* part = static_cast<float*>(ws);
   if (shm > 64 * 1024) {   // K > 113: above the default dynamic-LDS limit
     static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(dwconv_wgrad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
     if (attr != hipSuccess) return SEPR_EINVAL;
@@ -450,10 +454,9 @@ int launch_dwconv_wgrad(const float* x, const float* dy, int n, int T, int C, in
   if (K % 64 < 4 && K / 64 <= 2)
     while (nc < nc_max && (long long)n * ((nchunk + 2 * nc - 1) / (2 * nc)) * cblk >= 1024) nc *= 2;
   const int ngrp = (nchunk + nc - 1) / nc;
-  hipLaunchKernelGGL(dwconv_wgrad_kernel, dim3(n * ngrp, cblk), dim3(TPB), shm, s, x, dy, T, C, K, nchunk, part, nc, ngrp);
-  float* scratch = reinterpret_cast<float*>(static_cast<char*>(ws) + align_up((size_t)n * nchunk * (K + 1) * C * sizeof(float)));
+  hipLaunchKernelGGL(dwconv_wgrad_kernel, dim3(n * ngrp, cblk), dim3(TPB), shm, s, x, dy, T, C, K, nchunk, k.part, nc, ngrp);
   const float* rows = nullptr;
-  const int nrows = prereduce(part, n * ngrp, (K + 1) * C, scratch, &rows, s);
+  const int nrows = prereduce(k.part, n * ngrp, (K + 1) * C, k.scratch, &rows, s);
   hipLaunchKernelGGL(dwconv_wgrad_reduce_kernel, dim3(((K + 1) * C + TPB - 1) / TPB), dim3(TPB), 0, s, rows, nrows, C, K, dw_g, db_g);
   SEPR_CHECK_LAUNCH("dwconv_wgrad_kernel");
   return SEPR_OK;
@@ -623,20 +626,23 @@ __global__ __launch_bounds__(TPB) void bn_gelu_bwd_apply_kernel(const float* __r
 }
 }  // namespace
 
-size_t colstats_ws(long long M, int C) {
-  const long long nblk = (M + CR_ROWS - 1) / CR_ROWS;
-  return align_up((size_t)nblk * C * 2 * sizeof(double)) + align_up((size_t)2 * C * sizeof(float));
-}
+struct ColstatsWs {   // fp64 partials per 512-row chunk, then the two combined sums of launch_bn_gelu_bwd
+  double* part;
+  float* sums;
+  ColstatsWs(Arena& a, long long M, int C) { part = a.f64((size_t)((M + CR_ROWS - 1) / CR_ROWS) * C * 2); sums = a.f32((size_t)2 * C); }
+};
+size_t colstats_ws(long long M, int C) { return layout_bytes<ColstatsWs>(M, C); }
 int launch_colstats(const float* z, long long M, int C, float eps, float momentum, float* stats, float* run_mean, float* run_var,
                     void* ws, size_t ws_bytes, hipStream_t s) {
   if (M <= 0) return SEPR_EINVAL;
   if (!z || !stats || C <= 0 || C % 4) return SEPR_EINVAL;
-  if (!ws || ws_bytes < colstats_ws(M, C)) return SEPR_EWORKSPACE;
+  Arena ar(ws, ws_bytes);
+  const ColstatsWs k(ar, M, C);
+  if (!ar.ok_need()) return SEPR_EWORKSPACE;
   const int nblk = (int)((M + CR_ROWS - 1) / CR_ROWS);
-  double* part = static_cast<double*>(ws);
   hipLaunchKernelGGL((colred_kernel<0>), dim3(nblk, (C + 63) / 64), dim3(TPB), 0, s, z, (const float*)nullptr, (const float*)nullptr,
-                     (const float*)nullptr, (const float*)nullptr, M, C, part);
-  hipLaunchKernelGGL(colstats_final_kernel, dim3((C + 15) / 16), dim3(TPB), 0, s, part, nblk, M, C, eps, momentum, stats, run_mean,
+                     (const float*)nullptr, (const float*)nullptr, M, C, k.part);
+  hipLaunchKernelGGL(colstats_final_kernel, dim3((C + 15) / 16), dim3(TPB), 0, s, k.part, nblk, M, C, eps, momentum, stats, run_mean,
                      run_var);
   SEPR_CHECK_LAUNCH("colstats kernels");
   return SEPR_OK;
@@ -653,14 +659,14 @@ int launch_bn_gelu_bwd(const float* dy, const float* z, const float* stats, cons
                        float* db_g, long long M, int C, void* ws, size_t ws_bytes, hipStream_t s, int out16) {
   if (M <= 0) return SEPR_OK;
   if (!dy || !z || !stats || !g || !b || !dz || C <= 0 || C % 4) return SEPR_EINVAL;
-  if (!ws || ws_bytes < colstats_ws(M, C)) return SEPR_EWORKSPACE;
+  Arena ar(ws, ws_bytes);
+  const ColstatsWs k(ar, M, C);
+  if (!ar.ok_need()) return SEPR_EWORKSPACE;
   const int nblk = (int)((M + CR_ROWS - 1) / CR_ROWS);
-  double* part = static_cast<double*>(ws);
-  float* sums = reinterpret_cast<float*>(static_cast<char*>(ws) + align_up((size_t)nblk * C * 2 * sizeof(double)));
-  hipLaunchKernelGGL((colred_kernel<1>), dim3(nblk, (C + 63) / 64), dim3(TPB), 0, s, z, dy, stats, g, b, M, C, part);
-  hipLaunchKernelGGL(colred_final2_kernel, dim3((C + 15) / 16), dim3(TPB), 0, s, part, nblk, C, sums, dg_g, db_g);
+  hipLaunchKernelGGL((colred_kernel<1>), dim3(nblk, (C + 63) / 64), dim3(TPB), 0, s, z, dy, stats, g, b, M, C, k.part);
+  hipLaunchKernelGGL(colred_final2_kernel, dim3((C + 15) / 16), dim3(TPB), 0, s, k.part, nblk, C, k.sums, dg_g, db_g);
   if (out16 && static_cast<const void*>(dz) == static_cast<const void*>(dy)) return SEPR_EINVAL;      // a bf16 dz cannot overwrite the fp32 dy in place
-  hipLaunchKernelGGL(bn_gelu_bwd_apply_kernel, dim3(grid_for(M * (C >> 2), TPB, 1 << 16)), dim3(TPB), 0, s, dy, z, stats, g, b, sums, dz,
+  hipLaunchKernelGGL(bn_gelu_bwd_apply_kernel, dim3(grid_for(M * (C >> 2), TPB, 1 << 16)), dim3(TPB), 0, s, dy, z, stats, g, b, k.sums, dz,
                      M, C, out16);
   SEPR_CHECK_LAUNCH("bn_gelu_bwd kernels");
   return SEPR_OK;
@@ -1030,10 +1036,12 @@ __global__ __launch_bounds__(TPB) void gn_bwd_param_kernel(const float* __restri
 }
 }  // namespace
 
-size_t gn_bwd_ws(int n, int T, int F) {
-  const int nchunk = (T + GB_TC - 1) / GB_TC;
-  return align_up((size_t)n * nchunk * 2 * sizeof(double)) + align_up((size_t)n * nchunk * (F / 4) * 8 * sizeof(float));
-}
+struct GnBwdWs {   // per (sequence, chunk): the two fp64 scalar sums, then the per-channel (dgamma, dbeta) partials
+  double* sc_part;
+  float* ch_part;
+  GnBwdWs(Arena& a, size_t rows, int F) { sc_part = a.f64(rows * 2); ch_part = a.f32(rows * (F / 4) * 8); }
+};
+size_t gn_bwd_ws(int n, int T, int F) { return layout_bytes<GnBwdWs>((size_t)n * ((T + GB_TC - 1) / GB_TC), F); }
 int launch_gn_apply_oop(const float* v, const float* stats, const float* g, const float* b, float* y, int n, int T, int F,
                         hipStream_t s) {
   if (n <= 0) return SEPR_OK;
@@ -1048,15 +1056,15 @@ int launch_gn_bwd(const float* dy, const float* v, const float* stats, const flo
   if (n <= 0) return SEPR_OK;
   if (!dy || !v || !stats || !g || !dv || !dg_g || !db_g || F % 4 || F > 4 * TPB || F < 4) return SEPR_EINVAL;
   if (S > 0 && n % S) return SEPR_EINVAL;
-  if (!ws || ws_bytes < gn_bwd_ws(n, T, F)) return SEPR_EWORKSPACE;
+  Arena ar(ws, ws_bytes);
   const int nchunk = (T + GB_TC - 1) / GB_TC;
-  double* sc_part = static_cast<double*>(ws);
-  float* ch_part = reinterpret_cast<float*>(static_cast<char*>(ws) + align_up((size_t)n * nchunk * 2 * sizeof(double)));
-  hipLaunchKernelGGL(gn_bwd_partial_kernel, dim3(nchunk, n), dim3(TPB), 0, s, dy, v, stats, g, T, F, nchunk, sc_part, ch_part);
+  const GnBwdWs k(ar, (size_t)n * nchunk, F);
+  if (!ar.ok_need()) return SEPR_EWORKSPACE;
+  hipLaunchKernelGGL(gn_bwd_partial_kernel, dim3(nchunk, n), dim3(TPB), 0, s, dy, v, stats, g, T, F, nchunk, k.sc_part, k.ch_part);
   const long long total4 = (long long)n * T * F / 4;
-  hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3(grid_for(total4, TPB, 1 << 16)), dim3(TPB), 0, s, dy, v, stats, g, sc_part, nchunk, dv, T, F,
+  hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3(grid_for(total4, TPB, 1 << 16)), dim3(TPB), 0, s, dy, v, stats, g, k.sc_part, nchunk, dv, T, F,
                      S, total4);
-  hipLaunchKernelGGL(gn_bwd_param_kernel, dim3((F + 15) / 16), dim3(TPB), 0, s, ch_part, n * nchunk, F, dg_g, db_g);
+  hipLaunchKernelGGL(gn_bwd_param_kernel, dim3((F + 15) / 16), dim3(TPB), 0, s, k.ch_part, n * nchunk, F, dg_g, db_g);
   SEPR_CHECK_LAUNCH("gn_bwd kernels");
   return SEPR_OK;
 }
@@ -1146,12 +1154,10 @@ __global__ __launch_bounds__(TPB) void downconv_wgrad_reduce_kernel(const float*
 }
 }  // namespace
 
-size_t downconv_bwd_ws(int n, int T, int F, int K) {
-  const int pad = (K - 1) / 2;
-  const int To = (T + 2 * pad - K) / 2 + 1;
-  const int nchunk = (To + DC_TC - 1) / DC_TC;
-  return align_up((size_t)n * nchunk * F * 17 * sizeof(float)) + align_up((size_t)PR_GROUPS * F * 17 * sizeof(float));
-}
+struct DownconvBwdWs : PartWs {   // 17 = the 16 taps a DownConv has at most, and the bias column
+  DownconvBwdWs(Arena& a, int n, int To, int F) : PartWs(a, (size_t)n * ((To + DC_TC - 1) / DC_TC), (size_t)F * 17) {}
+};
+size_t downconv_bwd_ws(int n, int T, int F, int K) { return layout_bytes<DownconvBwdWs>(n, (T + 2 * ((K - 1) / 2) - K) / 2 + 1, F); }
 int launch_downconv_pre(const float* x, float* c, int n, int T, int To, int F, int K, const float* w, const float* b, hipStream_t s) {
   if (n <= 0) return SEPR_OK;
   if (!x || !c || !w || !b || F % 4 || K <= 0) return SEPR_EINVAL;
@@ -1164,15 +1170,15 @@ int launch_downconv_bwd(const float* x, const float* dc, float* dx, int n, int T
                         float* db_g, void* ws, size_t ws_bytes, hipStream_t s) {
   if (n <= 0) return SEPR_OK;
   if (!x || !dc || !dx || !w || !dw_g || !db_g || F % 4 || K <= 0 || K > 16) return SEPR_EINVAL;
-  if (!ws || ws_bytes < downconv_bwd_ws(n, T, F, K)) return SEPR_EWORKSPACE;
+  Arena ar(ws, ws_bytes);
+  const DownconvBwdWs k(ar, n, To, F);
+  if (!ar.ok_need()) return SEPR_EWORKSPACE;
   const long long total4 = (long long)n * T * F / 4;
   hipLaunchKernelGGL(downconv_bwd_dx_kernel, dim3(grid_for(total4, TPB, 1 << 16)), dim3(TPB), 0, s, dc, dx, T, To, F, K, w, total4);
   const int nchunk = (To + DC_TC - 1) / DC_TC;
-  float* part = static_cast<float*>(ws);
-  hipLaunchKernelGGL(downconv_wgrad_kernel, dim3(n * nchunk), dim3(F < TPB ? F : TPB), 0, s, x, dc, T, To, F, K, nchunk, part);
-  float* scratch = reinterpret_cast<float*>(static_cast<char*>(ws) + align_up((size_t)n * nchunk * F * 17 * sizeof(float)));
+  hipLaunchKernelGGL(downconv_wgrad_kernel, dim3(n * nchunk), dim3(F < TPB ? F : TPB), 0, s, x, dc, T, To, F, K, nchunk, k.part);
   const float* rows = nullptr;
-  const int nrows = prereduce(part, n * nchunk, F * 17, scratch, &rows, s);
+  const int nrows = prereduce(k.part, n * nchunk, F * 17, k.scratch, &rows, s);
   hipLaunchKernelGGL(downconv_wgrad_reduce_kernel, dim3((F * 17 + TPB - 1) / TPB), dim3(TPB), 0, s, rows, nrows, F, K, dw_g, db_g);
   SEPR_CHECK_LAUNCH("downconv_bwd kernels");
   return SEPR_OK;
