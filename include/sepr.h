@@ -818,6 +818,32 @@ size_t sepr_adamw_workspace(void);
 int sepr_adamw_step(const sepr_adamw_tables* t, const float* grads, long long grads_numel, float* exp_avg, float* exp_avg_sq,
                     double* step, const float* lr, double beta1, double beta2, double eps, double weight_decay, double max_norm,
                     float* scal, void* ws, size_t ws_bytes, sepr_stream_t stream);
+/* The same step behind a guard, for a loop that looks at the host once per log interval: the norm pass always runs (ws is always
+ * needed; max_norm <= 0 still means no clipping).  A total norm that is not finite sets scal[5] = 1 and skips the step: `step` does
+ * not advance, no parameter or moment is written, and of scal only [0] (the norm) and [5] are written: [1..4] keep the step before's.  Otherwise scal[5] = 0 and the arithmetic is sepr_adamw_step's, bit for bit.
+ * (sepr_adamw_step itself never writes scal[5].) */
+int sepr_adamw_step_guarded(const sepr_adamw_tables* t, const float* grads, long long grads_numel, float* exp_avg, float* exp_avg_sq,
+                            double* step, const float* lr, double beta1, double beta2, double eps, double weight_decay, double max_norm,
+                            float* scal, void* ws, size_t ws_bytes, sepr_stream_t stream);
+
+/* ---- run ledger: what a training loop needs to know about its steps, kept on the device ---------------------------------------
+ * One launch, one thread, plain stores, fixed order: fold one step into `ledger` (float64, zeroed by the caller at the start of
+ * an epoch).  parts: the step's loss scalars as one fp32 device vector (time loss, then one per stage).  opt_scal: the `scal` of the
+ * optimizer step that followed (NULL for validation: the gradient-norm slots then stay as they are).  A skipped step
+ * (opt_scal[5] != 0) adds to SEPR_LEDGER_SKIPPED and to nothing else.  Slots: */
+enum {
+  SEPR_LEDGER_STEPS = 0,      /* steps counted (not skipped) */
+  SEPR_LEDGER_SKIPPED = 1,    /* steps the guarded optimizer skipped */
+  SEPR_LEDGER_NONFINITE = 2,  /* counted steps with a non-finite loss part */
+  SEPR_LEDGER_GNORM_SUM = 3,  /* sum of the total gradient norm before clipping (scal[0]) */
+  SEPR_LEDGER_GNORM_MAX = 4,  /* its maximum */
+  SEPR_LEDGER_CLIPPED = 5,    /* steps with scal[1] < 1 */
+  SEPR_LEDGER_PART_SUM = 6,   /* [nparts] sum of each part; then [nparts] the last counted step's parts */
+  SEPR_LEDGER_MAX_PARTS = 64
+};
+int sepr_run_ledger_doubles(int nparts);      /* SEPR_LEDGER_PART_SUM + 2 nparts; 0 for nparts outside 1..SEPR_LEDGER_MAX_PARTS */
+int sepr_run_ledger_update(const float* parts, int nparts, const float* opt_scal, double* ledger, int ledger_doubles,
+                           sepr_stream_t stream);
 
 /* ---- opt-in kernel timer (bench.py roofline) ------------------------------------------------- */
 /* Sites a projection launch can be attributed to. */

@@ -603,6 +603,55 @@ def pack_table(plan: BatchPlan, speeds: Optional[Sequence[int]] = None) -> np.nd
     return np.concatenate([blocks[name].ravel().astype(np.int32, copy=False) for name in layout])
 
 
+class FeedOrder:
+    """The host-only half of a feed: the ``random.Random`` that permutes the keys and makes the planners' draws, the epoch counter, the
+    shard and the batch boundaries.  It needs no device, and it is what a checkpoint keeps of a feed (``state_dict``): written at an
+    epoch boundary, a fresh object that loads it yields the next epoch's key order and the same planner draws.  (The simulated-rooms
+    bank follows from ``(seed, epoch)``, so the epoch counter covers it.)"""
+
+    def __init__(self, default_keys: Optional[Sequence[str]], batch: int, seed=0, keys: Optional[Sequence[str]] = None,
+                 rank: int = 0, world: int = 1, drop_last: bool = True, fixed_length: bool = False):
+        from .dist import shard_range
+        shard_range(1, rank, world)                     # validates rank / world
+        if batch < 1:
+            raise ValueError("batch >= 1")
+        if fixed_length and not drop_last:
+            raise ValueError("drop_last=False yields a smaller last batch: variable-length mode only (fixed_length rows feed static tensors)")
+        self.batch, self.seed, self.rank, self.world, self.drop_last = int(batch), seed, rank, world, bool(drop_last)
+        self.rng = random.Random(seed)
+        self.epoch = 0
+        self.keys = None if keys is None else list(keys)
+        self.default_keys = None if default_keys is None else list(default_keys)
+        if self.keys is None and self.default_keys is None:
+            raise ValueError("the corpus has no roles (it was not read from scp lists): pass keys=")
+
+    def epoch_order(self) -> List[str]:
+        if self.keys is not None:
+            order = list(self.keys)
+        else:
+            order = list(self.default_keys)
+            self.rng.shuffle(order)
+        from .dist import shard_range
+        lo, hi = shard_range(len(order), self.rank, self.world)
+        return order[lo:hi]
+
+    def batches(self, order: Sequence[str]) -> List[List[str]]:
+        """The epoch's batches of keys: full ones, then - with ``drop_last=False`` - the remainder as a last, smaller one."""
+        full = len(order) - len(order) % self.batch
+        out = [list(order[i:i + self.batch]) for i in range(0, full, self.batch)]
+        if not self.drop_last and full < len(order):
+            out.append(list(order[full:]))
+        return out
+
+    def state_dict(self) -> dict:
+        return {"rng": self.rng.getstate(), "epoch": int(self.epoch), "seed": self.seed}
+
+    def load_state_dict(self, state: dict) -> None:
+        version, words, gauss = state["rng"]
+        self.rng.setstate((int(version), tuple(int(w) for w in words), gauss))      # (a list after a round trip through a file)
+        self.epoch = int(state["epoch"])
+
+
 class DynamicMixFeed:
     """``for input_sizes, mixture, src, key in feed`` - the reference's ``_collate`` tuple (``input_sizes`` float32 on the host,
     ``mixture [B, T]`` and the ``S`` tensors ``src[s] [B, T]`` on the device, the keys), one epoch per iteration.
@@ -614,7 +663,10 @@ class DynamicMixFeed:
     asynchronous copy into the static device table, one launch - all on the current stream, nothing waits for the device.
     ``keys``: the epoch's key order, used as given every epoch; default: the keys of the corpus's first role, permuted with the
     feed's ``random.Random(seed)`` before each epoch (the same generator then makes the examples' draws).  ``rank`` / ``world``:
-    this rank's contiguous shard of the key order (``dist.shard_range``).  A trailing partial batch is dropped.
+    this rank's contiguous shard of the key order (``dist.shard_range``).  A trailing partial batch is dropped; ``drop_last=False``
+    yields it as a last, smaller batch (the reference's validation loader) - variable-length mode only: static tensors have one
+    shape, so with ``fixed_length`` it is refused.  ``state_dict()`` / ``load_state_dict()``: the generator's state and the epoch
+    counter (``FeedOrder``, which holds the feed's host-only state), for a checkpoint written between epochs.
     ``fixed_length``: every row is ``max_len`` samples, shorter examples zero-padded - constant shapes, which a
     ``CapturedTrainStep`` needs; ``next_into(x, targets)`` then writes the next batch straight into the step's static tensors.
     ``rooms`` (a ``reverb.RoomSampler``, with ``rirs=RirBank.simulate(...)``): every ``rooms_every``-th epoch, the first included, begins by
@@ -625,7 +677,8 @@ class DynamicMixFeed:
 
     def __init__(self, corpus: Corpus, planner: Callable[..., Example], batch: int, max_len: int, seed: int = 0,
                  keys: Optional[Sequence[str]] = None, fixed_length: bool = False, rank: int = 0, world: int = 1,
-                 rirs: Optional[RirBank] = None, rooms=None, rooms_every: int = 1, speed_reverb: Optional[bool] = None):
+                 rirs: Optional[RirBank] = None, rooms=None, rooms_every: int = 1, speed_reverb: Optional[bool] = None,
+                 drop_last: bool = True):
         if corpus.device is None:
             raise RuntimeError("DynamicMixFeed needs a corpus on the HIP device (there is no CPU path)")
         if rirs is not None and not _same_device(rirs.device, corpus.device):
@@ -634,8 +687,8 @@ class DynamicMixFeed:
             raise ValueError("batch >= 1 and max_len >= 4")
         if fixed_length and max_len % 4:
             raise ValueError("fixed_length needs max_len to be a multiple of 4")
-        from .dist import shard_range
-        shard_range(1, rank, world)                     # validates rank / world
+        self.order = FeedOrder(list(next(iter(corpus.roles.values()))) if corpus.roles else None, batch, seed, keys, rank, world, drop_last,
+                               fixed_length=fixed_length)     # (refuses drop_last=False with fixed_length)
         self.corpus, self.planner, self.batch, self.max_len = corpus, planner, int(batch), int(max_len)
         self.fixed_length, self.rank, self.world, self.rirs = bool(fixed_length), rank, world, rirs
         if rooms is not None:
@@ -645,15 +698,10 @@ class DynamicMixFeed:
                 raise ValueError("rooms_every >= 1")
             if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or int(seed) < 0:
                 raise ValueError("rooms= needs a non-negative integer seed (the rooms of an epoch are drawn from (seed, epoch))")
-        self.rooms, self.rooms_every, self.seed, self.epoch = rooms, int(rooms_every), seed, 0
+        self.rooms, self.rooms_every, self.seed = rooms, int(rooms_every), seed
         if speed_reverb is None:                        # the flag the user bound on the planner
             speed_reverb = (getattr(planner, "keywords", None) or {}).get("speed_reverb", False)
         self.speed_reverb = bool(speed_reverb)
-        self.rng = random.Random(seed)
-        self.keys = None if keys is None else list(keys)
-        self._default_keys = list(next(iter(corpus.roles.values()))) if corpus.roles else None
-        if self.keys is None and self._default_keys is None:
-            raise ValueError("the corpus has no roles (it was not read from scp lists): pass keys=")
         self._table = None
         self._speeds: List[int] = []                    # the converter set: every speed a plan has used, in order of first use
         self._stage: List[torch.Tensor] = []
@@ -663,15 +711,20 @@ class DynamicMixFeed:
         self.last_plan: Optional[BatchPlan] = None
 
     # ---- host side ---------------------------------------------------------------------------------------------------------
+    rng = property(lambda self: self.order.rng)
+    keys = property(lambda self: self.order.keys)
+    epoch = property(lambda self: self.order.epoch, lambda self, v: setattr(self.order, "epoch", int(v)))
+
     def epoch_order(self) -> List[str]:
-        if self.keys is not None:
-            order = list(self.keys)
-        else:
-            order = list(self._default_keys)
-            self.rng.shuffle(order)
-        from .dist import shard_range
-        lo, hi = shard_range(len(order), self.rank, self.world)
-        return order[lo:hi]
+        return self.order.epoch_order()
+
+    def state_dict(self) -> dict:
+        """What a checkpoint written between epochs keeps of the feed (``FeedOrder.state_dict``)."""
+        return self.order.state_dict()
+
+    def load_state_dict(self, state: dict) -> None:
+        self.order.load_state_dict(state)
+        self._epoch = None                              # a batch iterator in flight belonged to the state that was replaced
 
     def _begin_epoch(self) -> None:
         """With ``rooms=``: before the first plan of every ``rooms_every``-th epoch the bank is re-simulated in place from
@@ -685,9 +738,8 @@ class DynamicMixFeed:
         """The batch plans of one epoch (host only - except with ``rooms=``, where the epoch begins by simulating its rooms on the device)."""
         self._begin_epoch()
         order = self.epoch_order()
-        for i in range(0, len(order) - self.batch + 1, self.batch):
-            yield collate_plan(self.corpus, [self.planner(self.corpus, self.rng, k, self.max_len) for k in order[i:i + self.batch]], self.rirs,
-                               self.speed_reverb)
+        for keys in self.order.batches(order):
+            yield collate_plan(self.corpus, [self.planner(self.corpus, self.rng, k, self.max_len) for k in keys], self.rirs, self.speed_reverb)
 
     # ---- device side -------------------------------------------------------------------------------------------------------
     def _launch(self, plan: BatchPlan, mix=None, src=None):
@@ -726,6 +778,13 @@ class DynamicMixFeed:
                 return plan
             self._epoch = None
         raise ValueError(f"an epoch of this shard holds fewer than {self.batch} keys")
+
+    def write(self, plan: BatchPlan, x: torch.Tensor, targets: Sequence[torch.Tensor]) -> None:
+        """Write the batch of ``plan`` (one of ``plans()``) into ``x`` and ``targets``: what ``next_into`` does with the plan it drew, for a
+        loop that walks exactly one epoch (``trainer.Trainer``)."""
+        if not self.fixed_length:
+            raise ValueError("write needs fixed_length=True (static tensors have one shape)")
+        self._launch(plan, x, list(targets)[:plan.S])
 
     def next_into(self, x: torch.Tensor, targets: Sequence[torch.Tensor]) -> BatchPlan:
         """Write the next batch into ``x [B, max_len]`` and ``targets`` (``S`` tensors ``[B, max_len]``), e.g. ``step.x`` and

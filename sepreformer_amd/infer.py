@@ -238,6 +238,12 @@ def evaluate_utterances_all(model, utterances: Iterable[Tuple[torch.Tensor, Sequ
 test_utterances.__test__ = False      # not a pytest test
 
 
+def load_checkpoint_weights(model, path: str):
+    """The weights of a checkpoint - the reference's, or one ``trainer.Trainer`` wrote (the same five keys) - or of a bare state dict."""
+    ck = torch.load(path, map_location="cpu")
+    return model.load_state_dict(ck.get("model_state_dict", ck), strict=False)      # utils/util_engine.py:43
+
+
 def _main() -> None:
     import argparse
     from .config import VARIANTS
@@ -259,8 +265,7 @@ def _main() -> None:
     out_rate = args.out_rate if args.out_rate in (None, "input") else int(args.out_rate)
     model = Model.from_config(VARIANTS[args.model], init_seed=0)
     if args.checkpoint:
-        ck = torch.load(args.checkpoint, map_location="cpu")
-        model.load_state_dict(ck.get("model_state_dict", ck), strict=False)      # utils/util_engine.py:43
+        load_checkpoint_weights(model, args.checkpoint)
     else:
         model.load_synthetic_(0)
     model = model.eval().to(args.device)

@@ -118,6 +118,16 @@ FrontGrad = _tstruct("FrontGrad", ["w_enc", "gn_g", "gn_b", "proj_w"])
 (TOP_GCFN, TOP_CLA, TOP_EGA, TOP_SPKATTN, TOP_DOWN, TOP_SPLIT, TOP_FUSE, TOP_OUT, TOP_FRONT, TOP_GCFN_FUSED, TOP_EGA_X3,
  TOP_GCFN_FUSED16) = range(12)
 
+# include/sepr.h SEPR_LEDGER_*: the run ledger's slots (the one Python mirror; tests/test_trainer_cpu.py keeps it equal to the header)
+LEDGER_SLOTS = {"steps": 0, "skipped": 1, "nonfinite": 2, "gnorm_sum": 3, "gnorm_max": 4, "clipped": 5, "part_sum": 6}
+LEDGER_MAX_PARTS = 64
+
+
+def ledger_doubles(nparts: int) -> int:
+    """Length of a ledger of ``nparts`` loss parts: the fixed slots, the sum of each part, the last step's parts."""
+    return LEDGER_SLOTS["part_sum"] + 2 * int(nparts)
+
+
 KNOB_X3_WIDE, KNOB_TRAIN_GCFN_PLANES, KNOB_TRAIN_ATTN_ONE, KNOB_TRAIN_CLA16, KNOB_FOLD_HEAD, KNOB_TN16, KNOB_GB_FUSE, KNOB_ATTN_PACK = range(8)
 
 # name -> (restype, argtypes); must list every symbol include/sepr.h declares (tests check this)
@@ -203,6 +213,9 @@ SIGNATURES = {
     "sepr_adamw_block_elems": (_i, []),
     "sepr_adamw_workspace": (_sz, []),
     "sepr_adamw_step": (_i, [C.POINTER(AdamWTables), _fp, _ll, _fp, _fp, _fp, _fp, _d, _d, _d, _d, _d, _fp, _fp, _sz, _fp]),
+    "sepr_adamw_step_guarded": (_i, [C.POINTER(AdamWTables), _fp, _ll, _fp, _fp, _fp, _fp, _d, _d, _d, _d, _d, _fp, _fp, _sz, _fp]),
+    "sepr_run_ledger_doubles": (_i, [_i]),
+    "sepr_run_ledger_update": (_i, [_fp, _i, _fp, _fp, _i, _fp]),
     "sepr_prof_start": (_i, [_i, _i]),
     "sepr_prof_stop": (_i, [C.POINTER(_ll), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "sepr_prof_last_bytes": (C.c_double, []),

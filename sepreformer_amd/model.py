@@ -283,7 +283,12 @@ class Model(torch.nn.Module):
     def _next_dropout_seed(self) -> int:
         """Per-step dropout seed from a PRIVATE CPU generator (the user's global RNG stream - shuffling, augmentation - is
         not consumed, as with the reference's device-side dropout), seeded from ``torch.initial_seed()`` and the
-        data-parallel rank so that replicas under one ``torch.manual_seed`` draw different masks."""
+        data-parallel rank so that replicas under one ``torch.manual_seed`` draw different masks.  An attribute ``dropout_seed_fn`` (a callable
+        returning an int; not set by default) replaces the draw: ``trainer.Trainer`` makes the seed a constant of the run, so that a
+        re-capture after a resume freezes the word the first capture froze."""
+        fn = self.__dict__.get("dropout_seed_fn")
+        if fn is not None:
+            return int(fn())
         gen = self.__dict__.get("_drop_gen")
         if gen is None:
             rank = torch.distributed.get_rank() if (torch.distributed.is_available() and torch.distributed.is_initialized()) else 0

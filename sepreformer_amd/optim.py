@@ -28,7 +28,8 @@ from . import lib as L
 class FlatAdamW(torch.optim.Optimizer):
     fused_clip = True          # train_step.CapturedTrainStep: step(max_norm=...) does the clipping itself
 
-    def __init__(self, model, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2):
+    def __init__(self, model, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
+                 skip_nonfinite: bool = False):
         params = [p for p in model.parameters() if p.requires_grad]
         if not params:
             raise ValueError("no trainable parameters")
@@ -45,6 +46,12 @@ class FlatAdamW(torch.optim.Optimizer):
                 raise ValueError("FlatAdamW: every parameter must be a contiguous, 16-byte aligned fp32 tensor on one device")
         super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, capturable=True))
         self._model, self._dev, self._lib = model, dev, L.load()
+        # skip_nonfinite: sepr_adamw_step_guarded - a non-finite total gradient norm skips the step (scal[5] = 1) instead of poisoning
+        # the weights; with finite gradients the arithmetic is the unguarded entry's, bit for bit
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._entry = self._lib.sepr_adamw_step_guarded if self.skip_nonfinite else self._lib.sepr_adamw_step
+        self._ledger: Optional[torch.Tensor] = None           # attach_ledger: float64 run ledger every step is folded into
+        self._parts: Optional[torch.Tensor] = None
         self._params = params
         blk = self._lib.sepr_adamw_block_elems()
         # moments: 64-element aligned slots, like the gradient buffer
@@ -171,13 +178,40 @@ class FlatAdamW(torch.optim.Optimizer):
                           nblocks=self._nblocks)
         with torch.cuda.device(self._dev):
             st = torch.cuda.current_stream(self._dev).cuda_stream
-            L.check(self._lib.sepr_adamw_step(C.byref(t), flat.data_ptr(), flat.numel(), self._exp_avg.data_ptr(), self._exp_avg_sq.data_ptr(),
-                                              self._step.data_ptr(), self._lr.data_ptr(), float(g["betas"][0]), float(g["betas"][1]),
-                                              float(g["eps"]), float(g["weight_decay"]), float(max_norm) if max_norm else 0.0,
-                                              self._scal.data_ptr(), self._ws.data_ptr(), self._ws.numel(), st), "sepr_adamw_step")
+            L.check(self._entry(C.byref(t), flat.data_ptr(), flat.numel(), self._exp_avg.data_ptr(), self._exp_avg_sq.data_ptr(),
+                                self._step.data_ptr(), self._lr.data_ptr(), float(g["betas"][0]), float(g["betas"][1]),
+                                float(g["eps"]), float(g["weight_decay"]), float(max_norm) if max_norm else 0.0,
+                                self._scal.data_ptr(), self._ws.data_ptr(), self._ws.numel(), st),
+                    "sepr_adamw_step_guarded" if self.skip_nonfinite else "sepr_adamw_step")
+            if self._ledger is not None:
+                # here and nowhere else: an eager step and a captured one (the launch is then part of the optimizer graph) both pass
+                # through this line, so the ledger sees every optimizer step exactly once
+                L.check(self._lib.sepr_run_ledger_update(self._parts.data_ptr(), self._parts.numel(), self._scal.data_ptr(),
+                                                         self._ledger.data_ptr(), self._ledger.numel(), st), "sepr_run_ledger_update")
         return self._scal[0] if max_norm else None
+
+    def attach_ledger(self, ledger: Optional[torch.Tensor], parts: Optional[torch.Tensor] = None) -> None:
+        """From now on every ``step`` ends with one ``sepr_run_ledger_update`` launch that folds ``parts`` (the step's loss scalars, fp32,
+        written by the caller before ``step``) and this optimizer's ``scal`` into ``ledger`` (float64, ``lib.ledger_doubles(len(parts))``
+        long).  A step captured into a graph keeps the two tensors it was captured with.  ``None`` detaches."""
+        if ledger is None:
+            self._ledger = self._parts = None
+            return
+        if parts is None or parts.dtype != torch.float32 or parts.dim() != 1 or not parts.is_contiguous() or parts.device != self._dev:
+            raise ValueError("parts: a contiguous 1-D fp32 tensor on the optimizer's device")
+        if not 1 <= parts.numel() <= L.LEDGER_MAX_PARTS:
+            raise ValueError(f"1 .. {L.LEDGER_MAX_PARTS} loss parts")
+        if ledger.dtype != torch.float64 or not ledger.is_contiguous() or ledger.device != self._dev or ledger.numel() != L.ledger_doubles(parts.numel()):
+            raise ValueError(f"ledger: a contiguous float64 tensor of {L.ledger_doubles(parts.numel())} elements on the optimizer's device")
+        self._ledger, self._parts = ledger, parts
+
+    @property
+    def skipped(self) -> torch.Tensor:
+        """Device scalar: 1 when the last guarded ``step`` was skipped for a non-finite gradient norm, else 0."""
+        return self._scal[5]
 
     @property
     def clip_coef(self) -> torch.Tensor:
-        """Device scalar: the clip coefficient of the last ``step(max_norm=...)``."""
+        """Device scalar: the clip coefficient of the last ``step(max_norm=...)`` that was applied.  A guarded step that was skipped
+        (``skipped`` = 1) writes the norm and the skip flag only: this scalar then still holds the step before's."""
         return self._scal[1]

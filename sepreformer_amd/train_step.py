@@ -31,7 +31,8 @@ CAPTURE_MODE = "thread_local"
 
 class CapturedTrainStep:
     def __init__(self, model, loss_fn: Callable, optimizer: torch.optim.Optimizer, example_x: torch.Tensor,
-                 example_targets: Sequence[torch.Tensor], max_norm: Optional[float] = None, warmup: int = 2):
+                 example_targets: Sequence[torch.Tensor], max_norm: Optional[float] = None, warmup: int = 2,
+                 salt_fn: Optional[Callable[[], int]] = None):
         if example_x.device.type != "cuda":
             raise RuntimeError("CapturedTrainStep needs the HIP device (no CPU path exists)")
         if not all(bool(g.get("capturable", False)) for g in optimizer.param_groups):
@@ -40,6 +41,9 @@ class CapturedTrainStep:
             raise ValueError("at least one eager warm-up step is needed (optimizer state, workspaces)")
         dev = example_x.device
         self.model, self.loss_fn, self.opt, self.max_norm = model, loss_fn, optimizer, max_norm
+        # salt_fn() -> the salt of the step about to run, in place of the model's stateful seed stream (trainer.Trainer: a hash of
+        # (run seed, global step), so a resumed run draws the masks the uninterrupted one draws); None = the stream
+        self.salt_fn = salt_fn
         self.params = [p for g in optimizer.param_groups for p in g["params"] if p.requires_grad]
         self.x = example_x.detach().clone()
         self.targets = [t.detach().clone() for t in example_targets]
@@ -118,7 +122,8 @@ class CapturedTrainStep:
 
     def _refresh_salt(self):
         if self.model.dropout_p > 0.0:
-            self.salt.fill_(self.model._next_dropout_seed() & 0x7FFFFFFFFFFFFFFF)
+            word = self.salt_fn() if self.salt_fn is not None else self.model._next_dropout_seed()
+            self.salt.fill_(int(word) & 0x7FFFFFFFFFFFFFFF)
 
     def __call__(self, x: torch.Tensor, targets: Sequence[torch.Tensor]):
         if x.shape != self.x.shape or len(targets) != len(self.targets):

@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Train a DM variant on real wav files at the captured step's rate: corpus on the device, dynamic mixing in one launch per batch
-(sepreformer_amd/datafeed.py), ``CapturedTrainStep`` + ``FlatAdamW``, the reference's 0.6 / 0.4 loss.  Prints the
-loss and utt/s every ``--log`` steps.  Schedulers, checkpoints and validation are not part of it.
+(sepreformer_amd/datafeed.py), ``CapturedTrainStep`` + ``FlatAdamW``, the reference's loss.  Two modes:
+``--steps N`` runs N steps at the fixed 0.6 / 0.4 mix and prints the loss and utt/s every ``--log`` steps - a rate check, the weights
+are not kept.  ``--epochs N`` runs the reference's training run (``sepreformer_amd/trainer.py``): epochs up to
+N - 1 (the reference's ``max_epoch``), each followed by a validation pass over ``--valid-scp``, the warm-up and plateau schedules,
+one checkpoint per epoch in ``--checkpoint-dir``, and ``--resume`` to continue from the latest one.
 
     python tools/train_from_scp.py --form wsj0 --scp s1=tr_s1.scp s2=tr_s2.scp --steps 200
     python tools/train_from_scp.py --form whamr --scp s1=.. s2=.. s1_reverb=.. s2_reverb=.. noise=.. --model SepReformer_Large_DM_WHAMR
@@ -10,6 +13,7 @@ loss and utt/s every ``--log`` steps.  Schedulers, checkpoints and validation ar
     python tools/train_from_scp.py --form whamr --scp s1=.. s2=.. noise=.. --synthetic-rirs 64:0.2:0.8
     python tools/train_from_scp.py --form whamr --scp s1=.. s2=.. noise=.. --room-rirs 64:0.2:0.6     # simulated rooms, redrawn per epoch (section 5e-4)
     python tools/train_from_scp.py --form whamr --scp s1=.. s2=.. noise=.. --room-rirs 64:0.2:0.6 --speeds 95:105      # each source perturbed, then reverberated (section 5e-5)
+    python tools/train_from_scp.py --form wsj0 --scp s1=tr_s1.scp s2=tr_s2.scp --epochs 200 --valid-scp mix=cv_mix.scp s1=cv_s1.scp s2=cv_s2.scp --checkpoint-dir ck [--resume]
 """
 import argparse
 import os
@@ -45,11 +49,26 @@ def main():
     ap.add_argument("--reverb-target", choices=["direct", "dry", "full"], default="direct", help="the targets under reverberation: the direct "
                     "path of the same impulse response (default), the dry source, or the whole response")
     ap.add_argument("--steps", type=int, default=100)
-    ap.add_argument("--log", type=int, default=10)
+    ap.add_argument("--epochs", type=int, default=None, metavar="N", help="run the epoch loop instead of --steps: the reference's max_epoch "
+                    "(epochs 1 .. N - 1); needs --valid-scp and --checkpoint-dir")
+    ap.add_argument("--valid-scp", nargs="+", default=None, metavar="ROLE=FILE", help="validation lists: roles mix s1 s2 (fixed mixtures, as the reference validates)")
+    ap.add_argument("--test-scp", nargs="+", default=None, metavar="ROLE=FILE", help="test lists (roles mix s1 s2) for the test loop at the reference's test epochs")
+    ap.add_argument("--checkpoint-dir", default=None, help="directory of epoch.NNNN.pth files")
+    ap.add_argument("--resume", action="store_true", help="continue from the latest checkpoint of --checkpoint-dir (without it a non-empty directory is an error)")
+    ap.add_argument("--warmup-steps", type=int, default=1000)
+    ap.add_argument("--start-scheduling", type=int, default=50)
+    ap.add_argument("--test-epochs", type=int, nargs="*", default=[100, 120, 150, 170], help="epochs after which the test loop runs over --test-scp")
+    ap.add_argument("--save", choices=["all", "best"], default="all")
+    ap.add_argument("--keep-last", type=int, default=None, help="keep only the N newest checkpoints")
+    ap.add_argument("--valid-batch", type=int, default=None, help="validation batch (default: --batch)")
+    ap.add_argument("--log", type=int, default=None, help="log interval in steps (default: 10 with --steps; with --epochs the Trainer's own, 50 - each "
+                    "log line there is one ledger read-back, a host synchronisation)")
     ap.add_argument("--lr", type=float, default=1.0e-4)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args()
+    if args.epochs is not None and (not args.valid_scp or not args.checkpoint_dir):
+        ap.error("--epochs needs --valid-scp and --checkpoint-dir")
     if args.speeds and args.form == "direct":
         ap.error("--speeds needs dynamic mixing (--form wsj0, wham or whamr)")
     reverb = args.rir_scp or args.synthetic_rirs or args.room_rirs
@@ -104,6 +123,8 @@ def main():
 
     cfg = VARIANTS[args.model]
     model = Model.from_config(cfg, init_seed=args.seed, precision=args.precision).to(dev).train()
+    if args.epochs is not None:
+        return run_epochs(args, df, model, feed, dev)
     crit_t = PIT_SISNR_time(dev, cfg.num_spks, True)
     crit_m = PIT_SISNR_mag(dev, 512, 128, "hann", cfg.num_stages, cfg.num_spks, True, False)
     sizes = torch.full((args.batch,), args.max_len)                           # fixed-length rows: the padding is part of the example
@@ -121,15 +142,42 @@ def main():
     step = CapturedTrainStep(model, loss_fn, opt, x, targets, max_norm=5.0)
     torch.cuda.synchronize()
     t0, done = time.perf_counter(), 0
+    log_every = args.log or 10
     for i in range(1, args.steps + 1):
         feed.next_into(step.x, step.targets)
         loss, gn = step(step.x, step.targets)
-        if i % args.log == 0 or i == args.steps:
+        if i % log_every == 0 or i == args.steps:
             val = float(loss.detach())                                        # synchronises: once per log interval
             dt = time.perf_counter() - t0
             print(f"step {i}: loss {val:.4f}  grad norm {float(gn):.3f}  {args.batch * (i - done) / dt:.1f} utt/s", flush=True)
             t0, done = time.perf_counter(), i
     step.release()
+
+
+def run_epochs(args, df, model, feed, dev):
+    """--epochs: the reference's run (sepreformer_amd.trainer.Trainer) on the training feed built above."""
+    from sepreformer_amd.trainer import Trainer, latest_checkpoint
+    if latest_checkpoint(args.checkpoint_dir) is not None and not args.resume:
+        sys.exit(f"{args.checkpoint_dir} holds checkpoints: pass --resume to continue from the latest, or another --checkpoint-dir")
+    vcorpus = df.Corpus.from_scp(dict(a.split("=", 1) for a in args.valid_scp), fs=args.fs, device=dev, resample=args.resample)
+    vkeys = vcorpus.roles["mix"]
+    valid = df.DynamicMixFeed(vcorpus, df.plan_direct, batch=args.valid_batch or args.batch, max_len=args.max_len, seed=args.seed, keys=vkeys,
+                              drop_last=False)
+    test = None
+    if args.test_scp:
+        import torch
+        from sepreformer_amd.infer import load_audio
+        tables = {role: df.parse_scp(path) for role, path in (a.split("=", 1) for a in args.test_scp)}
+        srcs = sorted(r for r in tables if r != "mix")
+
+        def test():                                                           # (mixture [1, T], [source_s [1, T]], key), one file at a time
+            for key, path in tables["mix"].items():
+                yield (torch.from_numpy(load_audio(path)[0])[None].to(dev), [torch.from_numpy(load_audio(tables[r][key])[0])[None].to(dev) for r in srcs],
+                       key)
+    trainer = Trainer(model, feed, valid, args.checkpoint_dir, lr=args.lr, seed=args.seed, max_epoch=args.epochs, warmup_steps=args.warmup_steps,
+                      start_scheduling=args.start_scheduling, test_epochs=args.test_epochs, save=args.save, keep_last=args.keep_last,
+                      test_utterances=test, log=lambda s: print(s, flush=True), **({} if args.log is None else {"log_every": args.log}))
+    trainer.run()
 
 
 if __name__ == "__main__":
