@@ -400,6 +400,38 @@ size_t sepr_stitch_workspace(int R, int total_chunks, int S);
 int sepr_stitch_fwd(const float* chunks, const int* chunk_offset, const int* lengths, int R, int S, int W, int O, int match_gain,
                     float* y, int* perm, float* gain, void* ws, size_t ws_bytes, sepr_stream_t stream);
 
+/* The stream bank: the stitch above, one boundary per call, for recordings whose length is known only at their end.
+ * A stream's window k covers [kH, kH + W).  Its state lives in a slot of `state`: the raw last O samples of its latest window (all S
+ * sources, un-permuted), P and g - g in float64, so that the gains equal sepr_stitch_fwd's bit for bit at every boundary.
+ * sepr_streambank_step advances the A >= 1 streams of one hop in ONE launch (one workgroup per stream, which does everything for it in
+ * order).  win: HOST array of S device pointers; win[s] holds source s of the hop's windows as [A][ld] rows (ld >= W, a multiple of 4;
+ * 16-byte aligned), row a belonging to table row a - the separator's outputs are read where the forward left them.
+ * table: DEVICE int64 [A][6] = slot, k, n_emit, has_window, out offset, track stride (the last two in elements).  For a row with a window:
+ *   k = 0: P = identity, g = 1.  k > 0: C, Ea, Eb over the saved tail and the window's first O samples with sepr_stitch_fwd's arithmetic and
+ *   order (shared code), its pi and ratio rules, then g(s) = g(s) * ratio[P(s)], P(s) = pi(P(s)).
+ *   Emit n_emit samples of every track s at out + offset + s * stride: sample j < O of a window k > 0 is
+ *   fmaf(w * g_k, c_k[P_k(s)][j], ((1.0f - w) * g_{k-1}) * tail[P_{k-1}(s)][j]) with sepr_stitch_fwd's w, any other j is g_k * c_k[P_k(s)][j]
+ *   (gains rounded to float32).  n_emit = H for a window that is not its stream's last, T - kH in (O, W] for the last.
+ *   Save the window's last O samples, P and g.
+ * A row without a window is the flush form, used when a stream ends on a full window: it emits g(s) * tail[P(s)][j] for j < n_emit <= O and
+ * leaves the state as it is.  Zeros are written for n_emit <= j < roundup4(n_emit) and nothing beyond; offset and stride are multiples of 4.
+ * perm [A][S] int32 and gain [A][S] float32 receive P and g of every row as the step leaves them.  The kernel clamps slot into [0, slots),
+ * n_emit into [0, W] ([0, O] for a flush) and a stored P into [0, S), and emits nothing for a row whose offset / stride are negative,
+ * misaligned or reach past out_elems: a bad table gives wrong samples, never an access outside the state, the windows or `out`.  Two rows of
+ * one launch must not name the same slot.  No workspace, no atomics, no host synchronisation (capturable); bit-identical from run to run.
+ * SEPR_EINVAL before any HIP call for null pointers (win[s] included), S outside 2..3, A < 1, slots < 1, W or O not multiples of 4, O <= 0,
+ * 2 O > W, ld < W or not a multiple of 4, out_elems < 4, misaligned buffers; SEPR_EWORKSPACE for a state shorter than
+ * sepr_streambank_state_bytes(slots, S, O) (0 for unsupported arguments).
+ * sepr_streambank_gather forms the [A][W] input of a hop in one launch: x[a][j] = sample start + j of the stream whose ring of `cap` samples
+ * begins at store + base (sample t lies at index t mod cap), zero for start + j >= received.  table: DEVICE int64 [A][3] = base, start,
+ * received; cap a multiple of 4 with cap >= W; base and start multiples of 4.  A row whose ring does not lie inside store_elems gives zeros.
+ * New entries, no struct change: ABI 4.13. */
+long long sepr_streambank_state_bytes(int slots, int S, int O);   /* (long long: the size_t entries are the workspace sizes) */
+int sepr_streambank_step(const float* const* win, long long ld, const long long* table, int A, int slots, int S, int W, int O, int match_gain,
+                         float* out, long long out_elems, int* perm, float* gain, void* state, size_t state_bytes, sepr_stream_t stream);
+int sepr_streambank_gather(const float* store, long long store_elems, long long cap, const long long* table, int A, int W, float* x,
+                           sepr_stream_t stream);
+
 /* Sample-rate conversion of whole recordings (the reference resamples on the host inside librosa.load(path, sr=fs),
  * engine.py:155).  Rational ratio fs_out / fs_in = L / M (coprime), K taps per output phase (K even), Hh = (K - 2) / 2:
  *   y[n] = sum_{j < K} tap[(n M) mod L][j] * x[floor(n M / L) - Hh + j],  x zero outside [0, T),  0 <= n < N = ceil(T L / M).

@@ -12,7 +12,9 @@ Mirrors ``models/SepReformer_Base_WSJ0/engine.py``:
 * ``evaluate_utterances_all`` - beyond the reference: the same loop with STOI and ESTOI of the estimates beside SI-SNRi and SDRi
   (``criterion.stoi``, DESIGN.md section 5f);
 * ``separate_long`` / ``separate_long_file`` - beyond the reference: recordings of any length by overlapping windows of the
-  training length, batched through the separator and stitched on the device (``longform.py``).
+  training length, batched through the separator and stitched on the device (``longform.py``, DESIGN.md section 5c);
+* ``separate_many_files`` - several files through the stream bank, whose forwards carry one window of every file in flight
+  (``streambank.py``).
 
 Host-side logic only; every waveform sample is computed by the HIP separator (``Model.forward``) and the HIP
 criterion kernels.  File I/O uses scipy (the reference uses librosa / soundfile, absent here): PCM16/PCM32/float
@@ -147,6 +149,19 @@ def separate_long_file(model, path: str, fs: int = 8000, out_prefix: Optional[st
     return _write_outputs(model, out_prefix if out_prefix is not None else path[:-4], file_mix, sr, mix, est, fs, out_rate)
 
 
+def separate_many_files(model, paths: Sequence[str], fs: int = 8000, slots: int = 32, chunk_seconds: float = 4.0,
+                        overlap_seconds: float = 1.0, match_gain: bool = False, resample: bool = False,
+                        out_rate: Union[None, int, str] = None) -> List[Tuple[np.ndarray, List[str]]]:
+    """``separate_long_file`` for several files at once through ``streambank.separate_many``: per file, the raw estimates and the
+    files written (the same names, the same 0.9 peak normalisation, the same ``resample`` / ``out_rate`` options)."""
+    from .streambank import separate_many
+    loaded = [_load_mixture(model, p, fs, resample) for p in paths]
+    ests = separate_many(model, [mix for _, mix, _ in loaded], slots=slots, chunk_seconds=chunk_seconds,
+                         overlap_seconds=overlap_seconds, fs=fs, match_gain=match_gain)
+    return [_write_outputs(model, p[:-4], file_mix, sr, mix, est, fs, out_rate)
+            for p, (file_mix, mix, sr), est in zip(paths, loaded, ests)]
+
+
 def _test_loop(model, utterances, sisnr_csv_path, sdr_csv_path, wav_dir, fs, with_sdr, stoi_csv_paths=None, stoi_out=None):
     """``Engine._test`` (engine.py:113-149): one utterance per step; PIT_SISNRi (eps 1e-15) and, when ``with_sdr``,
     PIT_SDRi; one csv row per utterance and criterion; running means divided by ``num_spks``; optional wav dumps.
@@ -248,14 +263,19 @@ def _main() -> None:
     import argparse
     from .config import VARIANTS
     from .model import Model
-    ap = argparse.ArgumentParser(description="separate one wav file (reference: run.py --engine-mode infer_sample)")
-    ap.add_argument("wav")
+    ap = argparse.ArgumentParser(description="separate one wav file (reference: run.py --engine-mode infer_sample), or several "
+                                             "through the stream bank")
+    ap.add_argument("wav", nargs="+")
     ap.add_argument("--model", default="SepReformer_Base_WSJ0", choices=sorted(VARIANTS))
     ap.add_argument("--checkpoint", default=None, help="reference checkpoint (.pth with model_state_dict); default: synthetic weights")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--chunk-seconds", type=float, default=None,
                     help="long-form mode: overlapping windows of this length, stitched on the device (default: one whole-file forward)")
     ap.add_argument("--overlap-seconds", type=float, default=1.0, help="long-form mode: overlap of consecutive windows")
+    ap.add_argument("--batch", type=int, default=32, help="long-form mode: windows of the recording per forward")
+    ap.add_argument("--slots", type=int, default=None,
+                    help="stream-bank mode (implied by several files): files in flight at once, one window of each per forward; "
+                         "windows of --chunk-seconds (default 4)")
     ap.add_argument("--match-gain", action="store_true", help="long-form mode: align each speaker track's gain across windows")
     ap.add_argument("--resample", action="store_true",
                     help="convert a file at another sampling rate to the model's rate on the device (default: such a file is an error)")
@@ -269,11 +289,17 @@ def _main() -> None:
     else:
         model.load_synthetic_(0)
     model = model.eval().to(args.device)
-    if args.chunk_seconds is None:
-        _, written = separate_file(model, args.wav, resample=args.resample, out_rate=out_rate)
+    if len(args.wav) > 1 or args.slots is not None:
+        done = separate_many_files(model, args.wav, slots=32 if args.slots is None else args.slots,
+                                   chunk_seconds=4.0 if args.chunk_seconds is None else args.chunk_seconds,
+                                   overlap_seconds=args.overlap_seconds, match_gain=args.match_gain, resample=args.resample,
+                                   out_rate=out_rate)
+        written = [w for _, ws in done for w in ws]
+    elif args.chunk_seconds is None:
+        _, written = separate_file(model, args.wav[0], resample=args.resample, out_rate=out_rate)
     else:
-        _, written = separate_long_file(model, args.wav, chunk_seconds=args.chunk_seconds, overlap_seconds=args.overlap_seconds,
-                                        match_gain=args.match_gain, resample=args.resample, out_rate=out_rate)
+        _, written = separate_long_file(model, args.wav[0], chunk_seconds=args.chunk_seconds, overlap_seconds=args.overlap_seconds,
+                                        match_gain=args.match_gain, batch=args.batch, resample=args.resample, out_rate=out_rate)
     print("\n".join(written))
 
 

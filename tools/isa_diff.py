@@ -30,6 +30,8 @@ def kernels(path, pattern):
                     name = line.split("<", 1)[1][:-2]
                     cur = out.setdefault(name, []) if pat.search(name) else None
                 elif cur is not None and line.startswith("\t"):
+                    if line.strip() == "...":       # objdump's elision of the zero padding behind a kernel: layout, not an instruction
+                        continue
                     cur.append(line.split("//")[0].strip())
     return out
 
