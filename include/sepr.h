@@ -432,6 +432,35 @@ int sepr_streambank_step(const float* const* win, long long ld, const long long*
 int sepr_streambank_gather(const float* store, long long store_elems, long long cap, const long long* table, int A, int W, float* x,
                            sepr_stream_t stream);
 
+/* Sample-rate conversion inside the stream bank: the converter of sepr_resample_fwd below - the same constants, tables and
+ * [K][L] device layout, the same float64 fma chain from 0.0 in the order j = 0 .. K - 1, n M in 64 bits, one rounding - computed a span of
+ * outputs at a time, so that a stream is converted while it arrives.  sepr_streambank_convert serves A >= 1 rows in ONE launch; a row is
+ * one stream on the input side, one (stream, track) on the output side.  table: DEVICE int64 [A][10] =
+ *   conv, n0, n1, T_known, src base, src origin, src cap, dst base, dst origin, dst cap.
+ * The row computes outputs [n0, n1) of converter conv < NC:  y[n] = float32(sum_{j < K} double(tap[(n M) mod L][j]) * double(x[floor(n M / L)
+ * - Hh + j])) with x zero outside [0, T_known).  Source sample t is read from the ring src[base + (t - origin) mod cap], output n is written to
+ * the ring dst[base + (n - origin) mod cap] (bases, origins and caps in elements; a linear buffer is a ring that never wraps).  The caller
+ * names only outputs whose inputs exist - floor(n M / L) + Hh + 2 <= T_known while the stream is open, every n < ceil(T L / M) once T is known
+ * - and then the result equals sepr_resample_fwd of the whole recording bit for bit.  conv_taps / conv_L / conv_M / conv_K: HOST arrays of NC
+ * converter descriptions as sepr_dynmix_speed_fwd takes them (conv_taps[k]: device pointer to the [K][L] table), 1 <= NC <= 16; rows of
+ * different converters share the launch, L = 1 included.  nmax: HOST, at least the largest n1 - n0 of the table; it sizes the grid, and a row
+ * computes at most nmax outputs.  The kernel clamps conv into [0, NC), n0 and n1 into [0, 2^62 / M] and computes nothing for a row whose
+ * src or dst ring does not lie inside src_elems / dst_elems: a bad table gives wrong samples, never an access outside the buffers.  Two rows
+ * must not write the same destination element, and dst must not overlap what the launch reads.  No workspace, no atomics, no host
+ * synchronisation or allocation (capturable); bit-identical from run to run.  SEPR_EINVAL before any HIP call for null pointers
+ * (conv_taps[k] included), A < 1 or > 65535, NC outside 1..16, L, M or K < 1, K odd, nmax < 1, src_elems or dst_elems < 1, buffers not
+ * 4-byte aligned (the table 8), and for a converter whose tile span (255 M / L + K + 1 samples) exceeds 64 KiB of doubles.
+ * sepr_streambank_carry keeps the history the output side needs.  buf holds rows [slots][S][row_len] (row_len >= 2 hist, both multiples of 4,
+ * 16-byte aligned): [0, hist) of a row are the last hist samples emitted before the hop, the step emits from hist on.  For the slot of every row
+ * of step_table (sepr_streambank_step's [A][6] table; column 0, clamped into [0, slots)) and every track, [0, hist) <- [hist, 2 hist): after a
+ * window that emitted hist = H samples, the row again starts with the last H emitted.  A launch of its own after the conversion that reads the
+ * old history - the order of two launches on one stream is the synchronisation.  New entries, no struct change: ABI 4.13. */
+int sepr_streambank_convert(const float* src, long long src_elems, float* dst, long long dst_elems, const long long* table, int A,
+                            long long nmax, const float* const* conv_taps, const int* conv_L, const int* conv_M, const int* conv_K, int NC,
+                            sepr_stream_t stream);
+int sepr_streambank_carry(float* buf, long long buf_elems, const long long* step_table, int A, int slots, int S, int hist, long long row_len,
+                          sepr_stream_t stream);
+
 /* Sample-rate conversion of whole recordings (the reference resamples on the host inside librosa.load(path, sr=fs),
  * engine.py:155).  Rational ratio fs_out / fs_in = L / M (coprime), K taps per output phase (K even), Hh = (K - 2) / 2:
  *   y[n] = sum_{j < K} tap[(n M) mod L][j] * x[floor(n M / L) - Hh + j],  x zero outside [0, T),  0 <= n < N = ceil(T L / M).

@@ -153,13 +153,26 @@ def separate_many_files(model, paths: Sequence[str], fs: int = 8000, slots: int 
                         overlap_seconds: float = 1.0, match_gain: bool = False, resample: bool = False,
                         out_rate: Union[None, int, str] = None) -> List[Tuple[np.ndarray, List[str]]]:
     """``separate_long_file`` for several files at once through ``streambank.separate_many``: per file, the raw estimates and the
-    files written (the same names, the same 0.9 peak normalisation, the same ``resample`` / ``out_rate`` options)."""
+    files written (the same names, the same 0.9 peak normalisation, the same ``resample`` / ``out_rate`` options).  With ``resample`` the
+    files' own samples and rates go to the bank, which converts every stream inside its hops (``separate_many(rates=...)``): no file is
+    converted in a launch and a synchronisation of its own.  The copy of the input is converted only where it is written at ``fs``."""
     from .streambank import separate_many
-    loaded = [_load_mixture(model, p, fs, resample) for p in paths]
-    ests = separate_many(model, [mix for _, mix, _ in loaded], slots=slots, chunk_seconds=chunk_seconds,
-                         overlap_seconds=overlap_seconds, fs=fs, match_gain=match_gain)
-    return [_write_outputs(model, p[:-4], file_mix, sr, mix, est, fs, out_rate)
-            for p, (file_mix, mix, sr), est in zip(paths, loaded, ests)]
+    if not resample:
+        loaded = [_load_mixture(model, p, fs, False) for p in paths]
+        ests = separate_many(model, [mix for _, mix, _ in loaded], slots=slots, chunk_seconds=chunk_seconds,
+                             overlap_seconds=overlap_seconds, fs=fs, match_gain=match_gain)
+        return [_write_outputs(model, p[:-4], file_mix, sr, mix, est, fs, out_rate)
+                for p, (file_mix, mix, sr), est in zip(paths, loaded, ests)]
+    from .resample import resample as _resample
+    files = [(torch.from_numpy(data), sr) for data, sr in map(load_audio, paths)]
+    ests = separate_many(model, [x for x, _ in files], slots=slots, chunk_seconds=chunk_seconds, overlap_seconds=overlap_seconds, fs=fs,
+                         match_gain=match_gain, rates=[sr for _, sr in files])
+    dev = next(model.parameters()).device
+    done = []
+    for p, (x, sr), est in zip(paths, files, ests):
+        at_fs = sr == fs or (fs if out_rate is None else (sr if out_rate == "input" else int(out_rate))) != fs
+        done.append(_write_outputs(model, p[:-4], x, sr, x if at_fs else _resample(x, sr, fs, device=dev), est, fs, out_rate))
+    return done
 
 
 def _test_loop(model, utterances, sisnr_csv_path, sdr_csv_path, wav_dir, fs, with_sdr, stoi_csv_paths=None, stoi_out=None):

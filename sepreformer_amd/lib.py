@@ -165,6 +165,8 @@ SIGNATURES = {
     "sepr_streambank_state_bytes": (_ll, [_i, _i, _i]),
     "sepr_streambank_step": (_i, [C.POINTER(_fp), _ll, _fp, _i, _i, _i, _i, _i, _i, _fp, _ll, _fp, _fp, _fp, _sz, _fp]),
     "sepr_streambank_gather": (_i, [_fp, _ll, _ll, _fp, _i, _i, _fp, _fp]),
+    "sepr_streambank_convert": (_i, [_fp, _ll, _fp, _ll, _fp, _i, _ll, C.POINTER(_fp), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _i, _fp]),
+    "sepr_streambank_carry": (_i, [_fp, _ll, _fp, _i, _i, _i, _i, _ll, _fp]),
     "sepr_resample_out_len": (_ll, [_ll, _i, _i]),
     "sepr_resample_workspace": (_sz, [_i]),
     "sepr_resample_fwd": (_i, [_fp, C.POINTER(_ll), _fp, C.POINTER(_ll), _i, _fp, _i, _i, _i, _fp, _sz, _fp]),

@@ -8,10 +8,13 @@
     own spread in this call.
 (b) Live cost: for A in {1, 8, 32} streams, the hipEvent device time per hop of the gather launch, the forward and the step launch,
     each against the same run's forward.  There is no bar: the ratio is written down.
+    With ``--rate N`` / ``--out-rate N`` every stream is pushed at N Hz / returned at N Hz and converted inside the hop (DESIGN.md
+    section 5c-3); the input-convert launch and the output-convert launch (with the history carry) are timed beside the others.
+    Condition: both together take at most 5 % of the same hop's forward (median over the hops of one pass).
 
 Each part runs in a child process of its own under ``timeout -k 10 <s>``; the first part that fails ends the run.
 
-    python tools/stream_bench.py [--out profiles/stream_bank.json]
+    python tools/stream_bench.py [--out profiles/stream_bank.json] [--rate N] [--out-rate N] [--parts corpus,live]
 """
 import argparse
 import json
@@ -75,42 +78,61 @@ def part_corpus():
             "pass": "yes" if b["median"] >= a["median"] + (a["max"] - a["min"]) else "no"}
 
 
-def part_live():
+def part_live(rate=None, out_rate=None):
     import torch
     from sepreformer_amd import streambank
     from sepreformer_amd.synth import synth_mixture
     m = _model()
     hops, rows = 12, []
+    fin = rate or FS
     for A in (1, 8, 32):
-        bank = streambank.StreamBank(m, slots=A)
-        x = synth_mixture(1, bank.W + (hops + 2) * bank.H, seed=A)[0].to("cuda:0")
-        sids = [bank.open() for _ in range(A)]
+        bank = streambank.StreamBank(m, slots=A, max_rate=max(fin, out_rate or FS, 48000))
+        L, M, K, Hh = streambank.geometry(fin, FS)
+
+        def upto(n):                                                       # input samples that make n model-rate samples computable
+            return n if fin == FS else (n - 1) * M // L + Hh + 2
+
+        x = synth_mixture(1, upto(bank.W + (hops + 2) * bank.H), seed=A)[0].to("cuda:0")
+        sids = [bank.open(fs_in=rate, fs_out=out_rate) for _ in range(A)]
         for sid in sids:
-            bank.push(sid, x[:bank.W])
+            bank.push(sid, x[:upto(bank.W)])
         for h in range(hops + 2):
             bank.profile = h >= 2                                          # two hops of warm-up (k = 0 has no boundary)
             assert len(bank.step()) == A
             for sid in sids:
-                bank.push(sid, x[bank.W + h * bank.H:bank.W + (h + 1) * bank.H])
+                bank.push(sid, x[upto(bank.W + h * bank.H):upto(bank.W + (h + 1) * bank.H)])
         torch.cuda.synchronize()
-        ms = [[e[i].elapsed_time(e[i + 1]) for i in range(3)] for e in bank.hop_events]
+        ms = [[e[i].elapsed_time(e[i + 1]) for i in range(5)] for e in bank.hop_events]
         med = [sorted(c)[len(c) // 2] for c in zip(*ms)]
-        rows.append({"A": A, "hops": len(ms), "gather_ms": med[0], "forward_ms": med[1], "step_ms": med[2],
-                     "gather_over_forward": med[0] / med[1], "step_over_forward": med[2] / med[1]})
-    return {"unit": "median hipEvent device ms per hop", "rows": rows}
+        share = sorted((c[0] + c[4]) / c[2] for c in ms)
+        rows.append({"A": A, "hops": len(ms), "convert_in_ms": med[0], "gather_ms": med[1], "forward_ms": med[2], "step_ms": med[3],
+                     "convert_out_ms": med[4], "gather_over_forward": med[1] / med[2], "step_over_forward": med[3] / med[2],
+                     "convert_over_forward": share[len(share) // 2], "convert_over_forward_max": share[-1]})
+    out = {"unit": "median hipEvent device ms per hop", "rate_in": fin, "rate_out": out_rate or FS, "rows": rows}
+    if fin != FS or (out_rate or FS) != FS:
+        out["condition"] = "input plus output conversion (with the carry) at most 5 % of the same hop's forward, median over the hops"
+        out["pass"] = "yes" if all(r["convert_over_forward"] <= 0.05 for r in rows) else "no"
+    return out
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "stream_bank.json"))
+    ap.add_argument("--rate", type=int, default=None, help="live part: push every stream at this rate (default: the model's)")
+    ap.add_argument("--out-rate", type=int, default=None, help="live part: return every stream at this rate (default: the model's)")
+    ap.add_argument("--parts", default="corpus,live", help="which parts to run")
     ap.add_argument("--part", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.part:
-        print("RESULT " + json.dumps({"corpus": part_corpus, "live": part_live}[args.part]()), flush=True)
+        fn = {"corpus": part_corpus, "live": lambda: part_live(args.rate, args.out_rate)}[args.part]
+        print("RESULT " + json.dumps(fn()), flush=True)
         return 0
     result = {"model": "SepReformer_Base_WSJ0", "precision": "bf16x3", "chunk_seconds": 4.0, "overlap_seconds": 1.0}
+    rates = [f"--{k}={v}" for k, v in (("rate", args.rate), ("out-rate", args.out_rate)) if v]
     for part, limit in PARTS:
-        r = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--part", part],
+        if part not in args.parts.split(","):
+            continue
+        r = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--part", part] + rates,
                            cwd=ROOT, capture_output=True, text=True)
         line = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")]
         if r.returncode != 0 or not line:
