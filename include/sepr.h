@@ -441,9 +441,9 @@ int sepr_streambank_gather(const float* store, long long store_elems, long long 
  * - Hh + j])) with x zero outside [0, T_known).  Source sample t is read from the ring src[base + (t - origin) mod cap], output n is written to
  * the ring dst[base + (n - origin) mod cap] (bases, origins and caps in elements; a linear buffer is a ring that never wraps).  The caller
  * names only outputs whose inputs exist - floor(n M / L) + Hh + 2 <= T_known while the stream is open, every n < ceil(T L / M) once T is known
- * - and then the result equals sepr_resample_fwd of the whole recording bit for bit.  conv_taps / conv_L / conv_M / conv_K: HOST arrays of NC
- * converter descriptions as sepr_dynmix_speed_fwd takes them (conv_taps[k]: device pointer to the [K][L] table), 1 <= NC <= 16; rows of
- * different converters share the launch, L = 1 included.  nmax: HOST, at least the largest n1 - n0 of the table; it sizes the grid, and a row
+ * - and then the result equals sepr_resample_fwd of the whole recording bit for bit.  conv_taps / conv_L / conv_M / conv_K / NC: a converter
+ * set (described once, at sepr_resample_fwd below) with 1 <= NC <= 16 and 4-byte aligned tables; rows of different converters share the
+ * launch, L = 1 included.  nmax: HOST, at least the largest n1 - n0 of the table; it sizes the grid, and a row
  * computes at most nmax outputs.  The kernel clamps conv into [0, NC), n0 and n1 into [0, 2^62 / M] and computes nothing for a row whose
  * src or dst ring does not lie inside src_elems / dst_elems: a bad table gives wrong samples, never an access outside the buffers.  Two rows
  * must not write the same destination element, and dst must not overlap what the launch reads.  No workspace, no atomics, no host
@@ -473,7 +473,11 @@ int sepr_streambank_carry(float* buf, long long buf_elems, const long long* step
  * n mod L (for L = 1 this is the tap row itself); sepreformer_amd/resample.py::plan builds the table for the Kaiser-windowed sinc of section 5d.
  * R <= 65535; ratios whose tile span (255 M / L + K + 1 samples, + K for L = 1) exceeds 64 KiB of doubles are SEPR_EINVAL.  Every argument
  * check returns SEPR_EINVAL (SEPR_EWORKSPACE for a short workspace) before any HIP call; no host synchronisation or allocation (capturable).
- * sepr_resample_out_len: 0 for T, L or M < 1.  Workspace: sepr_resample_workspace(R) bytes (0 for unsupported R). */
+ * sepr_resample_out_len: 0 for T, L or M < 1.  Workspace: sepr_resample_workspace(R) bytes (0 for unsupported R).
+ * A CONVERTER SET (conv_taps / conv_L / conv_M / conv_K / NC of sepr_streambank_convert, sepr_dynmix_speed_fwd, sepr_dynmix_speed_reverb_fwd) is
+ * NC <= 16 converters as HOST arrays read before the call returns: conv_taps[k] the DEVICE pointer to converter k's float32 [K][L] table in the
+ * layout above, conv_L[k], conv_M[k] >= 1, conv_K[k] even and >= 2; anything else, or a null array or table pointer while NC > 0, is
+ * SEPR_EINVAL.  The least NC, the span limit and the alignment are each entry's own. */
 long long sepr_resample_out_len(long long T, int L, int M);
 size_t sepr_resample_workspace(int R);
 int sepr_resample_fwd(const float* x, const long long* in_offset, float* y, const long long* out_offset, int R, const float* taps, int L,
@@ -509,8 +513,7 @@ int sepr_resample_fwd(const float* x, const long long* in_offset, float* y, cons
  *
  * sepr_dynmix_speed_fwd: sepr_dynmix_fwd with speed perturbation.  term_conv [B (M + S)] int32 (DEVICE): -1 = the term is
  * the stored utterance, as in sepr_dynmix_fwd and with its bits; k in 0 .. NC - 1 = the term is the utterance passed through converter k.  The
- * converters are HOST arrays read before the call returns: conv_taps [NC] device pointers, each a float32 [K][L] table in the layout of
- * sepr_resample_fwd; conv_L, conv_M, conv_K [NC]; 0 <= NC <= 16 (the four may be NULL for NC = 0).  The perturbed utterance has
+ * converters are a converter set (sepr_resample_fwd above) with 0 <= NC <= 16 (the four arrays may be NULL for NC = 0).  The perturbed utterance has
  * sepr_resample_out_len(T, L, M) samples and its sample y[n] is exactly sepr_resample_fwd's: exact float64 products summed in the order
  * j = 0 .. K - 1, rounded once to float32, x zero outside [0, T) of THAT utterance.  A perturbed term's value at output sample t is
  * (y[term_start + t] * term_norm) * term_gain: term_start indexes the perturbed utterance, the phase is ((term_start + t) M) mod L in 64-bit
@@ -541,7 +544,7 @@ int sepr_resample_fwd(const float* x, const long long* in_offset, float* y, cons
  * frozen, the table contents - RIR indices and tap counts included - are read at replay).
  *
  * sepr_dynmix_speed_reverb_fwd: both inside one launch, the talker first and the room second.  The arguments are the common
- * ones, the three columns term_conv, term_rir, term_taps [B (M + S)] int32 (DEVICE), the converter arrays of sepr_dynmix_speed_fwd (0 <= NC <= 16)
+ * ones, the three columns term_conv, term_rir, term_taps [B (M + S)] int32 (DEVICE), the converter set of sepr_dynmix_speed_fwd (0 <= NC <= 16)
  * and the bank arguments of sepr_dynmix_reverb_fwd.  A term is (utt, start, norm, gain, conv, rir, taps).  With conv >= 0 and rir >= 0, x the stored
  * utterance of T samples and (L, M, K) the converter:
  *   y    the perturbed utterance of P = sepr_resample_out_len(T, L, M) samples; y[n] is exactly sepr_dynmix_speed_fwd's / sepr_resample_fwd's float32

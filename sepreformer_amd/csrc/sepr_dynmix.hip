@@ -22,16 +22,16 @@
 //                        integer fields and the same-term flag are wave-uniform (readfirstlane) before any branch around a barrier.
 //     F = SpeedReverbForm (sepr_dynmix_speed_reverb_fwd, section 5e-5) a term may carry a converter AND a response: the utterance perturbed
 //                        first, reverberated second.  The geometry of ReverbForm; per tap chunk the span of the perturbed utterance that the
-//                        chunk reaches is converted into LDS as doubles (convert_tile's arithmetic, in passes whose input span fits the
+//                        chunk reaches is converted into LDS as doubles (the converter of sepr_polyphase.h, in passes whose input span fits the
 //                        staged doubles), then the FIR loop runs over it.  57 344 bytes of LDS; a term with one of the two takes that
 //                        form's code and gives its bits.
 //   dynmix_speed_kernel  (sepr_dynmix_speed_fwd, section 5e-2) the same batch with speed perturbation, a kernel of its own (docs/HISTORY.md:
 //                        as an instance of the skeleton it ran 0.8 to 1.1 us longer per launch at B = 16): a term whose term_conv is a converter
-//                        index is the stored utterance through that rational-ratio converter (the arithmetic of sepr_resample.hip).  The
+//                        index is the stored utterance through that rational-ratio converter (sepr_polyphase.h).  The
 //                        same tile geometry: input span staged in LDS as doubles, outputs converted one per lane, transposed through an
 //                        LDS tile of floats.  It shares term_value, scale8, store8 and the launcher.
 // Nothing here depends on the launch order of workgroups: results are bit-identical from run to run.
-#include "sepr_common.h"
+#include "sepr_polyphase.h"
 
 namespace sepr {
 namespace {
@@ -126,7 +126,6 @@ __device__ __forceinline__ void store8(float* __restrict__ row, const float v[8]
 // ---- the tiled forms: a workgroup makes DS_TILE outputs of one example, one output per lane, through 32 768 bytes of LDS ----------
 constexpr int DS_TILE = DM_TPB * DM_PER;   // output samples per workgroup
 constexpr int DS_SPAN = 3072;              // doubles of staged input: (DS_TILE - 1) M / L + K + 1 must fit (speeds of about 70 % to 140 %)
-constexpr int DS_MAX_NC = 16;
 constexpr int DR_CHUNK = 1024;             // taps per chunk: the chunk's span DS_TILE + DR_CHUNK - 1 = 3071 doubles fits xs [DS_SPAN]
 constexpr int DR_MAX_TAPS = 16384;
 static_assert(DS_TILE + DR_CHUNK - 1 <= DS_SPAN, "a chunk's input span must fit the staged doubles");
@@ -154,15 +153,10 @@ struct DmUtt {
 
   // xs[i] = double(sample g0 + i) for i < count, zero outside [0, T); all threads of the workgroup, no barrier
   __device__ __forceinline__ void stage(const DmCorpus& c, long long g0, int count, double* __restrict__ xs) const {
-    for (int i = threadIdx.x; i < count; i += DM_TPB) {
-      const long long g = g0 + i;
-      double v = 0.0;
-      if (g >= 0 && g < T) {
-        const long long e = clampll(e0 + g, 0, total - 1);
-        v = is16 ? (double)((float)c.buf16[e] * 3.0517578125e-05f) : (double)c.buf32[e];
-      }
-      xs[i] = v;
-    }
+    pp_stage<DM_TPB>(xs, count, g0, T, [&](long long g, int) {
+      const long long e = clampll(e0 + g, 0, total - 1);
+      return is16 ? (double)((float)c.buf16[e] * 3.0517578125e-05f) : (double)c.buf32[e];
+    });
   }
 };
 
@@ -178,19 +172,24 @@ __device__ __forceinline__ void tile_out8(const double acc[DM_PER], float* __res
   x[0] = lo.x, x[1] = lo.y, x[2] = lo.z, x[3] = lo.w, x[4] = hi.x, x[5] = hi.y, x[6] = hi.z, x[7] = hi.w;
 }
 
-struct DsConv {
-  const float* taps[DS_MAX_NC];            // [K][L], column q = the tap row of phase (q M) mod L (resample.device_table)
-  int L[DS_MAX_NC], M[DS_MAX_NC], K[DS_MAX_NC];
-  int NC;
-};
-
-__host__ __device__ inline long long ds_span(int L, int M, int K) { return ((long long)(DS_TILE - 1) * M) / L + K + 1; }
-
 struct DrBank {
   const float* h;                          // the R impulse responses back to back
   const long long* off;                    // [R + 1] cumulative sample counts
   long long total;
   int R;
+};
+
+// the first K of `taps` samples of response r >= 0 at hp; the table is not trusted: both are clamped so that every tap read is inside the bank
+struct DrResp {
+  int K;
+  const float* __restrict__ hp;
+  __device__ __forceinline__ DrResp(const DrBank& bk, int r, int taps) {
+    const int rr = r >= bk.R ? bk.R - 1 : r;
+    const long long h0 = clampll(bk.off[rr], 0, bk.total - 1);
+    const long long hl = clampll(bk.off[rr + 1] - h0, 1, bk.total - h0 < DR_MAX_TAPS ? bk.total - h0 : DR_MAX_TAPS);
+    K = taps < 1 ? 1 : (taps > (int)hl ? (int)hl : taps);
+    hp = bk.h + h0;
+  }
 };
 
 // outputs t = tile0 .. tile0 + DS_TILE - 1 of term (utt, start) convolved with the first `taps` samples of impulse response r, as
@@ -204,11 +203,9 @@ __device__ __forceinline__ void reverb_tile(const DmCorpus& c, const DrBank& bk,
   const int tid = threadIdx.x;
   const DmUtt ut(c, utt);
   const long long st = clampll(start, 0, ut.T > 0 ? ut.T : 0);
-  const int rr = r >= bk.R ? bk.R - 1 : r;                                   // r >= 0 here
-  const long long h0 = clampll(bk.off[rr], 0, bk.total - 1);
-  const long long hl = clampll(bk.off[rr + 1] - h0, 1, bk.total - h0 < DR_MAX_TAPS ? bk.total - h0 : DR_MAX_TAPS);
-  const int K = taps < 1 ? 1 : (taps > (int)hl ? (int)hl : taps);            // h0 + K <= total: every tap read is inside the bank
-  const float* __restrict__ hp = bk.h + h0;
+  const DrResp rs(bk, r, taps);                                              // r >= 0 here
+  const int K = rs.K;
+  const float* __restrict__ hp = rs.hp;
   const int left = n - tile0;                                                // > 0: the caller returned for tiles past n
   double acc[DM_PER];
 #pragma unroll
@@ -244,52 +241,32 @@ __device__ __forceinline__ void reverb_tile(const DmCorpus& c, const DrBank& bk,
 __device__ __forceinline__ void convert_tile(const DmCorpus& c, int utt, int start, const float* __restrict__ tp, int L, int M, int K,
                                              int tile0, int n, double* __restrict__ xs, float* __restrict__ ys) {
   const int tid = threadIdx.x;
-  const int u = utt < 0 ? 0 : (utt >= c.N ? c.N - 1 : utt);
-  const long long o0 = c.off[u], T = c.off[u + 1] - o0;
-  const bool is16 = u < c.N16;
-  const long long total = is16 ? c.total16 : c.total32;
-  const long long e0 = o0 - (is16 ? 0 : c.off[c.N16]);
+  const DmUtt ut(c, utt);
   const long long n0 = (long long)(start < 0 ? 0 : start) + tile0;          // first output of the tile, as an index of the perturbed utterance
   const int Hh = (K - 2) / 2;
-  const long long b0 = (n0 * M) / L, g0 = b0 - Hh;
-  const int span = (int)ds_span(L, M, K);                                    // <= DS_SPAN: the entry refuses any other converter
-  for (int i = tid; i < span; i += DM_TPB) {
-    const long long g = g0 + i;
-    double v = 0.0;
-    if (g >= 0 && g < T) {
-      const long long e = clampll(e0 + g, 0, total - 1);
-      v = is16 ? (double)((float)c.buf16[e] * 3.0517578125e-05f) : (double)c.buf32[e];
-    }
-    xs[i] = v;
-  }
+  const long long b0 = pp_base(n0, L, M), g0 = b0 - Hh;
+  const int span = (int)pp_span(DS_TILE, L, M, K);                           // <= DS_SPAN: the entry refuses any other converter
+  ut.stage(c, g0, span, xs);
   __syncthreads();
   const int left = n - tile0;                                                // > 0: the caller returned for tiles past n
   const int lim = span - K;                                                  // highest window base inside the staged span
-  double acc[DM_PER];
+  double acc[DM_PER] = {};
   const double* xp[DM_PER];
   const float* tq[DM_PER];
 #pragma unroll
   for (int i = 0; i < DM_PER; ++i) {
     const long long nn = n0 + tid + i * DM_TPB;
-    const long long d = (nn * M) / L - b0;                                   // 0 .. (DS_TILE - 1) M / L + 1
-    xp[i] = xs + (int)(d < 0 ? 0 : (d > lim ? lim : d));
-    tq[i] = tp + (int)(nn % L);
-    acc[i] = 0.0;
+    xp[i] = xs + pp_window(nn, L, M, b0, lim);                               // 0 .. (DS_TILE - 1) M / L + 1
+    tq[i] = tp + pp_phase(nn, L);
   }
-  if (tid < left) {                                                          // (per wave: whole waves past n skip the loop)
-#pragma unroll 2
-    for (int j = 0; j < K; ++j) {
-#pragma unroll
-      for (int i = 0; i < DM_PER; ++i) acc[i] = fma((double)tq[i][(long long)j * L], xp[i][j], acc[i]);
-    }
-  }
+  if (tid < left) pp_chain<DM_PER, 2>(tq, (long long)L, xp, K, acc);         // (per wave: whole waves past n skip the loop)
 #pragma unroll
   for (int i = 0; i < DM_PER; ++i) ys[tid + i * DM_TPB] = (float)acc[i];
   __syncthreads();
 }
 
 // a term of the speed kernel on samples t0 .. t0 + 7: through its converter when it has one, else term_value
-__device__ __forceinline__ void speed_term_value(const DmCorpus& c, const DsConv& cv, int conv, int utt, int start, float norm, float gain,
+__device__ __forceinline__ void speed_term_value(const DmCorpus& c, const ConvSet& cv, int conv, int utt, int start, float norm, float gain,
                                                  int tile0, int t0, int n, double* xs, float* ys, float v[8]) {
 #pragma clang fp contract(off)
   if (conv < 0 || cv.NC < 1) {
@@ -307,7 +284,7 @@ __device__ __forceinline__ void speed_term_value(const DmCorpus& c, const DsConv
 // The speed launch keeps the body and the code it had before the skeleton (per-lane reads of n and the term fields included: every lane
 // reads the same address, which is what keeps its barriers safe).
 template <int S>
-__global__ __launch_bounds__(DM_TPB) void dynmix_speed_kernel(DmCorpus c, DsConv cv, const int* __restrict__ term_utt,
+__global__ __launch_bounds__(DM_TPB) void dynmix_speed_kernel(DmCorpus c, ConvSet cv, const int* __restrict__ term_utt,
                                                               const int* __restrict__ term_start, const float* __restrict__ term_norm,
                                                               const float* __restrict__ term_gain, const int* __restrict__ term_conv,
                                                               const int* __restrict__ nlen, int M, int Tmax, float* __restrict__ mix, DmRows src) {
@@ -389,7 +366,7 @@ struct PlainForm {
 // the speed entry's corpus and converters for dynmix_launch; its kernel is dynmix_speed_kernel, not an instance of the skeleton
 struct SpeedForm {
   DmCorpus c;
-  DsConv cv;
+  ConvSet cv;
 };
 
 // a term whose rir is an index into the bank is the stored utterance under the first taps samples of that response; rir < 0: as stored
@@ -427,7 +404,7 @@ static_assert(sizeof(SrLds) <= 57344, "static LDS of the combined form");
 
 // perturbed samples of the positions i = i0 + tid + 256 k (k < NI) below i1 into yd[i]: position i is sample q0 + i >= 0 of the perturbed utterance,
 //   y[q] = float32(sum_{j < K} double(tap[(q M) mod L][j]) * x[floor(q M / L) - Hh + j]),
-// convert_tile's arithmetic and order; xs[0] is input sample b0 - Hh and `span` doubles are staged.  No barrier.  Every window base is clamped into
+// the window and the chain of sepr_polyphase.h; xs[0] is input sample b0 - Hh and `span` doubles are staged.  No barrier.  Every window base is clamped into
 // [0, span - K] (span <= DS_SPAN, K <= span: the entry refuses any other converter) and every phase lies in [0, L): no read leaves xs or the tap table.
 template <int NI>
 __device__ __forceinline__ void convert_group(const double* __restrict__ xs, int span, long long b0, const float* __restrict__ tp, int L, int M,
@@ -442,16 +419,10 @@ __device__ __forceinline__ void convert_group(const double* __restrict__ xs, int
   for (int i = 0; i < NI; ++i) {
     const int pos = i0 + tid + i * DM_TPB;
     const long long nn = q0 + (pos < i1 ? pos : i0);                        // a lane past i1 converts the group's first position and drops it
-    const long long d = (nn * M) / L - b0;
-    xp[i] = xs + (int)(d < 0 ? 0 : (d > lim ? lim : d));
-    tq[i] = tp + (int)(nn % L);
-    acc[i] = 0.0;
+    xp[i] = xs + pp_window(nn, L, M, b0, lim);
+    tq[i] = tp + pp_phase(nn, L);
   }
-#pragma unroll 2
-  for (int j = 0; j < K; ++j) {
-#pragma unroll
-    for (int i = 0; i < NI; ++i) acc[i] = fma((double)tq[i][(long long)j * L], xp[i][j], acc[i]);
-  }
+  pp_chain<NI, 2>(tq, (long long)L, xp, K, acc);
 #pragma unroll
   for (int i = 0; i < NI; ++i) {
     const int pos = i0 + tid + i * DM_TPB;
@@ -469,20 +440,18 @@ __device__ __forceinline__ void convert_group(const double* __restrict__ xs, int
 // The tables are not trusted.  conv is clamped to [0, NC - 1], r and taps as in reverb_tile (every tap read inside the bank), the utterance by
 // DmUtt (every staged element clamped into its buffer), start into [0, P]; ys is written and read at indices in [DR_CHUNK - kc, DS_TILE +
 // DR_CHUNK - 1) only, xs below `span` <= DS_SPAN only.
-__device__ __forceinline__ void speed_reverb_tile(const DmCorpus& c, const DsConv& cv, const DrBank& bk, int conv, int r, int taps, int utt,
+__device__ __forceinline__ void speed_reverb_tile(const DmCorpus& c, const ConvSet& cv, const DrBank& bk, int conv, int r, int taps, int utt,
                                                   int start, int tile0, int n, SrLds& lds, float x8[8]) {
   const int tid = threadIdx.x;
   const DmUtt ut(c, utt);
   const int ck = conv >= cv.NC ? cv.NC - 1 : conv;                           // conv >= 0 and NC >= 1 here
   const float* __restrict__ tp = cv.taps[ck];
   const int L = cv.L[ck], M = cv.M[ck], Kc = cv.K[ck], Hh = (Kc - 2) / 2;
-  const long long P = ut.T > 0 ? (ut.T * L + M - 1) / M : 0;                 // sepr_resample_out_len
+  const long long P = ut.T > 0 ? pp_out_len(ut.T, L, M) : 0;
   const long long st = clampll(start, 0, P);
-  const int rr = r >= bk.R ? bk.R - 1 : r;                                   // r >= 0 here
-  const long long h0 = clampll(bk.off[rr], 0, bk.total - 1);
-  const long long hl = clampll(bk.off[rr + 1] - h0, 1, bk.total - h0 < DR_MAX_TAPS ? bk.total - h0 : DR_MAX_TAPS);
-  const int K = taps < 1 ? 1 : (taps > (int)hl ? (int)hl : taps);            // h0 + K <= total: every tap read is inside the bank
-  const float* __restrict__ hp = bk.h + h0;
+  const DrResp rs(bk, r, taps);                                              // r >= 0 here
+  const int K = rs.K;
+  const float* __restrict__ hp = rs.hp;
   const int left = n - tile0;                                                // > 0: the caller returned for tiles past n
   const int top = (DR_CHUNK - 1) + (left < DS_TILE ? left : DS_TILE);        // positions from here on reach no output below n
   const long long Wl = ((long long)(DS_SPAN - Kc - 1) * L) / M + 1;          // ((W - 1) M) / L + K + 1 <= DS_SPAN
@@ -509,8 +478,8 @@ __device__ __forceinline__ void speed_reverb_tile(const DmCorpus& c, const DsCon
     for (int i = tid; i < kc; i += DM_TPB) hs[i] = (double)hp[k0 + i];
     for (int a = ca; a < cb; a += W) {
       const int e = cb - a > W ? a + W : cb;
-      const long long b0 = ((g0 + a) * M) / L;                               // g0 + a >= 0
-      const long long sp = ((g0 + e - 1) * M) / L - b0 + Kc;                 // <= ((W - 1) M) / L + 1 + K <= DS_SPAN
+      const long long b0 = pp_base(g0 + a, L, M);                             // g0 + a >= 0
+      const long long sp = pp_base(g0 + e - 1, L, M) - b0 + Kc;              // <= ((W - 1) M) / L + 1 + K <= DS_SPAN
       const int span = sp > DS_SPAN ? DS_SPAN : (int)sp;
       if (a != ca) __syncthreads();                                          // the pass before has read xs
       ut.stage(c, b0 - Hh, span, lds.a.xs);
@@ -524,7 +493,7 @@ __device__ __forceinline__ void speed_reverb_tile(const DmCorpus& c, const DsCon
       }
     }
     __syncthreads();
-    if (tid < left) {                                                        // (per wave: whole waves past n skip the loop)
+    if (tid < left) {                                                        // reverb_tile's loop, written again: as one function both kernels grow
 #pragma unroll 4
       for (int j = 0; j < kc; ++j) {
         const double hj = hs[j];
@@ -542,7 +511,7 @@ __device__ __forceinline__ void speed_reverb_tile(const DmCorpus& c, const DsCon
 struct SpeedReverbForm {
   static constexpr bool kTiled = true;
   DmCorpus c;
-  DsConv cv;
+  ConvSet cv;
   DrBank bk;
   struct Cols {
     int conv, rir, taps;
@@ -769,21 +738,8 @@ int dynmix_launch(const short* buf16, long long total16, const float* buf32, lon
   return SEPR_OK;
 }
 
-// the converter arguments of the speed entries, checked and copied into cv; 0 = fine
-int converters_bad(const float* const* conv_taps, const int* conv_L, const int* conv_M, const int* conv_K, int NC, DsConv& cv) {
-  if (NC < 0 || NC > DS_MAX_NC) return 1;
-  if (NC > 0 && (!conv_taps || !conv_L || !conv_M || !conv_K)) return 1;
-  cv.NC = NC;
-  for (int k = 0; k < NC; ++k) {
-    if (!conv_taps[k] || conv_L[k] < 1 || conv_M[k] < 1 || conv_K[k] < 1 || conv_K[k] % 2 != 0) return 1;
-    if (ds_span(conv_L[k], conv_M[k], conv_K[k]) > DS_SPAN) return 1;        // the tile's input span exceeds the kernel's LDS plan
-    cv.taps[k] = conv_taps[k];
-    cv.L[k] = conv_L[k];
-    cv.M[k] = conv_M[k];
-    cv.K[k] = conv_K[k];
-  }
-  return 0;
-}
+// the converter policy of the speed entries: none is fine, the tile's input span fits the kernel's LDS plan, the entries from NC on stay zero
+constexpr ConvPolicy DS_POLICY = {DS_TILE, 0, DS_SPAN, 0, false, false};
 
 // the bank arguments of the reverberant entries, checked and copied into bk; 0 = fine
 int bank_bad(const float* rir, long long rir_total, const long long* rir_off, int R, DrBank& bk) {
@@ -810,7 +766,7 @@ extern "C" int sepr_dynmix_speed_fwd(const short* buf16, long long total16, cons
                                      int NC, sepr_stream_t stream) {
   using namespace sepr;
   SpeedForm form = {};
-  if (!term_conv || converters_bad(conv_taps, conv_L, conv_M, conv_K, NC, form.cv)) return SEPR_EINVAL;
+  if (!term_conv || !pp_fill(conv_taps, conv_L, conv_M, conv_K, NC, DS_POLICY, form.cv)) return SEPR_EINVAL;
   return dynmix_launch(buf16, total16, buf32, total32, offsets, N16, N, term_utt, term_start, term_norm, term_gain, n, B, M, S, Tmax, mix, src,
                        stream, form, "dynmix speed kernel", term_conv);
 }
@@ -835,7 +791,7 @@ extern "C" int sepr_dynmix_speed_reverb_fwd(const short* buf16, long long total1
                                             const long long* rir_off, int R, sepr_stream_t stream) {
   using namespace sepr;
   SpeedReverbForm form = {};
-  if (!term_conv || converters_bad(conv_taps, conv_L, conv_M, conv_K, NC, form.cv)) return SEPR_EINVAL;
+  if (!term_conv || !pp_fill(conv_taps, conv_L, conv_M, conv_K, NC, DS_POLICY, form.cv)) return SEPR_EINVAL;
   if (!term_rir || !term_taps || bank_bad(rir, rir_total, rir_off, R, form.bk)) return SEPR_EINVAL;
   return dynmix_launch(buf16, total16, buf32, total32, offsets, N16, N, term_utt, term_start, term_norm, term_gain, n, B, M, S, Tmax, mix, src,
                        stream, form, "dynmix speed-reverb kernel", term_conv, term_rir, term_taps);

@@ -1,24 +1,16 @@
-// Sample-rate conversion of whole recordings: rational ratio L / M, band-limited, one tap row per output phase.
-//
-//   y[n] = sum_{j < K} tap[(n M) mod L][j] * x[floor(n M / L) - Hh + j],   Hh = (K - 2) / 2,   x = 0 outside [0, T)
-//
-// The taps and the samples are float32, so every product is exact in float64; the products are summed in float64 in the order
-// j = 0 .. K - 1 and the sum is rounded once to float32.  One thread per output sample, one workgroup per tile of RS_TILE
-// consecutive outputs of ONE recording (grid.y = recording): the tile's input span, (RS_TILE - 1) M / L + K + 1 samples, is staged
-// once in LDS already widened to double, zero-extended by predicate at both ends of the recording - a tile never reads another
-// recording's samples.  L = 1 (integer decimation): every output uses the same tap row, kept in LDS as doubles and read as a
+// Sample-rate conversion of whole recordings: the converter of sepr_polyphase.h - which states the filter, the span rule,
+// the window, the staging loop and the fma chain - one thread per output sample, one workgroup per tile of RS_TILE consecutive outputs of ONE
+// recording (grid.y = recording): the tile's input span is staged once in LDS, zero-extended at both ends of the recording - a tile never reads
+// another recording's samples.  L = 1 (integer decimation): every output uses the same tap row, kept in LDS as doubles and read as a
 // broadcast.  L > 1: the table arrives transposed and in output order, [K][L] indexed by n mod L, so consecutive lanes read
 // consecutive taps of a table that stays in L2.  No atomics, nothing depends on the launch order: bit-identical from run to run,
 // and a recording's result does not depend on what else is in the call.
-#include "sepr_common.h"
+#include "sepr_polyphase.h"
 
 namespace sepr {
 namespace {
 constexpr int RS_TILE = 256;
 constexpr int RS_MAX_R = 65535;                  // grid.y
-constexpr size_t RS_MAX_LDS = 64 * 1024;         // dynamic LDS of one workgroup
-
-__host__ __device__ inline int rs_span(int L, int M, int K) { return (int)(((long long)(RS_TILE - 1) * M) / L) + K + 1; }
 
 template <bool ONE>
 __global__ __launch_bounds__(RS_TILE) void resample_kernel(const float* __restrict__ x, const long long* __restrict__ in_off,
@@ -29,33 +21,26 @@ __global__ __launch_bounds__(RS_TILE) void resample_kernel(const float* __restri
   const long long xo = in_off[r], T = in_off[r + 1] - xo, yo = out_off[r], N = out_off[r + 1] - yo;
   const long long n0 = (long long)blockIdx.x * RS_TILE;
   if (n0 >= N) return;                                              // the grid is as wide as the longest recording
-  const int Hh = (K - 2) / 2, span = rs_span(L, M, K);
-  const long long b0 = ONE ? n0 * M : (n0 * M) / L;
+  const int Hh = (K - 2) / 2, span = (int)pp_span(RS_TILE, L, M, K), Lq = ONE ? 1 : L;   // (L = 1 as a constant: no division)
+  const long long b0 = pp_base(n0, Lq, M);
   double* xs = rs_lds;
   double* ts = rs_lds + span;
-  const long long g0 = b0 - Hh;
-  for (int i = tid; i < span; i += RS_TILE) {
-    const long long g = g0 + i;
-    xs[i] = (g >= 0 && g < T) ? (double)x[xo + g] : 0.0;
-  }
+  pp_stage<RS_TILE>(xs, span, b0 - Hh, T, [&](long long g, int) { return (double)x[xo + g]; });
   if (ONE)
     for (int j = tid; j < K; j += RS_TILE) ts[j] = (double)taps[j];
   __syncthreads();
   const long long n = n0 + tid;
   if (n >= N) return;
-  const long long nm = n * M;                                       // 64-bit: passes 2^31 after minutes of audio
-  const long long b = ONE ? nm : nm / L;
-  const double* xp = xs + (int)(b - b0);                            // 0 <= b - b0 <= (RS_TILE - 1) M / L + 1
-  double acc = 0.0;
-  if (ONE) {
+  const double* const xp[1] = {xs + (int)(pp_base(n, Lq, M) - b0)};  // n M in 64 bits; 0 <= b - b0 <= (RS_TILE - 1) M / L + 1
+  double acc[1] = {0.0};
+  if (ONE) {   // its own text, not pp_chain: through the template this instantiation takes two more instructions (docs/HISTORY.md)
 #pragma unroll 8
-    for (int j = 0; j < K; ++j) acc = fma(ts[j], xp[j], acc);
+    for (int j = 0; j < K; ++j) acc[0] = fma(ts[j], xp[0][j], acc[0]);
   } else {
-    const float* tp = taps + (int)(n % L);
-#pragma unroll 8
-    for (int j = 0; j < K; ++j) acc = fma((double)tp[(long long)j * L], xp[j], acc);
+    const float* const tq[1] = {taps + pp_phase(n, L)};
+    pp_chain<1, 8>(tq, (long long)L, xp, K, acc);
   }
-  y[yo + n] = (float)acc;
+  y[yo + n] = (float)acc[0];
 }
 struct ResampleWs {   // device copies of in_offset and out_offset [R + 1]
   long long *ioff, *ooff;
@@ -66,7 +51,7 @@ struct ResampleWs {   // device copies of in_offset and out_offset [R + 1]
 
 extern "C" long long sepr_resample_out_len(long long T, int L, int M) {
   if (T < 1 || L < 1 || M < 1 || T > (1LL << 62) / L) return 0;
-  return (T * L + M - 1) / M;
+  return sepr::pp_out_len(T, L, M);
 }
 
 extern "C" size_t sepr_resample_workspace(int R) {
@@ -80,8 +65,9 @@ extern "C" int sepr_resample_fwd(const float* x, const long long* in_offset, flo
   using namespace sepr;
   if (!x || !in_offset || !y || !out_offset || !taps) return SEPR_EINVAL;
   if (R < 1 || R > RS_MAX_R || L < 1 || M < 1 || K < 2 || K % 2 != 0) return SEPR_EINVAL;
-  const size_t lds = ((size_t)rs_span(L, M, K) + (L == 1 ? (size_t)K : 0)) * sizeof(double);
-  if ((long long)(RS_TILE - 1) * M / L + K + 1 > 0x7fffffffLL || lds > RS_MAX_LDS) return SEPR_EINVAL;   // ratio beyond one tile's LDS
+  const long long span = pp_span(RS_TILE, L, M, K);
+  const size_t lds = (size_t)(span + (L == 1 ? K : 0)) * sizeof(double);
+  if (span > 0x7fffffffLL || lds > PP_MAX_LDS) return SEPR_EINVAL;                                       // ratio beyond one tile's LDS
   if (in_offset[0] != 0 || out_offset[0] != 0) return SEPR_EINVAL;
   long long nmax = 0;
   for (int r = 0; r < R; ++r) {

@@ -1,45 +1,33 @@
-// Sample-rate conversion inside the stream bank: sepr_resample_fwd's filter, computed a span of outputs at a time
-// for A rows of one hop, each row with its own converter, reading from and writing to rings.
+// Sample-rate conversion inside the stream bank: the converter of sepr_polyphase.h - sepr_resample_fwd's filter, span rule,
+// window and fma chain, the same code and so the same bits - computed a span of outputs at a time for A rows of one hop, each row with its own
+// converter, reading from and writing to rings.
 //
-//   y[n] = float32( sum_{j < K} double(tap[(n M) mod L][j]) * double(x[floor(n M / L) - Hh + j]) ),   Hh = (K - 2) / 2,   x = 0 outside [0, T_known)
-//
-// The arithmetic is resample_kernel's (sepr_resample.hip), restated here so that kernel's code does not move: the span staged once in LDS
-// already widened to double and zero-extended by predicate, n M in 64 bits, one fma chain from 0.0 in the order j = 0 .. K - 1, one
-// rounding.  The taps are (double)taps[j][n mod L] of the [K][L] device table for every L - at L = 1 column 0 is the tap row itself, the value
-// resample_kernel<true> keeps in LDS - so one code path serves both and the bits are the same; a table of up to 4096 taps that fits beside the
-// span is widened into LDS once per tile (every L = 1 converter inside the span limit, and the small upsampling tables), a larger one is read
-// from global memory as resample_kernel<false> reads it.  What is new is the addressing: source
-// sample t lies at src + base + (t - origin) mod cap, output n goes to dst + base + (n - origin) mod cap, and the row's converter, span of
-// outputs [n0, n1) and T_known come from a DEVICE table.  One workgroup per tile of SR_TILE consecutive outputs of ONE row (grid.y = row), a
-// tile never reads another row's samples.  No atomics, nothing depends on the launch order: bit-identical from run to run.
+// The taps are (double)taps[j][n mod L] of the [K][L] device table for every L - at L = 1 column 0 is the tap row itself, the value
+// resample_kernel<true> keeps in LDS - so one code path serves both; a table of up to 4096 taps that fits beside the span is widened into LDS
+// once per tile (every L = 1 converter inside the span limit, and the small upsampling tables), a larger one is read from global memory as
+// resample_kernel<false> reads it.  What is this file's own is the addressing: source sample t lies at src + base + (t - origin) mod cap,
+// output n goes to dst + base + (n - origin) mod cap, and the row's converter, span of outputs [n0, n1) and T_known come from a DEVICE table.
+// One workgroup per tile of SR_TILE consecutive outputs of ONE row (grid.y = row), a tile never reads another row's samples.  No atomics,
+// nothing depends on the launch order: bit-identical from run to run.
 //
 // stream_carry_kernel moves the last `hist` emitted samples of every track of the hop's streams to the front of their rows, after the
 // conversion that read the old history has run (a launch of its own: the order of two launches on one stream is the whole synchronisation).
-#include "sepr_common.h"
+#include "sepr_polyphase.h"
 
 namespace sepr {
 namespace {
 constexpr int SR_TILE = 256;
-constexpr int SR_MAX_NC = 16;
 constexpr int SR_MAX_A = 65535;                  // grid.y
 constexpr int SR_COLS = 10;                      // include/sepr.h: the convert table's columns
 constexpr int SR_STEP_COLS = 6;                  // sepr_streambank_step's table, whose slot column the carry reads
-constexpr size_t SR_MAX_LDS = 64 * 1024;         // dynamic LDS of one workgroup: sepr_resample_fwd's limit
 
 constexpr long long SR_TAPS_LDS = 4096;          // a table of up to this many taps is staged in LDS beside the span, as doubles
 
-__host__ __device__ inline long long sr_span(int L, int M, int K) { return ((long long)(SR_TILE - 1) * M) / L + K + 1; }
 // a small table is read by every wave of the launch: from global memory its few cache lines are what the launch waits for
 __host__ __device__ inline bool sr_taps_in_lds(int L, int M, int K) {
   const long long n = (long long)K * L;
-  return n <= SR_TAPS_LDS && (size_t)(sr_span(L, M, K) + n) * sizeof(double) <= SR_MAX_LDS;
+  return n <= SR_TAPS_LDS && (size_t)(pp_span(SR_TILE, L, M, K) + n) * sizeof(double) <= PP_MAX_LDS;
 }
-
-struct SrConv {
-  const float* taps[SR_MAX_NC];                  // [K][L], column q = the tap row of phase (q M) mod L (resample.device_table)
-  int L[SR_MAX_NC], M[SR_MAX_NC], K[SR_MAX_NC];
-  int NC;
-};
 
 // (t - origin) mod cap in [0, cap), for any t and origin (the difference wraps in unsigned arithmetic instead of overflowing)
 __device__ __forceinline__ long long ring_at(long long t, long long origin, long long cap) {
@@ -49,7 +37,7 @@ __device__ __forceinline__ long long ring_at(long long t, long long origin, long
 
 __global__ __launch_bounds__(SR_TILE) void stream_convert_kernel(const float* __restrict__ src, long long src_elems, float* __restrict__ dst,
                                                                  long long dst_elems, const long long* __restrict__ table, long long nmax,
-                                                                 const SrConv cv) {
+                                                                 const ConvSet cv) {
   extern __shared__ double sr_lds[];
   const int a = blockIdx.y, tid = threadIdx.x;
   const long long* row = table + (long long)a * SR_COLS;
@@ -69,11 +57,12 @@ __global__ __launch_bounds__(SR_TILE) void stream_convert_kernel(const float* __
   const long long t0 = n0 + (long long)blockIdx.x * SR_TILE;
   if (t0 >= n1) return;
   if (scap < 1 || sbase < 0 || sbase > src_elems - scap || dcap < 1 || dbase < 0 || dbase > dst_elems - dcap) return;
-  const int Hh = (K - 2) / 2, span = (int)sr_span(L, M, K);
-  const long long b0 = (t0 * M) / L;
+  const int Hh = (K - 2) / 2, span = (int)pp_span(SR_TILE, L, M, K);
+  const long long b0 = pp_base(t0, L, M);
   double* xs = sr_lds;
   const long long g0 = b0 - Hh;
   const long long p0 = ring_at(g0, sorg, scap);
+  // its own staging loop, not pp_stage: with the ring position under the predicate the one-row launch measured 0.9 us longer (docs/HISTORY.md)
   for (int i = tid; i < span; i += SR_TILE) {
     const long long g = g0 + i;
     long long p = p0 + i;                                           // a ring at least a span long wraps at most once inside a tile
@@ -88,21 +77,17 @@ __global__ __launch_bounds__(SR_TILE) void stream_convert_kernel(const float* __
   __syncthreads();
   const long long n = t0 + tid;
   if (n >= n1) return;
-  const long long nm = n * M;                                       // 64-bit: passes 2^31 after minutes of audio
-  const long long b = nm / L;
-  const double* xp = xs + (int)(b - b0);                            // 0 <= b - b0 <= (SR_TILE - 1) M / L + 1
-  const int q = (int)(n % L);
-  double acc = 0.0;
+  const double* const xp[1] = {xs + (int)(pp_base(n, L, M) - b0)};  // n M in 64 bits; 0 <= b - b0 <= (SR_TILE - 1) M / L + 1
+  const int q = pp_phase(n, L);
+  double acc[1];
   if (staged) {                                                     // the same doubles, widened once per tile instead of once per use
-    const double* td = ts + q;
-#pragma unroll 8
-    for (int j = 0; j < K; ++j) acc = fma(td[j * L], xp[j], acc);
+    const double* const tq[1] = {ts + q};
+    pp_chain<1, 8>(tq, L, xp, K, acc);
   } else {
-    const float* tp = taps + q;
-#pragma unroll 8
-    for (int j = 0; j < K; ++j) acc = fma((double)tp[(long long)j * L], xp[j], acc);
+    const float* const tq[1] = {taps + q};
+    pp_chain<1, 8>(tq, (long long)L, xp, K, acc);
   }
-  dst[dbase + ring_at(n, dorg, dcap)] = (float)acc;
+  dst[dbase + ring_at(n, dorg, dcap)] = (float)acc[0];
 }
 
 // rows [slot][S] of `row_len` floats: [0, hist) <- [hist, 2 hist) for the slot of every row of the step table
@@ -123,26 +108,18 @@ extern "C" int sepr_streambank_convert(const float* src, long long src_elems, fl
                                        const int* conv_K, int NC, sepr_stream_t stream) {
   using namespace sepr;
   if (!src || !dst || !table || !conv_taps || !conv_L || !conv_M || !conv_K) return SEPR_EINVAL;
-  if (A < 1 || A > SR_MAX_A || NC < 1 || NC > SR_MAX_NC || src_elems < 1 || dst_elems < 1 || nmax < 1) return SEPR_EINVAL;
+  if (A < 1 || A > SR_MAX_A || src_elems < 1 || dst_elems < 1 || nmax < 1) return SEPR_EINVAL;
   if ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) % 4 != 0) return SEPR_EINVAL;
   if (reinterpret_cast<uintptr_t>(table) % 8 != 0) return SEPR_EINVAL;
-  SrConv cv;
+  // at least one converter, aligned tables, a ratio inside one tile's LDS (sepr_resample_fwd's limit); the unused entries repeat the last one
+  ConvSet cv;
+  if (!pp_fill(conv_taps, conv_L, conv_M, conv_K, NC, {SR_TILE, 1, 0, PP_MAX_LDS, true, true}, cv)) return SEPR_EINVAL;
   size_t lds = 0;
-  for (int k = 0; k < SR_MAX_NC; ++k) {
-    const int c = k < NC ? k : NC - 1;                              // the unused entries repeat the last one
-    if (!conv_taps[c] || reinterpret_cast<uintptr_t>(conv_taps[c]) % 4 != 0) return SEPR_EINVAL;
-    if (conv_L[c] < 1 || conv_M[c] < 1 || conv_K[c] < 2 || conv_K[c] % 2 != 0) return SEPR_EINVAL;
-    const long long span = sr_span(conv_L[c], conv_M[c], conv_K[c]);
-    // ratio beyond one tile's LDS: sepr_resample_fwd's limit, the tap row of L = 1 included
-    if (span > 0x7fffffffLL || (size_t)(span + (conv_L[c] == 1 ? conv_K[c] : 0)) * sizeof(double) > SR_MAX_LDS) return SEPR_EINVAL;
-    const size_t need = (size_t)(span + (sr_taps_in_lds(conv_L[c], conv_M[c], conv_K[c]) ? (long long)conv_K[c] * conv_L[c] : 0)) * sizeof(double);
+  for (int k = 0; k < NC; ++k) {
+    const long long tab = sr_taps_in_lds(cv.L[k], cv.M[k], cv.K[k]) ? (long long)cv.K[k] * cv.L[k] : 0;
+    const size_t need = (size_t)(pp_span(SR_TILE, cv.L[k], cv.M[k], cv.K[k]) + tab) * sizeof(double);
     lds = need > lds ? need : lds;
-    cv.taps[k] = conv_taps[c];
-    cv.L[k] = conv_L[c];
-    cv.M[k] = conv_M[c];
-    cv.K[k] = conv_K[c];
   }
-  cv.NC = NC;
   const long long tiles = (nmax + SR_TILE - 1) / SR_TILE;
   if (tiles > 0x7fffffffLL) return SEPR_EINVAL;
   hipStream_t st = static_cast<hipStream_t>(stream);

@@ -51,7 +51,6 @@ from .reverb import RirBank
 # (speed, RIR index or -1, taps) when it was given an RIR bank - the speed 100 unless it was given both (speed_reverb=True)
 Term = Union[Tuple[int, int, np.float32, np.float32], Tuple[int, int, np.float32, np.float32, int],
              Tuple[int, int, np.float32, np.float32, int, int, int]]
-MAX_CONVERTERS = 16                                     # converters one sepr_dynmix_speed_fwd call takes
 _ONE = np.float32(1.0)
 
 
@@ -527,12 +526,7 @@ def _converter_args(dev: torch.device, speeds: Sequence[int]):
     are built once per (device, speed) and stay on the device (``resample._table``), the host arrays once per (device, set)."""
     key = (str(dev), tuple(int(p) for p in speeds))
     if key not in _converters:
-        if len(key[1]) > MAX_CONVERTERS:
-            raise ValueError(f"{len(key[1])} distinct speeds: one launch takes {MAX_CONVERTERS} converters")
-        made = [R_._table(p, 100, dev) for p in key[1]]
-        NC = len(made)
-        _converters[key] = ((C.c_void_p * max(NC, 1))(*[t.data_ptr() for _, t in made]), (C.c_int * max(NC, 1))(*[p.L for p, _ in made]),
-                            (C.c_int * max(NC, 1))(*[p.M for p, _ in made]), (C.c_int * max(NC, 1))(*[p.K for p, _ in made]), NC)
+        _converters[key] = R_.converter_args([R_._table(p, 100, dev) for p in key[1]])
     return _converters[key]
 
 

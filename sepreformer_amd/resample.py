@@ -22,6 +22,8 @@ from . import lib as L_
 ZEROS = 64          # zero crossings of the sinc per side
 ROLLOFF = 0.945     # cut-off as a fraction of the lower Nyquist frequency
 BETA = 12.0         # Kaiser window parameter
+MAX_CONVERTERS = 16                     # converters one launch takes: sepr_dynmix_speed_fwd, sepr_streambank_convert (csrc/sepr_polyphase.h)
+SPAN_TILE, SPAN_BYTES = 256, 64 * 1024  # sepr_resample_fwd's and sepr_streambank_convert's tile of outputs and the LDS its input span must fit
 
 
 class Plan(NamedTuple):
@@ -32,17 +34,28 @@ class Plan(NamedTuple):
     taps: np.ndarray    # float32 [L][K]
 
 
-def plan(fs_in: int, fs_out: int) -> Plan:
-    """``(L, M, K, Hh, taps)`` of the converter ``fs_in -> fs_out``: ``taps[p][j] = rolloff s sinc(rolloff u) kaiser(u / Z)`` at
-    ``u = (p / L + Hh - j) s``, zero for ``|u| >= Z``; float64 arithmetic rounded once to float32."""
+def geometry(fs_in: int, fs_out: int) -> Tuple[int, int, int, int]:
+    """``(L, M, K, Hh)`` of the converter ``fs_in -> fs_out``: ``plan`` without the table."""
     fs_in, fs_out = int(fs_in), int(fs_out)
     if fs_in < 1 or fs_out < 1:
         raise ValueError(f"sampling rates must be positive, got {fs_in} -> {fs_out}")
     g = math.gcd(fs_in, fs_out)
     L, M = fs_out // g, fs_in // g
-    s = min(1.0, L / M)
     Hh = -((-ZEROS * max(L, M)) // L)               # ceil(Z / s) in integers: Z max(1, M / L)
-    K = 2 * Hh + 2
+    return L, M, 2 * Hh + 2, Hh
+
+
+def span_fits(L: int, M: int, K: int, tile: int = SPAN_TILE, lds_bytes: int = SPAN_BYTES) -> bool:
+    """Whether the input span of a tile of ``tile`` outputs, ``(tile - 1) M / L + K + 1`` doubles with the tap row of an ``L = 1``
+    converter beside it, fits ``lds_bytes``: the ratio limit of ``sepr_resample_fwd`` and ``sepr_streambank_convert``."""
+    return ((tile - 1) * M // L + K + 1 + (K if L == 1 else 0)) * 8 <= lds_bytes
+
+
+def plan(fs_in: int, fs_out: int) -> Plan:
+    """``(L, M, K, Hh, taps)`` of the converter ``fs_in -> fs_out``: ``taps[p][j] = rolloff s sinc(rolloff u) kaiser(u / Z)`` at
+    ``u = (p / L + Hh - j) s``, zero for ``|u| >= Z``; float64 arithmetic rounded once to float32."""
+    L, M, K, Hh = geometry(fs_in, fs_out)
+    s = min(1.0, L / M)
     p = np.arange(L, dtype=np.float64)[:, None]
     j = np.arange(K, dtype=np.float64)[None, :]
     u = (p / L + Hh - j) * s
@@ -59,11 +72,7 @@ def plan_oct(fs_in: int, fs_out: int = 10000) -> Plan:
     ``L``.  Output ``n`` at ``n M = b L + p`` is ``sum_r L h[p + L r] x[b - r]``, so ``taps[p][j] = L h[p + L (Hh - j)]`` with
     ``Hh = floor(Lh / L)`` and ``K = 2 Hh + 2`` (zero where ``|p + L (Hh - j)| > Lh``); float64 arithmetic rounded once to float32.
     ``sepr_resample_fwd`` runs it like any other plan."""
-    fs_in, fs_out = int(fs_in), int(fs_out)
-    if fs_in < 1 or fs_out < 1:
-        raise ValueError(f"sampling rates must be positive, got {fs_in} -> {fs_out}")
-    g = math.gcd(fs_in, fs_out)
-    L, M = fs_out // g, fs_in // g
+    L, M, _, _ = geometry(fs_in, fs_out)                # the ratio; the half length is this filter's own
     fc = 1.0 / (2 * max(L, M))
     Lh = int(math.ceil((60 - 8) / (28.714 * fc / 10)))
     t = np.arange(-Lh, Lh + 1, dtype=np.float64)
@@ -87,6 +96,16 @@ def device_table(p: Plan) -> np.ndarray:
     reads column ``n mod L``, so consecutive lanes read consecutive floats."""
     q = (np.arange(p.L, dtype=np.int64) * p.M) % p.L
     return np.ascontiguousarray(p.taps[q].T)
+
+
+def converter_args(tables: Sequence[Tuple[Plan, torch.Tensor]]):
+    """``(conv_taps, conv_L, conv_M, conv_K, NC)`` of a launch that takes a converter set (include/sepr.h) from ``(plan, device table)``
+    pairs: ctypes arrays, of one element when the set is empty."""
+    NC = len(tables)
+    if NC > MAX_CONVERTERS:
+        raise ValueError(f"{NC} converters: one launch takes {MAX_CONVERTERS}")
+    ints = [(C.c_int * max(NC, 1))(*[getattr(p, f) for p, _ in tables]) for f in ("L", "M", "K")]
+    return ((C.c_void_p * max(NC, 1))(*[t.data_ptr() for _, t in tables]), *ints, NC)
 
 
 _tables: Dict[Tuple[int, int, str, bool], Tuple[Plan, torch.Tensor]] = {}

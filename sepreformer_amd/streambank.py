@@ -26,7 +26,6 @@ Out of scope: changing a stream's rate after ``open``, more than one device, thr
 """
 from __future__ import annotations
 
-import math
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -34,28 +33,10 @@ import torch
 
 from . import lib as L
 from .longform import _as_list, check_geometry
+from .resample import MAX_CONVERTERS, _table, converter_args, geometry, out_len, span_fits   # the converter's one definition
 
 STEP_COLS, GATHER_COLS = 6, 3          # include/sepr.h: slot, k, n_emit, has_window, out offset, track stride | base, start, received
 CONVERT_COLS = 10                      # conv, n0, n1, T_known, src base, src origin, src cap, dst base, dst origin, dst cap
-MAX_CONVERTERS = 16                    # converter descriptions one sepr_streambank_convert launch takes
-SPAN_TILE, SPAN_BYTES = 256, 64 * 1024   # the convert kernel's tile and its LDS limit (sepr_resample_fwd's)
-
-
-def geometry(fs_in: int, fs_out: int) -> Tuple[int, int, int, int]:
-    """``(L, M, K, Hh)`` of the converter ``fs_in -> fs_out`` (``resample.plan`` without the table)."""
-    fs_in, fs_out = int(fs_in), int(fs_out)
-    if fs_in < 1 or fs_out < 1:
-        raise ValueError(f"sampling rates must be positive, got {fs_in} -> {fs_out}")
-    g = math.gcd(fs_in, fs_out)
-    L, M = fs_out // g, fs_in // g
-    Hh = -((-64 * max(L, M)) // L)
-    return L, M, 2 * Hh + 2, Hh
-
-
-def out_len(T: int, L: int, M: int) -> int:
-    """``ceil(T L / M)``"""
-    return -((-int(T) * L) // M)
-
 
 def ready_count(received: int, closed: bool, L: int, M: int, Hh: int) -> int:
     """How many outputs of a converter ``L / M`` with half length ``Hh`` may be computed from the first ``received`` input samples.  Output
@@ -170,7 +151,7 @@ class SlotTable:
         if other > self.max_rate:
             raise ValueError(f"{other} Hz is above this bank's max_rate of {self.max_rate} Hz")
         Lr, Mr, K, _ = geometry(fs_a, fs_b)
-        if ((SPAN_TILE - 1) * Mr // Lr + K + 1 + (K if Lr == 1 else 0)) * 8 > SPAN_BYTES:      # sepr_resample_fwd's limit
+        if not span_fits(Lr, Mr, K):
             raise RuntimeError(f"{fs_a} -> {fs_b} Hz: the converter's tile span exceeds the kernel's LDS: " + L._ERR[L.SEPR_EINVAL])
         if out_side and K > self.H:
             raise ValueError(f"{fs_a} -> {fs_b} Hz needs the last {K} emitted samples, more than one hop of {self.H}")
@@ -412,12 +393,8 @@ class StreamBank:
 
     def _converters(self):
         """The host arrays ``sepr_streambank_convert`` takes, rebuilt when the bank's converters changed."""
-        from .resample import _table
         if self._conv_epoch != self.table.conv_epoch:
-            tabs = [_table(a, b, self.dev) for a, b in self.table.convs]
-            NC = len(tabs)
-            self._conv_args = ((L._fp * NC)(*[t.data_ptr() for _, t in tabs]), (L._i * NC)(*[p.L for p, _ in tabs]),
-                               (L._i * NC)(*[p.M for p, _ in tabs]), (L._i * NC)(*[p.K for p, _ in tabs]), NC)
+            self._conv_args = converter_args([_table(a, b, self.dev) for a, b in self.table.convs])
             self._conv_epoch = self.table.conv_epoch
         return self._conv_args
 
