@@ -11,8 +11,9 @@ points at its slice.  What is built per projection ``y = norm_affine(x) . W^T + 
 * exact-f32 mode keeps fp32 ``[N,K]`` matrices, bf16x3 mode the ``pack_x3`` fragments (hi/lo bf16 planes); ``bf16`` mode
   (plain bf16 operands, one MFMA per product, fp32 accumulate and fp32 master weights: the training precision BASELINE
   configs[4] names) uses the same fragments with ``sepr_lin.planes = 1`` (the kernels then read the hi plane only);
-* GCFN blocks additionally get the fused kernel's weight forms (``pack.pack_gcfn_fused_batched``) when F is 64 or 128: their
-  train forward is then one launch that keeps only the LayerNorm statistics (``include/sepr.h`` sepr_gcfn_tw).
+* GCFN blocks additionally get the fused kernel's weight forms (``sepr_train_pack_gcfn_fused``, one launch for all blocks; the form
+  is ``pack.pack_gcfn_fused``'s) when F is 64 or 128: their train forward is then one launch that keeps only the LayerNorm statistics
+  (``include/sepr.h`` sepr_gcfn_tw).
 
 The raw parameters ride along for the gradient finishers (read IN PLACE: every parameter is a contiguous fp32 tensor), and a ``*Grad`` struct per block points into one flat fp32
 gradient buffer laid out exactly like the parameters (``GradBuffer``).
@@ -232,8 +233,8 @@ class TrainPack:
         self.fused_gcfn = (P in ("bf16x3", "bf16") and F in (64, 128) and os.environ.get("SEPR_TRAIN_FUSE_GCFN", "1") != "0")
         fw1 = fw2 = None
         if self.fused_gcfn:
-            # the fused kernel's forms of all blocks in ONE launch, from the parameters in place (sepr_train_pack_gcfn_fused; the batched torch
-            # formulation pack.pack_gcfn_fused_batched remains the inference packer's and the device test's reference)
+            # the fused kernel's forms of all blocks in ONE launch, from the parameters in place (sepr_train_pack_gcfn_fused; the torch
+            # statement of the form is pack.pack_gcfn_fused: the inference packer, and as pack_gcfn_fused_batched the device test's reference)
             G_, KS_, nch_ = len(gcfn_p), F // 32, 3 * F // 32
             fw1 = torch.empty(G_, nch_ * (4 * KS_ * 2048 + 4096), dtype=torch.uint8, device=dev)
             fw2 = torch.empty(G_, nch_, F // 16, 2, 64, 8, dtype=torch.bfloat16, device=dev)
