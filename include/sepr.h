@@ -889,6 +889,20 @@ int sepr_adamw_step(const sepr_adamw_tables* t, const float* grads, long long gr
 int sepr_adamw_step_guarded(const sepr_adamw_tables* t, const float* grads, long long grads_numel, float* exp_avg, float* exp_avg_sq,
                             double* step, const float* lr, double beta1, double beta2, double eps, double weight_decay, double max_norm,
                             float* scal, void* ws, size_t ws_bytes, sepr_stream_t stream);
+/* The guarded step that also keeps an exponential moving average (EMA) of the parameters: the same three launches and the same skip
+ * rule.  ema: a flat fp32 buffer of the caller, laid out by state_off like the two moments, 16-byte aligned.  With t the step counter
+ * after its increment, the prepare kernel forms in double d_t = ema_decay when ema_warmup <= 0, else
+ * d_t = min(ema_decay, (1 + t) / (ema_warmup + t)), and writes scal[6] = (float)(1 - d_t).  The update kernel stores the new parameter p
+ * and then, from the same register, e = e + scal[6] * (p - e): fp32, three rounded operations, no FMA.  Parameters, moments, the
+ * counter and scal[0..5] are sepr_adamw_step_guarded's, bit for bit.  A skipped step writes neither ema nor scal[6].
+ * SEPR_EINVAL for a null or misaligned ema, or an ema_decay outside [0, 1). */
+int sepr_adamw_step_ema(const sepr_adamw_tables* t, const float* grads, long long grads_numel, float* exp_avg, float* exp_avg_sq,
+                        double* step, const float* lr, double beta1, double beta2, double eps, double weight_decay, double max_norm,
+                        float* ema, double ema_decay, double ema_warmup, float* scal, void* ws, size_t ws_bytes, sepr_stream_t stream);
+/* One launch over the same block table: every parameter tensor trades places, bitwise, with its state_off slot of `shadow` (flat
+ * fp32, 16-byte aligned; an EMA buffer, for instance): float4 where four elements remain, scalars in the tail.  Twice is the
+ * identity.  grad_off is not read.  The caller re-packs whatever it derived from the parameters (Model.invalidate_packed). */
+int sepr_adamw_swap(const sepr_adamw_tables* t, float* shadow, sepr_stream_t stream);
 
 /* ---- run ledger: what a training loop needs to know about its steps, kept on the device ---------------------------------------
  * One launch, one thread, plain stores, fixed order: fold one step into `ledger` (float64, zeroed by the caller at the start of

@@ -5,8 +5,11 @@
 //   opt_adamw_kernel   one block per 1 024 elements of one tensor (block table), decoupled weight decay + Adam update
 // sepr_adamw_step_guarded is the same three launches with one difference: a non-finite total norm skips the step (scal[5] = 1, the
 // counter, parameters and moments untouched) instead of poisoning the weights; with a finite norm its arithmetic is sepr_adamw_step's.
-// The prepare and the update kernel are templates on the guard: sepr_adamw_step launches the <false> instantiations, whose code is what
-// the two kernels compiled to before the guard existed.
+// The prepare and the update kernel are templates on the guard: sepr_adamw_step launches the <false, false> instantiations, whose code is
+// what the two kernels compiled to before the guard existed.
+// sepr_adamw_step_ema is the guarded step that also keeps an exponential moving average of the parameters (the second template
+// argument): the prepare kernel leaves 1 - d_t in scal[6], the update kernel folds the parameter value it has just stored into the
+// flat `ema` buffer (36 bytes per parameter instead of 28).  sepr_adamw_swap exchanges the parameters with such a buffer, bitwise.
 // run_ledger_kernel folds a step's loss parts and optimizer scalars into the float64 run ledger the training loop reads once per
 // log interval (no per-step host synchronisation).
 // torch's route is one multi_tensor_apply launch per ~36 tensors (37 launches for the update, 12 for the norms, 37 for the clip
@@ -44,13 +47,14 @@ __global__ __launch_bounds__(OPT_TPB) void opt_sqsum_kernel(const float* __restr
 }
 
 // scal[0] = total norm, [1] = clip coefficient, [2] = lr / bias_correction1, [3] = sqrt(bias_correction2), [4] = lr * weight_decay,
-// [5] (guard only) = 1 when the step is skipped for a non-finite total norm, else 0
+// [5] (guard only) = 1 when the step is skipped for a non-finite total norm, else 0, [6] (EMA only) = 1 - d_t, the weight of the new
+// parameter value in the moving average of this step
 __device__ __forceinline__ bool opt_nonfinite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
 
-template <bool GUARD>
+template <bool GUARD, bool EMA>
 __global__ __launch_bounds__(OPT_TPB) void opt_prep_kernel(const double* __restrict__ part, int with_norm, float max_norm, const float* __restrict__ lr,
                                                           double beta1, double beta2, float weight_decay, double* __restrict__ step,
-                                                          float* __restrict__ scal) {
+                                                          float* __restrict__ scal, double ema_decay, double ema_warmup) {
   __shared__ double sh[OPT_TPB];
   double acc = 0.0;
   if (with_norm)
@@ -88,6 +92,15 @@ __global__ __launch_bounds__(OPT_TPB) void opt_prep_kernel(const double* __restr
   scal[2] = (float)((double)l / bc1);
   scal[3] = (float)sqrt(bc2);
   scal[4] = l * weight_decay;
+  if (EMA) {
+    // the decay of step t: ema_decay, ramped in as (1 + t) / (warmup + t) while that is smaller (trainer.ema_decay_at states it on the host)
+    double d = ema_decay;
+    if (ema_warmup > 0.0) {
+      const double r = (1.0 + t) / (ema_warmup + t);
+      d = r < d ? r : d;
+    }
+    scal[6] = (float)(1.0 - d);
+  }
 }
 
 struct OptTables {
@@ -98,10 +111,10 @@ struct OptTables {
   const int2* blocks;             // [nblocks] (tensor, first element)
 };
 
-template <bool GUARD>
+template <bool GUARD, bool EMA>
 __global__ __launch_bounds__(OPT_TPB) void opt_adamw_kernel(const OptTables t, const float* __restrict__ grads, float* __restrict__ exp_avg,
                                                            float* __restrict__ exp_avg_sq, const float* __restrict__ scal, float omb1,
-                                                           float beta2, float omb2, float eps) {
+                                                           float beta2, float omb2, float eps, float* __restrict__ ema) {
 #pragma clang fp contract(off)
   if (GUARD && scal[5] != 0.0f) return;                       // skipped step: parameters and moments stay as they are
   const int2 b = t.blocks[blockIdx.x];
@@ -143,6 +156,46 @@ __global__ __launch_bounds__(OPT_TPB) void opt_adamw_kernel(const OptTables t, c
   } else {
     for (int e = 0; e < cnt; ++e) { p[e] = pv[e]; exp_avg[so + e] = mv[e]; exp_avg_sq[so + e] = vv[e]; }
   }
+  if (EMA) {
+    // e += (1 - d_t) (p - e) with p the value stored above, from its register: three rounded operations (no contraction in this kernel)
+    const float w = scal[6];
+    float* __restrict__ ea = ema + so;
+    if (cnt == 4) {
+      float4 e4 = ld4(ea);
+      e4.x = e4.x + w * (pv[0] - e4.x);
+      e4.y = e4.y + w * (pv[1] - e4.y);
+      e4.z = e4.z + w * (pv[2] - e4.z);
+      e4.w = e4.w + w * (pv[3] - e4.w);
+      st4(ea, e4);
+    } else {
+      for (int e = 0; e < cnt; ++e) {
+        const float ev = ea[e];
+        ea[e] = ev + w * (pv[e] - ev);
+      }
+    }
+  }
+}
+
+// sepr_adamw_swap: one block per 1 024 elements of one tensor, over the update's block table; parameter and shadow slot trade places
+__global__ __launch_bounds__(OPT_TPB) void opt_swap_kernel(const OptTables t, float* __restrict__ shadow) {
+  const int2 b = t.blocks[blockIdx.x];
+  const int ti = b.x;
+  const int n = t.numel[ti];
+  const int e0 = b.y + 4 * threadIdx.x;
+  if (e0 >= n) return;
+  float* __restrict__ p = t.params[ti] + e0;
+  float* __restrict__ q = shadow + t.state_off[ti] + e0;
+  if (n - e0 >= 4) {
+    const float4 a = ld4(p), c = ld4(q);
+    st4(p, c);
+    st4(q, a);
+  } else {
+    for (int e = 0; e < n - e0; ++e) {
+      const float a = p[e];
+      p[e] = q[e];
+      q[e] = a;
+    }
+  }
 }
 
 // Run ledger (include/sepr.h SEPR_LEDGER_*): one thread folds one step into float64 slots, in fixed order, with plain stores.
@@ -178,31 +231,40 @@ extern "C" size_t sepr_adamw_workspace(void) { return OPT_PARTS * sizeof(double)
 
 static int adamw_step_impl(const sepr_adamw_tables* t, const float* grads, long long grads_numel, float* exp_avg, float* exp_avg_sq,
                            double* step, const float* lr, double beta1, double beta2, double eps, double weight_decay, double max_norm,
-                           float* scal, void* ws, size_t ws_bytes, sepr_stream_t stream, bool guard) {
+                           float* scal, void* ws, size_t ws_bytes, sepr_stream_t stream, bool guard, float* ema = nullptr,
+                           double ema_decay = 0.0, double ema_warmup = 0.0) {
   if (!t || !t->params || !t->grad_off || !t->state_off || !t->numel || !t->blocks || t->nblocks <= 0 || !grads || grads_numel <= 0 ||
       !exp_avg || !exp_avg_sq || !step || !lr || !scal)
     return SEPR_EINVAL;
   if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0) || !(weight_decay >= 0.0)) return SEPR_EINVAL;
   if ((reinterpret_cast<uintptr_t>(grads) & 15) || (reinterpret_cast<uintptr_t>(exp_avg) & 15) || (reinterpret_cast<uintptr_t>(exp_avg_sq) & 15))
     return SEPR_EINVAL;
+  if (ema && (!guard || (reinterpret_cast<uintptr_t>(ema) & 15) || !(ema_decay >= 0.0 && ema_decay < 1.0))) return SEPR_EINVAL;
   const int with_norm = (guard || max_norm > 0.0) ? 1 : 0;      // the guard judges the total norm, so it always runs the norm pass
   if (with_norm && (!ws || ws_bytes < sepr_adamw_workspace())) return SEPR_EWORKSPACE;
   hipStream_t s = static_cast<hipStream_t>(stream);
   double* part = static_cast<double*>(ws);
   if (with_norm) hipLaunchKernelGGL(opt_sqsum_kernel, dim3(OPT_PARTS), dim3(OPT_TPB), 0, s, grads, grads_numel, part);
-  if (guard)
-    hipLaunchKernelGGL(opt_prep_kernel<true>, dim3(1), dim3(OPT_TPB), 0, s, part, with_norm, (float)max_norm, lr, beta1, beta2, (float)weight_decay, step, scal);
+  const float wd = (float)weight_decay;
+  if (ema)
+    hipLaunchKernelGGL((opt_prep_kernel<true, true>), dim3(1), dim3(OPT_TPB), 0, s, part, with_norm, (float)max_norm, lr, beta1, beta2, wd, step, scal, ema_decay, ema_warmup);
+  else if (guard)
+    hipLaunchKernelGGL((opt_prep_kernel<true, false>), dim3(1), dim3(OPT_TPB), 0, s, part, with_norm, (float)max_norm, lr, beta1, beta2, wd, step, scal, 0.0, 0.0);
   else
-    hipLaunchKernelGGL(opt_prep_kernel<false>, dim3(1), dim3(OPT_TPB), 0, s, part, with_norm, (float)max_norm, lr, beta1, beta2, (float)weight_decay, step, scal);
+    hipLaunchKernelGGL((opt_prep_kernel<false, false>), dim3(1), dim3(OPT_TPB), 0, s, part, with_norm, (float)max_norm, lr, beta1, beta2, wd, step, scal, 0.0, 0.0);
   OptTables k;
   k.params = t->params; k.grad_off = t->grad_off; k.state_off = t->state_off; k.numel = t->numel;
   k.blocks = reinterpret_cast<const int2*>(t->blocks);
-  if (guard)
-    hipLaunchKernelGGL(opt_adamw_kernel<true>, dim3(t->nblocks), dim3(OPT_TPB), 0, s, k, grads, exp_avg, exp_avg_sq, scal, (float)(1.0 - beta1),
-                       (float)beta2, (float)(1.0 - beta2), (float)eps);
+  float* const no_ema = nullptr;
+  if (ema)
+    hipLaunchKernelGGL((opt_adamw_kernel<true, true>), dim3(t->nblocks), dim3(OPT_TPB), 0, s, k, grads, exp_avg, exp_avg_sq, scal, (float)(1.0 - beta1),
+                       (float)beta2, (float)(1.0 - beta2), (float)eps, ema);
+  else if (guard)
+    hipLaunchKernelGGL((opt_adamw_kernel<true, false>), dim3(t->nblocks), dim3(OPT_TPB), 0, s, k, grads, exp_avg, exp_avg_sq, scal, (float)(1.0 - beta1),
+                       (float)beta2, (float)(1.0 - beta2), (float)eps, no_ema);
   else
-    hipLaunchKernelGGL(opt_adamw_kernel<false>, dim3(t->nblocks), dim3(OPT_TPB), 0, s, k, grads, exp_avg, exp_avg_sq, scal, (float)(1.0 - beta1),
-                       (float)beta2, (float)(1.0 - beta2), (float)eps);
+    hipLaunchKernelGGL((opt_adamw_kernel<false, false>), dim3(t->nblocks), dim3(OPT_TPB), 0, s, k, grads, exp_avg, exp_avg_sq, scal, (float)(1.0 - beta1),
+                       (float)beta2, (float)(1.0 - beta2), (float)eps, no_ema);
   SEPR_CHECK_LAUNCH("adamw step kernels");
   return SEPR_OK;
 }
@@ -217,6 +279,25 @@ extern "C" int sepr_adamw_step_guarded(const sepr_adamw_tables* t, const float* 
                                        double* step, const float* lr, double beta1, double beta2, double eps, double weight_decay, double max_norm,
                                        float* scal, void* ws, size_t ws_bytes, sepr_stream_t stream) {
   return adamw_step_impl(t, grads, grads_numel, exp_avg, exp_avg_sq, step, lr, beta1, beta2, eps, weight_decay, max_norm, scal, ws, ws_bytes, stream, true);
+}
+
+extern "C" int sepr_adamw_step_ema(const sepr_adamw_tables* t, const float* grads, long long grads_numel, float* exp_avg, float* exp_avg_sq,
+                                   double* step, const float* lr, double beta1, double beta2, double eps, double weight_decay, double max_norm,
+                                   float* ema, double ema_decay, double ema_warmup, float* scal, void* ws, size_t ws_bytes, sepr_stream_t stream) {
+  if (!ema) return SEPR_EINVAL;
+  return adamw_step_impl(t, grads, grads_numel, exp_avg, exp_avg_sq, step, lr, beta1, beta2, eps, weight_decay, max_norm, scal, ws, ws_bytes, stream, true,
+                         ema, ema_decay, ema_warmup);
+}
+
+extern "C" int sepr_adamw_swap(const sepr_adamw_tables* t, float* shadow, sepr_stream_t stream) {
+  if (!t || !t->params || !t->state_off || !t->numel || !t->blocks || t->nblocks <= 0 || !shadow) return SEPR_EINVAL;
+  if (reinterpret_cast<uintptr_t>(shadow) & 15) return SEPR_EINVAL;
+  OptTables k;
+  k.params = t->params; k.grad_off = t->grad_off; k.state_off = t->state_off; k.numel = t->numel;
+  k.blocks = reinterpret_cast<const int2*>(t->blocks);
+  hipLaunchKernelGGL(opt_swap_kernel, dim3(t->nblocks), dim3(OPT_TPB), 0, static_cast<hipStream_t>(stream), k, shadow);
+  SEPR_CHECK_LAUNCH("adamw swap kernel");
+  return SEPR_OK;
 }
 
 extern "C" int sepr_run_ledger_doubles(int nparts) { return nparts >= 1 && nparts <= SEPR_LEDGER_MAX_PARTS ? SEPR_LEDGER_PART_SUM + 2 * nparts : 0; }

@@ -266,9 +266,15 @@ def evaluate_utterances_all(model, utterances: Iterable[Tuple[torch.Tensor, Sequ
 test_utterances.__test__ = False      # not a pytest test
 
 
-def load_checkpoint_weights(model, path: str):
-    """The weights of a checkpoint - the reference's, or one ``trainer.Trainer`` wrote (the same five keys) - or of a bare state dict."""
+def load_checkpoint_weights(model, path: str, ema: bool = False):
+    """The weights of a checkpoint - the reference's, or one ``trainer.Trainer`` wrote (the same five keys) - or of a bare state dict.
+    ``ema=True``: the averaged weights a ``Trainer(ema_decay=...)`` run saved beside them (``ema_state_dict``: the same keys, parameters
+    from the average, buffers from the model); a file without them is a ``ValueError``."""
     ck = torch.load(path, map_location="cpu")
+    if ema:
+        if "ema_state_dict" not in ck:
+            raise ValueError(f"{path} holds no ema_state_dict (it was written without a weight EMA): load it without ema")
+        return model.load_state_dict(ck["ema_state_dict"], strict=False)
     return model.load_state_dict(ck.get("model_state_dict", ck), strict=False)      # utils/util_engine.py:43
 
 
@@ -281,6 +287,7 @@ def _main() -> None:
     ap.add_argument("wav", nargs="+")
     ap.add_argument("--model", default="SepReformer_Base_WSJ0", choices=sorted(VARIANTS))
     ap.add_argument("--checkpoint", default=None, help="reference checkpoint (.pth with model_state_dict); default: synthetic weights")
+    ap.add_argument("--ema", action="store_true", help="with --checkpoint: load the averaged weights (ema_state_dict) a run with a weight EMA saved")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--chunk-seconds", type=float, default=None,
                     help="long-form mode: overlapping windows of this length, stitched on the device (default: one whole-file forward)")
@@ -297,8 +304,15 @@ def _main() -> None:
     args = ap.parse_args()
     out_rate = args.out_rate if args.out_rate in (None, "input") else int(args.out_rate)
     model = Model.from_config(VARIANTS[args.model], init_seed=0)
+    if args.ema and not args.checkpoint:
+        ap.error("--ema needs --checkpoint")
     if args.checkpoint:
-        load_checkpoint_weights(model, args.checkpoint)
+        try:
+            load_checkpoint_weights(model, args.checkpoint, ema=args.ema)
+        except ValueError as e:
+            if not args.ema:
+                raise
+            raise SystemExit(str(e))                     # a file without the averaged weights: the message, status 1
     else:
         model.load_synthetic_(0)
     model = model.eval().to(args.device)

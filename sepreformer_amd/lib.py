@@ -219,6 +219,8 @@ SIGNATURES = {
     "sepr_adamw_workspace": (_sz, []),
     "sepr_adamw_step": (_i, [C.POINTER(AdamWTables), _fp, _ll, _fp, _fp, _fp, _fp, _d, _d, _d, _d, _d, _fp, _fp, _sz, _fp]),
     "sepr_adamw_step_guarded": (_i, [C.POINTER(AdamWTables), _fp, _ll, _fp, _fp, _fp, _fp, _d, _d, _d, _d, _d, _fp, _fp, _sz, _fp]),
+    "sepr_adamw_step_ema": (_i, [C.POINTER(AdamWTables), _fp, _ll, _fp, _fp, _fp, _fp, _d, _d, _d, _d, _d, _fp, _d, _d, _fp, _fp, _sz, _fp]),
+    "sepr_adamw_swap": (_i, [C.POINTER(AdamWTables), _fp, _fp]),
     "sepr_run_ledger_doubles": (_i, [_i]),
     "sepr_run_ledger_update": (_i, [_fp, _i, _fp, _fp, _i, _fp]),
     "sepr_prof_start": (_i, [_i, _i]),

@@ -14,11 +14,19 @@ gradients are NOT scaled in place (the clip coefficient is applied inside the up
 a scheduler: the value is mirrored into a device scalar before each step, so a captured step (``train_step.CapturedTrainStep``)
 picks it up without a re-capture.  State (``exp_avg`` / ``exp_avg_sq`` / ``step``) is exposed per parameter as views of the flat
 buffers, so ``state_dict()`` has ``torch.optim.AdamW``'s layout.  No CPU path.
+
+``ema_decay=d`` (with ``skip_nonfinite=True``) keeps an exponential moving average of the parameters inside the update launch
+(``sepr_adamw_step_ema``): the kernel folds the parameter value it has just stored into a flat fp32 buffer,
+``e += (1 - d_t) (p - e)`` with ``d_t = min(d, (1 + t) / (ema_warmup + t))``.  ``averaged()`` exchanges parameters and averages in
+place (``sepr_adamw_swap``) for the length of a ``with`` block, so every inference path runs on the averaged weights without a second
+model; ``ema_state_dict()`` / ``load_ema_state_dict()`` carry the buffer under the model's ``state_dict`` names.  BatchNorm running
+statistics are buffers, not parameters: the averaged model uses the current ones.  ``state_dict()`` does not mention the EMA.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
-from typing import Optional
+from typing import Dict, Optional
 
 import torch
 
@@ -29,7 +37,13 @@ class FlatAdamW(torch.optim.Optimizer):
     fused_clip = True          # train_step.CapturedTrainStep: step(max_norm=...) does the clipping itself
 
     def __init__(self, model, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
-                 skip_nonfinite: bool = False):
+                 skip_nonfinite: bool = False, ema_decay: Optional[float] = None, ema_warmup: float = 10.0):
+        if ema_decay is not None:
+            # the EMA entry is the guarded step: an average that has taken in one poisoned iterate never recovers
+            if not skip_nonfinite:
+                raise ValueError("FlatAdamW: ema_decay needs skip_nonfinite=True (the EMA is kept by the guarded step)")
+            if not 0.0 <= float(ema_decay) < 1.0:
+                raise ValueError("FlatAdamW: ema_decay must lie in [0, 1)")
         params = [p for p in model.parameters() if p.requires_grad]
         if not params:
             raise ValueError("no trainable parameters")
@@ -79,6 +93,14 @@ class FlatAdamW(torch.optim.Optimizer):
         self._goff_host: Optional[list] = None
         self._ptrs = [p.data_ptr() for p in params]
         self._expose_state()
+        # weight EMA: a third flat buffer in the moments' layout, folded by the update launch itself
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_warmup = float(ema_warmup)
+        self._ema: Optional[torch.Tensor] = None
+        self._averaged = False                                # inside averaged(): the parameters hold the EMA, the buffer the raw weights
+        if self.ema_decay is not None:
+            self._ema = torch.zeros(off, dtype=torch.float32, device=dev)
+            self.reset_ema()
 
     # ---- torch.optim.Optimizer plumbing ---------------------------------------------------------------------------------
     def _expose_state(self):
@@ -169,26 +191,103 @@ class FlatAdamW(torch.optim.Optimizer):
             raise ValueError("FlatAdamW does not take a closure")
         if [p.data_ptr() for p in (self._params[0], self._params[-1])] != [self._ptrs[0], self._ptrs[-1]]:
             raise RuntimeError("FlatAdamW: the parameters moved (model.to(...) after the optimizer was built); build a new optimizer")
+        if self._averaged:
+            raise RuntimeError("FlatAdamW.step inside averaged(): the parameters hold the averaged weights there, not the trajectory")
         flat = self._grad_base()
         g = self.param_groups[0]
         if not torch.cuda.is_current_stream_capturing():
             self.refresh()
-        t = L.AdamWTables(params=self._t_params.data_ptr(), grad_off=self._t_goff.data_ptr(), state_off=self._t_soff.data_ptr(),
-                          numel=self._t_numel.data_ptr(), blocks=self._t_blocks.data_ptr(), ntensors=len(self._params),
-                          nblocks=self._nblocks)
+        t = self._tables()
         with torch.cuda.device(self._dev):
             st = torch.cuda.current_stream(self._dev).cuda_stream
-            L.check(self._entry(C.byref(t), flat.data_ptr(), flat.numel(), self._exp_avg.data_ptr(), self._exp_avg_sq.data_ptr(),
-                                self._step.data_ptr(), self._lr.data_ptr(), float(g["betas"][0]), float(g["betas"][1]),
-                                float(g["eps"]), float(g["weight_decay"]), float(max_norm) if max_norm else 0.0,
-                                self._scal.data_ptr(), self._ws.data_ptr(), self._ws.numel(), st),
-                    "sepr_adamw_step_guarded" if self.skip_nonfinite else "sepr_adamw_step")
+            head = (C.byref(t), flat.data_ptr(), flat.numel(), self._exp_avg.data_ptr(), self._exp_avg_sq.data_ptr(), self._step.data_ptr(),
+                    self._lr.data_ptr(), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
+                    float(max_norm) if max_norm else 0.0)
+            tail = (self._scal.data_ptr(), self._ws.data_ptr(), self._ws.numel(), st)
+            if self._ema is not None:
+                L.check(self._lib.sepr_adamw_step_ema(*head, self._ema.data_ptr(), self.ema_decay, self.ema_warmup, *tail), "sepr_adamw_step_ema")
+            else:
+                L.check(self._entry(*head, *tail), "sepr_adamw_step_guarded" if self.skip_nonfinite else "sepr_adamw_step")
             if self._ledger is not None:
                 # here and nowhere else: an eager step and a captured one (the launch is then part of the optimizer graph) both pass
                 # through this line, so the ledger sees every optimizer step exactly once
                 L.check(self._lib.sepr_run_ledger_update(self._parts.data_ptr(), self._parts.numel(), self._scal.data_ptr(),
                                                          self._ledger.data_ptr(), self._ledger.numel(), st), "sepr_run_ledger_update")
         return self._scal[0] if max_norm else None
+
+    def _tables(self) -> L.AdamWTables:
+        goff = self._t_goff if self._t_goff is not None else self._t_soff      # sepr_adamw_swap does not read the gradient offsets
+        return L.AdamWTables(params=self._t_params.data_ptr(), grad_off=goff.data_ptr(), state_off=self._t_soff.data_ptr(),
+                             numel=self._t_numel.data_ptr(), blocks=self._t_blocks.data_ptr(), ntensors=len(self._params),
+                             nblocks=self._nblocks)
+
+    # ---- the weight EMA ------------------------------------------------------------------------------------------------------
+    def _need_ema(self) -> torch.Tensor:
+        if self._ema is None:
+            raise RuntimeError("FlatAdamW was built without ema_decay: there is no averaged copy of the weights")
+        return self._ema
+
+    def _names(self) -> Dict[int, str]:
+        return {id(p): n for n, p in self._model.named_parameters()}
+
+    @torch.no_grad()
+    def reset_ema(self) -> None:
+        """The averages start (again) at the current parameters."""
+        ema = self._need_ema()
+        if self._averaged:
+            raise RuntimeError("FlatAdamW.reset_ema inside averaged()")
+        for p, so in zip(self._params, self._soff):
+            ema[so:so + p.numel()].copy_(p.detach().reshape(-1))
+
+    def ema_state_dict(self) -> Dict[str, torch.Tensor]:
+        """``{parameter name: compact CPU copy of its average}`` under the model's ``state_dict`` names."""
+        ema = self._need_ema()
+        if self._averaged:
+            raise RuntimeError("FlatAdamW.ema_state_dict inside averaged(): the buffer holds the raw weights there")
+        names = self._names()
+        return {names[id(p)]: ema[so:so + p.numel()].view(p.shape).detach().cpu().clone() for p, so in zip(self._params, self._soff)}
+
+    @torch.no_grad()
+    def load_ema_state_dict(self, sd) -> None:
+        """Takes what ``ema_state_dict`` returns (further keys, a model's buffers for instance, are ignored)."""
+        ema = self._need_ema()
+        if self._averaged:
+            raise RuntimeError("FlatAdamW.load_ema_state_dict inside averaged()")
+        names = self._names()
+        for p, so in zip(self._params, self._soff):
+            name = names[id(p)]
+            if name not in sd:
+                raise KeyError(f"load_ema_state_dict: no entry for parameter {name}")
+            v = sd[name]
+            if tuple(v.shape) != tuple(p.shape):
+                raise ValueError(f"load_ema_state_dict: {name} has shape {tuple(v.shape)}, the parameter {tuple(p.shape)}")
+            ema[so:so + p.numel()].copy_(v.reshape(-1).to(self._dev, torch.float32))
+
+    def _swap(self) -> None:
+        t = self._tables()
+        with torch.cuda.device(self._dev):
+            L.check(self._lib.sepr_adamw_swap(C.byref(t), self._ema.data_ptr(), torch.cuda.current_stream(self._dev).cuda_stream),
+                    "sepr_adamw_swap")
+        self._model.invalidate_packed()                       # the packed weight forms were derived from the other set
+
+    @contextlib.contextmanager
+    def averaged(self):
+        """Inside the block the model's parameters ARE the averaged weights (and the EMA buffer holds the raw ones): one in-place, bitwise
+        exchange on entry and one on exit, each followed by ``model.invalidate_packed()``.  No nesting, no ``step`` inside."""
+        self._need_ema()
+        if self._averaged:
+            raise RuntimeError("FlatAdamW.averaged() does not nest")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("FlatAdamW.averaged() inside a graph capture")
+        if [p.data_ptr() for p in self._params] != self._ptrs:
+            raise RuntimeError("FlatAdamW: a parameter moved after the optimizer was built; build a new optimizer")
+        self._swap()
+        self._averaged = True
+        try:
+            yield self
+        finally:
+            self._averaged = False
+            self._swap()
 
     def attach_ledger(self, ledger: Optional[torch.Tensor], parts: Optional[torch.Tensor] = None) -> None:
         """From now on every ``step`` ends with one ``sepr_run_ledger_update`` launch that folds ``parts`` (the step's loss scalars, fp32,

@@ -16,11 +16,19 @@ trajectory bit for bit: the dropout words of global step ``i`` are a pure functi
 ``salt_word``), the feeds' generator states travel in the file, and the first batch of a (re)start is the example batch of the
 capture - a real batch, a real step, counted.
 
+``ema_decay=d`` keeps an exponential moving average of the weights inside the optimizer's update launch (``FlatAdamW(ema_decay=d)``,
+DESIGN.md section 5g-2).  ``validate_with`` says which weights validation, the plateau schedule, ``best`` and the test loop see:
+``"ema"`` (the default; the passes run inside ``opt.averaged()``), ``"raw"``, or ``"both"`` (two ``[VALID]`` lines, the averaged
+result decides).  The checkpoint then carries ``ema_state_dict`` - the keys of ``model_state_dict``, parameters from the average,
+buffers from the model - which ``infer.load_checkpoint_weights(..., ema=True)`` or a plain ``load_state_dict`` takes on its own.  The
+EMA never touches the raw trajectory, and the decay schedule has no state: its ``t`` is the optimizer's step counter.
+
 Two deliberate differences from the reference: every epoch is saved by default (``save="all"``; the reference saves the epochs that
 beat the loss the run STARTED from), and non-finite steps are skipped instead of poisoning the weights.
 
 Out of scope: data-parallel runs (the feeds' ``rank`` / ``world`` and ``model.grad_sync`` are passed through untouched and not
-tested here), TensorBoard, the MAC summary, and ``mvn`` (refused; every shipped config has it false).
+tested here; with the EMA on, every rank would apply the same update to its own buffer, so the buffers would agree - untested
+too), TensorBoard, the MAC summary, and ``mvn`` (refused; every shipped config has it false).
 """
 from __future__ import annotations
 
@@ -35,6 +43,7 @@ from . import lib as L
 
 CHECKPOINT_KEYS = ("epoch", "model_state_dict", "optimizer_state_dict", "train_loss", "valid_loss")      # util_engine.py:98-105
 RUN_STATE_KEY = "sepr_run_state"
+EMA_KEY = "ema_state_dict"
 _NAME = re.compile(r"^epoch\.(\d+)\.pth$")
 _M64 = (1 << 64) - 1
 
@@ -74,6 +83,15 @@ def salt_word(seed: int, step: int) -> int:
     return _mix64(_mix64(int(seed) & _M64) ^ _mix64(int(step) & _M64)) & 0x7FFFFFFFFFFFFFFF
 
 
+def ema_decay_at(t: int, decay: float, warmup: float = 10.0) -> float:
+    """The EMA decay of optimizer step ``t`` (1-based, the optimizer's own counter after its increment), as the prepare kernel of
+    ``sepr_adamw_step_ema`` forms it in double: ``decay``, ramped in as ``(1 + t) / (warmup + t)`` while that is smaller; ``warmup <= 0``
+    turns the ramp off."""
+    if warmup <= 0:
+        return float(decay)
+    return min(float(decay), (1.0 + float(t)) / (float(warmup) + float(t)))
+
+
 def checkpoint_name(epoch: int) -> str:
     return f"epoch.{epoch:04}.pth"                      # util_engine.py:106
 
@@ -109,14 +127,21 @@ def prune_checkpoints(directory: str, keep_last: Optional[int]) -> List[str]:
 
 
 def write_checkpoint(directory: str, epoch: int, model_sd: dict, optimizer_sd: dict, train_loss: float, valid_loss: float,
-                     run_state: dict, keep_last: Optional[int] = None) -> str:
+                     run_state: dict, keep_last: Optional[int] = None, extra: Optional[dict] = None) -> str:
     """The reference's five keys plus ``sepr_run_state``, inside ONE file: the reference's loader parses every file name of the
-    directory as ``epoch.<int>.``, so nothing else may lie there - the file is written beside the directory and moved in."""
+    directory as ``epoch.<int>.``, so nothing else may lie there - the file is written beside the directory and moved in.
+    ``extra``: further top-level keys (``ema_state_dict``); none of the six may be replaced."""
+    body = {"epoch": int(epoch), "model_state_dict": model_sd, "optimizer_state_dict": optimizer_sd, "train_loss": float(train_loss),
+            "valid_loss": float(valid_loss), RUN_STATE_KEY: run_state}
+    if extra:
+        clash = set(extra) & set(body)
+        if clash:
+            raise ValueError(f"write_checkpoint: extra may not replace {sorted(clash)}")
+        body.update(extra)
     os.makedirs(directory, exist_ok=True)
     path = os.path.join(directory, checkpoint_name(epoch))
     tmp = os.path.join(os.path.dirname(os.path.abspath(directory)), "." + os.path.basename(os.path.abspath(directory)) + "." + checkpoint_name(epoch) + ".tmp")
-    torch.save({"epoch": int(epoch), "model_state_dict": model_sd, "optimizer_state_dict": optimizer_sd, "train_loss": float(train_loss),
-                "valid_loss": float(valid_loss), RUN_STATE_KEY: run_state}, tmp)
+    torch.save(body, tmp)
     os.replace(tmp, path)
     prune_checkpoints(directory, keep_last)
     return path
@@ -171,16 +196,20 @@ class Trainer:
                  seed: int = 0, max_epoch: int = 200, clip_norm: Optional[float] = 5.0, start_scheduling: int = 50,
                  test_epochs: Sequence[int] = (100, 120, 150, 170), warmup_steps: int = 1000, factor: float = 0.8, patience: int = 2,
                  min_lr: float = 1.0e-10, mvn: bool = False, save: str = "all", keep_last: Optional[int] = None, log_every: int = 50,
-                 max_skipped: int = 10, test_utterances: Optional[Callable[[], Iterable]] = None, log: Callable[[str], None] = print):
+                 max_skipped: int = 10, test_utterances: Optional[Callable[[], Iterable]] = None, log: Callable[[str], None] = print,
+                 ema_decay: Optional[float] = None, ema_warmup: float = 10.0, validate_with: str = "ema"):
         """``train_feed``: a ``DynamicMixFeed`` with ``fixed_length=True``; ``valid_feed``: one over ``plan_direct`` (``drop_last=False``
         keeps the trailing partial batch, as the reference's validation loader does).  ``test_utterances``: a callable returning the
         iterable ``infer.evaluate_utterances`` takes, run at ``test_epochs``.  The other arguments are the reference's ``engine`` /
-        ``optimizer`` / ``scheduler`` settings; the defaults are the values its four ``configs.yaml`` share."""
+        ``optimizer`` / ``scheduler`` settings; the defaults are the values its four ``configs.yaml`` share.  ``ema_decay`` / ``ema_warmup``:
+        the weight EMA of ``FlatAdamW``; ``validate_with`` (``"raw"``, ``"ema"``, ``"both"``) is ignored while it is off."""
         if mvn:
             raise ValueError("mvn: true is not supported (every shipped configuration has it false)")
         if not getattr(train_feed, "fixed_length", False):
             raise ValueError("the training feed must be built with fixed_length=True (the captured step has one shape)")
         should_save(save, 0.0, 0.0)
+        if validate_with not in ("raw", "ema", "both"):
+            raise ValueError("validate_with: 'raw', 'ema' or 'both'")
         if warmup_steps < 1 or log_every < 1:
             raise ValueError("warmup_steps >= 1 and log_every >= 1")
         from .criterion import PIT_SISNR_mag, PIT_SISNR_time
@@ -192,7 +221,10 @@ class Trainer:
         self.max_epoch, self.clip_norm, self.start_scheduling, self.test_epochs = int(max_epoch), clip_norm, int(start_scheduling), tuple(test_epochs)
         self.warmup_steps, self.save_mode, self.keep_last = int(warmup_steps), save, keep_last
         self.log_every, self.max_skipped, self.test_utterances, self.log = int(log_every), int(max_skipped), test_utterances, log
-        self.opt = FlatAdamW(model, lr=lr, weight_decay=weight_decay, skip_nonfinite=True)
+        self.opt = FlatAdamW(model, lr=lr, weight_decay=weight_decay, skip_nonfinite=True, ema_decay=ema_decay, ema_warmup=ema_warmup)
+        self.ema = ema_decay is not None
+        self.validate_with = validate_with if self.ema else "raw"
+        self.last_valid_raw: Optional[Tuple[float, float, int]] = None          # validate_with="both": the raw weights' result of the last epoch
         self.scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(self.opt, mode="min", factor=factor, patience=patience, min_lr=min_lr)
         S, R = self.cfg.num_spks, self.cfg.num_stages
         self.crit_t = PIT_SISNR_time(self.dev, S, True)
@@ -305,9 +337,18 @@ class Trainer:
         t, f = epoch_means(led.part_sum, led.steps, self.cfg.num_spks)
         return t, f, i
 
-    def validate(self) -> Tuple[float, float, int]:
+    def validate(self, weights: Optional[str] = None) -> Tuple[float, float, int]:
         """``_validate`` (``engine.py:86-110``): one pass over the validation feed -> the same three values.  The batch means are
-        averaged, so a trailing partial batch weighs as much as a full one."""
+        averaged, so a trailing partial batch weighs as much as a full one.  ``weights``: ``"raw"`` or ``"ema"``; the default is what
+        ``validate_with`` says (``"both"`` counts as ``"ema"`` here: ``run`` makes the second pass)."""
+        if weights is None:
+            weights = "raw" if self.validate_with == "raw" else "ema"
+        if weights == "ema":
+            with self.opt.averaged():
+                return self._validate()
+        return self._validate()
+
+    def _validate(self) -> Tuple[float, float, int]:
         lib = L.load()
         self.model.eval()
         nb = 0
@@ -331,12 +372,18 @@ class Trainer:
             return None
         from .infer import evaluate_utterances
         self.model.eval()
+        if self.validate_with != "raw":                    # "ema" and "both": the shipped weights are the averaged ones
+            with self.opt.averaged():
+                return evaluate_utterances(self.model, self.test_utterances())
         return evaluate_utterances(self.model, self.test_utterances())
 
     # ---- checkpoints --------------------------------------------------------------------------------------------------------------
     def run_state(self) -> dict:
-        return {"global_step": int(self.global_step), "plateau": self.scheduler.state_dict(), "train_feed": self.train_feed.state_dict(),
-                "valid_feed": self.valid_feed.state_dict(), "best": float(self.best), "seed": int(self.seed)}
+        rs = {"global_step": int(self.global_step), "plateau": self.scheduler.state_dict(), "train_feed": self.train_feed.state_dict(),
+              "valid_feed": self.valid_feed.state_dict(), "best": float(self.best), "seed": int(self.seed)}
+        if self.ema:
+            rs["ema"] = {"decay": float(self.opt.ema_decay), "warmup": float(self.opt.ema_warmup)}
+        return rs
 
     def save(self, epoch: int, train_loss: float, valid_loss: float) -> Optional[str]:
         """Every epoch (``save="all"``) or the epochs that beat the best so far (``"best"``); ``keep_last`` prunes older files."""
@@ -348,7 +395,12 @@ class Trainer:
         osd = self.opt.state_dict()
         osd = {"state": {k: {n: cpu(v) for n, v in st.items()} for k, st in osd["state"].items()}, "param_groups": osd["param_groups"]}
         msd = {k: cpu(v) for k, v in self.model.state_dict().items()}
-        self.last_checkpoint = write_checkpoint(self.dir, epoch, msd, osd, train_loss, valid_loss, self.run_state(), self.keep_last)
+        extra = None
+        if self.ema:
+            # the keys of model_state_dict: parameters from the average, buffers (BatchNorm statistics) from the model - loadable on its own
+            esd = self.opt.ema_state_dict()
+            extra = {EMA_KEY: {k: esd.get(k, v) for k, v in msd.items()}}
+        self.last_checkpoint = write_checkpoint(self.dir, epoch, msd, osd, train_loss, valid_loss, self.run_state(), self.keep_last, extra)
         return self.last_checkpoint
 
     def load_latest(self) -> int:
@@ -370,6 +422,12 @@ class Trainer:
             self.valid_feed.load_state_dict(rs["valid_feed"])
         else:
             self.global_step = int(float(self.opt._step.item()))
+        if self.ema:
+            if EMA_KEY in ck:
+                self.opt.load_ema_state_dict(ck[EMA_KEY])
+            else:
+                self.opt.reset_ema()
+                self.log(f"{path} carries no {EMA_KEY}: the weight EMA starts again at the loaded weights")
         self.last_checkpoint = path
         self.start_epoch = int(ck["epoch"]) + 1
         self.log(f"loaded {path}: resuming at epoch {self.start_epoch}, global step {self.global_step}")
@@ -390,11 +448,23 @@ class Trainer:
                 t0 = time.time()
                 tr_t, tr_f, tr_n = self.train_epoch(epoch)
                 t1 = time.time()
+                raw = None
+                if self.validate_with == "both":
+                    # the same batches for both passes: the raw pass is put back out of the feed's state, so the feed moves on once per epoch
+                    keep = self.valid_feed.state_dict()
+                    raw = self.validate("raw")
+                    self.valid_feed.load_state_dict(keep)
+                    t_raw = time.time()
                 va_t, va_f, va_n = self.validate()
                 t2 = time.time()
-                plateau_step(self.scheduler, epoch, self.start_scheduling, va_t)
+                plateau_step(self.scheduler, epoch, self.start_scheduling, va_t)      # with the EMA on ("ema", "both"): the averaged weights' loss
                 self.log(f"[TRAIN] Epoch {epoch:2d}: Loss_t = {tr_t:.4f} dB | Loss_f = {tr_f:.4f} dB | Speed = ({t1 - t0:.2f}s/{tr_n:d})")
-                self.log(f"[VALID] Epoch {epoch:2d}: Loss_t = {va_t:.4f} dB | Loss_f = {va_f:.4f} dB | Speed = ({t2 - t1:.2f}s/{va_n:d})")
+                if raw is not None:
+                    self.log(f"[VALID] Epoch {epoch:2d}: Loss_t = {raw[0]:.4f} dB | Loss_f = {raw[1]:.4f} dB | Speed = ({t_raw - t1:.2f}s/{raw[2]:d}) | raw")
+                    self.log(f"[VALID] Epoch {epoch:2d}: Loss_t = {va_t:.4f} dB | Loss_f = {va_f:.4f} dB | Speed = ({t2 - t_raw:.2f}s/{va_n:d}) | ema")
+                    self.last_valid_raw = raw
+                else:
+                    self.log(f"[VALID] Epoch {epoch:2d}: Loss_t = {va_t:.4f} dB | Loss_f = {va_f:.4f} dB | Speed = ({t2 - t1:.2f}s/{va_n:d})")
                 if epoch in self.test_epochs and self.test_utterances is not None:
                     t3 = time.time()
                     sisnri, sdri, n = self.test()

@@ -14,6 +14,7 @@ one checkpoint per epoch in ``--checkpoint-dir``, and ``--resume`` to continue f
     python tools/train_from_scp.py --form whamr --scp s1=.. s2=.. noise=.. --room-rirs 64:0.2:0.6     # simulated rooms, redrawn per epoch (section 5e-4)
     python tools/train_from_scp.py --form whamr --scp s1=.. s2=.. noise=.. --room-rirs 64:0.2:0.6 --speeds 95:105      # each source perturbed, then reverberated (section 5e-5)
     python tools/train_from_scp.py --form wsj0 --scp s1=tr_s1.scp s2=tr_s2.scp --epochs 200 --valid-scp mix=cv_mix.scp s1=cv_s1.scp s2=cv_s2.scp --checkpoint-dir ck [--resume]
+    python tools/train_from_scp.py ... --epochs 200 --valid-scp ... --checkpoint-dir ck --ema-decay 0.999 [--ema-warmup 10] [--validate-with raw|ema|both]      # weight EMA (section 5g-2)
 """
 import argparse
 import os
@@ -63,12 +64,21 @@ def main():
     ap.add_argument("--valid-batch", type=int, default=None, help="validation batch (default: --batch)")
     ap.add_argument("--log", type=int, default=None, help="log interval in steps (default: 10 with --steps; with --epochs the Trainer's own, 50 - each "
                     "log line there is one ledger read-back, a host synchronisation)")
+    ap.add_argument("--ema-decay", type=float, default=None, metavar="D", help="with --epochs: keep an exponential moving average of the weights inside "
+                    "the optimizer launch (DESIGN.md section 5g-2); the checkpoints then carry ema_state_dict (default: off)")
+    ap.add_argument("--ema-warmup", type=float, default=10.0, metavar="W", help="the decay of step t is min(D, (1 + t) / (W + t)); 0 turns the ramp off")
+    ap.add_argument("--validate-with", choices=["raw", "ema", "both"], default="ema", help="with --ema-decay: the weights validation, the plateau "
+                    "schedule, 'best' and the test loop see (both: two [VALID] lines, the averaged result decides)")
     ap.add_argument("--lr", type=float, default=1.0e-4)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args()
     if args.epochs is not None and (not args.valid_scp or not args.checkpoint_dir):
         ap.error("--epochs needs --valid-scp and --checkpoint-dir")
+    if args.ema_decay is not None and args.epochs is None:
+        ap.error("--ema-decay needs --epochs (the --steps mode keeps no weights)")
+    if args.ema_decay is not None and not 0.0 <= args.ema_decay < 1.0:
+        ap.error("--ema-decay must lie in [0, 1)")
     if args.speeds and args.form == "direct":
         ap.error("--speeds needs dynamic mixing (--form wsj0, wham or whamr)")
     reverb = args.rir_scp or args.synthetic_rirs or args.room_rirs
@@ -176,7 +186,8 @@ def run_epochs(args, df, model, feed, dev):
                        key)
     trainer = Trainer(model, feed, valid, args.checkpoint_dir, lr=args.lr, seed=args.seed, max_epoch=args.epochs, warmup_steps=args.warmup_steps,
                       start_scheduling=args.start_scheduling, test_epochs=args.test_epochs, save=args.save, keep_last=args.keep_last,
-                      test_utterances=test, log=lambda s: print(s, flush=True), **({} if args.log is None else {"log_every": args.log}))
+                      test_utterances=test, log=lambda s: print(s, flush=True), ema_decay=args.ema_decay, ema_warmup=args.ema_warmup,
+                      validate_with=args.validate_with, **({} if args.log is None else {"log_every": args.log}))
     trainer.run()
 
 
