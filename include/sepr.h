@@ -562,7 +562,31 @@ int sepr_resample_fwd(const float* x, const long long* in_offset, float* y, cons
  * the two entries do: a bad table yields wrong samples but never a read outside the corpus, the bank or a tap table.  SEPR_EINVAL before any HIP
  * call for everything sepr_dynmix_speed_fwd or sepr_dynmix_reverb_fwd refuses (a converter whose 2048-output span exceeds 3072 samples included).
  * No workspace, no host synchronisation or allocation (capturable: the pointers and the converter descriptions are frozen, the table contents are
- * read at replay).  A new entry, no struct change: ABI 4.13. */
+ * read at replay).  A new entry, no struct change: ABI 4.13.
+ *
+ * sepr_dynmix_turns_fwd: turn-taking - partially overlapped talkers - inside the one launch.  The arguments of
+ * sepr_dynmix_speed_reverb_fwd, two more columns term_on, term_off [B (M + S)] int32 (DEVICE) and the table ramp [RL] float32 (DEVICE, 4-byte aligned),
+ * 0 <= RL <= 4096, which the host makes as ramp[i] = float32(0.5 - 0.5 cos(pi (i + 0.5) / RL)) in float64; RL = 0 is a hard gate.  A term is
+ * (utt, start, norm, gain, conv, rir, taps, on, off): [on, off) is its TURN in output samples of the example; either end may lie outside [0, n).  For
+ * any integer t, negative ones included, with d = t - on and e = off - 1 - t,
+ *   w(t) = 0                    if d < 0 or e < 0
+ *        = ramp[min(d, e)]      if min(d, e) < RL
+ *        = 1                    otherwise.
+ * The gate acts on the talker's float32 signal y - the stored utterance, or the perturbed one when conv >= 0 - at index p = start + t, BEFORE any response:
+ *   g[p] = +0.0f                            where w(p - start) == 0   (a selection, not a product: never -0.0)
+ *        = float32(y[p] * w(p - start))     elsewhere (one float32 multiply),
+ * and the term is exactly what the forms above make of g in place of y: (g[start + t] * norm) * gain without a response,
+ * float32(sum_{j < taps} double(h[j]) * double(g[start + t - j])) and then the two multiplies with one.  The history before the crop (t - j < 0) is gated
+ * by the same w: a talker whose turn began before the window keeps their tail, one who starts inside it has silence behind them, and the room rings on
+ * after `off`, in the mixture and in the target alike - the talker stops, the room does not.  on and off are only compared and subtracted; the kernel
+ * clamps both to [-2^30, 2^30], so a term with (on, off) = (-2^30, 2^30) has w = 1 wherever it can be evaluated and - x * 1.0f being x - carries the bits
+ * of sepr_dynmix_speed_reverb_fwd, hence of every entry above.  One entry covers every kind of term: conv < 0 = no converter (NC = 0 allowed), rir < 0 = no
+ * response, and R = 0 (rir, rir_off may then be NULL) makes every rir none.  A target term that equals mixture term s in all nine fields is computed
+ * once.  A tile of 2048 outputs that lies past off + K - 1 (K = the clamped taps, 1 without a response) or ends at or before on is exactly +0 raw samples
+ * and skips its loads, its conversion and its tap chunks, as does a single tap chunk that reaches only closed samples; the two multiplies still act on
+ * the zeros.  Every clamp of sepr_dynmix_speed_reverb_fwd holds; the ramp index is below RL by construction.  SEPR_EINVAL before any HIP call for RL < 0,
+ * RL > 4096, a null ramp with RL > 0, a misaligned ramp, a null term_on or term_off, R < 0, and everything sepr_dynmix_speed_reverb_fwd refuses (its
+ * bank checks for R >= 1).  57344 bytes of LDS, no workspace, no host synchronisation or allocation (capturable).  A new entry, no struct change: ABI 4.13. */
 size_t sepr_corpus_energy_workspace(int N);
 int sepr_corpus_energy(const short* buf16, long long total16, const float* buf32, long long total32, const long long* offsets, int N16, int N,
                        long long* ss16, double* ss32, void* ws, size_t ws_bytes, sepr_stream_t stream);
@@ -583,6 +607,12 @@ int sepr_dynmix_speed_reverb_fwd(const short* buf16, long long total16, const fl
                                  float* mix, float* const* src, const float* const* conv_taps, const int* conv_L, const int* conv_M,
                                  const int* conv_K, int NC, const float* rir, long long rir_total, const long long* rir_off, int R,
                                  sepr_stream_t stream);
+int sepr_dynmix_turns_fwd(const short* buf16, long long total16, const float* buf32, long long total32, const long long* offsets, int N16, int N,
+                          const int* term_utt, const int* term_start, const float* term_norm, const float* term_gain, const int* term_conv,
+                          const int* term_rir, const int* term_taps, const int* term_on, const int* term_off, const int* n, int B, int M, int S,
+                          int Tmax, float* mix, float* const* src, const float* const* conv_taps, const int* conv_L, const int* conv_M,
+                          const int* conv_K, int NC, const float* rir, long long rir_total, const long long* rir_off, int R, const float* ramp,
+                          int RL, sepr_stream_t stream);
 
 /* ---- room impulse responses by the image-source method (a new entry, no struct change: ABI 4.13) -------
  * sepr_rir_ism_fwd simulates R impulse responses of N samples, one per shoebox room, in one call.  The definition is independent of the

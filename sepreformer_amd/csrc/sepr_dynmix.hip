@@ -25,6 +25,10 @@
 //                        chunk reaches is converted into LDS as doubles (the converter of sepr_polyphase.h, in passes whose input span fits the
 //                        staged doubles), then the FIR loop runs over it.  57 344 bytes of LDS; a term with one of the two takes that
 //                        form's code and gives its bits.
+//     F = TurnsForm      (sepr_dynmix_turns_fwd, section 5e-6) SpeedReverbForm's term with a turn [on, off): the talker's float32 signal under a
+//                        raised-cosine gate BEFORE the response, so the room rings on after the talker stops.  The gate is a parameter of the
+//                        four staging paths (NoGate in every other form: their code); a tile or a tap chunk that reaches only closed samples
+//                        is skipped.
 //   dynmix_speed_kernel  (sepr_dynmix_speed_fwd, section 5e-2) the same batch with speed perturbation, a kernel of its own (docs/HISTORY.md:
 //                        as an instance of the skeleton it ran 0.8 to 1.1 us longer per launch at B = 16): a term whose term_conv is a converter
 //                        index is the stored utterance through that rational-ratio converter (sepr_polyphase.h).  The
@@ -100,9 +104,45 @@ __device__ __forceinline__ void scale8(const float x[8], float norm, float gain,
   }
 }
 
+// ---- turns: a gate on the talker's float32 signal, before any response ------------------------------------------
+// A gate is a parameter of the four staging paths below (term_value, convert_tile, reverb_tile's staged input, speed_reverb_tile's perturbed
+// span).  Term time is t = p - start (p the sample's index in the stored or perturbed utterance, so t is the output sample it reaches through tap 0;
+// negative in a response's history).  A path rebases the gate once, on scalars, to the term time of its first staged sample - gate.at(base) - and
+// then gates sample i of its span with 32-bit arithmetic: gate(y, i).  NoGate is the identity and leaves the code each path had.
+struct NoGate {
+  static constexpr bool kOn = false;
+  __device__ __forceinline__ NoGate at(long long) const { return {}; }
+  __device__ __forceinline__ float operator()(float y, int) const { return y; }
+};
+
+// the turn [on, off) of one term under the raised-cosine table ramp [RL]:  w(t) = 0 outside the turn, ramp[min(t - on, off - 1 - t)] where that
+// is below RL, else 1.  on and off are clamped to [-2^30, 2^30] where the table is read (TurnsForm::cols) and again when the gate is rebased (an end
+// 2^30 samples from a span of a few thousand is out of its reach either way), and a span's index i lies within a few thousand of 0: no difference
+// overflows 32 bits.  The ramp index lies in [0, RL).  A closed gate SELECTS +0 (never -0, whatever y holds), an open one multiplies once in
+// float32, and w = 1 is y itself (y * 1.0f is y).
+struct TurnGate {
+  static constexpr bool kOn = true;
+  int on, off, RL;
+  const float* __restrict__ ramp;
+  __device__ __forceinline__ TurnGate at(long long base) const {
+    return {(int)clampll(on - base, -(1 << 30), 1 << 30), (int)clampll(off - base, -(1 << 30), 1 << 30), RL, ramp};
+  }
+  __device__ __forceinline__ float operator()(float y, int i) const {
+#pragma clang fp contract(off)
+    const int d = i - on, e = off - 1 - i;
+    if ((d | e) < 0) return 0.f;
+    const int m = d < e ? d : e;
+    return m < RL ? y * ramp[m] : y;
+  }
+  // outputs [t_lo, t_hi) of a term under K taps (K = 1 without a response) reach gated samples at t - j, j < K: all of them closed?
+  __device__ __forceinline__ bool silent(long long t_lo, long long t_hi, int K) const { return t_lo >= (long long)off + (K - 1) || t_hi <= on; }
+};
+
 // (sample * norm) * gain of the stored term (utt, start) on samples t0 .. t0 + 7.  The table is not trusted: the utterance index, the start
 // and the element position are clamped, so whatever it holds no read leaves the corpus buffers.
-__device__ __forceinline__ void term_value(const DmCorpus& c, int utt, int start, float norm, float gain, int t0, float v[8]) {
+template <class G = NoGate>
+__device__ __forceinline__ void term_value(const DmCorpus& c, int utt, int start, float norm, float gain, int t0, float v[8], const G& gate = G{},
+                                           int i0 = 0) {                     // i0: the gate's index of sample t0
   const int u = utt < 0 ? 0 : (utt >= c.N ? c.N - 1 : utt);
   const long long o0 = c.off[u], len = c.off[u + 1] - o0;
   const long long st = clampll(start, 0, len > 0 ? len : 0);
@@ -111,6 +151,10 @@ __device__ __forceinline__ void term_value(const DmCorpus& c, int utt, int start
     load8_i16(c.buf16, clampll(o0 + st + t0, 0, c.total16 - 1), (c.total16 + 7) & ~7LL, x);
   } else {
     load8_f32(c.buf32, clampll(o0 - c.off[c.N16] + st + t0, 0, c.total32 - 1), (c.total32 + 3) & ~3LL, x);
+  }
+  if constexpr (G::kOn) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) x[i] = gate(x[i], i0 + i);
   }
   scale8(x, norm, gain, v);
 }
@@ -158,6 +202,19 @@ struct DmUtt {
       return is16 ? (double)((float)c.buf16[e] * 3.0517578125e-05f) : (double)c.buf32[e];
     });
   }
+
+  // the same under a gate rebased to the term time of sample g0: sample g0 + i is gated as a float32, at index i, and widened after
+  template <class G>
+  __device__ __forceinline__ void stage(const DmCorpus& c, long long g0, int count, double* __restrict__ xs, const G& gate) const {
+    if constexpr (!G::kOn) {
+      stage(c, g0, count, xs);
+    } else {
+      pp_stage<DM_TPB>(xs, count, g0, T, [&](long long g, int i) {
+        const long long e = clampll(e0 + g, 0, total - 1);
+        return (double)gate(is16 ? (float)c.buf16[e] * 3.0517578125e-05f : c.buf32[e], i);
+      });
+    }
+  }
 };
 
 // the tile's outputs from one per lane (thread tid holds t = tile0 + tid + DM_TPB i) to x[0 .. 7] = t0 .. t0 + 7 (t0 = tile0 + 8 tid),
@@ -198,8 +255,11 @@ struct DrResp {
 // passes every barrier.  Thread tid owns the outputs tid + 256 i: consecutive lanes read consecutive doubles of xs, and the tap is one
 // broadcast read.  hs is the taps of a chunk as doubles while the chunks run, the tile of floats at the end.
 // The tables are not trusted: r, taps, the utterance and every read position are clamped, so no read leaves the bank or the corpus.
+// Under a gate x is the gated utterance; a chunk that reaches only closed samples adds fma(h, +0, acc) = acc and is skipped, as one before the
+// utterance is (the turn is workgroup-uniform, so the barriers stay matched).
+template <class G = NoGate>
 __device__ __forceinline__ void reverb_tile(const DmCorpus& c, const DrBank& bk, int r, int taps, int utt, int start, int tile0, int n,
-                                            DsLds& lds, float x8[8]) {
+                                            DsLds& lds, float x8[8], const G& gate = G{}) {
   const int tid = threadIdx.x;
   const DmUtt ut(c, utt);
   const long long st = clampll(start, 0, ut.T > 0 ? ut.T : 0);
@@ -218,8 +278,13 @@ __device__ __forceinline__ void reverb_tile(const DmCorpus& c, const DrBank& bk,
     // later chunk - their spans lie further back still - are skipped without changing a bit
     if (g0 + (DS_TILE + DR_CHUNK - 2) < 0) break;
     const int kc = K - k0 < DR_CHUNK ? K - k0 : DR_CHUNK;
+    if constexpr (G::kOn) {                                                  // the chunk's outputs below n, as a term of its own under kc taps
+      const long long ta = (long long)tile0 - k0, tb = ta + (left < DS_TILE ? left : DS_TILE);
+      if (tb <= gate.on) break;                                              // later chunks reach further back still
+      if (gate.silent(ta, tb, kc)) continue;
+    }
     __syncthreads();                                                         // the last readers of xs / hs (or of the float tile) are done
-    ut.stage(c, g0, DS_TILE + DR_CHUNK - 1, lds.xs);
+    ut.stage(c, g0, DS_TILE + DR_CHUNK - 1, lds.xs, gate.at(g0 - st));
     for (int i = tid; i < kc; i += DM_TPB) hs[i] = (double)hp[k0 + i];
     __syncthreads();
     if (tid < left) {                                                        // (per wave: whole waves past n skip the loop)
@@ -237,9 +302,10 @@ __device__ __forceinline__ void reverb_tile(const DmCorpus& c, const DrBank& bk,
 
 // outputs t = tile0 .. tile0 + DS_TILE - 1 (below n) of the perturbed utterance of term (utt, start) through converter (tp, L, M, K), left in
 // ys[t - tile0]; thread tid then owns ys[8 tid .. 8 tid + 7].  Workgroup-uniform arguments; two barriers.  The table is not trusted:
-// whatever it holds, the staging reads stay inside the utterance's slice of the corpus buffers.
+// whatever it holds, the staging reads stay inside the utterance's slice of the corpus buffers.  A gate acts on the perturbed sample, at its output.
+template <class G = NoGate>
 __device__ __forceinline__ void convert_tile(const DmCorpus& c, int utt, int start, const float* __restrict__ tp, int L, int M, int K,
-                                             int tile0, int n, double* __restrict__ xs, float* __restrict__ ys) {
+                                             int tile0, int n, double* __restrict__ xs, float* __restrict__ ys, const G& gate = G{}) {
   const int tid = threadIdx.x;
   const DmUtt ut(c, utt);
   const long long n0 = (long long)(start < 0 ? 0 : start) + tile0;          // first output of the tile, as an index of the perturbed utterance
@@ -261,7 +327,7 @@ __device__ __forceinline__ void convert_tile(const DmCorpus& c, int utt, int sta
   }
   if (tid < left) pp_chain<DM_PER, 2>(tq, (long long)L, xp, K, acc);         // (per wave: whole waves past n skip the loop)
 #pragma unroll
-  for (int i = 0; i < DM_PER; ++i) ys[tid + i * DM_TPB] = (float)acc[i];
+  for (int i = 0; i < DM_PER; ++i) ys[tid + i * DM_TPB] = gate((float)acc[i], tid + i * DM_TPB);       // the caller rebased the gate to tile0
   __syncthreads();
 }
 
@@ -406,9 +472,10 @@ static_assert(sizeof(SrLds) <= 57344, "static LDS of the combined form");
 //   y[q] = float32(sum_{j < K} double(tap[(q M) mod L][j]) * x[floor(q M / L) - Hh + j]),
 // the window and the chain of sepr_polyphase.h; xs[0] is input sample b0 - Hh and `span` doubles are staged.  No barrier.  Every window base is clamped into
 // [0, span - K] (span <= DS_SPAN, K <= span: the entry refuses any other converter) and every phase lies in [0, L): no read leaves xs or the tap table.
-template <int NI>
+// Under a gate - rebased to the term time of position 0 - the float32 perturbed sample is gated before it is widened.
+template <int NI, class G = NoGate>
 __device__ __forceinline__ void convert_group(const double* __restrict__ xs, int span, long long b0, const float* __restrict__ tp, int L, int M,
-                                              int K, long long q0, int i0, int i1, double* __restrict__ yd) {
+                                              int K, long long q0, int i0, int i1, double* __restrict__ yd, const G& gate = G{}) {
   const int tid = threadIdx.x;
   if (i0 + tid >= i1) return;                                                // (per wave: whole waves without a position skip the loop)
   const int lim = span - K;
@@ -426,7 +493,7 @@ __device__ __forceinline__ void convert_group(const double* __restrict__ xs, int
 #pragma unroll
   for (int i = 0; i < NI; ++i) {
     const int pos = i0 + tid + i * DM_TPB;
-    if (pos < i1) yd[pos] = (double)(float)acc[i];                          // the one rounding of the perturbed sample
+    if (pos < i1) yd[pos] = (double)gate((float)acc[i], pos);         // the one rounding of the perturbed sample
   }
 }
 
@@ -440,8 +507,11 @@ __device__ __forceinline__ void convert_group(const double* __restrict__ xs, int
 // The tables are not trusted.  conv is clamped to [0, NC - 1], r and taps as in reverb_tile (every tap read inside the bank), the utterance by
 // DmUtt (every staged element clamped into its buffer), start into [0, P]; ys is written and read at indices in [DR_CHUNK - kc, DS_TILE +
 // DR_CHUNK - 1) only, xs below `span` <= DS_SPAN only.
+// Under a gate y is the gated perturbed utterance: a chunk that reaches only closed samples is skipped as in reverb_tile, and of the others only the
+// positions inside the turn are converted - the rest are the +0 the gate would select.
+template <class G = NoGate>
 __device__ __forceinline__ void speed_reverb_tile(const DmCorpus& c, const ConvSet& cv, const DrBank& bk, int conv, int r, int taps, int utt,
-                                                  int start, int tile0, int n, SrLds& lds, float x8[8]) {
+                                                  int start, int tile0, int n, SrLds& lds, float x8[8], const G& gate = G{}) {
   const int tid = threadIdx.x;
   const DmUtt ut(c, utt);
   const int ck = conv >= cv.NC ? cv.NC - 1 : conv;                           // conv >= 0 and NC >= 1 here
@@ -468,9 +538,18 @@ __device__ __forceinline__ void speed_reverb_tile(const DmCorpus& c, const ConvS
     if (g0 + (DS_TILE + DR_CHUNK - 2) < 0) break;
     const int kc = K - k0 < DR_CHUNK ? K - k0 : DR_CHUNK;
     const int lo = DR_CHUNK - kc;                                            // the FIR loop reads ys[lo ..] only
-    const int ca = g0 + lo < 0 ? (int)(-g0) : lo;                            // positions [ca, cb) are converted, the rest of [lo, 3071) is zero:
+    int ca = g0 + lo < 0 ? (int)(-g0) : lo;                                  // positions [ca, cb) are converted, the rest of [lo, 3071) is zero:
     const long long pe = P - g0;                                             // before sample 0, from sample P on, or of no use below n
-    const int cb = pe < top ? (pe < 0 ? 0 : (int)pe) : top;
+    int cb = pe < top ? (pe < 0 ? 0 : (int)pe) : top;
+    const long long tq = g0 - st;                                            // the term time of ys[0]
+    const G cg = gate.at(tq);
+    if constexpr (G::kOn) {
+      const long long ta = (long long)tile0 - k0, tb = ta + (left < DS_TILE ? left : DS_TILE);
+      if (tb <= gate.on) break;
+      if (gate.silent(ta, tb, kc)) continue;
+      ca = (int)clampll(gate.on - tq, ca, DS_SPAN);                          // positions before `on` and from `off` on are closed
+      cb = (int)clampll(gate.off - tq, 0, cb);
+    }
     __syncthreads();                                                         // the last readers of ys / hs (or of the float tile) are done
     for (int i = lo + tid; i < DS_TILE + DR_CHUNK - 1; i += DM_TPB) {
       if (i < ca || i >= cb) ys[i] = 0.0;
@@ -486,9 +565,9 @@ __device__ __forceinline__ void speed_reverb_tile(const DmCorpus& c, const ConvS
       __syncthreads();
       for (int i0 = a; i0 < e; i0 += DS_TILE) {
         if (e - i0 > DS_TILE / 2) {
-          convert_group<DM_PER>(lds.a.xs, span, b0, tp, L, M, Kc, g0, i0, e - i0 > DS_TILE ? i0 + DS_TILE : e, ys);
+          convert_group<DM_PER>(lds.a.xs, span, b0, tp, L, M, Kc, g0, i0, e - i0 > DS_TILE ? i0 + DS_TILE : e, ys, cg);
         } else {
-          convert_group<DM_PER / 2>(lds.a.xs, span, b0, tp, L, M, Kc, g0, i0, e, ys);
+          convert_group<DM_PER / 2>(lds.a.xs, span, b0, tp, L, M, Kc, g0, i0, e, ys, cg);
         }
       }
     }
@@ -508,6 +587,43 @@ __device__ __forceinline__ void speed_reverb_tile(const DmCorpus& c, const ConvS
 
 // a term may carry a converter (conv >= 0), a response (rir >= 0), both or neither.  One of the two alone takes the code of the form that has
 // only that one (convert_tile, reverb_tile) in the first 32 768 bytes of the LDS, neither takes term_value: each with that form's bits.
+// The body the two forms below share.  Under a gate, a tile none of whose outputs below n reaches an open sample - it lies past off + K - 1 or ends at or
+// before on - is eight +0 per thread without a load, a conversion or a chunk; the turn and K are workgroup-uniform, so every thread of the
+// workgroup leaves here or none does, and scale8 of the zeros keeps the bits the long way round gives.
+template <class G>
+__device__ __forceinline__ void speed_reverb_value8(const DmCorpus& c, const ConvSet& cv, const DrBank& bk, int utt, int start, float norm, float gain,
+                                                    int conv, int rir, int taps, const G& gate, int tile0, int t0, int n, float v[8]) {
+  const bool perturbed = conv >= 0 && cv.NC >= 1;
+  if constexpr (G::kOn) {
+    const int K = rir < 0 ? 1 : DrResp(bk, rir, taps).K;
+    const int end = n - tile0 < DS_TILE ? n : tile0 + DS_TILE;
+    if (__builtin_amdgcn_readfirstlane(gate.silent(tile0, end, K))) {
+      const float x[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      scale8(x, norm, gain, v);
+      return;
+    }
+  }
+  if (!perturbed && rir < 0) {
+    term_value(c, utt, start, norm, gain, t0 < n ? t0 : 0, v, gate.at(tile0), t0 - tile0);
+    return;
+  }
+  __shared__ SrLds lds;
+  float x[8];
+  if (!perturbed) {
+    reverb_tile(c, bk, rir, taps, utt, start, tile0, n, lds.a, x, gate);
+  } else if (rir < 0) {
+    const int k = conv >= cv.NC ? cv.NC - 1 : conv;
+    float* ys = reinterpret_cast<float*>(lds.a.hs);
+    convert_tile(c, utt, start, cv.taps[k], cv.L[k], cv.M[k], cv.K[k], tile0, n, lds.a.xs, ys, gate.at(tile0));
+    const float4 lo = *reinterpret_cast<const float4*>(ys + threadIdx.x * DM_PER);
+    const float4 hi = *reinterpret_cast<const float4*>(ys + threadIdx.x * DM_PER + 4);
+    x[0] = lo.x, x[1] = lo.y, x[2] = lo.z, x[3] = lo.w, x[4] = hi.x, x[5] = hi.y, x[6] = hi.z, x[7] = hi.w;
+  } else {
+    speed_reverb_tile(c, cv, bk, conv, rir, taps, utt, start, tile0, n, lds, x, gate);
+  }
+  scale8(x, norm, gain, v);
+}
+
 struct SpeedReverbForm {
   static constexpr bool kTiled = true;
   DmCorpus c;
@@ -523,26 +639,38 @@ struct SpeedReverbForm {
   }
   __device__ __forceinline__ static bool same(Cols a, Cols b) { return a.conv == b.conv && a.rir == b.rir && a.taps == b.taps; }
   __device__ __forceinline__ void value8(int utt, int start, float norm, float gain, Cols t, int tile0, int t0, int n, float v[8]) const {
-    const bool perturbed = t.conv >= 0 && cv.NC >= 1;
-    if (!perturbed && t.rir < 0) {
-      term_value(c, utt, start, norm, gain, t0 < n ? t0 : 0, v);
-      return;
-    }
-    __shared__ SrLds lds;
-    float x[8];
-    if (!perturbed) {
-      reverb_tile(c, bk, t.rir, t.taps, utt, start, tile0, n, lds.a, x);
-    } else if (t.rir < 0) {
-      const int k = t.conv >= cv.NC ? cv.NC - 1 : t.conv;
-      float* ys = reinterpret_cast<float*>(lds.a.hs);
-      convert_tile(c, utt, start, cv.taps[k], cv.L[k], cv.M[k], cv.K[k], tile0, n, lds.a.xs, ys);
-      const float4 lo = *reinterpret_cast<const float4*>(ys + threadIdx.x * DM_PER);
-      const float4 hi = *reinterpret_cast<const float4*>(ys + threadIdx.x * DM_PER + 4);
-      x[0] = lo.x, x[1] = lo.y, x[2] = lo.z, x[3] = lo.w, x[4] = hi.x, x[5] = hi.y, x[6] = hi.z, x[7] = hi.w;
-    } else {
-      speed_reverb_tile(c, cv, bk, t.conv, t.rir, t.taps, utt, start, tile0, n, lds, x);
-    }
-    scale8(x, norm, gain, v);
+    speed_reverb_value8(c, cv, bk, utt, start, norm, gain, t.conv, t.rir, t.taps, NoGate{}, tile0, t0, n, v);
+  }
+};
+
+// ---- turn-taking: SpeedReverbForm's term with a turn [on, off), the talker gated before the room --------------------------
+// The LDS, the geometry and the code of SpeedReverbForm; the gate rides through the four staging paths.  A bank of R = 0 responses makes every rir none.
+constexpr int DT_MAX_RAMP = 4096;
+constexpr int DT_FAR = 1 << 30;                         // on and off are clamped to [-DT_FAR, DT_FAR]: (-DT_FAR, DT_FAR) is the open turn
+
+struct TurnsForm {
+  static constexpr bool kTiled = true;
+  DmCorpus c;
+  ConvSet cv;
+  DrBank bk;
+  const float* ramp;
+  int RL;
+  struct Cols {
+    int conv, rir, taps, on, off;
+  };
+  __device__ __forceinline__ static int turn_clamp(int v) { return v < -DT_FAR ? -DT_FAR : (v > DT_FAR ? DT_FAR : v); }
+  __device__ __forceinline__ static Cols cols(const int* __restrict__ term_conv, const int* __restrict__ term_rir, const int* __restrict__ term_taps,
+                                              const int* __restrict__ term_on, const int* __restrict__ term_off, int j) {
+    return {__builtin_amdgcn_readfirstlane(term_conv[j]), __builtin_amdgcn_readfirstlane(term_rir[j]),
+            __builtin_amdgcn_readfirstlane(term_taps[j]), turn_clamp(__builtin_amdgcn_readfirstlane(term_on[j])),
+            turn_clamp(__builtin_amdgcn_readfirstlane(term_off[j]))};
+  }
+  __device__ __forceinline__ static bool same(Cols a, Cols b) {
+    return a.conv == b.conv && a.rir == b.rir && a.taps == b.taps && a.on == b.on && a.off == b.off;
+  }
+  __device__ __forceinline__ void value8(int utt, int start, float norm, float gain, Cols t, int tile0, int t0, int n, float v[8]) const {
+    const TurnGate gate = {t.on, t.off, RL, ramp};
+    speed_reverb_value8(c, cv, bk, utt, start, norm, gain, t.conv, bk.R >= 1 ? t.rir : -1, t.taps, gate, tile0, t0, n, v);
   }
 };
 
@@ -705,7 +833,7 @@ extern "C" int sepr_corpus_energy(const short* buf16, long long total16, const f
 
 namespace sepr {
 namespace {
-// what the four mixing entries share: the checks of the common arguments, the corpus and the target rows as kernel arguments, the grid,
+// what the five mixing entries share: the checks of the common arguments, the corpus and the target rows as kernel arguments, the grid,
 // the dispatch on S and the launch check.  An entry checks its own arguments BEFORE it calls this and passes them in `form` and `col`;
 // every refusal is SEPR_EINVAL, so which check comes first does not show.
 template <class F, class... Col>
@@ -726,7 +854,7 @@ int dynmix_launch(const short* buf16, long long total16, const float* buf32, lon
   hipStream_t st = static_cast<hipStream_t>(stream);
   form.c = {buf16, buf32, offsets, total16, total32, N16, N};
   const dim3 grid((unsigned)cdiv(Tmax, DS_TILE), (unsigned)B);
-  // `head`: the kernel's leading arguments, its corpus and banks; `col`: term_conv (speed), term_rir and term_taps (reverb), all three (speed-reverb), none (plain)
+  // `head`: the kernel's leading arguments, its corpus and banks; `col`: term_conv (speed), term_rir and term_taps (reverb), all three (speed-reverb), those and term_on, term_off (turns), none (plain)
   auto go = [&](auto kernel, const auto&... head) {
     hipLaunchKernelGGL(kernel, grid, dim3(DM_TPB), 0, st, head..., term_utt, term_start, term_norm, term_gain, col..., n, M, Tmax, mix, rows);
   };
@@ -795,4 +923,21 @@ extern "C" int sepr_dynmix_speed_reverb_fwd(const short* buf16, long long total1
   if (!term_rir || !term_taps || bank_bad(rir, rir_total, rir_off, R, form.bk)) return SEPR_EINVAL;
   return dynmix_launch(buf16, total16, buf32, total32, offsets, N16, N, term_utt, term_start, term_norm, term_gain, n, B, M, S, Tmax, mix, src,
                        stream, form, "dynmix speed-reverb kernel", term_conv, term_rir, term_taps);
+}
+
+extern "C" int sepr_dynmix_turns_fwd(const short* buf16, long long total16, const float* buf32, long long total32, const long long* offsets, int N16,
+                                     int N, const int* term_utt, const int* term_start, const float* term_norm, const float* term_gain,
+                                     const int* term_conv, const int* term_rir, const int* term_taps, const int* term_on, const int* term_off,
+                                     const int* n, int B, int M, int S, int Tmax, float* mix, float* const* src, const float* const* conv_taps,
+                                     const int* conv_L, const int* conv_M, const int* conv_K, int NC, const float* rir, long long rir_total,
+                                     const long long* rir_off, int R, const float* ramp, int RL, sepr_stream_t stream) {
+  using namespace sepr;
+  TurnsForm form = {};
+  if (!term_conv || !pp_fill(conv_taps, conv_L, conv_M, conv_K, NC, DS_POLICY, form.cv)) return SEPR_EINVAL;
+  if (!term_rir || !term_taps || R < 0 || (R > 0 && bank_bad(rir, rir_total, rir_off, R, form.bk))) return SEPR_EINVAL;      // R = 0: no bank
+  if (!term_on || !term_off || RL < 0 || RL > DT_MAX_RAMP || (RL > 0 && !ramp) || reinterpret_cast<uintptr_t>(ramp) % 4 != 0) return SEPR_EINVAL;
+  form.ramp = ramp;
+  form.RL = RL;
+  return dynmix_launch(buf16, total16, buf32, total32, offsets, N16, N, term_utt, term_start, term_norm, term_gain, n, B, M, S, Tmax, mix, src,
+                       stream, form, "dynmix turns kernel", term_conv, term_rir, term_taps, term_on, term_off);
 }

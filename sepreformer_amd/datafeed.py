@@ -30,6 +30,10 @@ Both: with ``speed_reverb=True`` the three planners tak
 the PERTURBED utterance under the response - the talker speaks faster or slower, then the room answers - made inside the one launch
 (``sepr_dynmix_speed_reverb_fwd``).
 
+Turn-taking: the three planners take ``turns=Turns(overlap=(lo, hi), ramp=RL)`` - alone or with any of the above - and give
+every source a turn ``[on, off)`` of the example, so that the talkers overlap for a drawn fraction of their turns instead of the whole crop; the gate
+acts on the talker inside the launch (``sepr_dynmix_turns_fwd``), before the room, which therefore rings on after the talker stops.
+
 Shuffling: the reference shuffles through ``DataLoader(shuffle=True)`` (torch's generator); this feed takes the epoch's key order
 from the caller (``keys=``), and by default draws a permutation from its own ``random.Random`` before every epoch.
 """
@@ -48,10 +52,13 @@ from . import resample as R_
 from .reverb import RirBank
 
 # (utterance index, start sample, norm factor, gain), plus the speed in percent when the planner was given speeds, or plus
-# (speed, RIR index or -1, taps) when it was given an RIR bank - the speed 100 unless it was given both (speed_reverb=True)
+# (speed, RIR index or -1, taps) when it was given an RIR bank - the speed 100 unless it was given both (speed_reverb=True) - or plus
+# (speed, RIR index or -1, taps, on, off) when it was given turns: the turn [on, off) in output samples of the example
 Term = Union[Tuple[int, int, np.float32, np.float32], Tuple[int, int, np.float32, np.float32, int],
-             Tuple[int, int, np.float32, np.float32, int, int, int]]
+             Tuple[int, int, np.float32, np.float32, int, int, int], Tuple[int, int, np.float32, np.float32, int, int, int, int, int]]
 _ONE = np.float32(1.0)
+TURN_FAR = 1 << 30                                     # (-TURN_FAR, TURN_FAR) is the open turn: the gate is 1 wherever it can be evaluated
+MAX_TURN_RAMP = 4096                                   # the longest ramp table sepr_dynmix_turns_fwd takes
 
 
 class Example(NamedTuple):
@@ -61,7 +68,7 @@ class Example(NamedTuple):
     tgt: Tuple[Term, ...]       # S target terms
 
 
-class BatchPlan(NamedTuple):
+class _PlanFields(NamedTuple):
     keys: List[str]
     n: np.ndarray               # int32 [B], descending
     utt: np.ndarray             # int32 [B, M + S]: the M mixture terms, then the S target terms
@@ -73,6 +80,31 @@ class BatchPlan(NamedTuple):
     speed: Optional[np.ndarray] = None      # int32 [B, M + S] percent (100 = as recorded), None: planned without speeds
     rir: Optional[np.ndarray] = None        # int32 [B, M + S] index into the RIR bank (-1 = none), None: planned without RIRs
     taps: Optional[np.ndarray] = None       # int32 [B, M + S] leading samples of that RIR the term is convolved with
+
+
+class BatchPlan(_PlanFields):
+    """The tuple above and, beside it, the turn columns of a plan with turns: ``on`` and ``off``, int32 ``[B, M + S]``,
+    the term's turn ``[on, off)`` in output samples of the example; ``None``: planned without turns.  They are keyword arguments and
+    attributes, not fields of the tuple - its eleven fields, their order and their defaults are what a plan without turns has always had,
+    and code that builds or unpacks one by position keeps working.  ``_replace`` and ``_asdict`` take and keep them.  Whatever goes through
+    the bare tuple does NOT: ``BatchPlan(*plan)``, ``_make``, unpacking, ``==`` and ``hash`` see the eleven fields only, so a plan rebuilt by
+    position has lost its turns and would take the entry without them - carry ``on=plan.on, off=plan.off`` along, or use ``_replace``."""
+    on: Optional[np.ndarray] = None
+    off: Optional[np.ndarray] = None
+
+    def __new__(cls, *args, on: Optional[np.ndarray] = None, off: Optional[np.ndarray] = None, **kw):
+        self = super().__new__(cls, *args, **kw)
+        if (on is None) != (off is None):
+            raise ValueError("a plan with turns carries both columns, on and off")
+        self.on, self.off = on, off
+        return self
+
+    def _replace(self, **kw):
+        on, off = kw.pop("on", self.on), kw.pop("off", self.off)
+        return BatchPlan(*super()._replace(**kw), on=on, off=off)
+
+    def _asdict(self):
+        return {**super()._asdict(), "on": self.on, "off": self.off}
 
 
 def parse_scp(path: str) -> Dict[str, str]:
@@ -321,10 +353,68 @@ def _same_device(a: Optional[torch.device], b: Optional[torch.device]) -> bool:
     return idx(a) == idx(b)
 
 
+class Turns(NamedTuple):
+    """What a planner is given to make partially overlapped talkers: ``overlap = (lo, hi)`` in [0, 1], the range the
+    example's overlap ``rho`` is drawn from (1 = everybody talks throughout, today's mixture; 0 = back-to-back turns), and ``ramp``, the samples
+    of the raised-cosine fade at either end of a turn (0 = a hard gate)."""
+    overlap: Tuple[float, float] = (0.0, 1.0)
+    ramp: int = 80
+
+
+def parse_turns(text: str, ramp: int = 80) -> Turns:
+    """``"0:1"`` (LO:HI) or ``"0.5"`` (one value) -> ``Turns``."""
+    lo, _, hi = text.partition(":")
+    return _check_turns(Turns((float(lo), float(hi if hi else lo)), int(ramp)))
+
+
+def _check_turns(turns: Turns) -> Turns:
+    lo, hi = (float(v) for v in turns.overlap)
+    if not (0.0 <= lo <= hi <= 1.0):
+        raise ValueError(f"turns: overlap = {turns.overlap!r}, expected 0 <= lo <= hi <= 1")
+    if isinstance(turns.ramp, bool) or not isinstance(turns.ramp, (int, np.integer)) or not (0 <= int(turns.ramp) <= MAX_TURN_RAMP):
+        raise ValueError(f"turns: ramp = {turns.ramp!r}, expected an integer in 0 .. {MAX_TURN_RAMP}")
+    return turns
+
+
+def turn_ramp(RL: int) -> np.ndarray:
+    """The gate's table (include/sepr.h): float32 ``[RL]``, ``float32(0.5 - 0.5 cos(pi (i + 0.5) / RL))`` formed in float64."""
+    RL = int(RL)
+    if not (0 <= RL <= MAX_TURN_RAMP):
+        raise ValueError(f"a ramp of {RL} samples: 0 .. {MAX_TURN_RAMP}")
+    i = np.arange(RL, dtype=np.float64)
+    return (0.5 - 0.5 * np.cos(np.pi * (i + 0.5) / max(RL, 1))).astype(np.float32)
+
+
+def _draw_turns(rng: random.Random, turns: Optional[Turns], S: int, n: int) -> Optional[List[Tuple[int, int]]]:
+    """The sources' turns of an example of ``n`` samples, in source order; no draw without ``turns``.  Two draws, after every other draw of the
+    example: ``rho = rng.uniform(lo, hi)``, then the order of the talkers, ``rng.sample(range(S), S)``.  Every turn is
+    ``d = min(n, ceil(n / (S - (S - 1) rho)))`` samples long and the s-th talker's begins at ``s h``, ``h = (n - d) // (S - 1)``: together they
+    cover ``[0, n)``, neighbours overlap by ``d - h``, every source is active for at least ``n / S`` samples.  A turn that begins at or before
+    sample 0 began before the window (``on = -TURN_FAR``: no fade-in, the history kept), one that reaches ``n`` - and the last talker's - goes on
+    after it (``off = TURN_FAR``)."""
+    if turns is None:
+        return None
+    _check_turns(turns)
+    rho = rng.uniform(float(turns.overlap[0]), float(turns.overlap[1]))
+    order = rng.sample(range(S), S)
+    d = min(n, math.ceil(n / (S - (S - 1) * rho)))
+    h = (n - d) // (S - 1)
+    out: List[Tuple[int, int]] = [(0, 0)] * S
+    for s, who in enumerate(order):
+        on, off = s * h, s * h + d
+        out[who] = (-TURN_FAR if on <= 0 else on, TURN_FAR if off >= n or s == S - 1 else off)
+    return out
+
+
+_OPEN = (-TURN_FAR, TURN_FAR)                          # the turn of a term that is not gated inside a plan with turns (the noise)
 _NO_RIR = (-1, 1)                                      # a term that is not reverberated inside a plan with RIRs (the noise)
 
 
-def _terms(utts, starts, norms, gains, sp, rv=None) -> Tuple[Term, ...]:
+def _terms(utts, starts, norms, gains, sp, rv=None, tn=None) -> Tuple[Term, ...]:
+    if tn is not None:
+        k = len(tn)
+        return tuple((u, s, nf, g, p, r, t, on, off)
+                     for u, s, nf, g, p, (r, t), (on, off) in zip(utts, starts, norms, gains, sp or [100] * k, rv or [_NO_RIR] * k, tn))
     if rv is not None:
         return tuple((u, s, nf, g, p, r, k) for u, s, nf, g, p, (r, k) in zip(utts, starts, norms, gains, sp or [100] * len(rv), rv))
     if sp is None:
@@ -335,14 +425,15 @@ def _terms(utts, starts, norms, gains, sp, rv=None) -> Tuple[Term, ...]:
 def plan_wsj0(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs: Sequence[str] = ("s1", "s2"),
               accept: Callable[[str, str], bool] = wsj0_distinct_speakers, crop: bool = True,
               speeds: Optional[Sequence[int]] = None, rirs: Optional[RirBank] = None, target: Union[str, int] = "direct",
-              speed_reverb: bool = False) -> Example:
+              speed_reverb: bool = False, turns: Optional[Turns] = None) -> Example:
     """``SepReformer_Large_DM_WSJ0/dataset.py:84-139``.  ``crop=False`` is the reference's "test" partition (no ``max_len`` crop).
     ``speeds``: directly after the draw that orders the two sources, one ``rng.choice(speeds)`` per source; the perturbed lengths
     replace the stored ones, the norm factors keep the stored utterances' RMS (section 5e-2).  ``rirs``: at that same position, one
     ``rng.randrange(len(rirs))`` per source; the mixture terms take the whole impulse response, the target terms what ``target`` says
     (``_target_rv``); lengths and norm factors stay the stored utterances' (section 5e-3).  Both take ``speed_reverb=True``: the speeds are
     drawn first, then the responses; every later draw uses the perturbed lengths; a source term is the perturbed utterance under the
-    whole response and its target the same speed under what ``target`` says (section 5e-5)."""
+    whole response and its target the same speed under what ``target`` says (section 5e-5).  ``turns``: after every other draw of the example,
+    the two draws of ``_draw_turns``; each source's mixture term and its target carry the source's turn (section 5e-6)."""
     keys = corpus.roles[srcs[0]]
     while True:
         key_random = rng.choice(keys)
@@ -362,20 +453,21 @@ def plan_wsj0(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs: 
     if crop and n > max_len:
         st = rng.randint(0, n - max_len)
         starts, n = [s + st for s in starts], max_len
+    tn = _draw_turns(rng, turns, 2, n)
     if rv is not None:
-        return Example(key, n, _terms(utts, starts, norms, gains, sp, _mix_rv(rirs, rv)),
-                       _terms(utts, starts, norms, gains, sp, _target_rv(rirs, rv, target)))
-    terms = _terms(utts, starts, norms, gains, sp)
+        return Example(key, n, _terms(utts, starts, norms, gains, sp, _mix_rv(rirs, rv), tn),
+                       _terms(utts, starts, norms, gains, sp, _target_rv(rirs, rv, target), tn))
+    terms = _terms(utts, starts, norms, gains, sp, None, tn)
     return Example(key, n, terms, terms)
 
 
 def plan_wham(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs: Sequence[str] = ("s1", "s2"), noise: str = "noise",
               speeds: Optional[Sequence[int]] = None, rirs: Optional[RirBank] = None, target: Union[str, int] = "direct",
-              speed_reverb: bool = False) -> Example:
+              speed_reverb: bool = False, turns: Optional[Turns] = None) -> Example:
     """``SepReformer_Large_DM_WHAM/dataset.py``: no speaker rule, the noise of ``key`` normalised to the first source with a gain of
     its own from U(-5, 5) dB, everything cropped to ``min(max_len, lengths)`` at independent random indices.  ``speeds``: as in
     ``plan_wsj0``; the noise is not perturbed.  ``rirs`` / ``target`` / ``speed_reverb``: as in ``plan_wsj0``; the noise is not
-    reverberated."""
+    reverberated.  ``turns``: as in ``plan_wsj0``; the noise keeps the open turn."""
     key_random = rng.choice(corpus.roles[srcs[0]])
     i1, i2 = (0, 1) if rng.random() > 0.5 else (1, 0)
     sp = _draw_speeds(rng, speeds, 2)
@@ -394,22 +486,26 @@ def plan_wham(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs: 
     min_len = min([max_len] + lens)
     starts = [rng.randint(0, ln - min_len) for ln in lens]
     n = min_len - min_len % 4
+    tn = _draw_turns(rng, turns, 2, n)
+    tm = None if tn is None else tn + [_OPEN]
     if rv is not None:
-        return Example(key, n, _terms(utts, starts, norms, gains, sp, _mix_rv(rirs, rv) + [_NO_RIR]),
-                       _terms(utts[:2], starts, norms, gains, sp, _target_rv(rirs, rv, target)))
-    terms = _terms(utts, starts, norms, gains, sp)
+        return Example(key, n, _terms(utts, starts, norms, gains, sp, _mix_rv(rirs, rv) + [_NO_RIR], tm),
+                       _terms(utts[:2], starts, norms, gains, sp, _target_rv(rirs, rv, target), tn))
+    terms = _terms(utts, starts, norms, gains, sp, None, tm)
     return Example(key, n, terms, terms[:2])
 
 
 def plan_whamr(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs: Sequence[str] = ("s1", "s2"),
                reverb: Sequence[str] = ("s1_reverb", "s2_reverb"), noise: str = "noise", speeds: Optional[Sequence[int]] = None,
-               rirs: Optional[RirBank] = None, target: Union[str, int] = "direct", speed_reverb: bool = False) -> Example:
+               rirs: Optional[RirBank] = None, target: Union[str, int] = "direct", speed_reverb: bool = False,
+               turns: Optional[Turns] = None) -> Example:
     """``SepReformer_Large_DM_WHAMR/dataset.py:87-154``: the mixture is the two reverberant twins plus the noise (gains U(-3, 3) dB,
     noise U(-6, 3) dB), the targets are the anechoic sources with their twins' norm factor, gain and crop index.  ``speeds``: as in
     ``plan_wsj0``; a dry source and its reverberant twin share one speed, the noise is not perturbed.  ``rirs`` / ``target``: as in
     ``plan_wsj0``; the mixture is then the DRY sources reverberated in the launch plus the noise, and the ``reverb`` roles are never
     looked up - a corpus without pre-rendered twins serves.  ``speed_reverb=True`` with both: the dry sources perturbed and then
-    reverberated in the launch (playing a pre-rendered twin faster, the other order, is ``speeds=`` alone)."""
+    reverberated in the launch (playing a pre-rendered twin faster, the other order, is ``speeds=`` alone).  ``turns``: as in ``plan_wsj0``; the noise
+    keeps the open turn.  With ``rirs`` the room rings on after a talker stops; without, a pre-rendered twin is gated as recorded, tail and all."""
     key_random = rng.choice(corpus.roles[srcs[0]])
     i1, i2 = (0, 1) if rng.random() > 0.5 else (1, 0)
     sp = _draw_speeds(rng, speeds, 2)
@@ -429,12 +525,14 @@ def plan_whamr(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs:
     starts = [rng.randint(0, ln - min_len) for ln in lens]
     nstart = rng.randint(0, int(corpus.lengths[un]) - min_len)
     n = min_len - min_len % 4
+    tn = _draw_turns(rng, turns, 2, n)
+    tm = None if tn is None else tn + [_OPEN]
     if rv is not None:
         return Example(key, n, _terms(dry + [un], starts + [nstart], norms + [nnorm], gains + [ngain], None if sp is None else sp + [100],
-                                      _mix_rv(rirs, rv) + [_NO_RIR]),
-                       _terms(dry, starts, norms, gains, sp, _target_rv(rirs, rv, target)))
-    mix = _terms(wet + [un], starts + [nstart], norms + [nnorm], gains + [ngain], None if sp is None else sp + [100])
-    tgt = _terms(dry, starts, norms, gains, sp)
+                                      _mix_rv(rirs, rv) + [_NO_RIR], tm),
+                       _terms(dry, starts, norms, gains, sp, _target_rv(rirs, rv, target), tn))
+    mix = _terms(wet + [un], starts + [nstart], norms + [nnorm], gains + [ngain], None if sp is None else sp + [100], None, tm)
+    tgt = _terms(dry, starts, norms, gains, sp, None, tn)
     return Example(key, n, mix, tgt)
 
 
@@ -458,11 +556,14 @@ def plan_direct(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs
     return Example(key, n, mixt, tgt)
 
 
-def collate_plan(corpus: Corpus, examples: Sequence[Example], rirs: Optional[RirBank] = None, speed_reverb: bool = False) -> BatchPlan:
+def collate_plan(corpus: Corpus, examples: Sequence[Example], rirs: Optional[RirBank] = None, speed_reverb: bool = False,
+                 turns: bool = False) -> BatchPlan:
     """Order the examples by length, longest first (``_collate``'s stable ``sorted(..., reverse=True)``), check every term against its
     utterance - at its speed - and, for a reverberant term, against the bank ``rirs``, and lay the table out as the kernel reads it.
     ``speed_reverb``: terms may carry a speed and a response; a plan with responses then has ``speed``, ``rir`` and ``taps`` all set, whatever
-    speeds were drawn (so the batches of one feed share one table layout and one entry)."""
+    speeds were drawn (so the batches of one feed share one table layout and one entry).  A term that carries a turn (a 9-tuple) gives the plan
+    its ``on`` and ``off`` columns, a term without one the open turn; ``turns``: the plan has the columns whatever its terms carry.  In such a
+    plan a term's speed and response count only where they are set (a speed other than 100, a response index >= 0)."""
     egs = sorted(examples, key=lambda e: e.n, reverse=True)
     M, S = len(egs[0].mix), len(egs[0].tgt)
     if not (2 <= S <= 3 and S <= M <= S + 1):
@@ -472,7 +573,9 @@ def collate_plan(corpus: Corpus, examples: Sequence[Example], rirs: Optional[Rir
     norm, gain = np.zeros((B, M + S), np.float32), np.zeros((B, M + S), np.float32)
     speed = np.full((B, M + S), 100, np.int32)
     rir, taps = np.full((B, M + S), -1, np.int32), np.ones((B, M + S), np.int32)
+    on, off = np.full((B, M + S), -TURN_FAR, np.int32), np.full((B, M + S), TURN_FAR, np.int32)
     any_speed = any_rir = False
+    any_turn = bool(turns)
     for b, e in enumerate(egs):
         if len(e.mix) != M or len(e.tgt) != S:
             raise ValueError("every example of a batch needs the same number of terms")
@@ -482,7 +585,10 @@ def collate_plan(corpus: Corpus, examples: Sequence[Example], rirs: Optional[Rir
             u, s, nf, g = term[:4]
             p = int(term[4]) if len(term) > 4 else 100
             any_speed |= len(term) == 5 or p != 100
-            if len(term) > 5:
+            if len(term) > 7:
+                any_turn = True
+                on[b, j], off[b, j] = max(-TURN_FAR, min(TURN_FAR, int(term[7]))), max(-TURN_FAR, min(TURN_FAR, int(term[8])))
+            if len(term) > 5 and (len(term) == 7 or int(term[5]) >= 0):
                 any_rir = True
                 r, k = int(term[5]), int(term[6])
                 if rirs is None:
@@ -498,19 +604,32 @@ def collate_plan(corpus: Corpus, examples: Sequence[Example], rirs: Optional[Rir
         raise ValueError("a plan with speeds and RIRs takes speed_reverb=True (each source perturbed, then reverberated)")
     any_speed |= any_rir and speed_reverb
     return BatchPlan([e.key for e in egs], np.array([e.n for e in egs], np.int32), utt, start, norm, gain, M, S, speed if any_speed else None,
-                     rir if any_rir else None, taps if any_rir else None)
+                     rir if any_rir else None, taps if any_rir else None, on=on if any_turn else None, off=off if any_turn else None)
 
 
-def table_layout(B: int, NT: int, speeds: bool = False, rirs: bool = False) -> Dict[str, Tuple[int, int]]:
+def table_layout(B: int, NT: int, speeds: bool = False, rirs: bool = False, turns: bool = False) -> Dict[str, Tuple[int, int]]:
     """The device table of a plan, the one place that says where its blocks lie: name -> (first int32 word, words), in memory order
-    ``utt | start | norm | gain | n``, then ``conv`` for a plan with speeds, then ``rir | taps`` for one with RIRs."""
-    names = ("utt", "start", "norm", "gain", "n") + (("conv",) if speeds else ()) + (("rir", "taps") if rirs else ())
+    ``utt | start | norm | gain | n``, then ``conv`` for a plan with speeds, then ``rir | taps`` for one with RIRs.  A plan with turns has one
+    layout whatever else it carries - its one entry reads every column: ``... | conv | rir | taps | on | off``."""
+    speeds, rirs = speeds or turns, rirs or turns
+    names = ("utt", "start", "norm", "gain", "n") + (("conv",) if speeds else ()) + (("rir", "taps") if rirs else ()) + (("on", "off") if turns else ())
     words = [B if name == "n" else B * NT for name in names]
     return {name: (sum(words[:k]), words[k]) for k, name in enumerate(names)}
 
 
-def _table_words(B: int, NT: int, speeds: bool = False, rirs: bool = False) -> int:
-    return sum(words for _, words in table_layout(B, NT, speeds, rirs).values())
+def _table_words(B: int, NT: int, speeds: bool = False, rirs: bool = False, turns: bool = False) -> int:
+    return sum(words for _, words in table_layout(B, NT, speeds, rirs, turns).values())
+
+
+def _plan_layout(plan: BatchPlan) -> Tuple[int, int, bool, bool, bool]:
+    """The arguments of ``table_layout`` for ``plan``."""
+    return (*plan.utt.shape, plan.speed is not None, plan.rir is not None, plan.on is not None)
+
+
+def ramp_table(dev, RL: int) -> torch.Tensor:
+    """``turn_ramp(RL)`` on ``dev``: the gate's table as ``mix_batch`` takes it (``ramp=``).  One host-to-device copy - a feed makes it once, when
+    it is built; make it before a graph capture, not inside one."""
+    return torch.from_numpy(turn_ramp(RL)).to(dev)
 
 
 def plan_speeds(plan: BatchPlan) -> List[int]:
@@ -532,13 +651,17 @@ def _converter_args(dev: torch.device, speeds: Sequence[int]):
 
 def mix_batch(corpus: Corpus, plan: BatchPlan, Tmax: Optional[int] = None, mix: Optional[torch.Tensor] = None,
               src: Optional[Sequence[torch.Tensor]] = None, table: Optional[torch.Tensor] = None,
-              speeds: Optional[Sequence[int]] = None, rirs: Optional[RirBank] = None):
+              speeds: Optional[Sequence[int]] = None, rirs: Optional[RirBank] = None,
+              ramp: Union[int, torch.Tensor, None] = None):
     """One ``sepr_dynmix_fwd`` launch for ``plan`` on the corpus's device (current stream) -> ``(mix [B, Tmax], [src_s [B, Tmax]])``;
     a plan that carries speeds goes through ``sepr_dynmix_speed_fwd``, one that carries RIRs through ``sepr_dynmix_reverb_fwd`` with the
     bank ``rirs``, which must be on the corpus's device, one that carries both through ``sepr_dynmix_speed_reverb_fwd``.  ``table``: an int32 device tensor that already holds the plan in
     the kernel's layout (``DynamicMixFeed`` stages it through pinned memory); without it the plan is copied from pageable memory.
     ``speeds``: the converter set the table's index block refers to (``pack_table``); default: the plan's own speeds.  A captured launch
-    keeps the set it was captured with, so a table rewritten between replays must be packed against that set."""
+    keeps the set it was captured with, so a table rewritten between replays must be packed against that set.  A plan that carries turns
+    (``plan.on``) always goes through ``sepr_dynmix_turns_fwd``, whatever else it carries, with the gate's table ``ramp`` (required for such a
+    plan): the device tensor ``ramp_table(device, RL)``, or the length ``RL`` itself (0 = a hard gate), which uploads the table in this call -
+    one pageable copy per call, so a captured launch and a loop pass the tensor."""
     dev = corpus.device
     if dev is None:
         raise RuntimeError("the corpus is not on the HIP device (there is no CPU path)")
@@ -551,9 +674,15 @@ def mix_batch(corpus: Corpus, plan: BatchPlan, Tmax: Optional[int] = None, mix: 
             raise ValueError("the plan carries RIRs: pass the bank (rirs=)")
         if not _same_device(rirs.device, dev):
             raise ValueError(f"the RIR bank is on {rirs.device}, the corpus on {dev}")
+    if plan.on is not None:
+        if isinstance(ramp, (int, np.integer)) and not isinstance(ramp, bool) and 0 <= int(ramp) <= MAX_TURN_RAMP:
+            ramp = ramp_table(dev, int(ramp))
+        if not isinstance(ramp, torch.Tensor) or ramp.dtype != torch.float32 or ramp.dim() != 1 or ramp.numel() > MAX_TURN_RAMP \
+                or not ramp.is_contiguous() or not _same_device(ramp.device, dev):
+            raise ValueError(f"the plan carries turns: pass the gate's ramp (ramp_table(device, RL), or RL = 0 .. {MAX_TURN_RAMP}), got {ramp!r}")
     if table is None:
         table = torch.from_numpy(pack_table(plan, speeds)).to(dev)
-    if table.numel() < _table_words(B, NT, plan.speed is not None, plan.rir is not None):
+    if table.numel() < _table_words(*_plan_layout(plan)):
         raise ValueError("the device table is shorter than the plan's layout")
     if mix is None:
         mix = torch.empty(B, Tmax, dtype=torch.float32, device=dev)
@@ -565,10 +694,14 @@ def mix_batch(corpus: Corpus, plan: BatchPlan, Tmax: Optional[int] = None, mix: 
             raise ValueError(f"outputs must be contiguous float32 [{B}, {Tmax}] tensors on {dev}")
     if len(src) != plan.S:
         raise ValueError(f"{plan.S} target rows expected")
-    at = {name: table.data_ptr() + 4 * first for name, (first, _) in table_layout(B, NT, plan.speed is not None, plan.rir is not None).items()}
+    at = {name: table.data_ptr() + 4 * first for name, (first, _) in table_layout(*_plan_layout(plan)).items()}
     rows = (C.c_void_p * plan.S)(*[t.data_ptr() for t in src])
     entry, cols, own = "sepr_dynmix_fwd", (), ()        # the entry, the table columns of its form, the form's own arguments
-    if plan.rir is not None and plan.speed is not None:
+    if plan.on is not None:
+        entry, cols = "sepr_dynmix_turns_fwd", (at["conv"], at["rir"], at["taps"], at["on"], at["off"])
+        own = (*_converter_args(dev, plan_speeds(plan) if speeds is None else speeds),
+               *(rirs._bank_args() if plan.rir is not None else (None, 0, None, 0)), ramp.data_ptr() if ramp.numel() else None, ramp.numel())
+    elif plan.rir is not None and plan.speed is not None:
         entry, cols = "sepr_dynmix_speed_reverb_fwd", (at["conv"], at["rir"], at["taps"])
         own = (*_converter_args(dev, plan_speeds(plan) if speeds is None else speeds), *rirs._bank_args())
     elif plan.rir is not None:
@@ -583,9 +716,14 @@ def mix_batch(corpus: Corpus, plan: BatchPlan, Tmax: Optional[int] = None, mix: 
 
 def pack_table(plan: BatchPlan, speeds: Optional[Sequence[int]] = None) -> np.ndarray:
     """The plan as one int32 array in the order of ``table_layout`` (``norm`` and ``gain`` as their bits).  The ``conv`` block of a plan that
-    carries speeds: -1 for a term at 100 %, else the position of the term's speed in ``speeds`` (default ``plan_speeds(plan)``)."""
+    carries speeds: -1 for a term at 100 %, else the position of the term's speed in ``speeds`` (default ``plan_speeds(plan)``).  A plan with turns
+    has every column: ``conv`` and ``rir`` are -1 and ``taps`` 1 where it carries no speeds or no RIRs."""
     blocks = {"utt": plan.utt, "start": plan.start, "norm": plan.norm.view(np.int32), "gain": plan.gain.view(np.int32), "n": plan.n,
-              "rir": plan.rir, "taps": plan.taps}
+              "rir": plan.rir, "taps": plan.taps, "on": plan.on, "off": plan.off}
+    if plan.on is not None:
+        blocks["conv"] = np.full_like(plan.utt, -1)
+        if plan.rir is None:
+            blocks["rir"], blocks["taps"] = np.full_like(plan.utt, -1), np.ones_like(plan.utt)
     if plan.speed is not None:
         order = [int(p) for p in (plan_speeds(plan) if speeds is None else speeds)]
         index = {**{p: k for k, p in enumerate(order)}, 100: -1}
@@ -593,7 +731,7 @@ def pack_table(plan: BatchPlan, speeds: Optional[Sequence[int]] = None) -> np.nd
         if missing:
             raise ValueError(f"speeds {missing} of the plan are not in the converter set {order}")
         blocks["conv"] = np.array([index[int(p)] for p in plan.speed.ravel()], np.int32)
-    layout = table_layout(*plan.utt.shape, plan.speed is not None, plan.rir is not None)
+    layout = table_layout(*_plan_layout(plan))
     return np.concatenate([blocks[name].ravel().astype(np.int32, copy=False) for name in layout])
 
 
@@ -653,7 +791,8 @@ class DynamicMixFeed:
     ``planner(corpus, rng, key, max_len) -> Example`` is one of ``plan_wsj0`` / ``plan_wham`` / ``plan_whamr`` / ``plan_direct`` (bind
     other role names, or ``speeds=range(95, 106)`` for speed perturbation, with ``functools.partial``; for reverberation bind ``rirs=bank`` and
     pass the same bank as the feed's ``rirs=``; for both bind ``speed_reverb=True`` as well - the feed reads the flag from the
-    ``functools.partial`` and passes it to ``collate_plan``; a planner wrapped otherwise says it with the feed's ``speed_reverb=``).  Per batch: plan on the host, write the table into a pinned staging buffer, one
+    ``functools.partial`` and passes it to ``collate_plan``; a planner wrapped otherwise says it with the feed's ``speed_reverb=``; for turn-taking
+    bind ``turns=Turns(...)``, which the feed reads the same way - or takes as its own ``turns=`` - for the gate's ramp table).  Per batch: plan on the host, write the table into a pinned staging buffer, one
     asynchronous copy into the static device table, one launch - all on the current stream, nothing waits for the device.
     ``keys``: the epoch's key order, used as given every epoch; default: the keys of the corpus's first role, permuted with the
     feed's ``random.Random(seed)`` before each epoch (the same generator then makes the examples' draws).  ``rank`` / ``world``:
@@ -672,7 +811,7 @@ class DynamicMixFeed:
     def __init__(self, corpus: Corpus, planner: Callable[..., Example], batch: int, max_len: int, seed: int = 0,
                  keys: Optional[Sequence[str]] = None, fixed_length: bool = False, rank: int = 0, world: int = 1,
                  rirs: Optional[RirBank] = None, rooms=None, rooms_every: int = 1, speed_reverb: Optional[bool] = None,
-                 drop_last: bool = True):
+                 drop_last: bool = True, turns: Optional[Turns] = None):
         if corpus.device is None:
             raise RuntimeError("DynamicMixFeed needs a corpus on the HIP device (there is no CPU path)")
         if rirs is not None and not _same_device(rirs.device, corpus.device):
@@ -696,6 +835,10 @@ class DynamicMixFeed:
         if speed_reverb is None:                        # the flag the user bound on the planner
             speed_reverb = (getattr(planner, "keywords", None) or {}).get("speed_reverb", False)
         self.speed_reverb = bool(speed_reverb)
+        if turns is None:                               # the turns the user bound on the planner, read as speed_reverb is
+            turns = (getattr(planner, "keywords", None) or {}).get("turns")
+        self.turns = None if turns is None else _check_turns(turns)
+        self._ramp = None if self.turns is None else ramp_table(corpus.device, int(self.turns.ramp))      # once per feed and device
         self._table = None
         self._speeds: List[int] = []                    # the converter set: every speed a plan has used, in order of first use
         self._stage: List[torch.Tensor] = []
@@ -733,12 +876,13 @@ class DynamicMixFeed:
         self._begin_epoch()
         order = self.epoch_order()
         for keys in self.order.batches(order):
-            yield collate_plan(self.corpus, [self.planner(self.corpus, self.rng, k, self.max_len) for k in keys], self.rirs, self.speed_reverb)
+            yield collate_plan(self.corpus, [self.planner(self.corpus, self.rng, k, self.max_len) for k in keys], self.rirs, self.speed_reverb,
+                               self.turns is not None)
 
     # ---- device side -------------------------------------------------------------------------------------------------------
     def _launch(self, plan: BatchPlan, mix=None, src=None):
         dev = self.corpus.device
-        words = _table_words(*plan.utt.shape, plan.speed is not None, plan.rir is not None)
+        words = _table_words(*_plan_layout(plan))
         self._speeds += [p for p in plan_speeds(plan) if p not in self._speeds]
         if self._table is None or self._table.numel() != words:
             self._table = torch.empty(words, dtype=torch.int32, device=dev)
@@ -755,7 +899,7 @@ class DynamicMixFeed:
         self._events[k] = ev
         self.last_plan = plan
         return mix_batch(self.corpus, plan, self.max_len if self.fixed_length else None, mix, src, table=self._table, speeds=self._speeds,
-                         rirs=self.rirs)
+                         rirs=self.rirs, ramp=self._ramp)
 
     def __iter__(self):
         for plan in self.plans():

@@ -180,6 +180,9 @@ SIGNATURES = {
     "sepr_dynmix_speed_reverb_fwd": (_i, [_fp, _ll, _fp, _ll, _fp, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _fp,
                                           C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _i, _fp, _ll, _fp, _i,
                                           _fp]),
+    "sepr_dynmix_turns_fwd": (_i, [_fp, _ll, _fp, _ll, _fp, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _fp,
+                                   C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _i, _fp, _ll, _fp, _i, _fp, _i,
+                                   _fp]),
     "sepr_rir_ism_fwd": (_i, [_fp, _i, _i, _d, _fp, _fp, _fp, _fp, _i, _fp]),
     "sepr_pit_sisnr_fwd": (_i, [_fp, _fp, _fp, _i, _i, _i, C.c_double, C.c_double, C.c_double, _fp, _fp, _fp, _fp,
                                 _fp, _sz, _fp]),

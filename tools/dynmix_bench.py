@@ -25,6 +25,11 @@ hipEvent time of one ``sepr_rir_ism_fwd`` call for COUNT rooms, the numpy restat
 responses beside the nominal RT60, and the bf16 training step fed from a fixed simulated bank against the same feed re-simulating its
 rooms every epoch (three steps here), alternating.  Condition: one simulation takes less than one training step of the same run.
 
+``--turns LO:HI`` measures turn-taking (section 5e-6) on top of whatever ``--speeds`` and ``--rirs`` say, in one child process with the settings
+alternating: the launch of the plan without turns through the entry it has today beside the launch of the same planner with
+``turns=Turns((LO, HI))`` through ``sepr_dynmix_turns_fwd``, and the bf16 training step fed without and with turns.  ``--turns 1:1`` is the new
+entry at full overlap - the cost of the gate's code - and ``--turns 0:1`` what sparse overlap saves through the skipped tiles and chunks.
+
 ``--speeds 95:105 --rirs 64:0.6`` together measure both in one source (section 5e-5), in one child process with the settings alternating:
 the combined launch (each source perturbed, then under a whole response of RT60 seconds; direct-path targets at the same speed) beside the
 reverb-only and the speed-only launch of the same plan shapes (WHAMR form, B = 16 and 32 x 4 s), and the bf16 training step fed with
@@ -37,6 +42,7 @@ Every step runs in a child process of its own under ``timeout -k 10 <s>``; the f
     python tools/dynmix_bench.py --rirs 64:0.6 [--out profiles/dynmix_reverb.json]
     python tools/dynmix_bench.py --room-rirs 64:0.2:0.6 [--out profiles/rir_ism.json]
     python tools/dynmix_bench.py --speeds 95:105 --rirs 64:0.6 [--out profiles/dynmix_speed_reverb.json]
+    python tools/dynmix_bench.py [--speeds 95:105] [--rirs 64:0.6] --turns 0:1
 """
 import argparse
 import json
@@ -513,6 +519,73 @@ def step_speed_reverb(speeds, spec):
                      "host_plan_ms_per_batch": plan_ms}}
 
 
+def step_turns(turns, speeds, spec):
+    """The launch of a plan without turns, through the entry it has without them, beside the launch of the same planner with turns through the
+    new entry, and the training step fed without and with turns; everything alternating.  The corpus, the planners, the banks, the batches and the
+    generators' seeds are those of the step that measures the same ``--speeds`` / ``--rirs`` without ``--turns``, so its figures are the yardstick."""
+    import functools
+    import torch
+    from sepreformer_amd import datafeed as df
+    from sepreformer_amd.reverb import RirBank, parse_synthetic, synthetic_rirs
+    dev = torch.device("cuda:0")
+    keys, arrays = synth_corpus_arrays()
+    corpus = df.Corpus.from_arrays(arrays, device=dev, fs=FS)
+    corpus.roles = {r: list(keys) for r in ROLES}
+    tn = df.parse_turns(turns)
+    bank = loop_bank = None
+    base, loop_base = {}, {}
+    if speeds:
+        speeds = df.parse_speeds(speeds)
+        base["speeds"] = [p for p in speeds if p != 100]                         # "every source perturbed": 100 % left out of the draw
+        loop_base["speeds"] = speeds
+    if spec:
+        count, rt_lo, rt_hi = parse_synthetic(spec)
+        bank = RirBank.from_arrays(synthetic_rirs(count, FS, rt60=rt_hi, seed=0), FS, device=dev)
+        loop_bank = RirBank.from_arrays(synthetic_rirs(count, FS, rt60=(rt_lo, rt_hi), seed=1), FS, device=dev)
+        base.update(rirs=bank, speed_reverb=bool(speeds))
+        loop_base.update(rirs=loop_bank, speed_reverb=bool(speeds))
+    every = base.get("speeds", [])
+    ramp = df.ramp_table(dev, tn.ramp)
+    planners = {"base": functools.partial(df.plan_whamr, **base), "turns": functools.partial(df.plan_whamr, turns=tn, **base)}
+    DS_TILE = 2048
+    kernel = []
+    for B in (16, 32):
+        sets = {}
+        for name, planner in planners.items():
+            rng = random.Random(B)
+            plan = df.collate_plan(corpus, [planner(corpus, rng, keys[i % NKEYS], T4S) for i in range(B)], rirs=bank, speed_reverb=bool(speeds and spec))
+            table = torch.from_numpy(df.pack_table(plan, every)).to(dev)
+            sets[name] = (plan, table, torch.empty(B, T4S, device=dev), [torch.empty(B, T4S, device=dev) for _ in range(plan.S)], [])
+        for i in range(20 + 100):
+            for plan, table, mix, src, ms in sets.values():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                df.mix_batch(corpus, plan, T4S, mix, src, table=table, rirs=bank, speeds=every, ramp=ramp)
+                e1.record()
+                torch.cuda.synchronize()
+                if i >= 20:
+                    ms.append(e0.elapsed_time(e1))
+        plan = sets["turns"][0]
+        tiles = silent = 0                                                       # source terms' tiles, and those the skip rule takes whole
+        for b in range(B):
+            for j in list(range(2)) + list(range(plan.M, plan.M + plan.S)):
+                K = int(plan.taps[b, j]) if plan.rir is not None and plan.rir[b, j] >= 0 else 1
+                for t0 in range(0, int(plan.n[b]), DS_TILE):
+                    tiles += 1
+                    silent += t0 >= int(plan.off[b, j]) + K - 1 or min(t0 + DS_TILE, int(plan.n[b])) <= int(plan.on[b, j])
+        active = [(min(int(f), int(n)) - max(int(o), 0)) / int(n) for o, f, n in zip(plan.on[:, :2].ravel(), plan.off[:, :2].ravel(), plan.n.repeat(2))]
+        kernel.append({"form": "whamr", "B": B, "samples": T4S, "S": 2, "launches": 100, "base": {"device_ms": _stats(sets["base"][4])},
+                       "turns": {"device_ms": _stats(sets["turns"][4]), "source_tiles": tiles, "source_tiles_skipped_whole": int(silent),
+                                 "mean_active_fraction_of_a_source": sum(active) / len(active)}})
+    feeds = {name: df.DynamicMixFeed(corpus, functools.partial(df.plan_whamr, **kw), batch=16, max_len=T4S, seed=0, fixed_length=True, rirs=loop_bank)
+             for name, kw in (("base", loop_base), ("turns", dict(loop_base, turns=tn)))}
+    runs, plan_ms = _fed_loops(corpus, feeds)
+    return {"device": torch.cuda.get_device_name(0), "turns": {"overlap": list(tn.overlap), "ramp": tn.ramp}, "speeds": speeds or None, "rirs": spec or None,
+            "kernel": kernel,
+            "loop": {"model": "SepReformer_Base_WSJ0 bf16, batch 16 x 4 s, CapturedTrainStep + FlatAdamW, the reference's loss, fed in the WHAMR form",
+                     "steps_per_run": LOOP_STEPS, "base_ms_per_step": runs["base"], "turns_ms_per_step": runs["turns"], "host_plan_ms_per_batch": plan_ms}}
+
+
 def step_rooms(spec):
     """Simulating a bank of shoebox rooms on the device (section 5e-4): hipEvent time of one ``sepr_rir_ism_fwd`` call for COUNT rooms,
     the numpy restatement's CPU time for ONE of them (and that the two agree exactly), the realised decay of a few responses beside the
@@ -679,19 +752,23 @@ def main():
     ap.add_argument("--speeds", default=None, metavar="LO:HI", help="measure speed perturbation (an inclusive range or a comma list of percentages)")
     ap.add_argument("--rirs", default=None, metavar="COUNT:RT60", help="measure reverberation by convolution (COUNT synthetic impulse responses of RT60 s)")
     ap.add_argument("--room-rirs", default=None, metavar="COUNT[:RT60LO:RT60HI]", help="measure simulating COUNT shoebox rooms on the device (image-source method)")
+    ap.add_argument("--turns", default=None, metavar="LO:HI", help="measure turn-taking with the overlap drawn from [LO, HI], on top of --speeds and --rirs")
     args = ap.parse_args()
     both = bool(args.speeds and args.rirs)                                   # the two together: section 5e-5
+    if args.turns and args.room_rirs:
+        ap.error("--turns composes with --speeds and --rirs")
     if sum(bool(v) for v in (args.speeds, args.rirs, args.room_rirs)) > (2 if both and not args.room_rirs else 1):
         ap.error("--speeds, --rirs and --room-rirs are measured in runs of their own (--speeds with --rirs measures both in one source)")
     if args.step:
         rec = {"device": step_device, "host": step_host, "speed": lambda: step_speed(args.speeds), "reverb": lambda: step_reverb(args.rirs),
-               "rooms": lambda: step_rooms(args.room_rirs), "both": lambda: step_speed_reverb(args.speeds, args.rirs)}[args.step]()
+               "rooms": lambda: step_rooms(args.room_rirs), "both": lambda: step_speed_reverb(args.speeds, args.rirs),
+               "turns": lambda: step_turns(args.turns, args.speeds, args.rirs)}[args.step]()
         print("__RESULT__" + json.dumps(rec))
         return
     rec, failed = {}, None
-    for name, limit in ([("both", 600)] if both else [("speed", 600)] if args.speeds else [("reverb", 600)] if args.rirs else [("rooms", 600)] if args.room_rirs else STEPS):
+    for name, limit in ([("turns", 600)] if args.turns else [("both", 600)] if both else [("speed", 600)] if args.speeds else [("reverb", 600)] if args.rirs else [("rooms", 600)] if args.room_rirs else STEPS):
         cmd = (["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", name] + (["--speeds", args.speeds] if args.speeds else [])
-               + (["--rirs", args.rirs] if args.rirs else []) + (["--room-rirs", args.room_rirs] if args.room_rirs else []))
+               + (["--rirs", args.rirs] if args.rirs else []) + (["--room-rirs", args.room_rirs] if args.room_rirs else []) + (["--turns", args.turns] if args.turns else []))
         r = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
         lines = [ln for ln in r.stdout.splitlines() if ln.startswith("__RESULT__")]
         if r.returncode != 0 or not lines:
@@ -700,7 +777,16 @@ def main():
             break                                                          # nothing more runs on the device after a failure
         rec.update(json.loads(lines[-1][len("__RESULT__"):]))
         print(name, "done", flush=True)
-    if not failed and both:
+    if not failed and args.turns:
+        lp = rec["loop"]
+        a, b = lp["base_ms_per_step"], lp["turns_ms_per_step"]
+        mean = lambda v: sum(v) / len(v)                                    # noqa: E731
+        k = next(r for r in rec["kernel"] if r["B"] == 16)
+        rec["summary"] = {"base_launch_ms_median": k["base"]["device_ms"]["median"], "turns_launch_ms_median": k["turns"]["device_ms"]["median"],
+                          "turns_launch_over_base": k["turns"]["device_ms"]["median"] / k["base"]["device_ms"]["median"],
+                          "base_step_ms_mean": mean(a), "turns_step_ms_mean": mean(b), "difference_ms": mean(b) - mean(a),
+                          "base_step_spread_ms": max(a) - min(a), "turns_step_spread_ms": max(b) - min(b)}
+    elif not failed and both:
         lp = rec["loop"]
         a, b = lp["reverb_ms_per_step"], lp["both_ms_per_step"]
         mean = lambda v: sum(v) / len(v)                                    # noqa: E731

@@ -49,6 +49,11 @@ def main():
     ap.add_argument("--rooms-every", type=int, default=1, help="with --room-rirs: redraw the rooms at the start of every N-th epoch (default 1)")
     ap.add_argument("--reverb-target", choices=["direct", "dry", "full"], default="direct", help="the targets under reverberation: the direct "
                     "path of the same impulse response (default), the dry source, or the whole response")
+    ap.add_argument("--turns", default=None, metavar="LO:HI", help="turn-taking: every source talks for a turn of the example and the turns overlap by a "
+                    "fraction drawn per example from [LO, HI] (1 = full overlap, 0 = back to back; default: off); the talker is gated inside the "
+                    "mixing launch, before the room")
+    ap.add_argument("--turn-ramp", type=int, default=80, metavar="N", help="with --turns: samples of the raised-cosine fade at either end of a turn "
+                    "(0 = a hard gate; default 80)")
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--epochs", type=int, default=None, metavar="N", help="run the epoch loop instead of --steps: the reference's max_epoch "
                     "(epochs 1 .. N - 1); needs --valid-scp and --checkpoint-dir")
@@ -81,6 +86,8 @@ def main():
         ap.error("--ema-decay must lie in [0, 1)")
     if args.speeds and args.form == "direct":
         ap.error("--speeds needs dynamic mixing (--form wsj0, wham or whamr)")
+    if args.turns and args.form == "direct":
+        ap.error("--turns needs dynamic mixing (--form wsj0, wham or whamr)")
     reverb = args.rir_scp or args.synthetic_rirs or args.room_rirs
     if reverb and args.form == "direct":
         ap.error("--rir-scp / --synthetic-rirs / --room-rirs need dynamic mixing (--form wsj0, wham or whamr)")
@@ -127,6 +134,11 @@ def main():
             bank = RirBank.from_arrays(synthetic_rirs(synth[0], args.fs, rt60=synth[1:], seed=args.seed), args.fs, device=dev)
         planner = functools.partial(planner, rirs=bank, target=args.reverb_target, speed_reverb=bool(args.speeds))
         print(f"RIR bank: {len(bank)} impulse responses, {int(bank.lengths.min())} .. {int(bank.lengths.max())} samples", flush=True)
+    if args.turns:
+        try:
+            planner = functools.partial(planner, turns=df.parse_turns(args.turns, args.turn_ramp))
+        except ValueError as e:
+            ap.error(f"--turns / --turn-ramp: {e}")
     feed = df.DynamicMixFeed(corpus, planner, batch=args.batch, max_len=args.max_len, seed=args.seed, fixed_length=True, rirs=bank,
                               rooms=sampler, rooms_every=args.rooms_every)
     print(f"corpus: {len(corpus)} utterances, {corpus.total16 * 2 + corpus.total32 * 4} bytes on {dev}", flush=True)
