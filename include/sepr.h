@@ -645,6 +645,49 @@ int sepr_dynmix_turns_fwd(const short* buf16, long long total16, const float* bu
 int sepr_rir_ism_fwd(const double* rooms, int R, int N, double fsc, const double* lut, long long* acc, float* rir, int* peak_idx, int normalise,
                      sepr_stream_t stream);
 
+/* ---- conversations rendered and scored on the device (new entries, no struct change: ABI 4.13) ------------
+ * A conversation is a schedule of G_r >= 1 segments on S_r <= S_max talker tracks, laid along n_r output samples (a multiple of 4).  Segment g
+ * is (seg_utt, seg_start, seg_place, seg_len, seg_norm, seg_gain): sample seg_start + d of the utterance lands on output sample seg_place + d
+ * for 0 <= d < seg_len.  The segments of all R conversations lie in one table of G rows sorted by (conversation, track, place);
+ * track_off [R S_max + 1] int32 holds the cumulative segment counts per (conversation, track) - a track without a segment has an empty range -
+ * and out_off [R + 1] int64 the first flat output sample of each conversation (multiples of 4, out_off[R] = total).  The segments of one track do
+ * not overlap.  All eight tables are DEVICE memory; the corpus is described exactly as for sepr_dynmix_fwd.
+ *
+ * sepr_conversation_render: one launch renders every conversation.  With x the utterance's sample value (an int16 sample is s / 32768),
+ *   track_s[t] = (x[seg_start + t - seg_place] * seg_norm) * seg_gain  for the one segment of track s that covers t, else +0.0   (two separately
+ *                rounded float32 multiplies, never contracted: the arithmetic of sepr_dynmix_fwd)
+ *   mix[t]     = ((0 + track_0[t]) + track_1[t]) + ... over the S_max tracks in track order
+ * mix [total] float32, conversation r at out_off[r]; tracks [S_max][total] float32 or NULL, which skips the track rows; both 16-byte aligned.
+ * The kernel is tiled over the flat output samples: a tile finds its conversation and each track's first live segment by binary search over
+ * seg_place; a segment that covers the four samples of a thread is read with aligned vector loads and realigned in registers, its first and last
+ * samples one at a time.  The call cannot validate the tables: the kernel clamps every track range into [0, G], the utterance index, the start
+ * and every read position as sepr_dynmix_fwd does, and stores at flat samples below total only, so a bad table gives wrong samples but never an
+ * access outside the corpus buffers, the tables or the outputs.  SEPR_EINVAL before any HIP call for a null pointer (tracks excepted),
+ * R < 1 or R > 65535, S_max outside 1..8, G < 1, total < 4, not a multiple of 4 or above 2^40, a misaligned buffer or an inconsistent corpus
+ * description.  No workspace, no host synchronisation or allocation (capturable: the pointers are frozen, the tables are read at replay).
+ *
+ * sepr_segment_sisnr_fwd: the SI-SNR of every output channel, and of the mixture, against every segment.  est [C][ld], ref [S][ld], mix [ld]
+ * float32 with T <= ld valid samples per row; rows, begin, length [G] int32 (DEVICE): segment g is r = ref[rows[g]][begin[g] .. begin[g] +
+ * length[g]) and a signal a is the same span of an est row or of mix.  In float64 (a float32 value is exact in it), with n = length[g]:
+ *   a~ = a - (sum a) / n,   r~ = r - (sum r) / n,   s_rr = sum r~^2,   s_ar = sum a~ r~,   alpha = s_ar / (s_rr + eps)
+ *   value = 20 log10(eps + |alpha| sqrt(s_rr) / (sqrt(sum (a~ - alpha r~)^2) + eps))
+ * - the per-pair term of PIT_SISNRi over the segment.  The residual is summed DIRECTLY, in a pass after alpha is known, not formed from raw or
+ * centred moments, so the relative error of both norms does not depend on the SNR or on a DC offset.  v [G][C] float64 = the value of est
+ * row c, v_mix [G] float64 = the value of mix.  Every sum runs in a fixed order - thread i of 256 adds the samples i, i + 256, ..., a wave adds
+ * its lanes by butterfly, the four wave sums are added in wave order - with no atomics: bit-identical from run to run.  The grids are G and
+ * (G, C + 1) workgroups.  The kernels clamp rows[g] into [0, S), begin[g] into [0, T] and length[g] into [0, T - begin[g]] (an empty segment gives
+ * 20 log10(eps)).  Workspace: sepr_segment_sisnr_bytes(G, C) bytes (0 for G < 1 or C outside 1..8).  SEPR_EINVAL before any HIP call for a null
+ * pointer, G < 1, C or S outside 1..8, T < 1, ld < T, eps outside [0, 1], est, ref or mix not 4-byte aligned, v or v_mix not 8-byte aligned;
+ * SEPR_EWORKSPACE for a short workspace.  No host synchronisation or allocation (capturable). */
+int sepr_conversation_render(const short* buf16, long long total16, const float* buf32, long long total32, const long long* offsets, int N16,
+                             int N, const int* seg_utt, const int* seg_start, const int* seg_place, const int* seg_len, const float* seg_norm,
+                             const float* seg_gain, const int* track_off, const long long* out_off, int R, int S_max, int G, long long total,
+                             float* mix, float* tracks, sepr_stream_t stream);
+long long sepr_segment_sisnr_bytes(int G, int C);   /* (long long: the size_t entries are the workspace sizes of the older entries) */
+int sepr_segment_sisnr_fwd(const float* est, const float* ref, const float* mix, const int* rows, const int* begin, const int* length, int G,
+                           int C, int S, int T, long long ld, double eps, double* v, double* v_mix, void* ws, size_t ws_bytes,
+                           sepr_stream_t stream);
+
 /* ================================================================================================================= */
 /* Training path: train-mode forward twins that keep what the backward needs, and the       */
 /* backward of every block.  The reference trains through torch.autograd over the same modules (engine.py:50-83:     */

@@ -1,0 +1,357 @@
+"""Conversations rendered and scored on the device (contracts in include/sepr.h).
+
+``separate_long``, ``StreamBank`` and ``separate_many`` take recordings of any length; this module makes such recordings from the resident
+``Corpus`` of the training feed and scores what the separator does with them, utterance by utterance, as the continuous-speech-separation
+literature (LibriCSS) does:
+
+    convs = [plan_conversation(corpus, random.Random(i), seconds=600) for i in range(20)]
+    rd = render(corpus, convs)                                  # ONE launch: every mixture and every talker track
+    est = separate_long(model, [rd.mixture(r) for r in range(len(convs))])
+    ...                                                         # infer.evaluate_conversations is the whole loop
+
+* ``plan_conversation`` lays corpus utterances along a time line (a schedule: it touches no sample);
+* ``render`` is one ``sepr_conversation_render`` launch for all conversations - the arithmetic of ``sepr_dynmix_fwd``, so a numpy
+  restatement is bit-equal (tests/conversation_ref.py);
+* ``segment_sisnr`` is one ``sepr_segment_sisnr_fwd`` call: the SI-SNR of every output channel and of the mixture against every
+  utterance over that utterance's span, in float64;
+* ``score`` turns the two small matrices into utterance-wise SI-SNRi, the consistent-assignment SI-SNRi and the channel switch rate.
+"""
+from __future__ import annotations
+
+import itertools
+import random
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import lib as L_
+from .datafeed import Corpus, _gain, _norm
+
+MAX_TRACKS = 8                       # talker tracks of a conversation, and channels of a scored separator
+OVERLAP_BINS = ("0", "(0,0.2]", "(0.2,0.5]", "(0.5,1]")
+
+
+class Conversation(NamedTuple):
+    """A schedule: ``G`` segments sorted by ``(track, place)``.  Segment ``g`` puts the samples ``start[g] .. start[g] + len[g] - 1`` of utterance
+    ``utt[g]``, scaled by ``norm[g]`` and then ``gain[g]``, on the output samples ``place[g] .. place[g] + len[g] - 1`` of track ``track[g]``."""
+    key: str
+    n: int                           # output samples, a multiple of 4
+    S: int                           # talker tracks, 1 .. 8
+    utt: np.ndarray                  # int32 [G]
+    start: np.ndarray                # int32 [G]
+    place: np.ndarray                # int32 [G]
+    len: np.ndarray                  # int32 [G], at least 1
+    norm: np.ndarray                 # float32 [G]
+    gain: np.ndarray                 # float32 [G]
+    track: np.ndarray                # int32 [G]
+
+
+def make_conversation(key: str, n: int, S: int, segments: Sequence[Tuple[int, int, int, int, float, float, int]]) -> Conversation:
+    """A ``Conversation`` from ``(utt, start, place, len, norm, gain, track)`` tuples in any order: sorted by ``(track, place)`` and checked -
+    ``n`` a positive multiple of 4, ``S`` in 1..8, every segment of at least one sample inside ``[0, n)`` on a track below ``S``, no two
+    segments of one track overlapping."""
+    n, S = int(n), int(S)
+    if n < 4 or n % 4 or not 1 <= S <= MAX_TRACKS:
+        raise ValueError(f"a conversation has a positive multiple of 4 samples and 1..{MAX_TRACKS} tracks, got n = {n}, S = {S}")
+    if not segments:
+        raise ValueError("a conversation holds at least one segment")
+    segs = sorted(segments, key=lambda s: (int(s[6]), int(s[2])))
+    end = {}
+    for utt, start, place, ln, _, _, trk in segs:
+        if not 0 <= trk < S or ln < 1 or place < 0 or place + ln > n or start < 0 or utt < 0:
+            raise ValueError(f"segment {(utt, start, place, ln, trk)} does not lie inside a conversation of {n} samples and {S} tracks")
+        if place < end.get(trk, 0):
+            raise ValueError(f"two segments of track {trk} overlap at sample {place}")
+        end[trk] = place + ln
+    col = lambda i, dt: np.array([s[i] for s in segs], dtype=dt)
+    return Conversation(key, n, S, col(0, np.int32), col(1, np.int32), col(2, np.int32), col(3, np.int32), col(4, np.float32),
+                        col(5, np.float32), col(6, np.int32))
+
+
+def wsj0_speaker(name: str) -> Optional[str]:
+    """The speaker of corpus utterance ``role/key`` by the rule ``datafeed.wsj0_distinct_speakers`` reads: the first three letters of the 2nd
+    ``_`` field of the key for role ``s1``, of the 4th for ``s2``; ``None`` when the name does not parse."""
+    role, _, key = name.partition("/")
+    f = key.split("_")
+    i = {"s1": 1, "s2": 3}.get(role)
+    if i is None or len(f) <= i or len(f[i]) < 3:
+        return None
+    return f[i][:3]
+
+
+def plan_conversation(corpus: Corpus, rng: random.Random, seconds: float, roles: Sequence[str] = ("s1", "s2"), speakers: int = 2,
+                      overlap: Tuple[float, float] = (0.0, 0.4), pause: Tuple[float, float] = (0.0, 1.0), p_overlap: float = 0.5,
+                      gain_db: Tuple[float, float] = (-2.5, 2.5), max_active: int = 2, speaker_of: Optional[Callable[[str], Optional[str]]] = None,
+                      fs: Optional[int] = None, key: Optional[str] = None) -> Conversation:
+    """Lay corpus utterances along ``n = seconds * fs`` samples (rounded down to a multiple of 4; ``fs`` defaults to the corpus's), one track per
+    speaker.  The planner reads names, lengths and energies only - it touches no sample.
+
+    The pool is the utterances of ``roles`` (``corpus.roles``, in file order; a corpus without roles offers all its utterances).
+    ``speaker_of(name)`` names the speaker of corpus utterance ``name`` (``"role/key"``), by default ``wsj0_speaker``; an utterance it
+    returns ``None`` for counts as a speaker of its own.  Draws from ``rng``, in this order:
+
+    1. ``rng.sample`` of ``speakers`` distinct speakers from the sorted speaker names: track ``s`` belongs to the ``s``-th drawn;
+    2. per utterance: its track - track 0 for the first, then ``rng.randrange`` over the tracks other than the one before (no draw for
+       one or two tracks) -, ``rng.choice`` among that speaker's utterances, then the placement - the first utterance at sample 0, every
+       later one either ``rng.random() < p_overlap`` and ``u = rng.uniform(*overlap)``: it starts ``round(u * min(len_prev, len_new))`` samples
+       before the previous one ends, or ``rng.uniform(*pause)`` seconds after it ends -, then ``_gain(rng, *gain_db)``.
+
+    The start is then moved later, if need be, to the first sample where the track itself is free and at most ``max_active - 1`` other tracks
+    are still talking.  Every utterance is used from its first sample, RMS-normalised to the conversation's first (``_norm``) and scaled by its
+    gain.  The utterance that reaches ``n`` is cut there and ends the conversation; one that would start at or after ``n`` is dropped."""
+    fs = int(fs if fs is not None else (corpus.fs or 0))
+    if fs < 1:
+        raise ValueError("the corpus carries no sampling rate: pass fs")
+    n = int(seconds * fs) // 4 * 4
+    S = int(speakers)
+    if n < 4 or not 1 <= S <= MAX_TRACKS or max_active < 1:
+        raise ValueError(f"a conversation needs at least 4 samples, 1..{MAX_TRACKS} speakers and max_active >= 1")
+    if not (0.0 <= overlap[0] <= overlap[1] <= 1.0 and 0.0 <= pause[0] <= pause[1] and 0.0 <= p_overlap <= 1.0):
+        raise ValueError("overlap is a range inside [0, 1], pause a range of non-negative seconds, p_overlap a probability")
+    speaker_of = speaker_of or wsj0_speaker
+    names = [f"{r}/{k}" for r in roles for k in corpus.roles.get(r, [])] or list(corpus.names)
+    by_spk: Dict[str, List[int]] = {}
+    for nm in names:
+        spk = speaker_of(nm)
+        by_spk.setdefault(f"utt:{nm}" if spk is None else f"spk:{spk}", []).append(corpus.index[nm])
+    if len(by_spk) < S:
+        raise ValueError(f"{S} tracks need {S} distinct speakers, the pool holds {len(by_spk)}")
+    who = rng.sample(sorted(by_spk), S)
+    rms, lengths = corpus.rms, corpus.lengths
+    end = [0] * S                                  # the sample after each track's last segment
+    segs, prev, prev_len, first = [], -1, 0, -1
+    while True:
+        if prev < 0:
+            trk = 0
+        else:
+            others = [s for s in range(S) if s != prev] or [prev]
+            trk = others[rng.randrange(len(others))] if len(others) > 1 else others[0]
+        u = int(rng.choice(by_spk[who[trk]]))
+        ln = int(lengths[u])
+        if prev < 0:
+            place, first = 0, u
+        elif S > 1 and rng.random() < p_overlap:
+            place = end[prev] - int(round(rng.uniform(*overlap) * min(prev_len, ln)))
+        else:
+            place = end[prev] + int(round(rng.uniform(*pause) * fs))
+        gain = _gain(rng, *gain_db)
+        busy = sorted((end[s] for s in range(S) if s != trk), reverse=True)
+        place = max(place, end[trk], busy[max_active - 1] if len(busy) >= max_active else 0)
+        if place >= n:
+            break
+        ln = min(ln, n - place)
+        segs.append((u, 0, place, ln, _norm(rms[first], rms[u]), gain, trk))
+        end[trk], prev, prev_len = place + ln, trk, ln
+        if end[trk] >= n:
+            break
+    return make_conversation(key if key is not None else f"conv_{corpus.names[first]}", n, S, segs)
+
+
+def overlap_fraction(conv: Conversation) -> np.ndarray:
+    """float64 ``[G]``: the share of each segment's samples during which another track is active.  From the schedule alone, on the host."""
+    G = len(conv.utt)
+    out = np.zeros(G, dtype=np.float64)
+    a, b = conv.place.astype(np.int64), conv.place.astype(np.int64) + conv.len
+    for g in range(G):
+        other = conv.track != conv.track[g]
+        lo, hi = np.maximum(a[other], a[g]), np.minimum(b[other], b[g])
+        keep = hi > lo
+        covered, reach = 0, a[g]
+        for l, h in sorted(zip(lo[keep].tolist(), hi[keep].tolist())):          # the union of the other tracks' spans inside the segment
+            if h > reach:
+                covered += h - max(l, reach)
+                reach = h
+        out[g] = covered / float(b[g] - a[g])
+    return out
+
+
+# ---- render ---------------------------------------------------------------------------------------------------------------------------
+class ConvTable:
+    """The device tables of ``R`` conversations for ``sepr_conversation_render``: ``words`` int32 ``[6 G + R S_max + 1]`` - the columns utt,
+    start, place, len, norm, gain (the two float32 columns as their bits), then ``track_off`` - and ``out_off`` int64 ``[R + 1]``.
+    ``pack`` makes the host arrays of a list of conversations with the same ``(R, S_max, G)``; copying them into ``words`` / ``out_off``
+    re-targets a captured launch."""
+
+    def __init__(self, convs: Sequence[Conversation], device):
+        self.R, self.S_max, self.G = len(convs), max(c.S for c in convs), sum(len(c.utt) for c in convs)
+        words, out_off = self.pack(convs)
+        self.total = int(out_off[-1])
+        self.words = torch.from_numpy(words).to(device)
+        self.out_off = torch.from_numpy(out_off).to(device)
+        self.out_off_host = out_off
+
+    def pack(self, convs: Sequence[Conversation]) -> Tuple[np.ndarray, np.ndarray]:
+        R, S_max, G = self.R, self.S_max, self.G
+        if not 1 <= R <= 65535 or len(convs) != R or max(c.S for c in convs) > S_max or sum(len(c.utt) for c in convs) != G:
+            raise ValueError("the conversations do not fit this table's (R, S_max, G)")
+        cat = lambda f, dt: np.concatenate([np.asarray(getattr(c, f), dtype=dt) for c in convs])
+        counts = np.zeros(R * S_max, dtype=np.int64)
+        for r, c in enumerate(convs):
+            if np.any(np.diff(c.track.astype(np.int64) * (1 << 32) + c.place) < 0):
+                raise ValueError(f"{c.key}: the segments are not sorted by (track, place)")
+            counts[r * S_max:r * S_max + c.S] = np.bincount(c.track, minlength=c.S)
+        words = np.concatenate([cat("utt", np.int32), cat("start", np.int32), cat("place", np.int32), cat("len", np.int32),
+                                cat("norm", np.float32).view(np.int32), cat("gain", np.float32).view(np.int32),
+                                np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)])
+        out_off = np.concatenate([[0], np.cumsum([int(c.n) for c in convs])]).astype(np.int64)
+        if any(c.n % 4 or c.n < 4 for c in convs):
+            raise ValueError("every conversation holds a positive multiple of 4 samples")
+        return words, out_off
+
+    def columns(self) -> List[int]:
+        """Device addresses of utt, start, place, len, norm, gain and track_off."""
+        p = self.words.data_ptr()
+        return [p + 4 * k * self.G for k in range(7)]
+
+
+def render_into(corpus: Corpus, table: ConvTable, mix: torch.Tensor, tracks: Optional[torch.Tensor]) -> None:
+    """The one ``sepr_conversation_render`` launch on the current stream: ``mix`` float32 ``[total]``, ``tracks`` float32
+    ``[S_max, total]`` or ``None``.  No allocation, no synchronisation: capturable, and the tables are read at replay."""
+    dev = table.words.device
+    if dev.type != "cuda" or corpus.device is None:
+        raise RuntimeError("conversations are rendered on the HIP device, from a corpus resident there (there is no CPU path)")
+    for t, shape in ((mix, (table.total,)), (tracks, (table.S_max, table.total))):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev):
+            raise ValueError(f"expected a contiguous float32 {shape} tensor on {dev}")
+    lib = L_.load()
+    with torch.cuda.device(dev):
+        L_.check(lib.sepr_conversation_render(*corpus._corpus_args(), *table.columns(), table.out_off.data_ptr(), table.R, table.S_max, table.G,
+                                              table.total, mix.data_ptr(), None if tracks is None else tracks.data_ptr(),
+                                              torch.cuda.current_stream(dev).cuda_stream), "sepr_conversation_render")
+
+
+class Rendered:
+    """``mix`` float32 ``[total]`` with conversation ``r`` at ``out_off[r]``; ``tracks`` ``[S_max, total]`` or ``None``."""
+
+    def __init__(self, convs, table: ConvTable, mix: torch.Tensor, tracks: Optional[torch.Tensor]):
+        self.convs, self.table, self.mix, self.tracks = list(convs), table, mix, tracks
+        self.out_off = table.out_off_host
+
+    def mixture(self, r: int) -> torch.Tensor:
+        return self.mix[int(self.out_off[r]):int(self.out_off[r + 1])]
+
+    def tracks_of(self, r: int) -> torch.Tensor:
+        """``[S_r, n_r]`` view: the talker tracks of conversation ``r`` (row stride ``total``)."""
+        if self.tracks is None:
+            raise RuntimeError("rendered without tracks")
+        return self.tracks[:self.convs[r].S, int(self.out_off[r]):int(self.out_off[r + 1])]
+
+
+def render(corpus: Corpus, convs: Sequence[Conversation], tracks: bool = True) -> Rendered:
+    """Mixture and talker tracks of every conversation, in one launch from the resident corpus."""
+    if corpus.device is None:
+        raise RuntimeError("conversations are rendered on the HIP device, from a corpus resident there (there is no CPU path)")
+    table = ConvTable(convs, corpus.device)
+    mix = torch.empty(table.total, dtype=torch.float32, device=corpus.device)
+    trk = torch.empty(table.S_max, table.total, dtype=torch.float32, device=corpus.device) if tracks else None
+    render_into(corpus, table, mix, trk)
+    return Rendered(convs, table, mix, trk)
+
+
+# ---- segment-wise SI-SNR --------------------------------------------------------------------------------------------------------------
+def _rows(x: torch.Tensor, what: str) -> torch.Tensor:
+    if x.dim() == 1:
+        x = x[None]
+    if x.dim() != 2 or x.dtype != torch.float32 or x.device.type != "cuda":
+        raise ValueError(f"{what} must be a float32 [rows, T] tensor on the HIP device (there is no CPU path)")
+    return x if x.stride(1) == 1 and (x.shape[0] == 1 or x.stride(0) >= x.shape[1]) else x.contiguous()
+
+
+def segment_sisnr(est: torch.Tensor, ref: torch.Tensor, mix: torch.Tensor, rows, begin, length, eps: float = 1e-15
+                  ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One ``sepr_segment_sisnr_fwd`` call.  ``est`` ``[C, T]``, ``ref`` ``[S, T]``, ``mix`` ``[T]`` float32 on the device, each with any row
+    stride; segment ``g`` is ``ref[rows[g]][begin[g] : begin[g] + length[g]]``.  -> ``(v [G, C], v_mix [G])`` float64 on the device: the
+    SI-SNR in dB of every channel, and of the mixture, against every segment over that segment's span (include/sepr.h)."""
+    est, ref, mixr = _rows(est, "est"), _rows(ref, "ref"), _rows(mix, "mix")
+    T = int(mixr.shape[1])
+    if mixr.shape[0] != 1 or est.shape[1] != T or ref.shape[1] != T:
+        raise ValueError("est, ref and mix must hold the same number of samples per row")
+    C, S = int(est.shape[0]), int(ref.shape[0])
+    strides = {int(x.stride(0)) for x in (est, ref) if x.shape[0] > 1}
+    if len(strides) > 1:                                          # one row stride for the call: repack rows that have two
+        est, ref, strides = est.contiguous(), ref.contiguous(), {T}
+    ld = strides.pop() if strides else T
+    seg = np.stack([np.asarray(rows, dtype=np.int32), np.asarray(begin, dtype=np.int32), np.asarray(length, dtype=np.int32)])
+    G = int(seg.shape[1])
+    if seg.ndim != 2 or G < 1:
+        raise ValueError("rows, begin and length are one-dimensional, of the same positive length")
+    if seg[0].min() < 0 or seg[0].max() >= S or seg[1].min() < 0 or seg[2].min() < 1 or int((seg[1].astype(np.int64) + seg[2]).max()) > T:
+        raise ValueError("a segment lies outside ref")
+    dev = est.device
+    lib = L_.load()
+    segd = torch.from_numpy(np.ascontiguousarray(seg)).to(dev)
+    v = torch.empty(G, C, dtype=torch.float64, device=dev)
+    v_mix = torch.empty(G, dtype=torch.float64, device=dev)
+    ws = torch.empty(max(1, int(lib.sepr_segment_sisnr_bytes(G, C))), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        L_.check(lib.sepr_segment_sisnr_fwd(est.data_ptr(), ref.data_ptr(), mixr.data_ptr(), segd[0].data_ptr(), segd[1].data_ptr(),
+                                            segd[2].data_ptr(), G, C, S, T, ld, float(eps), v.data_ptr(), v_mix.data_ptr(), ws.data_ptr(),
+                                            ws.numel(), torch.cuda.current_stream(dev).cuda_stream), "sepr_segment_sisnr_fwd")
+    return v, v_mix
+
+
+# ---- scores ---------------------------------------------------------------------------------------------------------------------------
+def overlap_bin(f: float) -> int:
+    """The bin of an overlap fraction: 0 for no overlap, then (0, 0.2], (0.2, 0.5], (0.5, 1]."""
+    return 0 if f <= 0.0 else (1 if f <= 0.2 else (2 if f <= 0.5 else 3))
+
+
+def _mean(x: np.ndarray) -> float:
+    x = x[~np.isnan(x)]
+    return float(x.mean()) if x.size else float("nan")
+
+
+def score(v, v_mix, conv_of, track, S_of, C: int, overlap=None) -> dict:
+    """Scores from the two matrices of ``segment_sisnr`` - pure host arithmetic, after one copy.  ``conv_of [G]``: the conversation of each
+    segment, ``track [G]``: its track, ``S_of[r]``: the tracks of conversation ``r``, ``C``: the separator's channels.
+
+    * ``best[g]``: the lowest channel attaining ``max_c v[g][c]``; ``utt[g] = v[g][best[g]] - v_mix[g]``.
+    * A conversation with ``S <= C``: the injective track -> channel assignment ``pi`` maximising ``sum_g v[g][pi(track_g)]`` - the sum
+      taken per (track, channel) in segment order and then over the tracks in order, ties to the lexicographically first ``pi`` -,
+      ``cons[g] = v[g][pi(track_g)] - v_mix[g]``, ``assigned[g] = pi(track_g)``, ``switch[g] = best[g] != assigned[g]``.
+    * ``S > C``: ``cons`` and ``switch`` are NaN, ``assigned`` is -1, and the means leave them out.
+
+    Means: ``sisnri_utt``, ``sisnri_cons``, ``switch_rate``; with ``overlap`` (``overlap_fraction`` per segment) also ``bins``: per overlap bin
+    ``{"n", "sisnri_utt", "sisnri_cons"}`` in the order of ``OVERLAP_BINS``."""
+    v = (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)).astype(np.float64).reshape(-1, int(C))
+    v_mix = (v_mix.detach().cpu().numpy() if isinstance(v_mix, torch.Tensor) else np.asarray(v_mix)).astype(np.float64).reshape(-1)
+    conv_of, track = np.asarray(conv_of, dtype=np.int64), np.asarray(track, dtype=np.int64)
+    G = v.shape[0]
+    if not (v_mix.shape[0] == conv_of.shape[0] == track.shape[0] == G):
+        raise ValueError("one row of v, v_mix, conv_of and track per segment")
+    best = np.argmax(v, axis=1).astype(np.int64)                  # numpy's argmax returns the first maximum: the lowest channel
+    utt = v[np.arange(G), best] - v_mix
+    cons = np.full(G, np.nan)
+    switch = np.full(G, np.nan)
+    assigned = np.full(G, -1, dtype=np.int64)
+    assignment: Dict[int, Optional[Tuple[int, ...]]] = {}
+    for r in sorted(set(conv_of.tolist())):
+        S = int(S_of[r])
+        idx = np.nonzero(conv_of == r)[0]
+        if S > C:
+            assignment[r] = None
+            continue
+        M = np.zeros((S, C))
+        for g in idx:                                             # in segment order
+            M[track[g]] += v[g]
+        top, pi = -np.inf, None
+        for cand in itertools.permutations(range(C), S):          # lexicographic order; a later candidate must be strictly better
+            tot = 0.0
+            for s in range(S):
+                tot += M[s, cand[s]]
+            if pi is None or tot > top:
+                top, pi = tot, cand
+        assignment[r] = pi
+        assigned[idx] = np.asarray(pi, dtype=np.int64)[track[idx]]
+        cons[idx] = v[idx, assigned[idx]] - v_mix[idx]
+        switch[idx] = (best[idx] != assigned[idx]).astype(np.float64)
+    out = {"best": best, "assigned": assigned, "utt": utt, "cons": cons, "switch": switch, "assignment": assignment,
+           "sisnri_utt": _mean(utt), "sisnri_cons": _mean(cons), "switch_rate": _mean(switch), "n": int(G)}
+    if overlap is not None:
+        ov = np.asarray(overlap, dtype=np.float64)
+        which = np.array([overlap_bin(f) for f in ov])
+        out["overlap"] = ov
+        out["bins"] = {name: {"n": int((which == k).sum()), "sisnri_utt": _mean(utt[which == k]), "sisnri_cons": _mean(cons[which == k])}
+                       for k, name in enumerate(OVERLAP_BINS)}
+    return out

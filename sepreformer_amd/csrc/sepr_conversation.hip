@@ -1,0 +1,303 @@
+// Conversations rendered and scored on the device (contracts in include/sepr.h).
+//
+//   render_kernel        (sepr_conversation_render) mixture and per-talker tracks of R conversations of any length from the resident corpus of
+//                        the mixing launch.  A conversation is a schedule of segments - utterance, first sample used, output sample where it
+//                        lands, length, the two factors - sorted by (track, place).  One thread per four flat output samples (one float4 store per
+//                        row); a workgroup makes 1024.  The conversation of the tile's first sample and, per track, its first live segment are found
+//                        by binary search on addresses that depend on the workgroup alone (scalar loads); a thread walks forward from there, and
+//                        only a thread that lies in a later conversation than its tile's first sample searches for itself.  A segment that covers
+//                        the thread's four samples is read with two aligned 16-byte (float32) or 8-byte (int16) loads and realigned in registers;
+//                        a segment's first and last samples, where it covers part of the four, one clamped element at a time.
+//                        The arithmetic is sepr_dynmix_fwd's: (x * norm) * gain, two roundings, the tracks summed in track order from +0.
+//   segsnr_ref_kernel / segsnr_value_kernel   (sepr_segment_sisnr_fwd) the segment-wise SI-SNR of every output channel and of the mixture against
+//                        every utterance, in float64.  One workgroup per segment takes the reference's mean and centred energy into the workspace;
+//                        one workgroup per (signal, segment) then makes three passes over the segment - the signal's mean, the centred cross term,
+//                        and, alpha known, the residual summed directly.  A thread adds the samples tid, tid + 256, ... in order, a wave adds its
+//                        lanes by butterfly, and the four wave sums are added in wave order: a fixed order, no atomics.
+// Nothing here depends on the launch order of workgroups: results are bit-identical from run to run.  Neither entry trusts its device tables: every
+// index read from one is clamped, so a bad table gives wrong values but no access outside the buffers.
+#include "sepr_common.h"
+
+namespace sepr {
+namespace {
+constexpr int CV_TPB = 256;              // threads per workgroup of the render kernel
+constexpr int CV_PER = 4;                // output samples per thread: one float4
+constexpr int CV_TILE = CV_TPB * CV_PER;
+constexpr int CV_MAX_TRACKS = 8;
+constexpr int SN_TPB = 256;              // threads per workgroup of the metric kernels
+constexpr int SN_MAX_CH = 8;
+
+__device__ __forceinline__ long long cv_clamp(long long v, long long lo, long long hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+struct CvCorpus {
+  const short* buf16;
+  const float* buf32;
+  const long long* off;
+  long long total16, total32;
+  int N16, N;
+};
+
+struct CvTable {
+  const int* utt;
+  const int* start;
+  const int* place;
+  const int* len;
+  const float* norm;
+  const float* gain;
+  const int* track_off;                  // [R * S + 1] cumulative segment counts per (conversation, track)
+  const long long* out_off;              // [R + 1]
+  int R, S, G;
+};
+
+// one utterance's slice of the corpus buffers under a clamped index and start: element e0 of its buffer is the segment's first sample
+struct CvUtt {
+  long long e0, total;
+  bool is16;
+  __device__ __forceinline__ CvUtt(const CvCorpus& c, int utt, int start) {
+    const int u = utt < 0 ? 0 : (utt >= c.N ? c.N - 1 : utt);
+    const long long o0 = c.off[u], len = c.off[u + 1] - o0;
+    is16 = u < c.N16;
+    total = is16 ? c.total16 : c.total32;
+    e0 = o0 - (is16 ? 0 : c.off[c.N16]) + cv_clamp(start, 0, len > 0 ? len : 0);
+  }
+  // the sample d of the segment, its element position clamped into the buffer
+  __device__ __forceinline__ float one(const CvCorpus& c, long long d) const {
+    const long long e = cv_clamp(e0 + d, 0, total - 1);
+    return is16 ? (float)c.buf16[e] * 3.0517578125e-05f : c.buf32[e];
+  }
+  // the samples d .. d + 3 of the segment: aligned loads at the aligned-down element, realigned in registers.  The first element is clamped into
+  // the buffer and the second load is made only below the buffer's allocated end (its element count rounded up to 16 bytes): no load leaves it.
+  __device__ __forceinline__ void four(const CvCorpus& c, long long d, float x[4]) const {
+    const long long e = cv_clamp(e0 + d, 0, total - 1), a0 = e & ~3LL;
+    const int sh = (int)(e & 3);
+    if (is16) {
+      const long long pad = (total + 7) & ~7LL;
+      const uint2 lo = *reinterpret_cast<const uint2*>(c.buf16 + a0);
+      const uint2 hi = a0 + 4 < pad ? *reinterpret_cast<const uint2*>(c.buf16 + a0 + 4) : make_uint2(0u, 0u);
+      const unsigned w[4] = {lo.x, lo.y, hi.x, hi.y};
+      const int ds = sh >> 1;
+      const unsigned u0 = ds ? w[1] : w[0], u1 = ds ? w[2] : w[1], u2 = ds ? w[3] : w[2];
+      const bool odd = sh & 1;
+      const unsigned d0 = odd ? __builtin_amdgcn_alignbyte(u1, u0, 2) : u0, d1 = odd ? __builtin_amdgcn_alignbyte(u2, u1, 2) : u1;
+      x[0] = (float)(short)(d0 & 0xffffu) * 3.0517578125e-05f;
+      x[1] = (float)((int)d0 >> 16) * 3.0517578125e-05f;
+      x[2] = (float)(short)(d1 & 0xffffu) * 3.0517578125e-05f;
+      x[3] = (float)((int)d1 >> 16) * 3.0517578125e-05f;
+    } else {
+      const long long pad = (total + 3) & ~3LL;
+      const float4 q0 = ld4(c.buf32 + a0);
+      const float4 q1 = a0 + 4 < pad ? ld4(c.buf32 + a0 + 4) : zero4();
+      const float w[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) x[k] = sh == 0 ? w[k] : (sh == 1 ? w[k + 1] : (sh == 2 ? w[k + 2] : w[k + 3]));
+    }
+  }
+};
+
+// the conversation of flat output sample f: the last r in [0, R) with out_off[r] <= f (0 when there is none)
+__device__ __forceinline__ int cv_conversation(const long long* __restrict__ out_off, int R, long long f) {
+  int lo = 0, hi = R;                                              // the answer lies in [lo, hi)
+  while (hi - lo > 1) {
+    const int mid = lo + ((hi - lo) >> 1);
+    if (out_off[mid] <= f) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// the first segment of (conversation, track) j - the segments [lo, hi) of the table, both clamped into [0, G] - that is live at or after sample t: the
+// first with place + len > t, or hi.  The segments of a track are sorted by place and do not overlap, so their ends are sorted too: that is the
+// last segment with place <= t if it reaches past t, else the one after it.
+__device__ __forceinline__ int cv_first_live(const CvTable& tb, int j, long long t, int& hi) {
+  const int* __restrict__ place = tb.place;
+  const int* __restrict__ len = tb.len;
+  int lo = tb.track_off[j];
+  hi = tb.track_off[j + 1];
+  lo = lo < 0 ? 0 : (lo > tb.G ? tb.G : lo);
+  hi = hi < lo ? lo : (hi > tb.G ? tb.G : hi);
+  int a = lo, b = hi;                                              // place[g] <= t for g in [lo, a), place[g] > t for g in [b, hi)
+  while (a < b) {
+    const int mid = a + ((b - a) >> 1);
+    if (place[mid] <= t) a = mid + 1; else b = mid;
+  }
+  if (a > lo && (long long)place[a - 1] + len[a - 1] > t) return a - 1;
+  return a;
+}
+
+__global__ __launch_bounds__(CV_TPB) void render_kernel(CvCorpus c, CvTable tb, long long total, float* __restrict__ mix, float* __restrict__ tracks) {
+#pragma clang fp contract(off)
+  const long long tile0 = (long long)blockIdx.x * CV_TILE;
+  const long long f0 = tile0 + (long long)threadIdx.x * CV_PER;      // total is a multiple of 4: a thread's four samples are all below it or none is
+  if (f0 >= total) return;
+  const int rt = cv_conversation(tb.out_off, tb.R, tile0);          // of the tile's first sample: workgroup-uniform
+  const bool mine = f0 >= tb.out_off[rt + 1] && rt + 1 < tb.R;      // this thread lies in a later conversation (offsets are multiples of 4)
+  const int r = mine ? cv_conversation(tb.out_off, tb.R, f0) : rt;
+  const long long t0 = f0 - tb.out_off[r], tt = tile0 - tb.out_off[rt];
+  float acc[CV_PER] = {0.f, 0.f, 0.f, 0.f};
+  for (int s = 0; s < tb.S; ++s) {
+    int g, hi;
+    if (!mine) {
+      g = cv_first_live(tb, rt * tb.S + s, tt, hi);                // workgroup-uniform; the thread walks on from it below
+    } else {
+      g = cv_first_live(tb, r * tb.S + s, t0, hi);
+    }
+    float v[CV_PER] = {0.f, 0.f, 0.f, 0.f};                        // +0.0 where no segment of the track covers the sample
+    for (; g < hi; ++g) {
+      const long long p = tb.place[g], q = p + tb.len[g];          // the segment covers [p, q)
+      if (q <= t0) continue;
+      if (p >= t0 + CV_PER) break;
+      const CvUtt ut(c, tb.utt[g], tb.start[g]);
+      const float norm = tb.norm[g], gain = tb.gain[g];
+      if (p <= t0 && q >= t0 + CV_PER) {
+        float x[CV_PER];
+        ut.four(c, t0 - p, x);
+#pragma unroll
+        for (int i = 0; i < CV_PER; ++i) {
+          const float a = x[i] * norm;
+          v[i] = a * gain;
+        }
+      } else {
+#pragma unroll
+        for (int i = 0; i < CV_PER; ++i) {
+          if (t0 + i >= p && t0 + i < q) {
+            const float a = ut.one(c, t0 + i - p) * norm;
+            v[i] = a * gain;
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < CV_PER; ++i) acc[i] = acc[i] + v[i];       // ((0 + track 0) + track 1) + ...
+    if (tracks) st4(tracks + (long long)s * total + f0, make_float4(v[0], v[1], v[2], v[3]));
+  }
+  st4(mix + f0, make_float4(acc[0], acc[1], acc[2], acc[3]));
+}
+
+// ---- segment-wise SI-SNR ------------------------------------------------------------------------------------------------------------------
+struct SnSeg {
+  const float* r;                        // the reference segment's first sample
+  long long b;                           // its first sample's index in a row
+  int n;
+};
+
+// segment g under clamps: the row into [0, S), begin into [0, T], the length into [0, T - begin]
+__device__ __forceinline__ SnSeg sn_segment(const float* __restrict__ ref, const int* __restrict__ rows, const int* __restrict__ begin,
+                                            const int* __restrict__ length, int g, int S, int T, long long ld) {
+  const int row = rows[g] < 0 ? 0 : (rows[g] >= S ? S - 1 : rows[g]);
+  const int b = begin[g] < 0 ? 0 : (begin[g] > T ? T : begin[g]);
+  const int n = length[g] < 0 ? 0 : (length[g] > T - b ? T - b : length[g]);
+  return {ref + (long long)row * ld + b, b, n};
+}
+
+// the sum of one value per thread over the workgroup, in a fixed order; every thread gets it.  Two barriers.
+__device__ __forceinline__ double sn_block_sum(double v, double* red) {
+  v = wave_sum_d(v);
+  __syncthreads();                                                 // the readers of the sum before are done with red
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+__global__ __launch_bounds__(SN_TPB) void segsnr_ref_kernel(const float* __restrict__ ref, const int* __restrict__ rows, const int* __restrict__ begin,
+                                                            const int* __restrict__ length, int S, int T, long long ld, double* __restrict__ stat) {
+#pragma clang fp contract(off)
+  __shared__ double red[SN_TPB / 64];
+  const int g = blockIdx.x, tid = threadIdx.x;
+  const SnSeg sg = sn_segment(ref, rows, begin, length, g, S, T, ld);
+  double a = 0.0;
+  for (int i = tid; i < sg.n; i += SN_TPB) a += (double)sg.r[i];
+  const double mean = sg.n > 0 ? sn_block_sum(a, red) / (double)sg.n : 0.0;
+  double e = 0.0;
+  for (int i = tid; i < sg.n; i += SN_TPB) {
+    const double d = (double)sg.r[i] - mean;
+    e += d * d;
+  }
+  e = sn_block_sum(e, red);
+  if (tid == 0) {
+    stat[2 * (long long)g] = mean;
+    stat[2 * (long long)g + 1] = e;
+  }
+}
+
+// signal k = blockIdx.y < C is channel k of est, k = C the mixture; against segment g = blockIdx.x
+__global__ __launch_bounds__(SN_TPB) void segsnr_value_kernel(const float* __restrict__ est, const float* __restrict__ ref, const float* __restrict__ mix,
+                                                              const int* __restrict__ rows, const int* __restrict__ begin,
+                                                              const int* __restrict__ length, int C, int S, int T, long long ld, double eps,
+                                                              const double* __restrict__ stat, double* __restrict__ v, double* __restrict__ v_mix) {
+#pragma clang fp contract(off)
+  __shared__ double red[SN_TPB / 64];
+  const int g = blockIdx.x, k = blockIdx.y, tid = threadIdx.x;
+  const SnSeg sg = sn_segment(ref, rows, begin, length, g, S, T, ld);
+  const float* __restrict__ x = (k < C ? est + (long long)k * ld : mix) + sg.b;
+  const double mr = stat[2 * (long long)g], srr = stat[2 * (long long)g + 1];
+  double a = 0.0;
+  for (int i = tid; i < sg.n; i += SN_TPB) a += (double)x[i];
+  const double ma = sg.n > 0 ? sn_block_sum(a, red) / (double)sg.n : 0.0;
+  double sar = 0.0;
+  for (int i = tid; i < sg.n; i += SN_TPB) sar += ((double)x[i] - ma) * ((double)sg.r[i] - mr);
+  sar = sn_block_sum(sar, red);
+  const double alpha = sar / (srr + eps);
+  double res = 0.0;
+  for (int i = tid; i < sg.n; i += SN_TPB) {                       // the residual itself, not a difference of moments
+    const double d = ((double)x[i] - ma) - alpha * ((double)sg.r[i] - mr);
+    res += d * d;
+  }
+  res = sn_block_sum(res, red);
+  if (tid == 0) {
+    const double val = 20.0 * log10(eps + fabs(alpha) * sqrt(srr) / (sqrt(res) + eps));
+    if (k < C) v[(long long)g * C + k] = val; else v_mix[g] = val;
+  }
+}
+
+struct SnLayout {
+  double* stat;                          // [G][2]: the reference segment's mean and centred energy
+  SnLayout(Arena& a, int G) { stat = a.f64(2 * (size_t)G); }
+};
+}  // namespace
+}  // namespace sepr
+
+extern "C" int sepr_conversation_render(const short* buf16, long long total16, const float* buf32, long long total32, const long long* offsets, int N16,
+                                        int N, const int* seg_utt, const int* seg_start, const int* seg_place, const int* seg_len,
+                                        const float* seg_norm, const float* seg_gain, const int* track_off, const long long* out_off, int R, int S_max,
+                                        int G, long long total, float* mix, float* tracks, sepr_stream_t stream) {
+  using namespace sepr;
+  if (!offsets || N < 1 || N16 < 0 || N16 > N || total16 < 0 || total32 < 0) return SEPR_EINVAL;
+  if ((N16 > 0 && (!buf16 || total16 < 1)) || (N > N16 && (!buf32 || total32 < 1))) return SEPR_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(buf16) | reinterpret_cast<uintptr_t>(buf32)) % 16 != 0) return SEPR_EINVAL;       // aligned vector loads
+  if (!seg_utt || !seg_start || !seg_place || !seg_len || !seg_norm || !seg_gain || !track_off || !out_off || !mix) return SEPR_EINVAL;
+  if (R < 1 || R > 65535 || S_max < 1 || S_max > CV_MAX_TRACKS || G < 1) return SEPR_EINVAL;
+  if (total < 4 || total % 4 != 0 || total > (1LL << 40)) return SEPR_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(mix) | reinterpret_cast<uintptr_t>(tracks)) % 16 != 0) return SEPR_EINVAL;       // float4 stores
+  if (reinterpret_cast<uintptr_t>(out_off) % 8 != 0) return SEPR_EINVAL;
+  const CvCorpus c = {buf16, buf32, offsets, total16, total32, N16, N};
+  const CvTable tb = {seg_utt, seg_start, seg_place, seg_len, seg_norm, seg_gain, track_off, out_off, R, S_max, G};
+  hipLaunchKernelGGL(render_kernel, dim3((unsigned)cdiv(total, CV_TILE)), dim3(CV_TPB), 0, static_cast<hipStream_t>(stream), c, tb, total, mix,
+                     tracks);
+  SEPR_CHECK_LAUNCH("conversation render kernel");
+  return SEPR_OK;
+}
+
+extern "C" long long sepr_segment_sisnr_bytes(int G, int C) {
+  using namespace sepr;
+  if (G < 1 || C < 1 || C > SN_MAX_CH) return 0;
+  return (long long)layout_bytes<SnLayout>(G);
+}
+
+extern "C" int sepr_segment_sisnr_fwd(const float* est, const float* ref, const float* mix, const int* rows, const int* begin, const int* length, int G,
+                                      int C, int S, int T, long long ld, double eps, double* v, double* v_mix, void* ws, size_t ws_bytes,
+                                      sepr_stream_t stream) {
+  using namespace sepr;
+  if (!est || !ref || !mix || !rows || !begin || !length || !v || !v_mix) return SEPR_EINVAL;
+  if (G < 1 || C < 1 || C > SN_MAX_CH || S < 1 || S > CV_MAX_TRACKS || T < 1 || ld < T) return SEPR_EINVAL;
+  if (!(eps >= 0.0 && eps <= 1.0)) return SEPR_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(est) | reinterpret_cast<uintptr_t>(ref) | reinterpret_cast<uintptr_t>(mix)) % 4 != 0) return SEPR_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(v_mix)) % 8 != 0) return SEPR_EINVAL;
+  Arena arena(ws, ws_bytes);
+  const SnLayout lay(arena, G);
+  if (!arena.ok_need()) return SEPR_EWORKSPACE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(segsnr_ref_kernel, dim3((unsigned)G), dim3(SN_TPB), 0, st, ref, rows, begin, length, S, T, ld, lay.stat);
+  hipLaunchKernelGGL(segsnr_value_kernel, dim3((unsigned)G, (unsigned)(C + 1)), dim3(SN_TPB), 0, st, est, ref, mix, rows, begin, length, C, S, T, ld,
+                     eps, lay.stat, v, v_mix);
+  SEPR_CHECK_LAUNCH("segment SI-SNR kernels");
+  return SEPR_OK;
+}

@@ -266,6 +266,66 @@ def evaluate_utterances_all(model, utterances: Iterable[Tuple[torch.Tensor, Sequ
 test_utterances.__test__ = False      # not a pytest test
 
 
+def evaluate_conversations(model, corpus, convs, method: str = "long", chunk_seconds: float = 4.0, overlap_seconds: float = 1.0,
+                           batch: int = 32, slots: int = 32, match_gain: bool = False, csv_path: Optional[str] = None,
+                           wav_dir: Optional[str] = None, fs: int = 8000) -> dict:
+    """The test loop of the long-form paths: render every conversation of ``convs`` from the resident ``corpus``
+    in one launch (``conversation.render``), separate every mixture with ``separate_long`` (``method="long"``) or
+    ``streambank.separate_many`` (``"bank"``), score every output channel against every utterance over that utterance's span
+    (``conversation.segment_sisnr``, one call per conversation on views of the flat buffers) and reduce (``conversation.score``).
+    Returns that dict - ``sisnri_utt``, ``sisnri_cons``, ``switch_rate``, ``bins`` by overlap fraction, the per-segment vectors - plus
+    ``v`` ``[G, C]`` and ``v_mix`` ``[G]`` (numpy) and ``conversations``.  ``csv_path``: one row per segment - conversation key, segment
+    number, track, utterance name, begin, length, overlap fraction, best channel, assigned channel (-1 with more talkers than
+    channels), ``v_mix``, ``v[0 .. C - 1]`` - in the csv dialect of the test loop.  ``wav_dir``: the mixture and the outputs of every
+    conversation, ``0.5 / max|.|`` as ``test_save`` writes them."""
+    from . import conversation as cv
+    if method not in ("long", "bank"):
+        raise ValueError(f"method must be 'long' or 'bank', got {method!r}")
+    convs = list(convs)
+    rd = cv.render(corpus, convs, tracks=True)
+    mixes = [rd.mixture(r) for r in range(len(convs))]
+    if method == "long":
+        ests = separate_long(model, mixes, chunk_seconds=chunk_seconds, overlap_seconds=overlap_seconds, fs=fs, batch=batch,
+                             match_gain=match_gain)
+    else:
+        from .streambank import separate_many
+        ests = separate_many(model, mixes, slots=slots, chunk_seconds=chunk_seconds, overlap_seconds=overlap_seconds, fs=fs,
+                             match_gain=match_gain)
+    C = model.num_spks
+    est_all = torch.empty(C, rd.table.total, dtype=torch.float32, device=rd.mix.device)      # the row stride of the tracks: no repacking below
+    vs, vms = [], []
+    for r, (conv, est) in enumerate(zip(convs, ests)):
+        a, b = int(rd.out_off[r]), int(rd.out_off[r + 1])
+        for c in range(C):
+            est_all[c, a:b].copy_(est[c])
+        v, v_mix = cv.segment_sisnr(est_all[:, a:b], rd.tracks_of(r), rd.mixture(r), conv.track, conv.place, conv.len)
+        vs.append(v)
+        vms.append(v_mix)
+    v, v_mix = torch.cat(vs).cpu().numpy(), torch.cat(vms).cpu().numpy()                      # the one copy of the scores
+    conv_of = np.concatenate([np.full(len(c.utt), r) for r, c in enumerate(convs)])
+    out = cv.score(v, v_mix, conv_of, np.concatenate([c.track for c in convs]), [c.S for c in convs], C,
+                   overlap=np.concatenate([cv.overlap_fraction(c) for c in convs]))
+    out.update(v=v, v_mix=v_mix, conversations=len(convs))
+    if csv_path:
+        with open(csv_path, "w", newline="") as fh:
+            w = csv.writer(fh, quotechar="|", quoting=csv.QUOTE_MINIMAL)
+            g = 0
+            for conv in convs:
+                for k in range(len(conv.utt)):
+                    w.writerow([conv.key, k, int(conv.track[k]), corpus.names[int(conv.utt[k])], int(conv.place[k]), int(conv.len[k]),
+                                float(out["overlap"][g]), int(out["best"][g]), int(out["assigned"][g]), float(v_mix[g])] +
+                               [float(x) for x in v[g]])
+                    g += 1
+    if wav_dir:
+        os.makedirs(wav_dir, exist_ok=True)
+        for r, conv in enumerate(convs):
+            name = conv.key.replace("/", "_")
+            write_wav(os.path.join(wav_dir, f"{name}{r}_mixture.wav"), peak_normalise(mixes[r].cpu().numpy(), 0.5), fs)
+            for c in range(C):
+                write_wav(os.path.join(wav_dir, f"{name}{r}_out_{c}.wav"), peak_normalise(ests[r][c].cpu().numpy(), 0.5), fs)
+    return out
+
+
 def load_checkpoint_weights(model, path: str, ema: bool = False):
     """The weights of a checkpoint - the reference's, or one ``trainer.Trainer`` wrote (the same five keys) - or of a bare state dict.
     ``ema=True``: the averaged weights a ``Trainer(ema_decay=...)`` run saved beside them (``ema_state_dict``: the same keys, parameters

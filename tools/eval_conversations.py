@@ -1,0 +1,85 @@
+#!/usr/bin/env python3
+"""Score long-form separation on conversations rendered on the device (infer.evaluate_conversations).
+
+The utterances of the scp lists are loaded into a device-resident ``Corpus``; COUNT conversations of MINUTES minutes are planned from them
+(``conversation.plan_conversation``, seed = the conversation's number), rendered in one launch, separated with ``separate_long``
+(``--method long``) or the stream bank (``--method bank``) and scored per utterance: SI-SNRi of the best channel per utterance, SI-SNRi
+under the one consistent track -> channel assignment, the rate of channel switches, all three also by overlap ratio.
+
+    python tools/eval_conversations.py --scp s1=tt_s1.scp s2=tt_s2.scp --count 20 --minutes 10 --overlap 0:0.4 --method bank [--checkpoint F [--ema]]
+"""
+import argparse
+import json
+import os
+import random
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def _range(text, what):
+    lo, _, hi = text.partition(":")
+    try:
+        return float(lo), float(hi if hi else lo)
+    except ValueError:
+        raise SystemExit(f"{what}: expected LO:HI, got {text!r}")
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--scp", nargs="+", required=True, metavar="ROLE=FILE", help="utterance lists, one role per talker position: s1=... s2=...")
+    ap.add_argument("--count", type=int, default=20, help="conversations")
+    ap.add_argument("--minutes", type=float, default=10.0, help="length of each conversation")
+    ap.add_argument("--speakers", type=int, default=2, help="talker tracks per conversation (more than the model's channels: no assignment scores)")
+    ap.add_argument("--overlap", default="0:0.4", metavar="LO:HI", help="overlap of a turn with the one before, as a share of the shorter utterance")
+    ap.add_argument("--pause", default="0:1", metavar="LO:HI", help="seconds between turns that do not overlap")
+    ap.add_argument("--p-overlap", type=float, default=0.5, help="probability that a turn overlaps the one before")
+    ap.add_argument("--max-active", type=int, default=2, help="talkers active at once, at most")
+    ap.add_argument("--method", choices=["long", "bank"], default="long")
+    ap.add_argument("--chunk-seconds", type=float, default=4.0)
+    ap.add_argument("--overlap-seconds", type=float, default=1.0)
+    ap.add_argument("--batch", type=int, default=32, help="--method long: windows per forward")
+    ap.add_argument("--slots", type=int, default=32, help="--method bank: conversations in flight")
+    ap.add_argument("--match-gain", action="store_true")
+    ap.add_argument("--model", default="SepReformer_Base_WSJ0")
+    ap.add_argument("--checkpoint", default=None, help="checkpoint (.pth with model_state_dict); default: synthetic weights")
+    ap.add_argument("--ema", action="store_true", help="with --checkpoint: the averaged weights a run with a weight EMA saved")
+    ap.add_argument("--fs", type=int, default=8000)
+    ap.add_argument("--resample", action="store_true", help="convert files at another rate on the device (default: an error)")
+    ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--csv", default=None, help="one row per utterance of every conversation")
+    ap.add_argument("--wav-dir", default=None, help="write every mixture and every output channel")
+    args = ap.parse_args()
+    if args.ema and not args.checkpoint:
+        ap.error("--ema needs --checkpoint")
+    scps = {}
+    for item in args.scp:
+        role, eq, path = item.partition("=")
+        if not eq or not role or not path:
+            ap.error(f"--scp takes ROLE=FILE, got {item!r}")
+        scps[role] = path
+    from sepreformer_amd import conversation as cv
+    from sepreformer_amd import infer
+    from sepreformer_amd.config import VARIANTS
+    from sepreformer_amd.datafeed import Corpus
+    from sepreformer_amd.model import Model
+    model = Model.from_config(VARIANTS[args.model], init_seed=0)
+    if args.checkpoint:
+        infer.load_checkpoint_weights(model, args.checkpoint, ema=args.ema)
+    else:
+        model.load_synthetic_(0)
+    model = model.eval().to(args.device)
+    corpus = Corpus.from_scp(scps, fs=args.fs, device=args.device, resample=args.resample)
+    convs = [cv.plan_conversation(corpus, random.Random(i), seconds=60.0 * args.minutes, roles=tuple(scps), speakers=args.speakers,
+                                  overlap=_range(args.overlap, "--overlap"), pause=_range(args.pause, "--pause"), p_overlap=args.p_overlap,
+                                  max_active=args.max_active, key=f"conv{i:03d}") for i in range(args.count)]
+    out = infer.evaluate_conversations(model, corpus, convs, method=args.method, chunk_seconds=args.chunk_seconds,
+                                       overlap_seconds=args.overlap_seconds, batch=args.batch, slots=args.slots, match_gain=args.match_gain,
+                                       csv_path=args.csv, wav_dir=args.wav_dir, fs=args.fs)
+    print(json.dumps({"method": args.method, "conversations": out["conversations"], "utterances": out["n"], "sisnri_utt": out["sisnri_utt"],
+                      "sisnri_cons": out["sisnri_cons"], "switch_rate": out["switch_rate"], "bins": out["bins"]}))
+
+
+if __name__ == "__main__":
+    main()
