@@ -333,6 +333,20 @@ int sepr_pit_sisnr_mag_fwd(const float* est, const float* tgt, int S, int B, int
                            int frame_len, int frame_shift, double eps, float* loss, int* perm, void* ws,
                            size_t ws_bytes, sepr_stream_t stream);
 
+/* Source-aggregated, soft-thresholded SDR (SA-SDR with a threshold) - beyond the reference.  One ratio per
+ * utterance over all S sources, not scale-invariant, defined when a target is silent (~ = zero-mean):
+ *   D = sum_k |t~_k|^2,  E_p = sum_s |e~_s - t~_p(s)|^2,  loss[b] = min over permutations of 10 log10((E_p + tau D + eps) / (D + eps)),
+ *   tau = 10^(-snr_max / 10) (snr_max = 30: the -30 dB floor clamp_min gives the SI-SNR form), eps = 1e-8.
+ * perm [B,S] (NULL to skip) = the first minimiser of E_p in itertools.permutations order.  The magnitude form is the same expression on
+ * M = sqrt(re^2 + im^2 + 1e-10) of the conv-STFT of the zero-mean signals (geometry, padding and `dft` of sepr_pit_sisnr_mag_fwd, target
+ * scale 1, no projection), norms over bins and frames.  Same arguments as the SI-SNR siblings, snr_max in the place of clamp_min.
+ * Workspaces are the siblings' layouts and are sized by the siblings' entries: sepr_workspace_bytes(SEPR_OP_PIT, B, T, 0, 0, 0, S) and
+ * sepr_pit_sisnr_mag_workspace(S, B, T, frame_len, frame_shift). */
+int sepr_pit_sasdr_fwd(const float* est, const float* tgt, int S, int B, int T, double eps, double snr_max, float* loss, int* perm,
+                       void* ws, size_t ws_bytes, sepr_stream_t stream);
+int sepr_pit_sasdr_mag_fwd(const float* est, const float* tgt, int S, int B, int T, const float* dft, int frame_len, int frame_shift,
+                           double eps, double snr_max, float* loss, int* perm, void* ws, size_t ws_bytes, sepr_stream_t stream);
+
 /* BSS-eval source criteria of mir_eval 0.7 bss_eval_sources (compute_permutation=True, distortion filters of 512 taps), the
  * metric behind PIT_SDRi (utils/implements/criterions.py:264-289, engine.py:133) - evaluation only, no backward.
  * est, ref [S,B,T] float32 on the device, 2 <= S <= 3; mix [B,T] or NULL (then sdr_mix must be NULL); lengths [B] is a HOST
@@ -926,6 +940,15 @@ int sepr_pit_sisnr_mag_bwd(const float* est, const float* tgt, const int* perm, 
                            const float* dft_t, int frame_len, int frame_shift, double eps, float* dest, void* ws, size_t ws_bytes,
                            sepr_stream_t stream);
 size_t sepr_pit_sisnr_mag_bwd_workspace(int S, int B, int T, int frame_len, int frame_shift);
+/* Backward of sepr_pit_sasdr_fwd / sepr_pit_sasdr_mag_fwd: d(sum_b loss[b] * gl[b]) / d est with the forward's perm held fixed,
+ *   d loss[b] / d e_s = (20 / ln 10) / (E + tau D + eps) (e~_s - t~_p(s))     (on M, then re / M, STFT adjoint, overlap-add, de-mean)
+ * - no clamp branch, nothing flows through a target scale.  A pair that is bit-equal gets a gradient that is exactly 0.  Workspaces: the
+ * siblings' (sepr_pit_sisnr_bwd's, sepr_pit_sisnr_mag_bwd_workspace). */
+int sepr_pit_sasdr_bwd(const float* est, const float* tgt, const int* perm, const float* gl, int S, int B, int T, double eps,
+                       double snr_max, float* dest, void* ws, size_t ws_bytes, sepr_stream_t stream);
+int sepr_pit_sasdr_mag_bwd(const float* est, const float* tgt, const int* perm, const float* gl, int S, int B, int T, const float* dft,
+                           const float* dft_t, int frame_len, int frame_shift, double eps, double snr_max, float* dest, void* ws,
+                           size_t ws_bytes, sepr_stream_t stream);
 
 /* ---- optimizer step of the reference loop (ABI 3.03) ------------------------------------------------
  * engine.py:76-77: torch.nn.utils.clip_grad_norm_(params, max_norm) + torch.optim.AdamW.step() as three launches over the whole

@@ -20,6 +20,10 @@ Training: when an estimate requires grad, ``PIT_SISNR_t
 autograd-connected scalar; their backward is ``sepr_pit_sisnr_bwd`` / ``sepr_pit_sisnr_mag_bwd`` (closed form from the same
 moments; the STFT adjoint is one more projection with the transposed DFT kernel), the permutation chosen in the forward
 is held fixed, as ``torch.min`` does in the reference.
+
+Beyond the reference: ``PIT_SASDR_time`` / ``PIT_SASDR_mag``, the source-aggregated, soft-thresholded SDR with the
+siblings' call surface, defined - value and gradient - when a target is silent throughout (``sepr_pit_sasdr_fwd/_bwd``,
+``sepr_pit_sasdr_mag_fwd/_bwd``; the CPU restatement is ``tests/sasdr_ref.py``).
 """
 from __future__ import annotations
 
@@ -96,6 +100,60 @@ class _PitMagFn(torch.autograd.Function):
                                                dft_t.data_ptr(), frame_len, frame_shift, eps, dest.data_ptr(), ws.data_ptr(), ws.numel(),
                                                torch.cuda.current_stream(est.device).cuda_stream), "sepr_pit_sisnr_mag_bwd")
         return dest, None, None, None, None, None, None
+
+
+class _SaSdrTimeFn(torch.autograd.Function):
+    """Per-utterance PIT_SASDR_time loss with d/d est from sepr_pit_sasdr_bwd."""
+
+    @staticmethod
+    def forward(ctx, est, tgt, eps, snr_max):
+        out = pit_sasdr(est, tgt, eps=eps, snr_max=snr_max)
+        ctx.save_for_backward(est, tgt, out["perm"])
+        ctx.consts = (eps, snr_max)
+        return out["loss"]
+
+    @staticmethod
+    def backward(ctx, gl):
+        est, tgt, perm = ctx.saved_tensors
+        eps, snr_max = ctx.consts
+        S, B, T = est.shape
+        lib = L.load()
+        with torch.cuda.device(est.device):
+            nbytes = lib.sepr_workspace_bytes(L.OP_PIT, B, T, 0, 0, 0, S) + 16 * B * S + 512     # sepr_pit_sisnr_bwd's layout
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=est.device)
+            dest = torch.empty_like(est)
+            glc = gl.detach().to(torch.float32).contiguous()
+            L.check(lib.sepr_pit_sasdr_bwd(est.data_ptr(), tgt.data_ptr(), perm.data_ptr(), glc.data_ptr(), S, B, T, eps, snr_max,
+                                           dest.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(est.device).cuda_stream),
+                    "sepr_pit_sasdr_bwd")
+        return dest, None, None, None
+
+
+class _SaSdrMagFn(torch.autograd.Function):
+    """Per-utterance PIT_SASDR_mag loss with d/d est from sepr_pit_sasdr_mag_bwd."""
+
+    @staticmethod
+    def forward(ctx, est, tgt, dft, dft_t, frame_len, frame_shift, eps, snr_max):
+        out = pit_sasdr_mag(est, tgt, dft, frame_len, frame_shift, eps, snr_max)
+        ctx.save_for_backward(est, tgt, out["perm"], dft, dft_t)
+        ctx.consts = (frame_len, frame_shift, eps, snr_max)
+        return out["loss"]
+
+    @staticmethod
+    def backward(ctx, gl):
+        est, tgt, perm, dft, dft_t = ctx.saved_tensors
+        frame_len, frame_shift, eps, snr_max = ctx.consts
+        S, B, T = est.shape
+        lib = L.load()
+        with torch.cuda.device(est.device):
+            nbytes = lib.sepr_pit_sisnr_mag_bwd_workspace(S, B, T, frame_len, frame_shift)
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=est.device)
+            dest = torch.empty_like(est)
+            glc = gl.detach().to(torch.float32).contiguous()
+            L.check(lib.sepr_pit_sasdr_mag_bwd(est.data_ptr(), tgt.data_ptr(), perm.data_ptr(), glc.data_ptr(), S, B, T, dft.data_ptr(),
+                                               dft_t.data_ptr(), frame_len, frame_shift, eps, snr_max, dest.data_ptr(), ws.data_ptr(),
+                                               ws.numel(), torch.cuda.current_stream(est.device).cuda_stream), "sepr_pit_sasdr_mag_bwd")
+        return dest, None, None, None, None, None, None, None
 
 
 def _stack(x: _TensorList, what: str) -> torch.Tensor:
@@ -183,6 +241,51 @@ def pit_sisnr_mag(estims: _TensorList, targets: _TensorList, dft: torch.Tensor, 
     return {"loss": loss, "perm": perm}
 
 
+def pit_sasdr(estims: _TensorList, targets: _TensorList, eps: float = 1.0e-8, snr_max: float = 30.0):
+    """Source-aggregated, soft-thresholded SDR over ``[S,B,T]`` estimates / targets: ``loss`` ``[B]`` =
+    ``min_p 10 log10((E_p + tau D + eps) / (D + eps))`` and ``perm`` ``[B,S]``, the first minimiser of ``E_p``.  Defined for silent targets.
+    ``sepr_pit_sasdr_fwd``: the moment pass of ``pit_sisnr`` and one finalising launch."""
+    est, tgt = _stack(estims, "estims"), _stack(targets, "target_attr")
+    if est.shape != tgt.shape:
+        raise RuntimeError(f"estims {tuple(est.shape)} and targets {tuple(tgt.shape)} differ")
+    S, B, T = est.shape
+    dev = est.device
+    lib = L.load()
+    with torch.cuda.device(dev):
+        nbytes = lib.sepr_workspace_bytes(L.OP_PIT, B, T, 0, 0, 0, S)
+        if nbytes == 0:
+            raise RuntimeError(f"unsupported PIT problem: num_spks={S}, batch={B}, samples={T}")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        loss = torch.empty(B, dtype=torch.float32, device=dev)
+        perm = torch.empty(B, S, dtype=torch.int32, device=dev)
+        L.check(lib.sepr_pit_sasdr_fwd(est.data_ptr(), tgt.data_ptr(), S, B, T, eps, snr_max, loss.data_ptr(), perm.data_ptr(),
+                                       ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream), "sepr_pit_sasdr_fwd")
+    return {"loss": loss, "perm": perm}
+
+
+def pit_sasdr_mag(estims: _TensorList, targets: _TensorList, dft: torch.Tensor, frame_len: int, frame_shift: int,
+                  eps: float = 1.0e-12, snr_max: float = 30.0):
+    """``pit_sasdr`` on the STFT magnitudes of the zero-mean signals (the projection and the pair sums of ``pit_sisnr_mag`` with unit
+    target scales): ``loss`` ``[B]`` and ``perm`` ``[B,S]``.  ``sepr_pit_sasdr_mag_fwd``."""
+    est, tgt = _stack(estims, "estims"), _stack(targets, "target_attr")
+    if est.shape != tgt.shape:
+        raise RuntimeError(f"estims {tuple(est.shape)} and targets {tuple(tgt.shape)} differ")
+    S, B, T = est.shape
+    dev = est.device
+    lib = L.load()
+    with torch.cuda.device(dev):
+        nbytes = lib.sepr_pit_sisnr_mag_workspace(S, B, T, frame_len, frame_shift)
+        if nbytes == 0:
+            raise RuntimeError(f"unsupported PIT_SASDR_mag problem: num_spks={S}, batch={B}, samples={T}")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        loss = torch.empty(B, dtype=torch.float32, device=dev)
+        perm = torch.empty(B, S, dtype=torch.int32, device=dev)
+        L.check(lib.sepr_pit_sasdr_mag_fwd(est.data_ptr(), tgt.data_ptr(), S, B, T, dft.data_ptr(), frame_len, frame_shift, eps, snr_max,
+                                           loss.data_ptr(), perm.data_ptr(), ws.data_ptr(), ws.numel(),
+                                           torch.cuda.current_stream(dev).cuda_stream), "sepr_pit_sasdr_mag_fwd")
+    return {"loss": loss, "perm": perm}
+
+
 class _Base:
     def __init__(self, device, num_spks: int, scale_inv: bool = True):
         if not scale_inv:
@@ -258,6 +361,59 @@ class PIT_SISNR_mag:
             return torch.sum(loss) / kwargs["input_sizes"].shape[0]
         out = pit_sisnr_mag(estims, targets, self._dft, self.frame_length, self.frame_shift)
         return torch.sum(out["loss"]) / kwargs["input_sizes"].shape[0]             # reference :175-176
+
+
+class PIT_SASDR_time:
+    """``PIT_SASDR_time(device, num_spks, snr_max=30.0)`` with the call surface of ``PIT_SISNR_time``: the source-aggregated,
+    soft-thresholded SDR, the criterion for windows in which a talker is silent.  Returns
+    ``num_spks * mean_b loss[b]``: a loop that divides the criterion by ``num_spks`` (``trainer.mix_loss``) then reads dB per utterance, and
+    a fully active example weighs what the sum of its per-source terms weighs in the SI-SNR form."""
+
+    def __init__(self, device, num_spks: int, snr_max: float = 30.0):
+        self.device, self.num_spks, self.snr_max = torch.device(device), num_spks, float(snr_max)
+
+    def __repr__(self):
+        return f"<{type(self).__name__}(device={self.device!r}, num_spks={self.num_spks!r}, snr_max={self.snr_max!r})>"
+
+    def __call__(self, **kwargs) -> torch.Tensor:
+        estims, targets = kwargs["estims"], kwargs["target_attr"]
+        n = estims.shape[0] if isinstance(estims, torch.Tensor) else len(estims)
+        if n != self.num_spks:
+            raise RuntimeError(f"expected {self.num_spks} estimates, got {n}")
+        if _needs_grad(estims):
+            loss = _SaSdrTimeFn.apply(_stack_g(estims), _stack(targets, "target_attr"), 1.0e-8, self.snr_max)
+        else:
+            loss = pit_sasdr(estims, targets, snr_max=self.snr_max)["loss"]
+        return self.num_spks * torch.sum(loss) / kwargs["input_sizes"].shape[0]
+
+
+class PIT_SASDR_mag(PIT_SISNR_mag):
+    """``PIT_SASDR_mag(device, frame_length, frame_shift, window, num_stages, num_spks, snr_max=30.0)`` with the call surface of
+    ``PIT_SISNR_mag`` (whose STFT kernel and eps = 1e-12 it keeps): ``PIT_SASDR_time``'s expression on STFT magnitudes, target scale 1."""
+
+    def __init__(self, device, frame_length: int, frame_shift: int, window: str, num_stages: int, num_spks: int, snr_max: float = 30.0):
+        super().__init__(device, frame_length, frame_shift, window, num_stages, num_spks)
+        self.snr_max = float(snr_max)
+
+    def __repr__(self):
+        return (f"<PIT_SASDR_mag(device={self.device!r}, frame_length={self.frame_length}, frame_shift={self.frame_shift}, "
+                f"window={self.window!r}, num_stages={self.num_stages}, num_spks={self.num_spks}, snr_max={self.snr_max!r})>")
+
+    def __call__(self, **kwargs) -> torch.Tensor:
+        estims, targets = kwargs["estims"], kwargs["target_attr"]
+        if not 0 <= int(kwargs["idx"]) < self.num_stages:
+            raise IndexError("idx out of range")
+        n = estims.shape[0] if isinstance(estims, torch.Tensor) else len(estims)
+        if n != self.num_spks:
+            raise RuntimeError(f"expected {self.num_spks} estimates, got {n}")
+        if self._dft.device.type != "cuda":
+            raise RuntimeError("PIT_SASDR_mag was built for a non-HIP device (no CPU fallback exists)")
+        if _needs_grad(estims):
+            loss = _SaSdrMagFn.apply(_stack_g(estims), _stack(targets, "target_attr"), self._dft, self._dft_t, self.frame_length,
+                                     self.frame_shift, 1.0e-12, self.snr_max)
+        else:
+            loss = pit_sasdr_mag(estims, targets, self._dft, self.frame_length, self.frame_shift, snr_max=self.snr_max)["loss"]
+        return self.num_spks * torch.sum(loss) / kwargs["input_sizes"].shape[0]
 
 
 # ---- BSS-eval SDR (PIT_SDRi, criterions.py:264-289) ----------------------------------------------------------------------

@@ -14,6 +14,9 @@
 // fp64 throughout: the residual energy |a~|^2 - 2 alpha <a~,t~> + alpha^2 |t~|^2 cancels ~3 digits at 30 dB, which
 // fp32 moments could not afford; with fp64 moments the result is the exact-arithmetic value to ~1e-9 dB (the
 // reference's own fp32 evaluation differs from that by up to ~1e-3 dB at high SI-SNR).
+//
+// Beyond the reference: the source-aggregated, soft-thresholded SDR (sepr_pit_sasdr_*) on the same moment pass, the same
+// STFT projection and the same workspaces - a criterion that is defined when a target is silent throughout.
 #include "sepr_gemm_epi.h"
 
 namespace sepr {
@@ -143,6 +146,90 @@ __global__ __launch_bounds__(64) void pit_finalize_kernel(const double* __restri
     if (sisnri_perm) sisnri_perm[b * S + s] = ki;
   }
 }
+// ---- source-aggregated, soft-thresholded SDR: one ratio per utterance over all S sources ----
+//   D = sum_k |t~_k|^2,  E_p = sum_s |e~_s - t~_p(s)|^2,  loss = min_p 10 log10((E_p + tau D + eps) / (D + eps)),  tau = 10^(-snr_max / 10)
+// Not scale-invariant, no per-pair division by |t~_k|^2: a silent target costs nothing to state.  The time form takes its pair energies
+// from the moments (sasdr_pairs), the magnitude form from stft_pair_kernel's sums with unit scales; the walk, the value and the
+// gradient coefficient below serve both.
+template <int S>
+__device__ __forceinline__ int pit_perm_at(int p, int s) {          // itertools.permutations(range(S)) order
+  const int perms[6][3] = {{0, 1, 2}, {0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 0, 1}, {2, 1, 0}};
+  return S == 1 ? 0 : (S == 2 ? (p ^ s) & 1 : perms[p][s]);
+}
+// |e~_s - t~_k|^2 for every pair and D, from the one-pass moments.  A bit-equal pair gives exactly 0 (the three moments are then the same
+// fp64 number); cancellation below 0 is clamped as in pit_finalize_kernel.
+template <int S>
+__device__ __forceinline__ void sasdr_pairs(const double* q, double n, double (&res)[S][S], double& D) {
+  constexpr int NV = 2 * S + 1;
+  double aa[S], tt[S];
+  D = 0.0;
+#pragma unroll
+  for (int i = 0; i < S; ++i) {
+    const double a = q[NV + i] - q[i] * q[i] / n, t = q[NV + S + i] - q[S + i] * q[S + i] / n;
+    aa[i] = a > 0.0 ? a : 0.0;
+    tt[i] = t > 0.0 ? t : 0.0;
+    D += tt[i];
+  }
+#pragma unroll
+  for (int s = 0; s < S; ++s)
+#pragma unroll
+    for (int k = 0; k < S; ++k) {
+      const double at = q[2 * NV + s * S + k] - q[s] * q[S + k] / n;
+      const double r = (aa[s] - 2.0 * at) + tt[k];
+      res[s][k] = r > 0.0 ? r : 0.0;
+    }
+}
+template <int S>
+__device__ __forceinline__ double sasdr_energy(const double (&res)[S][S], const int* __restrict__ pk) {   // E of the permutation pk[0..S)
+  double e = 0.0;
+#pragma unroll
+  for (int s = 0; s < S; ++s) e += res[s][pk[s]];
+  return e;
+}
+// the first minimiser of E_p (the denominator does not depend on p) -> its index; E of it in `best`
+template <int S>
+__device__ __forceinline__ int sasdr_walk(const double (&res)[S][S], double& best) {
+  constexpr int NPERM = (S == 1) ? 1 : (S == 2 ? 2 : 6);
+  int arg = 0;
+  best = 0.0;
+  for (int p = 0; p < NPERM; ++p) {
+    double e = 0.0;
+#pragma unroll
+    for (int s = 0; s < S; ++s) e += res[s][pit_perm_at<S>(p, s)];
+    if (p == 0 || e < best) { best = e; arg = p; }
+  }
+  return arg;
+}
+__device__ __forceinline__ double sasdr_db(double E, double D, double tau, double eps) {
+  return 10.0 * log10((E + tau * D + eps) / (D + eps));
+}
+// d loss / d (e~_s - t~_p(s)) = sasdr_coef * (e~_s - t~_p(s)); the same number for every source of the utterance, no clamp branch
+__device__ __forceinline__ double sasdr_coef(double E, double D, double tau, double eps) {
+  return (20.0 / log(10.0)) / (E + tau * D + eps);
+}
+
+template <int S>
+__global__ __launch_bounds__(64) void sasdr_finalize_kernel(const double* __restrict__ part, int T, int nchunk, double eps, double tau,
+                                                           float* __restrict__ loss, int* __restrict__ perm) {
+  constexpr int NQ = pit_nq(S);
+  const int b = blockIdx.x;
+  __shared__ double q[NQ];
+  if (threadIdx.x < NQ) {
+    double s = 0.0;
+    for (int c = 0; c < nchunk; ++c) s += part[((long long)b * nchunk + c) * NQ + threadIdx.x];
+    q[threadIdx.x] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double res[S][S], D, E;
+  sasdr_pairs<S>(q, (double)T, res, D);
+  const int arg = sasdr_walk<S>(res, E);
+  loss[b] = (float)sasdr_db(E, D, tau, eps);
+  if (perm) {
+#pragma unroll
+    for (int s = 0; s < S; ++s) perm[b * S + s] = pit_perm_at<S>(arg, s);
+  }
+}
 }  // namespace
 
 struct PitWs {   // the chunks' fp64 partial moments; the backward adds four coefficients per (b, s)
@@ -190,6 +277,33 @@ extern "C" int sepr_pit_sisnr_fwd(const float* est, const float* tgt, const floa
   return SEPR_OK;
 }
 
+extern "C" int sepr_pit_sasdr_fwd(const float* est, const float* tgt, int S, int B, int T, double eps, double snr_max, float* loss,
+                                  int* perm, void* ws, size_t ws_bytes, sepr_stream_t stream) {
+  using namespace sepr;
+  if (!est || !tgt || !loss || S < 1 || S > PIT_SMAX || B <= 0 || T <= 0 || B > 65535) return SEPR_EINVAL;
+  Arena ar(ws, ws_bytes);
+  double* part = PitWs(ar, S, B, T, false).part;
+  if (!ar.ok_need()) return SEPR_EWORKSPACE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int nchunk = (T + PIT_CHUNK - 1) / PIT_CHUNK;
+  const double tau = pow(10.0, -snr_max / 10.0);
+#define SEPR_SASDR_CASE(SS)                                                                                                         \
+  case SS:                                                                                                                          \
+    hipLaunchKernelGGL((pit_partial_kernel<SS>), dim3(nchunk, B), dim3(PIT_TPB), 0, st, est, tgt, (const float*)nullptr, B, T,     \
+                       nchunk, part);                                                                                               \
+    hipLaunchKernelGGL((sasdr_finalize_kernel<SS>), dim3(B), dim3(64), 0, st, part, T, nchunk, eps, tau, loss, perm);              \
+    break;
+  switch (S) {
+    SEPR_SASDR_CASE(1)
+    SEPR_SASDR_CASE(2)
+    SEPR_SASDR_CASE(3)
+    default: return SEPR_EINVAL;
+  }
+#undef SEPR_SASDR_CASE
+  SEPR_CHECK_LAUNCH("pit_sasdr kernels");
+  return SEPR_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // PIT_SISNR_mag (criterions.py:117-176): the same permutation walk on STFT magnitudes
 //   loss(est_s, tgt_k) = -20 log10(eps + |M_k'| / (|M_s - M_k'| + eps)),  M = sqrt(re^2 + im^2 + 1e-10) of the conv-STFT
@@ -206,7 +320,7 @@ namespace {
 
 template <int S>
 __global__ __launch_bounds__(64) void mag_scales_kernel(const double* __restrict__ part, int T, int nchunk, double eps,
-                                                       float* __restrict__ means, float* __restrict__ scales, int B) {
+                                                       float* __restrict__ means, float* __restrict__ scales, int B, int unit /* 1: every scale is 1 (the aggregated form) */) {
   constexpr int NV = 2 * S + 1, NQ = pit_nq(S);
   const int b = blockIdx.x;
   __shared__ double q[NQ];
@@ -228,7 +342,7 @@ __global__ __launch_bounds__(64) void mag_scales_kernel(const double* __restrict
       double tt = q[NV + S + k] - q[S + k] * q[S + k] / n;
       tt = tt > 0.0 ? tt : 0.0;                        // cancellation on a DC-only target (see pit_finalize_kernel)
       const double sc = et / (tt + eps);
-      scales[(b * S + s) * S + k] = (float)(sc < 1e-2 ? 1e-2 : sc);             // torch.clamp(scale, min=1e-2)
+      scales[(b * S + s) * S + k] = unit ? 1.f : (float)(sc < 1e-2 ? 1e-2 : sc);   // torch.clamp(scale, min=1e-2)
     }
 }
 
@@ -306,6 +420,34 @@ __global__ __launch_bounds__(64) void mag_finalize_kernel(const double* __restri
   }
 }
 
+// the aggregated form over the pair sums of unit scales: sums[(b, s, k)] = (sum M_k^2, sum (M_s - M_k)^2); D reads the s = 0 row
+template <int S>
+__device__ __forceinline__ void sasdr_mag_pairs(const double* __restrict__ sums, int b, double (&res)[S][S], double& D) {
+  D = 0.0;
+#pragma unroll
+  for (int s = 0; s < S; ++s)
+#pragma unroll
+    for (int k = 0; k < S; ++k) {
+      const double* o = sums + ((long long)(b * S + s) * S + k) * 2;
+      res[s][k] = o[1];
+      if (s == 0) D += o[0];
+    }
+}
+template <int S>
+__global__ __launch_bounds__(64) void sasdr_mag_finalize_kernel(const double* __restrict__ sums, int B, double eps, double tau,
+                                                               float* __restrict__ loss, int* __restrict__ perm) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= B) return;
+  double res[S][S], D, E;
+  sasdr_mag_pairs<S>(sums, b, res, D);
+  const int arg = sasdr_walk<S>(res, E);
+  loss[b] = (float)sasdr_db(E, D, tau, eps);
+  if (perm) {
+#pragma unroll
+    for (int s = 0; s < S; ++s) perm[b * S + s] = pit_perm_at<S>(arg, s);
+  }
+}
+
 // geometry and workspace of the magnitude loss, carved from `a` (sized by the same code on Arena::sizing())
 struct MagPlan {
   int nchunk, NF, Tpad, nfr, ldc;
@@ -342,10 +484,11 @@ extern "C" size_t sepr_pit_sisnr_mag_workspace(int S, int B, int T, int frame_le
   return sepr::pit_mag_workspace_bytes(S, B, T, frame_len, frame_shift);
 }
 
-extern "C" int sepr_pit_sisnr_mag_fwd(const float* est, const float* tgt, int S, int B, int T, const float* dft, int frame_len,
-                                      int frame_shift, double eps, float* loss, int* perm, void* ws, size_t ws_bytes,
-                                      sepr_stream_t stream) {
-  using namespace sepr;
+namespace sepr {
+namespace {
+// both magnitude criteria: `agg` = 0 the per-pair SI-SNR form, 1 the aggregated form (unit scales, sasdr_mag_finalize_kernel with `tau`)
+int mag_fwd(const float* est, const float* tgt, int S, int B, int T, const float* dft, int frame_len, int frame_shift, double eps, int agg,
+            double tau, float* loss, int* perm, void* ws, size_t ws_bytes, sepr_stream_t stream) {
   if (!est || !tgt || !dft || !loss || S < 1 || S > PIT_SMAX || B <= 0 || T <= 0 || B > 65535) return SEPR_EINVAL;
   if (frame_len <= 0 || frame_len % 32 != 0 || frame_shift <= 0 || frame_shift % 4 != 0) return SEPR_EINVAL;
   Arena ar(ws, ws_bytes);
@@ -361,7 +504,7 @@ extern "C" int sepr_pit_sisnr_mag_fwd(const float* est, const float* tgt, int S,
   case SS:                                                                                                                   \
     hipLaunchKernelGGL((pit_partial_kernel<SS>), dim3(p.nchunk, B), dim3(PIT_TPB), 0, st, est, tgt, (const float*)nullptr,  \
                        B, T, p.nchunk, part);                                                                                \
-    hipLaunchKernelGGL((mag_scales_kernel<SS>), dim3(B), dim3(64), 0, st, part, T, p.nchunk, eps, means, scales, B);        \
+    hipLaunchKernelGGL((mag_scales_kernel<SS>), dim3(B), dim3(64), 0, st, part, T, p.nchunk, eps, means, scales, B, agg);   \
     break;
   switch (S) {
     SEPR_MAG_CASE(1)
@@ -386,7 +529,10 @@ extern "C" int sepr_pit_sisnr_mag_fwd(const float* est, const float* tgt, int S,
 #define SEPR_MAG_CASE2(SS)                                                                                                   \
   case SS:                                                                                                                   \
     hipLaunchKernelGGL((stft_pair_kernel<SS>), dim3(B, SS * SS), dim3(256), 0, st, C, p.ldc, B, p.nfr, nbin, scales, sums); \
-    hipLaunchKernelGGL((mag_finalize_kernel<SS>), dim3((B + 63) / 64), dim3(64), 0, st, sums, B, eps, loss, perm);          \
+    if (agg)                                                                                                                 \
+      hipLaunchKernelGGL((sasdr_mag_finalize_kernel<SS>), dim3((B + 63) / 64), dim3(64), 0, st, sums, B, eps, tau, loss, perm); \
+    else                                                                                                                     \
+      hipLaunchKernelGGL((mag_finalize_kernel<SS>), dim3((B + 63) / 64), dim3(64), 0, st, sums, B, eps, loss, perm);        \
     break;
   switch (S) {
     SEPR_MAG_CASE2(1)
@@ -397,6 +543,20 @@ extern "C" int sepr_pit_sisnr_mag_fwd(const float* est, const float* tgt, int S,
 #undef SEPR_MAG_CASE2
   SEPR_CHECK_LAUNCH("pit mag: pair sums");
   return SEPR_OK;
+}
+}  // namespace
+}  // namespace sepr
+
+extern "C" int sepr_pit_sisnr_mag_fwd(const float* est, const float* tgt, int S, int B, int T, const float* dft, int frame_len,
+                                      int frame_shift, double eps, float* loss, int* perm, void* ws, size_t ws_bytes,
+                                      sepr_stream_t stream) {
+  return sepr::mag_fwd(est, tgt, S, B, T, dft, frame_len, frame_shift, eps, 0, 0.0, loss, perm, ws, ws_bytes, stream);
+}
+extern "C" int sepr_pit_sasdr_mag_fwd(const float* est, const float* tgt, int S, int B, int T, const float* dft, int frame_len,
+                                      int frame_shift, double eps, double snr_max, float* loss, int* perm, void* ws, size_t ws_bytes,
+                                      sepr_stream_t stream) {
+  return sepr::mag_fwd(est, tgt, S, B, T, dft, frame_len, frame_shift, eps, 1, pow(10.0, -snr_max / 10.0), loss, perm, ws, ws_bytes,
+                       stream);
 }
 
 // =====================================================================================================================
@@ -449,6 +609,36 @@ __global__ __launch_bounds__(64) void pit_bwd_coef_kernel(const double* __restri
   float* o = coef + ((long long)b * S + s) * 4;
   o[0] = (float)ca; o[1] = (float)ct; o[2] = (float)(q[s] / n); o[3] = (float)(q[S + k] / n);
 }
+// the aggregated form's record: ca = k, ct = -k with k = sasdr_coef * gl[b], the two means.  A pair whose energy is exactly 0 in the moments
+// (bit-equal signals, two silent rows) gets ca = ct = 0: its gradient is exactly 0, which k a~ - k t~ rounded twice in float32 is not.
+template <int S>
+__global__ __launch_bounds__(64) void sasdr_bwd_coef_kernel(const double* __restrict__ part, const int* __restrict__ perm,
+                                                           const float* __restrict__ gl, int T, int nchunk, double eps, double tau,
+                                                           float* __restrict__ coef /*[B][S][4]: ca, ct, mean_a, mean_t*/) {
+  constexpr int NQ = pit_nq(S);
+  const int b = blockIdx.x;
+  __shared__ double q[NQ];
+  if (threadIdx.x < NQ) {
+    double s = 0.0;
+    for (int c = 0; c < nchunk; ++c) s += part[((long long)b * nchunk + c) * NQ + threadIdx.x];
+    q[threadIdx.x] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x >= S) return;
+  const int s = threadIdx.x;
+  int pk[S];
+#pragma unroll
+  for (int i = 0; i < S; ++i) {
+    const int k = perm[b * S + i];
+    pk[i] = k < 0 ? 0 : (k >= S ? S - 1 : k);               // res[][] is indexed by it
+  }
+  const double n = (double)T;
+  double res[S][S], D;
+  sasdr_pairs<S>(q, n, res, D);
+  const double k = res[s][pk[s]] > 0.0 ? sasdr_coef(sasdr_energy<S>(res, pk), D, tau, eps) * (double)gl[b] : 0.0;
+  float* o = coef + ((long long)b * S + s) * 4;
+  o[0] = (float)k; o[1] = (float)-k; o[2] = (float)(q[s] / n); o[3] = (float)(q[S + pk[s]] / n);
+}
 __global__ __launch_bounds__(256) void pit_bwd_apply_kernel(const float* __restrict__ est, const float* __restrict__ tgt,
                                                            const int* __restrict__ perm, const float* __restrict__ coef, int S, int B, int T,
                                                            float* __restrict__ dest) {
@@ -464,9 +654,11 @@ __global__ __launch_bounds__(256) void pit_bwd_apply_kernel(const float* __restr
 }  // namespace
 }  // namespace sepr
 
-extern "C" int sepr_pit_sisnr_bwd(const float* est, const float* tgt, const int* perm, const float* gl, int S, int B, int T, double eps,
-                                  double clamp_min, float* dest, void* ws, size_t ws_bytes, sepr_stream_t stream) {
-  using namespace sepr;
+namespace sepr {
+namespace {
+// both time criteria: `agg` = 0 the per-pair SI-SNR coefficients (lim = clamp_min), 1 the aggregated form's (lim = tau)
+int pit_bwd(const float* est, const float* tgt, const int* perm, const float* gl, int S, int B, int T, double eps, int agg, double lim,
+            float* dest, void* ws, size_t ws_bytes, sepr_stream_t stream) {
   if (!est || !tgt || !perm || !gl || !dest || S < 1 || S > PIT_SMAX || B <= 0 || T <= 0 || B > 65535) return SEPR_EINVAL;
   const int nchunk = (T + PIT_CHUNK - 1) / PIT_CHUNK;
   Arena ar(ws, ws_bytes);
@@ -479,7 +671,10 @@ extern "C" int sepr_pit_sisnr_bwd(const float* est, const float* tgt, const int*
   case SS:                                                                                                                        \
     hipLaunchKernelGGL((pit_partial_kernel<SS>), dim3(nchunk, B), dim3(PIT_TPB), 0, st, est, tgt, (const float*)nullptr, B, T,   \
                        nchunk, part);                                                                                             \
-    hipLaunchKernelGGL((pit_bwd_coef_kernel<SS>), dim3(B), dim3(64), 0, st, part, perm, gl, T, nchunk, eps, clamp_min, coef);    \
+    if (agg)                                                                                                                      \
+      hipLaunchKernelGGL((sasdr_bwd_coef_kernel<SS>), dim3(B), dim3(64), 0, st, part, perm, gl, T, nchunk, eps, lim, coef);       \
+    else                                                                                                                          \
+      hipLaunchKernelGGL((pit_bwd_coef_kernel<SS>), dim3(B), dim3(64), 0, st, part, perm, gl, T, nchunk, eps, lim, coef);         \
     break;
   switch (S) {
     SEPR_PITB(1)
@@ -492,6 +687,17 @@ extern "C" int sepr_pit_sisnr_bwd(const float* est, const float* tgt, const int*
   hipLaunchKernelGGL(pit_bwd_apply_kernel, dim3(gx, S * B), dim3(256), 0, st, est, tgt, perm, coef, S, B, T, dest);
   SEPR_CHECK_LAUNCH("pit_sisnr_bwd kernels");
   return SEPR_OK;
+}
+}  // namespace
+}  // namespace sepr
+
+extern "C" int sepr_pit_sisnr_bwd(const float* est, const float* tgt, const int* perm, const float* gl, int S, int B, int T, double eps,
+                                  double clamp_min, float* dest, void* ws, size_t ws_bytes, sepr_stream_t stream) {
+  return sepr::pit_bwd(est, tgt, perm, gl, S, B, T, eps, 0, clamp_min, dest, ws, ws_bytes, stream);
+}
+extern "C" int sepr_pit_sasdr_bwd(const float* est, const float* tgt, const int* perm, const float* gl, int S, int B, int T, double eps,
+                                  double snr_max, float* dest, void* ws, size_t ws_bytes, sepr_stream_t stream) {
+  return sepr::pit_bwd(est, tgt, perm, gl, S, B, T, eps, 1, pow(10.0, -snr_max / 10.0), dest, ws, ws_bytes, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -525,22 +731,37 @@ MagBwdPlan mag_bwd_plan(Arena& a, int S, int B, int T, int N, int hop) {
 
 // block = (b, s): pass 1 sums are already in `sums` (P^2, R^2 for every (b, s, k)); this kernel writes dC for the
 // estimate s of utterance b against its permuted target and reduces dL/dc
-template <int S>
+// AGG: the aggregated form (unit scales in `scales`, `tau` its threshold): dL/dM_e = sasdr_coef gl[b] (M_e - M_s), nothing flows to the scale
+template <int S, bool AGG>
 __global__ __launch_bounds__(256) void stft_pair_bwd_kernel(const float* __restrict__ C, int ldc, int B, int nfr, int nbin,
                                                            const float* __restrict__ scales, const double* __restrict__ sums,
-                                                           const int* __restrict__ perm, const float* __restrict__ gl, double eps,
+                                                           const int* __restrict__ perm, const float* __restrict__ gl, double eps, double tau,
                                                            float* __restrict__ dC, int ldd, double* __restrict__ dLdc) {
   const int b = blockIdx.x, s = blockIdx.y;
   const int k = perm[b * S + s];
   const float sc = scales[(b * S + s) * S + k];
-  const double* o = sums + ((long long)(b * S + s) * S + k) * 2;
-  const double P = sqrt(o[0]), R = sqrt(o[1]);
-  const double u = P / (R + eps);
-  const double gu = -(20.0 / log(10.0)) / (eps + u) * (double)gl[b];
-  const double kR = (R > 0.0) ? P / ((R + eps) * (R + eps) * R) : 0.0;
-  const float ge = (float)(-gu * kR);                       // dL/dM_e = ge (M_e - M_s)
-  const float gs1 = (float)(P > 0.0 ? gu / (P * (R + eps)) : 0.0);   // dL/dM_s = gs1 M_s + gs2 (M_e - M_s)
-  const float gs2 = (float)(gu * kR);
+  float ge, gs1, gs2;                                       // dL/dM_e = ge (M_e - M_s);  dL/dM_s = gs1 M_s + gs2 (M_e - M_s)
+  if (AGG) {
+    int pk[S];
+#pragma unroll
+    for (int i = 0; i < S; ++i) {
+      const int ki = perm[b * S + i];
+      pk[i] = ki < 0 ? 0 : (ki >= S ? S - 1 : ki);
+    }
+    double res[S][S], D;
+    sasdr_mag_pairs<S>(sums, b, res, D);
+    ge = (float)(sasdr_coef(sasdr_energy<S>(res, pk), D, tau, eps) * (double)gl[b]);
+    gs1 = gs2 = 0.f;
+  } else {
+    const double* o = sums + ((long long)(b * S + s) * S + k) * 2;
+    const double P = sqrt(o[0]), R = sqrt(o[1]);
+    const double u = P / (R + eps);
+    const double gu = -(20.0 / log(10.0)) / (eps + u) * (double)gl[b];
+    const double kR = (R > 0.0) ? P / ((R + eps) * (R + eps) * R) : 0.0;
+    ge = (float)(-gu * kR);
+    gs1 = (float)(P > 0.0 ? gu / (P * (R + eps)) : 0.0);
+    gs2 = (float)(gu * kR);
+  }
   const float* Ce = C + (long long)(s * B + b) * nfr * ldc;
   const float* Ct = C + (long long)((S + k) * B + b) * nfr * ldc;
   float* De = dC + (long long)(s * B + b) * nfr * ldd;
@@ -552,7 +773,8 @@ __global__ __launch_bounds__(256) void stft_pair_bwd_kernel(const float* __restr
     const float tr = Ct[(long long)f * ldc + w], ti = Ct[(long long)f * ldc + nbin + w];
     const float me = sqrtf(er * er + ei * ei + 1.0e-10f);
     const float t2 = tr * tr + ti * ti;
-    const float ms = sqrtf(sc * sc * t2 + 1.0e-10f);
+    // AGG: the expression of `me`, so that a bit-equal pair gives d = 0 and a gradient that is exactly 0
+    const float ms = AGG ? sqrtf(tr * tr + ti * ti + 1.0e-10f) : sqrtf(sc * sc * t2 + 1.0e-10f);
     const float d = me - ms;
     const float gme = ge * d;
     De[(long long)f * ldd + w] = gme * er / me;
@@ -634,10 +856,11 @@ extern "C" size_t sepr_pit_sisnr_mag_bwd_workspace(int S, int B, int T, int fram
   return a.need();
 }
 
-extern "C" int sepr_pit_sisnr_mag_bwd(const float* est, const float* tgt, const int* perm, const float* gl, int S, int B, int T,
-                                      const float* dft, const float* dft_t, int frame_len, int frame_shift, double eps, float* dest,
-                                      void* ws, size_t ws_bytes, sepr_stream_t stream) {
-  using namespace sepr;
+namespace sepr {
+namespace {
+// both magnitude criteria (`agg`, `tau` as in mag_fwd)
+int mag_bwd(const float* est, const float* tgt, const int* perm, const float* gl, int S, int B, int T, const float* dft, const float* dft_t,
+            int frame_len, int frame_shift, double eps, int agg, double tau, float* dest, void* ws, size_t ws_bytes, sepr_stream_t stream) {
   if (!est || !tgt || !perm || !gl || !dft || !dft_t || !dest || S < 1 || S > PIT_SMAX || B <= 0 || T <= 0 || B > 65535) return SEPR_EINVAL;
   if (frame_len <= 0 || frame_len % 32 != 0 || frame_shift <= 0 || frame_shift % 4 != 0) return SEPR_EINVAL;
   Arena ar(ws, ws_bytes);
@@ -654,7 +877,7 @@ extern "C" int sepr_pit_sisnr_mag_bwd(const float* est, const float* tgt, const 
   case SS:                                                                                                                          \
     hipLaunchKernelGGL((pit_partial_kernel<SS>), dim3(p.nchunk, B), dim3(PIT_TPB), 0, st, est, tgt, (const float*)nullptr, B, T,    \
                        p.nchunk, part);                                                                                             \
-    hipLaunchKernelGGL((mag_scales_kernel<SS>), dim3(B), dim3(64), 0, st, part, T, p.nchunk, eps, means, scales, B);               \
+    hipLaunchKernelGGL((mag_scales_kernel<SS>), dim3(B), dim3(64), 0, st, part, T, p.nchunk, eps, means, scales, B, agg);          \
     break;
   switch (S) {
     SEPR_MAGB1(1)
@@ -679,8 +902,12 @@ extern "C" int sepr_pit_sisnr_mag_bwd(const float* est, const float* tgt, const 
 #define SEPR_MAGB2(SS)                                                                                                              \
   case SS:                                                                                                                          \
     hipLaunchKernelGGL((stft_pair_kernel<SS>), dim3(B, SS * SS), dim3(256), 0, st, C, p.ldc, B, p.nfr, nbin, scales, sums);        \
-    hipLaunchKernelGGL((stft_pair_bwd_kernel<SS>), dim3(B, SS), dim3(256), 0, st, C, p.ldc, B, p.nfr, nbin, scales, sums, perm, gl, \
-                       eps, dC, bp.ldd, dLdc);                                                                                              \
+    if (agg)                                                                                                                        \
+      hipLaunchKernelGGL((stft_pair_bwd_kernel<SS, true>), dim3(B, SS), dim3(256), 0, st, C, p.ldc, B, p.nfr, nbin, scales, sums, perm, \
+                         gl, eps, tau, dC, bp.ldd, dLdc);                                                                           \
+    else                                                                                                                            \
+      hipLaunchKernelGGL((stft_pair_bwd_kernel<SS, false>), dim3(B, SS), dim3(256), 0, st, C, p.ldc, B, p.nfr, nbin, scales, sums, perm, \
+                         gl, eps, tau, dC, bp.ldd, dLdc);                                                                           \
     break;
   switch (S) {
     SEPR_MAGB2(1)
@@ -714,4 +941,19 @@ extern "C" int sepr_pit_sisnr_mag_bwd(const float* est, const float* tgt, const 
   hipLaunchKernelGGL(demean_kernel, dim3(S * B), dim3(256), 0, st, da, p.Tpad, T, dest);
   SEPR_CHECK_LAUNCH("pit mag bwd: adjoint");
   return SEPR_OK;
+}
+}  // namespace
+}  // namespace sepr
+
+extern "C" int sepr_pit_sisnr_mag_bwd(const float* est, const float* tgt, const int* perm, const float* gl, int S, int B, int T,
+                                      const float* dft, const float* dft_t, int frame_len, int frame_shift, double eps, float* dest,
+                                      void* ws, size_t ws_bytes, sepr_stream_t stream) {
+  return sepr::mag_bwd(est, tgt, perm, gl, S, B, T, dft, dft_t, frame_len, frame_shift, eps, 0, 0.0, dest, ws, ws_bytes, stream);
+}
+// the scale path of stft_ola_kernel reads dL/dc = 0 (gs1 = gs2 = 0 above) and adds exactly 0
+extern "C" int sepr_pit_sasdr_mag_bwd(const float* est, const float* tgt, const int* perm, const float* gl, int S, int B, int T,
+                                      const float* dft, const float* dft_t, int frame_len, int frame_shift, double eps, double snr_max,
+                                      float* dest, void* ws, size_t ws_bytes, sepr_stream_t stream) {
+  return sepr::mag_bwd(est, tgt, perm, gl, S, B, T, dft, dft_t, frame_len, frame_shift, eps, 1, pow(10.0, -snr_max / 10.0), dest, ws,
+                       ws_bytes, stream);
 }

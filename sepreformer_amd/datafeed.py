@@ -32,7 +32,9 @@ the PERTURBED utterance under the response - the talker speaks faster or slower,
 
 Turn-taking: the three planners take ``turns=Turns(overlap=(lo, hi), ramp=RL)`` - alone or with any of the above - and give
 every source a turn ``[on, off)`` of the example, so that the talkers overlap for a drawn fraction of their turns instead of the whole crop; the gate
-acts on the talker inside the launch (``sepr_dynmix_turns_fwd``), before the room, which therefore rings on after the talker stops.
+acts on the talker inside the launch (``sepr_dynmix_turns_fwd``), before the room, which therefore rings on after the talker stops.  With
+``absent=P`` beside ``turns`` one talker of an example, with probability P, is silent throughout - the empty turn, a ``+0.0`` target row - which the
+trainer's ``criterion="sasdr"`` can score.
 
 Shuffling: the reference shuffles through ``DataLoader(shuffle=True)`` (torch's generator); this feed takes the epoch's key order
 from the caller (``keys=``), and by default draws a permutation from its own ``random.Random`` before every epoch.
@@ -385,27 +387,54 @@ def turn_ramp(RL: int) -> np.ndarray:
     return (0.5 - 0.5 * np.cos(np.pi * (i + 0.5) / max(RL, 1))).astype(np.float32)
 
 
-def _draw_turns(rng: random.Random, turns: Optional[Turns], S: int, n: int) -> Optional[List[Tuple[int, int]]]:
+def _check_absent(absent: float, turns: Optional[Turns]) -> float:
+    if isinstance(absent, bool) or not isinstance(absent, (int, float)) or not (0.0 <= float(absent) <= 1.0):
+        raise ValueError(f"absent = {absent!r}, expected a probability in [0, 1]")
+    if float(absent) > 0.0 and turns is None:
+        raise ValueError("absent > 0 silences a talker by giving it the empty turn: it needs turns=Turns(...)")
+    return float(absent)
+
+
+def _lay_turns(order: Sequence[int], rho: float, n: int, out: List[Tuple[int, int]]) -> None:
+    """The talkers of ``order`` laid over ``[0, n)`` with overlap ``rho`` (the rule of ``_draw_turns``); one talker alone gets the open turn."""
+    k = len(order)
+    if k == 1:
+        out[order[0]] = (-TURN_FAR, TURN_FAR)
+        return
+    d = min(n, math.ceil(n / (k - (k - 1) * rho)))
+    h = (n - d) // (k - 1)
+    for s, who in enumerate(order):
+        on, off = s * h, s * h + d
+        out[who] = (-TURN_FAR if on <= 0 else on, TURN_FAR if off >= n or s == k - 1 else off)
+
+
+def _draw_turns(rng: random.Random, turns: Optional[Turns], S: int, n: int, absent: float = 0.0) -> Optional[List[Tuple[int, int]]]:
     """The sources' turns of an example of ``n`` samples, in source order; no draw without ``turns``.  Two draws, after every other draw of the
     example: ``rho = rng.uniform(lo, hi)``, then the order of the talkers, ``rng.sample(range(S), S)``.  Every turn is
     ``d = min(n, ceil(n / (S - (S - 1) rho)))`` samples long and the s-th talker's begins at ``s h``, ``h = (n - d) // (S - 1)``: together they
     cover ``[0, n)``, neighbours overlap by ``d - h``, every source is active for at least ``n / S`` samples.  A turn that begins at or before
     sample 0 began before the window (``on = -TURN_FAR``: no fade-in, the history kept), one that reaches ``n`` - and the last talker's - goes on
-    after it (``off = TURN_FAR``)."""
+    after it (``off = TURN_FAR``).  ``absent > 0``: two more draws after those two, ``rng.random() < absent`` and
+    ``who = rng.randrange(S)`` - both made whatever the first says, so an example consumes the generator alike either way; when the first
+    holds, talker ``who`` is silent throughout (the empty turn ``(TURN_FAR, TURN_FAR)``) and the other ``S - 1``, in their drawn order and with
+    the same ``rho``, are laid over ``[0, n)`` by the same rule.  ``absent = 0`` draws nothing more."""
+    absent = _check_absent(absent, turns)
     if turns is None:
         return None
     _check_turns(turns)
     rho = rng.uniform(float(turns.overlap[0]), float(turns.overlap[1]))
     order = rng.sample(range(S), S)
-    d = min(n, math.ceil(n / (S - (S - 1) * rho)))
-    h = (n - d) // (S - 1)
     out: List[Tuple[int, int]] = [(0, 0)] * S
-    for s, who in enumerate(order):
-        on, off = s * h, s * h + d
-        out[who] = (-TURN_FAR if on <= 0 else on, TURN_FAR if off >= n or s == S - 1 else off)
+    if absent > 0.0:
+        gone, who = rng.random() < absent, rng.randrange(S)
+        if gone:
+            out[who] = _EMPTY
+            order = [w for w in order if w != who]
+    _lay_turns(order, rho, n, out)
     return out
 
 
+_EMPTY = (TURN_FAR, TURN_FAR)                          # the turn of a talker who is silent throughout: on = off, nothing lies inside it
 _OPEN = (-TURN_FAR, TURN_FAR)                          # the turn of a term that is not gated inside a plan with turns (the noise)
 _NO_RIR = (-1, 1)                                      # a term that is not reverberated inside a plan with RIRs (the noise)
 
@@ -425,7 +454,7 @@ def _terms(utts, starts, norms, gains, sp, rv=None, tn=None) -> Tuple[Term, ...]
 def plan_wsj0(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs: Sequence[str] = ("s1", "s2"),
               accept: Callable[[str, str], bool] = wsj0_distinct_speakers, crop: bool = True,
               speeds: Optional[Sequence[int]] = None, rirs: Optional[RirBank] = None, target: Union[str, int] = "direct",
-              speed_reverb: bool = False, turns: Optional[Turns] = None) -> Example:
+              speed_reverb: bool = False, turns: Optional[Turns] = None, absent: float = 0.0) -> Example:
     """``SepReformer_Large_DM_WSJ0/dataset.py:84-139``.  ``crop=False`` is the reference's "test" partition (no ``max_len`` crop).
     ``speeds``: directly after the draw that orders the two sources, one ``rng.choice(speeds)`` per source; the perturbed lengths
     replace the stored ones, the norm factors keep the stored utterances' RMS (section 5e-2).  ``rirs``: at that same position, one
@@ -433,7 +462,9 @@ def plan_wsj0(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs: 
     (``_target_rv``); lengths and norm factors stay the stored utterances' (section 5e-3).  Both take ``speed_reverb=True``: the speeds are
     drawn first, then the responses; every later draw uses the perturbed lengths; a source term is the perturbed utterance under the
     whole response and its target the same speed under what ``target`` says (section 5e-5).  ``turns``: after every other draw of the example,
-    the two draws of ``_draw_turns``; each source's mixture term and its target carry the source's turn (section 5e-6)."""
+    the two draws of ``_draw_turns``; each source's mixture term and its target carry the source's turn (section 5e-6).  ``absent``: the
+    probability that one talker, drawn by ``_draw_turns`` after those, is silent throughout - its target and its mixture term carry the empty
+    turn (section 5e-7); it needs ``turns``."""
     keys = corpus.roles[srcs[0]]
     while True:
         key_random = rng.choice(keys)
@@ -453,7 +484,7 @@ def plan_wsj0(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs: 
     if crop and n > max_len:
         st = rng.randint(0, n - max_len)
         starts, n = [s + st for s in starts], max_len
-    tn = _draw_turns(rng, turns, 2, n)
+    tn = _draw_turns(rng, turns, 2, n, absent)
     if rv is not None:
         return Example(key, n, _terms(utts, starts, norms, gains, sp, _mix_rv(rirs, rv), tn),
                        _terms(utts, starts, norms, gains, sp, _target_rv(rirs, rv, target), tn))
@@ -463,11 +494,11 @@ def plan_wsj0(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs: 
 
 def plan_wham(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs: Sequence[str] = ("s1", "s2"), noise: str = "noise",
               speeds: Optional[Sequence[int]] = None, rirs: Optional[RirBank] = None, target: Union[str, int] = "direct",
-              speed_reverb: bool = False, turns: Optional[Turns] = None) -> Example:
+              speed_reverb: bool = False, turns: Optional[Turns] = None, absent: float = 0.0) -> Example:
     """``SepReformer_Large_DM_WHAM/dataset.py``: no speaker rule, the noise of ``key`` normalised to the first source with a gain of
     its own from U(-5, 5) dB, everything cropped to ``min(max_len, lengths)`` at independent random indices.  ``speeds``: as in
     ``plan_wsj0``; the noise is not perturbed.  ``rirs`` / ``target`` / ``speed_reverb``: as in ``plan_wsj0``; the noise is not
-    reverberated.  ``turns``: as in ``plan_wsj0``; the noise keeps the open turn."""
+    reverberated.  ``turns`` / ``absent``: as in ``plan_wsj0``; the noise keeps the open turn."""
     key_random = rng.choice(corpus.roles[srcs[0]])
     i1, i2 = (0, 1) if rng.random() > 0.5 else (1, 0)
     sp = _draw_speeds(rng, speeds, 2)
@@ -486,7 +517,7 @@ def plan_wham(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs: 
     min_len = min([max_len] + lens)
     starts = [rng.randint(0, ln - min_len) for ln in lens]
     n = min_len - min_len % 4
-    tn = _draw_turns(rng, turns, 2, n)
+    tn = _draw_turns(rng, turns, 2, n, absent)
     tm = None if tn is None else tn + [_OPEN]
     if rv is not None:
         return Example(key, n, _terms(utts, starts, norms, gains, sp, _mix_rv(rirs, rv) + [_NO_RIR], tm),
@@ -498,13 +529,13 @@ def plan_wham(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs: 
 def plan_whamr(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs: Sequence[str] = ("s1", "s2"),
                reverb: Sequence[str] = ("s1_reverb", "s2_reverb"), noise: str = "noise", speeds: Optional[Sequence[int]] = None,
                rirs: Optional[RirBank] = None, target: Union[str, int] = "direct", speed_reverb: bool = False,
-               turns: Optional[Turns] = None) -> Example:
+               turns: Optional[Turns] = None, absent: float = 0.0) -> Example:
     """``SepReformer_Large_DM_WHAMR/dataset.py:87-154``: the mixture is the two reverberant twins plus the noise (gains U(-3, 3) dB,
     noise U(-6, 3) dB), the targets are the anechoic sources with their twins' norm factor, gain and crop index.  ``speeds``: as in
     ``plan_wsj0``; a dry source and its reverberant twin share one speed, the noise is not perturbed.  ``rirs`` / ``target``: as in
     ``plan_wsj0``; the mixture is then the DRY sources reverberated in the launch plus the noise, and the ``reverb`` roles are never
     looked up - a corpus without pre-rendered twins serves.  ``speed_reverb=True`` with both: the dry sources perturbed and then
-    reverberated in the launch (playing a pre-rendered twin faster, the other order, is ``speeds=`` alone).  ``turns``: as in ``plan_wsj0``; the noise
+    reverberated in the launch (playing a pre-rendered twin faster, the other order, is ``speeds=`` alone).  ``turns`` / ``absent``: as in ``plan_wsj0``; the noise
     keeps the open turn.  With ``rirs`` the room rings on after a talker stops; without, a pre-rendered twin is gated as recorded, tail and all."""
     key_random = rng.choice(corpus.roles[srcs[0]])
     i1, i2 = (0, 1) if rng.random() > 0.5 else (1, 0)
@@ -525,7 +556,7 @@ def plan_whamr(corpus: Corpus, rng: random.Random, key: str, max_len: int, srcs:
     starts = [rng.randint(0, ln - min_len) for ln in lens]
     nstart = rng.randint(0, int(corpus.lengths[un]) - min_len)
     n = min_len - min_len % 4
-    tn = _draw_turns(rng, turns, 2, n)
+    tn = _draw_turns(rng, turns, 2, n, absent)
     tm = None if tn is None else tn + [_OPEN]
     if rv is not None:
         return Example(key, n, _terms(dry + [un], starts + [nstart], norms + [nnorm], gains + [ngain], None if sp is None else sp + [100],
@@ -792,7 +823,7 @@ class DynamicMixFeed:
     other role names, or ``speeds=range(95, 106)`` for speed perturbation, with ``functools.partial``; for reverberation bind ``rirs=bank`` and
     pass the same bank as the feed's ``rirs=``; for both bind ``speed_reverb=True`` as well - the feed reads the flag from the
     ``functools.partial`` and passes it to ``collate_plan``; a planner wrapped otherwise says it with the feed's ``speed_reverb=``; for turn-taking
-    bind ``turns=Turns(...)``, which the feed reads the same way - or takes as its own ``turns=`` - for the gate's ramp table).  Per batch: plan on the host, write the table into a pinned staging buffer, one
+    bind ``turns=Turns(...)``, which the feed reads the same way - or takes as its own ``turns=`` - for the gate's ramp table; ``absent=P`` bound beside it is kept as ``feed.absent``).  Per batch: plan on the host, write the table into a pinned staging buffer, one
     asynchronous copy into the static device table, one launch - all on the current stream, nothing waits for the device.
     ``keys``: the epoch's key order, used as given every epoch; default: the keys of the corpus's first role, permuted with the
     feed's ``random.Random(seed)`` before each epoch (the same generator then makes the examples' draws).  ``rank`` / ``world``:
@@ -838,6 +869,8 @@ class DynamicMixFeed:
         if turns is None:                               # the turns the user bound on the planner, read as speed_reverb is
             turns = (getattr(planner, "keywords", None) or {}).get("turns")
         self.turns = None if turns is None else _check_turns(turns)
+        # the probability of a silent talker the user bound on the planner (section 5e-7): what a trainer asks before it picks a criterion
+        self.absent = _check_absent((getattr(planner, "keywords", None) or {}).get("absent", 0.0), self.turns)
         self._ramp = None if self.turns is None else ramp_table(corpus.device, int(self.turns.ramp))      # once per feed and device
         self._table = None
         self._speeds: List[int] = []                    # the converter set: every speed a plan has used, in order of first use

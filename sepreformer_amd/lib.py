@@ -221,6 +221,10 @@ SIGNATURES = {
     "sepr_pit_sisnr_bwd": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _d, _d, _fp, _fp, _sz, _fp]),
     "sepr_pit_sisnr_mag_bwd_workspace": (_sz, [_i, _i, _i, _i, _i]),
     "sepr_pit_sisnr_mag_bwd": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _fp, _fp, _i, _i, _d, _fp, _fp, _sz, _fp]),
+    "sepr_pit_sasdr_fwd": (_i, [_fp, _fp, _i, _i, _i, _d, _d, _fp, _fp, _fp, _sz, _fp]),
+    "sepr_pit_sasdr_mag_fwd": (_i, [_fp, _fp, _i, _i, _i, _fp, _i, _i, _d, _d, _fp, _fp, _fp, _sz, _fp]),
+    "sepr_pit_sasdr_bwd": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _d, _d, _fp, _fp, _sz, _fp]),
+    "sepr_pit_sasdr_mag_bwd": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _fp, _fp, _i, _i, _d, _d, _fp, _fp, _sz, _fp]),
     "sepr_adamw_block_elems": (_i, []),
     "sepr_adamw_workspace": (_sz, []),
     "sepr_adamw_step": (_i, [C.POINTER(AdamWTables), _fp, _ll, _fp, _fp, _fp, _fp, _d, _d, _d, _d, _d, _fp, _fp, _sz, _fp]),

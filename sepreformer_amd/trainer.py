@@ -177,6 +177,27 @@ def mix_loss(l_time: torch.Tensor, l_mag: Sequence[torch.Tensor], w_time: torch.
     return (w_time * l_time + w_freq * (acc / len(l_mag))) / num_spks
 
 
+CRITERIA = ("sisnr", "sasdr")
+
+
+def check_criterion(criterion: str, absent: float) -> None:
+    """What ``Trainer`` refuses: an unknown criterion, and the SI-SNR criteria on a feed that makes windows with a silent talker."""
+    if criterion not in CRITERIA:
+        raise ValueError(f"criterion: one of {CRITERIA}, got {criterion!r}")
+    if criterion == "sisnr" and float(absent or 0.0) > 0.0:
+        raise ValueError(f"the training feed has absent = {absent}: on a silent target the SI-SNR criteria give the estimate a zero gradient "
+                         "(time form: alpha = 0) or one that grows like 1 / |estimate| (magnitude form); train it with criterion='sasdr'")
+
+
+def check_resume_criterion(criterion: str, run_state: Optional[dict], path: str = "the checkpoint") -> None:
+    """A checkpoint of a run with another criterion than ``"sisnr"`` records it in ``sepr_run_state`` (a missing key, or no run state at all,
+    means ``"sisnr"``); the losses of the two are different scales, so a run continues with the one it began with."""
+    was = (run_state or {}).get("criterion", "sisnr")
+    if was != criterion:
+        raise ValueError(f"{path} was trained with criterion={was!r}, this run asks for {criterion!r}: best, the plateau schedule and the "
+                         "loss curves would mix two scales - resume with the same criterion or start in a fresh directory")
+
+
 class Ledger:
     """Host view of one read of the device ledger (``lib.LEDGER_SLOTS``)."""
 
@@ -197,12 +218,15 @@ class Trainer:
                  test_epochs: Sequence[int] = (100, 120, 150, 170), warmup_steps: int = 1000, factor: float = 0.8, patience: int = 2,
                  min_lr: float = 1.0e-10, mvn: bool = False, save: str = "all", keep_last: Optional[int] = None, log_every: int = 50,
                  max_skipped: int = 10, test_utterances: Optional[Callable[[], Iterable]] = None, log: Callable[[str], None] = print,
-                 ema_decay: Optional[float] = None, ema_warmup: float = 10.0, validate_with: str = "ema"):
+                 ema_decay: Optional[float] = None, ema_warmup: float = 10.0, validate_with: str = "ema", criterion: str = "sisnr",
+                 snr_max: float = 30.0):
         """``train_feed``: a ``DynamicMixFeed`` with ``fixed_length=True``; ``valid_feed``: one over ``plan_direct`` (``drop_last=False``
         keeps the trailing partial batch, as the reference's validation loader does).  ``test_utterances``: a callable returning the
         iterable ``infer.evaluate_utterances`` takes, run at ``test_epochs``.  The other arguments are the reference's ``engine`` /
         ``optimizer`` / ``scheduler`` settings; the defaults are the values its four ``configs.yaml`` share.  ``ema_decay`` / ``ema_warmup``:
-        the weight EMA of ``FlatAdamW``; ``validate_with`` (``"raw"``, ``"ema"``, ``"both"``) is ignored while it is off."""
+        the weight EMA of ``FlatAdamW``; ``validate_with`` (``"raw"``, ``"ema"``, ``"both"``) is ignored while it is off.  ``criterion``:
+        ``"sisnr"`` (the reference's ``PIT_SISNR_time`` / ``PIT_SISNR_mag``) or ``"sasdr"`` (``PIT_SASDR_time`` / ``PIT_SASDR_mag`` with
+        ``snr_max``), for training and validation alike; a training feed with ``absent > 0`` needs ``"sasdr"``."""
         if mvn:
             raise ValueError("mvn: true is not supported (every shipped configuration has it false)")
         if not getattr(train_feed, "fixed_length", False):
@@ -212,7 +236,8 @@ class Trainer:
             raise ValueError("validate_with: 'raw', 'ema' or 'both'")
         if warmup_steps < 1 or log_every < 1:
             raise ValueError("warmup_steps >= 1 and log_every >= 1")
-        from .criterion import PIT_SISNR_mag, PIT_SISNR_time
+        check_criterion(criterion, getattr(train_feed, "absent", 0.0))
+        from .criterion import PIT_SASDR_mag, PIT_SASDR_time, PIT_SISNR_mag, PIT_SISNR_time
         from .optim import FlatAdamW
         self.model, self.train_feed, self.valid_feed, self.dir = model, train_feed, valid_feed, checkpoint_dir
         self.cfg = model.cfg
@@ -227,8 +252,13 @@ class Trainer:
         self.last_valid_raw: Optional[Tuple[float, float, int]] = None          # validate_with="both": the raw weights' result of the last epoch
         self.scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(self.opt, mode="min", factor=factor, patience=patience, min_lr=min_lr)
         S, R = self.cfg.num_spks, self.cfg.num_stages
-        self.crit_t = PIT_SISNR_time(self.dev, S, True)
-        self.crit_m = PIT_SISNR_mag(self.dev, 512, 128, "hann", R, S, True, False)
+        self.criterion, self.snr_max = criterion, float(snr_max)
+        if criterion == "sasdr":
+            self.crit_t = PIT_SASDR_time(self.dev, S, self.snr_max)
+            self.crit_m = PIT_SASDR_mag(self.dev, 512, 128, "hann", R, S, self.snr_max)
+        else:
+            self.crit_t = PIT_SISNR_time(self.dev, S, True)
+            self.crit_m = PIT_SISNR_mag(self.dev, 512, 128, "hann", R, S, True, False)
         self.nparts = 1 + R
         self.parts = torch.zeros(self.nparts, dtype=torch.float32, device=self.dev)
         self.ledger = torch.zeros(L.ledger_doubles(self.nparts), dtype=torch.float64, device=self.dev)
@@ -381,6 +411,8 @@ class Trainer:
     def run_state(self) -> dict:
         rs = {"global_step": int(self.global_step), "plateau": self.scheduler.state_dict(), "train_feed": self.train_feed.state_dict(),
               "valid_feed": self.valid_feed.state_dict(), "best": float(self.best), "seed": int(self.seed)}
+        if self.criterion != "sisnr":                     # a missing key means "sisnr": the layout of a run with the reference's criteria is unchanged
+            rs["criterion"] = self.criterion
         if self.ema:
             rs["ema"] = {"decay": float(self.opt.ema_decay), "warmup": float(self.opt.ema_warmup)}
         return rs
@@ -415,6 +447,7 @@ class Trainer:
         self.model.invalidate_packed()
         self.opt.load_state_dict(ck["optimizer_state_dict"])
         rs = ck.get(RUN_STATE_KEY)
+        check_resume_criterion(self.criterion, rs, path)
         if rs is not None:
             self.seed, self.global_step, self.best = int(rs["seed"]), int(rs["global_step"]), float(rs["best"])
             self.scheduler.load_state_dict(rs["plateau"])

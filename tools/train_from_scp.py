@@ -54,6 +54,11 @@ def main():
                     "mixing launch, before the room")
     ap.add_argument("--turn-ramp", type=int, default=80, metavar="N", help="with --turns: samples of the raised-cosine fade at either end of a turn "
                     "(0 = a hard gate; default 80)")
+    ap.add_argument("--turn-absent", type=float, default=0.0, metavar="P", help="with --turns: with probability P one talker of an example, drawn "
+                    "uniformly, is silent throughout - its target row is zero (default 0); needs --criterion sasdr")
+    ap.add_argument("--criterion", choices=["sisnr", "sasdr"], default="sisnr", help="the training and validation criteria: the reference's PIT SI-SNR "
+                    "pair (default) or the source-aggregated, soft-thresholded SDR pair, which is defined on a silent target (DESIGN.md section 5e-7)")
+    ap.add_argument("--snr-max", type=float, default=30.0, metavar="DB", help="with --criterion sasdr: the soft threshold tau = 10^(-DB / 10) (default 30)")
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--epochs", type=int, default=None, metavar="N", help="run the epoch loop instead of --steps: the reference's max_epoch "
                     "(epochs 1 .. N - 1); needs --valid-scp and --checkpoint-dir")
@@ -88,6 +93,12 @@ def main():
         ap.error("--speeds needs dynamic mixing (--form wsj0, wham or whamr)")
     if args.turns and args.form == "direct":
         ap.error("--turns needs dynamic mixing (--form wsj0, wham or whamr)")
+    if args.turn_absent and not args.turns:
+        ap.error("--turn-absent needs --turns")
+    if not 0.0 <= args.turn_absent <= 1.0:
+        ap.error("--turn-absent must lie in [0, 1]")
+    if args.turn_absent and args.criterion != "sasdr":
+        ap.error("--turn-absent needs --criterion sasdr: the SI-SNR criteria give a zero (time) or exploding (magnitude) gradient on a silent target")
     reverb = args.rir_scp or args.synthetic_rirs or args.room_rirs
     if reverb and args.form == "direct":
         ap.error("--rir-scp / --synthetic-rirs / --room-rirs need dynamic mixing (--form wsj0, wham or whamr)")
@@ -110,7 +121,7 @@ def main():
     import torch
     from sepreformer_amd import datafeed as df
     from sepreformer_amd.config import VARIANTS
-    from sepreformer_amd.criterion import PIT_SISNR_mag, PIT_SISNR_time
+    from sepreformer_amd.criterion import PIT_SASDR_mag, PIT_SASDR_time, PIT_SISNR_mag, PIT_SISNR_time
     from sepreformer_amd.model import Model
     from sepreformer_amd.optim import FlatAdamW
     from sepreformer_amd.train_step import CapturedTrainStep
@@ -136,7 +147,8 @@ def main():
         print(f"RIR bank: {len(bank)} impulse responses, {int(bank.lengths.min())} .. {int(bank.lengths.max())} samples", flush=True)
     if args.turns:
         try:
-            planner = functools.partial(planner, turns=df.parse_turns(args.turns, args.turn_ramp))
+            planner = functools.partial(planner, turns=df.parse_turns(args.turns, args.turn_ramp),
+                                        **({"absent": args.turn_absent} if args.turn_absent else {}))
         except ValueError as e:
             ap.error(f"--turns / --turn-ramp: {e}")
     feed = df.DynamicMixFeed(corpus, planner, batch=args.batch, max_len=args.max_len, seed=args.seed, fixed_length=True, rirs=bank,
@@ -147,8 +159,12 @@ def main():
     model = Model.from_config(cfg, init_seed=args.seed, precision=args.precision).to(dev).train()
     if args.epochs is not None:
         return run_epochs(args, df, model, feed, dev)
-    crit_t = PIT_SISNR_time(dev, cfg.num_spks, True)
-    crit_m = PIT_SISNR_mag(dev, 512, 128, "hann", cfg.num_stages, cfg.num_spks, True, False)
+    if args.criterion == "sasdr":
+        crit_t = PIT_SASDR_time(dev, cfg.num_spks, args.snr_max)
+        crit_m = PIT_SASDR_mag(dev, 512, 128, "hann", cfg.num_stages, cfg.num_spks, args.snr_max)
+    else:
+        crit_t = PIT_SISNR_time(dev, cfg.num_spks, True)
+        crit_m = PIT_SISNR_mag(dev, 512, 128, "hann", cfg.num_stages, cfg.num_spks, True, False)
     sizes = torch.full((args.batch,), args.max_len)                           # fixed-length rows: the padding is part of the example
     opt = FlatAdamW(model, lr=args.lr, weight_decay=1.0e-2)
 
@@ -199,7 +215,7 @@ def run_epochs(args, df, model, feed, dev):
     trainer = Trainer(model, feed, valid, args.checkpoint_dir, lr=args.lr, seed=args.seed, max_epoch=args.epochs, warmup_steps=args.warmup_steps,
                       start_scheduling=args.start_scheduling, test_epochs=args.test_epochs, save=args.save, keep_last=args.keep_last,
                       test_utterances=test, log=lambda s: print(s, flush=True), ema_decay=args.ema_decay, ema_warmup=args.ema_warmup,
-                      validate_with=args.validate_with, **({} if args.log is None else {"log_every": args.log}))
+                      validate_with=args.validate_with, criterion=args.criterion, snr_max=args.snr_max, **({} if args.log is None else {"log_every": args.log}))
     trainer.run()
 
 
