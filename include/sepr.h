@@ -692,7 +692,46 @@ int sepr_rir_ism_fwd(const double* rooms, int R, int N, double fsc, const double
  * (G, C + 1) workgroups.  The kernels clamp rows[g] into [0, S), begin[g] into [0, T] and length[g] into [0, T - begin[g]] (an empty segment gives
  * 20 log10(eps)).  Workspace: sepr_segment_sisnr_bytes(G, C) bytes (0 for G < 1 or C outside 1..8).  SEPR_EINVAL before any HIP call for a null
  * pointer, G < 1, C or S outside 1..8, T < 1, ld < T, eps outside [0, 1], est, ref or mix not 4-byte aligned, v or v_mix not 8-byte aligned;
- * SEPR_EWORKSPACE for a short workspace.  No host synchronisation or allocation (capturable). */
+ * SEPR_EWORKSPACE for a short workspace.  No host synchronisation or allocation (capturable).
+ *
+ * sepr_conversation_render_rooms: conversations in rooms (a new entry, no struct change: ABI 4.13).  A segment gains three
+ * int32 fields, seg_rir, seg_taps, seg_direct [G] (DEVICE).  rir = -1 means no response and stands for h = [1.0], taps = direct = 1; rir = r >= 0
+ * names response h_r of the bank of sepr_dynmix_reverb_fwd (rir [rir_total] float32, rir_off [NR + 1] int64, DEVICE), with
+ * 1 <= direct <= taps <= len_r <= 16384.  With x the utterance's float32 sample value (an int16 sample is s / 32768), for a segment g:
+ *   x_g[d]   = x[seg_start + d] for 0 <= d < seg_len, +0 for every other integer d: zero outside the SEGMENT, not outside the utterance - a cut
+ *              utterance does not ring with samples that were never played;
+ *   z_g^K[t] = float32(sum_{j = 0 .. K - 1} double(h[j]) * double(x_g[t - seg_place - j])), the products exact in float64, added as fma(h, x, acc) in
+ *              the order j = 0 .. K - 1 from acc = 0.0, one rounding: the arithmetic of sepr_dynmix_reverb_fwd;
+ *   v_g^K[t] = (z_g^K[t] * seg_norm) * seg_gain, the two separately rounded float32 multiplies, never contracted, on the support
+ *              seg_place <= t < min(n, seg_place + seg_len + K - 1): the tail runs past the segment's end and is cut only by the conversation's;
+ *   wet_s[t] = ((+0.0 + v_a^taps[t]) + v_b^taps[t]) + ... over the segments of track s whose support holds t, in table order (by place), in float32.
+ *              Several segments can contribute to one sample - a tail under the next turns of the same track.  A running sum that starts at +0.0 is
+ *              never -0.0, so leaving out a segment that contributes a zero is exact, and the kernel skips whatever reaches only silence;
+ *   tracks_s[t] the same sum with K = direct_g: the scoring reference, aligned in time with the mixture (the mixing launch's target = "direct");
+ *   mix[t]   = ((+0.0 + wet_0[t]) + wet_1[t]) + ... over the S_max tracks in order.
+ * So with every rir = -1, mix and tracks are sepr_conversation_render's on the same table, except that a track sample that is -0.0 there comes
+ * out +0.0 here (as a perturbed -0.0 does in section 5e-5); a unit impulse h = [1.0] gives the bits of rir = -1; and a response [0, .., 0, 1.0] of
+ * k + 1 taps gives the dry track delayed by k samples and cut at n.  A noise bed needs nothing of the kernel: it is one more track after the talkers,
+ * its segments rir = -1, summed into mix last because it is the last track.
+ * Arguments: sepr_conversation_render's up to seg_gain, the three columns, sepr_conversation_render's from track_off to tracks, the bank (NR >= 0
+ * responses; NR = 0 with NULL bank pointers makes every segment response-free), the stream.  The kernel makes tiles of 2048 flat output samples; a
+ * tile in which conversations meet makes the piece of each in turn, so no piece mixes two.  Per piece and track it finds the segments whose support
+ * can reach the piece - binary search over seg_place, then back while place + len + 16383 lies past the piece's start - and adds them in table
+ * order, each by the FIR plan of the mixing launch (taps in ascending chunks of 1024, the chunk's span staged in LDS as doubles, the float64 sums in
+ * registers across chunks; a thread owns eight consecutive outputs and slides a window of staged samples through its registers; the sum after
+ * `direct` taps is a prefix of the same sequence and is kept on the way).  A (track, piece) that no support
+ * reaches is zeros with nothing staged, and a tap chunk that reaches no sample of the segment is skipped.  The decomposition does not show in the
+ * result, there are no atomics, and two calls give equal bits.  The tables are device memory, so the kernel clamps: the response index (negative =
+ * none, above NR - 1 = NR - 1), taps to 1 .. min(len_r, 16384), direct to 1 .. taps, every bank read into [0, rir_total), and everything
+ * sepr_conversation_render clamps; stores go below total only.  A bad table gives wrong samples and bounded work, never an access outside a buffer.
+ * SEPR_EINVAL before any HIP call for everything sepr_conversation_render refuses, a null column, NR < 0, and with NR > 0 what
+ * sepr_dynmix_reverb_fwd refuses of a bank (a null rir or rir_off, rir_total < 1, a misaligned rir) or a rir_off that is not 8-byte aligned.
+ * 38912 bytes of LDS, no workspace, no host synchronisation or allocation (capturable: the pointers are frozen, the tables are read at replay). */
+int sepr_conversation_render_rooms(const short* buf16, long long total16, const float* buf32, long long total32, const long long* offsets, int N16,
+                                   int N, const int* seg_utt, const int* seg_start, const int* seg_place, const int* seg_len,
+                                   const float* seg_norm, const float* seg_gain, const int* seg_rir, const int* seg_taps, const int* seg_direct,
+                                   const int* track_off, const long long* out_off, int R, int S_max, int G, long long total, float* mix,
+                                   float* tracks, const float* rir, long long rir_total, const long long* rir_off, int NR, sepr_stream_t stream);
 int sepr_conversation_render(const short* buf16, long long total16, const float* buf32, long long total32, const long long* offsets, int N16,
                              int N, const int* seg_utt, const int* seg_start, const int* seg_place, const int* seg_len, const float* seg_norm,
                              const float* seg_gain, const int* track_off, const long long* out_off, int R, int S_max, int G, long long total,

@@ -11,7 +11,9 @@ literature (LibriCSS) does:
 
 * ``plan_conversation`` lays corpus utterances along a time line (a schedule: it touches no sample);
 * ``render`` is one ``sepr_conversation_render`` launch for all conversations - the arithmetic of ``sepr_dynmix_fwd``, so a numpy
-  restatement is bit-equal (tests/conversation_ref.py);
+  restatement is bit-equal (tests/conversation_ref.py); conversations whose talkers sit in rooms (``plan_conversation(rirs=...)``) or that
+  carry a noise bed (``noise=...``) go through ``sepr_conversation_render_rooms`` - the float64 convolution of the mixing launch per segment,
+  the tails running on under the next turns, the direct paths as the scoring references (section 5h-2, tests/conversation_rooms_ref.py);
 * ``segment_sisnr`` is one ``sepr_segment_sisnr_fwd`` call: the SI-SNR of every output channel and of the mixture against every
   utterance over that utterance's span, in float64;
 * ``score`` turns the two small matrices into utterance-wise SI-SNRi, the consistent-assignment SI-SNRi and the channel switch rate.
@@ -29,12 +31,11 @@ from . import lib as L_
 from .datafeed import Corpus, _gain, _norm
 
 MAX_TRACKS = 8                       # talker tracks of a conversation, and channels of a scored separator
+MAX_TAPS = 16384                     # samples of the longest impulse response (reverb.MAX_TAPS)
 OVERLAP_BINS = ("0", "(0,0.2]", "(0.2,0.5]", "(0.5,1]")
 
 
-class Conversation(NamedTuple):
-    """A schedule: ``G`` segments sorted by ``(track, place)``.  Segment ``g`` puts the samples ``start[g] .. start[g] + len[g] - 1`` of utterance
-    ``utt[g]``, scaled by ``norm[g]`` and then ``gain[g]``, on the output samples ``place[g] .. place[g] + len[g] - 1`` of track ``track[g]``."""
+class _Schedule(NamedTuple):
     key: str
     n: int                           # output samples, a multiple of 4
     S: int                           # talker tracks, 1 .. 8
@@ -47,26 +48,67 @@ class Conversation(NamedTuple):
     track: np.ndarray                # int32 [G]
 
 
-def make_conversation(key: str, n: int, S: int, segments: Sequence[Tuple[int, int, int, int, float, float, int]]) -> Conversation:
+class Conversation(_Schedule):
+    """A schedule: ``G`` segments sorted by ``(track, place)``.  Segment ``g`` puts the samples ``start[g] .. start[g] + len[g] - 1`` of utterance
+    ``utt[g]``, scaled by ``norm[g]`` and then ``gain[g]``, on the output samples ``place[g] .. place[g] + len[g] - 1`` of track ``track[g]``.
+
+    Four trailing fields with defaults carry the rooms (section 5h-2): ``rir``, ``taps``, ``direct`` (int32 ``[G]``, all three or ``None``) -
+    segment ``g`` rings with the first ``taps[g]`` samples of response ``rir[g]`` of an ``RirBank`` (-1: no response, ``taps = direct = 1``) and
+    its scoring reference keeps the first ``direct[g]`` - and ``bed`` (1: track ``S`` holds a noise bed, outside the talkers).  They are taken
+    positionally or by name and ``_replace`` knows them, but they are attributes beside the tuple: what iteration, slicing and comparison
+    see stays the ten fields above, as code that walks ``conv[3:]`` as the seven columns expects."""
+    ROOM_FIELDS = ("rir", "taps", "direct", "bed")
+
+    def __new__(cls, key, n, S, utt, start, place, len, norm, gain, track, rir=None, taps=None, direct=None, bed=0):
+        self = super().__new__(cls, key, n, S, utt, start, place, len, norm, gain, track)
+        self.rir, self.taps, self.direct, self.bed = rir, taps, direct, int(bed)
+        return self
+
+    def _replace(self, **kw):
+        rooms = {f: kw.pop(f, getattr(self, f)) for f in self.ROOM_FIELDS}
+        return Conversation(*super()._replace(**kw), **rooms)
+
+    def __reduce__(self):
+        return (Conversation, tuple(self) + tuple(getattr(self, f) for f in self.ROOM_FIELDS))
+
+
+def make_conversation(key: str, n: int, S: int, segments: Sequence[Tuple[int, int, int, int, float, float, int]],
+                      rooms: Optional[Sequence[Tuple[int, int, int]]] = None, bed: bool = False) -> Conversation:
     """A ``Conversation`` from ``(utt, start, place, len, norm, gain, track)`` tuples in any order: sorted by ``(track, place)`` and checked -
     ``n`` a positive multiple of 4, ``S`` in 1..8, every segment of at least one sample inside ``[0, n)`` on a track below ``S``, no two
-    segments of one track overlapping."""
-    n, S = int(n), int(S)
+    segments of one track overlapping.  ``rooms``: a ``(rir, taps, direct)`` triple per segment, sorted along with the segments -
+    ``rir >= -1``, ``1 <= direct <= taps <= 16384``, ``taps = direct = 1`` where ``rir = -1``.  ``bed=True``: segments may also lie on track
+    ``S``, the noise bed (``S + 1 <= 8``); they carry no response."""
+    n, S, bed = int(n), int(S), bool(bed)
     if n < 4 or n % 4 or not 1 <= S <= MAX_TRACKS:
         raise ValueError(f"a conversation has a positive multiple of 4 samples and 1..{MAX_TRACKS} tracks, got n = {n}, S = {S}")
+    if bed and S + 1 > MAX_TRACKS:
+        raise ValueError(f"{S} talkers leave no track for a noise bed: talkers and bed share {MAX_TRACKS} tracks")
     if not segments:
         raise ValueError("a conversation holds at least one segment")
-    segs = sorted(segments, key=lambda s: (int(s[6]), int(s[2])))
+    if rooms is not None and len(rooms) != len(segments):
+        raise ValueError("rooms holds one (rir, taps, direct) triple per segment")
+    order = sorted(range(len(segments)), key=lambda i: (int(segments[i][6]), int(segments[i][2])))
+    segs = [segments[i] for i in order]
     end = {}
     for utt, start, place, ln, _, _, trk in segs:
-        if not 0 <= trk < S or ln < 1 or place < 0 or place + ln > n or start < 0 or utt < 0:
+        if not 0 <= trk < S + bed or ln < 1 or place < 0 or place + ln > n or start < 0 or utt < 0:
             raise ValueError(f"segment {(utt, start, place, ln, trk)} does not lie inside a conversation of {n} samples and {S} tracks")
         if place < end.get(trk, 0):
             raise ValueError(f"two segments of track {trk} overlap at sample {place}")
         end[trk] = place + ln
     col = lambda i, dt: np.array([s[i] for s in segs], dtype=dt)
+    room_cols = (None, None, None)
+    if rooms is not None:
+        rms = [tuple(int(v) for v in rooms[i]) for i in order]
+        for (r, taps, direct), sg in zip(rms, segs):
+            if r < -1 or not 1 <= direct <= taps <= MAX_TAPS or (r == -1 and taps != 1):
+                raise ValueError(f"rooms {(r, taps, direct)}: rir >= -1, 1 <= direct <= taps <= {MAX_TAPS}, and taps = direct = 1 where rir = -1")
+            if r >= 0 and int(sg[6]) == S:
+                raise ValueError("a segment of the noise bed carries no response (rir = -1)")
+        room_cols = tuple(np.array([m[k] for m in rms], dtype=np.int32) for k in range(3))
     return Conversation(key, n, S, col(0, np.int32), col(1, np.int32), col(2, np.int32), col(3, np.int32), col(4, np.float32),
-                        col(5, np.float32), col(6, np.int32))
+                        col(5, np.float32), col(6, np.int32), *room_cols, int(bed))
 
 
 def wsj0_speaker(name: str) -> Optional[str]:
@@ -83,7 +125,8 @@ def wsj0_speaker(name: str) -> Optional[str]:
 def plan_conversation(corpus: Corpus, rng: random.Random, seconds: float, roles: Sequence[str] = ("s1", "s2"), speakers: int = 2,
                       overlap: Tuple[float, float] = (0.0, 0.4), pause: Tuple[float, float] = (0.0, 1.0), p_overlap: float = 0.5,
                       gain_db: Tuple[float, float] = (-2.5, 2.5), max_active: int = 2, speaker_of: Optional[Callable[[str], Optional[str]]] = None,
-                      fs: Optional[int] = None, key: Optional[str] = None) -> Conversation:
+                      fs: Optional[int] = None, key: Optional[str] = None, rirs=None, target: str = "direct", early_ms: float = 0.0,
+                      noise: Optional[str] = None, noise_db: Tuple[float, float] = (-6.0, 3.0)) -> Conversation:
     """Lay corpus utterances along ``n = seconds * fs`` samples (rounded down to a multiple of 4; ``fs`` defaults to the corpus's), one track per
     speaker.  The planner reads names, lengths and energies only - it touches no sample.
 
@@ -99,7 +142,18 @@ def plan_conversation(corpus: Corpus, rng: random.Random, seconds: float, roles:
 
     The start is then moved later, if need be, to the first sample where the track itself is free and at most ``max_active - 1`` other tracks
     are still talking.  Every utterance is used from its first sample, RMS-normalised to the conversation's first (``_norm``) and scaled by its
-    gain.  The utterance that reaches ``n`` is cut there and ends the conversation; one that would start at or after ``n`` is dropped."""
+    gain.  The utterance that reaches ``n`` is cut there and ends the conversation; one that would start at or after ``n`` is dropped.
+
+    Rooms and noise (section 5h-2); with both off not one more draw is made:
+
+    * ``rirs`` (an ``RirBank``): directly after step 1, one ``rng.randrange(len(rirs))`` per track, in track order - a talker sits still for
+      the conversation.  Every segment of the track takes that response ``r`` with ``taps = len_r``; ``direct`` is the direct path the mixing
+      planners use for ``target="direct"``, ``rirs._direct[r]``, plus ``round(early_ms fs / 1000)`` taps of early reflections, capped at
+      ``taps``; with ``target="full"`` it is ``taps``.
+    * ``noise`` (a role of the corpus): after the talker loop one ``_gain(rng, *noise_db)`` for the whole bed, then ``rng.choice`` over that
+      role's utterances in file order, repeated: each is laid from its first sample where the one before ended, normalised by
+      ``_norm(rms[first], rms[u])`` (``first`` the conversation's first utterance), and the last is cut at ``n`` - the bed covers ``[0, n)``
+      without a gap, on track ``speakers``, with no response."""
     fs = int(fs if fs is not None else (corpus.fs or 0))
     if fs < 1:
         raise ValueError("the corpus carries no sampling rate: pass fs")
@@ -118,6 +172,18 @@ def plan_conversation(corpus: Corpus, rng: random.Random, seconds: float, roles:
     if len(by_spk) < S:
         raise ValueError(f"{S} tracks need {S} distinct speakers, the pool holds {len(by_spk)}")
     who = rng.sample(sorted(by_spk), S)
+    if target not in ("direct", "full"):
+        raise ValueError(f"target = {target!r}: 'direct' or 'full'")
+    if noise is not None and (S + 1 > MAX_TRACKS or not corpus.roles.get(noise)):
+        raise ValueError(f"a noise bed needs a role {noise!r} with utterances in the corpus and a free track beside {S} talkers")
+    room_of = None
+    if rirs is not None:
+        extra = int(round(float(early_ms) * fs / 1000.0))
+        room_of = []
+        for _ in range(S):
+            r = rng.randrange(len(rirs))
+            taps = int(rirs.lengths[r])
+            room_of.append((r, taps, taps if target == "full" else min(taps, int(rirs._direct[r]) + extra)))
     rms, lengths = corpus.rms, corpus.lengths
     end = [0] * S                                  # the sample after each track's last segment
     segs, prev, prev_len, first = [], -1, 0, -1
@@ -145,16 +211,32 @@ def plan_conversation(corpus: Corpus, rng: random.Random, seconds: float, roles:
         end[trk], prev, prev_len = place + ln, trk, ln
         if end[trk] >= n:
             break
-    return make_conversation(key if key is not None else f"conv_{corpus.names[first]}", n, S, segs)
+    rooms = None if room_of is None else [room_of[sg[6]] for sg in segs]
+    if noise is not None:
+        gain = _gain(rng, *noise_db)
+        pool = [corpus.index[f"{noise}/{k}"] for k in corpus.roles[noise]]
+        if any(int(lengths[u]) < 1 for u in pool):
+            raise ValueError(f"role {noise!r} holds an empty utterance")
+        at = 0
+        while at < n:
+            u = int(rng.choice(pool))
+            ln = min(int(lengths[u]), n - at)
+            segs.append((u, 0, at, ln, _norm(rms[first], rms[u]), gain, S))
+            if rooms is not None:
+                rooms.append((-1, 1, 1))
+            at += ln
+    return make_conversation(key if key is not None else f"conv_{corpus.names[first]}", n, S, segs, rooms=rooms, bed=noise is not None)
 
 
 def overlap_fraction(conv: Conversation) -> np.ndarray:
-    """float64 ``[G]``: the share of each segment's samples during which another track is active.  From the schedule alone, on the host."""
+    """float64 ``[G]``: the share of each segment's samples during which another track is active.  From the schedule alone, on the host.  A noise
+    bed is ignored: it is no talker (its own segments get 0)."""
     G = len(conv.utt)
     out = np.zeros(G, dtype=np.float64)
     a, b = conv.place.astype(np.int64), conv.place.astype(np.int64) + conv.len
-    for g in range(G):
-        other = conv.track != conv.track[g]
+    talker = conv.track < conv.S
+    for g in np.nonzero(talker)[0]:
+        other = (conv.track != conv.track[g]) & talker
         lo, hi = np.maximum(a[other], a[g]), np.minimum(b[other], b[g])
         keep = hi > lo
         covered, reach = 0, a[g]
@@ -171,26 +253,33 @@ class ConvTable:
     """The device tables of ``R`` conversations for ``sepr_conversation_render``: ``words`` int32 ``[6 G + R S_max + 1]`` - the columns utt,
     start, place, len, norm, gain (the two float32 columns as their bits), then ``track_off`` - and ``out_off`` int64 ``[R + 1]``.
     ``pack`` makes the host arrays of a list of conversations with the same ``(R, S_max, G)``; copying them into ``words`` / ``out_off``
-    re-targets a captured launch."""
+    re-targets a captured launch.  A noise bed counts as one more track of its conversation.
+
+    When a conversation carries rooms or a bed (``has_rooms``), ``rooms`` int32 ``[3 G]`` holds the columns rir, taps, direct of
+    ``sepr_conversation_render_rooms``; ``pack_rooms`` is its half of ``pack``, and copying its result into ``rooms`` re-targets a captured
+    rooms launch."""
 
     def __init__(self, convs: Sequence[Conversation], device):
-        self.R, self.S_max, self.G = len(convs), max(c.S for c in convs), sum(len(c.utt) for c in convs)
+        self.R, self.S_max, self.G = len(convs), max(c.S + c.bed for c in convs), sum(len(c.utt) for c in convs)
         words, out_off = self.pack(convs)
         self.total = int(out_off[-1])
         self.words = torch.from_numpy(words).to(device)
         self.out_off = torch.from_numpy(out_off).to(device)
         self.out_off_host = out_off
+        self.has_rooms = any(c.rir is not None or c.bed for c in convs)
+        self.needs_bank = False
+        self.rooms = torch.from_numpy(self.pack_rooms(convs)).to(device) if self.has_rooms else None
 
     def pack(self, convs: Sequence[Conversation]) -> Tuple[np.ndarray, np.ndarray]:
         R, S_max, G = self.R, self.S_max, self.G
-        if not 1 <= R <= 65535 or len(convs) != R or max(c.S for c in convs) > S_max or sum(len(c.utt) for c in convs) != G:
+        if not 1 <= R <= 65535 or len(convs) != R or max(c.S + c.bed for c in convs) > S_max or sum(len(c.utt) for c in convs) != G:
             raise ValueError("the conversations do not fit this table's (R, S_max, G)")
         cat = lambda f, dt: np.concatenate([np.asarray(getattr(c, f), dtype=dt) for c in convs])
         counts = np.zeros(R * S_max, dtype=np.int64)
         for r, c in enumerate(convs):
             if np.any(np.diff(c.track.astype(np.int64) * (1 << 32) + c.place) < 0):
                 raise ValueError(f"{c.key}: the segments are not sorted by (track, place)")
-            counts[r * S_max:r * S_max + c.S] = np.bincount(c.track, minlength=c.S)
+            counts[r * S_max:r * S_max + c.S + c.bed] = np.bincount(c.track, minlength=c.S + c.bed)
         words = np.concatenate([cat("utt", np.int32), cat("start", np.int32), cat("place", np.int32), cat("len", np.int32),
                                 cat("norm", np.float32).view(np.int32), cat("gain", np.float32).view(np.int32),
                                 np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)])
@@ -199,15 +288,50 @@ class ConvTable:
             raise ValueError("every conversation holds a positive multiple of 4 samples")
         return words, out_off
 
+    def pack_rooms(self, convs: Sequence[Conversation], rirs=None) -> np.ndarray:
+        """int32 ``[3 G]``: rir, taps, direct of every segment (-1, 1, 1 for a conversation without rooms).  With ``rirs`` every response index and
+        tap count is checked against the bank."""
+        if len(convs) != self.R or sum(len(c.utt) for c in convs) != self.G:
+            raise ValueError("the conversations do not fit this table's (R, S_max, G)")
+        cols = []
+        for f, fill in (("rir", -1), ("taps", 1), ("direct", 1)):
+            cols.append(np.concatenate([np.full(len(c.utt), fill, dtype=np.int32) if getattr(c, f) is None else
+                                        np.asarray(getattr(c, f), dtype=np.int32) for c in convs]))
+        if rirs is not None:
+            check_rooms(convs, rirs)
+        self.needs_bank = bool((cols[0] >= 0).any())
+        return np.concatenate(cols)
+
     def columns(self) -> List[int]:
         """Device addresses of utt, start, place, len, norm, gain and track_off."""
         p = self.words.data_ptr()
         return [p + 4 * k * self.G for k in range(7)]
 
+    def room_columns(self) -> List[int]:
+        """Device addresses of rir, taps and direct."""
+        p = self.rooms.data_ptr()
+        return [p + 4 * k * self.G for k in range(3)]
 
-def render_into(corpus: Corpus, table: ConvTable, mix: torch.Tensor, tracks: Optional[torch.Tensor]) -> None:
-    """The one ``sepr_conversation_render`` launch on the current stream: ``mix`` float32 ``[total]``, ``tracks`` float32
-    ``[S_max, total]`` or ``None``.  No allocation, no synchronisation: capturable, and the tables are read at replay."""
+
+def check_rooms(convs: Sequence[Conversation], rirs) -> None:
+    """The host's check of the rooms of ``convs`` against the bank ``rirs`` (``ValueError``): a bank as soon as any ``rir >= 0``, every
+    ``rir < len(rirs)`` and every ``taps <= rirs.lengths[rir]``.  The kernel cannot make it: its tables are device memory."""
+    for c in convs:
+        if c.rir is None or not (c.rir >= 0).any():
+            continue
+        if rirs is None:
+            raise ValueError(f"{c.key}: its segments name impulse responses: pass the bank as rirs=")
+        wet = c.rir >= 0
+        if int(c.rir.max()) >= len(rirs):
+            raise ValueError(f"{c.key}: response {int(c.rir.max())} of a bank of {len(rirs)}")
+        if np.any(c.taps[wet] > rirs.lengths[c.rir[wet]]):
+            raise ValueError(f"{c.key}: a segment takes more taps than its response holds")
+
+
+def render_into(corpus: Corpus, table: ConvTable, mix: torch.Tensor, tracks: Optional[torch.Tensor], rirs=None) -> None:
+    """The one ``sepr_conversation_render`` launch on the current stream - ``sepr_conversation_render_rooms`` for a table with rooms or a bed -:
+    ``mix`` float32 ``[total]``, ``tracks`` float32 ``[S_max, total]`` or ``None``.  ``rirs``: the ``RirBank`` the table's response indices
+    name, on the corpus's device.  No allocation, no synchronisation: capturable, and the tables are read at replay."""
     dev = table.words.device
     if dev.type != "cuda" or corpus.device is None:
         raise RuntimeError("conversations are rendered on the HIP device, from a corpus resident there (there is no CPU path)")
@@ -215,14 +339,26 @@ def render_into(corpus: Corpus, table: ConvTable, mix: torch.Tensor, tracks: Opt
         if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev):
             raise ValueError(f"expected a contiguous float32 {shape} tensor on {dev}")
     lib = L_.load()
+    out = (table.out_off.data_ptr(), table.R, table.S_max, table.G, table.total, mix.data_ptr(), None if tracks is None else tracks.data_ptr())
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    if not table.has_rooms:
+        with torch.cuda.device(dev):
+            L_.check(lib.sepr_conversation_render(*corpus._corpus_args(), *table.columns(), *out, stream), "sepr_conversation_render")
+        return
+    if rirs is None and table.needs_bank:
+        raise ValueError("the table's segments name impulse responses: pass the bank as rirs=")
+    if rirs is not None and (rirs.device is None or rirs.device != torch.device(corpus.device)):
+        raise ValueError(f"the RIR bank must be resident on the corpus's device {corpus.device}")
+    bank = rirs._bank_args() if rirs is not None else (None, 0, None, 0)
+    cols = table.columns()
     with torch.cuda.device(dev):
-        L_.check(lib.sepr_conversation_render(*corpus._corpus_args(), *table.columns(), table.out_off.data_ptr(), table.R, table.S_max, table.G,
-                                              table.total, mix.data_ptr(), None if tracks is None else tracks.data_ptr(),
-                                              torch.cuda.current_stream(dev).cuda_stream), "sepr_conversation_render")
+        L_.check(lib.sepr_conversation_render_rooms(*corpus._corpus_args(), *cols[:6], *table.room_columns(), cols[6], *out, *bank, stream),
+                 "sepr_conversation_render_rooms")
 
 
 class Rendered:
-    """``mix`` float32 ``[total]`` with conversation ``r`` at ``out_off[r]``; ``tracks`` ``[S_max, total]`` or ``None``."""
+    """``mix`` float32 ``[total]`` with conversation ``r`` at ``out_off[r]``; ``tracks`` ``[S_max, total]`` or ``None`` - of a conversation in
+    rooms the direct-path references, and after its talkers the noise bed."""
 
     def __init__(self, convs, table: ConvTable, mix: torch.Tensor, tracks: Optional[torch.Tensor]):
         self.convs, self.table, self.mix, self.tracks = list(convs), table, mix, tracks
@@ -237,15 +373,25 @@ class Rendered:
             raise RuntimeError("rendered without tracks")
         return self.tracks[:self.convs[r].S, int(self.out_off[r]):int(self.out_off[r + 1])]
 
+    def bed_of(self, r: int) -> Optional[torch.Tensor]:
+        """``[n_r]`` view: the noise bed of conversation ``r``, or ``None`` when it has none."""
+        if self.tracks is None:
+            raise RuntimeError("rendered without tracks")
+        c = self.convs[r]
+        return self.tracks[c.S, int(self.out_off[r]):int(self.out_off[r + 1])] if c.bed else None
 
-def render(corpus: Corpus, convs: Sequence[Conversation], tracks: bool = True) -> Rendered:
-    """Mixture and talker tracks of every conversation, in one launch from the resident corpus."""
+
+def render(corpus: Corpus, convs: Sequence[Conversation], tracks: bool = True, rirs=None) -> Rendered:
+    """Mixture and talker tracks of every conversation, in one launch from the resident corpus.  Conversations with rooms or a noise bed go
+    through ``sepr_conversation_render_rooms`` (``rirs``: the bank their response indices name; the tracks are then the direct-path references);
+    all others through ``sepr_conversation_render`` as ever."""
+    check_rooms(convs, rirs)
     if corpus.device is None:
         raise RuntimeError("conversations are rendered on the HIP device, from a corpus resident there (there is no CPU path)")
     table = ConvTable(convs, corpus.device)
     mix = torch.empty(table.total, dtype=torch.float32, device=corpus.device)
     trk = torch.empty(table.S_max, table.total, dtype=torch.float32, device=corpus.device) if tracks else None
-    render_into(corpus, table, mix, trk)
+    render_into(corpus, table, mix, trk, rirs=rirs)
     return Rendered(convs, table, mix, trk)
 
 

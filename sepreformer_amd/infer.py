@@ -268,7 +268,7 @@ test_utterances.__test__ = False      # not a pytest test
 
 def evaluate_conversations(model, corpus, convs, method: str = "long", chunk_seconds: float = 4.0, overlap_seconds: float = 1.0,
                            batch: int = 32, slots: int = 32, match_gain: bool = False, csv_path: Optional[str] = None,
-                           wav_dir: Optional[str] = None, fs: int = 8000) -> dict:
+                           wav_dir: Optional[str] = None, fs: int = 8000, rirs=None) -> dict:
     """The test loop of the long-form paths: render every conversation of ``convs`` from the resident ``corpus``
     in one launch (``conversation.render``), separate every mixture with ``separate_long`` (``method="long"``) or
     ``streambank.separate_many`` (``"bank"``), score every output channel against every utterance over that utterance's span
@@ -277,12 +277,27 @@ def evaluate_conversations(model, corpus, convs, method: str = "long", chunk_sec
     ``v`` ``[G, C]`` and ``v_mix`` ``[G]`` (numpy) and ``conversations``.  ``csv_path``: one row per segment - conversation key, segment
     number, track, utterance name, begin, length, overlap fraction, best channel, assigned channel (-1 with more talkers than
     channels), ``v_mix``, ``v[0 .. C - 1]`` - in the csv dialect of the test loop.  ``wav_dir``: the mixture and the outputs of every
-    conversation, ``0.5 / max|.|`` as ``test_save`` writes them."""
+    conversation, ``0.5 / max|.|`` as ``test_save`` writes them.
+
+    Conversations in rooms or over a noise bed (section 5h-2; ``rirs``: the ``RirBank`` their segments name) are rendered by
+    ``sepr_conversation_render_rooms`` and scored against the direct-path tracks of the talkers only; the bed is in the mixture, hence in
+    ``v_mix``.  The scored span of a segment moves with the direct path: ``delay = rirs.direct_taps(0.0)[r] - 1`` (0 without a response),
+    ``begin = min(place + delay, n - 1)``, ``length = max(1, min(len, n - begin))`` - the csv's ``begin`` and ``length``."""
     from . import conversation as cv
     if method not in ("long", "bank"):
         raise ValueError(f"method must be 'long' or 'bank', got {method!r}")
     convs = list(convs)
-    rd = cv.render(corpus, convs, tracks=True)
+    rd = cv.render(corpus, convs, tracks=True, rirs=rirs)
+    peak = rirs.direct_taps(0.0) if rirs is not None else None
+    spans = []                                                    # per conversation: its talker segments, their scored begin and length
+    for conv in convs:
+        k = np.nonzero(conv.track < conv.S)[0]
+        delay = np.zeros(len(k), dtype=np.int64)
+        if conv.rir is not None and peak is not None:
+            wet = conv.rir[k] >= 0
+            delay[wet] = peak[conv.rir[k][wet]] - 1
+        begin = np.minimum(conv.place[k].astype(np.int64) + delay, conv.n - 1)
+        spans.append((k, begin.astype(np.int32), np.maximum(1, np.minimum(conv.len[k], conv.n - begin)).astype(np.int32)))
     mixes = [rd.mixture(r) for r in range(len(convs))]
     if method == "long":
         ests = separate_long(model, mixes, chunk_seconds=chunk_seconds, overlap_seconds=overlap_seconds, fs=fs, batch=batch,
@@ -298,21 +313,22 @@ def evaluate_conversations(model, corpus, convs, method: str = "long", chunk_sec
         a, b = int(rd.out_off[r]), int(rd.out_off[r + 1])
         for c in range(C):
             est_all[c, a:b].copy_(est[c])
-        v, v_mix = cv.segment_sisnr(est_all[:, a:b], rd.tracks_of(r), rd.mixture(r), conv.track, conv.place, conv.len)
+        k, begin, length = spans[r]
+        v, v_mix = cv.segment_sisnr(est_all[:, a:b], rd.tracks_of(r), rd.mixture(r), conv.track[k], begin, length)
         vs.append(v)
         vms.append(v_mix)
     v, v_mix = torch.cat(vs).cpu().numpy(), torch.cat(vms).cpu().numpy()                      # the one copy of the scores
-    conv_of = np.concatenate([np.full(len(c.utt), r) for r, c in enumerate(convs)])
-    out = cv.score(v, v_mix, conv_of, np.concatenate([c.track for c in convs]), [c.S for c in convs], C,
-                   overlap=np.concatenate([cv.overlap_fraction(c) for c in convs]))
+    conv_of = np.concatenate([np.full(len(k), r) for r, (k, _, _) in enumerate(spans)])
+    out = cv.score(v, v_mix, conv_of, np.concatenate([c.track[k] for c, (k, _, _) in zip(convs, spans)]), [c.S for c in convs], C,
+                   overlap=np.concatenate([cv.overlap_fraction(c)[k] for c, (k, _, _) in zip(convs, spans)]))
     out.update(v=v, v_mix=v_mix, conversations=len(convs))
     if csv_path:
         with open(csv_path, "w", newline="") as fh:
             w = csv.writer(fh, quotechar="|", quoting=csv.QUOTE_MINIMAL)
             g = 0
-            for conv in convs:
-                for k in range(len(conv.utt)):
-                    w.writerow([conv.key, k, int(conv.track[k]), corpus.names[int(conv.utt[k])], int(conv.place[k]), int(conv.len[k]),
+            for conv, (ks, begin, length) in zip(convs, spans):
+                for i, k in enumerate(ks):
+                    w.writerow([conv.key, int(k), int(conv.track[k]), corpus.names[int(conv.utt[k])], int(begin[i]), int(length[i]),
                                 float(out["overlap"][g]), int(out["best"][g]), int(out["assigned"][g]), float(v_mix[g])] +
                                [float(x) for x in v[g]])
                     g += 1

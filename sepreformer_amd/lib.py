@@ -185,6 +185,8 @@ SIGNATURES = {
                                    _fp]),
     "sepr_rir_ism_fwd": (_i, [_fp, _i, _i, _d, _fp, _fp, _fp, _fp, _i, _fp]),
     "sepr_conversation_render": (_i, [_fp, _ll, _fp, _ll, _fp, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _ll, _fp, _fp, _fp]),
+    "sepr_conversation_render_rooms": (_i, [_fp, _ll, _fp, _ll, _fp, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _ll,
+                                            _fp, _fp, _fp, _ll, _fp, _i, _fp]),
     "sepr_segment_sisnr_bytes": (_ll, [_i, _i]),
     "sepr_segment_sisnr_fwd": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _ll, _d, _fp, _fp, _fp, _sz, _fp]),
     "sepr_pit_sisnr_fwd": (_i, [_fp, _fp, _fp, _i, _i, _i, C.c_double, C.c_double, C.c_double, _fp, _fp, _fp, _fp,

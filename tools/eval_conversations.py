@@ -7,6 +7,12 @@ The utterances of the scp lists are loaded into a device-resident ``Corpus``; CO
 under the one consistent track -> channel assignment, the rate of channel switches, all three also by overlap ratio.
 
     python tools/eval_conversations.py --scp s1=tt_s1.scp s2=tt_s2.scp --count 20 --minutes 10 --overlap 0:0.4 --method bank [--checkpoint F [--ema]]
+
+Rooms and noise (section 5h-2), for the models trained on reverberant or noisy mixtures: every talker of a conversation sits in one room of a bank
+(``--rir-scp``, ``--synthetic-rirs`` or ``--room-rirs``, as ``tools/train_from_scp.py`` takes them) and is scored against the direct path of their
+own voice; ``--noise-role`` lays the utterances of that role end to end under the whole conversation.
+
+    python tools/eval_conversations.py --scp s1=tt_s1.scp s2=tt_s2.scp noise=tt_noise.scp --noise-role noise --room-rirs 64:0.2:0.6 --model SepReformer_Large_DM_WHAMR
 """
 import argparse
 import json
@@ -48,6 +54,20 @@ def main():
     ap.add_argument("--fs", type=int, default=8000)
     ap.add_argument("--resample", action="store_true", help="convert files at another rate on the device (default: an error)")
     ap.add_argument("--device", default="cuda:0")
+    rir = ap.add_mutually_exclusive_group()
+    rir.add_argument("--rir-scp", default=None, metavar="FILE", help="rooms: a 'key path' list of impulse-response wav files; one is drawn per talker "
+                     "and conversation and convolved inside the render launch")
+    rir.add_argument("--synthetic-rirs", default=None, metavar="COUNT:RT60LO:RT60HI", help="rooms from COUNT synthetic impulse responses with RT60 "
+                     "drawn from [RT60LO, RT60HI] seconds (sepreformer_amd.reverb.synthetic_rirs)")
+    rir.add_argument("--room-rirs", default=None, metavar="COUNT[:RT60LO:RT60HI]", help="rooms from COUNT shoebox rooms simulated on the device by the "
+                     "image-source method (sepreformer_amd.reverb.RoomSampler; default RT60 range 0.2:0.6)")
+    ap.add_argument("--reverb-target", choices=["direct", "full"], default="direct", help="the scoring reference of a talker in a room: the direct "
+                    "path of their response (default) or the whole response")
+    ap.add_argument("--early-ms", type=float, default=0.0, help="with --reverb-target direct: this much of the early reflections counts as direct")
+    ap.add_argument("--noise-role", default=None, metavar="ROLE", help="a noise bed under every conversation from the utterances of this --scp role")
+    ap.add_argument("--noise-db", default="-6:3", metavar="LO:HI", help="the bed's gain is 10^(-u / 20), u uniform in [LO, HI] dB (one draw per conversation); "
+                    "write a negative LO as --noise-db=-6:3")
+    ap.add_argument("--seed", type=int, default=0, help="seed of the synthetic or simulated rooms")
     ap.add_argument("--csv", default=None, help="one row per utterance of every conversation")
     ap.add_argument("--wav-dir", default=None, help="write every mixture and every output channel")
     args = ap.parse_args()
@@ -59,6 +79,14 @@ def main():
         if not eq or not role or not path:
             ap.error(f"--scp takes ROLE=FILE, got {item!r}")
         scps[role] = path
+    if args.noise_role is not None and args.noise_role not in scps:
+        ap.error(f"--noise-role {args.noise_role}: no such role among --scp")
+    from sepreformer_amd import reverb
+    try:
+        room_spec = reverb.parse_rooms(args.room_rirs) if args.room_rirs else None
+        synth = reverb.parse_synthetic(args.synthetic_rirs) if args.synthetic_rirs else None
+    except ValueError as e:
+        ap.error(f"--room-rirs / --synthetic-rirs: {e}")
     from sepreformer_amd import conversation as cv
     from sepreformer_amd import infer
     from sepreformer_amd.config import VARIANTS
@@ -71,12 +99,21 @@ def main():
         model.load_synthetic_(0)
     model = model.eval().to(args.device)
     corpus = Corpus.from_scp(scps, fs=args.fs, device=args.device, resample=args.resample)
-    convs = [cv.plan_conversation(corpus, random.Random(i), seconds=60.0 * args.minutes, roles=tuple(scps), speakers=args.speakers,
+    bank = None
+    if args.rir_scp:
+        bank = reverb.RirBank.from_scp(args.rir_scp, fs=args.fs, device=args.device, resample=args.resample)
+    elif room_spec:
+        bank = reverb.RirBank.simulate(reverb.RoomSampler(rt60=room_spec[1:]).draw(room_spec[0], seed=(args.seed, 0)), args.fs, device=args.device)
+    elif synth:
+        bank = reverb.RirBank.from_arrays(reverb.synthetic_rirs(synth[0], args.fs, rt60=synth[1:], seed=args.seed), args.fs, device=args.device)
+    talkers = tuple(r for r in scps if r != args.noise_role)
+    convs = [cv.plan_conversation(corpus, random.Random(i), seconds=60.0 * args.minutes, roles=talkers, speakers=args.speakers,
                                   overlap=_range(args.overlap, "--overlap"), pause=_range(args.pause, "--pause"), p_overlap=args.p_overlap,
-                                  max_active=args.max_active, key=f"conv{i:03d}") for i in range(args.count)]
+                                  max_active=args.max_active, key=f"conv{i:03d}", rirs=bank, target=args.reverb_target, early_ms=args.early_ms,
+                                  noise=args.noise_role, noise_db=_range(args.noise_db, "--noise-db")) for i in range(args.count)]
     out = infer.evaluate_conversations(model, corpus, convs, method=args.method, chunk_seconds=args.chunk_seconds,
                                        overlap_seconds=args.overlap_seconds, batch=args.batch, slots=args.slots, match_gain=args.match_gain,
-                                       csv_path=args.csv, wav_dir=args.wav_dir, fs=args.fs)
+                                       csv_path=args.csv, wav_dir=args.wav_dir, fs=args.fs, rirs=bank)
     print(json.dumps({"method": args.method, "conversations": out["conversations"], "utterances": out["n"], "sisnri_utt": out["sisnri_utt"],
                       "sisnri_cons": out["sisnri_cons"], "switch_rate": out["switch_rate"], "bins": out["bins"]}))
 
