@@ -665,7 +665,9 @@ int sepr_rir_ism_fwd(const double* rooms, int R, int N, double fsc, const double
  * for 0 <= d < seg_len.  The segments of all R conversations lie in one table of G rows sorted by (conversation, track, place);
  * track_off [R S_max + 1] int32 holds the cumulative segment counts per (conversation, track) - a track without a segment has an empty range -
  * and out_off [R + 1] int64 the first flat output sample of each conversation (multiples of 4, out_off[R] = total).  The segments of one track do
- * not overlap.  All eight tables are DEVICE memory; the corpus is described exactly as for sepr_dynmix_fwd.
+ * not overlap.  All eight tables are DEVICE memory; the corpus is described exactly as for sepr_dynmix_fwd.  A segment may begin before output
+ * sample 0 or end after n_r (seg_place >= -2^30; section 5e-8: a window cut out of a longer schedule): both render entries then make the part
+ * of it - and, in rooms, of its tail - that falls inside [0, n_r); every search and walk compares values only and stores are bounded by total.
  *
  * sepr_conversation_render: one launch renders every conversation.  With x the utterance's sample value (an int16 sample is s / 32768),
  *   track_s[t] = (x[seg_start + t - seg_place] * seg_norm) * seg_gain  for the one segment of track s that covers t, else +0.0   (two separately
@@ -740,6 +742,46 @@ long long sepr_segment_sisnr_bytes(int G, int C);   /* (long long: the size_t en
 int sepr_segment_sisnr_fwd(const float* est, const float* ref, const float* mix, const int* rows, const int* begin, const int* length, int G,
                            int C, int S, int T, long long ld, double eps, double* v, double* v_mix, void* ws, size_t ws_bytes,
                            sepr_stream_t stream);
+
+/* ---- Graph-PIT: assignment of the target rows of a conversation window to output channels (new entries, no struct
+ * change: ABI 4.13) -----------------------------------------------------------------------------------------------------------------------------
+ * A window holds U <= 8 target rows - one per utterance heard in it - for a separator of C <= 3 output channels; plain PIT has no answer to
+ * "which row goes on which channel" when U != C.  Graph-PIT (von Neumann et al., 2021): every row is a node, rows that may not share a channel are
+ * joined by an edge, a valid assignment is a colouring col: u -> c of that graph with C colours, and the loss is the minimum over the valid
+ * colourings.  est and rows are HOST arrays of C and U device pointers, each to a [B][T] float32 tensor, read at the call and frozen in a captured
+ * launch; spans [B][U][2] int32 and adj [B][U] uint32 are DEVICE tables, read at replay.  Row u of example b is t_u, ZERO outside its span
+ * [on, off) = (spans[b][u][0], spans[b][u][1]) whatever the buffer holds there: the kernels never read a row outside its span, clamped as on into
+ * [0, T] and off into [on, T].  An empty span makes a silent row: it is no node - always coloured 0, not enumerated, its adjacency bits ignored.
+ * Bit v of adj[b][u] says rows u and v may not share a channel; an edge named by either side counts, bits at or above U and a row's own bit do not.
+ *
+ * All arithmetic is float64 on exact float32 inputs; ~ is zero-mean over all T samples, as in sepr_pit_sasdr_fwd.  The moments of example b:
+ *   se_c = sum e_c, ee_c = sum e_c^2 over T;   st_u = sum t_u, tt_u = sum t_u^2, et_cu = sum e_c t_u over the span of u;
+ *   tv_uv = sum t_u t_v over the intersection of the spans of u and v (0 when empty) - rows of one colour may overlap, so the Gram term is exact.
+ * For a colouring, with the rows of a colour taken in ascending order and the pairs in lexicographic order:
+ *   Sy_c = sum_{u in c} st_u,   yy_c = sum_{u in c} tt_u + 2 sum_{u < v in c} tv_uv - Sy_c^2 / T,   ee~_c = ee_c - se_c^2 / T,
+ *   ey_c = sum_{u in c} et_cu - se_c Sy_c / T,   E = max(0, sum_c ((ee~_c - 2 ey_c) + yy_c)),   D = sum_c yy_c.
+ * sepr_graph_pit_assign: col [B][U] int32 = the first minimiser of E over the valid colourings in lexicographic order of (col(0), .., col(U - 1));
+ * value [B] float64 = 10 log10((E + tau D + eps) / (D + eps)), tau = 10^(-snr_max / 10): for U = C rows over all T, every pair adjacent, it is
+ * sepr_pit_sasdr_fwd's loss; status [B] int32 = 0.  Where no valid colouring exists status = 1, col = 0 and value = NaN.  Two launches: one
+ * workgroup per (example, moment) - thread i of 256 adds the samples i, i + 256, ... of the interval, a wave adds its lanes by butterfly, the four
+ * wave sums are added in wave order, an empty interval stores 0 at once - into the workspace; then one workgroup per example evaluates the at most
+ * 3^8 colourings, whole, from the moment tables in LDS, thread i the colourings i, i + 256, ..., and reduces the minimum and its first index in a
+ * fixed order.  Workspace: sepr_graph_pit_bytes(C, U, B) bytes (0 for unsupported C, U, B).
+ * sepr_graph_pit_assemble: out_c[b][t] = ((+0.0 + t_u1[t]) + t_u2[t]) + ... over the rows of colour c in ascending u - float32 adds, never
+ * contracted; a row is skipped outside its span, which changes no bit of a sum that began at +0.0.  out is a HOST array of C device pointers to
+ * [B][T] tensors; col is read at replay and clamped into [0, C).  One thread per four samples: a row that covers them is read with one aligned
+ * 16-byte load, one that covers some of them element by element under the span's mask - a span that starts at an odd sample causes no misaligned
+ * load -; one float4 store per thread and channel.
+ * Both: no atomics, results bit-identical from run to run; no host synchronisation or allocation (capturable); every table value is clamped, so a
+ * bad table gives wrong values but never an access outside a buffer.  SEPR_EINVAL before any HIP call for a null pointer (in the arrays too),
+ * C outside 1..3, U outside 1..8, B outside 1..65535, T < 4 or not a multiple of 4, eps outside [0, 1], snr_max outside [0, 300], an est pointer
+ * or table that is not 4-byte aligned, value not 8-byte aligned, and in assemble a row or out pointer that is not 16-byte aligned;
+ * SEPR_EWORKSPACE for a short workspace. */
+long long sepr_graph_pit_bytes(int C, int U, int B);
+int sepr_graph_pit_assign(const float* const* est, const float* const* rows, const int* spans, const unsigned* adj, int C, int U, int B, int T,
+                          double eps, double snr_max, int* col, double* value, int* status, void* ws, size_t ws_bytes, sepr_stream_t stream);
+int sepr_graph_pit_assemble(const float* const* rows, const int* spans, const int* col, int C, int U, int B, int T, float* const* out,
+                            sepr_stream_t stream);
 
 /* ================================================================================================================= */
 /* Training path: train-mode forward twins that keep what the backward needs, and the       */

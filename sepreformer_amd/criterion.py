@@ -416,8 +416,132 @@ class PIT_SASDR_mag(PIT_SISNR_mag):
         return self.num_spks * torch.sum(loss) / kwargs["input_sizes"].shape[0]
 
 
+# ---- Graph-PIT ------------------------------------------------------------------------------------
+GRAPH_MAX_CHANNELS, GRAPH_MAX_ROWS = 3, 8
+
+
+class GraphPIT:
+    """``GraphPIT(device, channels, rows, batch, samples, snr_max=30.0)``: the targets of a conversation window for a separator of ``channels``
+    outputs, from the window's ``rows`` target rows - one per utterance heard in it (``sepr_graph_pit_assign`` / ``sepr_graph_pit_assemble``,
+    include/sepr.h; the CPU restatement is ``tests/graphpit_ref.py``).  Rows that overlap in time may not share a channel; among the colourings
+    of that graph the one with the lowest source-aggregated error against the estimates is taken, and each channel's target is the sum of its
+    rows.
+
+    The object owns static device tensors, so both launches replay from a captured graph: ``spans`` int32 ``[B, U, 2]`` and ``adj`` int32
+    ``[B, U]`` (the tables ``load`` rewrites), ``col`` int32 ``[B, U]``, ``value`` float64 ``[B]``, ``status`` int32 ``[B]`` (1: the graph of
+    that example has no colouring with ``channels`` colours - ``col`` is 0, ``value`` NaN) and the ``channels`` assembled targets ``[B, T]``.
+
+    ``graph(estims, rows)`` returns those target tensors.  They are targets: nothing is differentiated through them.  The loss is the existing
+    ``PIT_SASDR_time`` / ``PIT_SASDR_mag`` on ``(estims, graph(estims, rows))`` - their permutation search includes the identity.  The SI-SNR
+    pair is refused (``check_pair``): an assembled channel is often silent, where those criteria have no usable gradient."""
+
+    SLOTS = 4               # pinned staging buffers in flight
+    EPS = 1.0e-8            # PIT_SASDR_time's
+
+    def __init__(self, device, channels: int, rows: int, batch: int, samples: int, snr_max: float = 30.0):
+        C_, U, B, T = int(channels), int(rows), int(batch), int(samples)
+        if not (1 <= C_ <= GRAPH_MAX_CHANNELS and 1 <= U <= GRAPH_MAX_ROWS and B >= 1 and T >= 4 and T % 4 == 0):
+            raise ValueError(f"GraphPIT: 1..{GRAPH_MAX_CHANNELS} channels, 1..{GRAPH_MAX_ROWS} rows, batch >= 1 and a positive multiple of 4 "
+                             f"samples, got {(C_, U, B, T)}")
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("GraphPIT runs on the HIP device (there is no CPU path)")
+        self.channels, self.rows, self.batch, self.samples, self.snr_max = C_, U, B, T, float(snr_max)
+        nbytes = int(L.load().sepr_graph_pit_bytes(C_, U, B))
+        if nbytes == 0:
+            raise RuntimeError(f"unsupported Graph-PIT problem: channels={C_}, rows={U}, batch={B}")
+        dev = self.device
+        self._table = torch.zeros(3 * B * U, dtype=torch.int32, device=dev)      # spans, then adj: one copy re-targets both launches
+        self.spans = self._table[:2 * B * U].view(B, U, 2)
+        self.adj = self._table[2 * B * U:].view(B, U)
+        self.col = torch.zeros(B, U, dtype=torch.int32, device=dev)
+        self.value = torch.zeros(B, dtype=torch.float64, device=dev)
+        self.status = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.targets = [torch.zeros(B, T, dtype=torch.float32, device=dev) for _ in range(C_)]
+        self._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self._stage: List[torch.Tensor] = []
+        self._events: list = []
+        self._slot = 0
+
+    def __repr__(self):
+        return (f"<GraphPIT(device={self.device!r}, channels={self.channels}, rows={self.rows}, batch={self.batch}, samples={self.samples}, "
+                f"snr_max={self.snr_max!r})>")
+
+    @staticmethod
+    def check_pair(*criteria) -> None:
+        """Refuse the SI-SNR criteria as the loss on assembled targets."""
+        for c in criteria:
+            if isinstance(c, (PIT_SISNR_time, PIT_SISNRi)) or type(c) is PIT_SISNR_mag:
+                raise ValueError(f"{type(c).__name__} on Graph-PIT targets: an assembled channel is often silent, where the SI-SNR criteria give "
+                                 "a zero or unbounded gradient - use PIT_SASDR_time / PIT_SASDR_mag")
+
+    def load(self, spans, adj) -> None:
+        """The tables of the next call, from host arrays (``spans`` ``[B, U, 2]``, ``adj`` ``[B, U]``, any integer type): written into a pinned
+        staging buffer, then one asynchronous copy on the current stream.  Nothing waits for the device."""
+        import numpy as np
+        B, U = self.batch, self.rows
+        sp, ad = np.asarray(spans), np.asarray(adj)
+        if sp.shape != (B, U, 2) or ad.shape != (B, U):
+            raise ValueError(f"GraphPIT.load: spans {(B, U, 2)} and adj {(B, U)}, got {sp.shape} and {ad.shape}")
+        if not self._stage:
+            self._stage = [torch.empty(3 * B * U, dtype=torch.int32).pin_memory() for _ in range(self.SLOTS)]
+            self._events = [None] * self.SLOTS
+        k = self._slot
+        self._slot = (k + 1) % self.SLOTS
+        if self._events[k] is not None:
+            self._events[k].synchronize()               # the copy that last read this staging buffer has run (SLOTS batches ago)
+        host = self._stage[k].numpy()
+        host[:2 * B * U] = sp.astype(np.int64).clip(-2 ** 31, 2 ** 31 - 1).astype(np.int32).ravel()
+        host[2 * B * U:] = (ad.astype(np.int64) & 0xFFFFFFFF).astype(np.uint32).view(np.int32).ravel()
+        self._table.copy_(self._stage[k], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.device))
+        self._events[k] = ev
+
+    def _pointers(self, tensors, count: int, what: str):
+        ts = list(tensors) if not isinstance(tensors, torch.Tensor) else list(tensors.unbind(0))
+        if len(ts) != count:
+            raise RuntimeError(f"expected {count} {what}, got {len(ts)}")
+        keep = []
+        for t in ts:
+            t = t.detach()
+            if t.device != self.device or tuple(t.shape) != (self.batch, self.samples):
+                raise RuntimeError(f"{what}: [{self.batch}, {self.samples}] tensors on {self.device}, got {tuple(t.shape)} on {t.device}")
+            keep.append(t.to(torch.float32).contiguous())
+        import ctypes
+        return (ctypes.c_void_p * count)(*[t.data_ptr() for t in keep]), keep
+
+    def assign(self, estims, rows) -> None:
+        """``col``, ``value`` and ``status`` of the batch in ``rows`` against ``estims`` under the loaded tables."""
+        lib = L.load()
+        ep, ek = self._pointers(estims, self.channels, "estimates")
+        rp, rk = self._pointers(rows, self.rows, "target rows")
+        with torch.cuda.device(self.device):
+            L.check(lib.sepr_graph_pit_assign(ep, rp, self.spans.data_ptr(), self.adj.data_ptr(), self.channels, self.rows, self.batch,
+                                              self.samples, self.EPS, self.snr_max, self.col.data_ptr(), self.value.data_ptr(),
+                                              self.status.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
+                                              torch.cuda.current_stream(self.device).cuda_stream), "sepr_graph_pit_assign")
+
+    def assemble(self, rows) -> List[torch.Tensor]:
+        """The channels' targets from ``rows`` under ``col``: written into ``self.targets`` and returned."""
+        import ctypes
+        lib = L.load()
+        rp, rk = self._pointers(rows, self.rows, "target rows")
+        op = (ctypes.c_void_p * self.channels)(*[t.data_ptr() for t in self.targets])
+        with torch.cuda.device(self.device):
+            L.check(lib.sepr_graph_pit_assemble(rp, self.spans.data_ptr(), self.col.data_ptr(), self.channels, self.rows, self.batch,
+                                                self.samples, op, torch.cuda.current_stream(self.device).cuda_stream),
+                    "sepr_graph_pit_assemble")
+        return self.targets
+
+    def __call__(self, estims, rows) -> List[torch.Tensor]:
+        with torch.no_grad():
+            self.assign(estims, rows)
+            return self.assemble(rows)
+
+
 # ---- BSS-eval SDR (PIT_SDRi, criterions.py:264-289) ----------------------------------------------------------------------
-BSS_FLEN = 512                     # mir_eval's distortion-filter length
+BSS_FLEN = 512                    # mir_eval's distortion-filter length
 BSS_WS_CAP = 1 << 30               # one call's workspace stays under 1 GiB: larger batches are split
 
 

@@ -189,6 +189,9 @@ SIGNATURES = {
                                             _fp, _fp, _fp, _ll, _fp, _i, _fp]),
     "sepr_segment_sisnr_bytes": (_ll, [_i, _i]),
     "sepr_segment_sisnr_fwd": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _ll, _d, _fp, _fp, _fp, _sz, _fp]),
+    "sepr_graph_pit_bytes": (_ll, [_i, _i, _i]),
+    "sepr_graph_pit_assign": (_i, [C.POINTER(_fp), C.POINTER(_fp), _fp, _fp, _i, _i, _i, _i, _d, _d, _fp, _fp, _fp, _fp, _sz, _fp]),
+    "sepr_graph_pit_assemble": (_i, [C.POINTER(_fp), _fp, _fp, _i, _i, _i, _i, C.POINTER(_fp), _fp]),
     "sepr_pit_sisnr_fwd": (_i, [_fp, _fp, _fp, _i, _i, _i, C.c_double, C.c_double, C.c_double, _fp, _fp, _fp, _fp,
                                 _fp, _sz, _fp]),
     "sepr_train_ctx_bytes": (_sz, [_i] * 8),

@@ -177,13 +177,22 @@ def mix_loss(l_time: torch.Tensor, l_mag: Sequence[torch.Tensor], w_time: torch.
     return (w_time * l_time + w_freq * (acc / len(l_mag))) / num_spks
 
 
-CRITERIA = ("sisnr", "sasdr")
+CRITERIA = ("sisnr", "sasdr", "graph_sasdr")
 
 
-def check_criterion(criterion: str, absent: float) -> None:
-    """What ``Trainer`` refuses: an unknown criterion, and the SI-SNR criteria on a feed that makes windows with a silent talker."""
+def check_criterion(criterion: str, absent: float, rows: Optional[int] = None) -> None:
+    """What ``Trainer`` refuses: an unknown criterion, the SI-SNR criteria on a feed that makes windows with a silent talker or target rows
+    (``rows``: the training feed's ``.rows``, ``None`` for a feed of sources), and Graph-PIT on a feed without rows."""
+    if criterion == "graph_sisnr":
+        raise ValueError("Graph-PIT is built on the SA-SDR pair only: an assembled channel is often silent, where the SI-SNR criteria give a zero "
+                         "or unbounded gradient - use criterion='graph_sasdr'")
     if criterion not in CRITERIA:
         raise ValueError(f"criterion: one of {CRITERIA}, got {criterion!r}")
+    if criterion == "graph_sasdr" and rows is None:
+        raise ValueError("criterion='graph_sasdr' needs a training feed of target rows (convfeed.ConversationWindowFeed: it has .rows)")
+    if criterion != "graph_sasdr" and rows is not None:
+        raise ValueError(f"the training feed makes {rows} target rows per window, not one source per channel: train it with "
+                         "criterion='graph_sasdr'")
     if criterion == "sisnr" and float(absent or 0.0) > 0.0:
         raise ValueError(f"the training feed has absent = {absent}: on a silent target the SI-SNR criteria give the estimate a zero gradient "
                          "(time form: alpha = 0) or one that grows like 1 / |estimate| (magnitude form); train it with criterion='sasdr'")
@@ -226,7 +235,9 @@ class Trainer:
         ``optimizer`` / ``scheduler`` settings; the defaults are the values its four ``configs.yaml`` share.  ``ema_decay`` / ``ema_warmup``:
         the weight EMA of ``FlatAdamW``; ``validate_with`` (``"raw"``, ``"ema"``, ``"both"``) is ignored while it is off.  ``criterion``:
         ``"sisnr"`` (the reference's ``PIT_SISNR_time`` / ``PIT_SISNR_mag``) or ``"sasdr"`` (``PIT_SASDR_time`` / ``PIT_SASDR_mag`` with
-        ``snr_max``), for training and validation alike; a training feed with ``absent > 0`` needs ``"sasdr"``."""
+        ``snr_max``), for training and validation alike; a training feed with ``absent > 0`` needs ``"sasdr"``.
+        ``"graph_sasdr"`` (section 5e-8): the SA-SDR pair on the targets a ``criterion.GraphPIT`` assembles from the target rows of a
+        ``convfeed.ConversationWindowFeed``; a validation feed without ``.rows`` is scored by the plain SA-SDR pair."""
         if mvn:
             raise ValueError("mvn: true is not supported (every shipped configuration has it false)")
         if not getattr(train_feed, "fixed_length", False):
@@ -236,8 +247,8 @@ class Trainer:
             raise ValueError("validate_with: 'raw', 'ema' or 'both'")
         if warmup_steps < 1 or log_every < 1:
             raise ValueError("warmup_steps >= 1 and log_every >= 1")
-        check_criterion(criterion, getattr(train_feed, "absent", 0.0))
-        from .criterion import PIT_SASDR_mag, PIT_SASDR_time, PIT_SISNR_mag, PIT_SISNR_time
+        check_criterion(criterion, getattr(train_feed, "absent", 0.0), getattr(train_feed, "rows", None))
+        from .criterion import GraphPIT, PIT_SASDR_mag, PIT_SASDR_time, PIT_SISNR_mag, PIT_SISNR_time
         from .optim import FlatAdamW
         self.model, self.train_feed, self.valid_feed, self.dir = model, train_feed, valid_feed, checkpoint_dir
         self.cfg = model.cfg
@@ -253,7 +264,7 @@ class Trainer:
         self.scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(self.opt, mode="min", factor=factor, patience=patience, min_lr=min_lr)
         S, R = self.cfg.num_spks, self.cfg.num_stages
         self.criterion, self.snr_max = criterion, float(snr_max)
-        if criterion == "sasdr":
+        if criterion in ("sasdr", "graph_sasdr"):
             self.crit_t = PIT_SASDR_time(self.dev, S, self.snr_max)
             self.crit_m = PIT_SASDR_mag(self.dev, 512, 128, "hann", R, S, self.snr_max)
         else:
@@ -269,7 +280,10 @@ class Trainer:
         B, T = train_feed.batch, train_feed.max_len
         self._sizes = torch.full((B,), T)                # fixed-length rows: the padding is part of the example
         self._x = torch.zeros(B, T, device=self.dev)
-        self._targets = [torch.zeros(B, T, device=self.dev) for _ in range(S)]
+        # Graph-PIT: the step's targets are the feed's rows, and the criteria see what the GraphPIT assembles from them inside the captured step
+        self.graph = GraphPIT(self.dev, S, train_feed.rows, B, T, self.snr_max) if criterion == "graph_sasdr" else None
+        self._vgraph = None                              # the validation feed's, built on its first batch of rows
+        self._targets = [torch.zeros(B, T, device=self.dev) for _ in range(S if self.graph is None else train_feed.rows)]
         self.step = None                                 # CapturedTrainStep, built on the first batch of a (re)start
         self._snap: Optional[torch.Tensor] = None        # pinned host copy of the ledger for the log interval's look
         self.global_step, self.best, self.start_epoch = 0, float("inf"), 1
@@ -282,7 +296,7 @@ class Trainer:
         self.w_freq.fill_(a)
 
     def _loss_fn(self, audio, aux, *targets):
-        tg = list(targets)
+        tg = list(targets) if self.graph is None else self.graph(audio, list(targets))
         l_time = self.crit_t(estims=audio, input_sizes=self._sizes, target_attr=tg).reshape(())
         l_mag = [self.crit_m(estims=a, idx=i, input_sizes=self._sizes, target_attr=tg).reshape(()) for i, a in enumerate(aux)]
         with torch.no_grad():
@@ -340,6 +354,8 @@ class Trainer:
         for plan in self.train_feed.plans():
             i += 1
             group["lr"] = batch_lr(group["lr"], self.base_lr, epoch, i, self.warmup_steps)
+            if self.graph is not None:
+                self.graph.load(plan.spans, plan.adj)     # the tables the step's two Graph-PIT launches read
             if self.step is None:
                 self.train_feed.write(plan, self._x, self._targets)
                 self._build_step()
@@ -384,8 +400,16 @@ class Trainer:
         nb = 0
         with torch.inference_mode():
             self.vledger.zero_()
+            rows = getattr(self.valid_feed, "rows", None) if self.graph is not None else None
             for sizes, mix, src, _ in self.valid_feed:
                 audio, aux = self.model(mix)
+                if rows is not None:                      # a feed of rows: the targets its own GraphPIT assembles against these estimates
+                    if self._vgraph is None:
+                        from .criterion import GraphPIT
+                        self._vgraph = GraphPIT(self.dev, self.cfg.num_spks, rows, int(mix.shape[0]), int(mix.shape[1]), self.snr_max)
+                    plan = self.valid_feed.last_plan
+                    self._vgraph.load(plan.spans, plan.adj)
+                    src = self._vgraph(audio, src)
                 l_time = self.crit_t(estims=audio, input_sizes=sizes, target_attr=src).reshape(())
                 l_mag = [self.crit_m(estims=a, idx=i, input_sizes=sizes, target_attr=src).reshape(()) for i, a in enumerate(aux)]
                 self.vparts.copy_(torch.stack([l_time] + l_mag))

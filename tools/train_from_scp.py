@@ -56,7 +56,15 @@ def main():
                     "(0 = a hard gate; default 80)")
     ap.add_argument("--turn-absent", type=float, default=0.0, metavar="P", help="with --turns: with probability P one talker of an example, drawn "
                     "uniformly, is silent throughout - its target row is zero (default 0); needs --criterion sasdr")
-    ap.add_argument("--criterion", choices=["sisnr", "sasdr"], default="sisnr", help="the training and validation criteria: the reference's PIT SI-SNR "
+    ap.add_argument("--conversation-windows", default=None, metavar="COUNT:SECONDS", help="train on windows of --max-len samples cut out of COUNT "
+                    "conversations of SECONDS seconds planned anew every epoch (sepreformer_amd.convfeed.ConversationWindowFeed): a varying number "
+                    "of utterances per window, talkers who speak twice, more talkers than output channels; the roles s1 s2 are the talkers' "
+                    "pool, --form wham / whamr lays the role noise under them as a bed, the room options seat every talker in a room; needs "
+                    "--criterion graph_sasdr")
+    ap.add_argument("--speakers", type=int, default=3, metavar="N", help="with --conversation-windows: talkers per conversation (default 3)")
+    ap.add_argument("--max-active", type=int, default=2, metavar="N", help="with --conversation-windows: talkers who may speak at once, at most the "
+                    "model's output channels (default 2)")
+    ap.add_argument("--criterion", choices=["sisnr", "sasdr", "graph_sasdr"], default="sisnr", help="the training and validation criteria: the reference's PIT SI-SNR "
                     "pair (default) or the source-aggregated, soft-thresholded SDR pair, which is defined on a silent target (DESIGN.md section 5e-7)")
     ap.add_argument("--snr-max", type=float, default=30.0, metavar="DB", help="with --criterion sasdr: the soft threshold tau = 10^(-DB / 10) (default 30)")
     ap.add_argument("--steps", type=int, default=100)
@@ -99,6 +107,23 @@ def main():
         ap.error("--turn-absent must lie in [0, 1]")
     if args.turn_absent and args.criterion != "sasdr":
         ap.error("--turn-absent needs --criterion sasdr: the SI-SNR criteria give a zero (time) or exploding (magnitude) gradient on a silent target")
+    windows = None
+    if args.conversation_windows:
+        try:
+            count, _, secs = args.conversation_windows.partition(":")
+            windows = (int(count), float(secs))
+            if windows[0] < 1 or not windows[1] > 0:
+                raise ValueError
+        except ValueError:
+            ap.error("--conversation-windows COUNT:SECONDS, e.g. 32:120")
+        if args.form == "direct" or args.speeds or args.turns:
+            ap.error("--conversation-windows plans its own conversations: --form wsj0, wham or whamr, without --speeds and --turns")
+        if args.reverb_target == "dry":
+            ap.error("--conversation-windows: --reverb-target direct or full (a conversation's references are aligned with its mixture)")
+        if not 1 <= args.max_active <= args.speakers <= 8:
+            ap.error("1 <= --max-active <= --speakers <= 8")
+    if (args.criterion == "graph_sasdr") != (windows is not None):
+        ap.error("--criterion graph_sasdr and --conversation-windows go together: Graph-PIT assigns the target rows of a window to the channels")
     reverb = args.rir_scp or args.synthetic_rirs or args.room_rirs
     if reverb and args.form == "direct":
         ap.error("--rir-scp / --synthetic-rirs / --room-rirs need dynamic mixing (--form wsj0, wham or whamr)")
@@ -143,7 +168,8 @@ def main():
             bank = RirBank.simulate(sampler.draw(room_spec[0], seed=(args.seed, 0)), args.fs, device=dev)      # the feed redraws it per epoch
         else:
             bank = RirBank.from_arrays(synthetic_rirs(synth[0], args.fs, rt60=synth[1:], seed=args.seed), args.fs, device=dev)
-        planner = functools.partial(planner, rirs=bank, target=args.reverb_target, speed_reverb=bool(args.speeds))
+        if windows is None:
+            planner = functools.partial(planner, rirs=bank, target=args.reverb_target, speed_reverb=bool(args.speeds))
         print(f"RIR bank: {len(bank)} impulse responses, {int(bank.lengths.min())} .. {int(bank.lengths.max())} samples", flush=True)
     if args.turns:
         try:
@@ -151,15 +177,33 @@ def main():
                                         **({"absent": args.turn_absent} if args.turn_absent else {}))
         except ValueError as e:
             ap.error(f"--turns / --turn-ramp: {e}")
-    feed = df.DynamicMixFeed(corpus, planner, batch=args.batch, max_len=args.max_len, seed=args.seed, fixed_length=True, rirs=bank,
-                              rooms=sampler, rooms_every=args.rooms_every)
+    cfg = VARIANTS[args.model]
+    if windows is not None:
+        from sepreformer_amd.conversation import plan_conversation
+        from sepreformer_amd.convfeed import ConversationWindowFeed
+        kw = dict(speakers=args.speakers, max_active=args.max_active)
+        if args.form in ("wham", "whamr"):
+            kw["noise"] = "noise"
+        if bank is not None:
+            kw["target"] = args.reverb_target                                 # (simulated rooms are drawn once: this feed does not redraw them)
+        try:
+            feed = ConversationWindowFeed(corpus, batch=args.batch, max_len=args.max_len, channels=cfg.num_spks, conversations=windows[0],
+                                          seconds=windows[1], planner=functools.partial(plan_conversation, **kw), seed=args.seed, rirs=bank)
+        except ValueError as e:
+            ap.error(f"--conversation-windows: {e}")
+    else:
+        feed = df.DynamicMixFeed(corpus, planner, batch=args.batch, max_len=args.max_len, seed=args.seed, fixed_length=True, rirs=bank,
+                                 rooms=sampler, rooms_every=args.rooms_every)
     print(f"corpus: {len(corpus)} utterances, {corpus.total16 * 2 + corpus.total32 * 4} bytes on {dev}", flush=True)
 
-    cfg = VARIANTS[args.model]
     model = Model.from_config(cfg, init_seed=args.seed, precision=args.precision).to(dev).train()
     if args.epochs is not None:
         return run_epochs(args, df, model, feed, dev)
-    if args.criterion == "sasdr":
+    graph = None
+    if windows is not None:
+        from sepreformer_amd.criterion import GraphPIT
+        graph = GraphPIT(dev, cfg.num_spks, feed.rows, args.batch, args.max_len, args.snr_max)
+    if args.criterion in ("sasdr", "graph_sasdr"):
         crit_t = PIT_SASDR_time(dev, cfg.num_spks, args.snr_max)
         crit_m = PIT_SASDR_mag(dev, 512, 128, "hann", cfg.num_stages, cfg.num_spks, args.snr_max)
     else:
@@ -169,20 +213,26 @@ def main():
     opt = FlatAdamW(model, lr=args.lr, weight_decay=1.0e-2)
 
     def loss_fn(audio, aux, *tg):
-        tg = list(tg)
+        tg = list(tg) if graph is None else graph(audio, list(tg))           # Graph-PIT: the channels' targets assembled from the window's rows
         l_time = crit_t(estims=audio, input_sizes=sizes, target_attr=tg)
         l_mag = [crit_m(estims=a, idx=i, input_sizes=sizes, target_attr=tg) for i, a in enumerate(aux)]
         return (0.6 * l_time + 0.4 * sum(l_mag) / len(l_mag)) / cfg.num_spks
 
     x = torch.zeros(args.batch, args.max_len, device=dev)
-    targets = [torch.zeros(args.batch, args.max_len, device=dev) for _ in range(cfg.num_spks)]
-    feed.next_into(x, targets)
+    targets = [torch.zeros(args.batch, args.max_len, device=dev) for _ in range(cfg.num_spks if graph is None else feed.rows)]
+
+    def next_into(x, targets):
+        plan = feed.next_into(x, targets)
+        if graph is not None:
+            graph.load(plan.spans, plan.adj)
+
+    next_into(x, targets)
     step = CapturedTrainStep(model, loss_fn, opt, x, targets, max_norm=5.0)
     torch.cuda.synchronize()
     t0, done = time.perf_counter(), 0
     log_every = args.log or 10
     for i in range(1, args.steps + 1):
-        feed.next_into(step.x, step.targets)
+        next_into(step.x, step.targets)
         loss, gn = step(step.x, step.targets)
         if i % log_every == 0 or i == args.steps:
             val = float(loss.detach())                                        # synchronises: once per log interval
