@@ -743,6 +743,46 @@ int sepr_segment_sisnr_fwd(const float* est, const float* ref, const float* mix,
                            int C, int S, int T, long long ld, double eps, double* v, double* v_mix, void* ws, size_t ws_bytes,
                            sepr_stream_t stream);
 
+/* ---- frame activity: what a channel emits when none of its talkers speaks (new entries, no struct change: ABI 4.13) ----
+ * sepr_frame_energy_fwd: x [rows][ld] float32 with T <= ld valid samples per row (rows may be views with the common row stride ld); frame a multiple
+ * of 4 in 32..4096; nF = ceil(T / frame), the last frame holding the 1..frame samples that are left.  e [rows][nF] float64 = the sum of x^2 over the
+ * frame; the square of a float32 value is exact in float64, so only the additions round.  One wave per (row, frame), in this order: lane l of 64
+ * starts from +0.0 and adds the squares of the samples 4 q, 4 q + 1, 4 q + 2, 4 q + 3 of the frame for q = l, l + 64, l + 128, ..., in ascending
+ * order, leaving out those at or past the frame's end; then the lanes are added by butterfly - for o = 32, 16, 8, 4, 2, 1 every lane adds the value of
+ * lane l ^ o to its own - and lane 0 stores.  One launch for all rows (frames by fours on grid.x, rows on grid.y).  Where x is 16-byte aligned and ld
+ * a multiple of 4 four samples are one load; the additions are the same either way.  Zero samples behind a recording add +0.0 and change no bit, so
+ * recordings laid out on frame boundaries in one buffer give the frames each gives alone.  SEPR_EINVAL before any HIP call for a null pointer, rows
+ * outside 1..65535, T < 1 or above 2^36, ld < T, a frame that is no multiple of 4 in 32..4096, x not 4-byte or e not 8-byte aligned.
+ *
+ * sepr_frame_activity_fwd: e [rows][nF] float64 (contiguous).  Per row: level[row] = the maximum of e[f] + 0.0 over the frames, a NaN never taken
+ * (-infinity when every frame is NaN) - a maximum does not depend on the order, and + 0.0 gives a zero one sign; t = level * ratio, one float64
+ * multiply, and thr = t > floor ? t : floor; raw[f] = e[f] > thr, strictly, so an all-zero row is inactive everywhere and a NaN frame is inactive;
+ * active [rows][nF] uint8 = 1 where raw[f'] holds for some f' in the row with |f' - f| <= hang, else 0.  The caller passes ratio = 10^(ratio_db / 10)
+ * as a double: the device calls no pow, and a host restatement has the same threshold.  hang = 0 (no widening) and hang >= nF (a row with one raw
+ * frame is active everywhere) are both legal.  Two launches: a workgroup per row finds level and counts raw into the workspace, cnt[row][f + 1] =
+ * #{f' <= f : raw[f']} in int32; a thread per frame then tests cnt[min(nF, f + hang + 1)] - cnt[max(0, f - hang)] > 0.  Integers only after the
+ * compare.  Workspace: sepr_frame_activity_bytes(rows, nF) bytes (0 for rows outside 1..65535 or nF outside 1..2^30).  SEPR_EINVAL before any HIP
+ * call for a null e, active or level, rows or nF outside those ranges, hang < 0, a ratio or floor that is negative, infinite or NaN, e or level not
+ * 8-byte aligned; SEPR_EWORKSPACE for a short or null workspace.
+ *
+ * sepr_frame_class_sums_fwd: e_est [C][nF] and e_mix [nF] float64, active [C][nF] and cls [C][nF] uint8 (DEVICE, read at replay); a class byte is
+ * used as cls & 3.  out [C][4][4] float64: for channel c and class k, over the frames f with (cls[c][f] & 3) == k: out[c][k][0] = their number,
+ * [1] = the number of them with active[c][f] != 0, [2] = the sum of e_est[c][f], [3] = the sum of e_mix[f].  The grid is (C, 4) workgroups of 256
+ * threads, in the form of segsnr_value_kernel: thread i starts from +0.0 and takes the frames i, i + 256, ... in order, adding only those of its class;
+ * a wave adds its lanes by the butterfly above; the four wave sums are added ((w0 + w1) + w2) + w3.  The counts are sums of ones in the same order:
+ * exact below 2^53.  The workspace, sepr_frame_class_sums_bytes(C, nF) bytes (0 for C outside 1..8 or nF outside 1..2^30), keeps the wave sums,
+ * part [C][4][4][4] float64 with the wave last, so that a restatement can be compared stage by stage.  SEPR_EINVAL before any HIP call for a null
+ * pointer, C or nF outside those ranges, e_est, e_mix or out not 8-byte aligned; SEPR_EWORKSPACE for a short or null workspace.
+ * All three: no atomics, two calls give equal bits, no host synchronisation or allocation (capturable: the pointers are frozen, the tables are read
+ * at replay). */
+int sepr_frame_energy_fwd(const float* x, int rows, long long T, long long ld, int frame, double* e, sepr_stream_t stream);
+long long sepr_frame_activity_bytes(int rows, int nF);
+int sepr_frame_activity_fwd(const double* e, int rows, int nF, double ratio, double floor, int hang, unsigned char* active, double* level, void* ws,
+                            size_t ws_bytes, sepr_stream_t stream);
+long long sepr_frame_class_sums_bytes(int C, int nF);
+int sepr_frame_class_sums_fwd(const double* e_est, const double* e_mix, const unsigned char* active, const unsigned char* cls, int C, int nF,
+                              double* out, void* ws, size_t ws_bytes, sepr_stream_t stream);
+
 /* ---- Graph-PIT: assignment of the target rows of a conversation window to output channels (new entries, no struct
  * change: ABI 4.13) -----------------------------------------------------------------------------------------------------------------------------
  * A window holds U <= 8 target rows - one per utterance heard in it - for a separator of C <= 3 output channels; plain PIT has no answer to

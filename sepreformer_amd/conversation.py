@@ -16,7 +16,10 @@ literature (LibriCSS) does:
   the tails running on under the next turns, the direct paths as the scoring references (section 5h-2, tests/conversation_rooms_ref.py);
 * ``segment_sisnr`` is one ``sepr_segment_sisnr_fwd`` call: the SI-SNR of every output channel and of the mixture against every
   utterance over that utterance's span, in float64;
-* ``score`` turns the two small matrices into utterance-wise SI-SNRi, the consistent-assignment SI-SNRi and the channel switch rate.
+* ``score`` turns the two small matrices into utterance-wise SI-SNRi, the consistent-assignment SI-SNRi and the channel switch rate;
+* ``colour`` is the assignment that exists for any number of talkers - utterances whose spans intersect go on different channels -,
+  ``frame_classes`` says which frames of a channel are its own, a collar, another talker's or nobody's, and ``idle_figures`` turns the class
+  sums of ``activity.frame_class_sums`` into leak, false-alarm and miss figures (section 5h-3).
 """
 from __future__ import annotations
 
@@ -448,7 +451,110 @@ def _mean(x: np.ndarray) -> float:
     return float(x.mean()) if x.size else float("nan")
 
 
-def score(v, v_mix, conv_of, track, S_of, C: int, overlap=None) -> dict:
+def colour(v, begin, length, C: int) -> Optional[np.ndarray]:
+    """The consistent assignment for any number of talkers: ``v [G][C]`` the scores of one conversation's segments
+    on every channel, ``begin``, ``length [G]`` their scored spans.  Segments ``g`` and ``h`` are adjacent iff ``[begin, begin + length)`` of
+    the two intersect - spans that only abut are not -, an assignment ``a: g -> channel`` is valid iff adjacent segments differ, and the
+    result is the valid ``a`` (int64 ``[G]``, by table index) maximising ``sum_g v[g][a(g)]``: the total accumulated in float64 from 0.0, left
+    to right over the segments ordered by ``(begin, table index)``; on a tie the lexicographically first ``(a(g_0), a(g_1), ..)`` in that
+    order.  ``None`` when more than ``C`` segments are open at once: there is no colouring.
+
+    The graph is an interval graph, so this is a sweep over the ordered segments whose state is the channels of the segments still open -
+    at most ``C`` of them, hence at most ``C! / (C - k)!`` states, never ``C^G`` assignments.  Two prefixes that reach the same open state
+    are merged: the larger total is kept, and on equal totals the lexicographically smaller prefix.  That is exact, because float addition
+    is monotone - ``s <= t`` implies ``fl(s + x) <= fl(t + x)`` -, so whatever follows, the kept prefix ends at least as high as the
+    dropped one, and a prefix with the very same total ends at the very same total.  One caveat: a strict gap between two prefixes can
+    round to a tie further on; the enumeration would then take the lexicographically first of the two, the sweep has kept the one that was
+    ahead."""
+    v = np.asarray(v, dtype=np.float64).reshape(-1, int(C))
+    b = np.asarray(begin, dtype=np.int64).reshape(-1)
+    e = b + np.asarray(length, dtype=np.int64).reshape(-1)
+    G, C = v.shape[0], int(C)
+    if b.shape[0] != G or e.shape[0] != G or G < 1:
+        raise ValueError("one row of v, begin and length per segment, and at least one segment")
+    order = sorted(range(G), key=lambda g: (int(b[g]), g))
+    open_: List[int] = []                                          # positions (in order) of the segments still open, ascending
+    states: Dict[Tuple[int, ...], Tuple[float, Tuple[int, ...]]] = {(): (0.0, ())}      # channels of the open segments -> (total, prefix)
+    for j, g in enumerate(order):
+        keep = [i for i, p in enumerate(open_) if e[order[p]] > b[g]]
+        if len(keep) >= C:
+            return None
+        open_ = [open_[i] for i in keep] + [j]
+        nxt: Dict[Tuple[int, ...], Tuple[float, Tuple[int, ...]]] = {}
+        for st, (tot, pre) in states.items():
+            held = tuple(st[i] for i in keep)
+            for c in range(C):
+                if c in held:
+                    continue
+                cand = (tot + v[g, c], pre + (c,))
+                old = nxt.get(held + (c,))
+                if old is None or cand[0] > old[0] or (cand[0] == old[0] and cand[1] < old[1]):
+                    nxt[held + (c,)] = cand
+        states = nxt
+    top = None
+    for tot, pre in states.values():
+        if top is None or tot > top[0] or (tot == top[0] and pre < top[1]):
+            top = (tot, pre)
+    out = np.empty(G, dtype=np.int64)
+    out[np.asarray(order)] = np.asarray(top[1], dtype=np.int64)
+    return out
+
+
+def frame_classes(conv_spans, coloured, n: int, C: int, frame: int, collar: int) -> np.ndarray:
+    """uint8 ``[C][nF]``, ``nF = ceil(n / frame)``: the class of every frame ``[f frame, min(n, (f + 1) frame))`` of every channel of one
+    conversation of ``n`` samples.  ``conv_spans = (begin, length)``: the scored spans of its segments, ``coloured [G]`` their channels
+    (``colour``; -1: none).  For channel ``c`` the first rule that holds:
+
+    * 0 (own): the frame intersects a scored span coloured ``c``;
+    * 3 (collar): it intersects such a span widened by ``collar`` samples on both sides;
+    * 1 (cross): it intersects any talker's widened span;
+    * 2 (quiet): nothing of the above.
+
+    The idle classes 1 and 2 therefore hold only frames that lie entirely outside every span that ``c`` owns, collar included."""
+    begin, length = (np.asarray(x, dtype=np.int64).reshape(-1) for x in conv_spans)
+    coloured = np.asarray(coloured, dtype=np.int64).reshape(-1)
+    n, C, frame, collar = int(n), int(C), int(frame), int(collar)
+    if n < 1 or frame < 1 or collar < 0 or C < 1 or not (begin.shape == length.shape == coloured.shape):
+        raise ValueError("n, frame and C are positive, collar is not negative, and begin, length and coloured hold one value per segment")
+    nF = -(-n // frame)
+    cls = np.full((C, nF), 2, dtype=np.uint8)
+
+    def frames(lo, hi):                                            # the frames that [lo, hi) clipped to [0, n) intersects
+        lo, hi = max(0, int(lo)), min(n, int(hi))
+        return slice(lo // frame, (hi - 1) // frame + 1) if hi > lo else slice(0, 0)
+
+    for b, ln in zip(begin, length):
+        cls[:, frames(b - collar, b + ln + collar)] = 1
+    for c in range(C):
+        own = np.nonzero(coloured == c)[0]
+        for g in own:
+            cls[c, frames(begin[g] - collar, begin[g] + length[g] + collar)] = 3
+        for g in own:
+            cls[c, frames(begin[g], begin[g] + length[g])] = 0
+    return cls
+
+
+def idle_figures(sums, eps: float = 1e-15) -> dict:
+    """The idle figures from class sums ``[..., 4, 4]`` (``activity.frame_class_sums``: per class the frames, the active frames, the sum of
+    ``e_est``, the sum of ``e_mix``), each of the leading shape: ``leak_db = 10 log10((sum e_est + eps) / (sum e_mix + eps))`` over class 1,
+    NaN where it has no frame or no mixture energy; ``quiet_db`` the same over class 2; ``false_alarm`` = active / all frames of the classes 1
+    and 2 together; ``miss`` = inactive / all frames of class 0; NaN where there is no such frame."""
+    s = np.asarray(sums, dtype=np.float64)
+    nan = np.full(s.shape[:-2], np.nan)
+
+    def db(k):
+        ok = (s[..., k, 0] > 0) & (s[..., k, 3] > 0)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(ok, 10.0 * np.log10((s[..., k, 2] + eps) / (s[..., k, 3] + eps)), nan)
+
+    n_idle, a_idle = s[..., 1, 0] + s[..., 2, 0], s[..., 1, 1] + s[..., 2, 1]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        fa = np.where(n_idle > 0, a_idle / n_idle, nan)
+        miss = np.where(s[..., 0, 0] > 0, (s[..., 0, 0] - s[..., 0, 1]) / s[..., 0, 0], nan)
+    return {"leak_db": db(1), "quiet_db": db(2), "false_alarm": fa, "miss": miss}
+
+
+def score(v, v_mix, conv_of, track, S_of, C: int, overlap=None, spans=None) -> dict:
     """Scores from the two matrices of ``segment_sisnr`` - pure host arithmetic, after one copy.  ``conv_of [G]``: the conversation of each
     segment, ``track [G]``: its track, ``S_of[r]``: the tracks of conversation ``r``, ``C``: the separator's channels.
 
@@ -459,7 +565,12 @@ def score(v, v_mix, conv_of, track, S_of, C: int, overlap=None) -> dict:
     * ``S > C``: ``cons`` and ``switch`` are NaN, ``assigned`` is -1, and the means leave them out.
 
     Means: ``sisnri_utt``, ``sisnri_cons``, ``switch_rate``; with ``overlap`` (``overlap_fraction`` per segment) also ``bins``: per overlap bin
-    ``{"n", "sisnri_utt", "sisnri_cons"}`` in the order of ``OVERLAP_BINS``."""
+    ``{"n", "sisnri_utt", "sisnri_cons"}`` in the order of ``OVERLAP_BINS``.
+
+    ``spans = (begin [G], length [G])``, the scored spans: the dict gains the assignment that exists for any number of talkers (``colour``,
+    per conversation) - ``coloured [G]`` (-1 where a conversation has no colouring), ``graph[g] = v[g][coloured[g]] - v_mix[g]`` (NaN
+    there), their mean ``sisnri_graph``, ``bins[*]["sisnri_graph"]`` and ``graph_switch_rate``, the share of coloured segments with
+    ``best != coloured``.  Without ``spans`` the dict is as it always was."""
     v = (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)).astype(np.float64).reshape(-1, int(C))
     v_mix = (v_mix.detach().cpu().numpy() if isinstance(v_mix, torch.Tensor) else np.asarray(v_mix)).astype(np.float64).reshape(-1)
     conv_of, track = np.asarray(conv_of, dtype=np.int64), np.asarray(track, dtype=np.int64)
@@ -500,4 +611,23 @@ def score(v, v_mix, conv_of, track, S_of, C: int, overlap=None) -> dict:
         out["overlap"] = ov
         out["bins"] = {name: {"n": int((which == k).sum()), "sisnri_utt": _mean(utt[which == k]), "sisnri_cons": _mean(cons[which == k])}
                        for k, name in enumerate(OVERLAP_BINS)}
+    if spans is not None:
+        begin, length = (np.asarray(x, dtype=np.int64).reshape(-1) for x in spans)
+        if not (begin.shape[0] == length.shape[0] == G):
+            raise ValueError("spans holds one begin and one length per segment")
+        coloured = np.full(G, -1, dtype=np.int64)
+        for r in sorted(set(conv_of.tolist())):
+            idx = np.nonzero(conv_of == r)[0]
+            a = colour(v[idx], begin[idx], length[idx], C)
+            if a is not None:
+                coloured[idx] = a
+        has = coloured >= 0
+        graph = np.full(G, np.nan)
+        graph[has] = v[has, coloured[has]] - v_mix[has]
+        gsw = np.full(G, np.nan)
+        gsw[has] = (best[has] != coloured[has]).astype(np.float64)
+        out.update(coloured=coloured, graph=graph, sisnri_graph=_mean(graph), graph_switch_rate=_mean(gsw))
+        if overlap is not None:
+            for k, name in enumerate(OVERLAP_BINS):
+                out["bins"][name]["sisnri_graph"] = _mean(graph[which == k])
     return out

@@ -14,7 +14,10 @@ Mirrors ``models/SepReformer_Base_WSJ0/engine.py``:
 * ``separate_long`` / ``separate_long_file`` - beyond the reference: recordings of any length by overlapping windows of the
   training length, batched through the separator and stitched on the device (``longform.py``, DESIGN.md section 5c);
 * ``separate_many_files`` - several files through the stream bank, whose forwards carry one window of every file in flight
-  (``streambank.py``).
+  (``streambank.py``, DESIGN.md section 5c-2);
+* ``evaluate_conversations`` / ``score_conversations`` - the test loop of the long-form paths on conversations rendered on the device
+  (DESIGN.md section 5h), with ``idle=True`` also what a channel emits while none of its talkers speaks (section 5h-3);
+* ``--activity-csv`` on every path that writes tracks: when each separated track carries signal (``activity.channel_activity``).
 
 Host-side logic only; every waveform sample is computed by the HIP separator (``Model.forward``) and the HIP
 criterion kernels.  File I/O uses scipy (the reference uses librosa / soundfile, absent here): PCM16/PCM32/float
@@ -110,10 +113,12 @@ def _load_mixture(model, path: str, fs: int, resample: bool) -> Tuple[torch.Tens
 
 
 def _write_outputs(model, prefix: str, file_mix: torch.Tensor, sr: int, mix: torch.Tensor, est: Sequence[torch.Tensor], fs: int,
-                   out_rate: Union[None, int, str]) -> Tuple[np.ndarray, List[str]]:
+                   out_rate: Union[None, int, str], activity: Optional[dict] = None) -> Tuple[np.ndarray, List[str]]:
     """``<prefix>_in.wav`` and ``<prefix>_out_<i>.wav``, peak-normalised to 0.9, at ``out_rate`` (None: ``fs``; "input": the file's
     rate ``sr``).  The copy of the input is the file's own samples converted from ``sr``; the estimates are converted from ``fs``,
-    all of them in one launch.  Returns the raw estimates ``[S,T]`` at ``fs`` as the separator produced them."""
+    all of them in one launch.  Returns the raw estimates ``[S,T]`` at ``fs`` as the separator produced them.
+    ``activity`` (``{"csv": path, "ratio_db": .., "hang_ms": ..}``): ``activity.channel_activity`` on the estimates at ``fs``, its runs written
+    to the csv (``activity.write_activity_csv``: channel, begin s, end s) and the path appended to the files written."""
     from .resample import resample as _resample
     rate = fs if out_rate is None else (sr if out_rate == "input" else int(out_rate))
     dev = next(model.parameters()).device
@@ -124,44 +129,58 @@ def _write_outputs(model, prefix: str, file_mix: torch.Tensor, sr: int, mix: tor
     for i, o in enumerate(outs):
         written.append(f"{prefix}_out_{i}.wav")
         write_wav(written[-1], peak_normalise(o.detach().cpu().numpy(), 0.9), rate)
+    if activity:
+        from . import activity as act
+        tracks = torch.stack([e.to(dev) for e in est])
+        active, _, _ = act.channel_activity(tracks, fs=fs, ratio_db=activity.get("ratio_db", -40.0), hang_ms=activity.get("hang_ms", 200.0))
+        act.write_activity_csv(activity["csv"], act.segments(active, act.frame_samples(fs), tracks.shape[1]), fs)
+        written.append(activity["csv"])
     return np.stack([e.detach().cpu().numpy() for e in est]), written
 
 
 def separate_file(model, path: str, fs: int = 8000, out_prefix: Optional[str] = None, resample: bool = False,
-                  out_rate: Union[None, int, str] = None) -> Tuple[np.ndarray, List[str]]:
+                  out_rate: Union[None, int, str] = None, activity: Optional[dict] = None) -> Tuple[np.ndarray, List[str]]:
     """``Engine._inference_sample``.  Returns the raw (un-normalised) estimates ``[S,T]`` at ``fs`` and the files written.
     ``resample``: a file at another rate is converted to ``fs`` on the device before separation (default: it raises).
     ``out_rate``: the estimates and the ``_in.wav`` copy are converted to that rate before peak normalisation and writing
-    (``"input"``: the file's own rate; default: ``fs``)."""
+    (``"input"``: the file's own rate; default: ``fs``).  ``activity``: see ``_write_outputs``."""
     file_mix, mix, sr = _load_mixture(model, path, fs, resample)
     est = [e[0] for e in separate(model, mix[None])]
-    return _write_outputs(model, out_prefix if out_prefix is not None else path[:-4], file_mix, sr, mix, est, fs, out_rate)
+    return _write_outputs(model, out_prefix if out_prefix is not None else path[:-4], file_mix, sr, mix, est, fs, out_rate, activity)
 
 
 def separate_long_file(model, path: str, fs: int = 8000, out_prefix: Optional[str] = None, chunk_seconds: float = 4.0,
                        overlap_seconds: float = 1.0, match_gain: bool = False, batch: int = 32, resample: bool = False,
-                       out_rate: Union[None, int, str] = None) -> Tuple[np.ndarray, List[str]]:
+                       out_rate: Union[None, int, str] = None, activity: Optional[dict] = None) -> Tuple[np.ndarray, List[str]]:
     """``separate_file`` through ``separate_long``: the same files, the same 0.9 peak normalisation, the same ``resample`` /
     ``out_rate`` options."""
     file_mix, mix, sr = _load_mixture(model, path, fs, resample)
     est = separate_long(model, mix, chunk_seconds=chunk_seconds, overlap_seconds=overlap_seconds, fs=fs, batch=batch,
                         match_gain=match_gain)
-    return _write_outputs(model, out_prefix if out_prefix is not None else path[:-4], file_mix, sr, mix, est, fs, out_rate)
+    return _write_outputs(model, out_prefix if out_prefix is not None else path[:-4], file_mix, sr, mix, est, fs, out_rate, activity)
 
 
 def separate_many_files(model, paths: Sequence[str], fs: int = 8000, slots: int = 32, chunk_seconds: float = 4.0,
                         overlap_seconds: float = 1.0, match_gain: bool = False, resample: bool = False,
-                        out_rate: Union[None, int, str] = None) -> List[Tuple[np.ndarray, List[str]]]:
+                        out_rate: Union[None, int, str] = None, activity: Optional[dict] = None) -> List[Tuple[np.ndarray, List[str]]]:
     """``separate_long_file`` for several files at once through ``streambank.separate_many``: per file, the raw estimates and the
     files written (the same names, the same 0.9 peak normalisation, the same ``resample`` / ``out_rate`` options).  With ``resample`` the
     files' own samples and rates go to the bank, which converts every stream inside its hops (``separate_many(rates=...)``): no file is
-    converted in a launch and a synchronisation of its own.  The copy of the input is converted only where it is written at ``fs``."""
+    converted in a launch and a synchronisation of its own.  The copy of the input is converted only where it is written at ``fs``.
+    ``activity``: see ``_write_outputs``; with several files the csv of file ``p`` is named ``<csv root>_<basename of p><csv extension>``."""
     from .streambank import separate_many
+
+    def act_of(p):
+        if not activity or len(paths) == 1:
+            return activity
+        root, ext = os.path.splitext(activity["csv"])
+        return {**activity, "csv": f"{root}_{os.path.splitext(os.path.basename(p))[0]}{ext}"}
+
     if not resample:
         loaded = [_load_mixture(model, p, fs, False) for p in paths]
         ests = separate_many(model, [mix for _, mix, _ in loaded], slots=slots, chunk_seconds=chunk_seconds,
                              overlap_seconds=overlap_seconds, fs=fs, match_gain=match_gain)
-        return [_write_outputs(model, p[:-4], file_mix, sr, mix, est, fs, out_rate)
+        return [_write_outputs(model, p[:-4], file_mix, sr, mix, est, fs, out_rate, act_of(p))
                 for p, (file_mix, mix, sr), est in zip(paths, loaded, ests)]
     from .resample import resample as _resample
     files = [(torch.from_numpy(data), sr) for data, sr in map(load_audio, paths)]
@@ -171,7 +190,7 @@ def separate_many_files(model, paths: Sequence[str], fs: int = 8000, slots: int 
     done = []
     for p, (x, sr), est in zip(paths, files, ests):
         at_fs = sr == fs or (fs if out_rate is None else (sr if out_rate == "input" else int(out_rate))) != fs
-        done.append(_write_outputs(model, p[:-4], x, sr, x if at_fs else _resample(x, sr, fs, device=dev), est, fs, out_rate))
+        done.append(_write_outputs(model, p[:-4], x, sr, x if at_fs else _resample(x, sr, fs, device=dev), est, fs, out_rate, act_of(p)))
     return done
 
 
@@ -268,7 +287,9 @@ test_utterances.__test__ = False      # not a pytest test
 
 def evaluate_conversations(model, corpus, convs, method: str = "long", chunk_seconds: float = 4.0, overlap_seconds: float = 1.0,
                            batch: int = 32, slots: int = 32, match_gain: bool = False, csv_path: Optional[str] = None,
-                           wav_dir: Optional[str] = None, fs: int = 8000, rirs=None) -> dict:
+                           wav_dir: Optional[str] = None, fs: int = 8000, rirs=None, idle: bool = False, frame_ms: float = 20.0,
+                           collar_seconds: float = 0.25, ratio_db: float = -40.0, hang_ms: float = 200.0,
+                           idle_csv_path: Optional[str] = None) -> dict:
     """The test loop of the long-form paths: render every conversation of ``convs`` from the resident ``corpus``
     in one launch (``conversation.render``), separate every mixture with ``separate_long`` (``method="long"``) or
     ``streambank.separate_many`` (``"bank"``), score every output channel against every utterance over that utterance's span
@@ -282,12 +303,56 @@ def evaluate_conversations(model, corpus, convs, method: str = "long", chunk_sec
     Conversations in rooms or over a noise bed (section 5h-2; ``rirs``: the ``RirBank`` their segments name) are rendered by
     ``sepr_conversation_render_rooms`` and scored against the direct-path tracks of the talkers only; the bed is in the mixture, hence in
     ``v_mix``.  The scored span of a segment moves with the direct path: ``delay = rirs.direct_taps(0.0)[r] - 1`` (0 without a response),
-    ``begin = min(place + delay, n - 1)``, ``length = max(1, min(len, n - begin))`` - the csv's ``begin`` and ``length``."""
+    ``begin = min(place + delay, n - 1)``, ``length = max(1, min(len, n - begin))`` - the csv's ``begin`` and ``length``.
+
+    ``idle=True`` (section 5h-3) also scores what a channel emits while none of its talkers speaks, and gives the assignment that exists
+    with more talkers than channels.  ``score`` gets the scored spans, so the dict gains ``coloured``, ``graph``, ``sisnri_graph``,
+    ``graph_switch_rate`` and ``bins[*]["sisnri_graph"]``.  The outputs and the mixture are copied into a scratch buffer ``[C + 1][P]`` in
+    which every conversation starts on a frame boundary, zeros behind it (zeros add +0.0: every frame has the bits it has alone); ONE
+    ``frame_energy`` launch covers it, ``activity.activity_of`` runs per conversation on its ``C`` output rows (a conversation is a
+    recording: the level is its own), ``conversation.frame_classes`` classes every frame of every channel from the colouring with a collar
+    of ``collar_seconds``, and ``frame_class_sums`` runs once per conversation into one ``[R][C][4][4]`` tensor - the one further copy to
+    the host.  Per conversation and channel, ``[R][C]``: ``leak_db = 10 log10((sum_cross e_est + eps) / (sum_cross e_mix + eps))``, NaN
+    where class 1 has no frame or no mixture energy, ``quiet_db`` the same over class 2, ``false_alarm`` = active / all frames of the classes
+    1 and 2 together, ``miss`` = inactive / all frames of class 0, ``class_frames [R][C][4]``; ``pooled``: the same four figures from the
+    energies and counts summed over all conversations and channels BEFORE the logarithm or the division.  ``class_sums [R][C][4][4]``
+    (numpy) and ``frames`` - ``frame``, ``collar``, ``hang``, ``offset [R + 1]`` (the first frame of each conversation in ``e``), ``e``
+    ``[C + 1][P / frame]`` (device; the last row the mixture), ``active`` and ``classes`` per conversation (device uint8 ``[C][nF_r]``) -
+    are what the figures were made from.  ``idle_csv_path``: one row per conversation and channel - key, conversation number, channel, the
+    four class counts, ``leak_db``, ``quiet_db``, ``false_alarm``, ``miss``.  With ``idle=False`` nothing of this runs."""
     from . import conversation as cv
     if method not in ("long", "bank"):
         raise ValueError(f"method must be 'long' or 'bank', got {method!r}")
     convs = list(convs)
     rd = cv.render(corpus, convs, tracks=True, rirs=rirs)
+    mixes = [rd.mixture(r) for r in range(len(convs))]
+    if method == "long":
+        ests = separate_long(model, mixes, chunk_seconds=chunk_seconds, overlap_seconds=overlap_seconds, fs=fs, batch=batch,
+                             match_gain=match_gain)
+    else:
+        from .streambank import separate_many
+        ests = separate_many(model, mixes, slots=slots, chunk_seconds=chunk_seconds, overlap_seconds=overlap_seconds, fs=fs,
+                             match_gain=match_gain)
+    C = model.num_spks
+    out = score_conversations(corpus, convs, rd, ests, C, csv_path=csv_path, fs=fs, rirs=rirs, idle=idle, frame_ms=frame_ms,
+                              collar_seconds=collar_seconds, ratio_db=ratio_db, hang_ms=hang_ms, idle_csv_path=idle_csv_path)
+    if wav_dir:
+        os.makedirs(wav_dir, exist_ok=True)
+        for r, conv in enumerate(convs):
+            name = conv.key.replace("/", "_")
+            write_wav(os.path.join(wav_dir, f"{name}{r}_mixture.wav"), peak_normalise(mixes[r].cpu().numpy(), 0.5), fs)
+            for c in range(C):
+                write_wav(os.path.join(wav_dir, f"{name}{r}_out_{c}.wav"), peak_normalise(ests[r][c].cpu().numpy(), 0.5), fs)
+    return out
+
+
+def score_conversations(corpus, convs, rd, ests, C: int, csv_path: Optional[str] = None, fs: int = 8000, rirs=None, idle: bool = False,
+                        frame_ms: float = 20.0, collar_seconds: float = 0.25, ratio_db: float = -40.0, hang_ms: float = 200.0,
+                        idle_csv_path: Optional[str] = None) -> dict:
+    """The scoring half of ``evaluate_conversations``, whose arguments these are: ``rd`` the rendered conversations (``conversation.render``
+    with tracks), ``ests[r]`` the ``C`` output rows ``[n_r]`` of conversation ``r`` on the device, however they were made."""
+    from . import conversation as cv
+    convs = list(convs)
     peak = rirs.direct_taps(0.0) if rirs is not None else None
     spans = []                                                    # per conversation: its talker segments, their scored begin and length
     for conv in convs:
@@ -298,15 +363,6 @@ def evaluate_conversations(model, corpus, convs, method: str = "long", chunk_sec
             delay[wet] = peak[conv.rir[k][wet]] - 1
         begin = np.minimum(conv.place[k].astype(np.int64) + delay, conv.n - 1)
         spans.append((k, begin.astype(np.int32), np.maximum(1, np.minimum(conv.len[k], conv.n - begin)).astype(np.int32)))
-    mixes = [rd.mixture(r) for r in range(len(convs))]
-    if method == "long":
-        ests = separate_long(model, mixes, chunk_seconds=chunk_seconds, overlap_seconds=overlap_seconds, fs=fs, batch=batch,
-                             match_gain=match_gain)
-    else:
-        from .streambank import separate_many
-        ests = separate_many(model, mixes, slots=slots, chunk_seconds=chunk_seconds, overlap_seconds=overlap_seconds, fs=fs,
-                             match_gain=match_gain)
-    C = model.num_spks
     est_all = torch.empty(C, rd.table.total, dtype=torch.float32, device=rd.mix.device)      # the row stride of the tracks: no repacking below
     vs, vms = [], []
     for r, (conv, est) in enumerate(zip(convs, ests)):
@@ -320,8 +376,42 @@ def evaluate_conversations(model, corpus, convs, method: str = "long", chunk_sec
     v, v_mix = torch.cat(vs).cpu().numpy(), torch.cat(vms).cpu().numpy()                      # the one copy of the scores
     conv_of = np.concatenate([np.full(len(k), r) for r, (k, _, _) in enumerate(spans)])
     out = cv.score(v, v_mix, conv_of, np.concatenate([c.track[k] for c, (k, _, _) in zip(convs, spans)]), [c.S for c in convs], C,
-                   overlap=np.concatenate([cv.overlap_fraction(c)[k] for c, (k, _, _) in zip(convs, spans)]))
+                   overlap=np.concatenate([cv.overlap_fraction(c)[k] for c, (k, _, _) in zip(convs, spans)]),
+                   spans=(np.concatenate([b for _, b, _ in spans]), np.concatenate([n for _, _, n in spans])) if idle else None)
     out.update(v=v, v_mix=v_mix, conversations=len(convs))
+    if idle:
+        from . import activity as act
+        frame, hang, collar = act.frame_samples(fs, frame_ms), act.hang_frames(frame_ms, hang_ms), int(round(float(collar_seconds) * fs))
+        offset = np.concatenate([[0], np.cumsum([-(-int(c.n) // frame) for c in convs])]).astype(np.int64)
+        pad = torch.zeros(C + 1, int(offset[-1]) * frame, dtype=torch.float32, device=rd.mix.device)      # conversations on frame boundaries
+        for r, conv in enumerate(convs):
+            a, p = int(rd.out_off[r]), int(offset[r]) * frame
+            pad[:C, p:p + conv.n].copy_(est_all[:, a:a + conv.n])
+            pad[C, p:p + conv.n].copy_(rd.mixture(r))
+        e = act.frame_energy(pad, frame)                                                                  # ONE launch: every row, every frame
+        sums = torch.empty(len(convs), C, 4, 4, dtype=torch.float64, device=e.device)
+        actives, classes, g = [], [], 0
+        for r, (conv, (k, begin, length)) in enumerate(zip(convs, spans)):
+            fa, fb = int(offset[r]), int(offset[r + 1])
+            e_est = e[:C, fa:fb].contiguous()
+            active, _ = act.activity_of(e_est, ratio_db=ratio_db, hang=hang)
+            cls = torch.from_numpy(cv.frame_classes((begin, length), out["coloured"][g:g + len(k)], conv.n, C, frame, collar)).to(e.device)
+            act.frame_class_sums(e_est, e[C, fa:fb], active, cls, out=sums[r])
+            actives.append(active)
+            classes.append(cls)
+            g += len(k)
+        sums_h = sums.cpu().numpy()                                                                       # the one copy of the idle sums
+        out.update(cv.idle_figures(sums_h))
+        pooled = cv.idle_figures(sums_h.reshape(-1, 4, 4).sum(axis=0))                                    # energies and counts first, then the log
+        out.update(class_frames=sums_h[..., 0].astype(np.int64), class_sums=sums_h, pooled={key: float(x) for key, x in pooled.items()},
+                   frames={"frame": frame, "collar": collar, "hang": hang, "offset": offset, "e": e, "active": actives, "classes": classes})
+        if idle_csv_path:
+            with open(idle_csv_path, "w", newline="") as fh:
+                w = csv.writer(fh, quotechar="|", quoting=csv.QUOTE_MINIMAL)
+                for r, conv in enumerate(convs):
+                    for c in range(C):
+                        w.writerow([conv.key, r, c] + [int(x) for x in out["class_frames"][r, c]] +
+                                   [float(out[key][r, c]) for key in ("leak_db", "quiet_db", "false_alarm", "miss")])
     if csv_path:
         with open(csv_path, "w", newline="") as fh:
             w = csv.writer(fh, quotechar="|", quoting=csv.QUOTE_MINIMAL)
@@ -332,13 +422,6 @@ def evaluate_conversations(model, corpus, convs, method: str = "long", chunk_sec
                                 float(out["overlap"][g]), int(out["best"][g]), int(out["assigned"][g]), float(v_mix[g])] +
                                [float(x) for x in v[g]])
                     g += 1
-    if wav_dir:
-        os.makedirs(wav_dir, exist_ok=True)
-        for r, conv in enumerate(convs):
-            name = conv.key.replace("/", "_")
-            write_wav(os.path.join(wav_dir, f"{name}{r}_mixture.wav"), peak_normalise(mixes[r].cpu().numpy(), 0.5), fs)
-            for c in range(C):
-                write_wav(os.path.join(wav_dir, f"{name}{r}_out_{c}.wav"), peak_normalise(ests[r][c].cpu().numpy(), 0.5), fs)
     return out
 
 
@@ -377,7 +460,14 @@ def _main() -> None:
                     help="convert a file at another sampling rate to the model's rate on the device (default: such a file is an error)")
     ap.add_argument("--out-rate", default=None, metavar="{N,input}",
                     help="write the outputs at N Hz, or at the input file's own rate (default: the model's rate)")
+    ap.add_argument("--activity-csv", default=None, metavar="OUT",
+                    help="also write when each separated track carries signal: one row per run of active 20 ms frames - channel, begin s, "
+                         "end s - at the model's rate (several files: OUT gains _<file name> before its extension)")
+    ap.add_argument("--activity-ratio-db", type=float, default=-40.0,
+                    help="--activity-csv: a frame is active above this level relative to the track's loudest frame (a convention, not a tuned value)")
+    ap.add_argument("--activity-hang-ms", type=float, default=200.0, help="--activity-csv: an active frame keeps its neighbours within this time active")
     args = ap.parse_args()
+    activity = {"csv": args.activity_csv, "ratio_db": args.activity_ratio_db, "hang_ms": args.activity_hang_ms} if args.activity_csv else None
     out_rate = args.out_rate if args.out_rate in (None, "input") else int(args.out_rate)
     model = Model.from_config(VARIANTS[args.model], init_seed=0)
     if args.ema and not args.checkpoint:
@@ -396,13 +486,13 @@ def _main() -> None:
         done = separate_many_files(model, args.wav, slots=32 if args.slots is None else args.slots,
                                    chunk_seconds=4.0 if args.chunk_seconds is None else args.chunk_seconds,
                                    overlap_seconds=args.overlap_seconds, match_gain=args.match_gain, resample=args.resample,
-                                   out_rate=out_rate)
+                                   out_rate=out_rate, activity=activity)
         written = [w for _, ws in done for w in ws]
     elif args.chunk_seconds is None:
-        _, written = separate_file(model, args.wav[0], resample=args.resample, out_rate=out_rate)
+        _, written = separate_file(model, args.wav[0], resample=args.resample, out_rate=out_rate, activity=activity)
     else:
         _, written = separate_long_file(model, args.wav[0], chunk_seconds=args.chunk_seconds, overlap_seconds=args.overlap_seconds,
-                                        match_gain=args.match_gain, batch=args.batch, resample=args.resample, out_rate=out_rate)
+                                        match_gain=args.match_gain, batch=args.batch, resample=args.resample, out_rate=out_rate, activity=activity)
     print("\n".join(written))
 
 

@@ -189,6 +189,11 @@ SIGNATURES = {
                                             _fp, _fp, _fp, _ll, _fp, _i, _fp]),
     "sepr_segment_sisnr_bytes": (_ll, [_i, _i]),
     "sepr_segment_sisnr_fwd": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _ll, _d, _fp, _fp, _fp, _sz, _fp]),
+    "sepr_frame_energy_fwd": (_i, [_fp, _i, _ll, _ll, _i, _fp, _fp]),
+    "sepr_frame_activity_bytes": (_ll, [_i, _i]),
+    "sepr_frame_activity_fwd": (_i, [_fp, _i, _i, _d, _d, _i, _fp, _fp, _fp, _sz, _fp]),
+    "sepr_frame_class_sums_bytes": (_ll, [_i, _i]),
+    "sepr_frame_class_sums_fwd": (_i, [_fp, _fp, _fp, _fp, _i, _i, _fp, _fp, _sz, _fp]),
     "sepr_graph_pit_bytes": (_ll, [_i, _i, _i]),
     "sepr_graph_pit_assign": (_i, [C.POINTER(_fp), C.POINTER(_fp), _fp, _fp, _i, _i, _i, _i, _d, _d, _fp, _fp, _fp, _fp, _sz, _fp]),
     "sepr_graph_pit_assemble": (_i, [C.POINTER(_fp), _fp, _fp, _i, _i, _i, _i, C.POINTER(_fp), _fp]),

@@ -13,6 +13,12 @@ Rooms and noise (section 5h-2), for the models trained on reverberant or noisy m
 own voice; ``--noise-role`` lays the utterances of that role end to end under the whole conversation.
 
     python tools/eval_conversations.py --scp s1=tt_s1.scp s2=tt_s2.scp noise=tt_noise.scp --noise-role noise --room-rirs 64:0.2:0.6 --model SepReformer_Large_DM_WHAMR
+
+Idle channels (section 5h-3): ``--idle`` adds the colouring-based assignment, which exists with more talkers than channels too, and what a channel
+emits in the frames none of its talkers owns - the pooled leak over the other talkers' frames, over quiet frames, the false-alarm and the miss rate
+of the activity detector.
+
+    python tools/eval_conversations.py --scp s1=tt_s1.scp s2=tt_s2.scp --speakers 3 --max-active 2 --idle --idle-csv idle.csv
 """
 import argparse
 import json
@@ -37,7 +43,7 @@ def main():
     ap.add_argument("--scp", nargs="+", required=True, metavar="ROLE=FILE", help="utterance lists, one role per talker position: s1=... s2=...")
     ap.add_argument("--count", type=int, default=20, help="conversations")
     ap.add_argument("--minutes", type=float, default=10.0, help="length of each conversation")
-    ap.add_argument("--speakers", type=int, default=2, help="talker tracks per conversation (more than the model's channels: no assignment scores)")
+    ap.add_argument("--speakers", type=int, default=2, help="talker tracks per conversation (more than the model's channels: score them with --idle)")
     ap.add_argument("--overlap", default="0:0.4", metavar="LO:HI", help="overlap of a turn with the one before, as a share of the shorter utterance")
     ap.add_argument("--pause", default="0:1", metavar="LO:HI", help="seconds between turns that do not overlap")
     ap.add_argument("--p-overlap", type=float, default=0.5, help="probability that a turn overlaps the one before")
@@ -70,7 +76,14 @@ def main():
     ap.add_argument("--seed", type=int, default=0, help="seed of the synthetic or simulated rooms")
     ap.add_argument("--csv", default=None, help="one row per utterance of every conversation")
     ap.add_argument("--wav-dir", default=None, help="write every mixture and every output channel")
+    ap.add_argument("--idle", action="store_true", help="also score idle channels (DESIGN.md section 5h-3): the colouring-based assignment that "
+                    "exists for any number of talkers, and what a channel emits in the frames none of its talkers owns")
+    ap.add_argument("--collar", type=float, default=0.25, help="--idle: seconds around a channel's own utterances that count as neither own nor idle")
+    ap.add_argument("--frame-ms", type=float, default=20.0, help="--idle: the frame of the activity measure")
+    ap.add_argument("--idle-csv", default=None, help="--idle: one row per conversation and channel")
     args = ap.parse_args()
+    if args.idle_csv and not args.idle:
+        ap.error("--idle-csv needs --idle")
     if args.ema and not args.checkpoint:
         ap.error("--ema needs --checkpoint")
     scps = {}
@@ -113,9 +126,13 @@ def main():
                                   noise=args.noise_role, noise_db=_range(args.noise_db, "--noise-db")) for i in range(args.count)]
     out = infer.evaluate_conversations(model, corpus, convs, method=args.method, chunk_seconds=args.chunk_seconds,
                                        overlap_seconds=args.overlap_seconds, batch=args.batch, slots=args.slots, match_gain=args.match_gain,
-                                       csv_path=args.csv, wav_dir=args.wav_dir, fs=args.fs, rirs=bank)
-    print(json.dumps({"method": args.method, "conversations": out["conversations"], "utterances": out["n"], "sisnri_utt": out["sisnri_utt"],
-                      "sisnri_cons": out["sisnri_cons"], "switch_rate": out["switch_rate"], "bins": out["bins"]}))
+                                       csv_path=args.csv, wav_dir=args.wav_dir, fs=args.fs, rirs=bank, idle=args.idle, frame_ms=args.frame_ms,
+                                       collar_seconds=args.collar, idle_csv_path=args.idle_csv)
+    summary = {"method": args.method, "conversations": out["conversations"], "utterances": out["n"], "sisnri_utt": out["sisnri_utt"],
+               "sisnri_cons": out["sisnri_cons"], "switch_rate": out["switch_rate"], "bins": out["bins"]}
+    if args.idle:
+        summary.update(sisnri_graph=out["sisnri_graph"], graph_switch_rate=out["graph_switch_rate"], **out["pooled"])
+    print(json.dumps(summary))
 
 
 if __name__ == "__main__":
