@@ -48,112 +48,63 @@ def _stack_g(x: _TensorList) -> torch.Tensor:
     return t.to(torch.float32).contiguous()
 
 
-class _PitTimeFn(torch.autograd.Function):
-    """sum_b w_b * loss_b of PIT_SISNR_time with d/d est from sepr_pit_sisnr_bwd (criterions.py:191-217)."""
+def _pit_time_bytes(lib, S: int, B: int, T: int) -> int:
+    return lib.sepr_workspace_bytes(L.OP_PIT, B, T, 0, 0, 0, S)
 
-    @staticmethod
-    def forward(ctx, est, tgt, eps, clamp_min):
-        out = pit_sisnr(est, tgt, eps_loss=eps, clamp_min=clamp_min)
-        ctx.save_for_backward(est, tgt, out["loss_perm"])
-        ctx.consts = (eps, clamp_min)
+
+def _pit_time_bwd_bytes(lib, S: int, B: int, T: int, *_) -> int:
+    """Workspace of ``sepr_pit_sisnr_bwd`` / ``sepr_pit_sasdr_bwd``.  Mirrors ``PitWs(..., bwd = true)`` of csrc/sepr_criterion.hip: the forward's
+    partial moments, then four float32 coefficients per (utterance, source), and room for the alignment of the two."""
+    return _pit_time_bytes(lib, S, B, T) + 16 * B * S + 512
+
+
+def _mag_bwd_bytes(lib, S: int, B: int, T: int, frame_len: int, frame_shift: int, *_) -> int:
+    return lib.sepr_pit_sisnr_mag_bwd_workspace(S, B, T, frame_len, frame_shift)
+
+
+def _pit_function(name: str, doc: str, forward, perm_key: str, bwd_entry: str, bwd_bytes):
+    """The autograd Function of one training criterion: ``apply(est, tgt, *consts)`` -> per-utterance loss ``[B]``, with ``consts`` the
+    criterion's constant tensors (the DFT kernels) followed by its scalars.  ``forward(est, tgt, *consts)`` is the functional wrapper's dict,
+    whose ``perm_key`` is held fixed in the backward; the backward is the C entry ``bwd_entry(est, tgt, perm, gl, S, B, T, *consts, dest, ws,
+    ws_bytes, stream)`` on a workspace of ``bwd_bytes(lib, S, B, T, *scalars)`` bytes."""
+
+    def fwd(ctx, est, tgt, *consts):
+        out = forward(est, tgt, *consts)
+        ctx.save_for_backward(est, tgt, out[perm_key], *(c for c in consts if isinstance(c, torch.Tensor)))
+        ctx.scalars = tuple(c for c in consts if not isinstance(c, torch.Tensor))
         return out["loss"]
 
-    @staticmethod
-    def backward(ctx, gl):
-        est, tgt, perm = ctx.saved_tensors
-        eps, clamp_min = ctx.consts
+    def bwd(ctx, gl):
+        est, tgt, perm, *tensors = ctx.saved_tensors
         S, B, T = est.shape
         lib = L.load()
         with torch.cuda.device(est.device):
-            nbytes = lib.sepr_workspace_bytes(L.OP_PIT, B, T, 0, 0, 0, S) + 16 * B * S + 512
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=est.device)
+            ws = torch.empty(bwd_bytes(lib, S, B, T, *ctx.scalars), dtype=torch.uint8, device=est.device)
             dest = torch.empty_like(est)
             glc = gl.detach().to(torch.float32).contiguous()
-            L.check(lib.sepr_pit_sisnr_bwd(est.data_ptr(), tgt.data_ptr(), perm.data_ptr(), glc.data_ptr(), S, B, T, eps, clamp_min,
-                                           dest.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(est.device).cuda_stream),
-                    "sepr_pit_sisnr_bwd")
-        return dest, None, None, None
+            L.check(getattr(lib, bwd_entry)(est.data_ptr(), tgt.data_ptr(), perm.data_ptr(), glc.data_ptr(), S, B, T,
+                                            *(t.data_ptr() for t in tensors), *ctx.scalars, dest.data_ptr(), ws.data_ptr(), ws.numel(),
+                                            torch.cuda.current_stream(est.device).cuda_stream), bwd_entry)
+        return (dest,) + (None,) * (1 + len(tensors) + len(ctx.scalars))
+
+    return type(name, (torch.autograd.Function,), {"__doc__": doc, "__module__": __name__, "forward": staticmethod(fwd),
+                                                   "backward": staticmethod(bwd)})
 
 
-class _PitMagFn(torch.autograd.Function):
-    """Per-utterance PIT_SISNR_mag loss with d/d est from sepr_pit_sisnr_mag_bwd (criterions.py:148-176)."""
-
-    @staticmethod
-    def forward(ctx, est, tgt, dft, dft_t, frame_len, frame_shift, eps):
-        out = pit_sisnr_mag(est, tgt, dft, frame_len, frame_shift, eps)
-        ctx.save_for_backward(est, tgt, out["perm"], dft, dft_t)
-        ctx.consts = (frame_len, frame_shift, eps)
-        return out["loss"]
-
-    @staticmethod
-    def backward(ctx, gl):
-        est, tgt, perm, dft, dft_t = ctx.saved_tensors
-        frame_len, frame_shift, eps = ctx.consts
-        S, B, T = est.shape
-        lib = L.load()
-        with torch.cuda.device(est.device):
-            nbytes = lib.sepr_pit_sisnr_mag_bwd_workspace(S, B, T, frame_len, frame_shift)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=est.device)
-            dest = torch.empty_like(est)
-            glc = gl.detach().to(torch.float32).contiguous()
-            L.check(lib.sepr_pit_sisnr_mag_bwd(est.data_ptr(), tgt.data_ptr(), perm.data_ptr(), glc.data_ptr(), S, B, T, dft.data_ptr(),
-                                               dft_t.data_ptr(), frame_len, frame_shift, eps, dest.data_ptr(), ws.data_ptr(), ws.numel(),
-                                               torch.cuda.current_stream(est.device).cuda_stream), "sepr_pit_sisnr_mag_bwd")
-        return dest, None, None, None, None, None, None
-
-
-class _SaSdrTimeFn(torch.autograd.Function):
-    """Per-utterance PIT_SASDR_time loss with d/d est from sepr_pit_sasdr_bwd."""
-
-    @staticmethod
-    def forward(ctx, est, tgt, eps, snr_max):
-        out = pit_sasdr(est, tgt, eps=eps, snr_max=snr_max)
-        ctx.save_for_backward(est, tgt, out["perm"])
-        ctx.consts = (eps, snr_max)
-        return out["loss"]
-
-    @staticmethod
-    def backward(ctx, gl):
-        est, tgt, perm = ctx.saved_tensors
-        eps, snr_max = ctx.consts
-        S, B, T = est.shape
-        lib = L.load()
-        with torch.cuda.device(est.device):
-            nbytes = lib.sepr_workspace_bytes(L.OP_PIT, B, T, 0, 0, 0, S) + 16 * B * S + 512     # sepr_pit_sisnr_bwd's layout
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=est.device)
-            dest = torch.empty_like(est)
-            glc = gl.detach().to(torch.float32).contiguous()
-            L.check(lib.sepr_pit_sasdr_bwd(est.data_ptr(), tgt.data_ptr(), perm.data_ptr(), glc.data_ptr(), S, B, T, eps, snr_max,
-                                           dest.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(est.device).cuda_stream),
-                    "sepr_pit_sasdr_bwd")
-        return dest, None, None, None
-
-
-class _SaSdrMagFn(torch.autograd.Function):
-    """Per-utterance PIT_SASDR_mag loss with d/d est from sepr_pit_sasdr_mag_bwd."""
-
-    @staticmethod
-    def forward(ctx, est, tgt, dft, dft_t, frame_len, frame_shift, eps, snr_max):
-        out = pit_sasdr_mag(est, tgt, dft, frame_len, frame_shift, eps, snr_max)
-        ctx.save_for_backward(est, tgt, out["perm"], dft, dft_t)
-        ctx.consts = (frame_len, frame_shift, eps, snr_max)
-        return out["loss"]
-
-    @staticmethod
-    def backward(ctx, gl):
-        est, tgt, perm, dft, dft_t = ctx.saved_tensors
-        frame_len, frame_shift, eps, snr_max = ctx.consts
-        S, B, T = est.shape
-        lib = L.load()
-        with torch.cuda.device(est.device):
-            nbytes = lib.sepr_pit_sisnr_mag_bwd_workspace(S, B, T, frame_len, frame_shift)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=est.device)
-            dest = torch.empty_like(est)
-            glc = gl.detach().to(torch.float32).contiguous()
-            L.check(lib.sepr_pit_sasdr_mag_bwd(est.data_ptr(), tgt.data_ptr(), perm.data_ptr(), glc.data_ptr(), S, B, T, dft.data_ptr(),
-                                               dft_t.data_ptr(), frame_len, frame_shift, eps, snr_max, dest.data_ptr(), ws.data_ptr(),
-                                               ws.numel(), torch.cuda.current_stream(est.device).cuda_stream), "sepr_pit_sasdr_mag_bwd")
-        return dest, None, None, None, None, None, None, None
+_PitTimeFn = _pit_function(
+    "_PitTimeFn", "sum_b w_b * loss_b of PIT_SISNR_time with d/d est from sepr_pit_sisnr_bwd (criterions.py:191-217): apply(est, tgt, eps, clamp_min).",
+    lambda est, tgt, eps, clamp_min: pit_sisnr(est, tgt, eps_loss=eps, clamp_min=clamp_min), "loss_perm", "sepr_pit_sisnr_bwd", _pit_time_bwd_bytes)
+_PitMagFn = _pit_function(
+    "_PitMagFn", "Per-utterance PIT_SISNR_mag loss with d/d est from sepr_pit_sisnr_mag_bwd (criterions.py:148-176): "
+    "apply(est, tgt, dft, dft_t, frame_len, frame_shift, eps).",
+    lambda est, tgt, dft, dft_t, *c: pit_sisnr_mag(est, tgt, dft, *c), "perm", "sepr_pit_sisnr_mag_bwd", _mag_bwd_bytes)
+_SaSdrTimeFn = _pit_function(
+    "_SaSdrTimeFn", "Per-utterance PIT_SASDR_time loss with d/d est from sepr_pit_sasdr_bwd (DESIGN.md section 5e-7): apply(est, tgt, eps, snr_max).",
+    lambda est, tgt, eps, snr_max: pit_sasdr(est, tgt, eps=eps, snr_max=snr_max), "perm", "sepr_pit_sasdr_bwd", _pit_time_bwd_bytes)
+_SaSdrMagFn = _pit_function(
+    "_SaSdrMagFn", "Per-utterance PIT_SASDR_mag loss with d/d est from sepr_pit_sasdr_mag_bwd (DESIGN.md section 5e-7): "
+    "apply(est, tgt, dft, dft_t, frame_len, frame_shift, eps, snr_max).",
+    lambda est, tgt, dft, dft_t, *c: pit_sasdr_mag(est, tgt, dft, *c), "perm", "sepr_pit_sasdr_mag_bwd", _mag_bwd_bytes)
 
 
 def _stack(x: _TensorList, what: str) -> torch.Tensor:
@@ -165,10 +116,11 @@ def _stack(x: _TensorList, what: str) -> torch.Tensor:
     return t.detach().to(torch.float32).contiguous()
 
 
-def pit_sisnr(estims: _TensorList, targets: _TensorList, mixture: torch.Tensor = None, eps_loss: float = 1.0e-8,
-              eps_i: float = 1.0e-15, clamp_min: float = -30.0):
-    """One launch pair over ``[S,B,T]`` estimates / targets.  Returns a dict with ``loss`` ``[B]`` (PIT_SISNR_time per
-    utterance), ``loss_perm`` ``[B,S]`` and, when ``mixture`` is given, ``sisnri`` ``[B,S]`` / ``sisnri_perm`` ``[B,S]``."""
+def _pit_call(entry: str, what: str, estims: _TensorList, targets: _TensorList, nbytes, consts: tuple, takes_mix: bool = False, mixture=None):
+    """One forward entry over ``[S,B,T]`` estimates / targets: ``entry(est, tgt, [mix,] S, B, T, *consts, loss, perm, [sisnri, sisnri_perm,]
+    ws, ws_bytes, stream)`` on a workspace of ``nbytes(lib, S, B, T)`` bytes (0: the problem is not supported); the bracketed arguments are those
+    of an entry that ``takes_mix``, null without a ``mixture`` ``[B,T]``.  Returns ``(loss [B], perm [B,S], sisnri, sisnri_perm)``,
+    the last two ``None`` without a mixture."""
     est, tgt = _stack(estims, "estims"), _stack(targets, "target_attr")
     if est.shape != tgt.shape:
         raise RuntimeError(f"estims {tuple(est.shape)} and targets {tuple(tgt.shape)} differ")
@@ -179,21 +131,29 @@ def pit_sisnr(estims: _TensorList, targets: _TensorList, mixture: torch.Tensor =
         mix = mixture.detach().to(torch.float32).contiguous()
         if tuple(mix.shape) != (B, T) or mix.device != dev:
             raise RuntimeError("mixture must be [batch, samples] on the same device as the estimates")
+    ptr = lambda t: None if t is None else t.data_ptr()
     lib = L.load()
     with torch.cuda.device(dev):
-        nbytes = lib.sepr_workspace_bytes(L.OP_PIT, B, T, 0, 0, 0, S)
-        if nbytes == 0:
-            raise RuntimeError(f"unsupported PIT problem: num_spks={S}, batch={B}, samples={T}")
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        n = nbytes(lib, S, B, T)
+        if n == 0:
+            raise RuntimeError(f"unsupported {what} problem: num_spks={S}, batch={B}, samples={T}")
+        ws = torch.empty(n, dtype=torch.uint8, device=dev)
         loss = torch.empty(B, dtype=torch.float32, device=dev)
-        loss_perm = torch.empty(B, S, dtype=torch.int32, device=dev)
+        perm = torch.empty(B, S, dtype=torch.int32, device=dev)
         sisnri = torch.empty(B, S, dtype=torch.float32, device=dev) if mix is not None else None
         sisnri_perm = torch.empty(B, S, dtype=torch.int32, device=dev) if mix is not None else None
-        L.check(lib.sepr_pit_sisnr_fwd(
-            est.data_ptr(), tgt.data_ptr(), None if mix is None else mix.data_ptr(), S, B, T, eps_loss, eps_i, clamp_min,
-            loss.data_ptr(), loss_perm.data_ptr(), None if sisnri is None else sisnri.data_ptr(),
-            None if sisnri_perm is None else sisnri_perm.data_ptr(), ws.data_ptr(), ws.numel(),
-            torch.cuda.current_stream(dev).cuda_stream), "sepr_pit_sisnr_fwd")
+        L.check(getattr(lib, entry)(est.data_ptr(), tgt.data_ptr(), *((ptr(mix),) if takes_mix else ()), S, B, T, *consts, loss.data_ptr(),
+                                    perm.data_ptr(), *((ptr(sisnri), ptr(sisnri_perm)) if takes_mix else ()), ws.data_ptr(), ws.numel(),
+                                    torch.cuda.current_stream(dev).cuda_stream), entry)
+    return loss, perm, sisnri, sisnri_perm
+
+
+def pit_sisnr(estims: _TensorList, targets: _TensorList, mixture: torch.Tensor = None, eps_loss: float = 1.0e-8,
+              eps_i: float = 1.0e-15, clamp_min: float = -30.0):
+    """One launch pair over ``[S,B,T]`` estimates / targets.  Returns a dict with ``loss`` ``[B]`` (PIT_SISNR_time per
+    utterance), ``loss_perm`` ``[B,S]`` and, when ``mixture`` is given, ``sisnri`` ``[B,S]`` / ``sisnri_perm`` ``[B,S]``."""
+    loss, loss_perm, sisnri, sisnri_perm = _pit_call("sepr_pit_sisnr_fwd", "PIT", estims, targets, _pit_time_bytes,
+                                                     (eps_loss, eps_i, clamp_min), takes_mix=True, mixture=mixture)
     return {"loss": loss, "loss_perm": loss_perm, "sisnri": sisnri, "sisnri_perm": sisnri_perm}
 
 
@@ -218,26 +178,16 @@ def stft_kernel(frame_len: int, frame_hop: int, window: str = "hann") -> torch.T
     return torch.cat([K, torch.zeros(pad, frame_len)], 0).to(torch.float32).contiguous()
 
 
+def _mag_bytes(frame_len: int, frame_shift: int):
+    return lambda lib, S, B, T: lib.sepr_pit_sisnr_mag_workspace(S, B, T, frame_len, frame_shift)
+
+
 def pit_sisnr_mag(estims: _TensorList, targets: _TensorList, dft: torch.Tensor, frame_len: int, frame_shift: int,
                   eps: float = 1.0e-12):
     """Per-utterance PIT_SISNR_mag loss ``[B]`` and its permutation ``[B,S]`` (one moment pass, one f32-MFMA STFT
     projection over all 2S waveforms, one pair-sum pass)."""
-    est, tgt = _stack(estims, "estims"), _stack(targets, "target_attr")
-    if est.shape != tgt.shape:
-        raise RuntimeError(f"estims {tuple(est.shape)} and targets {tuple(tgt.shape)} differ")
-    S, B, T = est.shape
-    dev = est.device
-    lib = L.load()
-    with torch.cuda.device(dev):
-        nbytes = lib.sepr_pit_sisnr_mag_workspace(S, B, T, frame_len, frame_shift)
-        if nbytes == 0:
-            raise RuntimeError(f"unsupported PIT_SISNR_mag problem: num_spks={S}, batch={B}, samples={T}")
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        loss = torch.empty(B, dtype=torch.float32, device=dev)
-        perm = torch.empty(B, S, dtype=torch.int32, device=dev)
-        L.check(lib.sepr_pit_sisnr_mag_fwd(est.data_ptr(), tgt.data_ptr(), S, B, T, dft.data_ptr(), frame_len, frame_shift, eps,
-                                           loss.data_ptr(), perm.data_ptr(), ws.data_ptr(), ws.numel(),
-                                           torch.cuda.current_stream(dev).cuda_stream), "sepr_pit_sisnr_mag_fwd")
+    loss, perm, _, _ = _pit_call("sepr_pit_sisnr_mag_fwd", "PIT_SISNR_mag", estims, targets, _mag_bytes(frame_len, frame_shift),
+                                 (dft.data_ptr(), frame_len, frame_shift, eps))
     return {"loss": loss, "perm": perm}
 
 
@@ -245,21 +195,7 @@ def pit_sasdr(estims: _TensorList, targets: _TensorList, eps: float = 1.0e-8, sn
     """Source-aggregated, soft-thresholded SDR over ``[S,B,T]`` estimates / targets: ``loss`` ``[B]`` =
     ``min_p 10 log10((E_p + tau D + eps) / (D + eps))`` and ``perm`` ``[B,S]``, the first minimiser of ``E_p``.  Defined for silent targets.
     ``sepr_pit_sasdr_fwd``: the moment pass of ``pit_sisnr`` and one finalising launch."""
-    est, tgt = _stack(estims, "estims"), _stack(targets, "target_attr")
-    if est.shape != tgt.shape:
-        raise RuntimeError(f"estims {tuple(est.shape)} and targets {tuple(tgt.shape)} differ")
-    S, B, T = est.shape
-    dev = est.device
-    lib = L.load()
-    with torch.cuda.device(dev):
-        nbytes = lib.sepr_workspace_bytes(L.OP_PIT, B, T, 0, 0, 0, S)
-        if nbytes == 0:
-            raise RuntimeError(f"unsupported PIT problem: num_spks={S}, batch={B}, samples={T}")
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        loss = torch.empty(B, dtype=torch.float32, device=dev)
-        perm = torch.empty(B, S, dtype=torch.int32, device=dev)
-        L.check(lib.sepr_pit_sasdr_fwd(est.data_ptr(), tgt.data_ptr(), S, B, T, eps, snr_max, loss.data_ptr(), perm.data_ptr(),
-                                       ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream), "sepr_pit_sasdr_fwd")
+    loss, perm, _, _ = _pit_call("sepr_pit_sasdr_fwd", "PIT", estims, targets, _pit_time_bytes, (eps, snr_max))
     return {"loss": loss, "perm": perm}
 
 
@@ -267,22 +203,8 @@ def pit_sasdr_mag(estims: _TensorList, targets: _TensorList, dft: torch.Tensor, 
                   eps: float = 1.0e-12, snr_max: float = 30.0):
     """``pit_sasdr`` on the STFT magnitudes of the zero-mean signals (the projection and the pair sums of ``pit_sisnr_mag`` with unit
     target scales): ``loss`` ``[B]`` and ``perm`` ``[B,S]``.  ``sepr_pit_sasdr_mag_fwd``."""
-    est, tgt = _stack(estims, "estims"), _stack(targets, "target_attr")
-    if est.shape != tgt.shape:
-        raise RuntimeError(f"estims {tuple(est.shape)} and targets {tuple(tgt.shape)} differ")
-    S, B, T = est.shape
-    dev = est.device
-    lib = L.load()
-    with torch.cuda.device(dev):
-        nbytes = lib.sepr_pit_sisnr_mag_workspace(S, B, T, frame_len, frame_shift)
-        if nbytes == 0:
-            raise RuntimeError(f"unsupported PIT_SASDR_mag problem: num_spks={S}, batch={B}, samples={T}")
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        loss = torch.empty(B, dtype=torch.float32, device=dev)
-        perm = torch.empty(B, S, dtype=torch.int32, device=dev)
-        L.check(lib.sepr_pit_sasdr_mag_fwd(est.data_ptr(), tgt.data_ptr(), S, B, T, dft.data_ptr(), frame_len, frame_shift, eps, snr_max,
-                                           loss.data_ptr(), perm.data_ptr(), ws.data_ptr(), ws.numel(),
-                                           torch.cuda.current_stream(dev).cuda_stream), "sepr_pit_sasdr_mag_fwd")
+    loss, perm, _, _ = _pit_call("sepr_pit_sasdr_mag_fwd", "PIT_SASDR_mag", estims, targets, _mag_bytes(frame_len, frame_shift),
+                                 (dft.data_ptr(), frame_len, frame_shift, eps, snr_max))
     return {"loss": loss, "perm": perm}
 
 

@@ -212,15 +212,6 @@ __global__ __launch_bounds__(256) void bss_update_kernel(double* __restrict__ ma
     for (int c = 0; c < 4; ++c) A[(i0 + tr + a) * n + j0 + tc + c] -= acc[a][c];
 }
 
-__device__ __forceinline__ double bss_block_sum(double v, double* red) {
-  // 256 threads -> one value, fixed order (wave butterfly, then the four wave sums in wave order)
-  v = wave_sum_d(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
 __device__ __forceinline__ double bss_db(double num, double den) {
   den = den > 0.0 ? den : 0.0;                                    // rounding may leave a tiny negative residual
   return den == 0.0 ? __builtin_huge_val() : 10.0 * log10(num / den);         // mir_eval _safe_db: a zero denominator is +inf
@@ -245,19 +236,19 @@ __global__ __launch_bounds__(256) void bss_crit_kernel(const float* __restrict__
     const float* x = r < S ? est + ((long long)r * B + b) * T : mix + (long long)b * T;
     double s = 0.0;
     for (int t = tid; t < L; t += 256) s = fma((double)x[t], (double)x[t], s);
-    E[r] = bss_block_sum(s, red);
+    E[r] = block_sum_d(s, red);
     const double* y = bss_mat(mats, S, b, 0) + (long long)(nj + r) * nj;
     double s0 = 0.0, s1 = 0.0;
     for (int c = tid; c < BSS_F; c += 256) s0 = fma(y[c], y[c], s0);
     for (int c = BSS_F + tid; c < nj; c += 256) s1 = fma(y[c], y[c], s1);
-    P[r][0] = bss_block_sum(s0, red);
-    Pall[r] = P[r][0] + bss_block_sum(s1, red);
+    P[r][0] = block_sum_d(s0, red);
+    Pall[r] = P[r][0] + block_sum_d(s1, red);
 #pragma unroll
     for (int j = 1; j < S; ++j) {
       const double* yj = bss_mat(mats, S, b, j) + (long long)(BSS_F + r) * BSS_F;
       double sj = 0.0;
       for (int c = tid; c < BSS_F; c += 256) sj = fma(yj[c], yj[c], sj);
-      P[r][j] = bss_block_sum(sj, red);
+      P[r][j] = block_sum_d(sj, red);
     }
   }
   if (tid != 0) return;
@@ -281,36 +272,28 @@ __global__ __launch_bounds__(256) void bss_crit_kernel(const float* __restrict__
     }
   }
   // itertools.permutations(range(S)) order; the first maximiser of mean_k SIR[popt[k], k] (np.argmax over np.mean)
-  constexpr int NPERM = S == 2 ? 2 : 6;
-  constexpr int PERMS[6][3] = {{0, 1, 2}, {0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 0, 1}, {2, 1, 0}};
-  constexpr int PERMS2[2][3] = {{0, 1, 0}, {1, 0, 0}};
-  double best = 0.0, osdr[S], osir[S], osar[S];
-  int oper[S];
-#pragma unroll
-  for (int p = 0; p < NPERM; ++p) {
+  double best;
+  const int popt = pit_walk_max<S>([&](int p) {
     double s = 0.0;
 #pragma unroll
-    for (int k = 0; k < S; ++k) s += vsir[S == 2 ? PERMS2[p][k] : PERMS[p][k]][k];
-    s /= S;
-    if (p == 0 || s > best) {
-      best = s;
-#pragma unroll
-      for (int k = 0; k < S; ++k) {
-        const int e = S == 2 ? PERMS2[p][k] : PERMS[p][k];
-        osdr[k] = vsdr[e][k];
-        osir[k] = vsir[e][k];
-        osar[k] = vsar[e];
-        oper[k] = e;
-      }
-    }
-  }
+    for (int k = 0; k < S; ++k) s += vsir[perm_at<S>(p, k)][k];
+    return s / S;
+  }, best);
   const double nan = __longlong_as_double(0x7ff8000000000000ll);
 #pragma unroll
   for (int k = 0; k < S; ++k) {
-    sdr[b * S + k] = st ? nan : osdr[k];
-    sir[b * S + k] = st ? nan : osir[k];
-    sar[b * S + k] = st ? nan : osar[k];
-    perm[b * S + k] = oper[k];
+    const int e = perm_at<S>(popt, k);
+    double osdr = vsdr[0][k], osir = vsir[0][k], osar = vsar[0];
+#pragma unroll
+    for (int r = 1; r < S; ++r) {                                 // row e by selects over constant indices: the tables stay in registers
+      osdr = r == e ? vsdr[r][k] : osdr;
+      osir = r == e ? vsir[r][k] : osir;
+      osar = r == e ? vsar[r] : osar;
+    }
+    sdr[b * S + k] = st ? nan : osdr;
+    sir[b * S + k] = st ? nan : osir;
+    sar[b * S + k] = st ? nan : osar;
+    perm[b * S + k] = e;
     if (sdr_mix) sdr_mix[b * S + k] = st ? nan : vsdr[S][k];     // identical rows: every SIR ties, popt = identity
   }
 }

@@ -161,6 +161,54 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+// One value per thread of a 256-thread workgroup -> their sum in a fixed order (wave butterfly, then the four wave sums in wave order); every
+// thread gets it.  red: 4 doubles of LDS.  Two barriers - the first lets the readers of the sum before finish with red - so every thread of
+// the workgroup must arrive: call it in workgroup-uniform control flow only.
+__device__ __forceinline__ double block_sum_d(double v, double* red) {
+  v = wave_sum_d(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// ---- the permutations of range(S), S <= 3, in lexicographic order = itertools.permutations(range(S)) --------------------------------------
+//   S = 1: 0;  S = 2: 01 10;  S = 3: 012 021 102 120 201 210
+template <int S>
+__host__ __device__ constexpr int perm_count() {
+  static_assert(S >= 1 && S <= 3, "perm_at is written out for S <= 3");
+  return S == 1 ? 1 : (S == 2 ? 2 : 6);
+}
+// pi(i) of permutation p
+template <int S>
+__host__ __device__ constexpr int perm_at(int p, int i) {
+  static_assert(S >= 1 && S <= 3, "perm_at is written out for S <= 3");
+  if (S == 1) return 0;
+  if (S == 2) return i == 0 ? p : 1 - p;
+  const int first = p >> 1, lo = first == 0 ? 1 : 0, hi = first == 2 ? 1 : 2;
+  return i == 0 ? first : (i == 1 ? ((p & 1) ? hi : lo) : ((p & 1) ? lo : hi));
+}
+// The walk over them: cost(p) for p = 0, 1, ... in turn; the first optimum wins (p == 0 or strictly better than the best so far: the
+// semantics of torch.min / torch.max / np.argmax).  Returns its index, its cost in `best`.
+template <int S, class Cost, class Better>
+__device__ __forceinline__ int pit_walk(Cost cost, Better better, double& best) {
+  int arg = 0;
+  best = 0.0;
+#pragma unroll
+  for (int p = 0; p < perm_count<S>(); ++p) {
+    const double c = cost(p);
+    if (p == 0 || better(c, best)) { best = c; arg = p; }
+  }
+  return arg;
+}
+template <int S, class Cost>
+__device__ __forceinline__ int pit_walk_min(Cost cost, double& best) {
+  return pit_walk<S>(cost, [](double c, double b) { return c < b; }, best);
+}
+template <int S, class Cost>
+__device__ __forceinline__ int pit_walk_max(Cost cost, double& best) {
+  return pit_walk<S>(cost, [](double c, double b) { return c > b; }, best);
+}
 
 // ---- dropout generator pieces shared by the training kernels and the projection epilogues (documented in sepr_train.h) ----
 __device__ __forceinline__ unsigned long long sepr_mix64(unsigned long long z) {

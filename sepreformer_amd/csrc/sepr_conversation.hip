@@ -429,15 +429,6 @@ __device__ __forceinline__ SnSeg sn_segment(const float* __restrict__ ref, const
   return {ref + (long long)row * ld + b, b, n};
 }
 
-// the sum of one value per thread over the workgroup, in a fixed order; every thread gets it.  Two barriers.
-__device__ __forceinline__ double sn_block_sum(double v, double* red) {
-  v = wave_sum_d(v);
-  __syncthreads();                                                 // the readers of the sum before are done with red
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
 __global__ __launch_bounds__(SN_TPB) void segsnr_ref_kernel(const float* __restrict__ ref, const int* __restrict__ rows, const int* __restrict__ begin,
                                                             const int* __restrict__ length, int S, int T, long long ld, double* __restrict__ stat) {
 #pragma clang fp contract(off)
@@ -446,13 +437,13 @@ __global__ __launch_bounds__(SN_TPB) void segsnr_ref_kernel(const float* __restr
   const SnSeg sg = sn_segment(ref, rows, begin, length, g, S, T, ld);
   double a = 0.0;
   for (int i = tid; i < sg.n; i += SN_TPB) a += (double)sg.r[i];
-  const double mean = sg.n > 0 ? sn_block_sum(a, red) / (double)sg.n : 0.0;
+  const double mean = sg.n > 0 ? block_sum_d(a, red) / (double)sg.n : 0.0;
   double e = 0.0;
   for (int i = tid; i < sg.n; i += SN_TPB) {
     const double d = (double)sg.r[i] - mean;
     e += d * d;
   }
-  e = sn_block_sum(e, red);
+  e = block_sum_d(e, red);
   if (tid == 0) {
     stat[2 * (long long)g] = mean;
     stat[2 * (long long)g + 1] = e;
@@ -472,17 +463,17 @@ __global__ __launch_bounds__(SN_TPB) void segsnr_value_kernel(const float* __res
   const double mr = stat[2 * (long long)g], srr = stat[2 * (long long)g + 1];
   double a = 0.0;
   for (int i = tid; i < sg.n; i += SN_TPB) a += (double)x[i];
-  const double ma = sg.n > 0 ? sn_block_sum(a, red) / (double)sg.n : 0.0;
+  const double ma = sg.n > 0 ? block_sum_d(a, red) / (double)sg.n : 0.0;
   double sar = 0.0;
   for (int i = tid; i < sg.n; i += SN_TPB) sar += ((double)x[i] - ma) * ((double)sg.r[i] - mr);
-  sar = sn_block_sum(sar, red);
+  sar = block_sum_d(sar, red);
   const double alpha = sar / (srr + eps);
   double res = 0.0;
   for (int i = tid; i < sg.n; i += SN_TPB) {                       // the residual itself, not a difference of moments
     const double d = ((double)x[i] - ma) - alpha * ((double)sg.r[i] - mr);
     res += d * d;
   }
-  res = sn_block_sum(res, red);
+  res = block_sum_d(res, red);
   if (tid == 0) {
     const double val = 20.0 * log10(eps + fabs(alpha) * sqrt(srr) / (sqrt(res) + eps));
     if (k < C) v[(long long)g * C + k] = val; else v_mix[g] = val;

@@ -17,13 +17,79 @@
 //
 // Beyond the reference: the source-aggregated, soft-thresholded SDR (sepr_pit_sasdr_*) on the same moment pass, the same
 // STFT projection and the same workspaces - a criterion that is defined when a target is silent throughout.
+//
+// What the eight entries share is stated once: the layout of the moment vector and the zero-mean moments with their clamp (pit_iq_*,
+// PitMoments), the fold of the chunk partials (pit_fold_moments), the permutations and the walk over them (perm_at / pit_walk of
+// sepr_common.h), the launch of the moment pass (launch_moments), the choice of the S instantiation (dispatch_S) and the forward launches
+// of the magnitude forms, which their backward repeats (mag_forward_launches).
+#include <type_traits>
+
 #include "sepr_gemm_epi.h"
 
 namespace sepr {
 
 namespace {
 constexpr int PIT_TPB = 256, PIT_CHUNK = 4096, PIT_SMAX = 3;
-__host__ __device__ constexpr int pit_nq(int S) { return 2 * (2 * S + 1) + S * S + S; }
+__host__ __device__ constexpr int pit_nchunk(int T) { return (T + PIT_CHUNK - 1) / PIT_CHUNK; }
+
+// The moment vector q of one utterance (and of one chunk of it in the workspace), over the NV = 2S + 1 waveforms v: est_s = s, tgt_k = S + k,
+// mix = 2S:  NV sums | NV sums of squares | S x S cross sums est_s . tgt_k, row-major | S cross sums mix . tgt_k
+__host__ __device__ constexpr int pit_iq_sum(int S, int v) { return v; }
+__host__ __device__ constexpr int pit_iq_sq(int S, int v) { return (2 * S + 1) + v; }
+__host__ __device__ constexpr int pit_iq_at(int S, int s, int k) { return 2 * (2 * S + 1) + s * S + k; }
+__host__ __device__ constexpr int pit_iq_xt(int S, int k) { return 2 * (2 * S + 1) + S * S + k; }
+__host__ __device__ constexpr int pit_nq(int S) { return pit_iq_xt(S, S); }
+
+// The zero-mean moments of an utterance of n samples from its moment vector: x~ = x - mean(x).
+template <int S>
+struct PitMoments {
+  const double* q;
+  double n;
+  __device__ __forceinline__ double sum(int v) const { return q[pit_iq_sum(S, v)]; }
+  __device__ __forceinline__ double mean(int v) const { return sum(v) / n; }
+  __device__ __forceinline__ double energy(int v) const {                       // |x~_v|^2
+    // sum(x^2) - sum(x)^2/n of a constant (DC-only) signal can cancel to a slightly negative number; the
+    // reference subtracts the mean first, so its energies are >= 0: clamp, or sqrt() would return NaN
+    const double e = q[pit_iq_sq(S, v)] - sum(v) * sum(v) / n;
+    return e > 0.0 ? e : 0.0;
+  }
+  __device__ __forceinline__ double sum_est(int s) const { return sum(s); }
+  __device__ __forceinline__ double sum_tgt(int k) const { return sum(S + k); }
+  __device__ __forceinline__ double mean_est(int s) const { return mean(s); }
+  __device__ __forceinline__ double mean_tgt(int k) const { return mean(S + k); }
+  __device__ __forceinline__ double aa(int s) const { return energy(s); }      // |a~_s|^2
+  __device__ __forceinline__ double tt(int k) const { return energy(S + k); }  // |t~_k|^2
+  __device__ __forceinline__ double mix_energy() const { return energy(2 * S); }
+  __device__ __forceinline__ double at(int s, int k) const { return q[pit_iq_at(S, s, k)] - sum_est(s) * sum_tgt(k) / n; }    // <a~_s, t~_k>
+  __device__ __forceinline__ double xt(int k) const { return q[pit_iq_xt(S, k)] - sum(2 * S) * sum_tgt(k) / n; }              // <x~, t~_k>
+};
+
+// The chunk partials of utterance b -> its moment vector q[pit_nq(S)] in LDS: thread i sums quantity i in chunk order, so each has one fixed
+// order.  Every thread of the workgroup (at least pit_nq(S) of them) calls it; it ends with the barrier after which all of them may read q.
+template <int S>
+__device__ __forceinline__ void pit_fold_moments(const double* __restrict__ part, int b, int nchunk, double* q) {
+  constexpr int NQ = pit_nq(S);
+  if (threadIdx.x < NQ) {
+    double s = 0.0;
+    for (int c = 0; c < nchunk; ++c) s += part[((long long)b * nchunk + c) * NQ + threadIdx.x];
+    q[threadIdx.x] = s;
+  }
+  __syncthreads();
+}
+
+// sum_s m[s][pi_p(s)]: what every walk below minimises or maximises
+template <int S>
+__device__ __forceinline__ double perm_cost(const double (&m)[S][S], int p) {
+  double c = 0.0;
+#pragma unroll
+  for (int s = 0; s < S; ++s) c += m[s][perm_at<S>(p, s)];
+  return c;
+}
+template <int S>
+__device__ __forceinline__ void store_perm(int* __restrict__ dst, int p) {
+#pragma unroll
+  for (int s = 0; s < S; ++s) dst[s] = perm_at<S>(p, s);
+}
 
 template <int S>
 __global__ __launch_bounds__(PIT_TPB) void pit_partial_kernel(const float* __restrict__ est, const float* __restrict__ tgt,
@@ -45,15 +111,15 @@ __global__ __launch_bounds__(PIT_TPB) void pit_partial_kernel(const float* __res
     v[2 * S] = mix ? (double)mix[(long long)b * T + t] : 0.0;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-      q[i] += v[i];
-      q[NV + i] = fma(v[i], v[i], q[NV + i]);
+      q[pit_iq_sum(S, i)] += v[i];
+      q[pit_iq_sq(S, i)] = fma(v[i], v[i], q[pit_iq_sq(S, i)]);
     }
 #pragma unroll
     for (int s = 0; s < S; ++s)
 #pragma unroll
-      for (int k = 0; k < S; ++k) q[2 * NV + s * S + k] = fma(v[s], v[S + k], q[2 * NV + s * S + k]);
+      for (int k = 0; k < S; ++k) q[pit_iq_at(S, s, k)] = fma(v[s], v[S + k], q[pit_iq_at(S, s, k)]);
 #pragma unroll
-    for (int k = 0; k < S; ++k) q[2 * NV + S * S + k] = fma(v[2 * S], v[S + k], q[2 * NV + S * S + k]);
+    for (int k = 0; k < S; ++k) q[pit_iq_xt(S, k)] = fma(v[2 * S], v[S + k], q[pit_iq_xt(S, k)]);
   }
   __shared__ double red[PIT_TPB / 64][NQ];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -85,65 +151,41 @@ __global__ __launch_bounds__(64) void pit_finalize_kernel(const double* __restri
                                                          double eps_i, double clamp_min, int have_mix, float* __restrict__ loss,
                                                          int* __restrict__ loss_perm, float* __restrict__ sisnri,
                                                          int* __restrict__ sisnri_perm) {
-  constexpr int NV = 2 * S + 1, NQ = pit_nq(S);
   const int b = blockIdx.x;
-  __shared__ double q[NQ];
-  if (threadIdx.x < NQ) {
-    double s = 0.0;
-    for (int c = 0; c < nchunk; ++c) s += part[((long long)b * nchunk + c) * NQ + threadIdx.x];
-    q[threadIdx.x] = s;
-  }
-  __syncthreads();
+  __shared__ double q[pit_nq(S)];
+  pit_fold_moments<S>(part, b, nchunk, q);
   if (threadIdx.x != 0) return;
-  const double n = (double)T;
-  double zz[NV];                                        // zero-mean energies
+  const PitMoments<S> m{q, (double)T};
+  double aa[S], tt[S];
 #pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    // sum(x^2) - sum(x)^2/n of a constant (DC-only) signal can cancel to a slightly negative number; the
-    // reference subtracts the mean first, so its energies are >= 0: clamp, or sqrt() would return NaN
-    const double e = q[NV + i] - q[i] * q[i] / n;
-    zz[i] = e > 0.0 ? e : 0.0;
+  for (int i = 0; i < S; ++i) {
+    aa[i] = m.aa(i);
+    tt[i] = m.tt(i);
   }
   double snr_l[S][S], snr_i[S][S], snr_x[S];
 #pragma unroll
   for (int k = 0; k < S; ++k) {
-    const double xt = q[2 * NV + S * S + k] - q[2 * S] * q[S + k] / n;
-    snr_x[k] = have_mix ? sisnr_db(zz[2 * S], zz[S + k], xt, eps_i) : 0.0;
+    const double xt = m.xt(k);
+    snr_x[k] = have_mix ? sisnr_db(m.mix_energy(), tt[k], xt, eps_i) : 0.0;
   }
 #pragma unroll
   for (int s = 0; s < S; ++s)
 #pragma unroll
     for (int k = 0; k < S; ++k) {
-      const double et = q[2 * NV + s * S + k] - q[s] * q[S + k] / n;
-      const double l = -sisnr_db(zz[s], zz[S + k], et, eps_loss);
+      const double et = m.at(s, k);
+      const double l = -sisnr_db(aa[s], tt[k], et, eps_loss);
       snr_l[s][k] = l < clamp_min ? clamp_min : l;      // torch.clamp(utt_loss, min=-30)
-      snr_i[s][k] = sisnr_db(zz[s], zz[S + k], et, eps_i) - snr_x[k];
+      snr_i[s][k] = sisnr_db(aa[s], tt[k], et, eps_i) - snr_x[k];
     }
-  // permutations in itertools.permutations(range(S)) order; first optimum wins (torch.min / torch.max semantics)
-  constexpr int NPERM = (S == 1) ? 1 : (S == 2 ? 2 : 6);
-  const int perms[6][3] = {{0, 1, 2}, {0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 0, 1}, {2, 1, 0}};
-  const int perms2[2][3] = {{0, 1, 0}, {1, 0, 0}};
-  double best_l = 0.0, best_i = 0.0;
-  int arg_l = 0, arg_i = 0;
-  for (int p = 0; p < NPERM; ++p) {
-    double sl = 0.0, si = 0.0;
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-      const int k = (S == 2) ? perms2[p][s] : perms[p][s];
-      sl += snr_l[s][k];
-      si += snr_i[s][k];
-    }
-    if (p == 0 || sl < best_l) { best_l = sl; arg_l = p; }
-    if (p == 0 || si > best_i) { best_i = si; arg_i = p; }
-  }
+  double best_l, best_i;
+  const int arg_l = pit_walk_min<S>([&](int p) { return perm_cost<S>(snr_l, p); }, best_l);
+  const int arg_i = pit_walk_max<S>([&](int p) { return perm_cost<S>(snr_i, p); }, best_i);
   loss[b] = (float)best_l;
+  if (loss_perm) store_perm<S>(loss_perm + b * S, arg_l);
+  if (sisnri_perm) store_perm<S>(sisnri_perm + b * S, arg_i);
+  if (sisnri) {
 #pragma unroll
-  for (int s = 0; s < S; ++s) {
-    const int kl = (S == 2) ? perms2[arg_l][s] : perms[arg_l][s];
-    const int ki = (S == 2) ? perms2[arg_i][s] : perms[arg_i][s];
-    if (loss_perm) loss_perm[b * S + s] = kl;
-    if (sisnri) sisnri[b * S + s] = (float)snr_i[s][ki];
-    if (sisnri_perm) sisnri_perm[b * S + s] = ki;
+    for (int s = 0; s < S; ++s) sisnri[b * S + s] = (float)snr_i[s][perm_at<S>(arg_i, s)];
   }
 }
 // ---- source-aggregated, soft-thresholded SDR: one ratio per utterance over all S sources ----
@@ -151,33 +193,35 @@ __global__ __launch_bounds__(64) void pit_finalize_kernel(const double* __restri
 // Not scale-invariant, no per-pair division by |t~_k|^2: a silent target costs nothing to state.  The time form takes its pair energies
 // from the moments (sasdr_pairs), the magnitude form from stft_pair_kernel's sums with unit scales; the walk, the value and the
 // gradient coefficient below serve both.
-template <int S>
-__device__ __forceinline__ int pit_perm_at(int p, int s) {          // itertools.permutations(range(S)) order
-  const int perms[6][3] = {{0, 1, 2}, {0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 0, 1}, {2, 1, 0}};
-  return S == 1 ? 0 : (S == 2 ? (p ^ s) & 1 : perms[p][s]);
-}
 // |e~_s - t~_k|^2 for every pair and D, from the one-pass moments.  A bit-equal pair gives exactly 0 (the three moments are then the same
-// fp64 number); cancellation below 0 is clamped as in pit_finalize_kernel.
+// fp64 number); cancellation below 0 is clamped as the energies are.
 template <int S>
-__device__ __forceinline__ void sasdr_pairs(const double* q, double n, double (&res)[S][S], double& D) {
-  constexpr int NV = 2 * S + 1;
+__device__ __forceinline__ void sasdr_pairs(const PitMoments<S>& m, double (&res)[S][S], double& D) {
   double aa[S], tt[S];
   D = 0.0;
 #pragma unroll
   for (int i = 0; i < S; ++i) {
-    const double a = q[NV + i] - q[i] * q[i] / n, t = q[NV + S + i] - q[S + i] * q[S + i] / n;
-    aa[i] = a > 0.0 ? a : 0.0;
-    tt[i] = t > 0.0 ? t : 0.0;
+    aa[i] = m.aa(i);
+    tt[i] = m.tt(i);
     D += tt[i];
   }
 #pragma unroll
   for (int s = 0; s < S; ++s)
 #pragma unroll
     for (int k = 0; k < S; ++k) {
-      const double at = q[2 * NV + s * S + k] - q[s] * q[S + k] / n;
+      const double at = m.at(s, k);
       const double r = (aa[s] - 2.0 * at) + tt[k];
       res[s][k] = r > 0.0 ? r : 0.0;
     }
+}
+// the permutation a backward was handed, clamped into range: res[][] is indexed by it
+template <int S>
+__device__ __forceinline__ void load_perm_clamped(const int* __restrict__ src, int (&pk)[S]) {
+#pragma unroll
+  for (int i = 0; i < S; ++i) {
+    const int k = src[i];
+    pk[i] = k < 0 ? 0 : (k >= S ? S - 1 : k);
+  }
 }
 template <int S>
 __device__ __forceinline__ double sasdr_energy(const double (&res)[S][S], const int* __restrict__ pk) {   // E of the permutation pk[0..S)
@@ -189,16 +233,7 @@ __device__ __forceinline__ double sasdr_energy(const double (&res)[S][S], const 
 // the first minimiser of E_p (the denominator does not depend on p) -> its index; E of it in `best`
 template <int S>
 __device__ __forceinline__ int sasdr_walk(const double (&res)[S][S], double& best) {
-  constexpr int NPERM = (S == 1) ? 1 : (S == 2 ? 2 : 6);
-  int arg = 0;
-  best = 0.0;
-  for (int p = 0; p < NPERM; ++p) {
-    double e = 0.0;
-#pragma unroll
-    for (int s = 0; s < S; ++s) e += res[s][pit_perm_at<S>(p, s)];
-    if (p == 0 || e < best) { best = e; arg = p; }
-  }
-  return arg;
+  return pit_walk_min<S>([&](int p) { return perm_cost<S>(res, p); }, best);
 }
 __device__ __forceinline__ double sasdr_db(double E, double D, double tau, double eps) {
   return 10.0 * log10((E + tau * D + eps) / (D + eps));
@@ -211,24 +246,15 @@ __device__ __forceinline__ double sasdr_coef(double E, double D, double tau, dou
 template <int S>
 __global__ __launch_bounds__(64) void sasdr_finalize_kernel(const double* __restrict__ part, int T, int nchunk, double eps, double tau,
                                                            float* __restrict__ loss, int* __restrict__ perm) {
-  constexpr int NQ = pit_nq(S);
   const int b = blockIdx.x;
-  __shared__ double q[NQ];
-  if (threadIdx.x < NQ) {
-    double s = 0.0;
-    for (int c = 0; c < nchunk; ++c) s += part[((long long)b * nchunk + c) * NQ + threadIdx.x];
-    q[threadIdx.x] = s;
-  }
-  __syncthreads();
+  __shared__ double q[pit_nq(S)];
+  pit_fold_moments<S>(part, b, nchunk, q);
   if (threadIdx.x != 0) return;
   double res[S][S], D, E;
-  sasdr_pairs<S>(q, (double)T, res, D);
+  sasdr_pairs<S>(PitMoments<S>{q, (double)T}, res, D);
   const int arg = sasdr_walk<S>(res, E);
   loss[b] = (float)sasdr_db(E, D, tau, eps);
-  if (perm) {
-#pragma unroll
-    for (int s = 0; s < S; ++s) perm[b * S + s] = pit_perm_at<S>(arg, s);
-  }
+  if (perm) store_perm<S>(perm + b * S, arg);
 }
 }  // namespace
 
@@ -236,7 +262,7 @@ struct PitWs {   // the chunks' fp64 partial moments; the backward adds four coe
   double* part;
   float* coef;
   PitWs(Arena& a, int S, int B, int T, bool bwd) {
-    part = a.f64((size_t)B * ((T + PIT_CHUNK - 1) / PIT_CHUNK) * pit_nq(S));
+    part = a.f64((size_t)B * pit_nchunk(T) * pit_nq(S));
     coef = bwd ? a.f32((size_t)B * S * 4) : nullptr;
   }
 };
@@ -244,6 +270,26 @@ size_t pit_workspace_bytes(int S, int B, int T) {
   if (S < 1 || S > PIT_SMAX || B <= 0 || T <= 0) return 0;
   return layout_bytes<PitWs>(S, B, T, false);
 }
+
+namespace {
+// f(std::integral_constant<int, S>) for the S the library is built for: the launches of an entry are written once, as a generic lambda
+template <class F>
+int dispatch_S(int S, F&& f) {
+  static_assert(PIT_SMAX == 3, "one case per S");
+  switch (S) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    default: return SEPR_EINVAL;
+  }
+}
+// the moment pass every entry starts with; mix may be null (its moments are then 0)
+template <int S>
+void launch_moments(const float* est, const float* tgt, const float* mix, int B, int T, double* part, hipStream_t st) {
+  const int nchunk = pit_nchunk(T);
+  hipLaunchKernelGGL((pit_partial_kernel<S>), dim3(nchunk, B), dim3(PIT_TPB), 0, st, est, tgt, mix, B, T, nchunk, part);
+}
+}  // namespace
 
 }  // namespace sepr
 
@@ -257,24 +303,15 @@ extern "C" int sepr_pit_sisnr_fwd(const float* est, const float* tgt, const floa
   double* part = PitWs(ar, S, B, T, false).part;
   if (!ar.ok_need()) return SEPR_EWORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int nchunk = (T + PIT_CHUNK - 1) / PIT_CHUNK;
-  const dim3 grid(nchunk, B);
   const int have_mix = mix ? 1 : 0;
-#define SEPR_PIT_CASE(SS)                                                                                                   \
-  case SS:                                                                                                                  \
-    hipLaunchKernelGGL((pit_partial_kernel<SS>), grid, dim3(PIT_TPB), 0, st, est, tgt, mix, B, T, nchunk, part);           \
-    hipLaunchKernelGGL((pit_finalize_kernel<SS>), dim3(B), dim3(64), 0, st, part, T, nchunk, eps_loss, eps_i, clamp_min,   \
-                       have_mix, loss, loss_perm, sisnri, sisnri_perm);                                                     \
-    break;
-  switch (S) {
-    SEPR_PIT_CASE(1)
-    SEPR_PIT_CASE(2)
-    SEPR_PIT_CASE(3)
-    default: return SEPR_EINVAL;
-  }
-#undef SEPR_PIT_CASE
-  SEPR_CHECK_LAUNCH("pit_sisnr kernels");
-  return SEPR_OK;
+  return dispatch_S(S, [&](auto ss) {
+    constexpr int SS = decltype(ss)::value;
+    launch_moments<SS>(est, tgt, mix, B, T, part, st);
+    hipLaunchKernelGGL((pit_finalize_kernel<SS>), dim3(B), dim3(64), 0, st, part, T, pit_nchunk(T), eps_loss, eps_i, clamp_min, have_mix,
+                       loss, loss_perm, sisnri, sisnri_perm);
+    SEPR_CHECK_LAUNCH("pit_sisnr kernels");
+    return SEPR_OK;
+  });
 }
 
 extern "C" int sepr_pit_sasdr_fwd(const float* est, const float* tgt, int S, int B, int T, double eps, double snr_max, float* loss,
@@ -285,23 +322,14 @@ extern "C" int sepr_pit_sasdr_fwd(const float* est, const float* tgt, int S, int
   double* part = PitWs(ar, S, B, T, false).part;
   if (!ar.ok_need()) return SEPR_EWORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int nchunk = (T + PIT_CHUNK - 1) / PIT_CHUNK;
   const double tau = pow(10.0, -snr_max / 10.0);
-#define SEPR_SASDR_CASE(SS)                                                                                                         \
-  case SS:                                                                                                                          \
-    hipLaunchKernelGGL((pit_partial_kernel<SS>), dim3(nchunk, B), dim3(PIT_TPB), 0, st, est, tgt, (const float*)nullptr, B, T,     \
-                       nchunk, part);                                                                                               \
-    hipLaunchKernelGGL((sasdr_finalize_kernel<SS>), dim3(B), dim3(64), 0, st, part, T, nchunk, eps, tau, loss, perm);              \
-    break;
-  switch (S) {
-    SEPR_SASDR_CASE(1)
-    SEPR_SASDR_CASE(2)
-    SEPR_SASDR_CASE(3)
-    default: return SEPR_EINVAL;
-  }
-#undef SEPR_SASDR_CASE
-  SEPR_CHECK_LAUNCH("pit_sasdr kernels");
-  return SEPR_OK;
+  return dispatch_S(S, [&](auto ss) {
+    constexpr int SS = decltype(ss)::value;
+    launch_moments<SS>(est, tgt, nullptr, B, T, part, st);
+    hipLaunchKernelGGL((sasdr_finalize_kernel<SS>), dim3(B), dim3(64), 0, st, part, T, pit_nchunk(T), eps, tau, loss, perm);
+    SEPR_CHECK_LAUNCH("pit_sasdr kernels");
+    return SEPR_OK;
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -321,26 +349,18 @@ namespace {
 template <int S>
 __global__ __launch_bounds__(64) void mag_scales_kernel(const double* __restrict__ part, int T, int nchunk, double eps,
                                                        float* __restrict__ means, float* __restrict__ scales, int B, int unit /* 1: every scale is 1 (the aggregated form) */) {
-  constexpr int NV = 2 * S + 1, NQ = pit_nq(S);
   const int b = blockIdx.x;
-  __shared__ double q[NQ];
-  if (threadIdx.x < NQ) {
-    double s = 0.0;
-    for (int c = 0; c < nchunk; ++c) s += part[((long long)b * nchunk + c) * NQ + threadIdx.x];
-    q[threadIdx.x] = s;
-  }
-  __syncthreads();
+  __shared__ double q[pit_nq(S)];
+  pit_fold_moments<S>(part, b, nchunk, q);
   if (threadIdx.x != 0) return;
-  const double n = (double)T;
+  const PitMoments<S> m{q, (double)T};
 #pragma unroll
-  for (int i = 0; i < 2 * S; ++i) means[i * B + b] = (float)(q[i] / n);       // waveform order: est_0.. est_{S-1}, tgt_0..
+  for (int i = 0; i < 2 * S; ++i) means[i * B + b] = (float)m.mean(i);        // waveform order: est_0.. est_{S-1}, tgt_0..
 #pragma unroll
   for (int s = 0; s < S; ++s)
 #pragma unroll
     for (int k = 0; k < S; ++k) {
-      const double et = q[2 * NV + s * S + k] - q[s] * q[S + k] / n;
-      double tt = q[NV + S + k] - q[S + k] * q[S + k] / n;
-      tt = tt > 0.0 ? tt : 0.0;                        // cancellation on a DC-only target (see pit_finalize_kernel)
+      const double et = m.at(s, k), tt = m.tt(k);
       const double sc = et / (tt + eps);
       scales[(b * S + s) * S + k] = unit ? 1.f : (float)(sc < 1e-2 ? 1e-2 : sc);   // torch.clamp(scale, min=1e-2)
     }
@@ -356,6 +376,21 @@ __global__ __launch_bounds__(256) void stft_prep_kernel(const float* __restrict_
     xz[(long long)wv * Tpad + t] = t < T ? src[t] - mu : 0.f;
 }
 
+// N values per thread of a 256-thread workgroup -> their N sums in every thread, the four wave sums taken in pairs, (r0 + r1) + (r2 + r3):
+// the order the three kernels below have had from the start (block_sum_d's left-to-right order rounds differently).  One barrier.
+template <int N>
+__device__ __forceinline__ void pair_block_sums(double (&v)[N], double (&red)[N][4]) {
+#pragma unroll
+  for (int i = 0; i < N; ++i) v[i] = wave_sum_d(v[i]);
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) red[i][threadIdx.x >> 6] = v[i];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < N; ++i) v[i] = (red[i][0] + red[i][1]) + (red[i][2] + red[i][3]);
+}
+
 template <int S>
 __global__ __launch_bounds__(256) void stft_pair_kernel(const float* __restrict__ C, int ldc, int B, int nfr, int nbin,
                                                        const float* __restrict__ scales, double* __restrict__ sums) {
@@ -364,7 +399,7 @@ __global__ __launch_bounds__(256) void stft_pair_kernel(const float* __restrict_
   const float sc = scales[(b * S + s) * S + k];
   const float* Ce = C + (long long)(s * B + b) * nfr * ldc;
   const float* Ct = C + (long long)((S + k) * B + b) * nfr * ldc;
-  double a0 = 0.0, a1 = 0.0;
+  double a[2] = {0.0, 0.0};
   const int total = nfr * nbin;
   for (int i = threadIdx.x; i < total; i += 256) {
     const int f = i / nbin, w = i - f * nbin;
@@ -373,19 +408,15 @@ __global__ __launch_bounds__(256) void stft_pair_kernel(const float* __restrict_
     const float me = sqrtf(er * er + ei * ei + 1.0e-10f);
     const float ms = sqrtf(tr * tr + ti * ti + 1.0e-10f);
     const double d = (double)me - (double)ms;
-    a0 = fma((double)ms, (double)ms, a0);
-    a1 = fma(d, d, a1);
+    a[0] = fma((double)ms, (double)ms, a[0]);
+    a[1] = fma(d, d, a[1]);
   }
   __shared__ double red[2][4];
-  a0 = wave_sum_d(a0);
-  a1 = wave_sum_d(a1);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) { red[0][w] = a0; red[1][w] = a1; }
-  __syncthreads();
+  pair_block_sums(a, red);
   if (threadIdx.x == 0) {
     double* o = sums + ((long long)(b * S + s) * S + k) * 2;
-    o[0] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-    o[1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+    o[0] = a[0];
+    o[1] = a[1];
   }
 }
 
@@ -402,22 +433,10 @@ __global__ __launch_bounds__(64) void mag_finalize_kernel(const double* __restri
       const double* o = sums + ((long long)(b * S + s) * S + k) * 2;
       l[s][k] = -20.0 * log10(eps + sqrt(o[0]) / (sqrt(o[1]) + eps));
     }
-  constexpr int NPERM = (S == 1) ? 1 : (S == 2 ? 2 : 6);
-  const int perms[6][3] = {{0, 1, 2}, {0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 0, 1}, {2, 1, 0}};
-  const int perms2[2][3] = {{0, 1, 0}, {1, 0, 0}};
-  double best = 0.0;
-  int arg = 0;
-  for (int p = 0; p < NPERM; ++p) {
-    double sl = 0.0;
-#pragma unroll
-    for (int s = 0; s < S; ++s) sl += l[s][(S == 2) ? perms2[p][s] : perms[p][s]];
-    if (p == 0 || sl < best) { best = sl; arg = p; }
-  }
+  double best;
+  const int arg = pit_walk_min<S>([&](int p) { return perm_cost<S>(l, p); }, best);
   loss[b] = (float)best;
-  if (perm) {
-#pragma unroll
-    for (int s = 0; s < S; ++s) perm[b * S + s] = (S == 2) ? perms2[arg][s] : perms[arg][s];
-  }
+  if (perm) store_perm<S>(perm + b * S, arg);
 }
 
 // the aggregated form over the pair sums of unit scales: sums[(b, s, k)] = (sum M_k^2, sum (M_s - M_k)^2); D reads the s = 0 row
@@ -442,10 +461,7 @@ __global__ __launch_bounds__(64) void sasdr_mag_finalize_kernel(const double* __
   sasdr_mag_pairs<S>(sums, b, res, D);
   const int arg = sasdr_walk<S>(res, E);
   loss[b] = (float)sasdr_db(E, D, tau, eps);
-  if (perm) {
-#pragma unroll
-    for (int s = 0; s < S; ++s) perm[b * S + s] = pit_perm_at<S>(arg, s);
-  }
+  if (perm) store_perm<S>(perm + b * S, arg);
 }
 
 // geometry and workspace of the magnitude loss, carved from `a` (sized by the same code on Arena::sizing())
@@ -457,7 +473,7 @@ struct MagPlan {
 };
 MagPlan mag_plan(Arena& a, int S, int B, int T, int N, int hop) {
   MagPlan p;
-  p.nchunk = (T + PIT_CHUNK - 1) / PIT_CHUNK;
+  p.nchunk = pit_nchunk(T);
   p.NF = (T + hop - 1) / hop;
   p.Tpad = p.NF * hop;
   p.nfr = p.Tpad >= N ? (p.Tpad - N) / hop + 1 : 0;
@@ -486,6 +502,29 @@ extern "C" size_t sepr_pit_sisnr_mag_workspace(int S, int B, int T, int frame_le
 
 namespace sepr {
 namespace {
+// The forward quantities of both magnitude criteria, which their backward recomputes launch for launch: moments, scales (`agg`: unit scales)
+// and means, the zero-mean padded copies of the 2S waveforms, their STFT as one projection, the pair sums.  `where` names the first
+// launch check; the caller makes the one after its own launches.
+template <int S>
+int mag_forward_launches(const MagPlan& p, const float* est, const float* tgt, int B, int T, const float* dft, int frame_len, int frame_shift,
+                         double eps, int agg, const char* where, hipStream_t st) {
+  launch_moments<S>(est, tgt, nullptr, B, T, p.part, st);
+  hipLaunchKernelGGL((mag_scales_kernel<S>), dim3(B), dim3(64), 0, st, p.part, T, p.nchunk, eps, p.means, p.scales, B, agg);
+  const int gx = (p.Tpad + 255) / 256 < 64 ? (p.Tpad + 255) / 256 : 64;
+  hipLaunchKernelGGL(stft_prep_kernel, dim3(gx, 2 * S * B), dim3(256), 0, st, est, tgt, p.means, S * B, T, p.Tpad, p.xz);
+  SEPR_CHECK_LAUNCH(where);
+  {  // STFT: row (waveform, frame f) of A = xz[waveform][hop*f : hop*f + N]; weight = DFT kernel [N+2 (padded to ldc), N]
+    GemmArgs a = gemm_args_zero();
+    a.M = 2 * S * B * p.nfr; a.N = p.ldc; a.K = frame_len;
+    a.A = p.xz; a.lda = frame_shift;
+    a.rows_out = p.nfr; a.rows_src = p.NF; a.rows_valid = p.nfr;
+    a.W = dft; a.bias = nullptr; a.Y = p.C; a.ldc = p.ldc;
+    SEPR_TRY(launch_gemm(PRO_PLAIN, EPI_STORE, a, SEPR_SITE_NONE, st));
+  }
+  hipLaunchKernelGGL((stft_pair_kernel<S>), dim3(B, S * S), dim3(256), 0, st, p.C, p.ldc, B, p.nfr, frame_len / 2 + 1, p.scales, p.sums);
+  return SEPR_OK;
+}
+
 // both magnitude criteria: `agg` = 0 the per-pair SI-SNR form, 1 the aggregated form (unit scales, sasdr_mag_finalize_kernel with `tau`)
 int mag_fwd(const float* est, const float* tgt, int S, int B, int T, const float* dft, int frame_len, int frame_shift, double eps, int agg,
             double tau, float* loss, int* perm, void* ws, size_t ws_bytes, sepr_stream_t stream) {
@@ -497,52 +536,16 @@ int mag_fwd(const float* est, const float* tgt, int S, int B, int T, const float
   if (!ar.ok_need()) return SEPR_EWORKSPACE;
   if ((long long)2 * S * B * p.nfr > 0x7fffffffLL / 8 || (long long)2 * S * B * p.Tpad >= (1LL << 32)) return SEPR_EINVAL;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  double *part = p.part, *sums = p.sums;
-  float *means = p.means, *scales = p.scales, *xz = p.xz, *C = p.C;
-  const int nbin = frame_len / 2 + 1;
-#define SEPR_MAG_CASE(SS)                                                                                                    \
-  case SS:                                                                                                                   \
-    hipLaunchKernelGGL((pit_partial_kernel<SS>), dim3(p.nchunk, B), dim3(PIT_TPB), 0, st, est, tgt, (const float*)nullptr,  \
-                       B, T, p.nchunk, part);                                                                                \
-    hipLaunchKernelGGL((mag_scales_kernel<SS>), dim3(B), dim3(64), 0, st, part, T, p.nchunk, eps, means, scales, B, agg);   \
-    break;
-  switch (S) {
-    SEPR_MAG_CASE(1)
-    SEPR_MAG_CASE(2)
-    SEPR_MAG_CASE(3)
-    default: return SEPR_EINVAL;
-  }
-#undef SEPR_MAG_CASE
-  {
-    const int gx = (p.Tpad + 255) / 256 < 64 ? (p.Tpad + 255) / 256 : 64;
-    hipLaunchKernelGGL(stft_prep_kernel, dim3(gx, 2 * S * B), dim3(256), 0, st, est, tgt, means, S * B, T, p.Tpad, xz);
-  }
-  SEPR_CHECK_LAUNCH("pit mag: moments / prep");
-  {  // STFT: row (waveform, frame f) of A = xz[waveform][hop*f : hop*f + N]; weight = DFT kernel [N+2 (padded to ldc), N]
-    GemmArgs a = gemm_args_zero();
-    a.M = 2 * S * B * p.nfr; a.N = p.ldc; a.K = frame_len;
-    a.A = xz; a.lda = frame_shift;
-    a.rows_out = p.nfr; a.rows_src = p.NF; a.rows_valid = p.nfr;
-    a.W = dft; a.bias = nullptr; a.Y = C; a.ldc = p.ldc;
-    SEPR_TRY(launch_gemm(PRO_PLAIN, EPI_STORE, a, SEPR_SITE_NONE, st));
-  }
-#define SEPR_MAG_CASE2(SS)                                                                                                   \
-  case SS:                                                                                                                   \
-    hipLaunchKernelGGL((stft_pair_kernel<SS>), dim3(B, SS * SS), dim3(256), 0, st, C, p.ldc, B, p.nfr, nbin, scales, sums); \
-    if (agg)                                                                                                                 \
-      hipLaunchKernelGGL((sasdr_mag_finalize_kernel<SS>), dim3((B + 63) / 64), dim3(64), 0, st, sums, B, eps, tau, loss, perm); \
-    else                                                                                                                     \
-      hipLaunchKernelGGL((mag_finalize_kernel<SS>), dim3((B + 63) / 64), dim3(64), 0, st, sums, B, eps, loss, perm);        \
-    break;
-  switch (S) {
-    SEPR_MAG_CASE2(1)
-    SEPR_MAG_CASE2(2)
-    SEPR_MAG_CASE2(3)
-    default: return SEPR_EINVAL;
-  }
-#undef SEPR_MAG_CASE2
-  SEPR_CHECK_LAUNCH("pit mag: pair sums");
-  return SEPR_OK;
+  return dispatch_S(S, [&](auto ss) {
+    constexpr int SS = decltype(ss)::value;
+    SEPR_TRY(mag_forward_launches<SS>(p, est, tgt, B, T, dft, frame_len, frame_shift, eps, agg, "pit mag: moments / prep", st));
+    if (agg)
+      hipLaunchKernelGGL((sasdr_mag_finalize_kernel<SS>), dim3((B + 63) / 64), dim3(64), 0, st, p.sums, B, eps, tau, loss, perm);
+    else
+      hipLaunchKernelGGL((mag_finalize_kernel<SS>), dim3((B + 63) / 64), dim3(64), 0, st, p.sums, B, eps, loss, perm);
+    SEPR_CHECK_LAUNCH("pit mag: pair sums");
+    return SEPR_OK;
+  });
 }
 }  // namespace
 }  // namespace sepr
@@ -575,22 +578,13 @@ template <int S>
 __global__ __launch_bounds__(64) void pit_bwd_coef_kernel(const double* __restrict__ part, const int* __restrict__ perm,
                                                          const float* __restrict__ gl, int T, int nchunk, double eps, double clamp_min,
                                                          float* __restrict__ coef /*[B][S][4]: ca, ct, mean_a, mean_t*/) {
-  constexpr int NV = 2 * S + 1, NQ = pit_nq(S);
   const int b = blockIdx.x;
-  __shared__ double q[NQ];
-  if (threadIdx.x < NQ) {
-    double s = 0.0;
-    for (int c = 0; c < nchunk; ++c) s += part[((long long)b * nchunk + c) * NQ + threadIdx.x];
-    q[threadIdx.x] = s;
-  }
-  __syncthreads();
+  __shared__ double q[pit_nq(S)];
+  pit_fold_moments<S>(part, b, nchunk, q);
   if (threadIdx.x >= S) return;
   const int s = threadIdx.x, k = perm[b * S + s];
-  const double n = (double)T;
-  double aa = q[NV + s] - q[s] * q[s] / n, tt = q[NV + S + k] - q[S + k] * q[S + k] / n;
-  aa = aa > 0.0 ? aa : 0.0;
-  tt = tt > 0.0 ? tt : 0.0;
-  const double at = q[2 * NV + s * S + k] - q[s] * q[S + k] / n;
+  const PitMoments<S> m{q, (double)T};
+  const double aa = m.aa(s), tt = m.tt(k), at = m.at(s, k);
   const double c = tt + eps, alpha = at / c;
   const double P = fabs(alpha) * sqrt(tt);
   double R2 = aa - 2.0 * alpha * at + alpha * alpha * tt;
@@ -607,7 +601,7 @@ __global__ __launch_bounds__(64) void pit_bwd_coef_kernel(const double* __restri
     ct = kt - ke * alpha - ke * et / c;
   }
   float* o = coef + ((long long)b * S + s) * 4;
-  o[0] = (float)ca; o[1] = (float)ct; o[2] = (float)(q[s] / n); o[3] = (float)(q[S + k] / n);
+  o[0] = (float)ca; o[1] = (float)ct; o[2] = (float)m.mean_est(s); o[3] = (float)m.mean_tgt(k);
 }
 // the aggregated form's record: ca = k, ct = -k with k = sasdr_coef * gl[b], the two means.  A pair whose energy is exactly 0 in the moments
 // (bit-equal signals, two silent rows) gets ca = ct = 0: its gradient is exactly 0, which k a~ - k t~ rounded twice in float32 is not.
@@ -615,29 +609,19 @@ template <int S>
 __global__ __launch_bounds__(64) void sasdr_bwd_coef_kernel(const double* __restrict__ part, const int* __restrict__ perm,
                                                            const float* __restrict__ gl, int T, int nchunk, double eps, double tau,
                                                            float* __restrict__ coef /*[B][S][4]: ca, ct, mean_a, mean_t*/) {
-  constexpr int NQ = pit_nq(S);
   const int b = blockIdx.x;
-  __shared__ double q[NQ];
-  if (threadIdx.x < NQ) {
-    double s = 0.0;
-    for (int c = 0; c < nchunk; ++c) s += part[((long long)b * nchunk + c) * NQ + threadIdx.x];
-    q[threadIdx.x] = s;
-  }
-  __syncthreads();
+  __shared__ double q[pit_nq(S)];
+  pit_fold_moments<S>(part, b, nchunk, q);
   if (threadIdx.x >= S) return;
   const int s = threadIdx.x;
   int pk[S];
-#pragma unroll
-  for (int i = 0; i < S; ++i) {
-    const int k = perm[b * S + i];
-    pk[i] = k < 0 ? 0 : (k >= S ? S - 1 : k);               // res[][] is indexed by it
-  }
-  const double n = (double)T;
+  load_perm_clamped<S>(perm + b * S, pk);
+  const PitMoments<S> m{q, (double)T};
   double res[S][S], D;
-  sasdr_pairs<S>(q, n, res, D);
+  sasdr_pairs<S>(m, res, D);
   const double k = res[s][pk[s]] > 0.0 ? sasdr_coef(sasdr_energy<S>(res, pk), D, tau, eps) * (double)gl[b] : 0.0;
   float* o = coef + ((long long)b * S + s) * 4;
-  o[0] = (float)k; o[1] = (float)-k; o[2] = (float)(q[s] / n); o[3] = (float)(q[S + pk[s]] / n);
+  o[0] = (float)k; o[1] = (float)-k; o[2] = (float)m.mean_est(s); o[3] = (float)m.mean_tgt(pk[s]);
 }
 __global__ __launch_bounds__(256) void pit_bwd_apply_kernel(const float* __restrict__ est, const float* __restrict__ tgt,
                                                            const int* __restrict__ perm, const float* __restrict__ coef, int S, int B, int T,
@@ -660,33 +644,25 @@ namespace {
 int pit_bwd(const float* est, const float* tgt, const int* perm, const float* gl, int S, int B, int T, double eps, int agg, double lim,
             float* dest, void* ws, size_t ws_bytes, sepr_stream_t stream) {
   if (!est || !tgt || !perm || !gl || !dest || S < 1 || S > PIT_SMAX || B <= 0 || T <= 0 || B > 65535) return SEPR_EINVAL;
-  const int nchunk = (T + PIT_CHUNK - 1) / PIT_CHUNK;
+  const int nchunk = pit_nchunk(T);
   Arena ar(ws, ws_bytes);
   const PitWs k(ar, S, B, T, true);
   if (!ar.ok_need()) return SEPR_EWORKSPACE;
   double* part = k.part;
   float* coef = k.coef;
   hipStream_t st = static_cast<hipStream_t>(stream);
-#define SEPR_PITB(SS)                                                                                                             \
-  case SS:                                                                                                                        \
-    hipLaunchKernelGGL((pit_partial_kernel<SS>), dim3(nchunk, B), dim3(PIT_TPB), 0, st, est, tgt, (const float*)nullptr, B, T,   \
-                       nchunk, part);                                                                                             \
-    if (agg)                                                                                                                      \
-      hipLaunchKernelGGL((sasdr_bwd_coef_kernel<SS>), dim3(B), dim3(64), 0, st, part, perm, gl, T, nchunk, eps, lim, coef);       \
-    else                                                                                                                          \
-      hipLaunchKernelGGL((pit_bwd_coef_kernel<SS>), dim3(B), dim3(64), 0, st, part, perm, gl, T, nchunk, eps, lim, coef);         \
-    break;
-  switch (S) {
-    SEPR_PITB(1)
-    SEPR_PITB(2)
-    SEPR_PITB(3)
-    default: return SEPR_EINVAL;
-  }
-#undef SEPR_PITB
-  const int gx = (T + 255) / 256 < 64 ? (T + 255) / 256 : 64;
-  hipLaunchKernelGGL(pit_bwd_apply_kernel, dim3(gx, S * B), dim3(256), 0, st, est, tgt, perm, coef, S, B, T, dest);
-  SEPR_CHECK_LAUNCH("pit_sisnr_bwd kernels");
-  return SEPR_OK;
+  return dispatch_S(S, [&](auto ss) {
+    constexpr int SS = decltype(ss)::value;
+    launch_moments<SS>(est, tgt, nullptr, B, T, part, st);
+    if (agg)
+      hipLaunchKernelGGL((sasdr_bwd_coef_kernel<SS>), dim3(B), dim3(64), 0, st, part, perm, gl, T, nchunk, eps, lim, coef);
+    else
+      hipLaunchKernelGGL((pit_bwd_coef_kernel<SS>), dim3(B), dim3(64), 0, st, part, perm, gl, T, nchunk, eps, lim, coef);
+    const int gx = (T + 255) / 256 < 64 ? (T + 255) / 256 : 64;
+    hipLaunchKernelGGL(pit_bwd_apply_kernel, dim3(gx, S * B), dim3(256), 0, st, est, tgt, perm, coef, S, B, T, dest);
+    SEPR_CHECK_LAUNCH("pit_sisnr_bwd kernels");
+    return SEPR_OK;
+  });
 }
 }  // namespace
 }  // namespace sepr
@@ -743,11 +719,7 @@ __global__ __launch_bounds__(256) void stft_pair_bwd_kernel(const float* __restr
   float ge, gs1, gs2;                                       // dL/dM_e = ge (M_e - M_s);  dL/dM_s = gs1 M_s + gs2 (M_e - M_s)
   if (AGG) {
     int pk[S];
-#pragma unroll
-    for (int i = 0; i < S; ++i) {
-      const int ki = perm[b * S + i];
-      pk[i] = ki < 0 ? 0 : (ki >= S ? S - 1 : ki);
-    }
+    load_perm_clamped<S>(perm + b * S, pk);
     double res[S][S], D;
     sasdr_mag_pairs<S>(sums, b, res, D);
     ge = (float)(sasdr_coef(sasdr_energy<S>(res, pk), D, tau, eps) * (double)gl[b]);
@@ -765,7 +737,7 @@ __global__ __launch_bounds__(256) void stft_pair_bwd_kernel(const float* __restr
   const float* Ce = C + (long long)(s * B + b) * nfr * ldc;
   const float* Ct = C + (long long)((S + k) * B + b) * nfr * ldc;
   float* De = dC + (long long)(s * B + b) * nfr * ldd;
-  double acc = 0.0;
+  double acc[1] = {0.0};
   const int total = nfr * nbin;
   for (int i = threadIdx.x; i < total; i += 256) {
     const int f = i / nbin, w = i - f * nbin;
@@ -780,18 +752,16 @@ __global__ __launch_bounds__(256) void stft_pair_bwd_kernel(const float* __restr
     De[(long long)f * ldd + w] = gme * er / me;
     De[(long long)f * ldd + nbin + w] = gme * ei / me;
     const float gms = gs1 * ms + gs2 * d;
-    acc += (double)(gms * sc * t2 / ms);
+    acc[0] += (double)(gms * sc * t2 / ms);
   }
   // zero the padding columns of this estimate's rows (the adjoint projection reads ldc columns)
   for (int i = threadIdx.x; i < nfr * (ldd - 2 * nbin); i += 256) {
     const int f = i / (ldd - 2 * nbin), w = i - f * (ldd - 2 * nbin);
     De[(long long)f * ldd + 2 * nbin + w] = 0.f;
   }
-  __shared__ double red[4];
-  acc = wave_sum_d(acc);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) dLdc[b * S + s] = (red[0] + red[1]) + (red[2] + red[3]);
+  __shared__ double red[1][4];
+  pair_block_sums(acc, red);
+  if (threadIdx.x == 0) dLdc[b * S + s] = acc[0];
 }
 
 // overlap-add gather of the adjoint frames + the scale path: da[t] = sum_{f: 0 <= t - hop f < N} fr[f][t - hop f] + cs t~[t]
@@ -800,28 +770,16 @@ __global__ __launch_bounds__(256) void stft_ola_kernel(const float* __restrict__
                                                       int hop, int Tpad, const double* __restrict__ dLdc, const double* __restrict__ part,
                                                       int nchunk, int T, const int* __restrict__ perm, double eps,
                                                       float* __restrict__ da) {
-  constexpr int NV = 2 * S + 1, NQ = pit_nq(S);
   const int sb = blockIdx.y;
   const int s = sb / B, b = sb - s * B;
   const int k = perm[b * S + s];
-  // scale path coefficient: dL/dc * [raw scale >= 1e-2] / (|t~|^2 + eps)
-  __shared__ float cs_s;
-  if (threadIdx.x == 0) {
-    double q[NQ];
-    for (int i = 0; i < NQ; ++i) {
-      double a = 0.0;
-      for (int c = 0; c < nchunk; ++c) a += part[((long long)b * nchunk + c) * NQ + i];
-      q[i] = a;
-    }
-    const double n = (double)T;
-    double tt = q[NV + S + k] - q[S + k] * q[S + k] / n;
-    tt = tt > 0.0 ? tt : 0.0;
-    const double et = q[2 * NV + s * S + k] - q[s] * q[S + k] / n;
-    const double raw = et / (tt + eps);
-    cs_s = raw >= 1e-2 ? (float)(dLdc[b * S + s] / (tt + eps)) : 0.f;
-  }
-  __syncthreads();
-  const float cs = cs_s;
+  // scale path coefficient: dL/dc * [raw scale >= 1e-2] / (|t~|^2 + eps), by every thread from the folded moments
+  __shared__ double q[pit_nq(S)];
+  pit_fold_moments<S>(part, b, nchunk, q);
+  const PitMoments<S> m{q, (double)T};
+  const double tt = m.tt(k), et = m.at(s, k);
+  const double raw = et / (tt + eps);
+  const float cs = raw >= 1e-2 ? (float)(dLdc[b * S + s] / (tt + eps)) : 0.f;
   const float* f0 = fr + (long long)sb * nfr * N;
   const float* tz = xz + (long long)((S + k) * B + b) * Tpad;
   for (int t = blockIdx.x * 256 + threadIdx.x; t < Tpad; t += gridDim.x * 256) {
@@ -835,13 +793,11 @@ __global__ __launch_bounds__(256) void stft_ola_kernel(const float* __restrict__
 __global__ __launch_bounds__(256) void demean_kernel(const float* __restrict__ da, int Tpad, int T, float* __restrict__ dest) {
   const int sb = blockIdx.x;
   const float* p = da + (long long)sb * Tpad;
-  double s = 0.0;
-  for (int i = threadIdx.x; i < T; i += 256) s += (double)p[i];
-  __shared__ double red[4];
-  s = wave_sum_d(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  const float mean = (float)(((red[0] + red[1]) + (red[2] + red[3])) / (double)T);
+  double s[1] = {0.0};
+  for (int i = threadIdx.x; i < T; i += 256) s[0] += (double)p[i];
+  __shared__ double red[1][4];
+  pair_block_sums(s, red);
+  const float mean = (float)(s[0] / (double)T);
   float* o = dest + (long long)sb * T;
   for (int i = threadIdx.x; i < T; i += 256) o[i] = p[i] - mean;
 }
@@ -869,78 +825,30 @@ int mag_bwd(const float* est, const float* tgt, const int* perm, const float* gl
   if (p.nfr <= 0) return SEPR_EINVAL;
   if (!ar.ok_need()) return SEPR_EWORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  double *part = p.part, *sums = p.sums, *dLdc = bp.dLdc;
-  float *means = p.means, *scales = p.scales, *xz = p.xz, *C = p.C, *dC = bp.dC, *fr = bp.fr, *da = bp.da;
-  const int nbin = frame_len / 2 + 1;
-  // ---- recompute the forward quantities (moments, scales, zero-mean padded waveforms, STFT of all 2S waveforms, pair sums)
-#define SEPR_MAGB1(SS)                                                                                                              \
-  case SS:                                                                                                                          \
-    hipLaunchKernelGGL((pit_partial_kernel<SS>), dim3(p.nchunk, B), dim3(PIT_TPB), 0, st, est, tgt, (const float*)nullptr, B, T,    \
-                       p.nchunk, part);                                                                                             \
-    hipLaunchKernelGGL((mag_scales_kernel<SS>), dim3(B), dim3(64), 0, st, part, T, p.nchunk, eps, means, scales, B, agg);          \
-    break;
-  switch (S) {
-    SEPR_MAGB1(1)
-    SEPR_MAGB1(2)
-    SEPR_MAGB1(3)
-    default: return SEPR_EINVAL;
-  }
-#undef SEPR_MAGB1
-  {
-    const int gx = (p.Tpad + 255) / 256 < 64 ? (p.Tpad + 255) / 256 : 64;
-    hipLaunchKernelGGL(stft_prep_kernel, dim3(gx, 2 * S * B), dim3(256), 0, st, est, tgt, means, S * B, T, p.Tpad, xz);
-  }
-  SEPR_CHECK_LAUNCH("pit mag bwd: moments / prep");
-  {
-    GemmArgs a = gemm_args_zero();
-    a.M = 2 * S * B * p.nfr; a.N = p.ldc; a.K = frame_len;
-    a.A = xz; a.lda = frame_shift;
-    a.rows_out = p.nfr; a.rows_src = p.NF; a.rows_valid = p.nfr;
-    a.W = dft; a.bias = nullptr; a.Y = C; a.ldc = p.ldc;
-    SEPR_TRY(launch_gemm(PRO_PLAIN, EPI_STORE, a, SEPR_SITE_NONE, st));
-  }
-#define SEPR_MAGB2(SS)                                                                                                              \
-  case SS:                                                                                                                          \
-    hipLaunchKernelGGL((stft_pair_kernel<SS>), dim3(B, SS * SS), dim3(256), 0, st, C, p.ldc, B, p.nfr, nbin, scales, sums);        \
-    if (agg)                                                                                                                        \
-      hipLaunchKernelGGL((stft_pair_bwd_kernel<SS, true>), dim3(B, SS), dim3(256), 0, st, C, p.ldc, B, p.nfr, nbin, scales, sums, perm, \
-                         gl, eps, tau, dC, bp.ldd, dLdc);                                                                           \
-    else                                                                                                                            \
-      hipLaunchKernelGGL((stft_pair_bwd_kernel<SS, false>), dim3(B, SS), dim3(256), 0, st, C, p.ldc, B, p.nfr, nbin, scales, sums, perm, \
-                         gl, eps, tau, dC, bp.ldd, dLdc);                                                                           \
-    break;
-  switch (S) {
-    SEPR_MAGB2(1)
-    SEPR_MAGB2(2)
-    SEPR_MAGB2(3)
-    default: return SEPR_EINVAL;
-  }
-#undef SEPR_MAGB2
-  SEPR_CHECK_LAUNCH("pit mag bwd: pair");
-  {  // adjoint frames: fr[row][n] = sum_c dC[row][c] K[c][n]  ->  projection with the transposed kernel dft_t [frame_len][ldd] (zero padded)
-    GemmArgs a = gemm_args_zero();
-    a.M = S * B * p.nfr; a.N = frame_len; a.K = bp.ldd;
-    a.A = dC; a.lda = bp.ldd; a.W = dft_t; a.bias = nullptr; a.Y = fr; a.ldc = frame_len;
-    SEPR_TRY(launch_gemm(PRO_PLAIN, EPI_STORE, a, SEPR_SITE_NONE, st));
-  }
-  {
-    const int gx = (p.Tpad + 255) / 256 < 64 ? (p.Tpad + 255) / 256 : 64;
-#define SEPR_MAGB3(SS)                                                                                                              \
-  case SS:                                                                                                                          \
-    hipLaunchKernelGGL((stft_ola_kernel<SS>), dim3(gx, SS * B), dim3(256), 0, st, fr, xz, B, p.nfr, frame_len, frame_shift, p.Tpad, \
-                       dLdc, part, p.nchunk, T, perm, eps, da);                                                                     \
-    break;
-    switch (S) {
-      SEPR_MAGB3(1)
-      SEPR_MAGB3(2)
-      SEPR_MAGB3(3)
-      default: return SEPR_EINVAL;
+  return dispatch_S(S, [&](auto ss) {
+    constexpr int SS = decltype(ss)::value;
+    const int nbin = frame_len / 2 + 1;
+    SEPR_TRY(mag_forward_launches<SS>(p, est, tgt, B, T, dft, frame_len, frame_shift, eps, agg, "pit mag bwd: moments / prep", st));
+    if (agg)
+      hipLaunchKernelGGL((stft_pair_bwd_kernel<SS, true>), dim3(B, SS), dim3(256), 0, st, p.C, p.ldc, B, p.nfr, nbin, p.scales, p.sums, perm,
+                         gl, eps, tau, bp.dC, bp.ldd, bp.dLdc);
+    else
+      hipLaunchKernelGGL((stft_pair_bwd_kernel<SS, false>), dim3(B, SS), dim3(256), 0, st, p.C, p.ldc, B, p.nfr, nbin, p.scales, p.sums, perm,
+                         gl, eps, tau, bp.dC, bp.ldd, bp.dLdc);
+    SEPR_CHECK_LAUNCH("pit mag bwd: pair");
+    {  // adjoint frames: fr[row][n] = sum_c dC[row][c] K[c][n]  ->  projection with the transposed kernel dft_t [frame_len][ldd] (zero padded)
+      GemmArgs a = gemm_args_zero();
+      a.M = S * B * p.nfr; a.N = frame_len; a.K = bp.ldd;
+      a.A = bp.dC; a.lda = bp.ldd; a.W = dft_t; a.bias = nullptr; a.Y = bp.fr; a.ldc = frame_len;
+      SEPR_TRY(launch_gemm(PRO_PLAIN, EPI_STORE, a, SEPR_SITE_NONE, st));
     }
-#undef SEPR_MAGB3
-  }
-  hipLaunchKernelGGL(demean_kernel, dim3(S * B), dim3(256), 0, st, da, p.Tpad, T, dest);
-  SEPR_CHECK_LAUNCH("pit mag bwd: adjoint");
-  return SEPR_OK;
+    const int gx = (p.Tpad + 255) / 256 < 64 ? (p.Tpad + 255) / 256 : 64;
+    hipLaunchKernelGGL((stft_ola_kernel<SS>), dim3(gx, SS * B), dim3(256), 0, st, bp.fr, p.xz, B, p.nfr, frame_len, frame_shift, p.Tpad,
+                       bp.dLdc, p.part, p.nchunk, T, perm, eps, bp.da);
+    hipLaunchKernelGGL(demean_kernel, dim3(S * B), dim3(256), 0, st, bp.da, p.Tpad, T, dest);
+    SEPR_CHECK_LAUNCH("pit mag bwd: adjoint");
+    return SEPR_OK;
+  });
 }
 }  // namespace
 }  // namespace sepr

@@ -51,13 +51,6 @@ __device__ __forceinline__ void gp_span(const int* __restrict__ spans, int b, in
   off = e < on ? on : (e > T ? T : e);
 }
 
-__device__ __forceinline__ double gp_block_sum(double v, double* red) {
-  v = wave_sum_d(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
 __global__ __launch_bounds__(GP_TPB) void gp_moment_kernel(GpEst est, GpRows rows, const int* __restrict__ spans, int C, int U, int T,
                                                            double* __restrict__ mom) {
 #pragma clang fp contract(off)
@@ -106,7 +99,7 @@ __global__ __launch_bounds__(GP_TPB) void gp_moment_kernel(GpEst est, GpRows row
   } else {
     for (int i = lo + tid; i < hi; i += GP_TPB) a += (double)x[i];
   }
-  a = gp_block_sum(a, red);
+  a = block_sum_d(a, red);                            // every thread is here: the one return above is workgroup-uniform
   if (tid == 0) *dst = a;
 }
 

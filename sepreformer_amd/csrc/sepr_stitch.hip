@@ -30,14 +30,6 @@ constexpr int STITCH_TPB = 256;
 
 __host__ __device__ constexpr int stitch_ns(int S) { return S * S + 2 * S; }
 
-// pi(i) of permutation p in lexicographic order (S = 2: 01 10; S = 3: 012 021 102 120 201 210)
-template <int S>
-__host__ __device__ constexpr int perm_at(int p, int i) {
-  if (S == 2) return i == 0 ? p : 1 - p;
-  const int first = p >> 1, lo = first == 0 ? 1 : 0, hi = first == 2 ? 1 : 2;
-  return i == 0 ? first : (i == 1 ? ((p & 1) ? hi : lo) : ((p & 1) ? lo : hi));
-}
-
 // largest r in [0, R) with coff[r] <= k (coff non-decreasing, coff[0] = 0 <= k)
 __device__ __forceinline__ int find_rec_chunk(const int* __restrict__ coff, int R, long long k) {
   int lo = 0, hi = R - 1;
@@ -135,7 +127,6 @@ __global__ __launch_bounds__(STITCH_TPB) void stitch_stats_kernel(const float* _
 template <int S>
 __device__ __forceinline__ int stitch_choose(const double* st, int O, int match_gain, double (&ratio)[S]) {
 #pragma clang fp contract(off)
-  constexpr int NP = S == 2 ? 2 : 6;
   double C[S * S], Ea[S], Eb[S];
 #pragma unroll
   for (int v = 0; v < S * S; ++v) C[v] = st[v];
@@ -147,7 +138,7 @@ __device__ __forceinline__ int stitch_choose(const double* st, int O, int match_
   double best = 0.0;
   int bp = 0;
 #pragma unroll
-  for (int p = 0; p < NP; ++p) {
+  for (int p = 0; p < perm_count<S>(); ++p) {
     double score = 0.0, rat[S];
 #pragma unroll
     for (int i = 0; i < S; ++i) {

@@ -31,15 +31,6 @@ __constant__ const int ST_EDGE[ST_BANDS + 1] = {7, 9, 11, 14, 17, 22, 27, 34, 43
 
 __host__ __device__ inline int st_frames(int T) { return T >= ST_FRAME ? (T - ST_FRAME) / ST_HOP + 1 : 0; }
 
-__device__ __forceinline__ double st_block_sum(double v, double* red) {
-  // 256 threads -> one value, fixed order (wave butterfly, then the four wave sums in wave order)
-  v = wave_sum_d(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
 __global__ __launch_bounds__(256) void stoi_mask_kernel(const float* __restrict__ ref, const int* __restrict__ lens, int S, int T, int Fmax,
                                                         const double* __restrict__ win, double* __restrict__ energy, int* __restrict__ idx,
                                                         int* __restrict__ nk, int* __restrict__ kept, int* __restrict__ status) {
@@ -238,8 +229,8 @@ __global__ __launch_bounds__(256) void stoi_seg_kernel(int S, int Fmax, int ntil
     }
     if (m0 + mi < nseg) de += cac / ((sqrt(caa) + ST_EPS) * (sqrt(ccc) + ST_EPS));
   }
-  ds = st_block_sum(ds, red);
-  de = st_block_sum(de, red);
+  ds = block_sum_d(ds, red);
+  de = block_sum_d(de, red);
   if (tid == 0) {
     double* o = part + ((long long)p * ntiles + blockIdx.x) * 2;
     o[0] = ds;

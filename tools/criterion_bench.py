@@ -4,7 +4,8 @@ their SI-SNR siblings ``sepr_pit_sisnr_*``, which share the moment pass and the 
 
 hipEvents around every launch, B = 16 x 32 000 samples, S = 2, the magnitude forms at 512 / 128; after a warm-up the entries run in turn, one
 launch each per round, 100 rounds, so that clock and cache states are shared alike; the median, minimum and maximum of each entry in
-microseconds.  ``--other-lib PATH``: the four SI-SNR entries of a second build of the library (an earlier commit's) in the same rotation.
+microseconds.  ``--other-lib PATH``: all eight entries of a second build of the library (an earlier commit's) in the same rotation, and per entry
+whether this build's median lies within the other build's own min - max band (``within_other_band``).
 
     python tools/criterion_bench.py [--other-lib sepreformer_amd/_native/libsepr_hip_<tag>.so] [--out profiles/sasdr.json]
 """
@@ -20,6 +21,7 @@ sys.path.insert(0, ROOT)
 
 S, B, T, N, HOP = 2, 16, 32000, 512, 128
 SIBLINGS = ("sepr_pit_sisnr_fwd", "sepr_pit_sisnr_bwd", "sepr_pit_sisnr_mag_fwd", "sepr_pit_sisnr_mag_bwd")
+ENTRIES = SIBLINGS + tuple(n.replace("sisnr", "sasdr") for n in SIBLINGS)
 
 
 def main():
@@ -32,7 +34,7 @@ def main():
 
     import torch
     from sepreformer_amd import lib as L
-    from sepreformer_amd.criterion import PIT_SISNR_mag
+    from sepreformer_amd.criterion import PIT_SISNR_mag, _pit_time_bwd_bytes
     dev = torch.device("cuda:0")
     lib = L.load()
     g = torch.Generator().manual_seed(0)
@@ -44,34 +46,31 @@ def main():
     dft, dft_t = crit._dft, crit._dft_t
     loss, perm = torch.empty(B, device=dev), torch.empty(B, S, dtype=torch.int32, device=dev)
     dest = torch.empty_like(est)
-    ws = torch.empty(max(lib.sepr_workspace_bytes(L.OP_PIT, B, T, 0, 0, 0, S) + 16 * B * S + 512, lib.sepr_pit_sisnr_mag_bwd_workspace(S, B, T, N, HOP)),
-                     dtype=torch.uint8, device=dev)
+    ws = torch.empty(max(_pit_time_bwd_bytes(lib, S, B, T), lib.sepr_pit_sisnr_mag_bwd_workspace(S, B, T, N, HOP)), dtype=torch.uint8, device=dev)
     st = torch.cuda.current_stream(dev).cuda_stream
     e, t, p, w, n = est.data_ptr(), tgt.data_ptr(), perm.data_ptr(), ws.data_ptr(), ws.numel()
 
-    def entries(h, names):
-        out = {}
-        if "sepr_pit_sisnr_fwd" in names:
-            out["sepr_pit_sisnr_fwd"] = lambda: h.sepr_pit_sisnr_fwd(e, t, None, S, B, T, 1e-8, 1e-15, -30.0, loss.data_ptr(), p, None, None, w, n, st)
-            out["sepr_pit_sisnr_bwd"] = lambda: h.sepr_pit_sisnr_bwd(e, t, p, gl.data_ptr(), S, B, T, 1e-8, -30.0, dest.data_ptr(), w, n, st)
-            out["sepr_pit_sisnr_mag_fwd"] = lambda: h.sepr_pit_sisnr_mag_fwd(e, t, S, B, T, dft.data_ptr(), N, HOP, 1e-12, loss.data_ptr(), p, w, n, st)
-            out["sepr_pit_sisnr_mag_bwd"] = lambda: h.sepr_pit_sisnr_mag_bwd(e, t, p, gl.data_ptr(), S, B, T, dft.data_ptr(), dft_t.data_ptr(), N, HOP,
-                                                                             1e-12, dest.data_ptr(), w, n, st)
-        if "sepr_pit_sasdr_fwd" in names:
-            out["sepr_pit_sasdr_fwd"] = lambda: h.sepr_pit_sasdr_fwd(e, t, S, B, T, 1e-8, 30.0, loss.data_ptr(), p, w, n, st)
-            out["sepr_pit_sasdr_bwd"] = lambda: h.sepr_pit_sasdr_bwd(e, t, p, gl.data_ptr(), S, B, T, 1e-8, 30.0, dest.data_ptr(), w, n, st)
-            out["sepr_pit_sasdr_mag_fwd"] = lambda: h.sepr_pit_sasdr_mag_fwd(e, t, S, B, T, dft.data_ptr(), N, HOP, 1e-12, 30.0, loss.data_ptr(), p, w, n, st)
-            out["sepr_pit_sasdr_mag_bwd"] = lambda: h.sepr_pit_sasdr_mag_bwd(e, t, p, gl.data_ptr(), S, B, T, dft.data_ptr(), dft_t.data_ptr(), N, HOP,
-                                                                             1e-12, 30.0, dest.data_ptr(), w, n, st)
-        return out
+    def entries(h):
+        return {
+            "sepr_pit_sisnr_fwd": lambda: h.sepr_pit_sisnr_fwd(e, t, None, S, B, T, 1e-8, 1e-15, -30.0, loss.data_ptr(), p, None, None, w, n, st),
+            "sepr_pit_sisnr_bwd": lambda: h.sepr_pit_sisnr_bwd(e, t, p, gl.data_ptr(), S, B, T, 1e-8, -30.0, dest.data_ptr(), w, n, st),
+            "sepr_pit_sisnr_mag_fwd": lambda: h.sepr_pit_sisnr_mag_fwd(e, t, S, B, T, dft.data_ptr(), N, HOP, 1e-12, loss.data_ptr(), p, w, n, st),
+            "sepr_pit_sisnr_mag_bwd": lambda: h.sepr_pit_sisnr_mag_bwd(e, t, p, gl.data_ptr(), S, B, T, dft.data_ptr(), dft_t.data_ptr(), N, HOP,
+                                                                                    1e-12, dest.data_ptr(), w, n, st),
+            "sepr_pit_sasdr_fwd": lambda: h.sepr_pit_sasdr_fwd(e, t, S, B, T, 1e-8, 30.0, loss.data_ptr(), p, w, n, st),
+            "sepr_pit_sasdr_bwd": lambda: h.sepr_pit_sasdr_bwd(e, t, p, gl.data_ptr(), S, B, T, 1e-8, 30.0, dest.data_ptr(), w, n, st),
+            "sepr_pit_sasdr_mag_fwd": lambda: h.sepr_pit_sasdr_mag_fwd(e, t, S, B, T, dft.data_ptr(), N, HOP, 1e-12, 30.0, loss.data_ptr(), p, w, n, st),
+            "sepr_pit_sasdr_mag_bwd": lambda: h.sepr_pit_sasdr_mag_bwd(e, t, p, gl.data_ptr(), S, B, T, dft.data_ptr(), dft_t.data_ptr(), N, HOP,
+                                                                                    1e-12, 30.0, dest.data_ptr(), w, n, st),
+        }
 
-    runs = {("this", k): f for k, f in entries(lib, SIBLINGS + ("sepr_pit_sasdr_fwd",)).items()}
+    runs = {("this", k): f for k, f in entries(lib).items()}
     if args.other_lib:
         other = C.CDLL(os.path.abspath(args.other_lib))
-        for name in SIBLINGS:
+        for name in ENTRIES:
             fn = getattr(other, name)
             fn.restype, fn.argtypes = L.SIGNATURES[name]
-        runs.update({("other", k): f for k, f in entries(other, SIBLINGS).items()})
+        runs.update({("other", k): f for k, f in entries(other).items()})
     with torch.cuda.device(dev):
         for f in runs.values():                                              # every forward before its backward: perm is valid
             for _ in range(args.warmup):
@@ -96,6 +95,9 @@ def main():
     res["difference_us"] = {n.replace("sisnr", "sasdr"): round(res["entries"][n.replace("sisnr", "sasdr") + "@this"]["median"] - res["entries"][f"{n}@{base}"]["median"], 2)
                             for n in SIBLINGS}
     res["difference_against"] = f"the SI-SNR entries of the {'other' if args.other_lib else 'same'} library"
+    if args.other_lib:
+        res["within_other_band"] = {n: res["entries"][f"{n}@other"]["min"] <= res["entries"][f"{n}@this"]["median"] <= res["entries"][f"{n}@other"]["max"]
+                                    for n in ENTRIES}
     text = json.dumps(res, indent=1)
     print(text)
     if args.out:
