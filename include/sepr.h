@@ -19,6 +19,11 @@
  *     [b, T, C] here (row = one frame); "rows" of a batch are (b, t) flattened;
  *   - weights are fp32 in the layouts noted per struct ("packed" = re-laid-out once on the host by
  *     sepreformer_amd/pack.py from the reference's state_dict tensors).
+ *
+ * This header is also READ AS TEXT: sepreformer_amd/lib.py derives its whole ctypes binding from it (sepreformer_amd/abi.py).  Inside the
+ * extern "C" block keep to: #define NAME integer; typedef struct { members } name; typedef type name; enum { A = n, B, ... }; prototypes
+ * with every parameter NAMED; base types void, char, short, int, unsigned, unsigned char, long long, unsigned long long, size_t, float,
+ * double and the typedefs and structs declared above the use; comments anywhere.  The reader raises, with the line, on anything else.
  */
 #ifndef SEPR_H_
 #define SEPR_H_
